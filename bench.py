@@ -8,13 +8,19 @@ measurement stream and the index list already resident in HBM.  Workload at N=1 
 BASELINE.json configs[2] (N = 1000 inverse-depth features, n = 6014, fp32), the configuration
 the north-star target is quoted on; `--features 200` runs configs[1].
 
-Extra objects on the same line:
-  roofline      dominant kernel (the symmetric downdate Sigma -= V V^T on f32 MFMA), algorithmic
-                flop / HIP-event duration measured over the timed steps.
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the workload and the library that ran).
+`--dump-outputs DIR` also writes what the last timed step left for a caller to read back
+(see dump_outputs()).  Everything else is measured only with `--full` (one GPU), on the same line:
+  roofline      dominant kernel (the symmetric downdate Sigma -= V V^T), algorithmic flop /
+                HIP-event duration sampled over the timed steps; HBM traffic from two
+                rocprofv3 --pmc child passes.
   p_propagate   HBM GB/s of the streaming P <- F P F^T + Q kernel (2 n^2 s bytes), measured in a
                 second pass of the same steps with EKF_OPT_PROPAGATE_STREAMING.
+  secondary_*   the drop-in step, M = 32, the exact-fp32 arithmetic, a 32-feature map.
   cpu_baseline  the reference's dense formulation restated in numpy/OpenBLAS (oracle, "port"),
                 one frame of the same workload on the host cores (rank 0, N=1 only).
+The --no-* options below switch parts of `--full` off.
 """
 import argparse
 import json
@@ -82,6 +88,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--features", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline and per-kernel figures, live PMC traffic, the "
+                         "secondary passes, the CPU baseline, --resize-every) and the end-of-run sanity check; one GPU only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left (mu, the diagonal of Sigma and a "
+                         "fixed sample of its rows) as DIR/<name>.npy; one GPU only")
     ap.add_argument("--device-warmup-ms", type=float, default=80.0,
                     help="before the W warm-up steps: this many ms of the same step on a SCRATCH map (never the measured one), so that the "
                          "clocks the device holds under this load are reached before the timed region, not inside it (a 20-step window "
@@ -102,7 +114,7 @@ def parse():
                     help="skip the short secondary pass that times the same steps with EKF_OPT_SPLIT_BF16 = 0")
     ap.add_argument("--resize-every", type=int, default=0,
                     help="configs[4] cadence: every K frames remove 1 %% of the features and add as many (SURVEY 8d); adds a "
-                         "`resize` object (ms per event, compaction GB/s, add cost per feature) from a separate pass")
+                         "`resize` object (ms per event, compaction GB/s, add cost per feature) from a separate pass; needs --full")
     return ap.parse_args()
 
 
@@ -180,6 +192,37 @@ def run_steps(ring, d_z, d_idx, n_feat, first, count, bytes_per_frame):
         flt = ring.at(f) if isinstance(ring, FilterRing) else ring
         flt.predict()
         flt.update_device(d_z.data_ptr() + f * bytes_per_frame, d_idx.data_ptr(), n_feat, False)
+
+
+DUMP_SIGMA_ROWS = 512                # rows of Sigma written by --dump-outputs (all of them for n <= 512)
+DUMP_SIGMA_ROWS_BYTES = 48 << 20     # ... and never more bytes than this (the dump stays under 64 MB)
+DUMP_SEED = 1237
+
+
+def dump_outputs(flt, out_dir):
+    """--dump-outputs DIR: what a caller reads back from the map the last timed step ran on, as computed (fp32):
+      mu.npy          the state, n
+      sigma_diag.npy  the diagonal of Sigma, n
+      sigma_rows.npy  whole rows of Sigma, (k, n): the camera rows and rows drawn with DUMP_SEED, in ascending order;
+                      the choice depends on n alone, so two runs with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = flt.stateDim()
+    cam = flt.camera_dim
+    k = max(cam, min(n, DUMP_SIGMA_ROWS, DUMP_SIGMA_ROWS_BYTES // (4 * n)))
+    drawn = np.random.default_rng(DUMP_SEED).choice(np.arange(cam, n), size=k - cam, replace=False)
+    rows = np.sort(np.concatenate([np.arange(cam), drawn]))
+    diag = np.empty(n, np.float32)
+    picked = np.empty((k, n), np.float32)
+    strip = 256                                              # Sigma read in strips of whole rows, never all at once
+    for r0 in range(0, n, strip):
+        r1 = min(n, r0 + strip)
+        block = flt.getSigmaBlock(r0, 0, r1 - r0, n)
+        diag[r0:r1] = block[np.arange(r1 - r0), np.arange(r0, r1)]
+        sel = (rows >= r0) & (rows < r1)
+        picked[sel] = block[rows[sel] - r0]
+    np.save(os.path.join(out_dir, "mu.npy"), flt.getFullState().astype(np.float32))
+    np.save(os.path.join(out_dir, "sigma_diag.npy"), diag)
+    np.save(os.path.join(out_dir, "sigma_rows.npy"), picked)
 
 
 def _oracle_pair(o, ocfg, n_feat, px0):
@@ -375,7 +418,7 @@ def live_pmc_traffic(args):
             d = os.path.join(work, counter)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--",
                    sys.executable, os.path.abspath(__file__), "--features", str(args.features), "--steps", "5", "--warmup", "2",
-                   "--no-cpu-baseline", "--no-live-traffic", "--pipeline", str(args.pipeline)]
+                   "--full", "--no-cpu-baseline", "--no-live-traffic", "--pipeline", str(args.pipeline)]
             proc = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                                     start_new_session=True)
             try:
@@ -412,6 +455,10 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.resize_every > 0 and not args.full:
+        raise SystemExit("--resize-every is a measurement of --full: add --full")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs: one GPU only")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -419,7 +466,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} does not match WORLD_SIZE={env_world} of the launcher")
     # (sizes above the headline workload are left to the committed passes: the profiler's counter pass itself crashed
     # on the N = 4000 run, rc -11, and nothing here should depend on it)
-    if (env_world is None and args.gpus == 1 and not args.no_live_traffic and not os.environ.get("EKF_BENCH_CHILD")
+    if (args.full and env_world is None and args.gpus == 1 and not args.no_live_traffic and not os.environ.get("EKF_BENCH_CHILD")
             and args.features <= 1000 and not under_profiler()):
         LIVE_PMC = live_pmc_traffic(args)                # before anything here initialises the GPU
     import torch
@@ -493,33 +540,23 @@ def bench_single(pkg, cfg, n_feat, px0, z, args, dev, torch):
     run_steps(flt, d_z, d_idx, n_feat, 0, args.warmup, bpf)
     flt.synchronize()
     torch.cuda.synchronize()
-    # EKF_OPT_PROFILE: HIP events around the dominant kernel only, and only in every 8th frame of the timed region
-    # (an event pair costs ~6 us of queue time; runs of fewer than 16 steps time every frame)
+    # --full: EKF_OPT_PROFILE, HIP events around the dominant kernel only, and only in every 8th frame of the timed region
+    # (an event pair costs ~6 us of queue time; runs of fewer than 16 steps time every frame).  A plain run records none.
     sample = 8 if args.steps >= 16 else 1
-    flt.set_option(2, 3 if sample == 8 else 1)
-    flt.profile_reset()
+    if args.full:
+        flt.set_option(2, 3 if sample == 8 else 1)
+        flt.profile_reset()
     t0 = time.perf_counter()
     run_steps(flt, d_z, d_idx, n_feat, args.warmup, args.steps, bpf)
     flt.synchronize()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    prof = flt.profile()
-    work = flt.profile_work()
-    flt.set_option(2, 0)
     elapsed = t1 - t0
     ms_per_step = 1e3 * elapsed / args.steps
-
-    # sanity of the run: finite state, unit quaternion, every feature still in view
     last = flt.at(frames - 1)
-    mu = last.getFullState()
-    last.predict()
-    h, vis, rem, S2 = last.predictions()
-    sane = bool(np.all(np.isfinite(mu)) and abs(np.linalg.norm(mu[3:7]) - 1) < 1e-4 and int(vis.sum()) >= int(0.98 * n_feat))
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs)
 
-    m = 2 * n_feat
-    syrk_ms, syrk_cnt = prof.get("downdate_syrk", (0.0, 0))
-    roofline = None
-    pieces = 1
     # which arithmetic the downdate ran in: the library switches to the bf16x6 kernel for maps of >= 23 tile rows
     # (round 6: read from the library's launch counters -- ekf_launch_count -- instead of re-deriving its selection rule)
     launches = {}
@@ -529,6 +566,43 @@ def bench_single(pkg, cfg, n_feat, px0, z, args, dev, torch):
     split_used = launches.get("downdate_bf16x6", 0) > 0
     if split_used and (launches.get("downdate_f32", 0) + launches.get("downdate_f32_fused_wu", 0) + launches.get("downdate_f32_half_tail", 0)) > 0:
         raise SystemExit("bench: the downdate ran on both arithmetics in one run (a per-chunk fall-back): the line would misreport dtype / roofline")
+    result = {
+        "metric": "EKF updates/sec at N features (state dim 14+6N)",
+        "value": round(args.steps / elapsed, 2), "unit": "updates/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32" if not split_used else
+                 "f32 (state, covariance, every accumulation and every other contraction in fp32; the products of the covariance "
+                 "downdate as 3 x bf16 splits of the fp32 operands, six bf16 products per fp32 product: the dropped terms are "
+                 "<= 2^-24 |a||b| in the worst case (2^-28 on average) -- the size of the fp32 product's own rounding; EKF_OPT_SPLIT_BF16 = 0 / --exact-fp32 runs v_mfma_f32_32x32x2_f32)",
+        "data": "synthetic",
+        "config": {"workload": f"N={n_feat} inverse-depth features, n={n}, M=N measured per frame, "
+                               f"fp32, 1xMI355X ({ {200: 'BASELINE configs[1]', 1000: 'BASELINE configs[2]', 4000: 'BASELINE configs[4] size on one GPU'}.get(n_feat, 'custom size') })",
+                   "features": n_feat, "state_dim": n, "measured_per_frame": n_feat,
+                   "camera": "conf_kinect.cfg/scale2", "dT": 1.0 / 30.0,
+                   "frames_per_map": flt.seg, "maps": len(flt.filters)},
+        "device_warmup": device_warmup,
+        "library": library_identity(pkg),
+    }
+    if not args.full:
+        flt.close()
+        return result
+
+    prof = flt.profile()
+    work = flt.profile_work()
+    flt.set_option(2, 0)
+
+    # sanity of the run: finite state, unit quaternion, every feature still in view
+    mu = last.getFullState()
+    last.predict()
+    h, vis, rem, S2 = last.predictions()
+    sane = bool(np.all(np.isfinite(mu)) and abs(np.linalg.norm(mu[3:7]) - 1) < 1e-4 and int(vis.sum()) >= int(0.98 * n_feat))
+
+    m = 2 * n_feat
+    syrk_ms, syrk_cnt = prof.get("downdate_syrk", (0.0, 0))
+    roofline = None
+    pieces = 1
     if syrk_cnt:
         # the timed launches and their algorithmic flop come from the library (ekf_profile_read / ekf_profile_work):
         # n^2 x the real columns of every downdate launch (symmetric half).  Exact-fp32 path with the default
@@ -625,30 +699,13 @@ def bench_single(pkg, cfg, n_feat, px0, z, args, dev, torch):
         roofline["traffic"] = pmc[dd_key]["hbm_bytes_per_launch"] if dd_key else None
         roofline["traffic_source"] = pmc_note
         roofline["mfma_busy"], roofline["mfma_busy_source"] = committed_mfma_busy("k_syrk_bf16x6" if split_used else "k_gemm_mfma<2, false")
-    result = {
-        "metric": "EKF updates/sec at N features (state dim 14+6N)",
-        "value": round(args.steps / elapsed, 2), "unit": "updates/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32" if not split_used else
-                 "f32 (state, covariance, every accumulation and every other contraction in fp32; the products of the covariance "
-                 "downdate as 3 x bf16 splits of the fp32 operands, six bf16 products per fp32 product: the dropped terms are "
-                 "<= 2^-24 |a||b| in the worst case (2^-28 on average) -- the size of the fp32 product's own rounding; EKF_OPT_SPLIT_BF16 = 0 / --exact-fp32 runs v_mfma_f32_32x32x2_f32)",
-        "data": "synthetic",
-        "config": {"workload": f"N={n_feat} inverse-depth features, n={n}, M=N measured per frame, "
-                               f"fp32, 1xMI355X ({ {200: 'BASELINE configs[1]', 1000: 'BASELINE configs[2]', 4000: 'BASELINE configs[4] size on one GPU'}.get(n_feat, 'custom size') })",
-                   "features": n_feat, "state_dim": n, "measured_per_frame": n_feat,
-                   "camera": "conf_kinect.cfg/scale2", "dT": 1.0 / 30.0,
-                   "frames_per_map": flt.seg, "maps": len(flt.filters)},
-        "device_warmup": device_warmup,
-        "library": library_identity(pkg),
+    result.update({
         "downdate_launch_kinds": {k_: v_ for k_, v_ in launches.items() if k_.startswith(("downdate", "row_", "chain"))},
         "run_sane": sane, "features_visible_at_end": int(vis.sum()), "features_rho_nonpositive_at_end": int(rem.sum()),
         "roofline": roofline,
         "roofline_step": roofline_step,
         "kernel_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in prof.items()},
-    }
+    })
 
     flt.close()                             # the secondary passes build their own maps
 

@@ -14,42 +14,42 @@ mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 STAGE="${1:-A}"
 if [ "$STAGE" = A ]; then
-echo "bench N=1000"; python3 "$R/bench.py" > "$O/${P}_bench.json" 2> "$O/bench.err"
+echo "bench N=1000"; python3 "$R/bench.py" --full > "$O/${P}_bench.json" 2> "$O/bench.err"
 echo "bench with the driver's arguments"; python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 > "$O/${P}_bench_driver_args.json" 2>> "$O/bench.err"
-echo "bench N=200 x 1000 frames"; python3 "$R/bench.py" --features 200 --steps 1000 --warmup 10 --no-cpu-baseline > "$O/${P}_bench_n200_1000frames.json" 2>> "$O/bench.err"
-echo "bench N=4000"; python3 "$R/bench.py" --features 4000 --steps 20 --warmup 3 --no-cpu-baseline --no-propagate-pass > "$O/${P}_bench_n4000.json" 2>> "$O/bench.err"
+echo "bench N=200 x 1000 frames"; python3 "$R/bench.py" --full --features 200 --steps 1000 --warmup 10 --no-cpu-baseline > "$O/${P}_bench_n200_1000frames.json" 2>> "$O/bench.err"
+echo "bench N=4000"; python3 "$R/bench.py" --full --features 4000 --steps 20 --warmup 3 --no-cpu-baseline --no-propagate-pass > "$O/${P}_bench_n4000.json" 2>> "$O/bench.err"
 echo "rocprofv3 kernel stats (the timed run of the default bench line)"; rm -rf "$O/prof"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --no-cpu-baseline --no-propagate-pass --no-live-traffic > "$O/${P}_bench_under_rocprof.json" 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --full --no-cpu-baseline --no-propagate-pass --no-live-traffic > "$O/${P}_bench_under_rocprof.json" 2>> "$O/bench.err"
 cp "$O"/prof/ks_kernel_stats.csv "$O/${P}_kernel_stats.csv"
 python3 "$R/tools/trace_timeline.py" "$O/prof/ks_kernel_trace.csv" > "$O/${P}_step_timeline.txt"
 echo "rocprofv3 kernel stats WITH the streaming P-propagate pass (k_propagate_streaming row)"; rm -rf "$O/prof"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --steps 40 --warmup 5 --no-cpu-baseline --no-live-traffic > "$O/${P}_bench_under_rocprof_propagate.json" 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --full --steps 40 --warmup 5 --no-cpu-baseline --no-live-traffic > "$O/${P}_bench_under_rocprof_propagate.json" 2>> "$O/bench.err"
 cp "$O"/prof/ks_kernel_stats.csv "$O/${P}_kernel_stats_with_propagate_pass.csv"
 echo "N=200 and N=4000 stats + timelines"; rm -rf "$O/prof"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --features 200 --steps 300 --warmup 10 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --full --features 200 --steps 300 --warmup 10 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
 cp "$O"/prof/ks_kernel_stats.csv "$O/${P}_kernel_stats_n200.csv"
 python3 "$R/tools/trace_timeline.py" "$O/prof/ks_kernel_trace.csv" > "$O/${P}_step_timeline_n200.txt"
 rm -rf "$O/prof"
 echo "N=32 (the reference's operating point) bench line, stats + timeline"
-python3 "$R/bench.py" --features 32 --steps 2000 --warmup 50 --no-cpu-baseline --no-live-traffic > "$O/${P}_bench_n32.json" 2>> "$O/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --features 32 --steps 500 --warmup 20 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
+python3 "$R/bench.py" --full --features 32 --steps 2000 --warmup 50 --no-cpu-baseline --no-live-traffic > "$O/${P}_bench_n32.json" 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --full --features 32 --steps 500 --warmup 20 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
 cp "$O"/prof/ks_kernel_stats.csv "$O/${P}_kernel_stats_n32.csv"
 python3 "$R/tools/trace_timeline.py" "$O/prof/ks_kernel_trace.csv" > "$O/${P}_step_timeline_n32.txt"
 rm -rf "$O/prof"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --features 4000 --steps 10 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o ks -- python3 "$R/bench.py" --full --features 4000 --steps 10 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
 cp "$O"/prof/ks_kernel_stats.csv "$O/${P}_kernel_stats_n4000.csv"
 python3 "$R/tools/trace_timeline.py" "$O/prof/ks_kernel_trace.csv" > "$O/${P}_step_timeline_n4000.txt"
 echo "PMC passes"; rm -rf "$O/pmc"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$O/pmc/pmc_fetch" -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > /dev/null 2>> "$O/bench.err"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$O/pmc/pmc_write" -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > /dev/null 2>> "$O/bench.err"
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$O/pmc/pmc_fetch" -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > /dev/null 2>> "$O/bench.err"
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$O/pmc/pmc_write" -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > /dev/null 2>> "$O/bench.err"
 cd "$R" && python3 tools/pmc_summary.py gpurun_out/$P/pmc gpurun_out/$P/${P}_pmc_traffic.json
 echo "MFMA utilisation passes (SQ / GRBM counters, counters + kernel trace only)"
 cd /tmp
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$O/pmc_mfma" -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
-rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d "$O/pmc_mfma2" -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$O/pmc_mfma" -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
+rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d "$O/pmc_mfma2" -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic > /dev/null 2>> "$O/bench.err"
 cd "$R" && python3 tools/pmc_mfma.py gpurun_out/$P gpurun_out/$P/${P}_pmc_mfma.json > "$O/${P}_pmc_mfma.txt"
 echo "configs[4] resize cadence on one GPU (N = 4000, an event every 10 frames so that a short run holds several)"
-python3 "$R/bench.py" --features 4000 --steps 40 --warmup 3 --no-cpu-baseline --no-propagate-pass --no-live-traffic --resize-every 10 > "$O/${P}_bench_n4000_resize.json" 2>> "$O/bench.err"
+python3 "$R/bench.py" --full --features 4000 --steps 40 --warmup 3 --no-cpu-baseline --no-propagate-pass --no-live-traffic --resize-every 10 > "$O/${P}_bench_n4000_resize.json" 2>> "$O/bench.err"
 rm -rf "$O/prof" "$O/pmc" "$O/pmc_mfma" "$O/pmc_mfma2"
 fi
 if [ "$STAGE" = B ]; then
@@ -87,6 +87,6 @@ for nf in "1000 3000" "2000 2500" "4000 1200"; do set -- $nf; python3 "$R/tools/
 fi
 if [ "$STAGE" = E ]; then
 echo "CPU baseline with the measured single-thread dense frame (--cpu-full)"
-python3 "$R/bench.py" --steps 20 --warmup 5 --no-propagate-pass --no-live-traffic --cpu-full > "$O/${P}_bench_cpu_full.json" 2>> "$O/bench.err"
+python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-propagate-pass --no-live-traffic --cpu-full > "$O/${P}_bench_cpu_full.json" 2>> "$O/bench.err"
 fi
 ls "$O"

@@ -2,10 +2,10 @@
 
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv \
-              -d $R/gpurun_out/r5/pmc_mfma -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic
+              -d $OUT/pmc_mfma -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-propagate-pass --no-live-traffic
     rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \
-              --kernel-trace --output-format csv -d $R/gpurun_out/r5/pmc_mfma2 -- python3 $R/bench.py ... (same)
-    python3 tools/pmc_mfma.py gpurun_out/r5 profiles/r5_pmc_mfma.json
+              --kernel-trace --output-format csv -d $OUT/pmc_mfma2 -- python3 $R/bench.py ... (same)
+    python3 tools/pmc_mfma.py $OUT profiles/r5_pmc_mfma.json
 
 mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x 256 CUs x the kernel's GPU cycles); the kernel's GPU cycles are
 GRBM_GUI_ACTIVE / 8 (rocprofv3 sums the counter over the 8 XCDs; MI355X_MICROARCH.md, DVFS give-back) -- i.e. the share of

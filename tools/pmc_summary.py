@@ -1,8 +1,8 @@
 """Summarise the two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) into profiles/<tag>_pmc_traffic.json.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/<dir>/pmc_fetch -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/<dir>/pmc_write -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline
-    python tools/pmc_summary.py gpurun_out/<dir> profiles/r1_pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <out>/pmc_fetch -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <out>/pmc_write -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
+    python tools/pmc_summary.py <out> profiles/r1_pmc_traffic.json
 
 Counters are KB per dispatch.  On gfx950 FETCH_SIZE reports half of the bytes of wide coalesced reads
 (MI355X_MICROARCH.md, HBM section), so the read side is doubled; WRITE_SIZE is exact."""
@@ -45,7 +45,7 @@ for name, cn in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
             out[k]["dispatches_" + name] = len(v)
 for k, v in out.items():
     v["hbm_bytes_per_launch"] = (2 * v.get("FETCH_SIZE_KB_mean", 0.0) + v.get("WRITE_SIZE_KB_mean", 0.0)) * 1024
-json.dump({"note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 5 --warmup 2 "
+json.dump({"note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 5 --warmup 2 "
                    "--no-cpu-baseline` (N=M=1000, fp32, default options: pipelined solve/downdate pieces); counters are KB per "
                    "dispatch; read side doubled per MI355X_MICROARCH.md (FETCH_SIZE reports 1/2 of wide coalesced reads on gfx950)",
            "csrc_sha16": csrc_sha(), "kernels": out}, open(dst, "w"), indent=1)
