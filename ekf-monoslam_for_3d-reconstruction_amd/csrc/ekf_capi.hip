@@ -16,6 +16,7 @@
 #include "../../include/ekf_monoslam.h"
 #include "ekf_dense.hpp"
 #include "ekf_image.hpp"
+#include "ekf_features.hpp"
 #include "ekf_syrk6.hpp"
 #include "ekf_chain.hpp"
 #include "ekf_small.hpp"
@@ -50,6 +51,10 @@ enum KernelId : int {
   KID_GATHER_S,
   KID_GATHER_V,
   KID_GATHER_SIGMA,
+  KID_SEED_MASK,
+  KID_SEED_RESPONSE,
+  KID_SEED_CANDIDATES,
+  KID_SEED_SELECT,
   KID_COUNT
 };
 
@@ -58,7 +63,8 @@ static const char* kKernelNames[KID_COUNT] = {
     "innovation",      "sigma_ht",         "innovation_cov",      "chol_diag",
     "chol_panel",      "chol_trailing",    "state_update",        "downdate_syrk",
     "solve_trmm",      "normalize_quat",  "add_feature",      "compact_transform",   "misc",
-    "w_update", "allgather_h", "allgather_s", "allgather_v", "allgather_sigma"};
+    "w_update", "allgather_h", "allgather_s", "allgather_v", "allgather_sigma",
+    "seed_mask", "seed_response", "seed_candidates", "seed_select"};
 
 // Which launch structure an update actually took (ekf_launch_count): host-side counters, always on, one increment per
 // launch.  The order is the ABI's `enum ekf_launch_kind`.
@@ -163,6 +169,10 @@ struct FilterBase {
   virtual int get_patch(int, int, unsigned char*) = 0;
   virtual int blur_predictions(void*) = 0;
   virtual int find_matches(double, void*, unsigned char*, float*) = 0;
+  virtual int get_track(int*, unsigned char*, float*, unsigned char*) = 0;
+  virtual int set_track(int, int, int, const float*, int) = 0;
+  virtual int find_new_features(int, double, double, int, float*, int*) = 0;
+  virtual int end_update(float, int, int*, int*, int*, int*) = 0;
   virtual int shard_configure(int, int, ekf_allgather_fn, void*) = 0;
   virtual int shard_info(ekf_shard_info*) = 0;
   virtual int shard_update(const void*, const int*, int, int) = 0;
@@ -203,6 +213,22 @@ struct Filter : FilterBase {
   // the patches archived at removal (vR.cpp:394-404): real_index on the host, XYZ + 3x3 covariance on the device
   std::vector<int> real_index, n_find;
   int patchnumbre = 1;
+  // the rest of a Patch's track state (Patch.cpp:85-93, 115-125, 218, 253, 279-281): n_tot, center, isInInnovation and
+  // the sticky removeFlag.  ekf_predict / ekf_measure fold their visibility / rho <= 0 flags into d_trk on the device
+  // (bit 0: visible at the last one, bit 1: rho <= 0 since the last read-back); pull_track() folds that into the host
+  // vectors before anything reads them or reorders the features (d_trk is all zero whenever trk_dirty is false)
+  std::vector<int> n_tot;
+  std::vector<float> center;                            // u, v per feature
+  std::vector<unsigned char> in_innovation, remove_flag;
+  unsigned char* d_trk = nullptr;
+  bool trk_dirty = false;
+  // corner seeding (ekf_features.hpp): mask, lambda, [max bits | candidate count], candidates, square origins, selection
+  unsigned char* d_seed_mask = nullptr;
+  double* d_seed_lam = nullptr;
+  unsigned long long* d_seed_aux = nullptr;
+  unsigned long long* d_seed_ckey = nullptr;
+  int *d_seed_cidx = nullptr, *d_seed_org = nullptr, *d_seed_out = nullptr;
+  bool have_seed_lam = false;
   std::vector<int> arch_real;
   T* d_archive = nullptr;
   size_t arch_cap = 0;
@@ -364,7 +390,8 @@ struct Filter : FilterBase {
                     d_frame, d_patch[0], d_patch[1], d_mpatch[0], d_mpatch[1], d_hb, d_zm, d_found, d_score, d_keep,
                     d_Vimg, d_stage_send, d_stage_recv, d_archive, d_arch_idx, d_panel_tiles, d_shard_solve, d_shard_syrk,
                     d_chain_tasks, d_chain_flags, d_chain_trace, d_td_blocks, d_small_stamps,
-                    d_dist_lists, d_dist_counters, d_dist_send, d_dist_recv, d_sf_lists};
+                    d_dist_lists, d_dist_counters, d_dist_send, d_dist_recv, d_sf_lists,
+                    d_trk, d_seed_mask, d_seed_lam, d_seed_aux, d_seed_ckey, d_seed_cidx, d_seed_org, d_seed_out};
     for (void* p : ptrs) if (p) hipFree(p);
     mark("host memory");
     for (int s = 0; s < kInSlots; ++s) { if (h_in[s]) hipHostFree(h_in[s]); if (ev_in[s]) hipEventDestroy(ev_in[s]); }
@@ -478,6 +505,8 @@ struct Filter : FilterBase {
     HIPCHK(hipMalloc(&d_Sd, cn * 4 * sizeof(T)));
     HIPCHK(hipMalloc(&d_flags, cn));
     HIPCHK(hipMalloc(&d_cflag, cn));
+    HIPCHK(hipMalloc(&d_trk, cn));
+    HIPCHK(hipMemsetAsync(d_trk, 0, cn, stream));
     HIPCHK(hipMalloc(&d_Jy, cn * 18 * sizeof(T)));
     HIPCHK(hipMalloc(&d_Yxyz, cn * 3 * sizeof(T)));
     HIPCHK(hipMalloc(&d_map_src, (size_t)n_pad * sizeof(int)));
@@ -782,6 +811,7 @@ struct Filter : FilterBase {
     const T hw = T(cam.half_window);
     if (!((uT > hw) && (vT > hw) && (uT < T(cam.width) - hw) && (vT < T(cam.height) - hw))) return 0;
     if (N >= capN) { err = "capacity_features exceeded"; return -EKF_ERR_CAPACITY; }
+    { int rct = pull_track(); if (rct) return -rct; }
     {
       Scope sc(this, KID_ADD_FEATURE);
       k_add_prepare<T><<<1, 64, 0, stream>>>(mu(), S(), ld, n, cam, uT, vT, T(cfg.rho_0), T(sigma_pixel_2),
@@ -800,6 +830,11 @@ struct Filter : FilterBase {
     coding.push_back(0);
     real_index.push_back(patchnumbre++);
     n_find.push_back(1);
+    n_tot.push_back(1);                                   // Patch.cpp:85-93
+    center.push_back(float(u));
+    center.push_back(float(v));
+    in_innovation.push_back(0);
+    remove_flag.push_back(0);
     N += 1;
     n += 6;
     shard_after_add();
@@ -906,11 +941,223 @@ struct Filter : FilterBase {
                                              d_score);
     }
     HIPCHK(hipGetLastError());
-    // the three results through the pinned bounce buffer: one synchronisation
-    if (z) { rc = rb_add(z, d_zm, (size_t)N * 2 * sizeof(T)); if (rc) return rc; }
-    if (found) { rc = rb_add(found, d_found, (size_t)N); if (rc) return rc; }
+    // the results through the pinned bounce buffer, together with the folded flags of the last predict: one
+    // synchronisation (z and found always come back: the track state follows them)
+    std::vector<T> zm((size_t)N * 2);
+    std::vector<unsigned char> fd(N), tb;
+    const bool fold = trk_dirty;
+    if (fold) { tb.resize(N); rc = rb_add(tb.data(), d_trk, (size_t)N); if (rc) return rc; }
+    rc = rb_add(zm.data(), d_zm, (size_t)N * 2 * sizeof(T)); if (rc) return rc;
+    rc = rb_add(fd.data(), d_found, (size_t)N); if (rc) return rc;
     if (score) { rc = rb_add(score, d_score, (size_t)N * sizeof(float)); if (rc) return rc; }
-    return rb_finish(false);
+    rc = rb_finish(false);
+    if (rc) return rc;
+    if (fold) {
+      HIPCHK(hipMemsetAsync(d_trk, 0, (size_t)N, stream));        // (stream-ordered: before the next fold)
+      apply_track(tb);
+    }
+    if (z) memcpy(z, zm.data(), zm.size() * sizeof(T));
+    if (found) memcpy(found, fd.data(), fd.size());
+    // Patch::findMatch of every searched (= visible) feature: n_tot + 1 (Patch.cpp:218), the centre becomes the matched
+    // pixel or (-1, -1) (:253, 279), a failed search clears isInInnovation (:281)
+    for (int i = 0; i < N; ++i) {
+      if (!in_innovation[i]) continue;
+      n_tot[i] += 1;
+      center[2 * i] = fd[i] ? float(zm[2 * i]) : -1.f;
+      center[2 * i + 1] = fd[i] ? float(zm[2 * i + 1]) : -1.f;
+      if (!fd[i]) in_innovation[i] = 0;
+    }
+    return EKF_OK;
+  }
+
+  // ---- track state: n_tot, center, isInInnovation, removeFlag ------------------------------------
+  int launch_track_fold() {
+    if (N > 0) {
+      k_track_fold<<<(N + 255) / 256, 256, 0, stream>>>(d_flags, d_trk, N);
+      HIPCHK(hipGetLastError());
+      trk_dirty = true;
+    }
+    return EKF_OK;
+  }
+  void apply_track(const std::vector<unsigned char>& b) {
+    for (int i = 0; i < N; ++i) {
+      in_innovation[i] = b[i] & 1;
+      remove_flag[i] |= (b[i] >> 1) & 1;
+    }
+    trk_dirty = false;
+  }
+  int pull_track() {
+    if (!trk_dirty) return EKF_OK;
+    std::vector<unsigned char> b(N);
+    if (N > 0) {
+      int rc = rb_add(b.data(), d_trk, (size_t)N);
+      if (rc) return rc;
+      rc = rb_finish(false);
+      if (rc) return rc;
+      HIPCHK(hipMemsetAsync(d_trk, 0, (size_t)N, stream));
+    }
+    apply_track(b);
+    return EKF_OK;
+  }
+  int get_track(int* nt, unsigned char* inn, float* cen, unsigned char* rem) override {
+    HIPCHK(hipSetDevice(device));
+    int rc = pull_track();
+    if (rc) return rc;
+    for (int i = 0; i < N; ++i) {
+      if (nt) nt[i] = n_tot[i];
+      if (inn) inn[i] = in_innovation[i];
+      if (cen) { cen[2 * i] = center[2 * i]; cen[2 * i + 1] = center[2 * i + 1]; }
+      if (rem) rem[i] = remove_flag[i];
+    }
+    return EKF_OK;
+  }
+  int set_track(int index, int nt, int inn, const float* cen, int rem) override {
+    HIPCHK(hipSetDevice(device));
+    if (index < 0 || index >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
+    int rc = pull_track();
+    if (rc) return rc;
+    if (nt >= 0) n_tot[index] = nt;
+    if (inn >= 0) in_innovation[index] = inn ? 1 : 0;
+    if (cen) { center[2 * index] = cen[0]; center[2 * index + 1] = cen[1]; }
+    if (rem >= 0) remove_flag[index] = rem ? 1 : 0;
+    return EKF_OK;
+  }
+
+  // ---- corner seeding: VSlamFilter::findNewFeatures (vR.cpp:783-837), kernels in ekf_features.hpp ---------------
+  // corners -> out (raster indices, acceptance order), *n_out corners
+  int detect_corners(int num, double quality, double min_distance, std::vector<int>& out) {
+    const int W = frame_w, H = frame_h, w = cfg.window_size;
+    const size_t px = (size_t)W * H;
+    if (!d_seed_mask) {
+      HIPCHK(hipMalloc(&d_seed_mask, px));
+      HIPCHK(hipMalloc(&d_seed_lam, px * sizeof(double)));
+      HIPCHK(hipMalloc(&d_seed_aux, 2 * sizeof(unsigned long long)));
+      HIPCHK(hipMalloc(&d_seed_ckey, px * sizeof(unsigned long long)));
+      HIPCHK(hipMalloc(&d_seed_cidx, px * sizeof(int)));
+      HIPCHK(hipMalloc(&d_seed_org, (size_t)std::max(capN, 1) * 2 * sizeof(int)));
+      HIPCHK(hipMalloc(&d_seed_out, (px + 1) * sizeof(int)));          // (more corners than pixels cannot be accepted)
+    }
+    int rc = pull_track();
+    if (rc) return rc;
+    // the squares of the existing patches (vR.cpp:795-817): float compares, (int) truncation of the origin
+    std::vector<int> org;
+    for (int i = 0; i < N; ++i) {
+      const float cx = center[2 * i], cy = center[2 * i + 1];
+      if (cx > (float)w && cy > (float)w && cx < (float)(W - w) && cy < (float)(H - w)) {
+        org.push_back((int)(cx - (float)w));
+        org.push_back((int)(cy - (float)w));
+      }
+    }
+    const int nsq = (int)org.size() / 2;
+    if (nsq) HIPCHK(hipMemcpyAsync(d_seed_org, org.data(), org.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_seed_aux, 0, 2 * sizeof(unsigned long long), stream));
+    // integer d^2 < md^2  <=>  d^2 < ceil(md^2); no two pixels are further apart than W^2 + H^2 (the clamp keeps the
+    // conversion defined for any finite min_distance)
+    const double dmax = (double)W * W + (double)H * H + 1.0;
+    const long long md2i = (long long)std::ceil(std::min(min_distance * min_distance, dmax));
+    const int g = (int)((px + 255) / 256);
+    int* d_cnt = reinterpret_cast<int*>(d_seed_aux + 1);
+    {
+      Scope sc(this, KID_SEED_MASK);
+      k_seed_mask_init<<<g, 256, 0, stream>>>(d_seed_mask, W, H, w);
+      if (nsq) k_seed_mask_paint<<<nsq, 256, 0, stream>>>(d_seed_mask, W, H, w, d_seed_org);
+    }
+    {
+      Scope sc(this, KID_SEED_RESPONSE);
+      k_seed_response<<<dim3((W + kSeedTile - 1) / kSeedTile, (H + kSeedTile - 1) / kSeedTile), 256, 0, stream>>>(
+          d_frame, W, H, d_seed_mask, d_seed_lam, d_seed_aux);
+    }
+    {
+      Scope sc(this, KID_SEED_CANDIDATES);
+      k_seed_candidates<<<g, 256, 0, stream>>>(d_seed_lam, W, H, d_seed_mask, quality, d_seed_aux, d_cnt, d_seed_ckey,
+                                               d_seed_cidx);
+    }
+    {
+      Scope sc(this, KID_SEED_SELECT);
+      k_seed_select<<<1, kSeedSelectThreads, 0, stream>>>(d_cnt, d_seed_ckey, d_seed_cidx, W, num, md2i, d_seed_out);
+    }
+    HIPCHK(hipGetLastError());
+    have_seed_lam = true;
+    out.assign((size_t)num + 1, 0);
+    rc = rb_add(out.data(), d_seed_out, out.size() * sizeof(int));     // (the count and the corners: one copy)
+    if (rc) return rc;
+    rc = rb_finish(false);
+    if (rc) return rc;
+    const int cnt = std::min(std::max(out[0], 0), num);
+    out.erase(out.begin());
+    out.resize(cnt);
+    return EKF_OK;
+  }
+  int find_new_features(int num, double quality, double min_distance, int add, float* out_uv, int* n_out) override {
+    HIPCHK(hipSetDevice(device));
+    if (!(quality >= 0.0) || !(min_distance >= 0.0) || !std::isfinite(quality) || !std::isfinite(min_distance))
+      FAIL(EKF_ERR_ARG, "quality_level and min_distance must be finite and >= 0");
+    if (!have_frame) FAIL(EKF_ERR_STATE, "ekf_find_new_features needs ekf_set_frame");
+    if (num <= 0) num = cfg.nInitFeatures;                            // vR.cpp:785
+    if (n_out) *n_out = 0;
+    if (num <= 0) return EKF_OK;
+    num = (int)std::min<long long>(num, (long long)frame_w * frame_h);   // (no more corners than pixels exist)
+    if (frame_w < 3 || frame_h < 3) FAIL(EKF_ERR_UNSUPPORTED, "frame smaller than 3 x 3");
+    std::vector<int> cs;
+    int rc = detect_corners(num, quality, min_distance, cs);
+    if (rc) return rc;
+    const int cnt = (int)cs.size();
+    if (out_uv)
+      for (int k = 0; k < cnt; ++k) { out_uv[2 * k] = float(cs[k] % frame_w); out_uv[2 * k + 1] = float(cs[k] / frame_w); }
+    if (n_out) *n_out = cnt;
+    if (add)
+      for (int k = 0; k < cnt && N < capN; ++k) {                    // addFeature (vR.cpp:830-833), up to the capacity
+        const int ra = add_feature(double(cs[k] % frame_w), double(cs[k] / frame_w));
+        if (ra < 0) return -ra;
+      }
+    return EKF_OK;
+  }
+
+  // ---- the end of VSlamFilter::update() (vR.cpp:1294-1317) ---------------------------------------------------
+  int end_update(float matching_ratio, int seed, int* removed, int* n_removed, int* n_visible, int* n_seeded) override {
+    HIPCHK(hipSetDevice(device));
+    if (n_removed) *n_removed = 0;
+    if (n_visible) *n_visible = 0;
+    if (n_seeded) *n_seeded = 0;
+    if (N == 0) return EKF_OK;
+    // seeding needs the frame: refused before anything changes, so a failed call leaves the map as it was
+    if (seed && !have_frame) FAIL(EKF_ERR_STATE, "ekf_end_update with seed != 0 needs ekf_set_frame");
+    int rc = pull_track();
+    if (rc) return rc;
+    // update_quality_index (Patch.cpp:143-150; n_find was counted by ekf_update_two_stage) and removal in descending order
+    std::vector<int> rm;
+    for (int i = N - 1; i >= 0; --i) {
+      const float q = (float)(n_tot[i] - n_find[i]) / ((float)n_find[i]);
+      if (q > matching_ratio) remove_flag[i] = 1;
+      if (remove_flag[i]) rm.push_back(i);
+    }
+    if (removed) for (size_t k = 0; k < rm.size(); ++k) removed[k] = rm[k];
+    if (n_removed) *n_removed = (int)rm.size();
+    if (!rm.empty()) {
+      rc = remove_features(rm.data(), (int)rm.size());
+      if (rc) return rc;
+    }
+    int vis = 0;                                                       // :1301-1302
+    for (int i = 0; i < N; ++i) vis += in_innovation[i] ? 1 : 0;
+    if (n_visible) *n_visible = vis;
+    if (vis < cfg.min_features) {                                      // :1311-1315
+      if (N > cfg.max_features) {
+        const int zero = 0;
+        rc = remove_features(&zero, 1);
+        if (rc) return rc;
+      }
+      const int want = cfg.min_features - vis;
+      if (seed) {
+        const int before = N;
+        rc = find_new_features(want, 0.01, 12.0, 1, nullptr, nullptr);
+        if (rc) return rc;
+        if (n_seeded) *n_seeded = N - before;
+      } else if (n_seeded) {
+        *n_seeded = want;
+      }
+    }
+    rc = convert(0, true);                                             // :1317
+    return rc < 0 ? -rc : EKF_OK;
   }
 
   // zero everything of buffer `b` outside the live n x n (up to what was ever written there)
@@ -972,8 +1219,11 @@ struct Filter : FilterBase {
   }
 
   int compact(const std::vector<char>& rm, const std::vector<char>& cv) {
+    { int rct = pull_track(); if (rct) return rct; }
     { int rca = archive_removed(rm); if (rca) return rca; }
-    std::vector<int> msrc, mconv, npos, ncoding, nreal, nfind;
+    std::vector<int> msrc, mconv, npos, ncoding, nreal, nfind, ntot;
+    std::vector<float> ncen;
+    std::vector<unsigned char> ninn, nrem;
     msrc.reserve(n); mconv.reserve(n);
     for (int i = 0; i < camera_dim; ++i) { msrc.push_back(i); mconv.push_back(-1); }
     for (int i = 0; i < N; ++i) {
@@ -982,6 +1232,11 @@ struct Filter : FilterBase {
       npos.push_back((int)msrc.size());
       nreal.push_back(real_index[i]);
       nfind.push_back(n_find[i]);
+      ntot.push_back(n_tot[i]);
+      ncen.push_back(center[2 * i]);
+      ncen.push_back(center[2 * i + 1]);
+      ninn.push_back(in_innovation[i]);
+      nrem.push_back(remove_flag[i]);
       if (cv[i]) {
         for (int e = 0; e < 3; ++e) { msrc.push_back(pos[i]); mconv.push_back(i * 3 + e); }
         ncoding.push_back(1);
@@ -1021,6 +1276,7 @@ struct Filter : FilterBase {
     cur = dst; cur_mu = dmu;
     pos.swap(npos); coding.swap(ncoding);
     real_index.swap(nreal); n_find.swap(nfind);
+    n_tot.swap(ntot); center.swap(ncen); in_innovation.swap(ninn); remove_flag.swap(nrem);
     N = (int)pos.size();
     n = n_new;
     shard_after_compact(rm);
@@ -1071,6 +1327,8 @@ struct Filter : FilterBase {
       k_measure<T><<<(N + 63) / 64, 64, 0, stream>>>(mu(), d_pos, d_coding, 0, N, cam, d_h, d_Hc, d_Hf, d_flags);
     }
     HIPCHK(hipGetLastError());
+    rc = launch_track_fold();
+    if (rc) return rc;
     have_meas = true;
     have_sd = false;
     return EKF_OK;
@@ -1095,6 +1353,8 @@ struct Filter : FilterBase {
       k_predict_fused<T><<<nstrip + (N + 255) / 256, 256, 0, stream>>>(mu(), d_scr, a, S(), ld, n, nstrip, d_pos, d_coding, N,
                                                                       cam, d_h, d_Hc, d_Hf, d_flags, d_status + 8, d_status);
       HIPCHK(hipGetLastError());
+      rc = launch_track_fold();
+      if (rc) return rc;
       have_motion = true;
       have_update = false;
       have_meas = true;
@@ -2211,6 +2471,18 @@ struct Filter : FilterBase {
       if (rows != 16 || cols != 2 || r0 != 0 || c0 != 0) FAIL(EKF_ERR_ARG, "stamp block out of range");
       HIPCHK(hipDeviceSynchronize());
       HIPCHK(hipMemcpy(out, d_small_stamps, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      return EKF_OK;
+    }
+    if (which == 4) {
+      // lambda of the last ekf_find_new_features (ekf_features.hpp): fp64 whatever the filter's dtype, frame rows x columns
+      if (!have_seed_lam) FAIL(EKF_ERR_STATE, "no corner response (call ekf_find_new_features first)");
+      if (r0 < 0 || c0 < 0 || rows < 0 || cols < 0 || r0 + rows > frame_h || c0 + cols > frame_w)
+        FAIL(EKF_ERR_ARG, "response block out of range");
+      if (rows == 0 || cols == 0) return EKF_OK;
+      HIPCHK(hipStreamSynchronize(stream));
+      const double* src = d_seed_lam + (size_t)r0 * frame_w + c0;
+      HIPCHK(hipMemcpy2D(out, (size_t)cols * sizeof(double), src, (size_t)frame_w * sizeof(double), (size_t)cols * sizeof(double),
+                         rows, hipMemcpyDeviceToHost));
       return EKF_OK;
     }
     if (which < 0 || which > 1) FAIL(EKF_ERR_ARG, "workspace id out of range");
@@ -3340,6 +3612,8 @@ struct Filter : FilterBase {
       k_unpack_features<T><<<dim3((mx * kFeatRec + 255) / 256, sh_world), 256, 0, stream>>>(d_stage_recv, slot, d_h, d_Hc, d_Hf, d_flags, tab);
       HIPCHK(hipGetLastError());
     }
+    rc = launch_track_fold();                              // the flags of every feature are on every rank now
+    if (rc) return rc;
     have_update = false;
     have_meas = true;
     have_sd = false;
@@ -3916,6 +4190,26 @@ int ekf_get_blur_predictions(ekf_filter* f, void* hb) { IMPL_OR_ARG(f); return f
 int ekf_find_matches(ekf_filter* f, double threshold, void* z, unsigned char* found, float* score) {
   IMPL_OR_ARG(f);
   return f->impl->find_matches(threshold, z, found, score);
+}
+int ekf_get_feature_track(ekf_filter* f, int* n_tot, unsigned char* in_innovation, float* center, unsigned char* remove_flag) {
+  IMPL_OR_ARG(f);
+  return f->impl->get_track(n_tot, in_innovation, center, remove_flag);
+}
+int ekf_set_feature_track(ekf_filter* f, int index, int n_tot, int in_innovation, const float* center, int remove_flag) {
+  IMPL_OR_ARG(f);
+  return f->impl->set_track(index, n_tot, in_innovation, center, remove_flag);
+}
+int ekf_find_new_features(ekf_filter* f, int num, double quality_level, double min_distance, int add, float* out_uv,
+                          int* n_out) {
+  IMPL_OR_ARG(f);
+  if (add) MUTATES(f);
+  return f->impl->find_new_features(num, quality_level, min_distance, add, out_uv, n_out);
+}
+int ekf_end_update(ekf_filter* f, float matching_ratio, int seed, int* removed, int* n_removed, int* n_visible,
+                   int* n_seeded) {
+  IMPL_OR_ARG(f);
+  MUTATES(f);
+  return f->impl->end_update(matching_ratio, seed, removed, n_removed, n_visible, n_seeded);
 }
 int ekf_export_points(ekf_filter* f, void* out, int conv) { IMPL_OR_ARG(f); if (!out) return EKF_ERR_ARG; return f->impl->export_points(out, conv); }
 int ekf_export_points_table(ekf_filter* f, void* out, int max_rows, int* rows) { IMPL_OR_ARG(f); return f->impl->export_points_table(out, max_rows, rows); }

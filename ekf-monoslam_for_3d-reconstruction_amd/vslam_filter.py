@@ -261,6 +261,44 @@ class VSlamFilter:
     def numArchived(self) -> int:
         return int(self._lib.ekf_num_archived(self._h))
 
+    def featureTrack(self):
+        """(n_tot, in_innovation, center (N,2) float32, remove_flag) per live feature: Patch::n_tot (Patch.cpp:85, 218),
+        Patch::isInInnovation (vR.cpp:520, 532, 561; Patch.cpp:281), Patch::center (Patch.cpp:93, 253, 279) and the
+        sticky Patch::removeFlag (vR.cpp:519, Patch.cpp:149)."""
+        N = self.numOfFeatures()
+        nt, inn = np.zeros(N, np.int32), np.zeros(N, np.uint8)
+        cen, rem = np.zeros((N, 2), np.float32), np.zeros(N, np.uint8)
+        self._check(self._lib.ekf_get_feature_track(self._h, self._ptr(nt), self._ptr(inn), self._ptr(cen), self._ptr(rem)))
+        return nt, inn.astype(bool), cen, rem.astype(bool)
+
+    def setFeatureTrack(self, index: int, n_tot: int = -1, in_innovation: int = -1, center=None, remove_flag: int = -1):
+        """For callers that run their own matcher: a negative value (center None) leaves that field alone."""
+        c = None if center is None else np.ascontiguousarray(center, np.float32).reshape(2)
+        self._check(self._lib.ekf_set_feature_track(self._h, int(index), int(n_tot), int(in_innovation),
+                                                    None if c is None else self._ptr(c), int(remove_flag)))
+
+    def findNewFeatures(self, num: int = -1, quality_level: float = 0.01, min_distance: float = 12.0, add: bool = True):
+        """VSlamFilter::findNewFeatures (vR.cpp:783-837): the mask of the existing patches and goodFeaturesToTrack(frame,
+        features, num, 0.01f, 12, mask) on the device; num <= 0 means nInitFeatures (:785).  Returns the corners (K,2)
+        float32 in order; with add, they are added (up to capacity_features) as vR.cpp:830-833 does."""
+        cap = int(num) if int(num) > 0 else int(self._cfg.nInitFeatures)
+        cap = max(min(cap, int(self._cfg.image_width) * int(self._cfg.image_height)), 1)
+        out = np.zeros((cap, 2), np.float32)
+        n = C.c_int(0)
+        self._check(self._lib.ekf_find_new_features(self._h, int(num), float(quality_level), float(min_distance),
+                                                    int(bool(add)), self._ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def endUpdate(self, matching_ratio: float = 0.2, seed: bool = True):
+        """The end of VSlamFilter::update() (vR.cpp:1294-1317): quality rule + removal, the visible count, eviction of
+        feature 0 and seeding when below min_features, convert2XYZ_ifLinearAll.  Returns a dict: removed (pre-removal
+        indices, descending), n_visible, n_seeded (added with seed, the count to seed without)."""
+        removed = np.zeros(max(self.numOfFeatures(), 1), np.int32)
+        nr, nv, ns = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.ekf_end_update(self._h, float(matching_ratio), int(bool(seed)), self._ptr(removed),
+                                             C.byref(nr), C.byref(nv), C.byref(ns)))
+        return {"removed": removed[:nr.value].copy(), "n_visible": nv.value, "n_seeded": ns.value}
+
     def searchEllipses(self, sigma_size: Optional[int] = None):
         """computeEllipsoidParameters (vR.cpp:1368-1382): (N,3) ints (a, b, theta_deg) per feature."""
         N = self.numOfFeatures()

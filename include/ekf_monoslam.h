@@ -304,7 +304,9 @@ int ekf_set_sigma_block(ekf_filter* f, const void* in, int r0, int c0, int rows,
  * whose word 0 counts the records): type | workgroup << 8 | critical << 24, block step, row block, column block, and the
  * 100 MHz wall clock at draw / dependencies met / computed / published (tools/chain_trace.py).
  * which = 3 (round 6; EKF_SMALL_STAMPS=1): the phase stamps of the one-launch update of a small map (k_update_small_onelaunch):
- * 16 64-bit words of the 100 MHz clock as rows = 16, cols = 2 32-bit halves, r0 = c0 = 0 (tools/small_stamps.py). */
+ * 16 64-bit words of the 100 MHz clock as rows = 16, cols = 2 32-bit halves, r0 = c0 = 0 (tools/small_stamps.py).
+ * which = 4: the corner response lambda of the last ekf_find_new_features (csrc/ekf_features.hpp), a block of the
+ * image_height x image_width frame, row-major, fp64 whatever the filter's dtype (r0 = row, c0 = column). */
 int ekf_peek_workspace(ekf_filter* f, int which, void* out, int r0, int c0, int rows, int cols);
 /* Covariance_Parameter (vR.cpp:841-866): trace of Sigma[0:7,0:7]. */
 int ekf_covariance_parameter(ekf_filter* f, double* out);
@@ -339,6 +341,52 @@ int ekf_get_feature_ids(const ekf_filter* f, int* real_index, int* n_find);
 int ekf_set_feature_meta(ekf_filter* f, int index, int real_index, int n_find);
 /* deleted_patches.size() */
 int ekf_num_archived(const ekf_filter* f);
+
+/* The rest of a Patch's track state per live feature (any pointer may be NULL):
+ *   n_tot: Patch::n_tot -- 1 at creation (Patch.cpp:85), +1 for every feature ekf_find_matches searches, i.e. every
+ *     feature visible at the last ekf_predict / ekf_measure (Patch.cpp:218; vR.cpp:872-873);
+ *   in_innovation: Patch::isInInnovation -- the visibility flag of the last ekf_predict / ekf_measure (vR.cpp:520, 532,
+ *     561), cleared by a failed search (Patch.cpp:281);
+ *   center: Patch::center, 2 floats per feature -- (u, v) at creation (Patch.cpp:93), after each ekf_find_matches the
+ *     matched pixel of a searched feature or (-1, -1) when it was not found (Patch.cpp:253, 279);
+ *   remove_flag: Patch::removeFlag, STICKY -- OR of the rho <= 0 flag of every ekf_predict / ekf_measure (vR.cpp:519)
+ *     and of the quality rule of ekf_end_update; cleared only when the feature goes away.  (The per-call remove flag
+ *     of ekf_get_predictions keeps its own meaning.)
+ * Every reordering of the features (add, removal, conversion, sharded or not) carries the state along.
+ * ekf_set_feature_track is for callers that run their own matcher, as ekf_set_feature_meta: a negative n_tot /
+ * in_innovation / remove_flag leaves that field alone, center == NULL leaves the centre alone. */
+int ekf_get_feature_track(ekf_filter* f, int* n_tot, unsigned char* in_innovation, float* center,
+                          unsigned char* remove_flag);
+int ekf_set_feature_track(ekf_filter* f, int index, int n_tot, int in_innovation, const float* center, int remove_flag);
+/* VSlamFilter::findNewFeatures (vR.cpp:783-837) on the device: the mask of the existing patches (their centres) and
+ * goodFeaturesToTrack(frame, features, num, quality_level, min_distance, mask) with the exact corner response of
+ * csrc/ekf_features.hpp (the arithmetic is pinned there and in DESIGN.md; the reference passes 0.01 and 12).
+ * num <= 0 means nInitFeatures (vR.cpp:785).  out_uv (2 floats per corner, room for num corners; may be NULL)
+ * receives the corners in order, *n_out (may be NULL) their count.  add != 0 adds them in that order through
+ * ekf_add_feature (vR.cpp:830-833; the template is captured from the current frame) until capacity_features is
+ * reached: corners that did not fit are reported, not an error -- the first min(*n_out, capacity - N) were added.
+ * add == 0 only reports.  No frame: EKF_ERR_STATE; quality_level or min_distance negative or not finite: EKF_ERR_ARG.
+ * The detector's launches are timed under the kernel ids "seed_mask", "seed_response", "seed_candidates" and
+ * "seed_select" (EKF_OPT_PROFILE).  The lambda image
+ * of the last call can be read with ekf_peek_workspace(which = 4). */
+int ekf_find_new_features(ekf_filter* f, int num, double quality_level, double min_distance, int add, float* out_uv,
+                          int* n_out);
+/* The end of VSlamFilter::update() (vR.cpp:1294-1317), in the reference's order:
+ *   1. quality = (float)(n_tot - n_find) / (float)n_find per feature, flagged when quality > matching_ratio (host fp32
+ *      as Patch.cpp:147-149; the reference's default is 0.2f).  n_find is NOT incremented here: ekf_update_two_stage
+ *      already counted the inliers (Patch.cpp:145);
+ *   2. every flagged feature (quality or the sticky rho <= 0 flag) is removed in one ekf_remove_features pass;
+ *      removed (room for N ints; may be NULL) receives their pre-removal indices in descending order, *n_removed
+ *      their count;
+ *   3. *n_visible = surviving features with in_innovation;
+ *   4. if n_visible < min_features: feature 0 is removed when N > max_features (:1313), then with seed != 0
+ *      findNewFeatures(min_features - n_visible) with 0.01 / 12 adds corners (*n_seeded = how many were added); with
+ *      seed == 0 *n_seeded is the count the caller should seed and nothing is added;
+ *   5. ekf_convert_xyz_if_linear_all (:1317), after the seeding as in the reference.
+ * An empty map is a no-op that reports 0.  seed != 0 needs a frame: without one the call returns EKF_ERR_STATE
+ * before it changes anything. */
+int ekf_end_update(ekf_filter* f, float matching_ratio, int seed, int* removed, int* n_removed, int* n_visible,
+                   int* n_seeded);
 
 /* Per-kernel HIP-event timing (EKF_OPT_PROFILE).  Kernel ids are dense in
  * [0, ekf_profile_kernels()). */
@@ -460,6 +508,9 @@ typedef struct ekf_shard_info {
  *   ekf_get_predictions WITH s2 and ekf_get_search_ellipses (the 2x2 St blocks; gathered once per predict, so the
  *   first of these calls after a predict is the collective one -- make the same calls on every rank),
  *   ekf_find_matches (the same 2x2 blocks),
+ *   ekf_end_update (its removals and conversion; the seeding runs replicated: every rank holds the same frame and
+ *   centres, so the detector yields the same corners everywhere, and the adds are the ordinary local add),
+ *   ekf_find_new_features (replicated detector, as above; with add, the ordinary add on every rank),
  *   ekf_feature_xyz, ekf_export_points, ekf_export_points_table (round 4: a feature's covariance block is valid on
  *   its owner only; the owners' diagonal blocks are all-gathered first, so every rank returns the same table.  Round 5:
  *   the gathered blocks stay valid until the next call that changes mu, Sigma, the layout or the sharding (predict, the

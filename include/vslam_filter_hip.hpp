@@ -7,6 +7,7 @@
 // that has Eigen can `Eigen::Map<MatrixXf>` the column-major buffers directly.
 // Link: -lekfslam_hip (built by ekf-monoslam_for_3d-reconstruction_amd/csrc/Makefile).
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -127,6 +128,41 @@ class VSlamFilterHip {
     real_index.assign((size_t)numOfFeatures(), 0);
     n_find.assign((size_t)numOfFeatures(), 0);
     check(ekf_get_feature_ids(h_, real_index.data(), n_find.data()));
+  }
+  // Patch::n_tot (Patch.cpp:85, 218), Patch::isInInnovation (vR.cpp:520, 532, 561; Patch.cpp:281), Patch::center
+  // (2 floats per feature; Patch.cpp:93, 253, 279) and the sticky Patch::removeFlag (vR.cpp:519, Patch.cpp:149)
+  void featureTrack(std::vector<int>& n_tot, std::vector<unsigned char>& in_innovation, std::vector<float>& center,
+                    std::vector<unsigned char>& remove_flag) {
+    const size_t N = (size_t)numOfFeatures();
+    n_tot.assign(N, 0); in_innovation.assign(N, 0); center.assign(2 * N, 0.f); remove_flag.assign(N, 0);
+    check(ekf_get_feature_track(h_, n_tot.data(), in_innovation.data(), center.data(), remove_flag.data()));
+  }
+  // for a caller's own matcher: a negative value (center == nullptr) leaves that field alone
+  void setFeatureTrack(int index, int n_tot, int in_innovation, const float* center, int remove_flag) {
+    check(ekf_set_feature_track(h_, index, n_tot, in_innovation, center, remove_flag));
+  }
+  // VSlamFilter::findNewFeatures (vR.cpp:783-837): mask + goodFeaturesToTrack(frame, features, num, 0.01f, 12, mask)
+  // on the device, the corners added in order; returns the corners, 2 floats each (num <= 0: nInitFeatures, and the
+  // corners are added without being returned)
+  std::vector<float> findNewFeatures(int num = -1, double quality_level = 0.01, double min_distance = 12.0,
+                                     bool add = true) {
+    const int cap = std::max(num, 1);
+    std::vector<float> uv(2 * (size_t)cap);
+    int n = 0;
+    check(ekf_find_new_features(h_, num > 0 ? num : -1, quality_level, min_distance, add ? 1 : 0,
+                                num > 0 ? uv.data() : nullptr, &n));
+    uv.resize(num > 0 ? 2 * (size_t)n : 0);
+    return uv;
+  }
+  // the end of VSlamFilter::update() (vR.cpp:1294-1317): quality rule + removal, visible count, eviction and seeding
+  // below min_features, convert2XYZ_ifLinearAll; returns the removed pre-removal indices (descending)
+  std::vector<int> endUpdate(float matching_ratio = 0.2f, bool seed = true, int* n_visible = nullptr,
+                             int* n_seeded = nullptr) {
+    std::vector<int> removed((size_t)std::max(numOfFeatures(), 1));
+    int nr = 0;
+    check(ekf_end_update(h_, matching_ratio, seed ? 1 : 0, removed.data(), &nr, n_visible, n_seeded));
+    removed.resize((size_t)nr);
+    return removed;
   }
 
   std::vector<float> getState() {              // VectorXf(14), vR.cpp:135-140
