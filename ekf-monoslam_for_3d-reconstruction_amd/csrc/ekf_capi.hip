@@ -322,18 +322,6 @@ struct Filter : FilterBase {
   // EKF_SYRK_STAGGER="h,m": de-phasing of the bf16x6 downdate's workgroups (Syrk6Args).  Round 6, N = 1000, knob A/B: every
   // (0, m) with m = 1 .. 6 measures 0.897-0.903 ms per step against 0.917-0.922 without; a late second half (h > 0) gains nothing
   int opt_syrk_stag_half = 0, opt_syrk_stag_mod4 = 2;
-  // EKF_CHAIN_PERSISTENT=1: the chain as one look-ahead launch per column chunk (ekf_chain.hpp).  Bit-identical to the
-  // per-step launches and NOT faster (round 6, measured: profiles/r6_chain_persistent_trace.txt): 45-50 us per block
-  // step against 35-39 -- the critical workgroup moves ~360 KB per step through ONE CU, whose write-through stores run at
-  // 10-50 GB/s.  Off by default.
-  int opt_chain_persistent = 0;
-  ChainPlan chain_plan;
-  ChainTask* d_chain_tasks = nullptr;
-  unsigned* d_chain_flags = nullptr;
-  int chain_flags_cap = 0;
-  unsigned chain_epoch = 0;
-  unsigned* d_chain_trace = nullptr;                    // EKF_CHAIN_TRACE=1 (diagnostics, tools/chain_trace.py): per-task time stamps of the last update
-  static constexpr int kChainTraceCap = 1 << 16;
   int opt_solve_s2 = 1;                                 // EKF_SOLVE_S2: latency-bound solve launches on two wave groups (halves of K)
   bool solve_s2_now = false;
   // A solve launch of under ~one round of tiles is bounded by the K steps of its heaviest tile: two wave groups per
@@ -389,7 +377,7 @@ struct Filter : FilterBase {
                     d_status, d_tmp, d_K, d_tilemap, d_counters, d_ibuf, d_rmask, d_pts, d_tab,
                     d_frame, d_patch[0], d_patch[1], d_mpatch[0], d_mpatch[1], d_hb, d_zm, d_found, d_score, d_keep,
                     d_Vimg, d_stage_send, d_stage_recv, d_archive, d_arch_idx, d_panel_tiles, d_shard_solve, d_shard_syrk,
-                    d_chain_tasks, d_chain_flags, d_chain_trace, d_td_blocks, d_small_stamps,
+                    d_td_blocks, d_small_stamps,
                     d_dist_lists, d_dist_counters, d_dist_send, d_dist_recv, d_sf_lists,
                     d_trk, d_seed_mask, d_seed_lam, d_seed_aux, d_seed_ckey, d_seed_cidx, d_seed_org, d_seed_out};
     for (void* p : ptrs) if (p) hipFree(p);
@@ -564,7 +552,6 @@ struct Filter : FilterBase {
         opt_syrk_stag_half = atoi(e);
         if (const char* c = strchr(e, ',')) opt_syrk_stag_mod4 = atoi(c + 1);
       }
-      if (const char* e = getenv("EKF_CHAIN_PERSISTENT")) opt_chain_persistent = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_CHAIN_FUSED_DIAG")) opt_chain_fused_diag = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_FUSE_SPLIT")) opt_fuse_split = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SU_TAIL")) opt_su_tail = atoi(e) ? 1 : 0;
@@ -578,9 +565,6 @@ struct Filter : FilterBase {
       if (const char* e = getenv("EKF_CHAIN_DEFER")) opt_chain_defer = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_TD_MIN_BLOCKS")) td_min_blocks = std::max(1, atoi(e));
       if (const char* e = getenv("EKF_TD_MAX_BLOCKS")) td_max_blocks = std::max(1, atoi(e));
-      if (const char* e = getenv("EKF_CHAIN_TRACE")) {
-        if (atoi(e)) HIPCHK(hipMalloc(&d_chain_trace, (size_t)(8 + 8 * kChainTraceCap) * sizeof(unsigned)));
-      }
       if (const char* e = getenv("EKF_SPLIT_TAIL")) opt_split_tail = atoi(e);
       if (const char* e = getenv("EKF_SPLIT_BF16")) opt_split_bf16 = atoi(e) ? 1 : 0;   // = EKF_OPT_SPLIT_BF16, for A/B runs
       if (const char* e = getenv("EKF_CHUNKS")) {           // tuning knob: chunk ends in block steps
@@ -612,8 +596,6 @@ struct Filter : FilterBase {
                                hipFuncAttributeMaxDynamicSharedMemorySize, diag_lds(64)));
     // (f32, NB = 128 uses k_chol_diag_packed: 66 KiB of static LDS)
     if constexpr (kIsF32) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chain_persistent),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLds));
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trail_diag),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLds));
     }
@@ -735,7 +717,7 @@ struct Filter : FilterBase {
     return with_status ? eval_status(st) : EKF_OK;
   }
   int eval_status(const int* st) {
-    if (st[0] || st[1] || st[2] || st[3]) {
+    if (st[0] || st[1] || st[3]) {
       HIPCHK(hipMemsetAsync(d_status, 0, 4 * sizeof(int), stream));
       if (st[3]) {
         // the arrival gate of k_predict_fused was left mid-count: every launch that could still add to it has to be
@@ -745,13 +727,6 @@ struct Filter : FilterBase {
         small_gate_total = 0;
         opt_fused = 0;
         FAIL(EKF_ERR_DEVICE, "a bounded device-side wait gave up (fused launch); EKF_OPT_FUSED_LAUNCHES is now off for this filter");
-      }
-      if (st[2]) {
-        // a hand-over of the persistent chain kernel was never published within its bound: the launch gave up (every
-        // workgroup left); the per-step launches take over for this filter
-        opt_chain_persistent = 0;
-        chain_epoch = 0;
-        FAIL(EKF_ERR_DEVICE, "a bounded device-side wait gave up (persistent chain); EKF_CHAIN_PERSISTENT is now off for this filter");
       }
       if (st[1])
         FAIL(EKF_ERR_ARG, "ekf_update_device: a device-resident index is outside [0, N) or the list is not strictly "
@@ -1720,70 +1695,6 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
 
-  // ---- the chain as ONE look-ahead launch per column chunk (ekf_chain.hpp) ------------------------------------------
-  bool chain_persistent_ok() const {
-    return kIsF32 && opt_mfma && opt_chain_persistent && (size_t)2 * ldy * ldy * sizeof(T) < ((size_t)1 << 31);
-  }
-  // Task lists of every launch of the chunk plan (cached until the plan changes), the hand-over words, and this update's epoch.
-  int chain_begin_update(int nblk, int nchunks, const int* cend) {
-    bool same = chain_plan.nblk == nblk && chain_plan.nchunks == nchunks;
-    for (int g = 0; same && g < nchunks; ++g) same = chain_plan.cend[g] == cend[g];
-    if (!same) {
-      build_chain_plan(chain_plan, nblk, nchunks, cend);
-      if (!validate_chain_plan(chain_plan)) {
-        chain_plan.nblk = 0;
-        FAIL(EKF_ERR_DEVICE, "internal: the task lists of the persistent chain do not complete with one worker per list");
-      }
-      HIPCHK(hipStreamSynchronize(stream));
-      if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
-      if (d_chain_tasks) HIPCHK(hipFree(d_chain_tasks));
-      d_chain_tasks = nullptr;
-      HIPCHK(hipMalloc(&d_chain_tasks, chain_plan.tasks.size() * sizeof(ChainTask)));
-      HIPCHK(hipMemcpy(d_chain_tasks, chain_plan.tasks.data(), chain_plan.tasks.size() * sizeof(ChainTask), hipMemcpyHostToDevice));
-      if (chain_plan.nflags > chain_flags_cap) {
-        if (d_chain_flags) HIPCHK(hipFree(d_chain_flags));
-        d_chain_flags = nullptr;
-        chain_flags_cap = chain_plan.nflags + 1024;
-        HIPCHK(hipMalloc(&d_chain_flags, (size_t)chain_flags_cap * sizeof(unsigned)));
-        chain_epoch = 0;
-      }
-    }
-    if (chain_epoch == 0 || chain_epoch >= (1u << (32 - kChainEpochShift)) - 2) {   // fresh words, or the epoch would wrap
-      HIPCHK(hipMemsetAsync(d_chain_flags, 0, (size_t)chain_flags_cap * sizeof(unsigned), stream));
-      chain_epoch = 0;
-    }
-    ++chain_epoch;
-    if (d_chain_trace) HIPCHK(hipMemsetAsync(d_chain_trace, 0, 8 * sizeof(unsigned), stream));
-    return EKF_OK;
-  }
-  // Launch gi of the plan: chunk gi's factor, panels and all but its last trailing update (+ the one chunk gi - 1 left).
-  // `whole_chip`: nothing else is running (chunk 0): one workgroup per CU; else the CUs the second stream leaves alone.
-  int chain_launch(int gi, int m, bool whole_chip, hipStream_t sc_) {
-    if (counter_next + 8 > kQueueCounters) FAIL(EKF_ERR_DEVICE, "internal: out of work-queue counters");
-    const ChainPlan::Launch& L = chain_plan.launch[gi];
-    ChainArgs a{};
-    if constexpr (kIsF32) { a.Y = d_Y; a.Dinv = d_Dinv; }
-    a.ldy = ldy;
-    a.y_bytes = (unsigned)((size_t)2 * ldy * ldy * sizeof(T));
-    a.dinv_bytes = (unsigned)((size_t)(ldy / 64) * 128 * 128 * sizeof(T));
-    a.status = d_status;
-    a.m = m;
-    a.s0 = gi ? chain_plan.cend[gi - 1] : 0; a.s1 = chain_plan.cend[gi]; a.deferred = gi > 0 ? 1 : 0;
-    a.nblk = chain_plan.nblk; a.rb = chain_plan.rb;
-    a.bulk = d_chain_tasks + L.bulk_off; a.nbulk = L.nbulk;
-    a.flags = d_chain_flags; a.abort_word = chain_plan.nflags - 1;
-    a.epoch = chain_epoch << kChainEpochShift;
-    a.counters = d_counters + counter_next;
-    a.trace = d_chain_trace; a.trace_cap = kChainTraceCap;
-    counter_next += 8;
-    const int avail = whole_chip ? num_cus : std::max(2, reserved_cus > 0 ? reserved_cus : 32);
-    const int grid = std::max(2, std::min(avail, 1 + L.nbulk));
-    Scope sc(this, KID_CHOL_DIAG, sc_);
-    ++launch_cnt[EKF_LAUNCH_CHAIN_PERSISTENT];
-    if constexpr (kIsF32) k_chain_persistent<<<grid, 1024, kChainLds, sc_>>>(a);
-    return EKF_OK;
-  }
-
   // ---- trailing update of step j + diagonal factor of step j + 1 as one launch (k_trail_diag) ---------------------------
   bool trail_diag_ok() const {
     return kIsF32 && opt_mfma && opt_chain_fused_diag && (size_t)2 * ldy * ldy * sizeof(T) < ((size_t)1 << 31);
@@ -2074,16 +1985,13 @@ struct Filter : FilterBase {
     const bool recompute = kIsF32 && opt_mfma && opt_wrecompute && nchunks > 1 && tile == 128 && !oneblock;
     int step = 0;
     bool b_inflight = false;
-    // the chain of a chunk as ONE look-ahead launch (ekf_chain.hpp) instead of three launches per block step
-    const bool pchain = chain_persistent_ok() && nb == 128 && !oneblock && nsteps >= 2;
-    if (pchain) { rc = chain_begin_update(nsteps, nchunks, cend); if (rc) return rc; }
     chain_diag_ahead = -1;
     chain_pending.step = -1;
     td_nblk = (td_nblk == nsteps) ? td_nblk : 0;
-    if (!pchain && !oneblock && trail_diag_ok() && nb == 128 && nsteps >= 2) { rc = ensure_trail_diag_lists(nsteps, nchunks, cend); if (rc) return rc; }
+    if (!oneblock && trail_diag_ok() && nb == 128 && nsteps >= 2) { rc = ensure_trail_diag_lists(nsteps, nchunks, cend); if (rc) return rc; }
     sf_now = false;
     if constexpr (kIsF32) {
-      if (opt_step_fused && opt_mfma && opt_fused && nb == 128 && nchunks == 1 && !oneblock && !pchain && !prof_on(KID_CHOL_DIAG) &&
+      if (opt_step_fused && opt_mfma && opt_fused && nb == 128 && nchunks == 1 && !oneblock && !prof_on(KID_CHOL_DIAG) &&
           !prof_on(KID_CHOL_PANEL) && !prof_on(KID_CHOL_TRAILING)) {
         rc = ensure_step_fused_lists(nsteps);
         if (rc) return rc;
@@ -2095,8 +2003,7 @@ struct Filter : FilterBase {
       const int c0 = step * nb, c1 = cend[gi] * nb;
       // chunk 0 has the chip to itself; later chunks run beside the tile GEMMs of stream_b, on the reserved CUs
       hipStream_t sc_ = stream;
-      if (pchain) { rc = chain_launch(gi, m, gi == 0, sc_); if (rc) return rc; }
-      else chain_steps(step, cend[gi], c0, c1, m, m_pad, sc_, oneblock, opt_chain_defer && gi + 1 < nchunks);
+      chain_steps(step, cend[gi], c0, c1, m, m_pad, sc_, oneblock, opt_chain_defer && gi + 1 < nchunks);
       step = cend[gi];
       const int width = c1 - c0;
       vimg_done = false;
@@ -2456,15 +2363,6 @@ struct Filter : FilterBase {
   // which = 0: W (the columns of every chunk as the solve read them), 1: V = W L^-T; row-major rows x cols
   int peek_work(int which, void* out, int r0, int c0, int rows, int cols) override {
     HIPCHK(hipSetDevice(device));
-    if (which == 2) {
-      // the task trace of the persistent chain kernel (EKF_CHAIN_TRACE=1): `rows` records of 8 32-bit words from record
-      // r0 on (cols must be 8; record -1 = the header, word 0 = records written); the words are copied as they are
-      if (!d_chain_trace) FAIL(EKF_ERR_STATE, "no chain trace (create the filter with EKF_CHAIN_TRACE=1)");
-      if (cols != 8 || r0 < -1 || rows < 0 || r0 + rows > kChainTraceCap) FAIL(EKF_ERR_ARG, "trace block out of range");
-      HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemcpy(out, d_chain_trace + 8 * (size_t)(r0 + 1), (size_t)rows * 8 * sizeof(unsigned), hipMemcpyDeviceToHost));
-      return EKF_OK;
-    }
     if (which == 3) {
       // the phase stamps of k_update_small_onelaunch (EKF_SMALL_STAMPS=1): 16 64-bit words (rows = 16, cols = 2 32-bit halves)
       if (!d_small_stamps) FAIL(EKF_ERR_STATE, "no stamps (create the filter with EKF_SMALL_STAMPS=1)");
@@ -3788,18 +3686,15 @@ struct Filter : FilterBase {
     bool side_busy = false;
     sf_now = false;                                        // (the fused block step is the plain path's)
     const bool dchain = dist_chain_ok(nsteps);             // the factorisation distributed over the ranks (see dist_chain_steps)
-    const bool pchain = !dchain && chain_persistent_ok() && nb == 128 && nsteps >= 2;
-    if (pchain) { rc = chain_begin_update(nsteps, nchunks, cend); if (rc) return rc; }
     if (dchain) { rc = ensure_dist_plan(nsteps, nchunks, cend); if (rc) return rc; }
     chain_diag_ahead = -1;
     chain_pending.step = -1;
     td_nblk = (td_nblk == nsteps) ? td_nblk : 0;
-    if (!pchain && !dchain && trail_diag_ok() && nb == 128 && nsteps >= 2) { rc = ensure_trail_diag_lists(nsteps, nchunks, cend); if (rc) return rc; }
+    if (!dchain && trail_diag_ok() && nb == 128 && nsteps >= 2) { rc = ensure_trail_diag_lists(nsteps, nchunks, cend); if (rc) return rc; }
     int pend_c0 = -1, pend_c1 = -1, pend_g = -1;           // overlapped chunk whose downdate is still to be issued
     for (int gi = 0; gi < nchunks; ++gi) {
       const int c0 = step * nb, c1 = cend[gi] * nb, width = c1 - c0;
-      if (pchain) { rc = chain_launch(gi, m, gi == 0, stream); if (rc) return rc; }
-      else if (dchain) { rc = dist_chain_steps(step, cend[gi], m, m_pad, stream); if (rc) return rc; }
+      if (dchain) { rc = dist_chain_steps(step, cend[gi], m, m_pad, stream); if (rc) return rc; }
       else chain_steps(step, cend[gi], c0, c1, m, m_pad, stream, false, opt_chain_defer && gi + 1 < nchunks);
       step = cend[gi];
       const bool overlap = (gi + 1 < nchunks);

@@ -1411,16 +1411,16 @@ __device__ __forceinline__ void diag_factor16(float* a, int LDA, int K0, float* 
   EKF_DIAG_STAMP(3);
 }
 
-// The body is shared by the stand-alone launch (k_chol_diag_packed, plain loads and stores) and by the persistent chain
-// kernel (ekf_chain.hpp: write-through stores, L1-bypassing loads): ldA(i, j0) = A[i][j0 .. j0 + 3], stA(i, j0, v) stores
-// them, stD(i, j, x) stores Linv[i][j].  1024 lanes; the LDS arrays are the caller's.
+// The body is shared by the stand-alone launch (k_chol_diag_packed) and by the kernels that factor a diagonal block inside a
+// larger launch (k_trail_diag, k_chain_step_fused, k_update_small_onelaunch): ldA(i, j0) = A[i][j0 .. j0 + 3], stA(i, j0, v)
+// stores them, stD(i, j, x) stores Linv[i][j].  1024 lanes; the LDS arrays are the caller's.
 struct DiagLds {
   float* a;                                      // [128 * 132]
   float (*x16)[16 * 20];                         // [2]
   float (*rinv)[16];                             // [2]
   float* junk16;                                 // [64 * 16]
 };
-// Three pieces (the persistent chain kernel's critical workgroup keeps the block in LDS between them and skips the load):
+// Three pieces (k_trail_diag and k_update_small_onelaunch build the block in LDS themselves and skip the load):
 //   diag_load_lds    global -> LDS image (lower triangle, zeros above)
 //   diag_factor_lds  the factorisation inside the image: L in the lower triangle, Z = L^-T in the strict upper one
 //   diag_store_lds   L -> global, L^-1 = Z^T -> Dinv

@@ -529,22 +529,6 @@ __global__ void k_measure_sd(const T* __restrict__ S, int ld, const int* __restr
 }
 
 // ---------------------------------------------------------------------------------------
-// a11: quaternion normalisation: mu[3:7] /= |q|, Qn = (|q|^2 I - q q^T)/|q|^3 -> scratch.
-// ---------------------------------------------------------------------------------------
-template <typename T>
-__global__ void k_normalize_quat(T* __restrict__ mu, T* __restrict__ scr) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const T q[4] = {mu[3], mu[4], mu[5], mu[6]};
-  const T nn = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-  const T norma = t_sqrt(nn);
-  const T inv3 = T(1) / (norma * norma * norma);
-  for (int i = 0; i < 4; ++i) mu[3 + i] = q[i] / norma;
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j)
-      scr[SCR_QN + i * 4 + j] = ((i == j ? norma * norma : T(0)) - q[i] * q[j]) * inv3;
-}
-
-// ---------------------------------------------------------------------------------------
 // a12 add feature, step 1 (one lane): new 6-vector into mu[n..n+6), G = d f/d[r,q] (6x7),
 // corner C = G Scc G^T + s_pix2 Jp Jp^T + e6 e6^T sigma_rho_0 (6x6).
 // ---------------------------------------------------------------------------------------
@@ -1044,12 +1028,6 @@ template <typename T>
 __global__ void k_inflate_diagonal(T* __restrict__ S, int ld, int first, int n, T delta) {
   const int i = first + blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) S[(size_t)i * ld + i] += delta;
-}
-
-template <typename T>
-__global__ void k_fill(T* __restrict__ p, size_t count, T v) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
-    p[i] = v;
 }
 
 }  // namespace ekf

@@ -299,10 +299,6 @@ int ekf_set_sigma_block(ekf_filter* f, const void* in, int r0, int c0, int rows,
 /* Diagnostics only (no reference counterpart; tools/determinism_probe_sharded.py): a block of the workspace of the LAST
  * update, row-major rows x cols in the filter's dtype.  which = 0: W = Sigma H^T as the triangular solves read it,
  * 1: V = W L^-T (the factor of the covariance downdate).  Rows: state rows, then the padding; columns: 2 x list slot.
- * which = 2 (round 6; a filter created with EKF_CHAIN_TRACE=1 in the environment): the task trace of the persistent chain
- * kernel of the last update -- `rows` records of 8 32-bit words from record r0 on (cols = 8; r0 = -1 starts at the header,
- * whose word 0 counts the records): type | workgroup << 8 | critical << 24, block step, row block, column block, and the
- * 100 MHz wall clock at draw / dependencies met / computed / published (tools/chain_trace.py).
  * which = 3 (round 6; EKF_SMALL_STAMPS=1): the phase stamps of the one-launch update of a small map (k_update_small_onelaunch):
  * 16 64-bit words of the 100 MHz clock as rows = 16, cols = 2 32-bit halves, r0 = c0 = 0 (tools/small_stamps.py).
  * which = 4: the corner response lambda of the last ekf_find_new_features (csrc/ekf_features.hpp), a block of the
@@ -426,7 +422,7 @@ enum ekf_launch_kind {
   EKF_LAUNCH_W_UPDATE_GEMM,           /* right-looking update of all of W (EKF_OPT_W_RECOMPUTE = 0), stand-alone launch  */
   EKF_LAUNCH_W_RECOMPUTE,             /* W' = Sigma' H^T re-evaluation launches (EKF_OPT_W_RECOMPUTE = 1)                */
   EKF_LAUNCH_CHAIN_STEP,              /* launches of the per-block-step chain (diagonal factor, panel, trailing)          */
-  EKF_LAUNCH_CHAIN_PERSISTENT,        /* one launch per column chunk: the look-ahead chain kernel (round 6)              */
+  EKF_LAUNCH_CHAIN_PERSISTENT,        /* retired (the look-ahead chain kernel of round 6 is removed): always counts 0    */
   EKF_LAUNCH_SOLVE,                   /* triangular-solve launches on one wave group per tile                            */
   EKF_LAUNCH_SOLVE_TWO_GROUPS,        /* ... on two wave groups per tile (EKF_SOLVE_S2)                                  */
   EKF_LAUNCH_UPDATE_ONEBLOCK,         /* k_solve_state_oneblock (2 M + 3 <= 128)                                         */

@@ -70,15 +70,3 @@ def test_syrk6_only_counts_what_it_issues(disassembly):
         waits = [l for l in body if re.search(r"s_waitcnt vmcnt\((63|22|6)\)", l)]
         assert len(waits) >= 3, f"{name}: the counted waits are gone ({len(waits)})"
 
-
-def test_chain_kernel_hand_overs_are_write_through(disassembly):
-    """Every access of Y / Dinv inside the persistent chain kernel is an sc1 buffer access (the hand-over form of
-    MI355X_MICROARCH.md needs EVERY load of handed-over bytes to bypass L1 and every store to be write-through)."""
-    # (chain::trail<0> -- ordinary accesses -- is k_trail_diag's instantiation: its hand-overs are launch boundaries)
-    names = [n for n in disassembly if "chain" in n and ("trailILi16E" in n or "panel" in n or "crit_" in n)]
-    assert names and any("trailILi16E" in n for n in names)
-    for name in names:
-        for l in disassembly[name]:
-            if re.search(r"\bbuffer_(load|store)_dword", l):
-                assert " sc1" in l, f"{name}: {l}"
-            assert not re.search(r"\bflat_load", l), f"{name}: {l}"

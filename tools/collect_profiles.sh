@@ -56,9 +56,8 @@ if [ "$STAGE" = B ]; then
 echo "diagonal factor + column-chain microbenchmarks"
 "$R/tools/diag_bench" > "$O/${P}_diag_bench.txt"
 "$R/tools/chain_latency" > "$O/${P}_chain_latency.txt"
-echo "per-kernel HIP-event times, the persistent chain kernel's task trace, the N = 200 accuracy decomposition"
+echo "per-kernel HIP-event times, the N = 200 accuracy decomposition"
 python3 "$R/tools/kernel_ms.py" 1000 40 2>/dev/null > "$O/${P}_kernel_ms_n1000.txt"
-python3 "$R/tools/chain_trace.py" 1000 2>/dev/null > "$O/${P}_chain_persistent_trace_final.txt"
 python3 "$R/tools/n200_chunk_accuracy.py" 2>/dev/null | grep EKF_OPT > "$O/${P}_n200_chunks.txt"
 python3 "$R/tools/n200_error_source.py" 2>/dev/null | tail -4 > "$O/${P}_n200_error_source.txt"
 echo "sharded step on one rank over RCCL (world 1, forced collectives), plain row panel vs symmetric own block"
@@ -72,7 +71,7 @@ for g in 2 3 4; do python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 
 echo "bench.py --gpus 5 rehearsal over gloo (five ranks on the one GPU: launcher + 5 ranks = the six processes the box allows)"
 EKF_BENCH_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 5 --master-addr 127.0.0.1 --master-port 29561 "$R/bench.py" --gpus 5 --steps 10 --warmup 2 2>/dev/null | grep "^{" > "$O/${P}_bench_gloo_5ranks.json" || true
 echo "knob A/B at N = 1000 (exact fp32 against the default, chunk plans) and accuracy of the same knobs"
-python3 "$R/tools/knob_ab.py" "" "EKF_CHAIN_FUSED_DIAG=0" "EKF_CHAIN_DEFER=0" "EKF_SU_TAIL=0" "EKF_SYRK_STAGGER=0,0" "EKF_FUSE_SPLIT=0" "EKF_CHAIN_FUSED_DIAG=0 EKF_CHAIN_DEFER=0 EKF_SU_TAIL=0 EKF_SYRK_STAGGER=0,0 EKF_FUSE_SPLIT=0" "EKF_CHAIN_PERSISTENT=1" "EKF_SPLIT_BF16=0" "EKF_W_RECOMPUTE=0" "EKF_CHUNKS=3,7,12,16" "EKF_CHUNKS=2,6,11,16" "EKF_RESERVED_CUS=24" "EKF_RESERVED_CUS=48" 2>/dev/null > "$O/${P}_knob_ab_n1000.txt"
+python3 "$R/tools/knob_ab.py" "" "EKF_CHAIN_FUSED_DIAG=0" "EKF_CHAIN_DEFER=0" "EKF_SU_TAIL=0" "EKF_SYRK_STAGGER=0,0" "EKF_FUSE_SPLIT=0" "EKF_CHAIN_FUSED_DIAG=0 EKF_CHAIN_DEFER=0 EKF_SU_TAIL=0 EKF_SYRK_STAGGER=0,0 EKF_FUSE_SPLIT=0" "EKF_SPLIT_BF16=0" "EKF_W_RECOMPUTE=0" "EKF_CHUNKS=3,7,12,16" "EKF_CHUNKS=2,6,11,16" "EKF_RESERVED_CUS=24" "EKF_RESERVED_CUS=48" 2>/dev/null > "$O/${P}_knob_ab_n1000.txt"
 KNOB_N=4000 KNOB_FRAMES=40 python3 "$R/tools/knob_ab.py" "" "EKF_CHAIN_FUSED_DIAG=0" "EKF_CHAIN_FUSED_DIAG=0 EKF_CHAIN_DEFER=0 EKF_SU_TAIL=0 EKF_SYRK_STAGGER=0,0" "EKF_SPLIT_BF16=0" 2>/dev/null > "$O/${P}_knob_ab_n4000.txt"
 KNOB_N=2000 KNOB_FRAMES=80 python3 "$R/tools/knob_ab.py" "" "EKF_CHAIN_FUSED_DIAG=0" "EKF_CHAIN_FUSED_DIAG=0 EKF_CHAIN_DEFER=0 EKF_SU_TAIL=0 EKF_SYRK_STAGGER=0,0" "EKF_SPLIT_BF16=0" 2>/dev/null > "$O/${P}_knob_ab_n2000.txt"
 python3 "$R/tools/acc_knobs.py" "" "EKF_SPLIT_BF16=0" "EKF_W_RECOMPUTE=0" "EKF_SPLIT_BF16=0 EKF_CHUNKS=3,7,16" 2>/dev/null > "$O/${P}_accuracy_knobs_n1000.txt"
