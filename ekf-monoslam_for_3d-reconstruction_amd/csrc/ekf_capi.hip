@@ -311,7 +311,6 @@ struct Filter : FilterBase {
   unsigned small_gate_total = 0;                        // arrivals the gate word (d_status[9]) has seen when every launch so far is over
   int opt_su_tail = 1;                                  // EKF_SU_TAIL=0: k_state_update as its own launch on the second stream beside the last downdate (round 5)
   int opt_fuse_split = 1;                               // EKF_FUSE_SPLIT=0: the plane image of V_g by its own launch behind the solve (rounds 5)
-  bool vimg_done = false;                               // this chunk's solve has written the plane image of V_g
   int opt_chain_defer = 1;                              // EKF_CHAIN_DEFER=0: a chunk's event behind the trailing update of its last step (rounds 1-5)
   int td_min_blocks = 24;                               // EKF_TD_MIN_BLOCKS: steps with fewer blocks in their update keep the three launches
   int td_max_blocks = 1 << 30;                          // EKF_TD_MAX_BLOCKS: ... and so do steps with more (many rounds of blocks: the 64 x 64 tile kernel's occupancy wins)
@@ -1309,15 +1308,48 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
 
-  int predict(const void* tc, const void* rc_, int vcontrol) override {
-    HIPCHK(hipSetDevice(device));
-    if (sh_on) return shard_predict(tc, rc_, vcontrol);
+  MotionArgs motion_args(const void* tc, const void* rc_, int vcontrol) const {
     MotionArgs a;
     a.dT = dT;
     const T* t = static_cast<const T*>(tc);
     const T* r = static_cast<const T*>(rc_);
     for (int i = 0; i < 3; ++i) { a.t_ctl[i] = t ? double(t[i]) : 0.0; a.r_ctl[i] = r ? double(r[i]) : 0.0; }
     for (int i = 0; i < 6; ++i) a.vdiag[i] = vcontrol ? vmax[i] : double(T(vmax[i]) * T(2));   // vR.cpp:202
+    return a;
+  }
+
+  // Camera step, Sigma's camera rows and columns propagated (in place by strips; `streaming`: into the other buffer), then the
+  // feature-noise inflation
+  int propagate(const MotionArgs& a, bool streaming) {
+    {
+      Scope sc(this, KID_PREDICT_CAMERA);
+      k_predict_camera<T><<<1, 64, 0, stream>>>(mu(), d_scr, a);
+    }
+    have_motion = true;
+    if (streaming) {
+      const int dst = 1 - cur;
+      {
+        Scope sc(this, KID_PROPAGATE_STREAMING);
+        k_propagate_streaming<T><<<n, 256, 0, stream>>>(S(), d_S[dst], ld, n, d_scr + SCR_FT, d_scr + SCR_Q);
+      }
+      extent[dst] = std::max(extent[dst], n);
+      int rc = zero_border(dst, n);
+      if (rc) return rc;
+      cur = dst;
+    } else {
+      Scope sc(this, KID_PROPAGATE_STRIPS);
+      k_strip_congruence<T, 13><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 0, d_scr + SCR_FT, d_scr + SCR_Q);
+    }
+    if (opt_feature_noise > 0.0 && n > camera_dim)
+      k_inflate_diagonal<T><<<(n - camera_dim + 255) / 256, 256, 0, stream>>>(S(), ld, camera_dim, n, T(opt_feature_noise));
+    HIPCHK(hipGetLastError());
+    return EKF_OK;
+  }
+
+  int predict(const void* tc, const void* rc_, int vcontrol) override {
+    HIPCHK(hipSetDevice(device));
+    if (sh_on) return shard_predict(tc, rc_, vcontrol);
+    const MotionArgs a = motion_args(tc, rc_, vcontrol);
     if (opt_fused && !opt_streaming && !(opt_feature_noise > 0.0) && N > 0 && !prof_on(KID_PREDICT_CAMERA) &&
         !prof_on(KID_PROPAGATE_STRIPS) && !prof_on(KID_MEASURE)) {
       // camera step, strip congruence and the per-feature h / H as ONE launch (k_predict_fused): same arithmetic,
@@ -1336,28 +1368,8 @@ struct Filter : FilterBase {
       have_sd = false;
       return launch_blur();
     }
-    {
-      Scope sc(this, KID_PREDICT_CAMERA);
-      k_predict_camera<T><<<1, 64, 0, stream>>>(mu(), d_scr, a);
-    }
-    have_motion = true;
-    if (opt_streaming) {
-      const int dst = 1 - cur;
-      {
-        Scope sc(this, KID_PROPAGATE_STREAMING);
-        k_propagate_streaming<T><<<n, 256, 0, stream>>>(S(), d_S[dst], ld, n, d_scr + SCR_FT, d_scr + SCR_Q);
-      }
-      extent[dst] = std::max(extent[dst], n);
-      int rc2 = zero_border(dst, n);
-      if (rc2) return rc2;
-      cur = dst;
-    } else {
-      Scope sc(this, KID_PROPAGATE_STRIPS);
-      k_strip_congruence<T, 13><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 0, d_scr + SCR_FT, d_scr + SCR_Q);
-    }
-    if (opt_feature_noise > 0.0 && n > camera_dim)
-      k_inflate_diagonal<T><<<(n - camera_dim + 255) / 256, 256, 0, stream>>>(S(), ld, camera_dim, n, T(opt_feature_noise));
-    HIPCHK(hipGetLastError());
+    int rcp = propagate(a, opt_streaming);
+    if (rcp) return rcp;
     have_update = false;
     int rcm = launch_measure();
     if (rcm) return rcm;
@@ -1569,14 +1581,23 @@ struct Filter : FilterBase {
 
   // Chunk ends (in block steps) of the factorisation.  One chunk = the plain algorithm (the strip is the
   // whole inverse); several chunks when the chain is long enough to be worth hiding.
-  int plan_chunks(int nsteps, int* cend, bool sharded = false) const {
-    const bool pipe = (opt_pipeline < 0) ? (nsteps >= 8) : (opt_pipeline != 0);
-    if (!pipe || nsteps < 2 || !stream_b) { cend[0] = nsteps; return 1; }
+  int plan_chunks(int nsteps, int* cend) const {
+    const bool sharded = sh_on;
+    const bool pipe = (opt_pipeline < 0) ? (nsteps >= (sharded ? 4 : 8)) : (opt_pipeline != 0);
+    // (the sharded step also needs the gather stream; its split by world size below takes chains of one step)
+    if (!pipe || !stream_b || (sharded ? !stream_g : nsteps < 2)) { cend[0] = nsteps; return 1; }
     if (env_nchunks > 0 && env_chunks[env_nchunks - 1] == nsteps) {
       for (int g = 0; g < env_nchunks; ++g) cend[g] = env_chunks[g];
       return env_nchunks;
     }
-    if (opt_pipeline < 2) {
+    int want;                                                // chunks of equal width
+    if (sharded && (sh_world > 1 || nsteps < 8)) {
+      // chunk count by world size: every chunk costs a pass over the remaining columns of W and re-reads the Sigma
+      // panel, and a rank's share of that work is 1 / world -- two ranks afford 4 chunks, four and more 8
+      // (one rank with >= 8 steps: the plain path's plan, with an earlier first cut)
+      const int cap = sh_world <= 1 ? 3 : (sh_world <= 2 ? 4 : 8);
+      want = std::min(cap, std::max(2, (nsteps + 1) / 2));
+    } else if (opt_pipeline < 2) {
       // default: three chunks ending at 3/16, 7/16 (8/16 through round 3) and 1 of the chain: the first chunk is
       // exposed, so it is short; every further chunk re-reads Sigma once in its downdate, so there are few; the chain and
       // the second stream end together
@@ -1617,8 +1638,9 @@ struct Filter : FilterBase {
         if (e > prev) { cend[k++] = e; prev = e; }
       }
       return k;
+    } else {
+      want = std::min(std::min(opt_pipeline, 8), nsteps);
     }
-    const int want = std::min(std::min(opt_pipeline, 8), nsteps);
     int k = 0, prev = 0;
     for (int g = 0; g < want; ++g) {
       int e = (int)(((long long)nsteps * (g + 1) + want - 1) / want);
@@ -1626,6 +1648,16 @@ struct Filter : FilterBase {
       if (e > prev) { cend[k++] = e; prev = e; }
     }
     return k;
+  }
+  // the chunk ends in rows, and the rows of the widest chunk (those of the identity strip under S)
+  static ChunkTab chunk_table(const int* cend, int nchunks, int nb, int* strip_rows) {
+    ChunkTab tab{nchunks, {}};
+    *strip_rows = 0;
+    for (int g = 0; g < nchunks; ++g) {
+      tab.end[g] = cend[g] * nb;
+      *strip_rows = std::max(*strip_rows, (cend[g] - (g ? cend[g - 1] : 0)) * nb);
+    }
+    return tab;
   }
 
   // W, S (and nu) for a measured set already resident in d_midx / d_z.
@@ -1866,6 +1898,114 @@ struct Filter : FilterBase {
       }
     }
   }
+  // ---- checks and launch steps shared by the plain and the sharded step ------------------
+  // A measured list from the caller: every index in [0, N), and strictly ascending if `ascending`
+  int check_list(const int* idx, int M, bool ascending) {
+    for (int k = 0; k < M; ++k) {
+      if (idx[k] < 0 || idx[k] >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
+      if (ascending && k > 0 && idx[k - 1] >= idx[k]) FAIL(EKF_ERR_ARG, "measured indices must be strictly ascending");
+    }
+    return EKF_OK;
+  }
+
+  // Only the innovation row (row npad_live of [W; nu^T]) updated right-looking for chunk [c0, c1):
+  // nu^T[c1:] -= y_g^T L[c1:, g]^T, by k_innov_row_update (`gemv`) or the 64 x 128 tile GEMM
+  void launch_row_update(int c0, int c1, int m_pad, hipStream_t ss, bool gemv) {
+    const size_t yrow = (size_t)round_up(n, NB()) * ldy;
+    Scope sc(this, KID_WUPDATE, ss);
+    ++launch_cnt[gemv ? EKF_LAUNCH_ROW_GEMV : EKF_LAUNCH_ROW_TILE_GEMM];
+    if constexpr (kIsF32) {
+      if (gemv) {
+        k_innov_row_update<<<(m_pad - c1 + 63) / 64, 64, 0, ss>>>(d_V + yrow + c0, d_Y + (size_t)c1 * ldy + c0, ldy,
+                                                                  d_W + yrow + c1, m_pad - c1, c1 - c0);
+        return;
+      }
+    }
+    gemm<ROLE_WUPDATE, false, 64, 128>(d_V + yrow + c0, ldy, d_Y + (size_t)c1 * ldy + c0, ldy, d_W + yrow + c1, ldy, NB(),
+                                       m_pad - c1, c1 - c0, T(-1), T(1), 0, 0, 0, 0, 0, ss);
+  }
+
+  // EKF_OPT_SPLIT_BF16: Sigma -= V_g V_g^T for chunk [c0, c1) on the bf16 matrix pipe at fp32 accuracy (ekf_syrk6.hpp), over
+  // the `ntiles` canonical tiles of `tiles` (none: the image only).  `split`: V_g is split into the plane image first (three
+  // bf16 per fp32, one 12 KB record per 128 rows x 16 columns; else the solve's tiles have written it).  Rows of Sigma valid
+  // here: [0, cam_rows) and [r0, r1).  `work`: the flop the launch adds to prof_work.  `rider`: the innovation row update of
+  // the chunk in the same launch (launch_row_update's sums); `su_tail`: the state update too (the last downdate of an update).
+  int launch_downdate_bf16x6(int c0, int c1, int m_pad, hipStream_t ss, bool split, const int* tiles, int ntiles, int cam_rows,
+                             int r0, int r1, double work, bool rider, bool su_tail) {
+    if constexpr (kIsF32) {
+      const int npad_live = round_up(n, NB()), width = c1 - c0;
+      if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
+      if (split) {
+        Scope sc(this, KID_MISC, ss);
+        dim3 grid(npad_live / 128, width / 16);
+        k_split_image<<<grid, 256, 0, ss>>>(d_V, ldy, npad_live, c0, width, d_Vimg, ldy / 16);
+      }
+      if (ntiles == 0) return EKF_OK;
+      Scope sc(this, KID_DOWNDATE, ss);
+      if (sc.on) prof_work[KID_DOWNDATE] += work;
+      Syrk6Args a{d_Vimg, ldy / 16, c0 / 16, width / 16, S(), ld, tiles, ntiles, d_counters + counter_next, cam_rows, r0, r1};
+      a.stag_half = opt_syrk_stag_half; a.stag_mod4 = opt_syrk_stag_mod4;
+      if (su_tail) {
+        a.su_mu = mu(); a.su_V = d_V; a.su_ldy = ldy; a.su_n = n; a.su_y = d_V + (size_t)npad_live * ldy; a.su_mpad = m_pad;
+        a.su_qn = d_scr + SCR_QN; a.su_counter = d_counters + counter_next + 1;
+        ++launch_cnt[EKF_LAUNCH_STATE_UPDATE_TAIL];
+      }
+      if (rider) {
+        a.ry = d_V + (size_t)npad_live * ldy + c0; a.rL = d_Y + (size_t)c1 * ldy + c0; a.rldl = ldy;
+        a.rnu = d_W + (size_t)npad_live * ldy + c1; a.rcols = m_pad - c1; a.rK = width; a.nrider = (m_pad - c1 + 255) / 256;
+        ++launch_cnt[EKF_LAUNCH_ROW_RIDER];
+      }
+      counter_next += 8;
+      ++launch_cnt[EKF_LAUNCH_DOWNDATE_BF16X6];
+      const int wgs = 2 * (ss == stream_b ? num_cus - reserved_cus : num_cus);
+      k_syrk_bf16x6<0><<<a.nrider + std::min(ntiles, wgs), 256, 0, ss>>>(a);
+    }
+    return EKF_OK;
+  }
+
+  // EKF_OPT_W_RECOMPUTE: W[rows, c1:c2) = Sigma' H^T, the columns of the next chunk from the downdated Sigma, for rows
+  // [0, rows0) and [row0, row1)
+  void launch_w_recompute(int c1, int c2, int m_pad, const int* list, int M, int plane, hipStream_t ss, int rows0,
+                          int row0 = 0, int row1 = 0) {
+    if constexpr (kIsF32) {
+      Scope sc(this, KID_SIGMA_HT, ss);
+      ++launch_cnt[EKF_LAUNCH_W_RECOMPUTE];
+      const int s0 = c1 / 2, s1 = c2 / 2;
+      const int range[2][2] = {{0, rows0}, {row0, row1}};
+      for (const auto& r : range) {
+        if (r[1] <= r[0]) continue;
+        constexpr int RB = 8;
+        dim3 grid((s1 - s0 + 127) / 128, (r[1] - r[0] + RB - 1) / RB);
+        k_sigma_ht_fast<RB><<<grid, 256, 0, ss>>>(S(), ld, r[1], d_Hc, d_Hf, d_pos, d_coding, list, M, plane, d_W, ldy, m_pad, N,
+                                                   s0, s1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r[0]);
+      }
+    }
+  }
+
+  // End of an update on the main stream: mu += V y with the quaternion normalisation (`state_update`), the normalisation
+  // congruence of Sigma (`normalize`), and the record of what the update did
+  int finish_update(int nchunks, const int* cend, bool recompute, int m, int m_pad, bool state_update, bool normalize) {
+    last_nchunks = nchunks;
+    last_recompute = recompute;
+    for (int g = 0; g < nchunks; ++g) last_cend[g] = cend[g];
+    if (state_update) {
+      Scope sc(this, KID_STATE_UPDATE);
+      k_state_update<T><<<(n + 7) / 8, 512, 0, stream>>>(mu(), d_V, ldy, n, d_V + (size_t)round_up(n, NB()) * ldy, m_pad,
+                                                        d_scr + SCR_QN);
+    }
+    if (normalize) {
+      Scope sc(this, KID_NORMALIZE);
+      k_strip_congruence<T, 4><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 3, d_scr + SCR_QN,
+                                                                       static_cast<const T*>(nullptr));
+    }
+    HIPCHK(hipGetLastError());
+    last_m = m; last_m_pad = m_pad; last_n = n;
+    have_update = true;
+    have_meas = false;                                    // h/H belong to the pre-update state
+    ++frame_seq;
+    return EKF_OK;
+  }
+
   // ---- a8-a11 update ---------------------------------------------------------------------
   int update(const void* z, const int* idx, int M, int plane, bool on_device) override {
     HIPCHK(hipSetDevice(device));
@@ -1887,12 +2027,7 @@ struct Filter : FilterBase {
     if (M == 0 && !plane) return EKF_OK;
     if (!have_meas) FAIL(EKF_ERR_STATE, "ekf_update needs the h/H of ekf_predict or ekf_measure");
     if (M > 0 && (!z || !idx)) FAIL(EKF_ERR_ARG, "z / indices are NULL");
-    if (!on_device) {
-      for (int k = 0; k < M; ++k) {
-        if (idx[k] < 0 || idx[k] >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
-        if (k > 0 && idx[k - 1] >= idx[k]) FAIL(EKF_ERR_ARG, "measured indices must be strictly ascending");
-      }
-    }
+    if (!on_device) { int rcl = check_list(idx, M, true); if (rcl) return rcl; }
     cur_z = nullptr;
     cur_midx = nullptr;
     if (M > 0) {
@@ -1921,12 +2056,8 @@ struct Filter : FilterBase {
     const int nsteps = m_pad / nb;
     int cend[8];
     const int nchunks = plan_chunks(nsteps, cend);
-    ChunkTab tab{nchunks, {}};
     int strip_rows = 0;
-    for (int g = 0; g < nchunks; ++g) {
-      tab.end[g] = cend[g] * nb;
-      strip_rows = std::max(strip_rows, (cend[g] - (g ? cend[g - 1] : 0)) * nb);
-    }
+    const ChunkTab tab = chunk_table(cend, nchunks, nb, &strip_rows);
     // One diagonal block (2 M + 3 <= 128, the reference's operating point): the chunk inverse is the transposed
     // Linv of the diagonal factor, so the panel launch, the solve and the state update are ONE launch
     // (k_solve_state_oneblock; small maps: the downdate and the normalisation too, k_update_oneblock_small): the step is
@@ -2006,7 +2137,7 @@ struct Filter : FilterBase {
       chain_steps(step, cend[gi], c0, c1, m, m_pad, sc_, oneblock, opt_chain_defer && gi + 1 < nchunks);
       step = cend[gi];
       const int width = c1 - c0;
-      vimg_done = false;
+      bool vimg_done = false;                       // this chunk's solve writes the plane image of V_g
       // the last chunk has nothing left to overlap with: it runs on the main stream, on every CU
       const bool overlap = (stream_b != nullptr) && (gi + 1 < nchunks);
       hipStream_t ss = overlap ? stream_b : stream;
@@ -2090,18 +2221,7 @@ struct Filter : FilterBase {
       if (row_rider) {
         // (nothing here: the row goes with the downdate's launch)
       } else if (c1 < m_pad && !fuse && recompute) {
-        // only the innovation row (row npad_live of [W; nu^T]) is updated right-looking: nu^T[c1:] -= y_g^T L[c1:, g]^T
-        Scope sc(this, KID_WUPDATE, ss);
-        ++launch_cnt[(kIsF32 && opt_row_gemv) ? EKF_LAUNCH_ROW_GEMV : EKF_LAUNCH_ROW_TILE_GEMM];
-        if constexpr (kIsF32) {
-          if (opt_row_gemv)
-            k_innov_row_update<<<(m_pad - c1 + 63) / 64, 64, 0, ss>>>(d_V + (size_t)npad_live * ldy + c0, Y + (size_t)c1 * ldy + c0, ldy,
-                                                                      d_W + (size_t)npad_live * ldy + c1, m_pad - c1, width);
-        }
-        if (!kIsF32 || !opt_row_gemv)
-          gemm<ROLE_WUPDATE, false, 64, 128>(d_V + (size_t)npad_live * ldy + c0, ldy, Y + (size_t)c1 * ldy + c0, ldy,
-                                             d_W + (size_t)npad_live * ldy + c1, ldy, nb, m_pad - c1, width, T(-1), T(1), 0, 0, 0,
-                                             0, 0, ss);
+        launch_row_update(c0, c1, m_pad, ss, kIsF32 && opt_row_gemv);
       } else if (c1 < m_pad && !fuse) {
         Scope sc(this, KID_WUPDATE, ss);
         ++launch_cnt[EKF_LAUNCH_W_UPDATE_GEMM];
@@ -2131,41 +2251,13 @@ struct Filter : FilterBase {
         k_state_update<T><<<(n + 7) / 8, 512, 0, stream_b>>>(mu(), d_V, ldy, n, d_V + (size_t)npad_live * ldy, m_pad, d_scr + SCR_QN);   // + quaternion normalisation
         b_inflight = true;
       }
-      bool split_done = false;
-      if constexpr (kIsF32) {
-        if (opt_split_bf16 && opt_mfma && tile == 128 && tri_count >= num_cus && counter_next + 8 <= kQueueCounters) {
-          // EKF_OPT_SPLIT_BF16: the same contraction on the bf16 matrix pipe at fp32 accuracy (ekf_syrk6.hpp): V_g is split
-          // into the plane image (three bf16 per fp32, one 12 KB record per 128 rows x 16 columns), then the lower tiles
-          // of Sigma are downdated from LDS-DMA-fed records
-          if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
-          if (!vimg_done) {                                 // (the solve's tiles have written the image already)
-            Scope sc(this, KID_MISC, ss);
-            ++launch_cnt[EKF_LAUNCH_SPLIT_IMAGE];
-            dim3 grid(npad_live / 128, width / 16);
-            k_split_image<<<grid, 256, 0, ss>>>(d_V, ldy, npad_live, c0, width, d_Vimg, ldy / 16);
-          }
-          vimg_done = false;
-          Scope sc(this, KID_DOWNDATE, ss);
-          if (sc.on) prof_work[KID_DOWNDATE] += double(n) * n * (std::min(c1, m) - std::min(c0, m));
-          Syrk6Args a{d_Vimg, ldy / 16, c0 / 16, width / 16, S(), ld, d_tilemap + tri6_off, tri_count, d_counters + counter_next,
-                      0, 0, INT_MAX};
-          a.stag_half = opt_syrk_stag_half; a.stag_mod4 = opt_syrk_stag_mod4;
-          if (su_tail) {
-            a.su_mu = mu(); a.su_V = d_V; a.su_ldy = ldy; a.su_n = n; a.su_y = d_V + (size_t)npad_live * ldy; a.su_mpad = m_pad;
-            a.su_qn = d_scr + SCR_QN; a.su_counter = d_counters + counter_next + 1;
-            ++launch_cnt[EKF_LAUNCH_STATE_UPDATE_TAIL];
-          }
-          if (row_rider) {
-            a.ry = d_V + (size_t)npad_live * ldy + c0; a.rL = Y + (size_t)c1 * ldy + c0; a.rldl = ldy;
-            a.rnu = d_W + (size_t)npad_live * ldy + c1; a.rcols = m_pad - c1; a.rK = width; a.nrider = (m_pad - c1 + 255) / 256;
-          }
-          counter_next += 8;
-          ++launch_cnt[EKF_LAUNCH_DOWNDATE_BF16X6];
-          if (row_rider) ++launch_cnt[EKF_LAUNCH_ROW_RIDER];
-          const int wgs = 2 * (overlap ? (num_cus - reserved_cus) : num_cus);
-          k_syrk_bf16x6<0><<<a.nrider + std::min(tri_count, wgs), 256, 0, ss>>>(a);
-          split_done = true;
-        }
+      if (split_now) {
+        // the lower tiles of Sigma, downdated from LDS-DMA-fed records of the plane image (only the plain step counts its
+        // image launches)
+        if (!vimg_done) ++launch_cnt[EKF_LAUNCH_SPLIT_IMAGE];
+        rc = launch_downdate_bf16x6(c0, c1, m_pad, ss, !vimg_done, d_tilemap + tri6_off, tri_count, 0, 0, INT_MAX,
+                                    double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail);
+        if (rc) return rc;
       }
       if (fuse) {
         if constexpr (kIsF32) {
@@ -2186,7 +2278,7 @@ struct Filter : FilterBase {
           k_gemm_mfma<ROLE_DOWNDATE, false><<<std::min(g.ntiles, wgs), 256, 0, ss>>>(g);
           if (!recompute) HIPCHK(hipEventRecord(ev_wu, stream_b));
         }
-      } else if (!split_done && !allinone) {
+      } else if (!split_now && !allinone) {
         Scope sc(this, KID_DOWNDATE, ss);                 // Sigma -= V_g V_g^T (lower tiles + mirror)
         if (sc.on) prof_work[KID_DOWNDATE] += double(n) * n * (std::min(c1, m) - std::min(c0, m));   // symmetric half, 2 flop per MAC
         const bool t64 = kIsF32 && opt_mfma && tri_count < num_cus;
@@ -2203,21 +2295,13 @@ struct Filter : FilterBase {
           gemm<ROLE_DOWNDATE, false>(d_V + c0, ldy, d_V + c0, ldy, S(), ld, npad_live, npad_live, width, T(-1), T(1), 2, 0,
                                      0, 0, 0, ss, d_tilemap, tri_count);
       }
-      if constexpr (kIsF32) {
-        if (recompute && gi + 1 < nchunks) {
-          // W[:, c1:c2) = Sigma' H^T for the features of the NEXT chunk, Sigma' = Sigma - sum_{g <= gi} V_g V_g^T (stream
-          // order: right behind this chunk's downdate, in front of the wait for the chain): the sequential form of the
-          // update.  Only these columns of Sigma' are read (a feature's six columns + the camera's), i.e. one more pass
-          // over Sigma in all; the right-looking GEMM update W[:, c1:] -= V_g L[c1:, g]^T of every chunk
-          // (2 n w_g (m - c1) flop) is not needed
-          Scope sc(this, KID_SIGMA_HT, ss);
-          ++launch_cnt[EKF_LAUNCH_W_RECOMPUTE];
-          const int s0 = c1 / 2, s1 = cend[gi + 1] * nb / 2;
-          constexpr int RB = 8;
-          dim3 grid((s1 - s0 + 127) / 128, (n + RB - 1) / RB);
-          k_sigma_ht_fast<RB><<<grid, 256, 0, ss>>>(S(), ld, n, d_Hc, d_Hf, d_pos, d_coding, ip_list, M, plane, d_W, ldy, m_pad, N,
-                                                    s0, s1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-        }
+      if (recompute && gi + 1 < nchunks) {
+        // W[:, c1:c2) = Sigma' H^T for the features of the NEXT chunk, Sigma' = Sigma - sum_{g <= gi} V_g V_g^T (stream
+        // order: right behind this chunk's downdate, in front of the wait for the chain): the sequential form of the
+        // update.  Only these columns of Sigma' are read (a feature's six columns + the camera's), i.e. one more pass
+        // over Sigma in all; the right-looking GEMM update W[:, c1:] -= V_g L[c1:, g]^T of every chunk
+        // (2 n w_g (m - c1) flop) is not needed
+        launch_w_recompute(c1, cend[gi + 1] * nb, m_pad, ip_list, M, plane, ss, n);
       }
     }
     if (b_inflight) {
@@ -2225,26 +2309,8 @@ struct Filter : FilterBase {
       HIPCHK(hipStreamWaitEvent(stream, ev_b, 0));
       b_inflight = false;
     }
-    last_nchunks = nchunks;
-    last_recompute = recompute;
-    for (int g = 0; g < nchunks; ++g) last_cend[g] = cend[g];
-    const T* V = d_V;
-    const T* yv = d_V + (size_t)npad_live * ldy;
-    if (nchunks == 1 && !oneblock) {
-      Scope sc(this, KID_STATE_UPDATE);             // mu += V y, then the quaternion normalisation (same launch)
-      k_state_update<T><<<(n + 7) / 8, 512, 0, stream>>>(mu(), V, ldy, n, yv, m_pad, d_scr + SCR_QN);
-    }
-    if (!allinone) {
-      Scope sc(this, KID_NORMALIZE);
-      k_strip_congruence<T, 4><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 3, d_scr + SCR_QN,
-                                                                       static_cast<const T*>(nullptr));
-    }
-    HIPCHK(hipGetLastError());
-    last_m = m; last_m_pad = m_pad; last_n = n;
-    have_update = true;
-    have_meas = false;                                    // h/H belong to the pre-update state
-    ++frame_seq;
-    return EKF_OK;
+    // (several chunks: the state update ran beside the last downdate or inside it; one block: inside the fused launch)
+    return finish_update(nchunks, cend, recompute, m, m_pad, nchunks == 1 && !oneblock, !allinone);
   }
 
   int innovation_covariance(const int* idx, int M, int plane, void* out) override {
@@ -2253,15 +2319,12 @@ struct Filter : FilterBase {
     if (!have_meas) FAIL(EKF_ERR_STATE, "ekf_innovation_covariance needs ekf_predict / ekf_measure first");
     const int mm = 2 * M + (plane ? 3 : 0);
     if (mm == 0) return EKF_OK;
-    for (int k = 0; k < M; ++k)
-      if (idx[k] < 0 || idx[k] >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
+    int rc = check_list(idx, M, sh_on);
+    if (rc) return rc;
     if (M > 0) HIPCHK(hipMemcpyAsync(d_midx, idx, (size_t)M * sizeof(int), hipMemcpyHostToDevice, stream));
     sh_list.clear();
     int m = 0, m_pad = 0;
-    int rc;
     if (sh_on) {
-      rc = check_ascending(idx, M);
-      if (rc) return rc;
       rc = shard_build_ws(idx, M, plane, nullptr, &m, &m_pad);       // W rows {camera, own}, own rows of S, "reassemble S"
     } else {
       rc = build_innovation(M, plane, false, &m, &m_pad);
@@ -2455,11 +2518,10 @@ struct Filter : FilterBase {
     HIPCHK(hipSetDevice(device));
     if (M <= 0) return EKF_OK;
     if (M > N || !cam_before || !z || !idx || !out) FAIL(EKF_ERR_ARG, "bad arguments");
-    for (int k = 0; k < M; ++k)
-      if (idx[k] < 0 || idx[k] >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
-    int rc = sync_layout();
+    int rc = check_list(idx, M, sh_on);
     if (rc) return rc;
-    if (sh_on) { rc = check_ascending(idx, M); if (rc) return rc; }
+    rc = sync_layout();
+    if (rc) return rc;
     rc = stage_inputs(z, idx, M, cam_before);          // pinned staging ring -> d_z / d_midx / d_tmp
     if (rc) return rc;
     sh_list.clear();
@@ -2586,8 +2648,7 @@ struct Filter : FilterBase {
     HIPCHK(hipSetDevice(device));
     if (M <= 0 || M > N || !z || !idx) FAIL(EKF_ERR_ARG, "bad measured set");
     if (!have_meas) FAIL(EKF_ERR_STATE, "ekf_ransac_1point needs ekf_predict / ekf_measure first");
-    for (int k = 0; k < M; ++k)
-      if (idx[k] < 0 || idx[k] >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
+    { int rcl = check_list(idx, M, sh_on); if (rcl) return rcl; }
     { int rcs = stage_inputs(z, idx, M); if (rcs) return rcs; }   // pinned staging ring -> d_z / d_midx
     sh_list.clear();
     int m = 0, m_pad = 0;
@@ -3134,11 +3195,6 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
 
-  int check_ascending(const int* idx, int M) {
-    for (int k = 1; k < M; ++k)
-      if (idx[k - 1] >= idx[k]) FAIL(EKF_ERR_ARG, "sharded filter: measured indices must be strictly ascending");
-    return EKF_OK;
-  }
   // list positions [start, start + count) of every rank's features in an ascending measured list
   ShardTab list_tab(const int* idx, int M) const {
     ShardTab t{sh_world, sh_rank, {}, {}};
@@ -3287,8 +3343,6 @@ struct Filter : FilterBase {
   // re-projects -- a rank evaluates EVERY hypothesis on the listed features it owns (its rows of W), the partial inlier
   // counts are all-gathered and summed; the inlier column of one hypothesis is gathered the same way (fetch_mask_column)
   int shard_ransac(const int* idx, int M, double thr, int* counts, unsigned char* inl, int* best) {
-    int rc = check_ascending(idx, M);
-    if (rc) return rc;
     int m = 0, m_pad = 0;
     {
       // W rows {camera, own} only (no S): the sigma_ht half of shard_build_ws
@@ -3334,7 +3388,7 @@ struct Filter : FilterBase {
     }
     HIPCHK(hipGetLastError());
     std::vector<unsigned char> host;
-    rc = gather_bytes_to_host(d_ibuf, (size_t)M * sizeof(int), (size_t)M * sizeof(int), host);
+    int rc = gather_bytes_to_host(d_ibuf, (size_t)M * sizeof(int), (size_t)M * sizeof(int), host);
     if (rc) return rc;
     const size_t slot_b = host.size() / sh_world;
     std::vector<int> cnt(M, 0);
@@ -3472,23 +3526,11 @@ struct Filter : FilterBase {
 
   int shard_predict(const void* tc, const void* rc_, int vcontrol) {
     if (shard_needs_rebalance()) { int rr = shard_rebalance(); if (rr) return rr; }
-    MotionArgs a;
-    a.dT = dT;
-    const T* t = static_cast<const T*>(tc);
-    const T* r = static_cast<const T*>(rc_);
-    for (int i = 0; i < 3; ++i) { a.t_ctl[i] = t ? double(t[i]) : 0.0; a.r_ctl[i] = r ? double(r[i]) : 0.0; }
-    for (int i = 0; i < 6; ++i) a.vdiag[i] = vcontrol ? vmax[i] : double(T(vmax[i]) * T(2));
     int rc = sync_layout();
     if (rc) return rc;
-    { Scope sc(this, KID_PREDICT_CAMERA); k_predict_camera<T><<<1, 64, 0, stream>>>(mu(), d_scr, a); }
-    have_motion = true;
-    {
-      // rows 0..12 are replicated; the column strip of foreign rows works on stale data nobody reads
-      Scope sc(this, KID_PROPAGATE_STRIPS);
-      k_strip_congruence<T, 13><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 0, d_scr + SCR_FT, d_scr + SCR_Q);
-    }
-    if (opt_feature_noise > 0.0 && n > camera_dim)
-      k_inflate_diagonal<T><<<(n - camera_dim + 255) / 256, 256, 0, stream>>>(S(), ld, camera_dim, n, T(opt_feature_noise));
+    // rows 0..12 are replicated; the column strip of foreign rows works on stale data nobody reads
+    rc = propagate(motion_args(tc, rc_, vcontrol), false);
+    if (rc) return rc;
     const int f0 = own_f0(), f1 = own_f1();
     if (f1 > f0) {
       Scope sc(this, KID_MEASURE);
@@ -3527,10 +3569,8 @@ struct Filter : FilterBase {
     if (M == 0 && !plane) return EKF_OK;
     if (!have_meas) FAIL(EKF_ERR_STATE, "the sharded update needs the h / H of the sharded predict");
     if (M > 0 && (!dz || !idx)) FAIL(EKF_ERR_ARG, "z / indices are NULL");
-    for (int k = 0; k < M; ++k) {
-      if (idx[k] < 0 || idx[k] >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
-      if (k > 0 && idx[k - 1] >= idx[k]) FAIL(EKF_ERR_ARG, "measured indices must be strictly ascending");
-    }
+    int rc = check_list(idx, M, true);
+    if (rc) return rc;
     if (M > 0 && ((int)sh_list.size() != M || memcmp(sh_list.data(), idx, (size_t)M * sizeof(int)) != 0)) {
       sh_list.assign(idx, idx + M);
       HIPCHK(hipMemcpyAsync(d_midx, sh_list.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -3541,7 +3581,7 @@ struct Filter : FilterBase {
     const int npad_live = round_up(n, nb);
     if (dbg_sync & 4) HIPCHK(hipDeviceSynchronize());
     // nu (replicated), W rows {camera, own}, own rows of S, "reassemble S"
-    int rc = shard_build_ws(idx, M, plane, d_zz, &m, &m_pad);
+    rc = shard_build_ws(idx, M, plane, d_zz, &m, &m_pad);
     if (rc) return rc;
     // own state rows, and the tile-padded panel [p0, p0 + prows) the tile GEMMs run on: it covers the own rows and,
     // at its ends, a few foreign ones (whose results nobody reads and the next gather overwrites); it never reaches
@@ -3570,37 +3610,9 @@ struct Filter : FilterBase {
     // exposed tail shrinks with the width of the last one.
     const int nsteps = m_pad / nb;
     int cend[8];
-    int nchunks;
-    {
-      const bool pipe = (opt_pipeline < 0) ? (nsteps >= 4) : (opt_pipeline != 0);
-      if (!pipe || !stream_b || !stream_g) {
-        cend[0] = nsteps;
-        nchunks = 1;
-      } else if (env_nchunks > 0 && env_chunks[env_nchunks - 1] == nsteps) {
-        for (int g = 0; g < env_nchunks; ++g) cend[g] = env_chunks[g];
-        nchunks = env_nchunks;
-      } else if (sh_world <= 1 && nsteps >= 8) {
-        nchunks = plan_chunks(nsteps, cend, true);           // one rank: the plain path's plan with an earlier first cut
-      } else {
-        // chunk count by world size: every chunk costs a pass over the remaining columns of W and re-reads the Sigma
-        // panel, and a rank's share of that work is 1 / world -- two ranks afford 4 chunks, four and more 8
-        const int cap = sh_world <= 1 ? 3 : (sh_world <= 2 ? 4 : 8);
-        const int want = std::min(cap, std::max(2, (nsteps + 1) / 2));
-        nchunks = 0;
-        int prev = 0;
-        for (int g = 0; g < want; ++g) {
-          int e = (int)(((long long)nsteps * (g + 1) + want - 1) / want);
-          if (g + 1 == want) e = nsteps;
-          if (e > prev) { cend[nchunks++] = e; prev = e; }
-        }
-      }
-    }
-    ChunkTab tab{nchunks, {}};
+    const int nchunks = plan_chunks(nsteps, cend);
     int strip_rows = 0;
-    for (int g = 0; g < nchunks; ++g) {
-      tab.end[g] = cend[g] * nb;
-      strip_rows = std::max(strip_rows, (cend[g] - (g ? cend[g - 1] : 0)) * nb);
-    }
+    const ChunkTab tab = chunk_table(cend, nchunks, nb, &strip_rows);
     T* Y = d_Y;
     T* Zs = d_Y + (size_t)m_pad * ldy;
     { Scope sc(this, KID_MISC);
@@ -3612,49 +3624,22 @@ struct Filter : FilterBase {
       shard_split = opt_split_bf16 && opt_mfma && nb == 128 && (npad_live / 128) * (npad_live / 128 + 1) / 2 >= num_cus;
     if (shard_split) { rc = ensure_shard_syrk_list(r0, r1, npad_live); if (rc) return rc; }
     bool sh_row_pending = false;                           // (sequential form) the innovation row still waits for chunk [c0, c1)
-    auto row_update_alone = [&](int c0, int c1, hipStream_t ss) {
-      if constexpr (kIsF32) {
-        Scope sc(this, KID_WUPDATE, ss);
-        ++launch_cnt[EKF_LAUNCH_ROW_GEMV];
-        k_innov_row_update<<<(m_pad - c1 + 63) / 64, 64, 0, ss>>>(d_V + (size_t)npad_live * ldy + c0, d_Y + (size_t)c1 * ldy + c0, ldy,
-                                                                  d_W + (size_t)npad_live * ldy + c1, m_pad - c1, c1 - c0);
-      }
-    };
     auto downdate_chunk = [&](int c0, int c1, hipStream_t ss) -> int {
-      if (sh_row_pending && !(kIsF32 && shard_split && counter_next + 8 <= kQueueCounters)) {
-        row_update_alone(c0, c1, ss);
+      const bool split = kIsF32 && shard_split && counter_next + 8 <= kQueueCounters;
+      if (sh_row_pending && !split) {
+        launch_row_update(c0, c1, m_pad, ss, true);
         sh_row_pending = false;
       }
-      if constexpr (kIsF32) {
-        if (shard_split && counter_next + 8 <= kQueueCounters) {
-          // EKF_OPT_SPLIT_BF16: V_g (every row: the gather is done) -> plane image, then ONE launch over the canonical tiles
-          // that touch the camera block or an own block; each element pair is the same sum as on the plain path
-          if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
-          {
-            Scope sc(this, KID_MISC, ss);
-            dim3 grid(npad_live / 128, (c1 - c0) / 16);
-            k_split_image<<<grid, 256, 0, ss>>>(d_V, ldy, npad_live, c0, c1 - c0, d_Vimg, ldy / 16);
-          }
-          if (shard_syrk_n > 0) {
-            Scope sc(this, KID_DOWNDATE, ss);
-            if (sc.on) prof_work[KID_DOWNDATE] += 2.0 * 128 * 128 * shard_syrk_n * double(std::min(c1, m) - std::min(c0, m));
-            Syrk6Args a{d_Vimg, ldy / 16, c0 / 16, (c1 - c0) / 16, S(), ld, d_shard_syrk, shard_syrk_n, d_counters + counter_next,
-                        camera_dim, r0, r1};
-            a.stag_half = opt_syrk_stag_half; a.stag_mod4 = opt_syrk_stag_mod4;
-            if (sh_row_pending) {
-              a.ry = d_V + (size_t)npad_live * ldy + c0; a.rL = d_Y + (size_t)c1 * ldy + c0; a.rldl = ldy;
-              a.rnu = d_W + (size_t)npad_live * ldy + c1; a.rcols = m_pad - c1; a.rK = c1 - c0; a.nrider = (m_pad - c1 + 255) / 256;
-              sh_row_pending = false;
-              ++launch_cnt[EKF_LAUNCH_ROW_RIDER];
-            }
-            ++launch_cnt[EKF_LAUNCH_DOWNDATE_BF16X6];
-            counter_next += 8;
-            const int wgs = 2 * ((ss == stream_b) ? (num_cus - reserved_cus) : num_cus);
-            k_syrk_bf16x6<0><<<a.nrider + std::min(shard_syrk_n, wgs), 256, 0, ss>>>(a);
-          }
-          if (sh_row_pending) { row_update_alone(c0, c1, ss); sh_row_pending = false; }
-          return EKF_OK;
-        }
+      if (split) {
+        // V_g (every row: the gather is done) -> plane image, then ONE launch over the canonical tiles that touch the camera
+        // block or an own block; each element pair is the same sum as on the plain path
+        const bool rider = sh_row_pending && shard_syrk_n > 0;
+        int rcd = launch_downdate_bf16x6(c0, c1, m_pad, ss, true, d_shard_syrk, shard_syrk_n, camera_dim, r0, r1,
+                                         2.0 * 128 * 128 * shard_syrk_n * double(std::min(c1, m) - std::min(c0, m)), rider, false);
+        if (rcd) return rcd;
+        if (sh_row_pending && !rider) launch_row_update(c0, c1, m_pad, ss, true);
+        sh_row_pending = false;
+        return EKF_OK;
       }
       for (int q = 0; q < 2; ++q) {                        // Sigma[rows, :] -= V_g[rows] V_g^T: camera tile, own panel
         const Rows& rr = ranges[q];
@@ -3756,20 +3741,8 @@ struct Filter : FilterBase {
           sh_row_pending = c1 < m_pad;
           rc = downdate_chunk(c0, c1, ss);
           if (rc) return rc;
-          if (gi + 1 < nchunks) {
-            Scope sc(this, KID_SIGMA_HT, ss);                // W'[rows, c1:c2) = Sigma'[rows, :] H^T, rows = camera + own
-            ++launch_cnt[EKF_LAUNCH_W_RECOMPUTE];
-            const int s0 = c1 / 2, s1 = cend[gi + 1] * nb / 2;
-            constexpr int RB = 8;
-            dim3 g1((s1 - s0 + 127) / 128, (camera_dim + RB - 1) / RB);
-            k_sigma_ht_fast<RB><<<g1, 256, 0, ss>>>(S(), ld, camera_dim, d_Hc, d_Hf, d_pos, d_coding, d_midx, M, plane, d_W, ldy, m_pad, N,
-                                                    s0, s1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-            if (r1 > r0) {
-              dim3 g2((s1 - s0 + 127) / 128, (r1 - r0 + RB - 1) / RB);
-              k_sigma_ht_fast<RB><<<g2, 256, 0, ss>>>(S(), ld, r1, d_Hc, d_Hf, d_pos, d_coding, d_midx, M, plane, d_W, ldy, m_pad, N,
-                                                      s0, s1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r0);
-            }
-          }
+          // W'[rows, c1:c2) = Sigma'[rows, :] H^T, rows = camera + own
+          if (gi + 1 < nchunks) launch_w_recompute(c1, cend[gi + 1] * nb, m_pad, d_midx, M, plane, ss, camera_dim, r0, r1);
           if (dbg_sync & 2) HIPCHK(hipDeviceSynchronize());
           continue;
         }
@@ -3818,23 +3791,8 @@ struct Filter : FilterBase {
       }
     }
     HIPCHK(hipGetLastError());
-    last_nchunks = nchunks;
-    last_recompute = sh_rec;
-    for (int g = 0; g < nchunks; ++g) last_cend[g] = cend[g];
-    {
-      Scope sc(this, KID_STATE_UPDATE);                    // mu is replicated: every rank adds V y over all rows
-      k_state_update<T><<<(n + 7) / 8, 512, 0, stream>>>(mu(), d_V, ldy, n, d_V + (size_t)npad_live * ldy, m_pad, d_scr + SCR_QN);
-    }
-    {
-      Scope sc(this, KID_NORMALIZE);
-      k_strip_congruence<T, 4><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 3, d_scr + SCR_QN,
-                                                                       static_cast<const T*>(nullptr));
-    }
-    HIPCHK(hipGetLastError());
-    last_m = m; last_m_pad = m_pad; last_n = n;
-    have_update = true;
-    have_meas = false;
-    ++frame_seq;
+    rc = finish_update(nchunks, cend, sh_rec, m, m_pad, true, true);   // mu is replicated: every rank adds V y over all rows
+    if (rc) return rc;
     if (dbg_sync & 1) HIPCHK(hipDeviceSynchronize());
     return EKF_OK;
   }
