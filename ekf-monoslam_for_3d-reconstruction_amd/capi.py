@@ -118,6 +118,20 @@ _PROTOS = {
     "ekf_shard_rebalance": (C.c_int, [_P]),
     "ekf_device_mu": (_P, [_P]),
     "ekf_device_sigma": (_P, [_P, C.POINTER(C.c_int)]),
+    "ekf_sba_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "ekf_sba_destroy": (None, [_P]),
+    "ekf_sba_last_error": (C.c_char_p, [_P]),
+    "ekf_sba_add_nodes": (C.c_int, [_P, C.c_int, _P]),
+    "ekf_sba_add_points": (C.c_int, [_P, C.c_int, _P]),
+    "ekf_sba_add_projections": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
+    "ekf_sba_counts": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ekf_sba_run": (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_int)]),
+    "ekf_sba_cost": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ekf_sba_get_nodes": (C.c_int, [_P, _P]),
+    "ekf_sba_get_points": (C.c_int, [_P, _P]),
+    "ekf_sba_get_log": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "ekf_sba_profile": (C.c_int, [_P, C.c_int]),
+    "ekf_sba_get_profile": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
 }
 
 _lib = None

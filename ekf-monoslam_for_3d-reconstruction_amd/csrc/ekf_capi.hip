@@ -3,12 +3,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -23,6 +25,7 @@
 #include "ekf_step.hpp"
 #include "ekf_kernels.hpp"
 #include "ekf_shard.hpp"
+#include "ekf_sba.hpp"
 
 namespace ekf {
 
@@ -3865,6 +3868,268 @@ struct Filter : FilterBase {
   }
 };
 
+
+// ---------------------------------------------------------------------------------------
+// Bundle adjustment of the key-frame map: host side of ekf_sba_*.  The host keeps the problem
+// (nodes, points, the (point, node)-sorted projections) and builds the index lists once per change of structure;
+// ekf_sba_run uploads the state, runs the LM loop on its own stream and reads back one SbaResult per iteration.
+// ---------------------------------------------------------------------------------------
+struct SbaSystem {
+  std::string err;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  SbaCamera K{};
+  int cap_nodes = 0, cap_points = 0, cap_prj = 0;
+  std::vector<double> nodes, points;                         // 7 per node (t, q w x y z), 3 per point
+  std::map<std::pair<int, int>, std::array<double, 2>> prj;  // (point, node) -> keypoint
+  double lambda = 1e-4;                                      // kept for continuation, as SysSBA::lambda
+  std::vector<double> log;                                   // 5 per iteration of the last run
+  bool dirty = true;
+  // profile (ekf_sba_profile): per phase and per iteration, milliseconds
+  bool profile = false;
+  double phase_ms[5] = {0, 0, 0, 0, 0};
+  std::vector<double> iter_ms;
+  hipEvent_t ev[6] = {};
+  // device
+  struct Buf { void* p = nullptr; size_t bytes = 0; };
+  enum { B_NODES, B_OLDN, B_NM, B_PTS, B_OLDP, B_POFF, B_PNODE, B_PPOINT, B_UV, B_PRJ, B_TPS, B_COFF, B_CPRJ,
+         B_PAIR_AB, B_PAIR_OFF, B_ITEMS, B_EMPTY, B_A, B_L, B_B, B_X, B_R, B_DX, B_DINV, B_PART, B_RES, B_COUNT };
+  Buf buf[B_COUNT];
+  int npairs = 0, nfree = 0, npad = 0;
+
+  ~SbaSystem() {
+    hipSetDevice(device);
+    for (auto& b : buf) if (b.p) hipFree(b.p);
+    for (auto& e : ev) if (e) hipEventDestroy(e);
+    if (stream) hipStreamDestroy(stream);
+  }
+  template <typename T> T* dp(int i) { return static_cast<T*>(buf[i].p); }
+  int ensure(int i, size_t bytes) {
+    if (bytes == 0) bytes = 8;
+    if (buf[i].bytes >= bytes) return EKF_OK;
+    if (buf[i].p) HIPCHK(hipFree(buf[i].p));
+    buf[i].p = nullptr;
+    buf[i].bytes = 0;
+    HIPCHK(hipMalloc(&buf[i].p, bytes));
+    buf[i].bytes = bytes;
+    return EKF_OK;
+  }
+  int init(const ekf_sba_camera* cam, int cn, int cp, int cj, int dev) {
+    device = dev;
+    K = SbaCamera{cam->fx, cam->fy, cam->cx, cam->cy};
+    cap_nodes = cn; cap_points = cp; cap_prj = cj;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipMalloc(&buf[B_RES].p, sizeof(SbaResult)));
+    buf[B_RES].bytes = sizeof(SbaResult);
+    return EKF_OK;
+  }
+  int nn() const { return (int)nodes.size() / 7; }
+  int np() const { return (int)points.size() / 3; }
+
+  // structure: projection arrays in (point, node) order, per-camera lists, the pair lists; allocations
+  int build() {
+    const int P = (int)prj.size(), N = nn(), M = np();
+    nfree = std::max(N - 1, 0);
+    npad = (6 * nfree + 63) / 64 * 64;
+    std::vector<int> poff(M + 1, 0), pnode(P), ppoint(P);
+    std::vector<double> uv(2 * P);
+    std::vector<std::vector<int>> cam(nfree);
+    int k = 0;
+    for (const auto& e : prj) {
+      pnode[k] = e.first.second;
+      ppoint[k] = e.first.first;
+      uv[2 * k] = e.second[0];
+      uv[2 * k + 1] = e.second[1];
+      ++poff[e.first.first + 1];
+      if (e.first.second > 0) cam[e.first.second - 1].push_back(k);
+      ++k;
+    }
+    for (int p = 0; p < M; ++p) poff[p + 1] += poff[p];
+    std::vector<int> coff(nfree + 1, 0), cprj, empty(std::max(nfree, 1), 0);
+    for (int a = 0; a < nfree; ++a) {
+      coff[a + 1] = coff[a] + (int)cam[a].size();
+      cprj.insert(cprj.end(), cam[a].begin(), cam[a].end());
+      empty[a] = cam[a].empty() ? 1 : 0;
+    }
+    std::map<std::pair<int, int>, std::vector<int>> pairs;
+    for (int p = 0; p < M; ++p)
+      for (int i = poff[p]; i < poff[p + 1]; ++i) {
+        if (pnode[i] == 0) continue;
+        for (int j = i; j < poff[p + 1]; ++j) {
+          auto& v = pairs[{pnode[i] - 1, pnode[j] - 1}];
+          v.push_back(i);
+          v.push_back(j);
+        }
+      }
+    npairs = (int)pairs.size();
+    std::vector<int> pair_ab, pair_off(1, 0), items;
+    for (const auto& e : pairs) {
+      pair_ab.push_back(e.first.first);
+      pair_ab.push_back(e.first.second);
+      items.insert(items.end(), e.second.begin(), e.second.end());
+      pair_off.push_back((int)items.size() / 2);
+    }
+    const size_t D = sizeof(double), I = sizeof(int);
+    int rc;
+    if ((rc = ensure(B_NODES, 7 * D * N)) || (rc = ensure(B_OLDN, 7 * D * N)) || (rc = ensure(B_NM, kSbaNM * D * N)) ||
+        (rc = ensure(B_PTS, 3 * D * M)) || (rc = ensure(B_OLDP, 3 * D * M)) || (rc = ensure(B_POFF, I * (M + 1))) ||
+        (rc = ensure(B_PNODE, I * P)) || (rc = ensure(B_PPOINT, I * P)) || (rc = ensure(B_UV, 2 * D * P)) ||
+        (rc = ensure(B_PRJ, kSbaPR * D * P)) || (rc = ensure(B_TPS, 3 * D * M)) || (rc = ensure(B_COFF, I * coff.size())) ||
+        (rc = ensure(B_CPRJ, I * cprj.size())) || (rc = ensure(B_PAIR_AB, I * pair_ab.size())) ||
+        (rc = ensure(B_PAIR_OFF, I * pair_off.size())) || (rc = ensure(B_ITEMS, I * items.size())) ||
+        (rc = ensure(B_EMPTY, I * empty.size())) || (rc = ensure(B_A, D * npad * npad)) ||
+        (rc = ensure(B_L, D * npad * npad)) || (rc = ensure(B_B, D * npad)) || (rc = ensure(B_X, D * npad)) ||
+        (rc = ensure(B_R, D * npad)) || (rc = ensure(B_DX, D * npad)) || (rc = ensure(B_DINV, D * 64 * 64)) ||
+        (rc = ensure(B_PART, 3 * D * ((P + 255) / 256))))
+      return rc;
+    auto up = [&](int i, const void* src, size_t bytes) -> int {
+      if (bytes) HIPCHK(hipMemcpyAsync(buf[i].p, src, bytes, hipMemcpyHostToDevice, stream));
+      return EKF_OK;
+    };
+    if ((rc = up(B_POFF, poff.data(), I * poff.size())) || (rc = up(B_PNODE, pnode.data(), I * P)) ||
+        (rc = up(B_PPOINT, ppoint.data(), I * P)) || (rc = up(B_UV, uv.data(), 2 * D * P)) ||
+        (rc = up(B_COFF, coff.data(), I * coff.size())) || (rc = up(B_CPRJ, cprj.data(), I * cprj.size())) ||
+        (rc = up(B_PAIR_AB, pair_ab.data(), I * pair_ab.size())) || (rc = up(B_PAIR_OFF, pair_off.data(), I * pair_off.size())) ||
+        (rc = up(B_ITEMS, items.data(), I * items.size())) || (rc = up(B_EMPTY, empty.data(), I * empty.size())))
+      return rc;
+    HIPCHK(hipStreamSynchronize(stream));          // the host vectors above go out of scope
+    dirty = false;
+    return EKF_OK;
+  }
+  int upload_state() {
+    int rc;
+    if (dirty && (rc = build())) return rc;
+    HIPCHK(hipMemcpyAsync(buf[B_NODES].p, nodes.data(), sizeof(double) * nodes.size(), hipMemcpyHostToDevice, stream));
+    if (!points.empty())
+      HIPCHK(hipMemcpyAsync(buf[B_PTS].p, points.data(), sizeof(double) * points.size(), hipMemcpyHostToDevice, stream));
+    return EKF_OK;
+  }
+  static int blocks(int n, int t = 256) { return (n + t - 1) / t; }
+  // node matrices + the cost pass (dist2: the RMS cut) into B_RES
+  int launch_cost(double dist2) {
+    const int P = (int)prj.size();
+    k_sba_node_prep<<<blocks(nn()), 256, 0, stream>>>(dp<double>(B_NODES), nn(), K, dp<double>(B_NM));
+    k_sba_cost<<<blocks(P), 256, 0, stream>>>(dp<double>(B_NM), dp<double>(B_PTS), dp<int>(B_PNODE), dp<int>(B_PPOINT),
+                                               dp<double>(B_UV), P, dist2, dp<double>(B_PART));
+    k_sba_cost_final<<<1, 256, 0, stream>>>(dp<double>(B_PART), blocks(P), dp<SbaResult>(B_RES));
+    HIPCHK(hipGetLastError());
+    return EKF_OK;
+  }
+  int read_result(SbaResult* r) {
+    HIPCHK(hipMemcpyAsync(r, buf[B_RES].p, sizeof(SbaResult), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return EKF_OK;
+  }
+  int download_state() {
+    HIPCHK(hipMemcpyAsync(nodes.data(), buf[B_NODES].p, sizeof(double) * nodes.size(), hipMemcpyDeviceToHost, stream));
+    if (!points.empty())
+      HIPCHK(hipMemcpyAsync(points.data(), buf[B_PTS].p, sizeof(double) * points.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return EKF_OK;
+  }
+  int cost(double dist, double* sq, double* rms) {
+    HIPCHK(hipSetDevice(device));
+    if (prj.empty()) {
+      if (sq) *sq = 0.0;
+      if (rms) *rms = std::nan("");
+      return EKF_OK;
+    }
+    int rc;
+    SbaResult r{};
+    if ((rc = upload_state()) || (rc = launch_cost(dist * dist)) || (rc = read_result(&r))) return rc;
+    if (sq) *sq = r.cost;
+    if (rms) *rms = std::sqrt(r.cost_in / r.n_in);
+    return EKF_OK;
+  }
+  void mark(int e) { if (profile) hipEventRecord(ev[e], stream); }
+
+  // SysSBA::doSBA (sba.cpp:1312-1585)
+  int run(int niter, double s_lambda, int* iterations) {
+    log.clear();
+    *iterations = -1;
+    if (prj.empty() || points.empty() || nodes.empty()) return EKF_OK;
+    HIPCHK(hipSetDevice(device));
+    if (s_lambda > 0.0) lambda = s_lambda;
+    int rc;
+    SbaResult r{};
+    if ((rc = upload_state()) || (rc = launch_cost(1e300)) || (rc = read_result(&r))) return rc;
+    double cost = r.cost, laminc = 2.0;
+    const int N = nn(), M = np(), n6 = 6 * nfree, P = (int)prj.size();
+    int iter = 0;
+    for (; iter < niter; ++iter) {
+      if (nfree == 0) break;                       // B has no rows: |x|^2 = 0 < 1e-16 (sba.cpp:1425-1432)
+      const double lam = 1.0 + lambda;
+      mark(0);
+      HIPCHK(hipMemsetAsync(&dp<SbaResult>(B_RES)->status, 0, sizeof(int), stream));
+      k_sba_node_prep<<<blocks(N), 256, 0, stream>>>(dp<double>(B_NODES), N, K, dp<double>(B_NM));
+      mark(1);
+      k_sba_point<<<blocks(M), 256, 0, stream>>>(dp<double>(B_NM), dp<double>(B_NODES), dp<double>(B_PTS), dp<int>(B_POFF),
+                                                  dp<int>(B_PNODE), dp<double>(B_UV), M, K, lam, dp<double>(B_PRJ),
+                                                  dp<double>(B_TPS));
+      mark(2);
+      HIPCHK(hipMemsetAsync(buf[B_A].p, 0, sizeof(double) * npad * npad, stream));
+      k_sba_rhs<<<blocks(n6), 256, 0, stream>>>(dp<int>(B_COFF), dp<int>(B_CPRJ), dp<int>(B_PPOINT), dp<double>(B_PRJ),
+                                                dp<double>(B_TPS), nfree, dp<double>(B_B));
+      if (npairs)
+        k_sba_pairs<<<npairs, 64, 0, stream>>>(dp<int>(B_PAIR_AB), dp<int>(B_PAIR_OFF), dp<int>(B_ITEMS), dp<double>(B_PRJ),
+                                               dp<double>(B_A), npad);
+      k_sba_diag<<<blocks(npad), 256, 0, stream>>>(dp<double>(B_A), npad, n6, npad, dp<int>(B_EMPTY), lam);
+      HIPCHK(hipMemcpyAsync(buf[B_L].p, buf[B_A].p, sizeof(double) * npad * npad, hipMemcpyDeviceToDevice, stream));
+      mark(3);
+      sba_chol_f64(dp<double>(B_L), npad, npad, dp<double>(B_DINV), &dp<SbaResult>(B_RES)->status, stream);
+      k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_B), dp<double>(B_X));
+      k_sba_resid<<<blocks(n6, 4), 256, 0, stream>>>(dp<double>(B_A), npad, n6, dp<double>(B_X), dp<double>(B_B),
+                                                      dp<double>(B_R));
+      k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_R), dp<double>(B_DX));
+      k_sba_refine<<<1, 256, 0, stream>>>(dp<double>(B_X), dp<double>(B_DX), n6, dp<SbaResult>(B_RES));
+      mark(4);
+      k_sba_update_nodes<<<blocks(N), 256, 0, stream>>>(dp<double>(B_NODES), dp<double>(B_OLDN), N, dp<double>(B_X),
+                                                         dp<SbaResult>(B_RES));
+      k_sba_update_points<<<blocks(M), 256, 0, stream>>>(dp<double>(B_PTS), dp<double>(B_OLDP), M, dp<double>(B_TPS),
+                                                          dp<int>(B_POFF), dp<int>(B_PNODE), dp<double>(B_PRJ),
+                                                          dp<double>(B_X), dp<SbaResult>(B_RES));
+      if ((rc = launch_cost(1e300))) return rc;
+      mark(5);
+      if ((rc = read_result(&r))) return rc;       // the one read-back of the iteration
+      if (profile) {
+        float ms[5], tot = 0.f;
+        for (int e = 0; e < 5; ++e) {
+          HIPCHK(hipEventElapsedTime(&ms[e], ev[e], ev[e + 1]));
+          phase_ms[e] += ms[e];
+          tot += ms[e];
+        }
+        iter_ms.push_back(tot);
+      }
+      if (r.status) {
+        *iterations = iter;                        // the iterations completed before the failed factor
+        if ((rc = download_state())) return rc;
+        FAIL(EKF_ERR_NUMERIC, "ekf_sba_run: the reduced camera system has a non-positive pivot");
+      }
+      if (r.x2 < 1e-16) break;                     // converged: no update was made (a NaN step goes on and is rejected)
+      const double before = cost, newcost = r.cost;
+      int acc;
+      if (newcost < cost) {
+        cost = newcost;
+        lambda *= 0.5;
+        acc = 1;
+      } else {
+        lambda *= laminc;
+        laminc *= 2.0;
+        HIPCHK(hipMemcpyAsync(buf[B_NODES].p, buf[B_OLDN].p, sizeof(double) * 7 * N, hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemcpyAsync(buf[B_PTS].p, buf[B_OLDP].p, sizeof(double) * 3 * M, hipMemcpyDeviceToDevice, stream));
+        acc = 0;                                   // the restored state's cost is `cost` (same kernels, same data)
+      }
+      const double row[5] = {before, newcost, lambda, double(acc), r.x2};
+      log.insert(log.end(), row, row + 5);
+    }
+    (void)P;
+    *iterations = iter;
+    return download_state();
+  }
+};
+
 }  // namespace ekf
 
 // =============================================================================================
@@ -4094,5 +4359,200 @@ int ekf_shard_rebalance(ekf_filter* f) { IMPL_OR_ARG(f); MUTATES(f); return f->i
 
 void* ekf_device_mu(ekf_filter* f) { return f ? f->impl->dev_mu() : nullptr; }
 void* ekf_device_sigma(ekf_filter* f, int* ld) { return f ? f->impl->dev_sigma(ld) : nullptr; }
+
+// ---- bundle adjustment --------------------------------------------------
+struct ekf_sba {
+  ekf::SbaSystem* impl;
+};
+
+static bool sba_finite(const double* v, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+int ekf_sba_create(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
+                   int device, ekf_sba** out) {
+  if (!out) return EKF_ERR_ARG;
+  *out = nullptr;
+  if (!K || !sba_finite(&K->fx, 4) || !(K->fx > 0.0) || !(K->fy > 0.0) || capacity_nodes < 1 ||
+      capacity_nodes > ekf::kSbaMaxN / 6 || capacity_points < 1 || capacity_projections < 1) {
+    ekf::g_create_error = "ekf_sba_create: bad argument (K finite with fx, fy > 0; 1 <= capacity_nodes <= 1024; "
+                          "capacities >= 1)";
+    return EKF_ERR_ARG;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    ekf::g_create_error = "ekf_sba_create: no HIP device (this library has no CPU fallback)";
+    return EKF_ERR_DEVICE;
+  }
+  auto* s = new ekf::SbaSystem();
+  const int rc = s->init(K, capacity_nodes, capacity_points, capacity_projections, device);
+  if (rc != EKF_OK) {
+    ekf::g_create_error = s->err;
+    delete s;
+    return rc;
+  }
+  *out = new ekf_sba{s};
+  return EKF_OK;
+}
+
+void ekf_sba_destroy(ekf_sba* s) {
+  if (!s) return;
+  delete s->impl;
+  delete s;
+}
+
+const char* ekf_sba_last_error(const ekf_sba* s) {
+  if (!s) return ekf::g_create_error.c_str();
+  return s->impl->err.c_str();
+}
+
+int ekf_sba_add_nodes(ekf_sba* s, int n, const double* pose7) {
+  if (!s) return EKF_ERR_ARG;
+  auto* q = s->impl;
+  if (n < 0 || (n > 0 && !pose7) || !sba_finite(pose7, 7 * n)) {
+    q->err = "ekf_sba_add_nodes: n >= 0 finite poses (x y z qw qx qy qz)";
+    return EKF_ERR_ARG;
+  }
+  if (q->nn() + n > q->cap_nodes) {
+    q->err = "ekf_sba_add_nodes: capacity_nodes exceeded";
+    return EKF_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n; ++i) {
+    const double* p = pose7 + 7 * i;
+    // Node::normRot (node.cpp:52-66)
+    double v[3] = {p[4], p[5], p[6]};
+    if (p[3] < 0) { v[0] = -v[0]; v[1] = -v[1]; v[2] = -v[2]; }
+    const double sn = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+    if (sn >= 0.9999) {
+      const double f = -1.0 / (std::sqrt(sn) * 1.0001);
+      v[0] *= f; v[1] *= f; v[2] *= f;
+    }
+    const double w = std::sqrt(1.0 - (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+    const double rec[7] = {p[0], p[1], p[2], w, v[0], v[1], v[2]};
+    q->nodes.insert(q->nodes.end(), rec, rec + 7);
+  }
+  if (n) q->dirty = true;
+  return EKF_OK;
+}
+
+int ekf_sba_add_points(ekf_sba* s, int n, const double* xyz) {
+  if (!s) return EKF_ERR_ARG;
+  auto* q = s->impl;
+  if (n < 0 || (n > 0 && !xyz) || !sba_finite(xyz, 3 * n)) {
+    q->err = "ekf_sba_add_points: n >= 0 finite points";
+    return EKF_ERR_ARG;
+  }
+  if (q->np() + n > q->cap_points) {
+    q->err = "ekf_sba_add_points: capacity_points exceeded";
+    return EKF_ERR_CAPACITY;
+  }
+  q->points.insert(q->points.end(), xyz, xyz + 3 * n);
+  if (n) q->dirty = true;
+  return EKF_OK;
+}
+
+int ekf_sba_add_projections(ekf_sba* s, int n, const int* node, const int* point, const double* uv, int* added) {
+  if (!s) return EKF_ERR_ARG;
+  auto* q = s->impl;
+  if (added) *added = 0;
+  if (n < 0 || (n > 0 && (!node || !point || !uv))) {
+    q->err = "ekf_sba_add_projections: bad argument";
+    return EKF_ERR_ARG;
+  }
+  for (int i = 0; i < n; ++i)
+    if (node[i] < 0 || node[i] >= q->nn() || point[i] < 0 || point[i] >= q->np() || !sba_finite(uv + 2 * i, 2)) {
+      q->err = "ekf_sba_add_projections: node / point index out of range or keypoint not finite";
+      return EKF_ERR_ARG;
+    }
+  // count the new pairs first: the call is all or nothing
+  std::map<std::pair<int, int>, int> fresh;
+  for (int i = 0; i < n; ++i) {
+    const std::pair<int, int> key{point[i], node[i]};
+    if (!q->prj.count(key)) fresh.emplace(key, i);
+  }
+  if ((long long)q->prj.size() + (long long)fresh.size() > q->cap_prj) {
+    q->err = "ekf_sba_add_projections: capacity_projections exceeded";
+    return EKF_ERR_CAPACITY;
+  }
+  int cnt = 0;
+  for (int i = 0; i < n; ++i) {
+    // addMonoProj (sba.cpp:133-143): a repeat of (node, point) keeps the first keypoint
+    auto r = q->prj.emplace(std::pair<int, int>{point[i], node[i]}, std::array<double, 2>{uv[2 * i], uv[2 * i + 1]});
+    cnt += r.second ? 1 : 0;
+  }
+  if (cnt) q->dirty = true;
+  if (added) *added = cnt;
+  return EKF_OK;
+}
+
+int ekf_sba_counts(const ekf_sba* s, int* nodes, int* points, int* projections) {
+  if (!s) return EKF_ERR_ARG;
+  if (nodes) *nodes = s->impl->nn();
+  if (points) *points = s->impl->np();
+  if (projections) *projections = (int)s->impl->prj.size();
+  return EKF_OK;
+}
+
+int ekf_sba_run(ekf_sba* s, int niter, double lambda, int* iterations) {
+  if (!s) return EKF_ERR_ARG;
+  if (!iterations) {
+    s->impl->err = "ekf_sba_run: iterations must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  if (niter < 0 || std::isnan(lambda) || std::isinf(lambda)) {
+    s->impl->err = "ekf_sba_run: niter >= 0, lambda finite";
+    return EKF_ERR_ARG;
+  }
+  return s->impl->run(niter, lambda, iterations);
+}
+
+int ekf_sba_cost(ekf_sba* s, double dist, double* sq_cost, double* rms) {
+  if (!s) return EKF_ERR_ARG;
+  if (!(dist > 0.0)) {
+    s->impl->err = "ekf_sba_cost: dist must be > 0";
+    return EKF_ERR_ARG;
+  }
+  return s->impl->cost(dist, sq_cost, rms);
+}
+
+int ekf_sba_get_nodes(const ekf_sba* s, double* pose7) {
+  if (!s || (!pose7 && s->impl->nn())) return EKF_ERR_ARG;
+  std::copy(s->impl->nodes.begin(), s->impl->nodes.end(), pose7);
+  return EKF_OK;
+}
+
+int ekf_sba_get_points(const ekf_sba* s, double* xyz) {
+  if (!s || (!xyz && s->impl->np())) return EKF_ERR_ARG;
+  std::copy(s->impl->points.begin(), s->impl->points.end(), xyz);
+  return EKF_OK;
+}
+
+int ekf_sba_get_log(const ekf_sba* s, int max_rows, double* rows, int* n) {
+  if (!s || !n || max_rows < 0 || (max_rows > 0 && !rows)) return EKF_ERR_ARG;
+  const int total = (int)s->impl->log.size() / 5;
+  *n = total;
+  const int m = std::min(total, max_rows);
+  std::copy(s->impl->log.begin(), s->impl->log.begin() + 5 * m, rows);
+  return EKF_OK;
+}
+
+int ekf_sba_profile(ekf_sba* s, int enable) {
+  if (!s) return EKF_ERR_ARG;
+  s->impl->profile = enable != 0;
+  for (double& v : s->impl->phase_ms) v = 0.0;
+  s->impl->iter_ms.clear();
+  return EKF_OK;
+}
+
+int ekf_sba_get_profile(const ekf_sba* s, double* phase_ms, int max_iters, double* iter_ms, int* n) {
+  if (!s || !phase_ms || !n || max_iters < 0 || (max_iters > 0 && !iter_ms)) return EKF_ERR_ARG;
+  std::copy(s->impl->phase_ms, s->impl->phase_ms + 5, phase_ms);
+  const int total = (int)s->impl->iter_ms.size();
+  *n = total;
+  std::copy(s->impl->iter_ms.begin(), s->impl->iter_ms.begin() + std::min(total, max_iters), iter_ms);
+  return EKF_OK;
+}
 
 }  // extern "C"

@@ -1,0 +1,395 @@
+// Sparse bundle adjustment of the key-frame map: the reference's sba_add step.
+// fp64 throughout, as in the reference.  Paths are under sparse_bundle_adjustment/.
+//
+// One LM iteration (SysSBA::doSBA, sba.cpp:1312-1585) is, on one stream:
+//   k_sba_point      per point: error, Jacobians and products of every projection (proj.cpp:60-187), Hpp * lam, its
+//                    3 x 3 inverse, tp, and T_a = Hpc_a^T Hppi per projection (setupSparseSys, sba.cpp:1163-1290)
+//   k_sba_rhs        B per free camera, over its projections in point order
+//   k_sba_pairs      the 6 x 6 blocks of A per (a, b) free-camera pair from a host-built (proj_a, proj_b) list
+//   k_sba_diag       the lam scaling of A's diagonal (csparse.cpp:279), identity blocks (deviation 1) and padding
+//   Cholesky         k_chol_diag_packed_f64 / k_panel_direct_f64 / k_gemm_mfma_f64 (ekf_dense.hpp) via sba_chol_f64
+//   k_sba_trsv       x = A^-1 B (one workgroup), k_sba_resid r = B - A x, k_sba_trsv again, k_sba_refine x += dx
+//                    (doChol's one step of iterative refinement, csparse.cpp:307-363) and |x|^2
+//   k_sba_update_*   camera and point update (skipped on the device when |x|^2 < 1e-16 or the factor failed)
+//   k_sba_node_prep  w2n, w2i, dRd* per node;  k_sba_cost / k_sba_cost_final: the cost, two fixed-order passes
+// Every sum has one fixed order (no atomics), so a run is bit-reproducible.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ekf {
+
+struct SbaCamera { double fx, fy, cx, cy; };
+
+// Device result block, read back once per LM iteration.
+struct SbaResult {
+  double x2;          // |x|^2 of the refined step
+  double cost;        // sum of squared errors (all projections)
+  double cost_in;     // sum over the projections with e^2 < dist^2
+  double n_in;        // their count
+  int status;         // 1: a non-positive pivot
+  int pad[3];
+};
+
+constexpr int kSbaNM = 52;            // per node: w2n (12), w2i (12), dRdx, dRdy, dRdz (27), pad
+constexpr int kSbaMaxN = 6144;        // 6 F + padding: k_sba_trsv keeps its vector in LDS (48 KiB)
+
+// Eigen's Quaternion::toRotationMatrix, q = (w, x, y, z)
+__device__ __forceinline__ void sba_quat_rot(const double* q, double R[9]) {
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+
+// transformW2F + setProjection + setDr(true) (node.cpp:96-108): one thread per node
+__global__ void __launch_bounds__(256) k_sba_node_prep(const double* __restrict__ nodes, int nn, SbaCamera K,
+                                                       double* __restrict__ nm) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  const double* t = nodes + 7 * i;
+  double R[9];
+  sba_quat_rot(t + 3, R);
+  double* o = nm + (size_t)kSbaNM * i;
+  double w2n[12];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) w2n[4 * r + c] = R[3 * c + r];                    // R^T
+    w2n[4 * r + 3] = -(w2n[4 * r] * t[0] + w2n[4 * r + 1] * t[1] + w2n[4 * r + 2] * t[2]);
+  }
+  for (int k = 0; k < 12; ++k) o[k] = w2n[k];
+  for (int c = 0; c < 4; ++c) {                                                   // K w2n
+    o[12 + c] = K.fx * w2n[c] + K.cx * w2n[8 + c];
+    o[16 + c] = K.fy * w2n[4 + c] + K.cy * w2n[8 + c];
+    o[20 + c] = w2n[8 + c];
+  }
+  // dRi* R^T with the constant dRi* of node.cpp:18-30 (rows written out; w2n row r = R^T row r)
+  const double* a0 = w2n; const double* a1 = w2n + 4; const double* a2 = w2n + 8;
+  for (int c = 0; c < 3; ++c) {
+    o[24 + c] = 0.0;          o[27 + c] = 2.0 * a2[c];  o[30 + c] = -2.0 * a1[c];     // dRdx
+    o[33 + c] = -2.0 * a2[c]; o[36 + c] = 0.0;          o[39 + c] = 2.0 * a0[c];      // dRdy
+    o[42 + c] = 2.0 * a1[c];  o[45 + c] = -2.0 * a0[c]; o[48 + c] = 0.0;              // dRdz
+  }
+}
+
+// calcErrMono_ (proj.cpp:143-187): e = p1.xy / p1.z - kp, or 0 when p1.z <= 0
+__device__ __forceinline__ void sba_error(const double* w2i, const double* X, const double* kp, double e[2]) {
+  const double p0 = w2i[0] * X[0] + w2i[1] * X[1] + w2i[2] * X[2] + w2i[3];
+  const double p1 = w2i[4] * X[0] + w2i[5] * X[1] + w2i[6] * X[2] + w2i[7];
+  const double p2 = w2i[8] * X[0] + w2i[9] * X[1] + w2i[10] * X[2] + w2i[11];
+  if (p2 <= 0.0) { e[0] = 0.0; e[1] = 0.0; return; }
+  e[0] = p0 / p2 - kp[0];
+  e[1] = p1 / p2 - kp[1];
+}
+
+// Per projection record: Hcc (36), Hpc (18, 3 x 6), T (18, Tpc 6 x 3), JcTE (6)
+constexpr int kSbaPR = 78;
+
+// setupSparseSys per point (sba.cpp:1190-1251): one thread per point, its projections in node order
+__global__ void __launch_bounds__(256) k_sba_point(const double* __restrict__ nm, const double* __restrict__ nodes,
+                                                   const double* __restrict__ pts, const int* __restrict__ poff,
+                                                   const int* __restrict__ pnode, const double* __restrict__ uv,
+                                                   int npts, SbaCamera K, double lam, double* __restrict__ prj,
+                                                   double* __restrict__ tps) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npts) return;
+  const int k0 = poff[p], k1 = poff[p + 1];
+  if (k1 == k0) return;
+  const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+  double Hpp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bp[3] = {0, 0, 0};
+  for (int k = k0; k < k1; ++k) {
+    const int n = pnode[k];
+    const double* m = nm + (size_t)kSbaNM * n;
+    const double* w2n = m;
+    double e[2];
+    sba_error(m + 12, X, uv + 2 * k, e);
+    const double px = w2n[0] * X[0] + w2n[1] * X[1] + w2n[2] * X[2] + w2n[3];
+    const double py = w2n[4] * X[0] + w2n[5] * X[1] + w2n[6] * X[2] + w2n[7];
+    const double pz = w2n[8] * X[0] + w2n[9] * X[1] + w2n[10] * X[2] + w2n[11];
+    const double ipz2 = 1.0 / (pz * pz);
+    const double ipz2fx = ipz2 * K.fx, ipz2fy = ipz2 * K.fy;
+    const double* t = nodes + 7 * n;
+    const double pwt[3] = {X[0] - t[0], X[1] - t[1], X[2] - t[2]};
+    double jc[2][6], jp[2][3];
+    for (int a = 0; a < 3; ++a) {
+      const double* D = m + 24 + 9 * a;
+      const double d0 = D[0] * pwt[0] + D[1] * pwt[1] + D[2] * pwt[2];
+      const double d1 = D[3] * pwt[0] + D[4] * pwt[1] + D[5] * pwt[2];
+      const double d2 = D[6] * pwt[0] + D[7] * pwt[1] + D[8] * pwt[2];
+      jc[0][3 + a] = (pz * d0 - px * d2) * ipz2fx;
+      jc[1][3 + a] = (pz * d1 - py * d2) * ipz2fy;
+    }
+    for (int a = 0; a < 3; ++a) {
+      const double d0 = w2n[a], d1 = w2n[4 + a], d2 = w2n[8 + a];
+      jc[0][a] = (pz * -d0 - px * -d2) * ipz2fx;
+      jc[1][a] = (pz * -d1 - py * -d2) * ipz2fy;
+      jp[0][a] = (pz * d0 - px * d2) * ipz2fx;
+      jp[1][a] = (pz * d1 - py * d2) * ipz2fy;
+    }
+    double* o = prj + (size_t)kSbaPR * k;
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) o[6 * r + c] = jc[0][r] * jc[0][c] + jc[1][r] * jc[1][c];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 6; ++c) o[36 + 6 * r + c] = jp[0][r] * jc[0][c] + jp[1][r] * jc[1][c];
+    for (int r = 0; r < 6; ++r) o[72 + r] = jc[0][r] * e[0] + jc[1][r] * e[1];
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) Hpp[3 * r + c] += jp[0][r] * jp[0][c] + jp[1][r] * jp[1][c];
+      bp[r] -= jp[0][r] * e[0] + jp[1][r] * e[1];
+    }
+  }
+  Hpp[0] *= lam; Hpp[4] *= lam; Hpp[8] *= lam;
+  // Eigen's 3 x 3 cofactor inverse
+  double c[9];
+  c[0] = Hpp[4] * Hpp[8] - Hpp[5] * Hpp[7]; c[1] = Hpp[2] * Hpp[7] - Hpp[1] * Hpp[8]; c[2] = Hpp[1] * Hpp[5] - Hpp[2] * Hpp[4];
+  c[3] = Hpp[5] * Hpp[6] - Hpp[3] * Hpp[8]; c[4] = Hpp[0] * Hpp[8] - Hpp[2] * Hpp[6]; c[5] = Hpp[2] * Hpp[3] - Hpp[0] * Hpp[5];
+  c[6] = Hpp[3] * Hpp[7] - Hpp[4] * Hpp[6]; c[7] = Hpp[1] * Hpp[6] - Hpp[0] * Hpp[7]; c[8] = Hpp[0] * Hpp[4] - Hpp[1] * Hpp[3];
+  const double det = Hpp[0] * c[0] + Hpp[1] * c[3] + Hpp[2] * c[6];
+  double Hi[9];
+  for (int q = 0; q < 9; ++q) Hi[q] = c[q] / det;
+  double tp[3];
+  for (int r = 0; r < 3; ++r) tp[r] = Hi[3 * r] * bp[0] + Hi[3 * r + 1] * bp[1] + Hi[3 * r + 2] * bp[2];
+  tps[3 * p] = tp[0]; tps[3 * p + 1] = tp[1]; tps[3 * p + 2] = tp[2];
+  for (int k = k0; k < k1; ++k) {
+    if (pnode[k] == 0) continue;                                          // node 0 is fixed
+    double* o = prj + (size_t)kSbaPR * k;
+    const double* Hpc = o + 36;
+    for (int r = 0; r < 6; ++r)
+      for (int q = 0; q < 3; ++q)
+        o[54 + 3 * r + q] = Hpc[r] * Hi[q] + Hpc[6 + r] * Hi[3 + q] + Hpc[12 + r] * Hi[6 + q];
+  }
+}
+
+// B_a = -sum (JcTE + Hpc^T tp) over the camera's projections in point order: one thread per (camera, row)
+__global__ void __launch_bounds__(256) k_sba_rhs(const int* __restrict__ coff, const int* __restrict__ cprj,
+                                                 const int* __restrict__ ppoint, const double* __restrict__ prj,
+                                                 const double* __restrict__ tps, int nfree, double* __restrict__ B) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= 6 * nfree) return;
+  const int a = g / 6, r = g % 6;
+  double b = 0.0;
+  for (int i = coff[a]; i < coff[a + 1]; ++i) {
+    const int k = cprj[i];
+    const double* o = prj + (size_t)kSbaPR * k;
+    const double* tp = tps + 3 * ppoint[k];
+    b -= o[72 + r];
+    b -= o[36 + r] * tp[0] + o[42 + r] * tp[1] + o[48 + r] * tp[2];
+  }
+  B[g] = b;
+}
+
+// A_ab = sum over the pair's (proj_a, proj_b) list in point order of [Hcc if a == b] - T_a Hpc_b.  One workgroup of 64
+// per pair, 36 lanes; a diagonal pair computes its upper triangle (as the reference stores it) and mirrors it.
+__global__ void __launch_bounds__(64) k_sba_pairs(const int* __restrict__ pair_ab, const int* __restrict__ pair_off,
+                                                  const int* __restrict__ items, const double* __restrict__ prj,
+                                                  double* __restrict__ A, int lda) {
+  const int pr = blockIdx.x, t = threadIdx.x;
+  if (t >= 36) return;
+  const int a = pair_ab[2 * pr], b = pair_ab[2 * pr + 1];
+  const int r = t / 6, c = t % 6;
+  const bool diag = (a == b);
+  if (diag && r > c) return;
+  double acc = 0.0;
+  for (int i = pair_off[pr]; i < pair_off[pr + 1]; ++i) {
+    const double* oa = prj + (size_t)kSbaPR * items[2 * i];
+    const double* ob = prj + (size_t)kSbaPR * items[2 * i + 1];
+    if (diag) acc += oa[6 * r + c];
+    const double m = oa[54 + 3 * r] * ob[36 + c] + oa[54 + 3 * r + 1] * ob[42 + c] + oa[54 + 3 * r + 2] * ob[48 + c];
+    acc += -m;
+  }
+  A[(size_t)(6 * a + r) * lda + 6 * b + c] = acc;
+  A[(size_t)(6 * b + c) * lda + 6 * a + r] = acc;
+}
+
+// diagonal: *= lam (csparse.cpp:279); identity for a projection-less free node (deviation 1) and for the padding
+__global__ void __launch_bounds__(256) k_sba_diag(double* __restrict__ A, int lda, int n6, int npad,
+                                                  const int* __restrict__ empty, double lam) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npad) return;
+  double* d = A + (size_t)i * lda + i;
+  if (i >= n6 || empty[i / 6]) *d = 1.0;
+  else *d = *d * lam;
+}
+
+// L L^T x = b for the lower factor L (row-major, ld), one workgroup: column-oriented forward substitution, then
+// the transposed solve on the same LDS vector.  Every element is updated in a fixed order.  The finished element j
+// is written back at step j + 1 (after the barrier), so no thread reads a value another one is changing.
+__global__ void __launch_bounds__(1024) k_sba_trsv(const double* __restrict__ L, int ld, int n,
+                                                   const double* __restrict__ b, double* __restrict__ x) {
+  __shared__ double y[kSbaMaxN];
+  const int tid = threadIdx.x, NT = blockDim.x;
+  for (int i = tid; i < n; i += NT) y[i] = b[i];
+  double prev = 0.0;
+  for (int j = 0; j < n; ++j) {
+    __syncthreads();
+    if (tid == 0 && j > 0) y[j - 1] = prev;
+    const double yj = y[j] / L[(size_t)j * ld + j];
+    prev = yj;
+    for (int i = j + 1 + tid; i < n; i += NT) y[i] -= L[(size_t)i * ld + j] * yj;
+  }
+  __syncthreads();
+  if (tid == 0 && n > 0) y[n - 1] = prev;
+  for (int j = n - 1; j >= 0; --j) {
+    __syncthreads();
+    if (tid == 0 && j < n - 1) y[j + 1] = prev;
+    const double xj = y[j] / L[(size_t)j * ld + j];
+    prev = xj;
+    const double* Lj = L + (size_t)j * ld;
+    for (int i = tid; i < j; i += NT) y[i] -= Lj[i] * xj;
+  }
+  __syncthreads();
+  if (tid == 0 && n > 0) y[0] = prev;
+  __syncthreads();
+  for (int i = tid; i < n; i += NT) x[i] = y[i];
+}
+
+// r = B - A x with the unfactored A: one wave per row, lane-strided partial sums and a fixed-shape tree
+__global__ void __launch_bounds__(256) k_sba_resid(const double* __restrict__ A, int lda, int n,
+                                                   const double* __restrict__ x, const double* __restrict__ B,
+                                                   double* __restrict__ r) {
+  __shared__ double s[256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  double acc = 0.0;
+  if (row < n) {
+    const double* Ar = A + (size_t)row * lda;
+    for (int k = lane; k < n; k += 64) acc += Ar[k] * x[k];
+  }
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if (lane < w) s[threadIdx.x] += s[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (lane == 0 && row < n) r[row] = B[row] - s[threadIdx.x];
+}
+
+// x += dx and |x|^2 (one workgroup, fixed-order tree)
+__global__ void __launch_bounds__(256) k_sba_refine(double* __restrict__ x, const double* __restrict__ dx, int n,
+                                                    SbaResult* __restrict__ res) {
+  __shared__ double s[256];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int i = tid; i < n; i += 256) {
+    const double v = x[i] + dx[i];
+    x[i] = v;
+    acc += v * v;
+  }
+  s[tid] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) s[tid] += s[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) res->x2 = s[0];
+}
+
+__device__ __forceinline__ bool sba_skip_update(const SbaResult* res) {
+  return res->status != 0 || res->x2 < 1e-16;            // converged (sba.cpp:1425-1432) or a failed factor
+}
+
+// camera update (sba.cpp:1435-1466): trans += x[0:3]; qrot = normalize(qrot * (x[3:6], sqrt(1 - |x[3:6]|^2)))
+__global__ void __launch_bounds__(256) k_sba_update_nodes(double* __restrict__ nodes, double* __restrict__ old, int nn,
+                                                          const double* __restrict__ x, const SbaResult* __restrict__ res) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn || sba_skip_update(res)) return;
+  double* nd = nodes + 7 * i;
+  for (int k = 0; k < 7; ++k) old[7 * i + k] = nd[k];
+  if (i == 0) return;                                     // node 0 is fixed
+  const double* d = x + 6 * (i - 1);
+  nd[0] += d[0]; nd[1] += d[1]; nd[2] += d[2];
+  const double vx = d[3], vy = d[4], vz = d[5];
+  const double vw = sqrt(1.0 - (vx * vx + vy * vy + vz * vz));
+  const double w = nd[3], qx = nd[4], qy = nd[5], qz = nd[6];
+  double q[4] = {w * vw - qx * vx - qy * vy - qz * vz,
+                 w * vx + qx * vw + qy * vz - qz * vy,
+                 w * vy + qy * vw + qz * vx - qx * vz,
+                 w * vz + qz * vw + qx * vy - qy * vx};
+  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int k = 0; k < 4; ++k) nd[3 + k] = q[k] / nrm;
+}
+
+// point update (sba.cpp:1468-1490): X += tp - sum_free T_a^T x_a, node order
+__global__ void __launch_bounds__(256) k_sba_update_points(double* __restrict__ pts, double* __restrict__ old, int npts,
+                                                           const double* __restrict__ tps, const int* __restrict__ poff,
+                                                           const int* __restrict__ pnode, const double* __restrict__ prj,
+                                                           const double* __restrict__ x,
+                                                           const SbaResult* __restrict__ res) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npts || sba_skip_update(res)) return;
+  double* X = pts + 3 * p;
+  old[3 * p] = X[0]; old[3 * p + 1] = X[1]; old[3 * p + 2] = X[2];
+  const int k0 = poff[p], k1 = poff[p + 1];
+  if (k1 == k0) return;
+  double tp[3] = {tps[3 * p], tps[3 * p + 1], tps[3 * p + 2]};
+  for (int k = k0; k < k1; ++k) {
+    const int n = pnode[k];
+    if (n == 0) continue;
+    const double* T = prj + (size_t)kSbaPR * k + 54;     // Tpc, 6 x 3
+    const double* d = x + 6 * (n - 1);
+    for (int q = 0; q < 3; ++q) {
+      const double v = T[q] * d[0] + T[3 + q] * d[1] + T[6 + q] * d[2] + T[9 + q] * d[3] + T[12 + q] * d[4] +
+                       T[15 + q] * d[5];
+      tp[q] -= v;
+    }
+  }
+  X[0] += tp[0]; X[1] += tp[1]; X[2] += tp[2];
+}
+
+// cost, pass 1: one projection per thread, a fixed tree per workgroup -> (sum, sum with e^2 < d2, count) partials
+__global__ void __launch_bounds__(256) k_sba_cost(const double* __restrict__ nm, const double* __restrict__ pts,
+                                                  const int* __restrict__ pnode, const int* __restrict__ ppoint,
+                                                  const double* __restrict__ uv, int nprj, double d2,
+                                                  double* __restrict__ part) {
+  __shared__ double s[3][256];
+  const int tid = threadIdx.x, k = blockIdx.x * 256 + tid;
+  double e2 = 0.0, ein = 0.0, cin = 0.0;
+  if (k < nprj) {
+    double e[2];
+    sba_error(nm + (size_t)kSbaNM * pnode[k] + 12, pts + 3 * ppoint[k], uv + 2 * k, e);
+    e2 = e[0] * e[0] + e[1] * e[1];
+    if (e2 < d2) { ein = e2; cin = 1.0; }
+  }
+  s[0][tid] = e2; s[1][tid] = ein; s[2][tid] = cin;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) { s[0][tid] += s[0][tid + w]; s[1][tid] += s[1][tid + w]; s[2][tid] += s[2][tid + w]; }
+    __syncthreads();
+  }
+  if (tid == 0) { part[3 * blockIdx.x] = s[0][0]; part[3 * blockIdx.x + 1] = s[1][0]; part[3 * blockIdx.x + 2] = s[2][0]; }
+}
+
+// cost, pass 2: one workgroup sums the partials (strided, then the same fixed tree)
+__global__ void __launch_bounds__(256) k_sba_cost_final(const double* __restrict__ part, int nblk,
+                                                        SbaResult* __restrict__ res) {
+  __shared__ double s[3][256];
+  const int tid = threadIdx.x;
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int i = tid; i < nblk; i += 256) { a += part[3 * i]; b += part[3 * i + 1]; c += part[3 * i + 2]; }
+  s[0][tid] = a; s[1][tid] = b; s[2][tid] = c;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) { s[0][tid] += s[0][tid + w]; s[1][tid] += s[1][tid + w]; s[2][tid] += s[2][tid + w]; }
+    __syncthreads();
+  }
+  if (tid == 0) { res->cost = s[0][0]; res->cost_in = s[1][0]; res->n_in = s[2][0]; }
+}
+
+// Blocked right-looking Cholesky of the lower triangle of the n x n (n % 64 == 0) row-major A in place, with the
+// filter's fp64 chain kernels: per 64-column step the packed diagonal factor (and its inverse in Dinv), the panel
+// P <- P Linv^T, and the lower tiles of the trailing update.  A non-positive pivot sets status[0].
+inline void sba_chol_f64(double* A, int ld, int n, double* Dinv, int* status, hipStream_t st) {
+  for (int j = 0; j < n; j += 64) {
+    k_chol_diag_packed_f64<<<1, 512, 0, st>>>(A + (size_t)j * ld + j, ld, Dinv, status, 4);
+    const int r0 = j + 64, rows = n - r0;
+    if (rows <= 0) break;
+    double* P = A + (size_t)r0 * ld + j;
+    k_panel_direct_f64<<<(rows + 63) / 64, 256, 0, st>>>(P, ld, Dinv, rows);
+    GemmArgs g{P, ld, P, ld, A + (size_t)r0 * ld + r0, ld, 64, -1.0, 1.0, 1, r0, r0, 0, 0,
+               nullptr, 0, nullptr, 0, 0, 0};
+    k_gemm_mfma_f64<ROLE_TRAILING, false><<<dim3(rows / 64, rows / 64), 256, 0, st>>>(g);
+  }
+}
+
+}  // namespace ekf

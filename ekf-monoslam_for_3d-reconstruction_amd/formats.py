@@ -104,6 +104,62 @@ def read_camera_covs(path_or_file) -> np.ndarray:
     return vals.reshape(-1, 7, 7)
 
 
+def write_points_out(path_or_file, xyz) -> None:
+    """Points_Out.txt of sba_add (sba_add.cpp:324-336): ``PointsOut << All_points << '\\n'``, one x y z row per point."""
+    a = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    _write(path_or_file, format_eigen(a) + "\n")
+
+
+def read_points_out(path_or_file) -> np.ndarray:
+    vals = np.array(_read(path_or_file).split(), dtype=np.float64)
+    if vals.size % 3:
+        raise ValueError("Points_Out.txt does not hold rows of 3 numbers")
+    return vals.reshape(-1, 3)
+
+
+def write_nodes_out(path_or_file, ids, pose7) -> None:
+    """Nodes_Out.txt of sba_add (sba_add.cpp:339-356): per node ``P<id>``, the 3 x 1 centre, then w x y z of the
+    normalised quaternion, one per line."""
+    poses = np.asarray(pose7, dtype=np.float64).reshape(-1, 7)
+    out = []
+    for pid, p in zip(ids, poses):
+        q = p[3:7] / np.sqrt(float(p[3:7] @ p[3:7]))
+        out.append("P%d\n%s\n%s\n" % (int(pid), format_eigen(p[:3]), "\n".join(_coeff(v, 6) for v in q)))
+    _write(path_or_file, "".join(out))
+
+
+def read_nodes_out(path_or_file):
+    """Parse Nodes_Out.txt: (ids, N x 7 poses (x y z qw qx qy qz))."""
+    lines = [ln for ln in _read(path_or_file).splitlines() if ln.strip()]
+    if len(lines) % 8:
+        raise ValueError("Nodes_Out.txt records are 8 lines")
+    ids, poses = [], []
+    for i in range(0, len(lines), 8):
+        if not lines[i].startswith("P"):
+            raise ValueError("record must start with P<id>: %r" % lines[i])
+        ids.append(int(lines[i][1:]))
+        poses.append([float(lines[i + 1 + k]) for k in range(7)])
+    return ids, np.array(poses, dtype=np.float64).reshape(-1, 7)
+
+
+def point4sba_rows(real_index, in_innovation, coding, center) -> np.ndarray:
+    """The ``Point4sba`` rows of mono-slam vslamRansac.cpp:1319-1336 (commented out in the reference, the only producer
+    the nodes_and_prjcts.txt projections were designed for), from the per-feature getters: features in innovation and
+    XYZ-coded (coding 1), ``(real_index, (int) z.x, (int) z.y)`` with z the track centre.  Row 0 is (re)written while
+    its first entry is 0 (``if (Point4sba(0) == 0)``); every later row must satisfy ``u < 640 && v < 480``.  No feature:
+    the single ``0 0 0`` row, which a key-frame record writes as "no projection"."""
+    rows = [[0, 0, 0]]
+    for ri, inn, cod, c in zip(real_index, in_innovation, coding, np.asarray(center, dtype=np.float32).reshape(-1, 2)):
+        if not (inn and int(cod) == 1):
+            continue
+        r = [int(ri), int(c[0]), int(c[1])]                       # float -> int: truncation, as the Eigen assignment
+        if rows[0][0] == 0:
+            rows[0] = r
+        elif r[1] < 640 and r[2] < 480:
+            rows.append(r)
+    return np.array(rows, dtype=np.int64).reshape(-1, 3)
+
+
 def _write(path_or_file, text: str) -> None:
     if hasattr(path_or_file, "write"):
         path_or_file.write(text)

@@ -1,0 +1,198 @@
+"""Bundle adjustment of the key-frame map on the GPU: the reference's `sba_add` step.
+
+`BundleAdjuster` binds one `ekf_sba` handle (include/ekf_monoslam.h): fp64 Levenberg-Marquardt on the reduced camera
+system, node 0 fixed, as SysSBA::doSBA (sparse_bundle_adjustment/src/sba.cpp:1312-1585).  `sba_add` is the driver
+(sba_add.cpp:71-290) over the three files the filter's node writes (`formats`), with the deviations of DESIGN.md
+§11.4.  There is no CPU fallback: without a HIP device the constructor raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import formats
+from .capi import EkfError, load_library
+
+REFERENCE_SBA_CAMERA = (2217.0187, 2217.0187, 1280.5, 960.5)     # sba_add.cpp:206-211 (fx, fy, cx, cy)
+
+
+class SbaCamera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class BundleAdjuster:
+    """One bundle-adjustment problem on the GPU (SysSBA restricted to what sba_add uses)."""
+
+    def __init__(self, camera=REFERENCE_SBA_CAMERA, capacity_nodes=256, capacity_points=65536,
+                 capacity_projections=262144, device=0):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        rc = self._lib.ekf_sba_create(C.byref(SbaCamera(*[float(c) for c in camera])), int(capacity_nodes),
+                                      int(capacity_points), int(capacity_projections), int(device), C.byref(self._h))
+        if rc:
+            raise EkfError(rc, self._lib.ekf_sba_last_error(None).decode())
+        self.camera = tuple(float(c) for c in camera)
+
+    def close(self):
+        if self._h:
+            self._lib.ekf_sba_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc:
+            raise EkfError(rc, self._lib.ekf_sba_last_error(self._h).decode())
+
+    # --- building ---------------------------------------------------------------------------------------
+    def add_nodes(self, pose7):
+        """Rows (x y z qw qx qy qz); returns the index of the first new node."""
+        a = np.ascontiguousarray(np.asarray(pose7, dtype=np.float64).reshape(-1, 7))
+        first = self.counts()[0]
+        self._check(self._lib.ekf_sba_add_nodes(self._h, a.shape[0], _ptr(a)))
+        return first
+
+    def add_points(self, xyz):
+        a = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+        first = self.counts()[1]
+        self._check(self._lib.ekf_sba_add_points(self._h, a.shape[0], _ptr(a)))
+        return first
+
+    def add_projections(self, node, point, uv):
+        """Returns the number of new (node, point) pairs (a repeat keeps the first keypoint)."""
+        n = np.ascontiguousarray(np.asarray(node, dtype=np.int32).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(point, dtype=np.int32).reshape(-1))
+        m = np.ascontiguousarray(np.asarray(uv, dtype=np.float64).reshape(-1, 2))
+        if not (n.size == p.size == m.shape[0]):
+            raise ValueError("node, point and uv must have the same length")
+        added = C.c_int()
+        self._check(self._lib.ekf_sba_add_projections(self._h, n.size, _ptr(n), _ptr(p), _ptr(m), C.byref(added)))
+        return added.value
+
+    def counts(self):
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self._lib.ekf_sba_counts(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    # --- solving --------------------------------------------------------------------------------------------
+    def run(self, niter=10, lam=1e-4):
+        """SysSBA::doSBA(niter, lam): the iteration count, -1 for an empty problem."""
+        it = C.c_int()
+        self._check(self._lib.ekf_sba_run(self._h, int(niter), float(lam), C.byref(it)))
+        return it.value
+
+    def cost(self, dist=10000.0):
+        """(calcCost, calcRMSCost(dist))."""
+        sq, rms = C.c_double(), C.c_double()
+        self._check(self._lib.ekf_sba_cost(self._h, float(dist), C.byref(sq), C.byref(rms)))
+        return sq.value, rms.value
+
+    def rms_cost(self, dist=10000.0):
+        return self.cost(dist)[1]
+
+    def nodes(self):
+        out = np.zeros((self.counts()[0], 7))
+        self._check(self._lib.ekf_sba_get_nodes(self._h, _ptr(out)))
+        return out
+
+    def points(self):
+        out = np.zeros((self.counts()[1], 3))
+        self._check(self._lib.ekf_sba_get_points(self._h, _ptr(out)))
+        return out
+
+    def log(self):
+        """Per iteration of the last run: cost before, cost after, lambda after, accepted, |x|^2."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_get_log(self._h, 0, None, C.byref(n)))
+        out = np.zeros((n.value, 5))
+        self._check(self._lib.ekf_sba_get_log(self._h, n.value, _ptr(out), C.byref(n)))
+        return out
+
+    def profile(self, enable=True):
+        self._check(self._lib.ekf_sba_profile(self._h, 1 if enable else 0))
+
+    def get_profile(self):
+        """(ms per phase: prep, Schur, assemble, factor + solve, update + cost; ms per iteration)."""
+        ph = np.zeros(5)
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_get_profile(self._h, _ptr(ph), 0, None, C.byref(n)))
+        it = np.zeros(n.value)
+        self._check(self._lib.ekf_sba_get_profile(self._h, _ptr(ph), n.value, _ptr(it), C.byref(n)))
+        return ph, it
+
+    def rms_wrapper(self):
+        """SBANode::doSBA (sba_add.cpp:259-290): doSBA(10, 1e-4), and more while the RMS stays above 4 px."""
+        if self.counts()[0] == 0:
+            return
+        self.run(10, 1e-4)
+        c = self.rms_cost()
+        if math.isnan(c) or math.isinf(c):
+            return
+        if self.rms_cost() > 4.0:
+            self.run(10, 1e-4)
+        if self.rms_cost() > 4.0:
+            self.run(15, 1e-4)
+
+
+def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA, every=10, points_out=None,
+            nodes_out=None, device=0):
+    """The reference's sba_add driver on the GPU.
+
+    `points`, `nodes_and_prjcts`, `cams_cov`: paths or file objects of the filter's three files (formats.py), or
+    already parsed values (an N x 12 table; a list of (id, pose7, projections); cams_cov is read for its shape
+    only -- the reference computes projection covariances from it but never uses them, usecovariance = false).
+    Node and point values pass through float32, as sba_add reads them (sba_add.cpp:83-86).  After every `every`-th
+    node and once at the end the RMS wrapper runs.  Deviations: points.txt row 0 is an ordinary
+    point, a `0  0  0` projection line means no projection, `P0` is a node id.
+
+    Limit (deviation 4): at most 1024 key-frame records, the largest reduced system the
+    single-workgroup triangular solve holds; more raise EkfError (EKF_ERR_ARG) when the handle is created.
+
+    Returns (table, nodes, ids): the refined N x 3 table (rows of points that were never added -- all-zero ones --
+    stay zero), the refined nodes (x y z qw qx qy qz) and their ids.  Writes Points_Out.txt / Nodes_Out.txt when
+    `points_out` / `nodes_out` are given.
+    """
+    table = points if isinstance(points, np.ndarray) else formats.read_points(points)
+    table = np.asarray(table, dtype=np.float32)
+    records = nodes_and_prjcts if isinstance(nodes_and_prjcts, list) else formats.read_pose_records(nodes_and_prjcts)
+    if cams_cov is not None and not isinstance(cams_cov, np.ndarray):
+        formats.read_camera_covs(cams_cov)
+    rows = [i for i in range(table.shape[0]) if table[i, 0] or table[i, 1] or table[i, 2]]
+    row_of = {r: k for k, r in enumerate(rows)}
+    nproj = sum(len(r[2]) for r in records)
+    ba = BundleAdjuster(camera, capacity_nodes=max(len(records), 1), capacity_points=max(len(rows), 1),
+                        capacity_projections=max(nproj, 1), device=device)
+    if rows:
+        ba.add_points(table[rows, :3].astype(np.float64))
+    ids = []
+    for pid, pose, prj in records:
+        ni = ba.add_nodes(np.asarray(pose, dtype=np.float32).astype(np.float64).reshape(1, 7))
+        ids.append(int(pid))
+        sel = [(row_of[int(ri)], float(int(u)), float(int(v))) for ri, u, v in np.asarray(prj).reshape(-1, 3)
+               if not (ri == 0 and u == 0 and v == 0) and int(ri) in row_of]
+        if sel:
+            s = np.array(sel)
+            ba.add_projections(np.full(len(sel), ni), s[:, 0].astype(np.int32), s[:, 1:])
+        if every and (ni + 1) % every == 0:
+            ba.rms_wrapper()
+    ba.rms_wrapper()
+    out = np.zeros((table.shape[0], 3))
+    if rows:
+        out[rows] = ba.points()
+    nodes = ba.nodes()
+    if points_out is not None:
+        formats.write_points_out(points_out, ba.points())
+    if nodes_out is not None:
+        formats.write_nodes_out(nodes_out, ids, nodes)
+    ba.close()
+    return out, nodes, ids

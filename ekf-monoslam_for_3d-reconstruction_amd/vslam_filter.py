@@ -271,6 +271,15 @@ class VSlamFilter:
         self._check(self._lib.ekf_get_feature_track(self._h, self._ptr(nt), self._ptr(inn), self._ptr(cen), self._ptr(rem)))
         return nt, inn.astype(bool), cen, rem.astype(bool)
 
+    def keyframeProjections(self):
+        """``Point4sba`` (mono-slam vslamRansac.cpp:1319-1336): the (real_index, u, v) rows a key-frame record of
+        nodes_and_prjcts.txt carries, built from the feature getters by ``formats.point4sba_rows``."""
+        from .formats import point4sba_rows
+        ri, _ = self.featureIds()
+        _, inn, cen, _ = self.featureTrack()
+        _, cod = self.featureLayout()
+        return point4sba_rows(ri, inn, cod, cen)
+
     def setFeatureTrack(self, index: int, n_tot: int = -1, in_innovation: int = -1, center=None, remove_flag: int = -1):
         """For callers that run their own matcher: a negative value (center None) leaves that field alone."""
         c = None if center is None else np.ascontiguousarray(center, np.float32).reshape(2)

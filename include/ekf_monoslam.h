@@ -527,6 +527,45 @@ int ekf_shard_rebalance(ekf_filter* f);
 void* ekf_device_mu(ekf_filter* f);
 void* ekf_device_sigma(ekf_filter* f, int* ld);
 
+/* ---- bundle adjustment of the key-frame map --------------------------------------------------
+ * The reference's sparse_bundle_adjustment as sba_add drives it (SysSBA, sba.cpp): monocular projections, node 0
+ * fixed, Levenberg-Marquardt on the reduced camera system, fp64.  One handle = one problem on its own stream.
+ *  - nodes: (x y z qw qx qy qz), camera centre and attitude, normalised on add as Node::normRot (node.cpp:52-66);
+ *  - points: (x y z) world;  projections: (node, point, u v).  A repeat of a (node, point) pair keeps the first
+ *    keypoint (addMonoProj, sba.cpp:133-143); `added` (may be NULL) receives the number of new pairs;
+ *  - arguments are checked before the device is touched: EKF_ERR_ARG for bad indices or non-finite values,
+ *    EKF_ERR_CAPACITY beyond a capacity (the call then adds nothing);  capacity_nodes <= 1024;
+ *  - ekf_sba_run = SysSBA::doSBA(niter, lambda): *iterations = the iteration count, -1 for an empty problem;
+ *    lambda > 0 sets the LM damping, otherwise the last run's value continues (initially 1e-4).  A non-positive
+ *    pivot other than a projection-less free node (whose step is 0) is EKF_ERR_NUMERIC: the nodes and points stay
+ *    at the last accepted iterate, *iterations = the iterations completed before it (the log holds their rows);
+ *  - ekf_sba_cost: calcCost (sum of squared errors) and calcRMSCost(dist) (sba.cpp:289-360);
+ *  - ekf_sba_get_log: per iteration of the last run, 5 doubles: cost before, cost after the step, lambda after,
+ *    accepted (1 / 0), |x|^2;  *n = the number of rows (at most max_rows are written);
+ *  - ekf_sba_profile / ekf_sba_get_profile: HIP-event milliseconds per phase (prep, Schur, assemble,
+ *    factor + solve, update + cost) summed over the iterations since the last ekf_sba_profile, and per iteration. */
+typedef struct ekf_sba ekf_sba;
+typedef struct ekf_sba_camera {
+  double fx, fy, cx, cy;
+} ekf_sba_camera;
+
+int ekf_sba_create(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
+                   int device, ekf_sba** out);
+void ekf_sba_destroy(ekf_sba* s);
+/* Message of the last failure (s may be NULL: last failure of ekf_sba_create). */
+const char* ekf_sba_last_error(const ekf_sba* s);
+int ekf_sba_add_nodes(ekf_sba* s, int n, const double* pose7);
+int ekf_sba_add_points(ekf_sba* s, int n, const double* xyz);
+int ekf_sba_add_projections(ekf_sba* s, int n, const int* node, const int* point, const double* uv, int* added);
+int ekf_sba_counts(const ekf_sba* s, int* nodes, int* points, int* projections);
+int ekf_sba_run(ekf_sba* s, int niter, double lambda, int* iterations);
+int ekf_sba_cost(ekf_sba* s, double dist, double* sq_cost, double* rms);
+int ekf_sba_get_nodes(const ekf_sba* s, double* pose7);
+int ekf_sba_get_points(const ekf_sba* s, double* xyz);
+int ekf_sba_get_log(const ekf_sba* s, int max_rows, double* rows, int* n);
+int ekf_sba_profile(ekf_sba* s, int enable);
+int ekf_sba_get_profile(const ekf_sba* s, double* phase_ms, int max_iters, double* iter_ms, int* n);
+
 #ifdef __cplusplus
 }
 #endif

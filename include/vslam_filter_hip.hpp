@@ -165,6 +165,31 @@ class VSlamFilterHip {
     return removed;
   }
 
+  // Point4sba (mono-slam vslamRansac.cpp:1319-1336): (real_index, (int) z.x, (int) z.y) of the features in innovation
+  // and XYZ-coded, z the track centre; row 0 is (re)written while its first entry is 0, every later row needs
+  // u < 640 && v < 480; no feature: the single row 0 0 0.  3 ints per row, as formats.point4sba_rows.
+  std::vector<int> keyframeProjections() {
+    std::vector<int> ri, nf, nt, pos, cod;
+    std::vector<unsigned char> inn, rem;
+    std::vector<float> cen;
+    featureIds(ri, nf);
+    featureTrack(nt, inn, cen, rem);
+    pos.assign(ri.size(), 0);
+    cod.assign(ri.size(), 0);
+    check(ekf_get_feature_layout(h_, pos.data(), cod.data()));
+    std::vector<int> rows(3, 0);
+    for (size_t i = 0; i < ri.size(); ++i) {
+      if (!inn[i] || cod[i] != 1) continue;
+      const int r[3] = {ri[i], (int)cen[2 * i], (int)cen[2 * i + 1]};
+      if (rows[0] == 0) {
+        rows[0] = r[0]; rows[1] = r[1]; rows[2] = r[2];
+      } else if (r[1] < 640 && r[2] < 480) {
+        rows.insert(rows.end(), r, r + 3);
+      }
+    }
+    return rows;
+  }
+
   std::vector<float> getState() {              // VectorXf(14), vR.cpp:135-140
     std::vector<float> s(STATE_DIM);
     check(ekf_get_state(h_, s.data(), 0, STATE_DIM));
@@ -203,4 +228,55 @@ class VSlamFilterHip {
   int count(int rc) { if (rc < 0) throw std::runtime_error(ekf_last_error(h_)); return rc; }
   ekf_filter* h_ = nullptr;
   double old_ts_ = -1;   // vR.cpp:145
+};
+
+// SysSbaHip -- header-only mirror of the part of the reference's `sba::SysSBA` (sparse_bundle_adjustment/include/
+// sparse_bundle_adjustment/sba.h) that sba_add drives, over the ekf_sba_* functions of ekf_monoslam.h: monocular
+// projections, node 0 fixed, doSBA with the CHOLMOD solve, calcCost / calcRMSCost.  Poses are
+// (x y z qw qx qy qz), points (x y z), as plain double arrays.
+class SysSbaHip {
+ public:
+  explicit SysSbaHip(double fx, double fy, double cx, double cy, int capacity_nodes = 256,
+                     int capacity_points = 65536, int capacity_projections = 262144, int device = 0) {
+    const ekf_sba_camera K = {fx, fy, cx, cy};
+    if (ekf_sba_create(&K, capacity_nodes, capacity_points, capacity_projections, device, &h_) != EKF_OK)
+      throw std::runtime_error(std::string("ekf_sba_create: ") + ekf_sba_last_error(nullptr));
+  }
+  ~SysSbaHip() { ekf_sba_destroy(h_); }
+  SysSbaHip(const SysSbaHip&) = delete;
+  SysSbaHip& operator=(const SysSbaHip&) = delete;
+
+  // addNode (sba.cpp:83-100): returns the node index
+  int addNode(const double pose7[7]) { const int i = counts(0); check(ekf_sba_add_nodes(h_, 1, pose7)); return i; }
+  // addPoint: returns the point index
+  int addPoint(const double xyz[3]) { const int i = counts(1); check(ekf_sba_add_points(h_, 1, xyz)); return i; }
+  // addMonoProj (sba.cpp:133-143): false when the (node, point) pair is already there
+  bool addMonoProj(int ci, int pi, const double uv[2]) {
+    int added = 0;
+    check(ekf_sba_add_projections(h_, 1, &ci, &pi, uv, &added));
+    return added == 1;
+  }
+  // doSBA(niter, sLambda): the iteration count, -1 for an empty problem
+  int doSBA(int niter, double sLambda = 1.0e-4) {
+    int it = 0;
+    check(ekf_sba_run(h_, niter, sLambda, &it));
+    return it;
+  }
+  double calcCost() { double c = 0, r = 0; check(ekf_sba_cost(h_, 10000.0, &c, &r)); return c; }
+  double calcRMSCost(double dist = 10000.0) { double c = 0, r = 0; check(ekf_sba_cost(h_, dist, &c, &r)); return r; }
+  std::vector<double> nodes() { std::vector<double> v(7 * (size_t)counts(0)); check(ekf_sba_get_nodes(h_, v.data())); return v; }
+  std::vector<double> points() { std::vector<double> v(3 * (size_t)counts(1)); check(ekf_sba_get_points(h_, v.data())); return v; }
+  int numNodes() { return counts(0); }
+  int numPoints() { return counts(1); }
+  int numProjections() { return counts(2); }
+  ekf_sba* handle() { return h_; }
+
+ private:
+  int counts(int which) {
+    int c[3] = {0, 0, 0};
+    check(ekf_sba_counts(h_, &c[0], &c[1], &c[2]));
+    return c[which];
+  }
+  void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_sba_last_error(h_)); }
+  ekf_sba* h_ = nullptr;
 };
