@@ -127,6 +127,14 @@ _PROTOS = {
     "ekf_sba_counts": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ekf_sba_run": (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_int)]),
     "ekf_sba_cost": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ekf_sba_set_huber": (C.c_int, [_P, C.c_double]),
+    "ekf_sba_get_huber": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "ekf_sba_count_bad": (C.c_int, [_P, C.c_double, C.POINTER(C.c_int)]),
+    "ekf_sba_remove_bad": (C.c_int, [_P, C.c_double, C.POINTER(C.c_int)]),
+    "ekf_sba_reduce_tracks": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ekf_sba_num_bad_points": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ekf_sba_avg_error": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "ekf_sba_get_projections": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "ekf_sba_get_nodes": (C.c_int, [_P, _P]),
     "ekf_sba_get_points": (C.c_int, [_P, _P]),
     "ekf_sba_get_log": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),

@@ -3873,7 +3873,14 @@ struct Filter : FilterBase {
 // Bundle adjustment of the key-frame map: host side of ekf_sba_*.  The host keeps the problem
 // (nodes, points, the (point, node)-sorted projections) and builds the index lists once per change of structure;
 // ekf_sba_run uploads the state, runs the LM loop on its own stream and reads back one SbaResult per iteration.
+// A change of validity (remove_bad, reduce_tracks) is a change of structure: the per-camera and pair lists hold
+// valid projections only, so k_sba_rhs / k_sba_pairs / k_sba_diag need no flag test.
 // ---------------------------------------------------------------------------------------
+struct SbaProj {
+  double u, v;
+  bool valid;                                                // Proj::isValid
+};
+
 struct SbaSystem {
   std::string err;
   int device = 0;
@@ -3881,8 +3888,9 @@ struct SbaSystem {
   SbaCamera K{};
   int cap_nodes = 0, cap_points = 0, cap_prj = 0;
   std::vector<double> nodes, points;                         // 7 per node (t, q w x y z), 3 per point
-  std::map<std::pair<int, int>, std::array<double, 2>> prj;  // (point, node) -> keypoint
+  std::map<std::pair<int, int>, SbaProj> prj;                // (point, node) -> keypoint, validity
   double lambda = 1e-4;                                      // kept for continuation, as SysSBA::lambda
+  double huber = 0.0;                                        // SysSBA::huber (sba.h:113), 0: plain squared error
   std::vector<double> log;                                   // 5 per iteration of the last run
   bool dirty = true;
   // profile (ekf_sba_profile): per phase and per iteration, milliseconds
@@ -3892,7 +3900,7 @@ struct SbaSystem {
   hipEvent_t ev[6] = {};
   // device
   struct Buf { void* p = nullptr; size_t bytes = 0; };
-  enum { B_NODES, B_OLDN, B_NM, B_PTS, B_OLDP, B_POFF, B_PNODE, B_PPOINT, B_UV, B_PRJ, B_TPS, B_COFF, B_CPRJ,
+  enum { B_NODES, B_OLDN, B_NM, B_PTS, B_OLDP, B_POFF, B_PNODE, B_PPOINT, B_UV, B_VALID, B_PRJ, B_TPS, B_COFF, B_CPRJ,
          B_PAIR_AB, B_PAIR_OFF, B_ITEMS, B_EMPTY, B_A, B_L, B_B, B_X, B_R, B_DX, B_DINV, B_PART, B_RES, B_COUNT };
   Buf buf[B_COUNT];
   int npairs = 0, nfree = 0, npad = 0;
@@ -3935,15 +3943,17 @@ struct SbaSystem {
     npad = (6 * nfree + 63) / 64 * 64;
     std::vector<int> poff(M + 1, 0), pnode(P), ppoint(P);
     std::vector<double> uv(2 * P);
+    std::vector<unsigned char> valid(P);
     std::vector<std::vector<int>> cam(nfree);
     int k = 0;
     for (const auto& e : prj) {
       pnode[k] = e.first.second;
       ppoint[k] = e.first.first;
-      uv[2 * k] = e.second[0];
-      uv[2 * k + 1] = e.second[1];
+      uv[2 * k] = e.second.u;
+      uv[2 * k + 1] = e.second.v;
+      valid[k] = e.second.valid ? 1 : 0;
       ++poff[e.first.first + 1];
-      if (e.first.second > 0) cam[e.first.second - 1].push_back(k);
+      if (e.second.valid && e.first.second > 0) cam[e.first.second - 1].push_back(k);
       ++k;
     }
     for (int p = 0; p < M; ++p) poff[p + 1] += poff[p];
@@ -3956,8 +3966,9 @@ struct SbaSystem {
     std::map<std::pair<int, int>, std::vector<int>> pairs;
     for (int p = 0; p < M; ++p)
       for (int i = poff[p]; i < poff[p + 1]; ++i) {
-        if (pnode[i] == 0) continue;
+        if (pnode[i] == 0 || !valid[i]) continue;
         for (int j = i; j < poff[p + 1]; ++j) {
+          if (!valid[j]) continue;
           auto& v = pairs[{pnode[i] - 1, pnode[j] - 1}];
           v.push_back(i);
           v.push_back(j);
@@ -3976,6 +3987,7 @@ struct SbaSystem {
     if ((rc = ensure(B_NODES, 7 * D * N)) || (rc = ensure(B_OLDN, 7 * D * N)) || (rc = ensure(B_NM, kSbaNM * D * N)) ||
         (rc = ensure(B_PTS, 3 * D * M)) || (rc = ensure(B_OLDP, 3 * D * M)) || (rc = ensure(B_POFF, I * (M + 1))) ||
         (rc = ensure(B_PNODE, I * P)) || (rc = ensure(B_PPOINT, I * P)) || (rc = ensure(B_UV, 2 * D * P)) ||
+        (rc = ensure(B_VALID, P)) ||
         (rc = ensure(B_PRJ, kSbaPR * D * P)) || (rc = ensure(B_TPS, 3 * D * M)) || (rc = ensure(B_COFF, I * coff.size())) ||
         (rc = ensure(B_CPRJ, I * cprj.size())) || (rc = ensure(B_PAIR_AB, I * pair_ab.size())) ||
         (rc = ensure(B_PAIR_OFF, I * pair_off.size())) || (rc = ensure(B_ITEMS, I * items.size())) ||
@@ -3990,6 +4002,7 @@ struct SbaSystem {
     };
     if ((rc = up(B_POFF, poff.data(), I * poff.size())) || (rc = up(B_PNODE, pnode.data(), I * P)) ||
         (rc = up(B_PPOINT, ppoint.data(), I * P)) || (rc = up(B_UV, uv.data(), 2 * D * P)) ||
+        (rc = up(B_VALID, valid.data(), P)) ||
         (rc = up(B_COFF, coff.data(), I * coff.size())) || (rc = up(B_CPRJ, cprj.data(), I * cprj.size())) ||
         (rc = up(B_PAIR_AB, pair_ab.data(), I * pair_ab.size())) || (rc = up(B_PAIR_OFF, pair_off.data(), I * pair_off.size())) ||
         (rc = up(B_ITEMS, items.data(), I * items.size())) || (rc = up(B_EMPTY, empty.data(), I * empty.size())))
@@ -4012,7 +4025,8 @@ struct SbaSystem {
     const int P = (int)prj.size();
     k_sba_node_prep<<<blocks(nn()), 256, 0, stream>>>(dp<double>(B_NODES), nn(), K, dp<double>(B_NM));
     k_sba_cost<<<blocks(P), 256, 0, stream>>>(dp<double>(B_NM), dp<double>(B_PTS), dp<int>(B_PNODE), dp<int>(B_PPOINT),
-                                               dp<double>(B_UV), P, dist2, dp<double>(B_PART));
+                                               dp<double>(B_UV), dp<unsigned char>(B_VALID), huber, P, dist2,
+                                               dp<double>(B_PART));
     k_sba_cost_final<<<1, 256, 0, stream>>>(dp<double>(B_PART), blocks(P), dp<SbaResult>(B_RES));
     HIPCHK(hipGetLastError());
     return EKF_OK;
@@ -4043,6 +4057,79 @@ struct SbaSystem {
     if (rms) *rms = std::sqrt(r.cost_in / r.n_in);
     return EKF_OK;
   }
+  // countBad / removeBad (sba.cpp:416-462) on the Huber-weighted error at the current nodes and points.  Marking
+  // clears the flags on the device; one copy of P bytes brings them back for the host's map and its lists.
+  int flag_bad(double dist, bool mark_them, int* n) {
+    *n = 0;
+    if (prj.empty()) return EKF_OK;
+    HIPCHK(hipSetDevice(device));
+    const int P = (int)prj.size();
+    int rc;
+    SbaResult r{};
+    if ((rc = upload_state())) return rc;
+    k_sba_node_prep<<<blocks(nn()), 256, 0, stream>>>(dp<double>(B_NODES), nn(), K, dp<double>(B_NM));
+    k_sba_flag_bad<<<blocks(P), 256, 0, stream>>>(dp<double>(B_NM), dp<double>(B_PTS), dp<int>(B_PNODE), dp<int>(B_PPOINT),
+                                                   dp<double>(B_UV), dp<unsigned char>(B_VALID), huber, P, dist * dist,
+                                                   mark_them ? 1 : 0, dp<double>(B_PART));
+    k_sba_cost_final<<<1, 256, 0, stream>>>(dp<double>(B_PART), blocks(P), dp<SbaResult>(B_RES));
+    HIPCHK(hipGetLastError());
+    if ((rc = read_result(&r))) return rc;
+    *n = (int)r.cost;
+    if (mark_them && *n > 0) {
+      std::vector<unsigned char> valid(P);
+      HIPCHK(hipMemcpyAsync(valid.data(), buf[B_VALID].p, P, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      int k = 0;
+      for (auto& e : prj) e.second.valid = valid[k++] != 0;
+      dirty = true;
+    }
+    return EKF_OK;
+  }
+  // reduceTracks (sba.cpp:467-502): erase the invalid projections; a point left with fewer than 2 loses them all
+  int reduce_tracks() {
+    const int M = np();
+    std::vector<int> good(M, 0);
+    for (auto it = prj.begin(); it != prj.end();) {
+      if (it->second.valid) {
+        ++good[it->first.first];
+        ++it;
+      } else {
+        it = prj.erase(it);
+        dirty = true;
+      }
+    }
+    int cleared = 0;
+    for (int p = 0; p < M; ++p) cleared += good[p] < 2 ? 1 : 0;
+    for (auto it = prj.begin(); it != prj.end();) {
+      if (good[it->first.first] < 2) {
+        it = prj.erase(it);
+        dirty = true;
+      } else {
+        ++it;
+      }
+    }
+    return cleared;
+  }
+  // calcAvgError and numBadPoints (sba.cpp:365-411)
+  int stats(double* avg, int* nbad) {
+    if (avg) *avg = std::nan("");
+    if (nbad) *nbad = 0;
+    if (prj.empty()) return EKF_OK;
+    HIPCHK(hipSetDevice(device));
+    const int P = (int)prj.size();
+    int rc;
+    SbaResult r{};
+    if ((rc = upload_state())) return rc;
+    k_sba_node_prep<<<blocks(nn()), 256, 0, stream>>>(dp<double>(B_NODES), nn(), K, dp<double>(B_NM));
+    k_sba_stats<<<blocks(P), 256, 0, stream>>>(dp<double>(B_NM), dp<double>(B_PTS), dp<int>(B_PNODE), dp<int>(B_PPOINT),
+                                                dp<double>(B_UV), dp<unsigned char>(B_VALID), huber, P, dp<double>(B_PART));
+    k_sba_cost_final<<<1, 256, 0, stream>>>(dp<double>(B_PART), blocks(P), dp<SbaResult>(B_RES));
+    HIPCHK(hipGetLastError());
+    if ((rc = read_result(&r))) return rc;
+    if (avg) *avg = r.cost / r.cost_in;             // 0 / 0 without a valid projection, as the reference
+    if (nbad) *nbad = (int)r.n_in;
+    return EKF_OK;
+  }
   void mark(int e) { if (profile) hipEventRecord(ev[e], stream); }
 
   // SysSBA::doSBA (sba.cpp:1312-1585)
@@ -4066,8 +4153,8 @@ struct SbaSystem {
       k_sba_node_prep<<<blocks(N), 256, 0, stream>>>(dp<double>(B_NODES), N, K, dp<double>(B_NM));
       mark(1);
       k_sba_point<<<blocks(M), 256, 0, stream>>>(dp<double>(B_NM), dp<double>(B_NODES), dp<double>(B_PTS), dp<int>(B_POFF),
-                                                  dp<int>(B_PNODE), dp<double>(B_UV), M, K, lam, dp<double>(B_PRJ),
-                                                  dp<double>(B_TPS));
+                                                  dp<int>(B_PNODE), dp<double>(B_UV), dp<unsigned char>(B_VALID), huber, M,
+                                                  K, lam, dp<double>(B_PRJ), dp<double>(B_TPS));
       mark(2);
       HIPCHK(hipMemsetAsync(buf[B_A].p, 0, sizeof(double) * npad * npad, stream));
       k_sba_rhs<<<blocks(n6), 256, 0, stream>>>(dp<int>(B_COFF), dp<int>(B_CPRJ), dp<int>(B_PPOINT), dp<double>(B_PRJ),
@@ -4088,8 +4175,8 @@ struct SbaSystem {
       k_sba_update_nodes<<<blocks(N), 256, 0, stream>>>(dp<double>(B_NODES), dp<double>(B_OLDN), N, dp<double>(B_X),
                                                          dp<SbaResult>(B_RES));
       k_sba_update_points<<<blocks(M), 256, 0, stream>>>(dp<double>(B_PTS), dp<double>(B_OLDP), M, dp<double>(B_TPS),
-                                                          dp<int>(B_POFF), dp<int>(B_PNODE), dp<double>(B_PRJ),
-                                                          dp<double>(B_X), dp<SbaResult>(B_RES));
+                                                          dp<int>(B_POFF), dp<int>(B_PNODE), dp<unsigned char>(B_VALID),
+                                                          dp<double>(B_PRJ), dp<double>(B_X), dp<SbaResult>(B_RES));
       if ((rc = launch_cost(1e300))) return rc;
       mark(5);
       if ((rc = read_result(&r))) return rc;       // the one read-back of the iteration
@@ -4479,7 +4566,7 @@ int ekf_sba_add_projections(ekf_sba* s, int n, const int* node, const int* point
   int cnt = 0;
   for (int i = 0; i < n; ++i) {
     // addMonoProj (sba.cpp:133-143): a repeat of (node, point) keeps the first keypoint
-    auto r = q->prj.emplace(std::pair<int, int>{point[i], node[i]}, std::array<double, 2>{uv[2 * i], uv[2 * i + 1]});
+    auto r = q->prj.emplace(std::pair<int, int>{point[i], node[i]}, ekf::SbaProj{uv[2 * i], uv[2 * i + 1], true});
     cnt += r.second ? 1 : 0;
   }
   if (cnt) q->dirty = true;
@@ -4515,6 +4602,84 @@ int ekf_sba_cost(ekf_sba* s, double dist, double* sq_cost, double* rms) {
     return EKF_ERR_ARG;
   }
   return s->impl->cost(dist, sq_cost, rms);
+}
+
+int ekf_sba_set_huber(ekf_sba* s, double huber) {
+  if (!s) return EKF_ERR_ARG;
+  if (!std::isfinite(huber) || huber < 0.0) {
+    s->impl->err = "ekf_sba_set_huber: huber must be finite and >= 0 (0 switches the weighting off)";
+    return EKF_ERR_ARG;
+  }
+  s->impl->huber = huber;
+  return EKF_OK;
+}
+
+int ekf_sba_get_huber(const ekf_sba* s, double* huber) {
+  if (!s || !huber) return EKF_ERR_ARG;
+  *huber = s->impl->huber;
+  return EKF_OK;
+}
+
+int ekf_sba_count_bad(ekf_sba* s, double dist, int* n) {
+  if (!s) return EKF_ERR_ARG;
+  if (!n || !(dist > 0.0)) {
+    s->impl->err = "ekf_sba_count_bad: dist must be > 0 and n not NULL";
+    return EKF_ERR_ARG;
+  }
+  return s->impl->flag_bad(dist, false, n);
+}
+
+int ekf_sba_remove_bad(ekf_sba* s, double dist, int* n) {
+  if (!s) return EKF_ERR_ARG;
+  if (!n || !(dist > 0.0)) {
+    s->impl->err = "ekf_sba_remove_bad: dist must be > 0 and n not NULL";
+    return EKF_ERR_ARG;
+  }
+  return s->impl->flag_bad(dist, true, n);
+}
+
+int ekf_sba_reduce_tracks(ekf_sba* s, int* cleared) {
+  if (!s) return EKF_ERR_ARG;
+  if (!cleared) {
+    s->impl->err = "ekf_sba_reduce_tracks: cleared must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  *cleared = s->impl->reduce_tracks();
+  return EKF_OK;
+}
+
+int ekf_sba_num_bad_points(ekf_sba* s, int* n) {
+  if (!s) return EKF_ERR_ARG;
+  if (!n) {
+    s->impl->err = "ekf_sba_num_bad_points: n must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  return s->impl->stats(nullptr, n);
+}
+
+int ekf_sba_avg_error(ekf_sba* s, double* avg) {
+  if (!s) return EKF_ERR_ARG;
+  if (!avg) {
+    s->impl->err = "ekf_sba_avg_error: avg must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  return s->impl->stats(avg, nullptr);
+}
+
+int ekf_sba_get_projections(const ekf_sba* s, int max_rows, int* node, int* point, double* uv, unsigned char* valid,
+                            int* n) {
+  if (!s || !n || max_rows < 0) return EKF_ERR_ARG;
+  *n = (int)s->impl->prj.size();
+  int k = 0;
+  for (const auto& e : s->impl->prj) {
+    if (k >= max_rows) break;
+    if (node) node[k] = e.first.second;
+    if (point) point[k] = e.first.first;
+    if (uv) { uv[2 * k] = e.second.u; uv[2 * k + 1] = e.second.v; }
+    if (valid) valid[k] = e.second.valid ? 1 : 0;
+    ++k;
+  }
+  return EKF_OK;
 }
 
 int ekf_sba_get_nodes(const ekf_sba* s, double* pose7) {

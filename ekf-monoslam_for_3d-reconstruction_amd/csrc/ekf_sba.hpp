@@ -13,6 +13,15 @@
 //   k_sba_update_*   camera and point update (skipped on the device when |x|^2 < 1e-16 or the factor failed)
 //   k_sba_node_prep  w2n, w2i, dRd* per node;  k_sba_cost / k_sba_cost_final: the cost, two fixed-order passes
 // Every sum has one fixed order (no atomics), so a run is bit-reproducible.
+//
+// Robust cost and pruning: every projection carries a `valid` byte beside its keypoint, and the
+// error of a valid projection passes through sba_huber (SysSBA::huber, proj.cpp:162-176) wherever it is used.  An
+// invalid projection is skipped by k_sba_point, k_sba_update_points and the cost; the host-built lists of k_sba_rhs /
+// k_sba_pairs / k_sba_diag hold valid projections only.  Outside the LM loop:
+//   k_sba_flag_bad   countBad / removeBad (sba.cpp:416-462): counts, and optionally clears, the valid projections with
+//                    e^2 >= dist^2
+//   k_sba_stats      calcAvgError and numBadPoints (sba.cpp:365-411)
+// both reduced by k_sba_cost_final, in the cost's fixed order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,10 +29,12 @@ namespace ekf {
 
 struct SbaCamera { double fx, fy, cx, cy; };
 
-// Device result block, read back once per LM iteration.
+// Device result block, read back once per LM iteration.  k_sba_cost_final fills (cost, cost_in, n_in) from whichever
+// first pass ran: k_sba_cost as named; k_sba_flag_bad (flagged count, 0, 0); k_sba_stats (sum |e|, valid count,
+// count of exactly-zero errors).  The counts are whole numbers below 2^53, exact in a double.
 struct SbaResult {
   double x2;          // |x|^2 of the refined step
-  double cost;        // sum of squared errors (all projections)
+  double cost;        // sum of squared errors (all valid projections)
   double cost_in;     // sum over the projections with e^2 < dist^2
   double n_in;        // their count
   int status;         // 1: a non-positive pivot
@@ -84,6 +95,22 @@ __device__ __forceinline__ void sba_error(const double* w2i, const double* X, co
   e[1] = p1 / p2 - kp[1];
 }
 
+// The pseudo-Huber weight of calcErrMono_ (proj.cpp:162-176), in its operation order: for huber > 0 and
+// e2 = |e|^2 > huber^2, e *= sqrt((2 huber sqrt(e2) - huber^2) / e2).  huber = 0 leaves e alone.  The one place the
+// weight lives: the linear system, the cost and the pruning all call it on what sba_error returned.
+__device__ __forceinline__ void sba_huber(double huber, double e[2]) {
+  if (huber > 0.0) {
+    const double b2 = huber * huber;
+    const double e2 = e[0] * e[0] + e[1] * e[1];
+    if (e2 > b2) {
+      const double c = 2.0 * huber * sqrt(e2) - b2;
+      const double w = sqrt(c / e2);
+      e[0] *= w;
+      e[1] *= w;
+    }
+  }
+}
+
 // Per projection record: Hcc (36), Hpc (18, 3 x 6), T (18, Tpc 6 x 3), JcTE (6)
 constexpr int kSbaPR = 78;
 
@@ -91,7 +118,8 @@ constexpr int kSbaPR = 78;
 __global__ void __launch_bounds__(256) k_sba_point(const double* __restrict__ nm, const double* __restrict__ nodes,
                                                    const double* __restrict__ pts, const int* __restrict__ poff,
                                                    const int* __restrict__ pnode, const double* __restrict__ uv,
-                                                   int npts, SbaCamera K, double lam, double* __restrict__ prj,
+                                                   const unsigned char* __restrict__ valid, double huber, int npts,
+                                                   SbaCamera K, double lam, double* __restrict__ prj,
                                                    double* __restrict__ tps) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npts) return;
@@ -99,12 +127,16 @@ __global__ void __launch_bounds__(256) k_sba_point(const double* __restrict__ nm
   if (k1 == k0) return;
   const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
   double Hpp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bp[3] = {0, 0, 0};
+  int nv = 0;
   for (int k = k0; k < k1; ++k) {
+    if (!valid[k]) continue;
+    ++nv;
     const int n = pnode[k];
     const double* m = nm + (size_t)kSbaNM * n;
     const double* w2n = m;
     double e[2];
     sba_error(m + 12, X, uv + 2 * k, e);
+    sba_huber(huber, e);                                                  // the Jacobians stay unweighted
     const double px = w2n[0] * X[0] + w2n[1] * X[1] + w2n[2] * X[2] + w2n[3];
     const double py = w2n[4] * X[0] + w2n[5] * X[1] + w2n[6] * X[2] + w2n[7];
     const double pz = w2n[8] * X[0] + w2n[9] * X[1] + w2n[10] * X[2] + w2n[11];
@@ -139,6 +171,7 @@ __global__ void __launch_bounds__(256) k_sba_point(const double* __restrict__ nm
       bp[r] -= jp[0][r] * e[0] + jp[1][r] * e[1];
     }
   }
+  if (nv == 0) return;                                                    // every projection pruned: as a point without any
   Hpp[0] *= lam; Hpp[4] *= lam; Hpp[8] *= lam;
   // Eigen's 3 x 3 cofactor inverse
   double c[9];
@@ -152,7 +185,7 @@ __global__ void __launch_bounds__(256) k_sba_point(const double* __restrict__ nm
   for (int r = 0; r < 3; ++r) tp[r] = Hi[3 * r] * bp[0] + Hi[3 * r + 1] * bp[1] + Hi[3 * r + 2] * bp[2];
   tps[3 * p] = tp[0]; tps[3 * p + 1] = tp[1]; tps[3 * p + 2] = tp[2];
   for (int k = k0; k < k1; ++k) {
-    if (pnode[k] == 0) continue;                                          // node 0 is fixed
+    if (pnode[k] == 0 || !valid[k]) continue;                             // node 0 is fixed
     double* o = prj + (size_t)kSbaPR * k;
     const double* Hpc = o + 36;
     for (int r = 0; r < 6; ++r)
@@ -313,19 +346,22 @@ __global__ void __launch_bounds__(256) k_sba_update_nodes(double* __restrict__ n
 // point update (sba.cpp:1468-1490): X += tp - sum_free T_a^T x_a, node order
 __global__ void __launch_bounds__(256) k_sba_update_points(double* __restrict__ pts, double* __restrict__ old, int npts,
                                                            const double* __restrict__ tps, const int* __restrict__ poff,
-                                                           const int* __restrict__ pnode, const double* __restrict__ prj,
-                                                           const double* __restrict__ x,
+                                                           const int* __restrict__ pnode,
+                                                           const unsigned char* __restrict__ valid,
+                                                           const double* __restrict__ prj, const double* __restrict__ x,
                                                            const SbaResult* __restrict__ res) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npts || sba_skip_update(res)) return;
   double* X = pts + 3 * p;
   old[3 * p] = X[0]; old[3 * p + 1] = X[1]; old[3 * p + 2] = X[2];
   const int k0 = poff[p], k1 = poff[p + 1];
-  if (k1 == k0) return;
+  int nv = 0;
+  for (int k = k0; k < k1; ++k) nv += valid[k] ? 1 : 0;
+  if (nv == 0) return;                                    // no (valid) projection: k_sba_point wrote no tp
   double tp[3] = {tps[3 * p], tps[3 * p + 1], tps[3 * p + 2]};
   for (int k = k0; k < k1; ++k) {
     const int n = pnode[k];
-    if (n == 0) continue;
+    if (n == 0 || !valid[k]) continue;
     const double* T = prj + (size_t)kSbaPR * k + 54;     // Tpc, 6 x 3
     const double* d = x + 6 * (n - 1);
     for (int q = 0; q < 3; ++q) {
@@ -340,14 +376,15 @@ __global__ void __launch_bounds__(256) k_sba_update_points(double* __restrict__ 
 // cost, pass 1: one projection per thread, a fixed tree per workgroup -> (sum, sum with e^2 < d2, count) partials
 __global__ void __launch_bounds__(256) k_sba_cost(const double* __restrict__ nm, const double* __restrict__ pts,
                                                   const int* __restrict__ pnode, const int* __restrict__ ppoint,
-                                                  const double* __restrict__ uv, int nprj, double d2,
-                                                  double* __restrict__ part) {
+                                                  const double* __restrict__ uv, const unsigned char* __restrict__ valid,
+                                                  double huber, int nprj, double d2, double* __restrict__ part) {
   __shared__ double s[3][256];
   const int tid = threadIdx.x, k = blockIdx.x * 256 + tid;
   double e2 = 0.0, ein = 0.0, cin = 0.0;
-  if (k < nprj) {
+  if (k < nprj && valid[k]) {
     double e[2];
     sba_error(nm + (size_t)kSbaNM * pnode[k] + 12, pts + 3 * ppoint[k], uv + 2 * k, e);
+    sba_huber(huber, e);
     e2 = e[0] * e[0] + e[1] * e[1];
     if (e2 < d2) { ein = e2; cin = 1.0; }
   }
@@ -374,6 +411,59 @@ __global__ void __launch_bounds__(256) k_sba_cost_final(const double* __restrict
     __syncthreads();
   }
   if (tid == 0) { res->cost = s[0][0]; res->cost_in = s[1][0]; res->n_in = s[2][0]; }
+}
+
+// The workgroup tree of k_sba_cost for the two kernels below: three values per thread -> part[3 * block ..]
+__device__ __forceinline__ void sba_block_sum3(double a, double b, double c, double* __restrict__ part) {
+  __shared__ double s[3][256];
+  const int tid = threadIdx.x;
+  s[0][tid] = a; s[1][tid] = b; s[2][tid] = c;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) { s[0][tid] += s[0][tid + w]; s[1][tid] += s[1][tid + w]; s[2][tid] += s[2][tid + w]; }
+    __syncthreads();
+  }
+  if (tid == 0) { part[3 * blockIdx.x] = s[0][0]; part[3 * blockIdx.x + 1] = s[1][0]; part[3 * blockIdx.x + 2] = s[2][0]; }
+}
+
+// countBad / removeBad (sba.cpp:416-462), pass 1: one projection per thread.  A valid projection whose weighted
+// e^2 >= d2 counts; with mark != 0 its flag is cleared as well (each thread writes its own byte only).
+__global__ void __launch_bounds__(256) k_sba_flag_bad(const double* __restrict__ nm, const double* __restrict__ pts,
+                                                      const int* __restrict__ pnode, const int* __restrict__ ppoint,
+                                                      const double* __restrict__ uv, unsigned char* __restrict__ valid,
+                                                      double huber, int nprj, double d2, int mark,
+                                                      double* __restrict__ part) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  double bad = 0.0;
+  if (k < nprj && valid[k]) {
+    double e[2];
+    sba_error(nm + (size_t)kSbaNM * pnode[k] + 12, pts + 3 * ppoint[k], uv + 2 * k, e);
+    sba_huber(huber, e);
+    if (e[0] * e[0] + e[1] * e[1] >= d2) {
+      bad = 1.0;
+      if (mark) valid[k] = 0;
+    }
+  }
+  sba_block_sum3(bad, 0.0, 0.0, part);
+}
+
+// calcAvgError and numBadPoints (sba.cpp:365-411), pass 1: (sum of the weighted |e|, valid projections, valid
+// projections whose unweighted error is exactly (0, 0): in practice p1.z <= 0)
+__global__ void __launch_bounds__(256) k_sba_stats(const double* __restrict__ nm, const double* __restrict__ pts,
+                                                   const int* __restrict__ pnode, const int* __restrict__ ppoint,
+                                                   const double* __restrict__ uv, const unsigned char* __restrict__ valid,
+                                                   double huber, int nprj, double* __restrict__ part) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  double en = 0.0, nv = 0.0, nz = 0.0;
+  if (k < nprj && valid[k]) {
+    double e[2];
+    sba_error(nm + (size_t)kSbaNM * pnode[k] + 12, pts + 3 * ppoint[k], uv + 2 * k, e);
+    nv = 1.0;
+    if (e[0] == 0.0 && e[1] == 0.0) nz = 1.0;
+    sba_huber(huber, e);
+    en = sqrt(e[0] * e[0] + e[1] * e[1]);
+  }
+  sba_block_sum3(en, nv, nz, part);
 }
 
 // Blocked right-looking Cholesky of the lower triangle of the n x n (n % 64 == 0) row-major A in place, with the

@@ -3,7 +3,9 @@
 `BundleAdjuster` binds one `ekf_sba` handle (include/ekf_monoslam.h): fp64 Levenberg-Marquardt on the reduced camera
 system, node 0 fixed, as SysSBA::doSBA (sparse_bundle_adjustment/src/sba.cpp:1312-1585).  `sba_add` is the driver
 (sba_add.cpp:71-290) over the three files the filter's node writes (`formats`), with the deviations of DESIGN.md
-§11.4.  There is no CPU fallback: without a HIP device the constructor raises.
+§11.4.  The pseudo-Huber cost (SysSBA::huber) and the pruning of outlying projections (countBad, removeBad,
+reduceTracks) are there as well, off by default.  There is no CPU fallback: without a HIP device the
+constructor raises.
 """
 from __future__ import annotations
 
@@ -84,6 +86,58 @@ class BundleAdjuster:
         self._check(self._lib.ekf_sba_counts(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def projections(self):
+        """The stored projections, point-major and node ascending within a point: (node, point, uv, valid)."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_get_projections(self._h, 0, None, None, None, None, C.byref(n)))
+        node, point = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        uv, valid = np.zeros((n.value, 2)), np.zeros(n.value, np.uint8)
+        self._check(self._lib.ekf_sba_get_projections(self._h, n.value, _ptr(node), _ptr(point), _ptr(uv), _ptr(valid),
+                                                      C.byref(n)))
+        return node, point, uv, valid.astype(bool)
+
+    # --- robust cost and pruning (DESIGN.md §11.6) ------------------------------------------------------
+    @property
+    def huber(self):
+        """SysSBA::huber in pixels (proj.cpp:162-176); 0 (the default) is the plain squared error."""
+        h = C.c_double()
+        self._check(self._lib.ekf_sba_get_huber(self._h, C.byref(h)))
+        return h.value
+
+    @huber.setter
+    def huber(self, value):
+        self._check(self._lib.ekf_sba_set_huber(self._h, float(value)))
+
+    def count_bad(self, dist):
+        """countBad: valid projections whose weighted squared error at the current state is >= dist^2."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_count_bad(self._h, float(dist), C.byref(n)))
+        return n.value
+
+    def remove_bad(self, dist):
+        """removeBad: marks those projections invalid; returns how many."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_remove_bad(self._h, float(dist), C.byref(n)))
+        return n.value
+
+    def reduce_tracks(self):
+        """reduceTracks: erases invalid projections and the tracks left with fewer than 2; returns the points cleared."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_reduce_tracks(self._h, C.byref(n)))
+        return n.value
+
+    def num_bad_points(self):
+        """numBadPoints: valid projections with an exactly zero error (the point is not in front of the camera)."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_num_bad_points(self._h, C.byref(n)))
+        return n.value
+
+    def avg_error(self):
+        """calcAvgError: mean weighted |e| over the valid projections (NaN without any)."""
+        a = C.c_double()
+        self._check(self._lib.ekf_sba_avg_error(self._h, C.byref(a)))
+        return a.value
+
     # --- solving --------------------------------------------------------------------------------------------
     def run(self, niter=10, lam=1e-4):
         """SysSBA::doSBA(niter, lam): the iteration count, -1 for an empty problem."""
@@ -143,9 +197,17 @@ class BundleAdjuster:
         if self.rms_cost() > 4.0:
             self.run(15, 1e-4)
 
+    def rms_wrapper_pruned(self, prune_dist=None):
+        """The RMS wrapper, then (with `prune_dist`) remove_bad(prune_dist); if that removed anything,
+        reduce_tracks() and one more run(10, 1e-4).  The pruning is not part of the reference driver."""
+        self.rms_wrapper()
+        if prune_dist is not None and self.counts()[0] and self.remove_bad(prune_dist):
+            self.reduce_tracks()
+            self.run(10, 1e-4)
+
 
 def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA, every=10, points_out=None,
-            nodes_out=None, device=0):
+            nodes_out=None, device=0, huber=0.0, prune_dist=None):
     """The reference's sba_add driver on the GPU.
 
     `points`, `nodes_and_prjcts`, `cams_cov`: paths or file objects of the filter's three files (formats.py), or
@@ -157,6 +219,11 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
 
     Limit (deviation 4): at most 1024 key-frame records, the largest reduced system the
     single-workgroup triangular solve holds; more raise EkfError (EKF_ERR_ARG) when the handle is created.
+
+    `huber` (pixels) is set on the handle before the first run (SysSBA::huber; the reference driver leaves it 0).
+    With `prune_dist` every call of the RMS wrapper is followed by remove_bad(prune_dist) and, if that removed
+    anything, reduce_tracks() and one more run(10, 1e-4).  The reference driver has no such option (the library
+    calls exist, sba_add.cpp never makes them); the defaults reproduce it exactly.
 
     Returns (table, nodes, ids): the refined N x 3 table (rows of points that were never added -- all-zero ones --
     stay zero), the refined nodes (x y z qw qx qy qz) and their ids.  Writes Points_Out.txt / Nodes_Out.txt when
@@ -172,6 +239,7 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
     nproj = sum(len(r[2]) for r in records)
     ba = BundleAdjuster(camera, capacity_nodes=max(len(records), 1), capacity_points=max(len(rows), 1),
                         capacity_projections=max(nproj, 1), device=device)
+    ba.huber = huber
     if rows:
         ba.add_points(table[rows, :3].astype(np.float64))
     ids = []
@@ -184,8 +252,8 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
             s = np.array(sel)
             ba.add_projections(np.full(len(sel), ni), s[:, 0].astype(np.int32), s[:, 1:])
         if every and (ni + 1) % every == 0:
-            ba.rms_wrapper()
-    ba.rms_wrapper()
+            ba.rms_wrapper_pruned(prune_dist)
+    ba.rms_wrapper_pruned(prune_dist)
     out = np.zeros((table.shape[0], 3))
     if rows:
         out[rows] = ba.points()

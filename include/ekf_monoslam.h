@@ -543,7 +543,31 @@ void* ekf_device_sigma(ekf_filter* f, int* ld);
  *  - ekf_sba_get_log: per iteration of the last run, 5 doubles: cost before, cost after the step, lambda after,
  *    accepted (1 / 0), |x|^2;  *n = the number of rows (at most max_rows are written);
  *  - ekf_sba_profile / ekf_sba_get_profile: HIP-event milliseconds per phase (prep, Schur, assemble,
- *    factor + solve, update + cost) summed over the iterations since the last ekf_sba_profile, and per iteration. */
+ *    factor + solve, update + cost) summed over the iterations since the last ekf_sba_profile, and per iteration.
+ *
+ * Robust cost and pruning.  All of it is off by default: huber = 0 and every projection valid.
+ *  - ekf_sba_set_huber / ekf_sba_get_huber = SysSBA::huber (sba.h:113), in pixels; 0 switches it off, a negative
+ *    or non-finite value is EKF_ERR_ARG.  For huber > 0 a projection with |e|^2 > huber^2 has its error scaled by
+ *    sqrt((2 huber |e| - huber^2) / |e|^2) (calcErrMono_, proj.cpp:162-176).  The weighted error enters the cost, the
+ *    RMS cost and its dist test (sba.cpp:300, :350), JcTE and bp of the linear system, and everything below; the
+ *    Jacobian products are not weighted, as in the reference;
+ *  - every stored projection has a validity flag (Proj::isValid), set on add.  An invalid one contributes to
+ *    nothing (sba.cpp:299, :1212, :1242, :1255, :1513) but keeps its slot and still blocks a repeat of its
+ *    (node, point) pair until ekf_sba_reduce_tracks erases it.  A point whose projections are all invalid is left
+ *    alone like a point without any, and a free node whose projections are all invalid takes a zero step;
+ *  - ekf_sba_count_bad = countBad(dist) (sba.cpp:416-440): *n = the valid projections whose weighted |e|^2 at the
+ *    current nodes and points is >= dist^2 (the state doSBA leaves its stored errors at);  dist > 0;
+ *  - ekf_sba_remove_bad = removeBad(dist) (sba.cpp:445-462): marks those invalid, *n = how many;
+ *  - ekf_sba_reduce_tracks = reduceTracks (sba.cpp:467-502): erases the invalid projections, then every projection
+ *    of a point left with fewer than 2; *cleared = the number of such points, those without any projection
+ *    included.  ekf_sba_counts' third figure is the number of stored projections and falls accordingly;
+ *  - ekf_sba_num_bad_points = numBadPoints (sba.cpp:389-411): valid projections whose unweighted error is exactly
+ *    (0, 0), in practice the ones with p1.z <= 0;
+ *  - ekf_sba_avg_error = calcAvgError (sba.cpp:365-386): the mean weighted |e| over the valid projections, NaN
+ *    when there are none;
+ *  - ekf_sba_get_projections: the stored projections, point-major and node ascending within a point (the order
+ *    of the reference's tracks and their maps); *n = their number, at most max_rows rows are written, and each of
+ *    node / point / uv (2 per row) / valid may be NULL. */
 typedef struct ekf_sba ekf_sba;
 typedef struct ekf_sba_camera {
   double fx, fy, cx, cy;
@@ -560,6 +584,15 @@ int ekf_sba_add_projections(ekf_sba* s, int n, const int* node, const int* point
 int ekf_sba_counts(const ekf_sba* s, int* nodes, int* points, int* projections);
 int ekf_sba_run(ekf_sba* s, int niter, double lambda, int* iterations);
 int ekf_sba_cost(ekf_sba* s, double dist, double* sq_cost, double* rms);
+int ekf_sba_set_huber(ekf_sba* s, double huber);
+int ekf_sba_get_huber(const ekf_sba* s, double* huber);
+int ekf_sba_count_bad(ekf_sba* s, double dist, int* n);
+int ekf_sba_remove_bad(ekf_sba* s, double dist, int* n);
+int ekf_sba_reduce_tracks(ekf_sba* s, int* cleared);
+int ekf_sba_num_bad_points(ekf_sba* s, int* n);
+int ekf_sba_avg_error(ekf_sba* s, double* avg);
+int ekf_sba_get_projections(const ekf_sba* s, int max_rows, int* node, int* point, double* uv, unsigned char* valid,
+                            int* n);
 int ekf_sba_get_nodes(const ekf_sba* s, double* pose7);
 int ekf_sba_get_points(const ekf_sba* s, double* xyz);
 int ekf_sba_get_log(const ekf_sba* s, int max_rows, double* rows, int* n);

@@ -232,7 +232,8 @@ class VSlamFilterHip {
 
 // SysSbaHip -- header-only mirror of the part of the reference's `sba::SysSBA` (sparse_bundle_adjustment/include/
 // sparse_bundle_adjustment/sba.h) that sba_add drives, over the ekf_sba_* functions of ekf_monoslam.h: monocular
-// projections, node 0 fixed, doSBA with the CHOLMOD solve, calcCost / calcRMSCost.  Poses are
+// projections, node 0 fixed, doSBA with the CHOLMOD solve, calcCost / calcRMSCost, the pseudo-Huber cost and the
+// pruning of outlying projections.  Poses are
 // (x y z qw qx qy qz), points (x y z), as plain double arrays.
 class SysSbaHip {
  public:
@@ -264,6 +265,15 @@ class SysSbaHip {
   }
   double calcCost() { double c = 0, r = 0; check(ekf_sba_cost(h_, 10000.0, &c, &r)); return c; }
   double calcRMSCost(double dist = 10000.0) { double c = 0, r = 0; check(ekf_sba_cost(h_, dist, &c, &r)); return r; }
+  // SysSBA::huber (sba.h:113): the pseudo-Huber width in pixels, 0 = off
+  void setHuber(double huber) { check(ekf_sba_set_huber(h_, huber)); }
+  double huber() { double v = 0; check(ekf_sba_get_huber(h_, &v)); return v; }
+  // countBad / removeBad / reduceTracks / numBadPoints / calcAvgError (sba.cpp:365-502)
+  int countBad(double dist) { int n = 0; check(ekf_sba_count_bad(h_, dist, &n)); return n; }
+  int removeBad(double dist) { int n = 0; check(ekf_sba_remove_bad(h_, dist, &n)); return n; }
+  int reduceTracks() { int n = 0; check(ekf_sba_reduce_tracks(h_, &n)); return n; }
+  int numBadPoints() { int n = 0; check(ekf_sba_num_bad_points(h_, &n)); return n; }
+  double calcAvgError() { double a = 0; check(ekf_sba_avg_error(h_, &a)); return a; }
   std::vector<double> nodes() { std::vector<double> v(7 * (size_t)counts(0)); check(ekf_sba_get_nodes(h_, v.data())); return v; }
   std::vector<double> points() { std::vector<double> v(3 * (size_t)counts(1)); check(ekf_sba_get_points(h_, v.data())); return v; }
   int numNodes() { return counts(0); }

@@ -1,7 +1,10 @@
 """HIP-event times of the GPU bundle adjustment per phase and per LM iteration, at the four test
 sizes of tests/test_gpu_sba.py, with the numpy oracle's host time for the same run next to each.
 
-    python tools/sba_timing.py [--out profiles/sba_timing_mi355x.json] [--niter 10]
+    python tools/sba_timing.py [--out profiles/sba_timing_mi355x.json] [--niter 10] [--huber H]
+
+--huber H sets the pseudo-Huber width (pixels) on the GPU handle; the oracle column is then the robust
+oracle's.  0 (the default) is the plain squared error.
 
 Phases (ekf_sba_get_profile): prep (node matrices), Schur (per-point Jacobians, Hpp^-1, tp, T_a), assemble (B, the
 6 x 6 blocks of A, the diagonal, the copy for the refinement), factor + solve (Cholesky, two triangular solves, the
@@ -30,6 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sba_timing_mi355x.json"))
     ap.add_argument("--niter", type=int, default=10)
+    ap.add_argument("--huber", type=float, default=0.0)
     a = ap.parse_args()
     pkg = g.load_package()
     rows = []
@@ -41,6 +45,7 @@ def main():
             ba.add_nodes(scene["nodes"])
             ba.add_points(scene["points"])
             ba.add_projections(scene["node"], scene["point"], scene["uv"])
+            ba.huber = a.huber
             ba.profile(True)
             t0 = time.perf_counter()
             it = ba.run(a.niter, 1e-4)
@@ -49,6 +54,11 @@ def main():
             nprj = ba.counts()[2]
             ba.close()
         ref = sc.oracle_system(scene)
+        if a.huber:
+            import sba_robust_oracle as ro
+            ref, plain = ro.RobustSysSBA(scene["camera"], a.huber), ref
+            ref.trans, ref.qrot, ref.points, ref.tracks = plain.trans, plain.qrot, plain.points, plain.tracks
+            ref.valid = [{ni: True for ni in tr} for tr in ref.tracks]
         t0 = time.perf_counter()
         it_ref = ref.do_sba(a.niter, 1e-4)
         host = (time.perf_counter() - t0) * 1e3
@@ -61,7 +71,8 @@ def main():
         print(json.dumps(row))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
-        json.dump({"device": "MI355X (gfx950)", "niter": a.niter, "lambda": 1e-4, "sizes": rows}, fh, indent=1)
+        json.dump({"device": "MI355X (gfx950)", "niter": a.niter, "lambda": 1e-4, "huber": a.huber, "sizes": rows}, fh,
+                  indent=1)
 
 
 if __name__ == "__main__":
