@@ -119,6 +119,11 @@ _PROTOS = {
     "ekf_device_mu": (_P, [_P]),
     "ekf_device_sigma": (_P, [_P, C.POINTER(C.c_int)]),
     "ekf_sba_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "ekf_sba_create_solver": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "ekf_sba_get_solver": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ekf_sba_set_cg": (C.c_int, [_P, C.c_double, C.c_int]),
+    "ekf_sba_get_cg": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "ekf_sba_get_cg_log": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "ekf_sba_destroy": (None, [_P]),
     "ekf_sba_last_error": (C.c_char_p, [_P]),
     "ekf_sba_add_nodes": (C.c_int, [_P, C.c_int, _P]),

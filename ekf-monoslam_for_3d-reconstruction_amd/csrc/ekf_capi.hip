@@ -3893,6 +3893,12 @@ struct SbaSystem {
   double huber = 0.0;                                        // SysSBA::huber (sba.h:113), 0: plain squared error
   std::vector<double> log;                                   // 5 per iteration of the last run
   bool dirty = true;
+  // solver: EKF_SBA_SOLVER_CHOLESKY or EKF_SBA_SOLVER_BPCG; the CG settings of doSBA (sba.h:158-159)
+  int solver = EKF_SBA_SOLVER_CHOLESKY;
+  double cg_tol = 1e-8;
+  int cg_max = 100;
+  double cg_residual = 0.0;                                  // jacobiBPCG::residual: dn / 2 of the last solve
+  std::vector<double> cg_log;                                // 3 per iteration of the last run: CG iterations, dn, d0
   // profile (ekf_sba_profile): per phase and per iteration, milliseconds
   bool profile = false;
   double phase_ms[5] = {0, 0, 0, 0, 0};
@@ -3901,9 +3907,13 @@ struct SbaSystem {
   // device
   struct Buf { void* p = nullptr; size_t bytes = 0; };
   enum { B_NODES, B_OLDN, B_NM, B_PTS, B_OLDP, B_POFF, B_PNODE, B_PPOINT, B_UV, B_VALID, B_PRJ, B_TPS, B_COFF, B_CPRJ,
-         B_PAIR_AB, B_PAIR_OFF, B_ITEMS, B_EMPTY, B_A, B_L, B_B, B_X, B_R, B_DX, B_DINV, B_PART, B_RES, B_COUNT };
+         B_PAIR_AB, B_PAIR_OFF, B_ITEMS, B_EMPTY, B_A, B_L, B_B, B_X, B_R, B_DX, B_DINV, B_PART, B_RES,
+         B_PAIR_SLOT, B_BLK, B_J, B_ADJ_OFF, B_ADJ, B_Q, B_S, B_PART_DQ, B_PART_RS, B_COUNT };
   Buf buf[B_COUNT];
-  int npairs = 0, nfree = 0, npad = 0;
+  int npairs = 0, nfree = 0, npad = 0, noff = 0;
+  static constexpr int kCgChunk = 256;                       // CG rounds enqueued between two reads of the CG state
+  bool pcg() const { return solver == EKF_SBA_SOLVER_BPCG; }
+  SbaCg* dcg() { return reinterpret_cast<SbaCg*>(dp<SbaResult>(B_RES) + 1); }
 
   ~SbaSystem() {
     hipSetDevice(device);
@@ -3922,15 +3932,16 @@ struct SbaSystem {
     buf[i].bytes = bytes;
     return EKF_OK;
   }
-  int init(const ekf_sba_camera* cam, int cn, int cp, int cj, int dev) {
+  int init(const ekf_sba_camera* cam, int cn, int cp, int cj, int dev, int slv) {
     device = dev;
+    solver = slv;
     K = SbaCamera{cam->fx, cam->fy, cam->cx, cam->cy};
     cap_nodes = cn; cap_points = cp; cap_prj = cj;
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipMalloc(&buf[B_RES].p, sizeof(SbaResult)));
-    buf[B_RES].bytes = sizeof(SbaResult);
+    HIPCHK(hipMalloc(&buf[B_RES].p, sizeof(SbaResult) + sizeof(SbaCg)));     // the CG state sits behind the result
+    buf[B_RES].bytes = sizeof(SbaResult) + sizeof(SbaCg);
     return EKF_OK;
   }
   int nn() const { return (int)nodes.size() / 7; }
@@ -3982,6 +3993,29 @@ struct SbaSystem {
       items.insert(items.end(), e.second.begin(), e.second.end());
       pair_off.push_back((int)items.size() / 2);
     }
+    // PCG: the block slot of every pair and, per block row, the ascending (neighbour, slot, transposed) list
+    std::vector<int> pair_slot, adj_off, adj;
+    noff = 0;
+    if (pcg()) {
+      std::vector<std::vector<std::array<int, 3>>> rows(nfree);
+      for (const auto& e : pairs) {                  // the map's order: (a, b) ascending, a <= b
+        const int a = e.first.first, b = e.first.second;
+        if (a == b) {
+          pair_slot.push_back(a);
+          continue;
+        }
+        const int slot = nfree + noff++;
+        pair_slot.push_back(slot);
+        rows[a].push_back({b, slot, 0});
+        rows[b].push_back({a, slot, 1});
+      }
+      adj_off.assign(1, 0);
+      for (auto& rw : rows) {
+        std::sort(rw.begin(), rw.end());
+        for (const auto& t : rw) adj.insert(adj.end(), t.begin(), t.end());
+        adj_off.push_back((int)adj.size() / 3);
+      }
+    }
     const size_t D = sizeof(double), I = sizeof(int);
     int rc;
     if ((rc = ensure(B_NODES, 7 * D * N)) || (rc = ensure(B_OLDN, 7 * D * N)) || (rc = ensure(B_NM, kSbaNM * D * N)) ||
@@ -3991,11 +4025,21 @@ struct SbaSystem {
         (rc = ensure(B_PRJ, kSbaPR * D * P)) || (rc = ensure(B_TPS, 3 * D * M)) || (rc = ensure(B_COFF, I * coff.size())) ||
         (rc = ensure(B_CPRJ, I * cprj.size())) || (rc = ensure(B_PAIR_AB, I * pair_ab.size())) ||
         (rc = ensure(B_PAIR_OFF, I * pair_off.size())) || (rc = ensure(B_ITEMS, I * items.size())) ||
-        (rc = ensure(B_EMPTY, I * empty.size())) || (rc = ensure(B_A, D * npad * npad)) ||
-        (rc = ensure(B_L, D * npad * npad)) || (rc = ensure(B_B, D * npad)) || (rc = ensure(B_X, D * npad)) ||
-        (rc = ensure(B_R, D * npad)) || (rc = ensure(B_DX, D * npad)) || (rc = ensure(B_DINV, D * 64 * 64)) ||
+        (rc = ensure(B_EMPTY, I * empty.size())) || (rc = ensure(B_B, D * npad)) || (rc = ensure(B_X, D * npad)) ||
+        (rc = ensure(B_R, D * npad)) || (rc = ensure(B_DX, D * npad)) ||
         (rc = ensure(B_PART, 3 * D * ((P + 255) / 256))))
       return rc;
+    if (pcg()) {                                     // no dense matrix: the blocks, their inverses, the CG vectors
+      const size_t nb = (size_t)nfree + noff, wg = (size_t)cg_blocks();
+      if ((rc = ensure(B_PAIR_SLOT, I * pair_slot.size())) || (rc = ensure(B_BLK, 36 * D * nb)) ||
+          (rc = ensure(B_J, 36 * D * nfree)) || (rc = ensure(B_ADJ_OFF, I * adj_off.size())) ||
+          (rc = ensure(B_ADJ, I * adj.size())) || (rc = ensure(B_Q, D * npad)) || (rc = ensure(B_S, D * npad)) ||
+          (rc = ensure(B_PART_DQ, D * wg)) || (rc = ensure(B_PART_RS, D * wg)))
+        return rc;
+    } else if ((rc = ensure(B_A, D * npad * npad)) || (rc = ensure(B_L, D * npad * npad)) ||
+               (rc = ensure(B_DINV, D * 64 * 64))) {
+      return rc;
+    }
     auto up = [&](int i, const void* src, size_t bytes) -> int {
       if (bytes) HIPCHK(hipMemcpyAsync(buf[i].p, src, bytes, hipMemcpyHostToDevice, stream));
       return EKF_OK;
@@ -4005,7 +4049,9 @@ struct SbaSystem {
         (rc = up(B_VALID, valid.data(), P)) ||
         (rc = up(B_COFF, coff.data(), I * coff.size())) || (rc = up(B_CPRJ, cprj.data(), I * cprj.size())) ||
         (rc = up(B_PAIR_AB, pair_ab.data(), I * pair_ab.size())) || (rc = up(B_PAIR_OFF, pair_off.data(), I * pair_off.size())) ||
-        (rc = up(B_ITEMS, items.data(), I * items.size())) || (rc = up(B_EMPTY, empty.data(), I * empty.size())))
+        (rc = up(B_ITEMS, items.data(), I * items.size())) || (rc = up(B_EMPTY, empty.data(), I * empty.size())) ||
+        (rc = up(B_PAIR_SLOT, pair_slot.data(), I * pair_slot.size())) ||
+        (rc = up(B_ADJ_OFF, adj_off.data(), I * adj_off.size())) || (rc = up(B_ADJ, adj.data(), I * adj.size())))
       return rc;
     HIPCHK(hipStreamSynchronize(stream));          // the host vectors above go out of scope
     dirty = false;
@@ -4020,6 +4066,7 @@ struct SbaSystem {
     return EKF_OK;
   }
   static int blocks(int n, int t = 256) { return (n + t - 1) / t; }
+  int cg_blocks() const { return std::max(blocks(nfree, kSbaCgRows), 1); }
   // node matrices + the cost pass (dist2: the RMS cut) into B_RES
   int launch_cost(double dist2) {
     const int P = (int)prj.size();
@@ -4031,9 +4078,12 @@ struct SbaSystem {
     HIPCHK(hipGetLastError());
     return EKF_OK;
   }
-  int read_result(SbaResult* r) {
-    HIPCHK(hipMemcpyAsync(r, buf[B_RES].p, sizeof(SbaResult), hipMemcpyDeviceToHost, stream));
+  int read_result(SbaResult* r, SbaCg* cg = nullptr) {
+    struct { SbaResult r; SbaCg cg; } both;        // one copy: the CG state sits behind the result
+    HIPCHK(hipMemcpyAsync(&both, buf[B_RES].p, cg ? sizeof(both) : sizeof(SbaResult), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
+    *r = both.r;
+    if (cg) *cg = both.cg;
     return EKF_OK;
   }
   int download_state() {
@@ -4132,9 +4182,46 @@ struct SbaSystem {
   }
   void mark(int e) { if (profile) hipEventRecord(ev[e], stream); }
 
+  // CSparse::doBPCG (csparse.cpp:383-395) on the block array: J, the head of doBPCG2, up to cg_max rounds of three
+  // launches, |x|^2.  Up to kCgChunk rounds the whole solve is enqueued blind; the rounds after `dn < d0` return at
+  // once on the device.  A larger cg_max is enqueued in chunks of kCgChunk rounds with one read of the CG state
+  // between two chunks, so that a converged solve does not pay for thousands of idle launches.
+  int solve_pcg(int sba_iter) {
+    const int n6 = 6 * nfree, nb = cg_blocks();
+    SbaResult* res = dp<SbaResult>(B_RES);
+    SbaCg* cg = dcg();
+    double *x = dp<double>(B_X), *rr = dp<double>(B_R), *d = dp<double>(B_DX), *q = dp<double>(B_Q), *sv = dp<double>(B_S);
+    k_sba_blk_inv<<<blocks(nfree), 256, 0, stream>>>(dp<double>(B_BLK), nfree, dp<double>(B_J), res);
+    k_sba_cg_step<true><<<nb, 256, 0, stream>>>(dp<double>(B_J), nullptr, 0, dp<double>(B_B), d, q, x, rr, sv, nfree,
+                                                 dp<double>(B_PART_RS), cg);
+    k_sba_cg_dir<true><<<blocks(n6), 256, 0, stream>>>(dp<double>(B_PART_RS), nb, sv, d, n6, cg, cg_tol,
+                                                        sba_iter > 0 ? 1 : 0, cg_residual);
+    for (int i0 = 0; i0 < cg_max; i0 += kCgChunk) {
+      const int i1 = std::min(cg_max, i0 + kCgChunk);
+      for (int i = i0; i < i1; ++i) {
+        k_sba_cg_mv<<<nb, 256, 0, stream>>>(dp<double>(B_BLK), dp<int>(B_ADJ_OFF), dp<int>(B_ADJ), d, nfree, q,
+                                            dp<double>(B_PART_DQ), cg, res);
+        k_sba_cg_step<false><<<nb, 256, 0, stream>>>(dp<double>(B_J), dp<double>(B_PART_DQ), nb, nullptr, d, q, x, rr, sv,
+                                                      nfree, dp<double>(B_PART_RS), cg);
+        k_sba_cg_dir<false><<<blocks(n6), 256, 0, stream>>>(dp<double>(B_PART_RS), nb, sv, d, n6, cg, 0.0, 0, 0.0);
+      }
+      HIPCHK(hipGetLastError());
+      if (i1 < cg_max) {
+        SbaResult r{};
+        SbaCg c{};
+        int rc;
+        if ((rc = read_result(&r, &c))) return rc;
+        if (c.dn < c.d0 || r.status) break;
+      }
+    }
+    k_sba_cg_end<<<1, 256, 0, stream>>>(x, n6, res);
+    return EKF_OK;
+  }
+
   // SysSBA::doSBA (sba.cpp:1312-1585)
   int run(int niter, double s_lambda, int* iterations) {
     log.clear();
+    cg_log.clear();
     *iterations = -1;
     if (prj.empty() || points.empty() || nodes.empty()) return EKF_OK;
     HIPCHK(hipSetDevice(device));
@@ -4156,21 +4243,30 @@ struct SbaSystem {
                                                   dp<int>(B_PNODE), dp<double>(B_UV), dp<unsigned char>(B_VALID), huber, M,
                                                   K, lam, dp<double>(B_PRJ), dp<double>(B_TPS));
       mark(2);
-      HIPCHK(hipMemsetAsync(buf[B_A].p, 0, sizeof(double) * npad * npad, stream));
+      if (!pcg()) HIPCHK(hipMemsetAsync(buf[B_A].p, 0, sizeof(double) * npad * npad, stream));
       k_sba_rhs<<<blocks(n6), 256, 0, stream>>>(dp<int>(B_COFF), dp<int>(B_CPRJ), dp<int>(B_PPOINT), dp<double>(B_PRJ),
                                                 dp<double>(B_TPS), nfree, dp<double>(B_B));
-      if (npairs)
-        k_sba_pairs<<<npairs, 64, 0, stream>>>(dp<int>(B_PAIR_AB), dp<int>(B_PAIR_OFF), dp<int>(B_ITEMS), dp<double>(B_PRJ),
-                                               dp<double>(B_A), npad);
-      k_sba_diag<<<blocks(npad), 256, 0, stream>>>(dp<double>(B_A), npad, n6, npad, dp<int>(B_EMPTY), lam);
-      HIPCHK(hipMemcpyAsync(buf[B_L].p, buf[B_A].p, sizeof(double) * npad * npad, hipMemcpyDeviceToDevice, stream));
-      mark(3);
-      sba_chol_f64(dp<double>(B_L), npad, npad, dp<double>(B_DINV), &dp<SbaResult>(B_RES)->status, stream);
-      k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_B), dp<double>(B_X));
-      k_sba_resid<<<blocks(n6, 4), 256, 0, stream>>>(dp<double>(B_A), npad, n6, dp<double>(B_X), dp<double>(B_B),
-                                                      dp<double>(B_R));
-      k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_R), dp<double>(B_DX));
-      k_sba_refine<<<1, 256, 0, stream>>>(dp<double>(B_X), dp<double>(B_DX), n6, dp<SbaResult>(B_RES));
+      if (pcg()) {
+        if (npairs)
+          k_sba_pairs_blk<<<npairs, 64, 0, stream>>>(dp<int>(B_PAIR_AB), dp<int>(B_PAIR_OFF), dp<int>(B_ITEMS),
+                                                     dp<double>(B_PRJ), dp<int>(B_PAIR_SLOT), dp<double>(B_BLK));
+        k_sba_diag_blk<<<blocks(n6), 256, 0, stream>>>(dp<double>(B_BLK), n6, dp<int>(B_EMPTY), lam);
+        mark(3);
+        if ((rc = solve_pcg(iter))) return rc;
+      } else {
+        if (npairs)
+          k_sba_pairs<<<npairs, 64, 0, stream>>>(dp<int>(B_PAIR_AB), dp<int>(B_PAIR_OFF), dp<int>(B_ITEMS), dp<double>(B_PRJ),
+                                                 dp<double>(B_A), npad);
+        k_sba_diag<<<blocks(npad), 256, 0, stream>>>(dp<double>(B_A), npad, n6, npad, dp<int>(B_EMPTY), lam);
+        HIPCHK(hipMemcpyAsync(buf[B_L].p, buf[B_A].p, sizeof(double) * npad * npad, hipMemcpyDeviceToDevice, stream));
+        mark(3);
+        sba_chol_f64(dp<double>(B_L), npad, npad, dp<double>(B_DINV), &dp<SbaResult>(B_RES)->status, stream);
+        k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_B), dp<double>(B_X));
+        k_sba_resid<<<blocks(n6, 4), 256, 0, stream>>>(dp<double>(B_A), npad, n6, dp<double>(B_X), dp<double>(B_B),
+                                                        dp<double>(B_R));
+        k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_R), dp<double>(B_DX));
+        k_sba_refine<<<1, 256, 0, stream>>>(dp<double>(B_X), dp<double>(B_DX), n6, dp<SbaResult>(B_RES));
+      }
       mark(4);
       k_sba_update_nodes<<<blocks(N), 256, 0, stream>>>(dp<double>(B_NODES), dp<double>(B_OLDN), N, dp<double>(B_X),
                                                          dp<SbaResult>(B_RES));
@@ -4179,7 +4275,13 @@ struct SbaSystem {
                                                           dp<double>(B_PRJ), dp<double>(B_X), dp<SbaResult>(B_RES));
       if ((rc = launch_cost(1e300))) return rc;
       mark(5);
-      if ((rc = read_result(&r))) return rc;       // the one read-back of the iteration
+      SbaCg cgr{};
+      if ((rc = read_result(&r, pcg() ? &cgr : nullptr))) return rc;       // the one read-back of the iteration
+      if (pcg()) {
+        cg_residual = cgr.dn / 2.0;                // bpcg.h:314; kept in the handle, as CSparse keeps its jacobiBPCG
+        const double crow[3] = {double(cgr.iters), cgr.dn, cgr.d0};
+        cg_log.insert(cg_log.end(), crow, crow + 3);
+      }
       if (profile) {
         float ms[5], tot = 0.f;
         for (int e = 0; e < 5; ++e) {
@@ -4192,6 +4294,7 @@ struct SbaSystem {
       if (r.status) {
         *iterations = iter;                        // the iterations completed before the failed factor
         if ((rc = download_state())) return rc;
+        if (pcg()) FAIL(EKF_ERR_NUMERIC, "ekf_sba_run: a diagonal block of the reduced camera system has a non-positive pivot");
         FAIL(EKF_ERR_NUMERIC, "ekf_sba_run: the reduced camera system has a non-positive pivot");
       }
       if (r.x2 < 1e-16) break;                     // converged: no update was made (a NaN step goes on and is rejected)
@@ -4458,29 +4561,87 @@ static bool sba_finite(const double* v, int n) {
   return true;
 }
 
-int ekf_sba_create(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
-                   int device, ekf_sba** out) {
+// The node capacity of a PCG handle: 64 * capacity_nodes (above the 52 doubles of node matrices per node and the 6
+// rows per node) must fit in int; the block and vector offsets themselves are size_t.
+static const int kSbaMaxNodesPcg = INT_MAX / 64;
+
+static int sba_create(const char* who, const ekf_sba_camera* K, int capacity_nodes, int capacity_points,
+                      int capacity_projections, int device, int solver, ekf_sba** out) {
   if (!out) return EKF_ERR_ARG;
   *out = nullptr;
+  if (solver != EKF_SBA_SOLVER_CHOLESKY && solver != EKF_SBA_SOLVER_BPCG) {
+    ekf::g_create_error = std::string(who) + ": solver must be EKF_SBA_SOLVER_CHOLESKY (0) or EKF_SBA_SOLVER_BPCG (3)";
+    return EKF_ERR_ARG;
+  }
+  const int max_nodes = solver == EKF_SBA_SOLVER_BPCG ? kSbaMaxNodesPcg : ekf::kSbaMaxN / 6;
   if (!K || !sba_finite(&K->fx, 4) || !(K->fx > 0.0) || !(K->fy > 0.0) || capacity_nodes < 1 ||
-      capacity_nodes > ekf::kSbaMaxN / 6 || capacity_points < 1 || capacity_projections < 1) {
-    ekf::g_create_error = "ekf_sba_create: bad argument (K finite with fx, fy > 0; 1 <= capacity_nodes <= 1024; "
-                          "capacities >= 1)";
+      capacity_nodes > max_nodes || capacity_points < 1 || capacity_projections < 1) {
+    ekf::g_create_error = std::string(who) + ": bad argument (K finite with fx, fy > 0; 1 <= capacity_nodes <= " +
+                          std::to_string(max_nodes) + "; capacities >= 1)";
     return EKF_ERR_ARG;
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    ekf::g_create_error = "ekf_sba_create: no HIP device (this library has no CPU fallback)";
+    ekf::g_create_error = std::string(who) + ": no HIP device (this library has no CPU fallback)";
     return EKF_ERR_DEVICE;
   }
   auto* s = new ekf::SbaSystem();
-  const int rc = s->init(K, capacity_nodes, capacity_points, capacity_projections, device);
+  const int rc = s->init(K, capacity_nodes, capacity_points, capacity_projections, device, solver);
   if (rc != EKF_OK) {
     ekf::g_create_error = s->err;
     delete s;
     return rc;
   }
   *out = new ekf_sba{s};
+  return EKF_OK;
+}
+
+int ekf_sba_create(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
+                   int device, ekf_sba** out) {
+  return sba_create("ekf_sba_create", K, capacity_nodes, capacity_points, capacity_projections, device,
+                    EKF_SBA_SOLVER_CHOLESKY, out);
+}
+
+int ekf_sba_create_solver(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
+                          int device, int solver, ekf_sba** out) {
+  return sba_create("ekf_sba_create_solver", K, capacity_nodes, capacity_points, capacity_projections, device, solver,
+                    out);
+}
+
+int ekf_sba_get_solver(const ekf_sba* s, int* solver) {
+  if (!s || !solver) return EKF_ERR_ARG;
+  *solver = s->impl->solver;
+  return EKF_OK;
+}
+
+int ekf_sba_set_cg(ekf_sba* s, double init_tol, int max_iters) {
+  if (!s) return EKF_ERR_ARG;
+  if (!std::isfinite(init_tol) || init_tol < 0.0 || max_iters < 1) {
+    s->impl->err = "ekf_sba_set_cg: init_tol must be finite and >= 0, max_iters >= 1";
+    return EKF_ERR_ARG;
+  }
+  s->impl->cg_tol = init_tol;
+  s->impl->cg_max = max_iters;
+  return EKF_OK;
+}
+
+int ekf_sba_get_cg(const ekf_sba* s, double* init_tol, int* max_iters) {
+  if (!s) return EKF_ERR_ARG;
+  if (init_tol) *init_tol = s->impl->cg_tol;
+  if (max_iters) *max_iters = s->impl->cg_max;
+  return EKF_OK;
+}
+
+int ekf_sba_get_cg_log(const ekf_sba* s, int max_rows, int* cg_iters, double* dn_final, double* d0, int* n) {
+  if (!s || !n || max_rows < 0) return EKF_ERR_ARG;
+  const std::vector<double>& l = s->impl->cg_log;
+  const int total = (int)l.size() / 3;
+  *n = total;
+  for (int i = 0; i < std::min(total, max_rows); ++i) {
+    if (cg_iters) cg_iters[i] = (int)l[3 * i];
+    if (dn_final) dn_final[i] = l[3 * i + 1];
+    if (d0) d0[i] = l[3 * i + 2];
+  }
   return EKF_OK;
 }
 

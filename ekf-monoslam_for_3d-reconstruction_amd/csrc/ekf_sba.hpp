@@ -13,6 +13,8 @@
 //   k_sba_update_*   camera and point update (skipped on the device when |x|^2 < 1e-16 or the factor failed)
 //   k_sba_node_prep  w2n, w2i, dRd* per node;  k_sba_cost / k_sba_cost_final: the cost, two fixed-order passes
 // Every sum has one fixed order (no atomics), so a run is bit-reproducible.
+// On a PCG handle k_sba_pairs_blk / k_sba_diag_blk assemble 6 x 6 blocks instead of the dense A, and
+// k_sba_blk_inv + the k_sba_cg_* kernels (further down) take the place of the Cholesky and the triangular solves.
 //
 // Robust cost and pruning: every projection carries a `valid` byte beside its keypoint, and the
 // error of a valid projection passes through sba_huber (SysSBA::huber, proj.cpp:162-176) wherever it is used.  An
@@ -214,16 +216,18 @@ __global__ void __launch_bounds__(256) k_sba_rhs(const int* __restrict__ coff, c
 
 // A_ab = sum over the pair's (proj_a, proj_b) list in point order of [Hcc if a == b] - T_a Hpc_b.  One workgroup of 64
 // per pair, 36 lanes; a diagonal pair computes its upper triangle (as the reference stores it) and mirrors it.
-__global__ void __launch_bounds__(64) k_sba_pairs(const int* __restrict__ pair_ab, const int* __restrict__ pair_off,
-                                                  const int* __restrict__ items, const double* __restrict__ prj,
-                                                  double* __restrict__ A, int lda) {
-  const int pr = blockIdx.x, t = threadIdx.x;
-  if (t >= 36) return;
-  const int a = pair_ab[2 * pr], b = pair_ab[2 * pr + 1];
-  const int r = t / 6, c = t % 6;
+// sba_pair_sum is the sum of lane t = 6 r + c of pair pr, for both destinations below; false: the lane has no entry.
+__device__ __forceinline__ bool sba_pair_sum(const int* __restrict__ pair_ab, const int* __restrict__ pair_off,
+                                             const int* __restrict__ items, const double* __restrict__ prj, int pr, int t,
+                                             int& a, int& b, int& r, int& c, double& acc) {
+  if (t >= 36) return false;
+  a = pair_ab[2 * pr];
+  b = pair_ab[2 * pr + 1];
+  r = t / 6;
+  c = t % 6;
   const bool diag = (a == b);
-  if (diag && r > c) return;
-  double acc = 0.0;
+  if (diag && r > c) return false;
+  acc = 0.0;
   for (int i = pair_off[pr]; i < pair_off[pr + 1]; ++i) {
     const double* oa = prj + (size_t)kSbaPR * items[2 * i];
     const double* ob = prj + (size_t)kSbaPR * items[2 * i + 1];
@@ -231,8 +235,46 @@ __global__ void __launch_bounds__(64) k_sba_pairs(const int* __restrict__ pair_a
     const double m = oa[54 + 3 * r] * ob[36 + c] + oa[54 + 3 * r + 1] * ob[42 + c] + oa[54 + 3 * r + 2] * ob[48 + c];
     acc += -m;
   }
+  return true;
+}
+
+// destination 1: the dense A of the Cholesky solver, both triangles
+__global__ void __launch_bounds__(64) k_sba_pairs(const int* __restrict__ pair_ab, const int* __restrict__ pair_off,
+                                                  const int* __restrict__ items, const double* __restrict__ prj,
+                                                  double* __restrict__ A, int lda) {
+  int a, b, r, c;
+  double acc;
+  if (!sba_pair_sum(pair_ab, pair_off, items, prj, blockIdx.x, threadIdx.x, a, b, r, c, acc)) return;
   A[(size_t)(6 * a + r) * lda + 6 * b + c] = acc;
   A[(size_t)(6 * b + c) * lda + 6 * a + r] = acc;
+}
+
+// destination 2: the block array of the PCG solver, 36 doubles per slot, row-major.  slot[pr] is the
+// node index for a diagonal pair (mirrored, so all 36 entries are written) and nfree + the running number of the
+// off-diagonal pair (a < b) otherwise: the block M of block row a, block column b (CSparse::addOffdiagBlock).
+__global__ void __launch_bounds__(64) k_sba_pairs_blk(const int* __restrict__ pair_ab, const int* __restrict__ pair_off,
+                                                      const int* __restrict__ items, const double* __restrict__ prj,
+                                                      const int* __restrict__ slot, double* __restrict__ blk) {
+  int a, b, r, c;
+  double acc;
+  if (!sba_pair_sum(pair_ab, pair_off, items, prj, blockIdx.x, threadIdx.x, a, b, r, c, acc)) return;
+  double* o = blk + (size_t)36 * slot[blockIdx.x];
+  o[6 * r + c] = acc;
+  if (a == b) o[6 * c + r] = acc;
+}
+
+// k_sba_diag for the block array: one thread per diagonal element i = 6 a + r of the free nodes
+__global__ void __launch_bounds__(256) k_sba_diag_blk(double* __restrict__ blk, int n6, const int* __restrict__ empty,
+                                                      double lam) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n6) return;
+  const int a = i / 6, r = i % 6;
+  double* row = blk + (size_t)36 * a + 6 * r;
+  if (empty[a]) {
+    for (int c = 0; c < 6; ++c) row[c] = (c == r) ? 1.0 : 0.0;
+  } else {
+    row[r] = row[r] * lam;
+  }
 }
 
 // diagonal: *= lam (csparse.cpp:279); identity for a projection-less free node (deviation 1) and for the padding
@@ -464,6 +506,222 @@ __global__ void __launch_bounds__(256) k_sba_stats(const double* __restrict__ nm
     en = sqrt(e[0] * e[0] + e[1] * e[1]);
   }
   sba_block_sum3(en, nv, nz, part);
+}
+
+// ---------------------------------------------------------------------------------------
+// Block-Jacobi preconditioned conjugate gradient: jacobiBPCG<6>::doBPCG2 (bpcg/bpcg.h:238-316) on
+// the block array of k_sba_pairs_blk.  Per CG iteration three launches, all on the solver's stream:
+//   k_sba_cg_mv      q = A d per block row (neighbours ascending) and the partial sums of d . q
+//   k_sba_cg_step    a = dn / (d . q);  x += a d;  r -= a q;  s = J r;  the partial sums of r . s
+//   k_sba_cg_dir     dn = r . s;  d = s + (dn / dold) d;  the iteration counter
+// The scalars live in SbaCg on the device.  k_sba_cg_mv evaluates the loop's exit test `dn < d0` at the head of every
+// round and records it; from then on the launches of that solve return at once.  Every dot product is a per-workgroup
+// tree plus a strided sum and the same tree over the partials, which each workgroup of the next kernel repeats for
+// itself (same order, same bits), so no kernel waits for another one's last workgroup.
+// ---------------------------------------------------------------------------------------
+struct SbaCg {
+  double dn;          // r . s of the last finished iteration (the value that ends the loop)
+  double dold;        // dn of the iteration before (k_sba_cg_step moves it here)
+  double d0;          // the stopping bound: tol * dn_0, or the carried-over residual if that is larger
+  double a;           // the last step length
+  int iters;          // finished CG iterations
+  int done;           // 1 once dn < d0 was seen (or the block inverse failed)
+  int pad[2];
+};
+
+constexpr int kSbaCgRows = 42;        // block rows per 256-thread workgroup: 252 lanes, one per vector element
+
+// Sum of one value per thread over the 256-thread workgroup, k_sba_cost's tree; every thread gets the result.
+__device__ __forceinline__ double sba_block_sum(double v, double* __restrict__ s) {
+  const int tid = threadIdx.x;
+  __syncthreads();                                        // s may still be read from the call before
+  s[tid] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) s[tid] += s[tid + w];
+    __syncthreads();
+  }
+  return s[0];
+}
+
+// k_sba_cost_final's shape: a strided sum of the n partials, then the tree
+__device__ __forceinline__ double sba_part_sum(const double* __restrict__ part, int n, double* __restrict__ s) {
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) a += part[i];
+  return sba_block_sum(a, s);
+}
+
+// J_i = D_i^-1 through the Cholesky factor D = L L^T: Linv by forward substitution, J = Linv^T Linv.  One thread per
+// free node, everything in registers (all loops have constant bounds).  A pivot that is not > 0 sets res->status.
+__global__ void __launch_bounds__(256) k_sba_blk_inv(const double* __restrict__ blk, int nfree, double* __restrict__ J,
+                                                     SbaResult* __restrict__ res) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nfree) return;
+  const double* D = blk + (size_t)36 * i;
+  double L[6][6], W[6][6];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double p = D[7 * j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) p -= L[j][k] * L[j][k];
+    if (!(p > 0.0)) bad = true;
+    const double l = sqrt(p);
+    L[j][j] = l;
+#pragma unroll
+    for (int r = j + 1; r < 6; ++r) {
+      double v = D[6 * r + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v -= L[r][k] * L[j][k];
+      L[r][j] = v / l;
+    }
+  }
+  // W = L^-1 (lower): column c of the identity through forward substitution
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+#pragma unroll
+    for (int r = c; r < 6; ++r) {
+      double v = (r == c) ? 1.0 : 0.0;
+#pragma unroll
+      for (int k = c; k < r; ++k) v -= L[r][k] * W[k][c];
+      W[r][c] = v / L[r][r];
+    }
+  }
+  double* o = J + (size_t)36 * i;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+#pragma unroll
+    for (int c = r; c < 6; ++c) {
+      double v = 0.0;
+#pragma unroll
+      for (int k = c; k < 6; ++k) v += W[k][r] * W[k][c];
+      o[6 * r + c] = v;
+      o[6 * c + r] = v;
+    }
+  }
+  if (bad) res->status = 1;
+}
+
+// q = A d (jacobiBPCG::mMV2, bpcg.h:142-161) and the partials of d . q.  Lane (row i, r): D_i d_i first, then the
+// neighbours of block row i ascending, each as one 6-term product added to the sum: (neighbour, slot, transposed)
+// triples in adj, built by the host.  The reference's entry order (block column, then block row, ascending) visits
+// the neighbours of one row in the same ascending order.
+__global__ void __launch_bounds__(256) k_sba_cg_mv(const double* __restrict__ blk, const int* __restrict__ adj_off,
+                                                   const int* __restrict__ adj, const double* __restrict__ d, int nfree,
+                                                   double* __restrict__ q, double* __restrict__ part,
+                                                   SbaCg* __restrict__ cg, const SbaResult* __restrict__ res) {
+  __shared__ double s[256];
+  const int tid = threadIdx.x;
+  const bool done = cg->dn < cg->d0 || res->status != 0;          // `if (dn < d0) break;` (bpcg.h:298)
+  if (blockIdx.x == 0 && tid == 0) cg->done = done ? 1 : 0;       // read by the two kernels after this one
+  if (done) return;
+  const int row = blockIdx.x * kSbaCgRows + tid / 6, r = tid % 6;
+  double v = 0.0;
+  if (tid < 6 * kSbaCgRows && row < nfree) {
+    const double* D = blk + (size_t)36 * row + 6 * r;
+    const double* di = d + 6 * row;
+    double acc = D[0] * di[0] + D[1] * di[1] + D[2] * di[2] + D[3] * di[3] + D[4] * di[4] + D[5] * di[5];
+    for (int k = adj_off[row]; k < adj_off[row + 1]; ++k) {
+      const double* M = blk + (size_t)36 * adj[3 * k + 1];
+      const double* dv = d + 6 * adj[3 * k];
+      double t;
+      if (adj[3 * k + 2])                                         // block row `neighbour`, column `row`: M^T d
+        t = M[r] * dv[0] + M[6 + r] * dv[1] + M[12 + r] * dv[2] + M[18 + r] * dv[3] + M[24 + r] * dv[4] + M[30 + r] * dv[5];
+      else
+        t = M[6 * r] * dv[0] + M[6 * r + 1] * dv[1] + M[6 * r + 2] * dv[2] + M[6 * r + 3] * dv[3] + M[6 * r + 4] * dv[4] +
+            M[6 * r + 5] * dv[5];
+      acc += t;
+    }
+    q[6 * row + r] = acc;
+    v = di[r] * acc;
+  }
+  const double sum = sba_block_sum(v, s);
+  if (tid == 0) part[blockIdx.x] = sum;
+}
+
+// kInit: x = 0, r = b, s = J r and the partials of r . s (the head of doBPCG2, bpcg.h:284-287).
+// Otherwise the middle of one iteration (bpcg.h:300-304): a from the partials of d . q, x += a d, r -= a q, s = J r.
+// The new r of a block goes through LDS so that the six lanes of the block read each other's value, not memory.
+template <bool kInit>
+__global__ void __launch_bounds__(256) k_sba_cg_step(const double* __restrict__ J, const double* __restrict__ part_dq,
+                                                     int nblk, const double* __restrict__ b, const double* __restrict__ d,
+                                                     const double* __restrict__ q, double* __restrict__ x,
+                                                     double* __restrict__ r, double* __restrict__ sv, int nfree,
+                                                     double* __restrict__ part_rs, SbaCg* __restrict__ cg) {
+  __shared__ double s[256];
+  __shared__ double rn[256];
+  const int tid = threadIdx.x;
+  double a = 0.0;
+  if (!kInit) {
+    if (cg->done) return;
+    const double dq = sba_part_sum(part_dq, nblk, s);
+    a = cg->dn / dq;
+    if (blockIdx.x == 0 && tid == 0) { cg->dold = cg->dn; cg->a = a; }     // dn is not written in this kernel
+  }
+  const int g = blockIdx.x * 6 * kSbaCgRows + tid;
+  const bool active = tid < 6 * kSbaCgRows && g < 6 * nfree;
+  double rv = 0.0;
+  if (active) {
+    if (kInit) {
+      x[g] = 0.0;
+      rv = b[g];
+    } else {
+      x[g] += a * d[g];
+      rv = r[g] - a * q[g];
+    }
+    r[g] = rv;
+  }
+  rn[tid] = rv;
+  __syncthreads();
+  double v = 0.0;
+  if (active) {
+    const int c = tid % 6;
+    const double* Jr = J + (size_t)36 * (g / 6) + 6 * c;
+    const double* rb = rn + (tid - c);
+    const double t = Jr[0] * rb[0] + Jr[1] * rb[1] + Jr[2] * rb[2] + Jr[3] * rb[3] + Jr[4] * rb[4] + Jr[5] * rb[5];
+    sv[g] = t;
+    v = rv * t;
+  }
+  const double sum = sba_block_sum(v, s);
+  if (tid == 0) part_rs[blockIdx.x] = sum;
+}
+
+// kInit: dn = r . d, d0 = tol dn, raised to the residual the solve before left when abstol is set (bpcg.h:287-292),
+// d = s.  Otherwise the tail of one iteration (bpcg.h:305-308): dn = r . s, d = s + (dn / dold) d, one more iteration.
+template <bool kInit>
+__global__ void __launch_bounds__(256) k_sba_cg_dir(const double* __restrict__ part_rs, int nblk,
+                                                    const double* __restrict__ sv, double* __restrict__ d, int n6,
+                                                    SbaCg* __restrict__ cg, double tol, int abstol, double residual) {
+  __shared__ double s[256];
+  const int tid = threadIdx.x;
+  if (!kInit && cg->done) return;
+  const double dn = sba_part_sum(part_rs, nblk, s);
+  const double beta = kInit ? 0.0 : dn / cg->dold;               // dold is not written in this kernel
+  const int g = blockIdx.x * 256 + tid;
+  if (g < n6) d[g] = kInit ? sv[g] : sv[g] + beta * d[g];
+  if (blockIdx.x == 0 && tid == 0) {
+    cg->dn = dn;
+    if (kInit) {
+      double d0 = tol * dn;
+      if (abstol && residual > d0) d0 = residual;
+      cg->d0 = d0;
+      cg->dold = dn;
+      cg->a = 0.0;
+      cg->iters = 0;
+      cg->done = 0;
+    } else {
+      cg->iters += 1;
+    }
+  }
+}
+
+// |x|^2 of the CG result, k_sba_refine's sum (one workgroup, fixed-order tree)
+__global__ void __launch_bounds__(256) k_sba_cg_end(const double* __restrict__ x, int n, SbaResult* __restrict__ res) {
+  __shared__ double s[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += x[i] * x[i];
+  const double sum = sba_block_sum(acc, s);
+  if (threadIdx.x == 0) res->x2 = sum;
 }
 
 // Blocked right-looking Cholesky of the lower triangle of the n x n (n % 64 == 0) row-major A in place, with the

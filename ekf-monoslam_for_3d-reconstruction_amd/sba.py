@@ -4,7 +4,9 @@
 system, node 0 fixed, as SysSBA::doSBA (sparse_bundle_adjustment/src/sba.cpp:1312-1585).  `sba_add` is the driver
 (sba_add.cpp:71-290) over the three files the filter's node writes (`formats`), with the deviations of DESIGN.md
 §11.4.  The pseudo-Huber cost (SysSBA::huber) and the pruning of outlying projections (countBad, removeBad,
-reduceTracks) are there as well, off by default.  There is no CPU fallback: without a HIP device the
+reduceTracks) are there as well, off by default (DESIGN.md §11.6).  The linear solver is the dense Cholesky by default;
+`solver="pcg"` is the reference's block-Jacobi preconditioned conjugate gradient (SBA_BLOCK_JACOBIAN_PCG, DESIGN.md
+§11.7), which holds no dense matrix and has no 1024-node limit.  There is no CPU fallback: without a HIP device the
 constructor raises.
 """
 from __future__ import annotations
@@ -18,6 +20,7 @@ from . import formats
 from .capi import EkfError, load_library
 
 REFERENCE_SBA_CAMERA = (2217.0187, 2217.0187, 1280.5, 960.5)     # sba_add.cpp:206-211 (fx, fy, cx, cy)
+SOLVERS = {"cholesky": 0, "pcg": 3}                              # doSBA's useCSparse (SBA_BLOCK_JACOBIAN_PCG = 3)
 
 
 class SbaCamera(C.Structure):
@@ -32,14 +35,23 @@ class BundleAdjuster:
     """One bundle-adjustment problem on the GPU (SysSBA restricted to what sba_add uses)."""
 
     def __init__(self, camera=REFERENCE_SBA_CAMERA, capacity_nodes=256, capacity_points=65536,
-                 capacity_projections=262144, device=0):
+                 capacity_projections=262144, device=0, solver="cholesky", cg_tol=1e-8, cg_max_iters=100):
+        if solver not in SOLVERS:
+            raise ValueError("solver must be 'cholesky' or 'pcg'")
         self._lib = load_library()
         self._h = C.c_void_p()
-        rc = self._lib.ekf_sba_create(C.byref(SbaCamera(*[float(c) for c in camera])), int(capacity_nodes),
-                                      int(capacity_points), int(capacity_projections), int(device), C.byref(self._h))
+        cam = SbaCamera(*[float(c) for c in camera])
+        if solver == "cholesky":
+            rc = self._lib.ekf_sba_create(C.byref(cam), int(capacity_nodes), int(capacity_points),
+                                          int(capacity_projections), int(device), C.byref(self._h))
+        else:
+            rc = self._lib.ekf_sba_create_solver(C.byref(cam), int(capacity_nodes), int(capacity_points),
+                                                 int(capacity_projections), int(device), SOLVERS[solver],
+                                                 C.byref(self._h))
         if rc:
             raise EkfError(rc, self._lib.ekf_sba_last_error(None).decode())
         self.camera = tuple(float(c) for c in camera)
+        self.set_cg(cg_tol, cg_max_iters)
 
     def close(self):
         if self._h:
@@ -138,6 +150,32 @@ class BundleAdjuster:
         self._check(self._lib.ekf_sba_avg_error(self._h, C.byref(a)))
         return a.value
 
+    # --- linear solver ----------------------------------------------------------------
+    @property
+    def solver(self):
+        """"cholesky" or "pcg", fixed when the handle is made."""
+        v = C.c_int()
+        self._check(self._lib.ekf_sba_get_solver(self._h, C.byref(v)))
+        return {n: k for k, n in SOLVERS.items()}[v.value]
+
+    def set_cg(self, tol=1e-8, max_iters=100):
+        """doSBA's initTol and maxCGiters (sba.h:158-159); stored and ignored by the Cholesky solver."""
+        self._check(self._lib.ekf_sba_set_cg(self._h, float(tol), int(max_iters)))
+
+    def get_cg(self):
+        t, m = C.c_double(), C.c_int()
+        self._check(self._lib.ekf_sba_get_cg(self._h, C.byref(t), C.byref(m)))
+        return t.value, m.value
+
+    def cg_log(self):
+        """Per LM iteration of the last run: (CG iterations, the r.s that ended the loop, the bound d0); empty for
+        the Cholesky solver."""
+        n = C.c_int()
+        self._check(self._lib.ekf_sba_get_cg_log(self._h, 0, None, None, None, C.byref(n)))
+        it, dn, d0 = np.zeros(n.value, np.int32), np.zeros(n.value), np.zeros(n.value)
+        self._check(self._lib.ekf_sba_get_cg_log(self._h, n.value, _ptr(it), _ptr(dn), _ptr(d0), C.byref(n)))
+        return it, dn, d0
+
     # --- solving --------------------------------------------------------------------------------------------
     def run(self, niter=10, lam=1e-4):
         """SysSBA::doSBA(niter, lam): the iteration count, -1 for an empty problem."""
@@ -207,7 +245,7 @@ class BundleAdjuster:
 
 
 def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA, every=10, points_out=None,
-            nodes_out=None, device=0, huber=0.0, prune_dist=None):
+            nodes_out=None, device=0, huber=0.0, prune_dist=None, solver="cholesky", cg_tol=1e-8, cg_max_iters=100):
     """The reference's sba_add driver on the GPU.
 
     `points`, `nodes_and_prjcts`, `cams_cov`: paths or file objects of the filter's three files (formats.py), or
@@ -217,8 +255,9 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
     node and once at the end the RMS wrapper runs.  Deviations: points.txt row 0 is an ordinary
     point, a `0  0  0` projection line means no projection, `P0` is a node id.
 
-    Limit (deviation 4): at most 1024 key-frame records, the largest reduced system the
-    single-workgroup triangular solve holds; more raise EkfError (EKF_ERR_ARG) when the handle is created.
+    Limit of the default solver (deviation 4): at most 1024 key-frame records, the largest reduced
+    system the single-workgroup triangular solve holds; more raise EkfError (EKF_ERR_ARG) when the handle is created.
+    `solver="pcg"` has no such limit; `cg_tol` and `cg_max_iters` are doSBA's initTol and maxCGiters.
 
     `huber` (pixels) is set on the handle before the first run (SysSBA::huber; the reference driver leaves it 0).
     With `prune_dist` every call of the RMS wrapper is followed by remove_bad(prune_dist) and, if that removed
@@ -238,7 +277,8 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
     row_of = {r: k for k, r in enumerate(rows)}
     nproj = sum(len(r[2]) for r in records)
     ba = BundleAdjuster(camera, capacity_nodes=max(len(records), 1), capacity_points=max(len(rows), 1),
-                        capacity_projections=max(nproj, 1), device=device)
+                        capacity_projections=max(nproj, 1), device=device, solver=solver, cg_tol=cg_tol,
+                        cg_max_iters=cg_max_iters)
     ba.huber = huber
     if rows:
         ba.add_points(table[rows, :3].astype(np.float64))

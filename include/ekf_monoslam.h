@@ -534,7 +534,8 @@ void* ekf_device_sigma(ekf_filter* f, int* ld);
  *  - points: (x y z) world;  projections: (node, point, u v).  A repeat of a (node, point) pair keeps the first
  *    keypoint (addMonoProj, sba.cpp:133-143); `added` (may be NULL) receives the number of new pairs;
  *  - arguments are checked before the device is touched: EKF_ERR_ARG for bad indices or non-finite values,
- *    EKF_ERR_CAPACITY beyond a capacity (the call then adds nothing);  capacity_nodes <= 1024;
+ *    EKF_ERR_CAPACITY beyond a capacity (the call then adds nothing);  capacity_nodes <= 1024 for the Cholesky
+ *    solver (ekf_sba_create), no such limit for the PCG solver (below);
  *  - ekf_sba_run = SysSBA::doSBA(niter, lambda): *iterations = the iteration count, -1 for an empty problem;
  *    lambda > 0 sets the LM damping, otherwise the last run's value continues (initially 1e-4).  A non-positive
  *    pivot other than a projection-less free node (whose step is 0) is EKF_ERR_NUMERIC: the nodes and points stay
@@ -567,7 +568,25 @@ void* ekf_device_sigma(ekf_filter* f, int* ld);
  *    when there are none;
  *  - ekf_sba_get_projections: the stored projections, point-major and node ascending within a point (the order
  *    of the reference's tracks and their maps); *n = their number, at most max_rows rows are written, and each of
- *    node / point / uv (2 per row) / valid may be NULL. */
+ *    node / point / uv (2 per row) / valid may be NULL.
+ *
+ * Linear solver.  ekf_sba_create gives the dense Cholesky solver.  ekf_sba_create_solver takes
+ * doSBA's useCSparse choice: EKF_SBA_SOLVER_CHOLESKY (0, exactly ekf_sba_create, its 1024-node limit included) or
+ * EKF_SBA_SOLVER_BPCG (3 = SBA_BLOCK_JACOBIAN_PCG): the reduced system kept as 6 x 6 blocks and solved by a conjugate
+ * gradient preconditioned with the inverse diagonal blocks (jacobiBPCG<6>::doBPCG2, bpcg/bpcg.h:238-316).  A PCG handle
+ * holds no dense matrix and takes any capacity_nodes up to INT_MAX / 64.  Any other solver value is EKF_ERR_ARG.
+ *  - ekf_sba_set_cg / ekf_sba_get_cg: doSBA's initTol and maxCGiters (defaults 1e-8 and 100, sba.h:158-159);
+ *    init_tol finite and >= 0, max_iters >= 1, otherwise EKF_ERR_ARG.  A Cholesky handle stores and ignores them;
+ *  - a solve that ends at max_iters without reaching its bound is not an error: the step is applied and the cost
+ *    test of the LM loop accepts or rejects it, as in the reference.  A diagonal block with a non-positive pivot is
+ *    EKF_ERR_NUMERIC, with the state kept as described for ekf_sba_run;
+ *  - ekf_sba_get_cg_log: per iteration of the last run, the CG iterations made, the r . s that ended the loop and
+ *    the bound d0 it was compared with;  *n = the number of rows (0 on a Cholesky handle), at most max_rows are
+ *    written, each of the three arrays may be NULL;
+ *  - in ekf_sba_get_profile the "factor + solve" phase of a PCG handle is the block inverse and the CG. */
+#define EKF_SBA_SOLVER_CHOLESKY 0
+#define EKF_SBA_SOLVER_BPCG 3
+
 typedef struct ekf_sba ekf_sba;
 typedef struct ekf_sba_camera {
   double fx, fy, cx, cy;
@@ -575,6 +594,12 @@ typedef struct ekf_sba_camera {
 
 int ekf_sba_create(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
                    int device, ekf_sba** out);
+int ekf_sba_create_solver(const ekf_sba_camera* K, int capacity_nodes, int capacity_points, int capacity_projections,
+                          int device, int solver, ekf_sba** out);
+int ekf_sba_get_solver(const ekf_sba* s, int* solver);
+int ekf_sba_set_cg(ekf_sba* s, double init_tol, int max_iters);
+int ekf_sba_get_cg(const ekf_sba* s, double* init_tol, int* max_iters);
+int ekf_sba_get_cg_log(const ekf_sba* s, int max_rows, int* cg_iters, double* dn_final, double* d0, int* n);
 void ekf_sba_destroy(ekf_sba* s);
 /* Message of the last failure (s may be NULL: last failure of ekf_sba_create). */
 const char* ekf_sba_last_error(const ekf_sba* s);

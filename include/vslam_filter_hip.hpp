@@ -232,16 +232,18 @@ class VSlamFilterHip {
 
 // SysSbaHip -- header-only mirror of the part of the reference's `sba::SysSBA` (sparse_bundle_adjustment/include/
 // sparse_bundle_adjustment/sba.h) that sba_add drives, over the ekf_sba_* functions of ekf_monoslam.h: monocular
-// projections, node 0 fixed, doSBA with the CHOLMOD solve, calcCost / calcRMSCost, the pseudo-Huber cost and the
-// pruning of outlying projections.  Poses are
-// (x y z qw qx qy qz), points (x y z), as plain double arrays.
+// projections, node 0 fixed, doSBA with the CHOLMOD solve or the block-Jacobi PCG, calcCost /
+// calcRMSCost, the pseudo-Huber cost and the pruning of outlying projections.  Poses are
+// (x y z qw qx qy qz), points (x y z), as plain double arrays.  The linear solver belongs to the handle, so it is a
+// constructor argument: EKF_SBA_SOLVER_CHOLESKY (the default, at most 1024 nodes) or EKF_SBA_SOLVER_BPCG.
 class SysSbaHip {
  public:
   explicit SysSbaHip(double fx, double fy, double cx, double cy, int capacity_nodes = 256,
-                     int capacity_points = 65536, int capacity_projections = 262144, int device = 0) {
+                     int capacity_points = 65536, int capacity_projections = 262144, int device = 0,
+                     int solver = EKF_SBA_SOLVER_CHOLESKY) {
     const ekf_sba_camera K = {fx, fy, cx, cy};
-    if (ekf_sba_create(&K, capacity_nodes, capacity_points, capacity_projections, device, &h_) != EKF_OK)
-      throw std::runtime_error(std::string("ekf_sba_create: ") + ekf_sba_last_error(nullptr));
+    if (ekf_sba_create_solver(&K, capacity_nodes, capacity_points, capacity_projections, device, solver, &h_) != EKF_OK)
+      throw std::runtime_error(std::string("ekf_sba_create_solver: ") + ekf_sba_last_error(nullptr));
   }
   ~SysSbaHip() { ekf_sba_destroy(h_); }
   SysSbaHip(const SysSbaHip&) = delete;
@@ -262,6 +264,28 @@ class SysSbaHip {
     int it = 0;
     check(ekf_sba_run(h_, niter, sLambda, &it));
     return it;
+  }
+  // doSBA(niter, sLambda, useCSparse, initTol, maxCGiters) (sba.cpp:1312): useCSparse 0 (dense Cholesky) and 1
+  // (sparse Cholesky) are this project's Cholesky solver, 3 (SBA_BLOCK_JACOBIAN_PCG) its PCG solver with the two CG
+  // settings; 2 (SBA_GRADIENT) is not supported.  The choice must be the one the handle was constructed with.
+  int doSBA(int niter, double sLambda, int useCSparse, double initTol = 1.0e-8, int maxCGiters = 100) {
+    if (useCSparse == 2) throw std::runtime_error("SysSbaHip::doSBA: useCSparse = 2 (SBA_GRADIENT) is not supported");
+    if (useCSparse != 0 && useCSparse != 1 && useCSparse != EKF_SBA_SOLVER_BPCG)
+      throw std::runtime_error("SysSbaHip::doSBA: useCSparse must be 0, 1 or 3");
+    const int want = useCSparse == EKF_SBA_SOLVER_BPCG ? EKF_SBA_SOLVER_BPCG : EKF_SBA_SOLVER_CHOLESKY;
+    if (want != solver())
+      throw std::runtime_error("SysSbaHip::doSBA: useCSparse does not match the solver the handle was constructed with");
+    if (want == EKF_SBA_SOLVER_BPCG) check(ekf_sba_set_cg(h_, initTol, maxCGiters));
+    return doSBA(niter, sLambda);
+  }
+  int solver() { int v = 0; check(ekf_sba_get_solver(h_, &v)); return v; }
+  // per LM iteration of the last doSBA with the PCG solver: the CG iterations made
+  std::vector<int> cgIterations() {
+    int n = 0;
+    check(ekf_sba_get_cg_log(h_, 0, nullptr, nullptr, nullptr, &n));
+    std::vector<int> v((size_t)n);
+    check(ekf_sba_get_cg_log(h_, n, v.data(), nullptr, nullptr, &n));
+    return v;
   }
   double calcCost() { double c = 0, r = 0; check(ekf_sba_cost(h_, 10000.0, &c, &r)); return c; }
   double calcRMSCost(double dist = 10000.0) { double c = 0, r = 0; check(ekf_sba_cost(h_, dist, &c, &r)); return r; }
