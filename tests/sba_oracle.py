@@ -335,6 +335,42 @@ class SysSBA:
         return np.array([np.concatenate([t, q]) for t, q in zip(self.trans, self.qrot)]).reshape(-1, 7)
 
 
+def solve_refined(A, B, max_steps=20):
+    """Test-only: the linear solve to numpy.longdouble accuracy.  The float64 Cholesky factor is the preconditioner of
+    an iterative refinement whose residual and solution are kept in longdouble, until the correction stops shrinking.
+    Against `SysSBA.solve` this measures how far float64 rounding in the solve alone moves the LM trajectory."""
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError as exc:
+        raise NotPositiveDefinite(str(exc)) from None
+    T = np.longdouble
+    b = B.astype(T)
+
+    def resid(x):
+        out = np.empty(len(b), dtype=T)
+        for r0 in range(0, len(b), 512):                 # row chunks: a 6138 x 6138 longdouble copy would be 600 MB
+            out[r0:r0 + 512] = b[r0:r0 + 512] - A[r0:r0 + 512].astype(T) @ x
+        return out
+
+    x = np.zeros(len(b), dtype=T)
+    last = np.inf
+    for _ in range(max_steps):
+        r = resid(x).astype(np.float64)
+        dx = _tri_solve(L.T, _tri_solve(L, r, lower=True), lower=False)
+        step = float(np.abs(dx).max()) if dx.size else 0.0
+        if not step < last:
+            break
+        x = x + dx.astype(T)
+        last = step
+    return x.astype(np.float64)
+
+
+class RefinedSolve:
+    """Mix-in in front of SysSBA / RobustSysSBA: `solve` is `solve_refined` (test-only, see there)."""
+
+    solve = staticmethod(solve_refined)
+
+
 def sba_add(points_table, records, camera=REFERENCE_SBA_CAMERA, every=10, run=True):
     """The driver (SBANode::addFrame, sba_add.cpp:71-185) with deviation 3: points.txt row 0 is an ordinary point,
     `0 0 0` means no projection, P0 is a node id.  `points_table` is the N x 12 float32 table, `records` the
