@@ -12,3 +12,4 @@ The directory name contains '-', so it is imported through `__graft_entry__.load
 from .capi import (EkfConfig, EkfError, LIB_PATH, declared_symbols, load_library)  # noqa: F401
 from .vslam_filter import VSlamFilter, kinect_config, sim_config  # noqa: F401
 from .sba import BundleAdjuster, REFERENCE_SBA_CAMERA, sba_add  # noqa: F401
+from .keyframes import KeyframeSelector, KeyframeRecorder, KeyframeRecord, KeyframeResult  # noqa: F401

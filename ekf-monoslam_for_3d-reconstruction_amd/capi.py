@@ -12,6 +12,8 @@ HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "ekf_monoslam.h")
 EKF_F32, EKF_F64 = 0, 1
 EKF_OPT_PROPAGATE_STREAMING, EKF_OPT_USE_MFMA, EKF_OPT_PROFILE, EKF_OPT_PIPELINE = 0, 1, 2, 3
 EKF_OPT_SPLIT_BF16, EKF_OPT_FEATURE_NOISE, EKF_OPT_FUSED_LAUNCHES, EKF_OPT_W_RECOMPUTE = 4, 5, 6, 7
+EKF_KF_NONE, EKF_KF_CANDIDATE, EKF_KF_EMIT_CURRENT, EKF_KF_EMIT_CANDIDATE, EKF_KF_EMIT_FIRST = 0, 1, 2, 3, 4
+EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS = 0
 STATUS_NAMES = {0: "EKF_OK", 1: "EKF_ERR_ARG", 2: "EKF_ERR_CAPACITY", 3: "EKF_ERR_DEVICE",
                 4: "EKF_ERR_STATE", 5: "EKF_ERR_NUMERIC", 6: "EKF_ERR_UNSUPPORTED"}
 
@@ -145,6 +147,15 @@ _PROTOS = {
     "ekf_sba_get_log": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),
     "ekf_sba_profile": (C.c_int, [_P, C.c_int]),
     "ekf_sba_get_profile": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "ekf_keyframe_create": (C.c_int, [_P, C.c_float, C.POINTER(_P)]),
+    "ekf_keyframe_destroy": (None, [_P]),
+    "ekf_keyframe_last_error": (C.c_char_p, [_P]),
+    "ekf_keyframe_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
+    "ekf_keyframe_observe": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ekf_keyframe_get_emitted": (C.c_int, [_P, C.POINTER(C.c_int), _P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "ekf_keyframe_get_image": (C.c_int, [_P, _P, C.c_int]),
+    "ekf_keyframe_get_state": (C.c_int, [_P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "ekf_keyframe_reset": (C.c_int, [_P]),
 }
 
 _lib = None

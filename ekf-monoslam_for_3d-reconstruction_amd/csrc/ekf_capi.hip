@@ -26,6 +26,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_shard.hpp"
 #include "ekf_sba.hpp"
+#include "ekf_keyframe.hpp"
 
 namespace ekf {
 
@@ -180,6 +181,8 @@ struct FilterBase {
   virtual int shard_info(ekf_shard_info*) = 0;
   virtual int shard_update(const void*, const int*, int, int) = 0;
   virtual int shard_rebalance() = 0;
+  virtual int kf_create(KfSelector*) = 0;
+  virtual int kf_observe(KfSelector*, int, KfRecord*) = 0;
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -2815,6 +2818,79 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
 
+  // ---- key-frame selection (kernels in ekf_keyframe.hpp) ------------------------------------------------
+  int kf_create(KfSelector* k) override {
+    if (sh_on) FAIL(EKF_ERR_STATE, "ekf_keyframe_create: a sharded filter has no key-frame selector (Sigma[0:7,0:7] lives on one rank)");
+    HIPCHK(hipSetDevice(device));
+    k->device = device;
+    k->img_w = cam.width;
+    k->img_h = cam.height;
+    const size_t px = (size_t)std::max(cam.width, 1) * std::max(cam.height, 1);
+    HIPCHK(hipMalloc(&k->d_state, 2 * sizeof(KfState)));
+    HIPCHK(hipMalloc(&k->d_rec, sizeof(KfRecord)));
+    HIPCHK(hipMalloc(&k->d_cand, px));
+    HIPCHK(hipMalloc(&k->d_emit, px));
+    const KfState s0 = KfSelector::initial();
+    HIPCHK(hipMemcpy(k->d_state, &s0, sizeof(s0), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(k->d_rec, 0, sizeof(KfRecord)));
+    return EKF_OK;
+  }
+  // Point4sba (mono-slam vslamRansac.cpp:1319-1336) from the host's track state, as formats.point4sba_rows
+  void kf_point4sba(std::vector<int>& rows) const {
+    rows.assign(3, 0);
+    for (int i = 0; i < N; ++i) {
+      if (!(in_innovation[i] && coding[i] == 1)) continue;
+      const int r[3] = {real_index[i], (int)center[2 * i], (int)center[2 * i + 1]};
+      if (rows[0] == 0) std::copy(r, r + 3, rows.begin());
+      else if (r[1] < 640 && r[2] < 480) rows.insert(rows.end(), r, r + 3);
+    }
+  }
+  // One probe on the filter's stream, the image grid when a frame is set, ONE read-back (record, status words and -- only
+  // when a predict / measure left them unread -- the track flags), then the host obeys the action word.
+  int kf_observe(KfSelector* k, int frame_id, KfRecord* r) override {
+    if (sh_on) FAIL(EKF_ERR_STATE, "ekf_keyframe_observe: the filter is sharded (Sigma[0:7,0:7] lives on one rank)");
+    HIPCHK(hipSetDevice(device));
+    const bool img = have_frame && frame_w == k->img_w && frame_h == k->img_h;
+    k_keyframe_probe<T><<<1, 64, 0, stream>>>(mu(), S(), ld, frame_id, k->move_thresh, k->d_state + k->parity,
+                                              k->d_state + (k->parity ^ 1), k->d_rec);
+    if (img) {
+      const size_t bytes = (size_t)frame_w * frame_h;
+      const int grid = (int)std::min<size_t>((bytes / 16 + 255) / 256 + 1, 1024);
+      k_keyframe_snapshot<<<grid, 256, 0, stream>>>(k->d_rec, d_frame, k->d_cand, k->d_emit, bytes);
+    }
+    // A failure from here on leaves the rule's state where it was (the roles are not flipped), but the image grid may have
+    // run on a record nobody read: either slot may hold this frame now.  Both stop vouching for their image, so that a
+    // later emit reports EKF_ERR_STATE from ekf_keyframe_get_image rather than pair an old id with a newer frame.
+    auto failed = [&](int rc) { if (img) k->cand_has_image = k->emit_has_image = false; return rc; };
+    { const hipError_t launch = hipGetLastError(); if (launch != hipSuccess) failed(0); HIPCHK(launch); }
+    { int rc = rb_add(r, k->d_rec, sizeof(KfRecord)); if (rc) return failed(rc); }
+    std::vector<unsigned char> tb;
+    const bool fold = trk_dirty && N > 0;
+    if (fold) { tb.resize(N); int rc = rb_add(tb.data(), d_trk, (size_t)N); if (rc) return failed(rc); }
+    { int rc = rb_finish(true); if (rc) return failed(rc); }
+    if (fold) { HIPCHK(hipMemsetAsync(d_trk, 0, (size_t)N, stream)); apply_track(tb); }
+    k->parity ^= 1;
+    switch (r->action) {
+      case kKfCandidate:
+        kf_point4sba(k->cand_rows);
+        k->cand_has_image = img;
+        break;
+      case kKfEmitCandidate:
+        k->emit_rows = k->cand_rows;
+        k->emit_has_image = img && k->cand_has_image;
+        break;
+      case kKfEmitCurrent:
+      case kKfEmitFirst:
+        if (k->keep_current) kf_point4sba(k->emit_rows);
+        else k->emit_rows.assign(3, 0);                      // the literal "0  0  0" (monoslam_ransac.cpp:640, :672)
+        k->emit_has_image = img;
+        break;
+      default: break;
+    }
+    if (r->action >= kKfEmitCurrent) { k->emitted = *r; k->have_emit = true; }
+    return EKF_OK;
+  }
+
   // ---- multi-GPU row-panel sharding ------------------------------------------------
   // One process per GPU; every rank holds the same feature list and runs every resize operation, rank g OWNS the
   // contiguous features [sh_fb[g], sh_fb[g+1]) and keeps valid: the rows of Sigma / W / V of those features (all
@@ -4878,6 +4954,139 @@ int ekf_sba_get_profile(const ekf_sba* s, double* phase_ms, int max_iters, doubl
   const int total = (int)s->impl->iter_ms.size();
   *n = total;
   std::copy(s->impl->iter_ms.begin(), s->impl->iter_ms.begin() + std::min(total, max_iters), iter_ms);
+  return EKF_OK;
+}
+
+// ---- key-frame selection -----------------------------------------------------------------------------
+struct ekf_keyframe { ekf::KfSelector* impl; };
+
+int ekf_keyframe_create(const ekf_filter* f, float move_thresh, ekf_keyframe** out) {
+  if (!out) return EKF_ERR_ARG;
+  *out = nullptr;
+  if (!f || !(move_thresh > 0.f) || !std::isfinite(move_thresh)) {
+    ekf::g_create_error = "ekf_keyframe_create: a filter and a finite move_thresh > 0";
+    return EKF_ERR_ARG;
+  }
+  auto* k = new ekf::KfSelector();
+  k->owner = f->impl;
+  k->move_thresh = move_thresh;
+  const int rc = f->impl->kf_create(k);
+  if (rc != EKF_OK) {
+    ekf::g_create_error = f->impl->err;
+    delete k;
+    return rc;
+  }
+  *out = new ekf_keyframe{k};
+  return EKF_OK;
+}
+
+void ekf_keyframe_destroy(ekf_keyframe* s) {
+  if (!s) return;
+  delete s->impl;
+  delete s;
+}
+
+const char* ekf_keyframe_last_error(const ekf_keyframe* s) {
+  if (!s) return ekf::g_create_error.c_str();
+  return s->impl->err.c_str();
+}
+
+int ekf_keyframe_set_option(ekf_keyframe* s, int option, int value) {
+  if (!s) return EKF_ERR_ARG;
+  if (option != EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS || (value != 0 && value != 1)) {
+    s->impl->err = "ekf_keyframe_set_option: unknown option, or a value other than 0 / 1";
+    return EKF_ERR_ARG;
+  }
+  s->impl->keep_current = value;
+  return EKF_OK;
+}
+
+int ekf_keyframe_observe(ekf_keyframe* s, ekf_filter* f, int frame_id, int* action, float* dist, float* cov) {
+  if (!s || !f) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  if (!action || frame_id < 0) {
+    k->err = "ekf_keyframe_observe: action must not be NULL and frame_id >= 0";
+    return EKF_ERR_ARG;
+  }
+  if (k->owner != f->impl) {
+    k->err = "ekf_keyframe_observe: the selector was created for another filter";
+    return EKF_ERR_ARG;
+  }
+  ekf::KfRecord r{};
+  const int rc = f->impl->kf_observe(k, frame_id, &r);
+  if (rc != EKF_OK) {
+    k->err = f->impl->err;
+    return rc;
+  }
+  *action = r.action;
+  if (dist) *dist = r.dist;
+  if (cov) *cov = r.cov;
+  return EKF_OK;
+}
+
+int ekf_keyframe_get_emitted(const ekf_keyframe* s, int* id, double* pose7, double* cov49, int max_rows, int* prj_rows,
+                             int* n_rows) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  if (max_rows < 0 || (max_rows > 0 && !prj_rows)) {
+    k->err = "ekf_keyframe_get_emitted: max_rows >= 0, and prj_rows with it";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit) {
+    k->err = "ekf_keyframe_get_emitted: no key frame was emitted yet";
+    return EKF_ERR_STATE;
+  }
+  if (id) *id = k->emitted.id;
+  if (pose7) for (int i = 0; i < 7; ++i) pose7[i] = k->emitted.pose[i];
+  if (cov49) for (int r = 0; r < 7; ++r) for (int c = 0; c < 7; ++c) cov49[c * 7 + r] = k->emitted.sig[r * 7 + c];
+  const int total = (int)k->emit_rows.size() / 3;
+  if (n_rows) *n_rows = total;
+  std::copy(k->emit_rows.begin(), k->emit_rows.begin() + 3 * std::min(total, max_rows), prj_rows);
+  return EKF_OK;
+}
+
+int ekf_keyframe_get_image(const ekf_keyframe* s, unsigned char* gray, int stride) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  if (!gray || stride < k->img_w) {
+    k->err = "ekf_keyframe_get_image: gray must not be NULL and stride >= image_width";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit || !k->emit_has_image) {
+    k->err = "ekf_keyframe_get_image: no emitted key frame with an image (ekf_set_frame before ekf_keyframe_observe)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = k->err;
+  HIPCHK(hipSetDevice(k->device));
+  HIPCHK(hipMemcpy2D(gray, (size_t)stride, k->d_emit, (size_t)k->img_w, (size_t)k->img_w, (size_t)k->img_h, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last_vrot3, float* min_cov, int* candidate_id) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  std::string& err = k->err;
+  ekf::KfState st;
+  HIPCHK(hipSetDevice(k->device));
+  HIPCHK(hipMemcpy(&st, k->d_state + k->parity, sizeof(st), hipMemcpyDeviceToHost));
+  if (last_pose7) std::copy(st.last_pose, st.last_pose + 7, last_pose7);
+  if (last_vrot3) std::copy(st.last_vrot, st.last_vrot + 3, last_vrot3);
+  if (min_cov) *min_cov = st.min_cov;
+  if (candidate_id) *candidate_id = st.cand_id;
+  return EKF_OK;
+}
+
+int ekf_keyframe_reset(ekf_keyframe* s) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  std::string& err = k->err;
+  const ekf::KfState s0 = ekf::KfSelector::initial();
+  HIPCHK(hipSetDevice(k->device));
+  HIPCHK(hipMemcpy(k->d_state + k->parity, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  k->cand_rows.clear();
+  k->emit_rows.clear();
+  k->cand_has_image = k->emit_has_image = k->have_emit = false;
+  k->emitted = ekf::KfRecord{};
   return EKF_OK;
 }
 

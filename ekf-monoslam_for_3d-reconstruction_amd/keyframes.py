@@ -1,0 +1,166 @@
+"""Key-frame selection: the per-frame rule of the reference's node (mono-slam
+monoslam_ransac.cpp:585-687) on the device, and a recorder that writes what the node writes.
+
+``KeyframeSelector.observe(frame_id)`` after every update is one small launch on the filter's stream and one
+read-back; the candidate's and the emitted frame's image stay on the device until ``emitted_image()`` asks for
+the one that was selected.  ``KeyframeRecorder`` appends each emitted key frame to ``nodes_and_prjcts.txt`` and
+``cams_cov.txt`` (``formats``) and ``finish()`` adds ``points.txt``: the three files ``sba.sba_add`` reads.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import capi, formats
+from .capi import EkfError
+
+NONE, CANDIDATE, EMIT_CURRENT, EMIT_CANDIDATE, EMIT_FIRST = (capi.EKF_KF_NONE, capi.EKF_KF_CANDIDATE, capi.EKF_KF_EMIT_CURRENT,
+                                                             capi.EKF_KF_EMIT_CANDIDATE, capi.EKF_KF_EMIT_FIRST)
+ACTION_NAMES = {NONE: "NONE", CANDIDATE: "CANDIDATE", EMIT_CURRENT: "EMIT_CURRENT", EMIT_CANDIDATE: "EMIT_CANDIDATE",
+                EMIT_FIRST: "EMIT_FIRST"}
+
+
+@dataclass
+class KeyframeRecord:
+    """One emitted key frame: what a record of nodes_and_prjcts.txt / cams_cov.txt holds."""
+    id: int
+    pose: np.ndarray               # (7,) float32: r, q
+    sigma: np.ndarray              # (7, 7) float32
+    projections: np.ndarray        # (k, 3) int64 rows (real_index, u, v); the single row 0 0 0 = none
+
+
+@dataclass
+class KeyframeResult:
+    action: int
+    dist: float                    # poses_diff against the last key frame
+    cov: float                     # Covariance_Parameter in fp32
+    record: Optional[KeyframeRecord] = None
+
+    @property
+    def emitted(self) -> bool:
+        return self.record is not None
+
+    @property
+    def action_name(self) -> str:
+        return ACTION_NAMES.get(self.action, str(self.action))
+
+
+class KeyframeSelector:
+    """monoslam_ransac.cpp:585-687 for one (unsharded) filter."""
+
+    def __init__(self, filter, move_thresh: float = 18.0, keep_current_projections: bool = False):
+        self._lib = capi.load_library()
+        self._filter = filter
+        self._h = C.c_void_p()
+        rc = self._lib.ekf_keyframe_create(filter._h, float(move_thresh), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.ekf_keyframe_last_error(None)
+            raise EkfError(rc, msg.decode() if msg else "ekf_keyframe_create failed")
+        self.move_thresh = float(move_thresh)
+        self.image_shape = (int(filter._cfg.image_height), int(filter._cfg.image_width))
+        if keep_current_projections:
+            self._check(self._lib.ekf_keyframe_set_option(self._h, capi.EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS, 1))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.ekf_keyframe_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = self._lib.ekf_keyframe_last_error(self._h)
+            raise EkfError(rc, msg.decode() if msg else "")
+
+    def observe(self, frame_id: int) -> KeyframeResult:
+        """Call after the frame's update.  On EMIT_* the result carries the emitted record."""
+        action, dist, cov = C.c_int(0), C.c_float(0), C.c_float(0)
+        self._check(self._lib.ekf_keyframe_observe(self._h, self._filter._h, int(frame_id), C.byref(action),
+                                                   C.byref(dist), C.byref(cov)))
+        res = KeyframeResult(action.value, dist.value, cov.value)
+        if action.value in (EMIT_CURRENT, EMIT_CANDIDATE, EMIT_FIRST):
+            res.record = self.emitted()
+        return res
+
+    def emitted(self) -> KeyframeRecord:
+        """The last emitted key frame (EKF_ERR_STATE before the first)."""
+        kid, n = C.c_int(0), C.c_int(0)
+        pose, cov = np.zeros(7, np.float64), np.zeros(49, np.float64)
+        self._check(self._lib.ekf_keyframe_get_emitted(self._h, C.byref(kid), pose.ctypes.data_as(C.c_void_p),
+                                                       cov.ctypes.data_as(C.c_void_p), 0, None, C.byref(n)))
+        rows = np.zeros((n.value, 3), np.int32)                    # the number of rows first, then a buffer that holds them
+        self._check(self._lib.ekf_keyframe_get_emitted(self._h, None, None, None, n.value,
+                                                       rows.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return KeyframeRecord(kid.value, pose.astype(np.float32), cov.reshape(7, 7).T.astype(np.float32),
+                              rows[:n.value].astype(np.int64))
+
+    def emitted_image(self) -> np.ndarray:
+        """The image of the last emitted key frame, uint8 (height, width): the frame that was set when it was observed."""
+        out = np.zeros(self.image_shape, np.uint8)
+        self._check(self._lib.ekf_keyframe_get_image(self._h, out.ctypes.data_as(C.c_void_p), out.strides[0]))
+        return out
+
+    def state(self) -> dict:
+        pose, vrot = np.zeros(7, np.float32), np.zeros(3, np.float32)
+        mc, cid = C.c_float(0), C.c_int(0)
+        self._check(self._lib.ekf_keyframe_get_state(self._h, pose.ctypes.data_as(C.c_void_p), vrot.ctypes.data_as(C.c_void_p),
+                                                     C.byref(mc), C.byref(cid)))
+        return {"last_pose": pose, "last_vrot": vrot, "min_cov": mc.value, "candidate_id": cid.value}
+
+    def reset(self):
+        self._check(self._lib.ekf_keyframe_reset(self._h))
+
+
+def write_pgm(path: str, gray) -> None:
+    """Binary P5."""
+    g = np.ascontiguousarray(gray, np.uint8)
+    with open(path, "wb") as fh:
+        fh.write(b"P5\n%d %d\n255\n" % (g.shape[1], g.shape[0]))
+        fh.write(g.tobytes())
+
+
+class KeyframeRecorder:
+    """What the node writes around the selector: ``observe()`` per frame, ``finish()`` at the end."""
+
+    def __init__(self, selector: KeyframeSelector, directory: str, images: bool = False):
+        self.selector = selector
+        self.directory = directory
+        self.images = bool(images)
+        os.makedirs(directory, exist_ok=True)
+        self.nodes_path = os.path.join(directory, "nodes_and_prjcts.txt")
+        self.covs_path = os.path.join(directory, "cams_cov.txt")
+        self.points_path = os.path.join(directory, "points.txt")
+        open(self.nodes_path, "w").close()
+        open(self.covs_path, "w").close()
+        self.ids = []
+
+    def observe(self, frame_id: int) -> KeyframeResult:
+        res = self.selector.observe(frame_id)
+        if res.emitted:
+            self.append(res.record)
+            if self.images:
+                write_pgm(os.path.join(self.directory, "%d.pgm" % res.record.id), self.selector.emitted_image())
+        return res
+
+    def append(self, record: KeyframeRecord) -> None:
+        prj = record.projections
+        none = len(prj) == 0 or (len(prj) == 1 and not prj[0].any())
+        with open(self.nodes_path, "a") as fh:
+            fh.write(formats.pose_record(record.id, record.pose, None if none else prj))
+        with open(self.covs_path, "a") as fh:
+            fh.write(formats.camera_cov_record(record.sigma))
+        self.ids.append(int(record.id))
+
+    def finish(self):
+        """points.txt from the filter's table; (points, nodes_and_prjcts, cams_cov) as ``sba.sba_add`` takes them."""
+        formats.write_points(self.points_path, self.selector._filter.getPointsTable())
+        return self.points_path, self.nodes_path, self.covs_path

@@ -624,6 +624,56 @@ int ekf_sba_get_log(const ekf_sba* s, int max_rows, double* rows, int* n);
 int ekf_sba_profile(ekf_sba* s, int enable);
 int ekf_sba_get_profile(const ekf_sba* s, double* phase_ms, int max_iters, double* iter_ms, int* n);
 
+/* ---- key-frame selection ----------------------------------------------------------------------
+ * The per-frame rule of the reference's node (mono-slam monoslam_ransac.cpp:585-687 with quat2vec / poses_diff,
+ * :40-60): after every update the caller passes its frame id, and the selector decides whether a frame becomes a key
+ * frame, keeping the lowest-covariance pose of the half-to-full move_thresh window as the candidate.  The rule's state
+ * (last pose, last rotation vector, the smallest covariance figure, the candidate's pose and 7 x 7 block) and the
+ * candidate's / the emitted frame's image live on the device: one observe is one small launch on the filter's stream, one
+ * image launch when a frame is set (ekf_set_frame) and ONE synchronisation.  Everything is fp32 whatever the filter's
+ * dtype.  The selector belongs to the filter it was created for; it must be observed with that filter and may outlive it
+ * only to be read and destroyed.
+ *  - create: move_thresh finite and > 0 (the reference's MoveThresh is 18).  A sharded filter is EKF_ERR_STATE (here
+ *    and at observe): Sigma[0:7,0:7] lives on one rank, a collective selector does not exist;
+ *  - set_option: EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS (0 / 1, default 0).  An emit of the CURRENT frame writes the single
+ *    projection row "0 0 0" as the reference does (:640, :672); with 1 it carries the frame's own Point4sba rows;
+ *  - observe: frame_id >= 0 is the caller's numbering (the reference counts from 1; ids below 5 may be emitted without
+ *    a candidate).  *action = enum ekf_keyframe_action, *dist = poses_diff against the last key frame, *cov = the
+ *    covariance figure of ekf_covariance_parameter in fp32 (dist / cov may be NULL).  The status words of earlier
+ *    updates are read in the same round trip, as the getters do.  A failed observe leaves the rule's state, the
+ *    candidate's and the last emitted record unchanged; when a frame was set, the image launch may have run on a record
+ *    nobody read, so the stored images are no longer vouched for: get_image is EKF_ERR_STATE for the last emit and for
+ *    an emit of the candidate stored before the failure (its id, pose, block and rows are still delivered);
+ *  - get_emitted: the last emitted key frame: its id, pose (7), Sigma[0:7,0:7] (49, column-major as
+ *    ekf_get_sigma_block) and its projection rows (real_index, u, v; 3 ints per row).  *n_rows = their number, at most
+ *    max_rows rows are written; every output may be NULL.  EKF_ERR_STATE before the first emit;
+ *  - get_image: the emitted key frame's image, image_height rows of image_width bytes, `stride` bytes apart: the one
+ *    copy an image makes to the host.  EKF_ERR_STATE when nothing was emitted or no frame had been set for it;
+ *  - get_state: last_pose (7), last_vrot (3), min_cov and the candidate id (0: none yet), each may be NULL;
+ *  - reset: back to the state after create (options kept).
+ * Null handles and out-of-range arguments are EKF_ERR_ARG before the device is touched. */
+typedef struct ekf_keyframe ekf_keyframe;
+enum ekf_keyframe_action {
+  EKF_KF_NONE = 0,            /* nothing stored, nothing emitted                                                  */
+  EKF_KF_CANDIDATE = 1,       /* this frame is the new candidate                                                  */
+  EKF_KF_EMIT_CURRENT = 2,    /* key frame = this frame (its covariance is within 0.000085 of the candidate's)    */
+  EKF_KF_EMIT_CANDIDATE = 3,  /* key frame = the stored candidate                                                 */
+  EKF_KF_EMIT_FIRST = 4       /* key frame = this frame, no candidate and frame_id < 5                            */
+};
+#define EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS 0
+
+int ekf_keyframe_create(const ekf_filter* f, float move_thresh, ekf_keyframe** out);
+void ekf_keyframe_destroy(ekf_keyframe* s);
+/* Message of the last failure (s may be NULL: last failure of ekf_keyframe_create). */
+const char* ekf_keyframe_last_error(const ekf_keyframe* s);
+int ekf_keyframe_set_option(ekf_keyframe* s, int option, int value);
+int ekf_keyframe_observe(ekf_keyframe* s, ekf_filter* f, int frame_id, int* action, float* dist, float* cov);
+int ekf_keyframe_get_emitted(const ekf_keyframe* s, int* id, double* pose7, double* cov49, int max_rows, int* prj_rows,
+                             int* n_rows);
+int ekf_keyframe_get_image(const ekf_keyframe* s, unsigned char* gray, int stride);
+int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last_vrot3, float* min_cov, int* candidate_id);
+int ekf_keyframe_reset(ekf_keyframe* s);
+
 #ifdef __cplusplus
 }
 #endif

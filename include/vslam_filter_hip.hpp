@@ -314,3 +314,66 @@ class SysSbaHip {
   void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_sba_last_error(h_)); }
   ekf_sba* h_ = nullptr;
 };
+
+// KeyframeSelectorHip -- header-only mirror of the node's key-frame rule (mono-slam monoslam_ransac.cpp:585-687) over
+// the ekf_keyframe_* functions of ekf_monoslam.h: observe(frameId) after every update() is one small
+// launch on the filter's stream and one read-back; the candidate's and the emitted frame's image stay on the device.
+// The selector must not outlive the use of its filter (observe needs it); values are plain float / int arrays.
+class KeyframeSelectorHip {
+ public:
+  struct Emitted {
+    int id = 0;
+    float pose[7] = {};                 // r, q
+    float cov[49] = {};                 // Sigma[0:7,0:7], column-major
+    std::vector<int> projections;       // rows (real_index, u, v); the single row 0 0 0 = none
+  };
+  struct Result {
+    int action = EKF_KF_NONE;           // enum ekf_keyframe_action
+    float dist = 0, cov = 0;            // poses_diff against the last key frame, Covariance_Parameter
+    bool emitted() const { return action == EKF_KF_EMIT_CURRENT || action == EKF_KF_EMIT_CANDIDATE || action == EKF_KF_EMIT_FIRST; }
+  };
+
+  explicit KeyframeSelectorHip(VSlamFilterHip& filter, float MoveThresh = 18.f, bool keep_current_projections = false)
+      : f_(filter.handle()) {
+    if (ekf_keyframe_create(f_, MoveThresh, &h_) != EKF_OK)
+      throw std::runtime_error(std::string("ekf_keyframe_create: ") + ekf_keyframe_last_error(nullptr));
+    if (keep_current_projections) check(ekf_keyframe_set_option(h_, EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS, 1));
+  }
+  ~KeyframeSelectorHip() { ekf_keyframe_destroy(h_); }
+  KeyframeSelectorHip(const KeyframeSelectorHip&) = delete;
+  KeyframeSelectorHip& operator=(const KeyframeSelectorHip&) = delete;
+
+  Result observe(int frameId) {
+    Result r;
+    check(ekf_keyframe_observe(h_, f_, frameId, &r.action, &r.dist, &r.cov));
+    return r;
+  }
+  // the last emitted key frame: what one record of nodes_and_prjcts.txt / cams_cov.txt holds
+  Emitted emitted() {
+    Emitted e;
+    double pose[7], cov[49];
+    int n = 0;
+    check(ekf_keyframe_get_emitted(h_, &e.id, pose, cov, 0, nullptr, &n));
+    e.projections.resize(3 * (size_t)n);
+    check(ekf_keyframe_get_emitted(h_, nullptr, nullptr, nullptr, n, e.projections.data(), &n));
+    std::copy(pose, pose + 7, e.pose);
+    std::copy(cov, cov + 49, e.cov);
+    return e;
+  }
+  // the emitted key frame's image: height rows of width bytes
+  std::vector<unsigned char> emittedImage(int width, int height) {
+    std::vector<unsigned char> g((size_t)width * height);
+    check(ekf_keyframe_get_image(h_, g.data(), width));
+    return g;
+  }
+  void state(float last_pose[7], float last_vrot[3], float* min_cov, int* candidate_id) {
+    check(ekf_keyframe_get_state(h_, last_pose, last_vrot, min_cov, candidate_id));
+  }
+  void reset() { check(ekf_keyframe_reset(h_)); }
+  ekf_keyframe* handle() { return h_; }
+
+ private:
+  void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_keyframe_last_error(h_)); }
+  ekf_filter* f_ = nullptr;
+  ekf_keyframe* h_ = nullptr;
+};
