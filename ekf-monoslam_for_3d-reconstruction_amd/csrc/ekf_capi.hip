@@ -312,7 +312,6 @@ struct Filter : FilterBase {
   int opt_step_fused = 1;
   struct StepPlan { int nblk = 0, s1 = 0; std::vector<int> off, cnt; } sfp;
   int* d_sf_lists = nullptr;
-  bool sf_now = false;                                  // this update's chain may take the fused step (set by update())
   unsigned long long* d_small_stamps = nullptr;         // EKF_SMALL_STAMPS=1: phase stamps of its workgroup 0 (ekf_peek_workspace, which = 3)
   unsigned small_gate_total = 0;                        // arrivals the gate word (d_status[9]) has seen when every launch so far is over
   int opt_su_tail = 1;                                  // EKF_SU_TAIL=0: k_state_update as its own launch on the second stream beside the last downdate (round 5)
@@ -323,12 +322,10 @@ struct Filter : FilterBase {
   int* d_td_blocks = nullptr;
   std::vector<int> td_off, td_cnt;                      // per block step: its list of (I, K) blocks inside d_td_blocks
   int td_nblk = 0, td_nchunks = 0, td_cend[8] = {};
-  int chain_diag_ahead = -1;                            // block step whose diagonal factor the last k_trail_diag launch has already done
   // EKF_SYRK_STAGGER="h,m": de-phasing of the bf16x6 downdate's workgroups (Syrk6Args).  Round 6, N = 1000, knob A/B: every
   // (0, m) with m = 1 .. 6 measures 0.897-0.903 ms per step against 0.917-0.922 without; a late second half (h > 0) gains nothing
   int opt_syrk_stag_half = 0, opt_syrk_stag_mod4 = 2;
   int opt_solve_s2 = 1;                                 // EKF_SOLVE_S2: latency-bound solve launches on two wave groups (halves of K)
-  bool solve_s2_now = false;
   // A solve launch of under ~one round of tiles is bounded by the K steps of its heaviest tile: two wave groups per
   // workgroup then take half of K each (k_gemm_mfma<.., S2>).  The rule only looks at the chunk width and the size of the
   // WHOLE state (never at the rows one rank holds), so the plain and the sharded path sum every element in the same order.
@@ -337,7 +334,6 @@ struct Filter : FilterBase {
   }
   int opt_fused = 1;                                    // EKF_OPT_FUSED_LAUNCHES: k_predict_fused, k_solve_state_oneblock, k_update_oneblock_small
   int opt_solve_one_per_cu = 1;                         // EKF_SOLVE_ONE_PER_CU: the last solve on one workgroup per CU when it has 1 .. 2 tiles per CU
-  bool solve_one_per_cu_now = false;
   int opt_wrecompute = 1;                               // EKF_OPT_W_RECOMPUTE / EKF_W_RECOMPUTE: next chunk's W re-evaluated from the downdated Sigma
   int opt_row_gemv = 1;                                 // EKF_ROW_GEMV=0: the innovation-row update through the tile GEMM (A/B, bit-identity check)
   int opt_fuse_wu = 1;                                  // EKF_FUSE_WU: 0 never, 1 every overlapped chunk but the one before the last, 2 every overlapped chunk
@@ -345,11 +341,8 @@ struct Filter : FilterBase {
   int opt_pipeline = -1;                                 // -1 auto: on when the chain has >= 8 block steps
   int* d_tilemap = nullptr;                             // work lists: [lower-tri super-tiles | solve heavy-first]
   int tilemap_nt = 0, tilemap_ntc = 0, tri_count = 0, solve_off = 0;
-  const T* cur_z = nullptr;                              // measured pixels / list of the update in flight
-  const int* cur_midx = nullptr;
   int w_zeroed_n = -1;                                   // n for which the pad rows of W were last cleared
   int* d_counters = nullptr;                            // one work-queue head per queued launch of an update
-  int counter_next = 0;
   int num_cus = 256, reserved_cus = 32;
   // profiling
   struct Pending { int kid; hipEvent_t a, b; };
@@ -1466,35 +1459,88 @@ struct Filter : FilterBase {
   }
 
   // ---- dense tile GEMM dispatch -----------------------------------------------------------
-  // C[rows x cols] = beta C + alpha A op(B); rows, cols multiples of the tile.
+  // One launch of the tile GEMM C[rows x cols] = beta C + alpha A op(B); rows, cols multiples of the tile.  tri .. zcol_end
+  // and the image triple are GemmArgs' (ekf_dense.hpp); a call site names what it uses, the rest is zero.
+  struct GemmCall {
+    const T* A = nullptr; int lda = 0;
+    const T* B = nullptr; int ldb = 0;
+    T* C = nullptr; int ldc = 0;
+    int rows = 0, cols = 0, K = 0;
+    T alpha = T(1), beta = T(0);
+    int tri = TRI_ALL, row_off = 0, col_off = 0, ktri = KTRI_FULL, ktile_off = 0;
+    int zrow = 0, zcol_end = 0;
+    const int* tile_list = nullptr; int ntiles = 0;     // queued launch: the list, and its work-queue head
+    int* counter = nullptr;                             // (UpdateCtx::take_queue(); none left: the plain grid)
+    void* img = nullptr; int img_nkc = 0, img_c0 = 0;
+    bool two_groups = false;                            // ROLE_SOLVE: two wave groups per workgroup (want_solve_s2)
+    bool one_per_cu = false;                            // ROLE_SOLVE, queued: one workgroup per CU (solve_shape)
+    hipStream_t st = nullptr;                           // null: the main stream
+  };
+  // Everything an update decides before its first launch: filled once by plan_update(), a local of update() / shard_update()
+  struct Rows { int r0, count; };
+  struct UpdatePlan {
+    int M = 0, plane = 0;
+    int nb = 0, tile = 0, m = 0, m_pad = 0, npad_live = 0, nsteps = 0;
+    int nchunks = 1, cend[8] = {};                      // chunk ends in block steps (plan_chunks)
+    ChunkTab tab{};                                     // ... in rows
+    int strip_rows = 0;                                 // rows of the widest chunk: those of the identity strip under S
+    int ntr = 0, ntc = 0;                               // row / column tiles of the solve
+    bool oneblock = false, allinone = false, onelaunch = false;   // one diagonal block: see plan_update()
+    int small_rc = 0, small_nchunk = 0, small_nt64 = 0; // onelaunch: small_chunking(), and the 64 x 64 lower tiles of Sigma
+    bool recompute = false;                             // EKF_OPT_W_RECOMPUTE is in force (both paths: the sequential form)
+    // sharded step: own state rows [r0, r1), the tile-padded panel [p0, p0 + prows), and {camera tile, panel, innovation block}
+    int r0 = 0, r1 = 0, p0 = 0, prows = 0;
+    Rows ranges[3] = {};
+    bool sym_panel = false, shard_split = false;
+    int c0(int g) const { return (g ? cend[g - 1] : 0) * nb; }
+    int c1(int g) const { return cend[g] * nb; }
+  };
+  // What an update carries from one launch to the next: lives on the stack of update() / shard_update()
+  struct UpdateCtx {
+    const T* z;                                         // measured pixels and list of this update (device memory)
+    const int* midx;
+    int* counters;                                      // one work-queue head per queued launch (cleared by the update's first launch)
+    int counter_next = 0;
+    bool step_fused = false;                            // the chain may take the fused block step (prepare_chain)
+    int diag_ahead = -1;                                // block step whose diagonal factor the last k_trail_diag launch has already done
+    struct { int step = -1, c0 = 0, c1 = 0; } pending;  // trailing update a chunk left to the next chain_steps call
+    bool row_pending = false;                           // sharded, sequential form: the innovation row still waits for its chunk
+    bool queue_room(int ints = 8) const { return counter_next + ints <= kQueueCounters; }
+    int* take_queue() {
+      if (!queue_room()) return nullptr;
+      counter_next += 8;
+      return counters + counter_next - 8;
+    }
+  };
+
   // TM x TN: MFMA tile shape (64 or 128 each); the VALU path always uses 64 x 64.
   template <int ROLE, bool BT, int TM = 128, int TN = 128>
-  void gemm(const T* A, int lda, const T* B, int ldb, T* C, int ldc, int rows, int cols, int K, T alpha, T beta,
-            int tri, int row_off, int col_off, int ktri, int ktile_off = 0, hipStream_t st = nullptr,
-            const int* tile_list = nullptr, int ntiles = 0, int zrow = 0, int zcol_end = 0, void* img = nullptr,
-            int img_nkc = 0, int img_c0 = 0) {
-    GemmArgs g{A, lda, B, ldb, C, ldc, K, double(alpha), double(beta), tri, row_off, col_off, ktri, ktile_off,
-               nullptr, 0, nullptr, zrow, zcol_end, (ROLE == ROLE_DOWNDATE) ? 1 : 0};
-    g.img = img; g.img_nkc = img_nkc; g.img_c0 = img_c0;
-    if (!st) st = stream;
+  void gemm(const GemmCall& c) {
+    GemmArgs g{};
+    g.A = c.A; g.lda = c.lda; g.B = c.B; g.ldb = c.ldb; g.C = c.C; g.ldc = c.ldc;
+    g.K = c.K; g.alpha = double(c.alpha); g.beta = double(c.beta);
+    g.tri = c.tri; g.row_off = c.row_off; g.col_off = c.col_off; g.ktri = c.ktri; g.ktile_off = c.ktile_off;
+    g.zrow = c.zrow; g.zcol_end = c.zcol_end;
+    g.stagger = (ROLE == ROLE_DOWNDATE) ? 1 : 0;
+    g.img = c.img; g.img_nkc = c.img_nkc; g.img_c0 = c.img_c0;
+    hipStream_t st = c.st ? c.st : stream;
     const bool mf = kIsF32 && opt_mfma;
-    dim3 grid(cols / (mf ? TN : 64), rows / (mf ? TM : 64));
-    if (tile_list && counter_next + 8 <= kQueueCounters) {
-      g.tile_map = tile_list;
-      g.ntiles = ntiles;
-      g.counter = d_counters + counter_next;
-      counter_next += 8;
+    dim3 grid(c.cols / (mf ? TN : 64), c.rows / (mf ? TM : 64));
+    if (c.tile_list && c.counter) {
+      g.tile_map = c.tile_list;
+      g.ntiles = c.ntiles;
+      g.counter = c.counter;
       // persistent grid: two workgroups per CU the stream may use
       const bool side = (st == stream_b);
       int wgs = 2 * (side ? (num_cus - reserved_cus) : num_cus);
-      if (ROLE == ROLE_SOLVE && solve_one_per_cu_now) wgs = num_cus;      // (see the last chunk's solve in update())
-      grid = dim3(std::min(ntiles, wgs), 1);
+      if (ROLE == ROLE_SOLVE && c.one_per_cu) wgs = num_cus;
+      grid = dim3(std::min(c.ntiles, wgs), 1);
     }
     if constexpr (kIsF32) {
       if (opt_mfma) {
         if constexpr (ROLE == ROLE_SOLVE) {
-          ++launch_cnt[solve_s2_now ? EKF_LAUNCH_SOLVE_TWO_GROUPS : EKF_LAUNCH_SOLVE];
-          if (solve_s2_now) {
+          ++launch_cnt[c.two_groups ? EKF_LAUNCH_SOLVE_TWO_GROUPS : EKF_LAUNCH_SOLVE];
+          if (c.two_groups) {
             k_gemm_mfma<ROLE, BT, TM, TN, true><<<grid, 512, 0, st>>>(g);
             return;
           }
@@ -1527,7 +1573,10 @@ struct Filter : FilterBase {
         return;
       }
     }
-    gemm<ROLE_PANEL, false, 64, 128>(P, ldy, Dj, nb, P, ldy, vrows, nb, nb, T(1), T(0), 0, 0, 0, 0, 0, st);
+    GemmCall c;
+    c.A = P; c.lda = ldy; c.B = Dj; c.ldb = nb; c.C = P; c.ldc = ldy;
+    c.rows = vrows; c.cols = nb; c.K = nb; c.st = st;
+    gemm<ROLE_PANEL, false, 64, 128>(c);
   }
 
   // Work lists for the queued GEMMs: (1) lower-triangular tiles of an nt x nt grid in 8x8
@@ -1666,9 +1715,9 @@ struct Filter : FilterBase {
     return tab;
   }
 
-  // W, S (and nu) for a measured set already resident in d_midx / d_z.
-  int build_innovation(int M, int plane, bool with_nu, int* m_out, int* m_pad_out, const ChunkTab* tab = nullptr,
-                       int strip_rows = 0, bool w_only = false) {
+  // W, S (and nu = zp - h, `with_nu`) for the measured list `ip` (device memory).
+  int build_innovation(const T* zp, const int* ip, int M, int plane, bool with_nu, int* m_out, int* m_pad_out,
+                       const ChunkTab* tab = nullptr, int strip_rows = 0, bool w_only = false) {
     const int nb = NB();
     const int m = 2 * M + (plane ? 3 : 0);
     const int m_pad = round_up(m, nb);
@@ -1680,9 +1729,6 @@ struct Filter : FilterBase {
       HIPCHK(hipMemsetAsync(d_W + (size_t)n * ldy, 0, (size_t)(npad_live - n + nb) * ldy * sizeof(T), stream));
       w_zeroed_n = n;
     }
-    const T* zp = cur_z ? cur_z : d_z;
-    const int* ip = cur_midx ? cur_midx : d_midx;
-    if (with_nu) counter_next = 0;
     // small problems are latency-bound: fewer rows / features per workgroup so that the grid fills the chip
     const bool small = (size_t)n * m_pad < ((size_t)1 << 22);
     {
@@ -1728,8 +1774,8 @@ struct Filter : FilterBase {
       }
     }
     HIPCHK(hipGetLastError());
-    *m_out = m;
-    *m_pad_out = m_pad;
+    if (m_out) *m_out = m;
+    if (m_pad_out) *m_pad_out = m_pad;
     return EKF_OK;
   }
 
@@ -1772,7 +1818,7 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
   // true: launched (and the factor of step + 1 is done); false: this step keeps the separate launches
-  bool launch_trail_diag(int step, int m, hipStream_t sc_) {
+  bool launch_trail_diag(UpdateCtx& ux, int step, int m, hipStream_t sc_) {
     if constexpr (kIsF32) {
       if (!trail_diag_ok() || NB() != 128 || td_nblk == 0 || step + 1 >= td_nblk || td_cnt[step] < td_min_blocks ||
           td_cnt[step] > td_max_blocks)
@@ -1785,7 +1831,7 @@ struct Filter : FilterBase {
       Scope sc(this, KID_CHOL_TRAILING, sc_);
       ++launch_cnt[EKF_LAUNCH_CHAIN_TRAIL_DIAG];
       k_trail_diag<<<a.nblocks + 1, 1024, kChainLds, sc_>>>(a);
-      chain_diag_ahead = step + 1;
+      ux.diag_ahead = step + 1;
       return true;
     }
     return false;
@@ -1826,9 +1872,9 @@ struct Filter : FilterBase {
     sfp.nblk = nblk; sfp.s1 = s1;
     return EKF_OK;
   }
-  bool launch_step_fused(int step, int m, hipStream_t sc_) {
+  bool launch_step_fused(const UpdateCtx& ux, int step, int m, hipStream_t sc_) {
     if constexpr (kIsF32) {
-      if (!sf_now || sfp.nblk == 0 || step >= sfp.nblk || sfp.cnt[step] > num_cus / 2 || sc_ != stream) return false;   // (every workgroup resident, with room to spare)
+      if (!ux.step_fused || sfp.nblk == 0 || step >= sfp.nblk || sfp.cnt[step] > num_cus / 2 || sc_ != stream) return false;   // (every workgroup resident, with room to spare)
       StepFusedArgs a{};
       a.Y = d_Y; a.ldy = ldy; a.Dj = d_Dinv + (size_t)step * 128 * 128; a.status = d_status; a.m = m; a.j = step;
       a.wl = d_sf_lists + sfp.off[step]; a.nwg = sfp.cnt[step];
@@ -1842,35 +1888,37 @@ struct Filter : FilterBase {
     }
     return false;
   }
-  struct PendingTrailing { int step = -1, c0 = 0, c1 = 0; } chain_pending;
-  void chain_trailing(int step, int c0, int c1, int m, int m_pad, hipStream_t sc_, bool allow_fused) {
+  void chain_trailing(UpdateCtx& ux, int step, int c0, int c1, int m, int m_pad, hipStream_t sc_, bool allow_fused) {
     const int nb = NB();
     T* Y = d_Y;
     const int j = step * nb, r0 = j + nb;
     const int vrows = m_pad - c0, tcols = m_pad - r0;
     if (r0 >= m_pad || tcols <= 0) return;
-    if (allow_fused && launch_trail_diag(step, m, sc_)) return;       // the update of this step and the factor of the next one as one launch
+    if (allow_fused && launch_trail_diag(ux, step, m, sc_)) return;       // the update of this step and the factor of the next one as one launch
     Scope sc(this, KID_CHOL_TRAILING, sc_);                            // Y[r0.., r0:] -= P P_S^T; strip rows stop at c1
     const T* P = Y + (size_t)r0 * ldy + j;
     T* C = Y + (size_t)r0 * ldy + r0;
     ++launch_cnt[EKF_LAUNCH_CHAIN_STEP];
-    gemm<ROLE_TRAILING, false, 64, 64>(P, ldy, P, ldy, C, ldy, vrows, tcols, nb, T(-1), T(1), 1, r0, r0, 0, 0,
-                                       sc_, nullptr, 0, m_pad, c1);
+    GemmCall g;
+    g.A = P; g.lda = ldy; g.B = P; g.ldb = ldy; g.C = C; g.ldc = ldy;
+    g.rows = vrows; g.cols = tcols; g.K = nb; g.alpha = T(-1); g.beta = T(1);
+    g.tri = TRI_LOWER; g.row_off = r0; g.col_off = r0; g.zrow = m_pad; g.zcol_end = c1; g.st = sc_;
+    gemm<ROLE_TRAILING, false, 64, 64>(g);
   }
-  void chain_steps(int step0, int step1, int c0, int c1, int m, int m_pad, hipStream_t sc_, bool skip_panel = false,
-                   bool defer_last = false) {
+  void chain_steps(UpdateCtx& ux, int step0, int step1, int c0, int c1, int m, int m_pad, hipStream_t sc_,
+                   bool skip_panel = false, bool defer_last = false) {
     const int nb = NB();
     T* Y = d_Y;
-    if (chain_pending.step >= 0) {
-      chain_trailing(chain_pending.step, chain_pending.c0, chain_pending.c1, m, m_pad, sc_, true);
-      chain_pending.step = -1;
+    if (ux.pending.step >= 0) {
+      chain_trailing(ux, ux.pending.step, ux.pending.c0, ux.pending.c1, m, m_pad, sc_, true);
+      ux.pending.step = -1;
     }
     for (int step = step0; step < step1; ++step) {
-      if (!skip_panel && !defer_last && chain_diag_ahead != step && launch_step_fused(step, m, sc_)) continue;
+      if (!skip_panel && !defer_last && ux.diag_ahead != step && launch_step_fused(ux, step, m, sc_)) continue;
       const int j = step * nb;
       T* Ajj = Y + (size_t)j * ldy + j;
       T* Dj = d_Dinv + (size_t)step * nb * nb;
-      if (chain_diag_ahead != step) {
+      if (ux.diag_ahead != step) {
         Scope sc(this, KID_CHOL_DIAG, sc_);
         ++launch_cnt[EKF_LAUNCH_CHAIN_STEP];
         if (nb == 128) {
@@ -1898,9 +1946,9 @@ struct Filter : FilterBase {
         launch_panel(P, Dj, vrows, sc_);
       }
       if (defer_last && step == step1 - 1 && r0 < m_pad) {
-        chain_pending.step = step; chain_pending.c0 = c0; chain_pending.c1 = c1;
+        ux.pending.step = step; ux.pending.c0 = c0; ux.pending.c1 = c1;
       } else {
-        chain_trailing(step, c0, c1, m, m_pad, sc_, !skip_panel);
+        chain_trailing(ux, step, c0, c1, m, m_pad, sc_, !skip_panel);
       }
     }
   }
@@ -1927,8 +1975,10 @@ struct Filter : FilterBase {
         return;
       }
     }
-    gemm<ROLE_WUPDATE, false, 64, 128>(d_V + yrow + c0, ldy, d_Y + (size_t)c1 * ldy + c0, ldy, d_W + yrow + c1, ldy, NB(),
-                                       m_pad - c1, c1 - c0, T(-1), T(1), 0, 0, 0, 0, 0, ss);
+    GemmCall g;
+    g.A = d_V + yrow + c0; g.lda = ldy; g.B = d_Y + (size_t)c1 * ldy + c0; g.ldb = ldy; g.C = d_W + yrow + c1; g.ldc = ldy;
+    g.rows = NB(); g.cols = m_pad - c1; g.K = c1 - c0; g.alpha = T(-1); g.beta = T(1); g.st = ss;
+    gemm<ROLE_WUPDATE, false, 64, 128>(g);
   }
 
   // EKF_OPT_SPLIT_BF16: Sigma -= V_g V_g^T for chunk [c0, c1) on the bf16 matrix pipe at fp32 accuracy (ekf_syrk6.hpp), over
@@ -1936,7 +1986,7 @@ struct Filter : FilterBase {
   // bf16 per fp32, one 12 KB record per 128 rows x 16 columns; else the solve's tiles have written it).  Rows of Sigma valid
   // here: [0, cam_rows) and [r0, r1).  `work`: the flop the launch adds to prof_work.  `rider`: the innovation row update of
   // the chunk in the same launch (launch_row_update's sums); `su_tail`: the state update too (the last downdate of an update).
-  int launch_downdate_bf16x6(int c0, int c1, int m_pad, hipStream_t ss, bool split, const int* tiles, int ntiles, int cam_rows,
+  int launch_downdate_bf16x6(UpdateCtx& ux, int c0, int c1, int m_pad, hipStream_t ss, bool split, const int* tiles, int ntiles, int cam_rows,
                              int r0, int r1, double work, bool rider, bool su_tail) {
     if constexpr (kIsF32) {
       const int npad_live = round_up(n, NB()), width = c1 - c0;
@@ -1949,11 +1999,12 @@ struct Filter : FilterBase {
       if (ntiles == 0) return EKF_OK;
       Scope sc(this, KID_DOWNDATE, ss);
       if (sc.on) prof_work[KID_DOWNDATE] += work;
-      Syrk6Args a{d_Vimg, ldy / 16, c0 / 16, width / 16, S(), ld, tiles, ntiles, d_counters + counter_next, cam_rows, r0, r1};
+      int* head = ux.take_queue();                        // (the callers have checked queue_room())
+      Syrk6Args a{d_Vimg, ldy / 16, c0 / 16, width / 16, S(), ld, tiles, ntiles, head, cam_rows, r0, r1};
       a.stag_half = opt_syrk_stag_half; a.stag_mod4 = opt_syrk_stag_mod4;
       if (su_tail) {
         a.su_mu = mu(); a.su_V = d_V; a.su_ldy = ldy; a.su_n = n; a.su_y = d_V + (size_t)npad_live * ldy; a.su_mpad = m_pad;
-        a.su_qn = d_scr + SCR_QN; a.su_counter = d_counters + counter_next + 1;
+        a.su_qn = d_scr + SCR_QN; a.su_counter = head + 1;
         ++launch_cnt[EKF_LAUNCH_STATE_UPDATE_TAIL];
       }
       if (rider) {
@@ -1961,7 +2012,6 @@ struct Filter : FilterBase {
         a.rnu = d_W + (size_t)npad_live * ldy + c1; a.rcols = m_pad - c1; a.rK = width; a.nrider = (m_pad - c1 + 255) / 256;
         ++launch_cnt[EKF_LAUNCH_ROW_RIDER];
       }
-      counter_next += 8;
       ++launch_cnt[EKF_LAUNCH_DOWNDATE_BF16X6];
       const int wgs = 2 * (ss == stream_b ? num_cus - reserved_cus : num_cus);
       k_syrk_bf16x6<0><<<a.nrider + std::min(ntiles, wgs), 256, 0, ss>>>(a);
@@ -1988,27 +2038,311 @@ struct Filter : FilterBase {
     }
   }
 
-  // End of an update on the main stream: mu += V y with the quaternion normalisation (`state_update`), the normalisation
-  // congruence of Sigma (`normalize`), and the record of what the update did
-  int finish_update(int nchunks, const int* cend, bool recompute, int m, int m_pad, bool state_update, bool normalize) {
-    last_nchunks = nchunks;
-    last_recompute = recompute;
-    for (int g = 0; g < nchunks; ++g) last_cend[g] = cend[g];
-    if (state_update) {
-      Scope sc(this, KID_STATE_UPDATE);
-      k_state_update<T><<<(n + 7) / 8, 512, 0, stream>>>(mu(), d_V, ldy, n, d_V + (size_t)round_up(n, NB()) * ldy, m_pad,
-                                                        d_scr + SCR_QN);
-    }
+  // mu += V y with the quaternion normalisation, on stream st
+  void launch_state_update(int m_pad, hipStream_t st) {
+    Scope sc(this, KID_STATE_UPDATE, st);
+    k_state_update<T><<<(n + 7) / 8, 512, 0, st>>>(mu(), d_V, ldy, n, d_V + (size_t)round_up(n, NB()) * ldy, m_pad, d_scr + SCR_QN);
+  }
+
+  // End of an update on the main stream: the state update (`state_update`), the normalisation congruence of Sigma
+  // (`normalize`), and the record of what the update did
+  int finish_update(const UpdatePlan& p, bool state_update, bool normalize) {
+    last_nchunks = p.nchunks;
+    last_recompute = p.recompute;
+    for (int g = 0; g < p.nchunks; ++g) last_cend[g] = p.cend[g];
+    if (state_update) launch_state_update(p.m_pad, stream);
     if (normalize) {
       Scope sc(this, KID_NORMALIZE);
       k_strip_congruence<T, 4><<<(2 * n + 255) / 256, 256, 0, stream>>>(S(), ld, n, 3, d_scr + SCR_QN,
                                                                        static_cast<const T*>(nullptr));
     }
     HIPCHK(hipGetLastError());
-    last_m = m; last_m_pad = m_pad; last_n = n;
+    last_m = p.m; last_m_pad = p.m_pad; last_n = n;
     have_update = true;
     have_meas = false;                                    // h/H belong to the pre-update state
     ++frame_seq;
+    return EKF_OK;
+  }
+
+  // ---- the plan of an update --------------------------------------------------------------
+  // Everything the update of M measured features (+ the plane rows) decides before its first launch, for the plain and
+  // the sharded step alike.
+  UpdatePlan plan_update(int M, int plane) const {
+    UpdatePlan p;
+    p.M = M; p.plane = plane;
+    p.nb = NB();
+    p.tile = (kIsF32 && opt_mfma) ? 128 : 64;
+    p.m = 2 * M + (plane ? 3 : 0);
+    p.m_pad = round_up(p.m, p.nb);
+    p.npad_live = round_up(n, p.nb);
+    p.nsteps = p.m_pad / p.nb;
+    p.nchunks = plan_chunks(p.nsteps, p.cend);
+    p.tab = chunk_table(p.cend, p.nchunks, p.nb, &p.strip_rows);
+    p.ntr = (p.npad_live + p.nb) / p.tile;
+    p.ntc = p.m_pad / p.tile;
+    // EKF_OPT_W_RECOMPUTE (fp32 MFMA path, several chunks): the W columns of chunk g + 1 come from the downdated Sigma
+    // instead of the right-looking GEMM update (see the option's comment in ekf_monoslam.h)
+    p.recompute = kIsF32 && opt_mfma && opt_wrecompute && p.nchunks > 1;
+    if (sh_on) {
+      // own state rows, and the tile-padded panel [p0, p0 + prows) the tile GEMMs run on: it covers the own rows and,
+      // at its ends, a few foreign ones (whose results nobody reads and the next gather overwrites); it never reaches
+      // past the padded live block (row npad_live of W / V is the nu / y row)
+      p.r0 = row_of_feature(own_f0()); p.r1 = row_of_feature(own_f1());
+      // (round 3: the panel starts on a tile boundary, so that the tiles that lie INSIDE the own rows on both sides -- the
+      // own x own block of Sigma minus its ragged ends -- are computed once, as lower tiles, and mirrored: both rows of a
+      // mirrored pair are then owned.  Per rank the downdate is rows x m x (2 n - rows) flop instead of 2 rows n m.)
+      if (p.r1 > p.r0) {
+        p.p0 = p.r0 / p.nb * p.nb;
+        p.prows = round_up(p.r1, p.nb) - p.p0;
+      }
+      p.ranges[0] = {0, p.p0 > 0 || p.prows == 0 ? p.nb : 0};
+      p.ranges[1] = {p.p0, p.prows};
+      p.ranges[2] = {p.npad_live, p.nb};
+      p.sym_panel = kIsF32 && opt_mfma && p.nb == 128 && p.prows > 0 && opt_shard_sym;
+      // (the plain path's rule: the lower tiles of the WHOLE matrix fill the chip)
+      p.shard_split = kIsF32 && opt_split_bf16 && opt_mfma && p.nb == 128 &&
+                      (p.npad_live / 128) * (p.npad_live / 128 + 1) / 2 >= num_cus;
+      return p;
+    }
+    if constexpr (kIsF32) {
+      // One diagonal block (2 M + 3 <= 128, the reference's operating point): the chunk inverse is the transposed
+      // Linv of the diagonal factor, so the panel launch, the solve and the state update are ONE launch
+      // (k_solve_state_oneblock; small maps: the downdate and the normalisation too, k_update_oneblock_small): the step is
+      // launch-bound there.
+      p.oneblock = opt_fused && opt_mfma && p.nchunks == 1 && p.m_pad == 128 && p.nb == 128 && !prof_on(KID_SOLVE) &&
+                   !prof_on(KID_STATE_UPDATE) && !prof_on(KID_CHOL_PANEL);
+      // small map: downdate and normalisation congruence in the same launch, one 64 x 64 tile of Sigma per workgroup
+      p.small_nt64 = (p.npad_live / 64) * (p.npad_live / 64 + 1) / 2;
+      p.allinone = p.oneblock && p.small_nt64 <= num_cus && !prof_on(KID_DOWNDATE) && !prof_on(KID_NORMALIZE);
+      // Small map (n_pad <= 256: the reference's 20-35 features): W, S, the factor, the solve, the state update, the downdate
+      // and the normalisation as ONE launch (ekf_small.hpp) -- every workgroup forms W, S and the factor for itself
+      p.onelaunch = p.oneblock && opt_small_onelaunch && p.npad_live <= kSmallMaxRows && p.small_nt64 <= num_cus && ld % 4 == 0 &&
+                    small_chunking(n, round_up(p.m, 4), &p.small_rc, &p.small_nchunk) && M <= 62 && !prof_on(KID_SIGMA_HT) &&
+                    !prof_on(KID_INNOVATION_COV) && !prof_on(KID_CHOL_DIAG) && !prof_on(KID_DOWNDATE) && !prof_on(KID_NORMALIZE);
+      p.allinone = p.allinone || p.onelaunch;
+    }
+    return p;
+  }
+  // The chain's cached work lists for this plan: the blocks of k_trail_diag, and for a one-chunk plan of the plain step
+  // those of the fused block step (`dist`: the distributed chain of the sharded step has lists of its own)
+  int prepare_chain(const UpdatePlan& p, UpdateCtx& ux, bool dist) {
+    if (td_nblk != p.nsteps) td_nblk = 0;                  // lists of another plan: launch_trail_diag must not take them
+    if (!p.oneblock && !dist && trail_diag_ok() && p.nb == 128 && p.nsteps >= 2) {
+      int rc = ensure_trail_diag_lists(p.nsteps, p.nchunks, p.cend);
+      if (rc) return rc;
+    }
+    if constexpr (kIsF32) {                                // (the fused block step is the plain path's)
+      if (!sh_on && opt_step_fused && opt_mfma && opt_fused && p.nb == 128 && p.nchunks == 1 && !p.oneblock &&
+          !prof_on(KID_CHOL_DIAG) && !prof_on(KID_CHOL_PANEL) && !prof_on(KID_CHOL_TRAILING)) {
+        int rc = ensure_step_fused_lists(p.nsteps);
+        if (rc) return rc;
+        ux.step_fused = true;
+      }
+    }
+    return EKF_OK;
+  }
+
+  // ---- what chunk g of the plain step does (each rule once; `ux`: the work-queue heads still free) -------------------
+  // the last chunk has nothing left to overlap with: it runs on the main stream, on every CU
+  bool chunk_overlaps(const UpdatePlan& p, int g) const { return stream_b != nullptr && g + 1 < p.nchunks; }
+  // workgroups of a persistent grid on the chunk's stream: two per CU the stream may use
+  int chunk_slots(const UpdatePlan& p, int g) const { return 2 * (chunk_overlaps(p, g) ? num_cus - reserved_cus : num_cus); }
+  // the downdate on the bf16 matrix pipe (EKF_OPT_SPLIT_BF16): the 128 x 128 lower tiles of Sigma fill the chip
+  bool chunk_splits(const UpdatePlan& p, const UpdateCtx& ux) const {
+    return kIsF32 && opt_split_bf16 && opt_mfma && p.tile == 128 && tri_count >= num_cus && ux.queue_room();
+  }
+  // W update and downdate of an overlapped chunk go out as ONE queued launch when both run on 128 x 128 tiles:
+  // they read the same V_g, and sharing a launch saves one ramp and one partially filled last round.  Not for
+  // the chunk before the last: the last solve starts on that chunk's W update, not on its downdate.
+  bool chunk_fuses(const UpdatePlan& p, int g, const UpdateCtx& ux) const {
+    return kIsF32 && opt_fuse_wu && (opt_fuse_wu > 1 || p.recompute || g + 2 < p.nchunks) && opt_mfma && chunk_overlaps(p, g) &&
+           p.c1(g) < p.m_pad && !opt_split_bf16 && p.tile == 128 && tri_count >= num_cus && ux.queue_room();
+  }
+  // the innovation row update rides in the chunk's k_syrk_bf16x6 launch
+  bool chunk_row_rider(const UpdatePlan& p, int g, const UpdateCtx& ux) const {
+    return chunk_splits(p, ux) && p.recompute && opt_row_gemv && p.c1(g) < p.m_pad && !chunk_fuses(p, g, ux);
+  }
+  // (round 6: when the last downdate is the bf16x6 kernel, its workgroups take the state update's rows when they run out of
+  // tiles -- Syrk6Args::su_*: no launch, no second stream, no events at the end of the step)
+  bool chunk_su_tail(const UpdatePlan& p, int g, const UpdateCtx& ux) const {
+    return kIsF32 && opt_su_tail && !chunk_overlaps(p, g) && p.nchunks > 1 && chunk_splits(p, ux);
+  }
+  enum SolveShape { SOLVE_64X64, SOLVE_128_ONE_PER_CU, SOLVE_64X128, SOLVE_128 };
+  SolveShape solve_shape(const UpdatePlan& p, int g) const {
+    const bool mf = kIsF32 && opt_mfma;
+    const int tiles = (p.c1(g) - p.c0(g)) / p.tile * p.ntr, slots = chunk_slots(p, g);
+    if (mf && 4 * tiles < slots) return SOLVE_64X64;      // small map: 64 x 64 tiles
+    // the last chunk's solve, alone on the chip, between one and two tiles of 128 x 128 per CU (N = 1000: 432 tiles with
+    // K = 128 .. 1152): ONE workgroup per CU drawing the tiles heaviest-first -- a workgroup that has its CU to itself
+    // runs a K step in 2.0 us against 3.2 us beside a second one, and with at most two per CU the heaviest tile bounds
+    // the launch either way; the light tiles then fill the CUs that finish first.  96 -> 86 us, bit-identical
+    // (round 4; 128 x 128 tiles on two workgroups per CU: 1.203 ms per step, 64 x 128 tiles: 1.149, this: 1.142)
+    if (mf && !chunk_overlaps(p, g) && opt_solve_one_per_cu && tiles < slots && tiles > num_cus) return SOLVE_128_ONE_PER_CU;
+    if (mf && tiles < slots) return SOLVE_64X128;          // narrow chunk: 64-row tiles fill the chip
+    return SOLVE_128;
+  }
+
+  // ---- the launches of the plain step, phase by phase --------------------------------------
+  // The whole update of a small map as ONE launch (plan: onelaunch)
+  int launch_update_small(const UpdatePlan& p, const UpdateCtx& ux) {
+    if constexpr (kIsF32) {
+      if (w_zeroed_n != n) {              // (what build_innovation keeps: pad rows of W and the rows behind nu are zero)
+        HIPCHK(hipMemsetAsync(d_W + (size_t)n * ldy, 0, (size_t)(p.npad_live - n + p.nb) * ldy * sizeof(T), stream));
+        w_zeroed_n = n;
+      }
+      SmallUpdateArgs a{};
+      a.S = S(); a.ld = ld; a.n = n; a.npad = p.npad_live;
+      a.Hc = d_Hc; a.Hf = d_Hf; a.pos = d_pos; a.coding = d_coding; a.midx = ux.midx;
+      a.M = p.M; a.plane = p.plane; a.nfeat = N;
+      a.z = ux.z; a.h = d_h; a.mu = mu();
+      a.r_pix = T(sigma_pixel_2); a.r_plane = T(0.00001);
+      a.W = d_W; a.ldw = ldy; a.Y = d_Y; a.ldy = ldy; a.Dinv = d_Dinv; a.V = d_V; a.ldv = ldy;
+      a.scr_qn = d_scr + SCR_QN; a.status = d_status;
+      a.gate = reinterpret_cast<unsigned*>(d_status + 9);
+      small_gate_total += (unsigned)(p.small_nt64 + 1);
+      a.gate_target = small_gate_total;
+      a.ntiles = p.small_nt64; a.wp = round_up(p.m, 4); a.stamps = d_small_stamps;
+      a.rc = p.small_rc; a.nchunk = p.small_nchunk;
+      ++launch_cnt[EKF_LAUNCH_UPDATE_ONELAUNCH];
+      k_update_small_onelaunch<<<p.small_nt64 + 1, 1024, 0, stream>>>(a);
+    }
+    return EKF_OK;
+  }
+
+  // The solve V_g = [W_g; nu_g^T] Z_gg of chunk gi on stream ss (one block: with everything behind it, see plan_update).
+  // *vimg_done: the tiles have written the plane image of V_g the bf16x6 downdate reads
+  int solve_chunk(const UpdatePlan& p, int gi, UpdateCtx& ux, hipStream_t ss, bool* vimg_done) {
+    const int c0 = p.c0(gi), width = p.c1(gi) - c0, ntr = p.ntr, ntc = p.ntc;
+    T* Zs = d_Y + (size_t)p.m_pad * ldy;                   // the strip
+    if (p.oneblock) {
+      if constexpr (kIsF32) {
+        ++launch_cnt[p.allinone ? EKF_LAUNCH_UPDATE_ALLINONE : EKF_LAUNCH_UPDATE_ONEBLOCK];
+        if (p.allinone)
+          k_update_oneblock_small<<<p.small_nt64 + 1, 512, 0, ss>>>(d_W, ldy, d_Dinv, d_V, ldy, p.npad_live, mu(), n, d_scr + SCR_QOLD,
+                                                                   d_scr + SCR_QN, Zs, ldy, S(), ld, p.small_nt64);
+        else
+          k_solve_state_oneblock<<<p.npad_live / 64 + 1, 256, 0, ss>>>(d_W, ldy, d_Dinv, d_V, ldy, p.npad_live, mu(), n,
+                                                                      d_scr + SCR_QN, Zs, ldy);
+      }
+      return EKF_OK;
+    }
+    Scope sc(this, KID_SOLVE, ss);                        // column tiles of the chunk, heaviest first
+    const int wt = width / p.tile;
+    GemmCall c;
+    c.A = d_W + c0; c.lda = ldy; c.B = Zs + c0; c.ldb = ldy; c.C = d_V + c0; c.ldc = ldy;
+    c.rows = p.npad_live + p.nb; c.cols = width; c.K = width; c.ktri = KTRI_UPPER;
+    c.two_groups = want_solve_s2(width, p.npad_live);
+    c.st = ss;
+    switch (solve_shape(p, gi)) {
+      case SOLVE_64X64:
+        c.tile_list = d_tilemap + solve6464_off + 2 * (2 * ntc - 2 * wt) * 2 * ntr; c.ntiles = 2 * wt * 2 * ntr;
+        c.counter = ux.take_queue();
+        gemm<ROLE_SOLVE, true, 64, 64>(c);
+        break;
+      case SOLVE_128_ONE_PER_CU:
+        c.tile_list = d_tilemap + solve_off + 2 * (ntc - wt) * ntr; c.ntiles = wt * ntr;
+        c.counter = ux.take_queue();
+        c.one_per_cu = true;
+        gemm<ROLE_SOLVE, true>(c);
+        break;
+      case SOLVE_64X128:
+        // (round 6: when the bf16x6 downdate follows, the tiles also write the plane image of V_g it reads)
+        if (kIsF32 && opt_fuse_split && opt_split_bf16 && p.tile == 128 && tri_count >= num_cus && ux.queue_room(16)) {
+          if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
+          c.img = d_Vimg; c.img_nkc = ldy / 16; c.img_c0 = c0;
+          *vimg_done = true;
+        }
+        c.tile_list = d_tilemap + solve64_off + 2 * (ntc - wt) * 2 * ntr; c.ntiles = wt * 2 * ntr;
+        c.counter = ux.take_queue();
+        gemm<ROLE_SOLVE, true, 64, 128>(c);
+        break;
+      case SOLVE_128:
+        c.tile_list = d_tilemap + solve_off + 2 * (ntc - wt) * ntr; c.ntiles = wt * ntr;
+        c.counter = ux.take_queue();
+        gemm<ROLE_SOLVE, true>(c);
+        break;
+    }
+    return EKF_OK;
+  }
+
+  // The W update [W; nu^T][:, c1:] -= V_g L[c1:, c0:c1]^T of chunk gi on stream ss, where it is a launch of its own: the
+  // innovation row alone when W is recomputed (nothing when the row rides in the downdate's launch), nothing when the
+  // downdate's launch carries the update (chunk_fuses)
+  void wupdate_chunk(const UpdatePlan& p, int gi, const UpdateCtx& ux, hipStream_t ss) {
+    const int c0 = p.c0(gi), c1 = p.c1(gi);
+    if (c1 >= p.m_pad || chunk_fuses(p, gi, ux) || chunk_row_rider(p, gi, ux)) return;
+    if (p.recompute) {
+      launch_row_update(c0, c1, p.m_pad, ss, kIsF32 && opt_row_gemv);
+      return;
+    }
+    Scope sc(this, KID_WUPDATE, ss);
+    ++launch_cnt[EKF_LAUNCH_W_UPDATE_GEMM];
+    GemmCall c;
+    c.A = d_V + c0; c.lda = ldy; c.B = d_Y + (size_t)c1 * ldy + c0; c.ldb = ldy; c.C = d_W + c1; c.ldc = ldy;
+    c.rows = p.npad_live + p.nb; c.cols = p.m_pad - c1; c.K = c1 - c0; c.alpha = T(-1); c.beta = T(1);
+    c.st = ss;
+    if (kIsF32 && opt_mfma && ((p.m_pad - c1) / 128) * p.ntr < chunk_slots(p, gi))
+      gemm<ROLE_WUPDATE, false, 64, 128>(c);
+    else
+      gemm<ROLE_WUPDATE, false>(c);
+  }
+
+  // The downdate Sigma -= V_g V_g^T of chunk gi on stream ss: the bf16x6 kernel (with the row rider / the state update in
+  // its tail), the fp32 tiles together with the W update (chunk_fuses), or the fp32 tiles alone; nothing when the
+  // solve's launch has done it (allinone)
+  int downdate_chunk(const UpdatePlan& p, int gi, UpdateCtx& ux, hipStream_t ss, bool vimg_done) {
+    const int c0 = p.c0(gi), c1 = p.c1(gi), width = c1 - c0, m = p.m, m_pad = p.m_pad, npad_live = p.npad_live;
+    if (chunk_splits(p, ux)) {
+      // the lower tiles of Sigma, downdated from LDS-DMA-fed records of the plane image (only the plain step counts its
+      // image launches)
+      const bool row_rider = chunk_row_rider(p, gi, ux), su_tail = chunk_su_tail(p, gi, ux);
+      if (!vimg_done) ++launch_cnt[EKF_LAUNCH_SPLIT_IMAGE];
+      return launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, !vimg_done, d_tilemap + tri6_off, tri_count, 0, 0, INT_MAX,
+                                    double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail);
+    }
+    if (chunk_fuses(p, gi, ux)) {
+      if constexpr (kIsF32) {
+        Scope sc(this, KID_DOWNDATE, ss);               // W[:, c1:] -= V_g L[c1:, g]^T, then Sigma -= V_g V_g^T
+        // (recompute: of [W; nu^T] only the row tile that holds nu^T -- the rows of W are re-evaluated from Sigma)
+        const int nr2 = p.recompute ? 1 : (npad_live + p.nb) / 128, n2 = nr2 * ((m_pad - c1) / 128);
+        if (sc.on) {
+          const double w = std::min(c1, m) - std::min(c0, m);
+          prof_work[KID_DOWNDATE] += double(n) * n * w + 2.0 * (p.recompute ? 1 : n + 1) * std::max(0, m - c1) * w;
+        }
+        GemmArgs g{};
+        g.A = d_V + c0; g.lda = ldy; g.B = d_V + c0; g.ldb = ldy; g.C = S(); g.ldc = ld;
+        g.K = width; g.alpha = -1.0; g.beta = 1.0; g.tri = TRI_LOWER_MIRROR;
+        g.tile_map = d_tilemap; g.ntiles = n2 + tri_count; g.counter = ux.take_queue(); g.stagger = 1;
+        g.B2 = d_Y + (size_t)c1 * ldy + c0; g.ldb2 = ldy; g.C2 = d_W + c1; g.ldc2 = ldy;
+        g.n2 = n2; g.nr2 = nr2; g.row2 = p.recompute ? npad_live / 128 : 0;
+        ++launch_cnt[EKF_LAUNCH_DOWNDATE_F32_FUSED_WU];
+        const int wgs = 2 * (num_cus - reserved_cus);
+        k_gemm_mfma<ROLE_DOWNDATE, false><<<std::min(g.ntiles, wgs), 256, 0, ss>>>(g);
+      }
+      return EKF_OK;
+    }
+    if (p.allinone) return EKF_OK;
+    Scope sc(this, KID_DOWNDATE, ss);                 // Sigma -= V_g V_g^T (lower tiles + mirror)
+    if (sc.on) prof_work[KID_DOWNDATE] += double(n) * n * (std::min(c1, m) - std::min(c0, m));   // symmetric half, 2 flop per MAC
+    const bool mf = kIsF32 && opt_mfma;
+    const bool t64 = mf && tri_count < num_cus;
+    const bool half_tail = !t64 && mf && ss != stream_b && trih_count > tri_count && ux.queue_room();
+    ++launch_cnt[t64 ? EKF_LAUNCH_DOWNDATE_F32_T64 : (half_tail ? EKF_LAUNCH_DOWNDATE_F32_HALF_TAIL : EKF_LAUNCH_DOWNDATE_F32)];
+    GemmCall c;
+    c.A = d_V + c0; c.lda = ldy; c.B = d_V + c0; c.ldb = ldy; c.C = S(); c.ldc = ld;
+    c.rows = npad_live; c.cols = npad_live; c.K = width; c.alpha = T(-1); c.beta = T(1); c.tri = TRI_LOWER_MIRROR;
+    c.counter = ux.take_queue();
+    c.st = ss;
+    if (t64) {                                        // small map: 64 x 64 tiles, or most of the chip idles
+      c.tile_list = d_tilemap + tri64_off; c.ntiles = tri64_count;
+      gemm<ROLE_DOWNDATE, false, 64, 64>(c);
+    } else if (mf && ss != stream_b) {                // half tiles at the end of the list: the launch on every CU only (128 x 128 MFMA kernel)
+      c.tile_list = d_tilemap + trih_off; c.ntiles = trih_count;
+      gemm<ROLE_DOWNDATE, false>(c);
+    } else {
+      c.tile_list = d_tilemap; c.ntiles = tri_count;
+      gemm<ROLE_DOWNDATE, false>(c);
+    }
     return EKF_OK;
   }
 
@@ -2034,12 +2368,11 @@ struct Filter : FilterBase {
     if (!have_meas) FAIL(EKF_ERR_STATE, "ekf_update needs the h/H of ekf_predict or ekf_measure");
     if (M > 0 && (!z || !idx)) FAIL(EKF_ERR_ARG, "z / indices are NULL");
     if (!on_device) { int rcl = check_list(idx, M, true); if (rcl) return rcl; }
-    cur_z = nullptr;
-    cur_midx = nullptr;
+    UpdateCtx ux{d_z, d_midx, d_counters};
     if (M > 0) {
       if (on_device) {              // resident inputs are read in place (they must outlive the step)
-        cur_z = static_cast<const T*>(z);
-        cur_midx = idx;
+        ux.z = static_cast<const T*>(z);
+        ux.midx = idx;
       } else {
         // host z / indices go through a small ring of pinned staging slots: the two copies are then truly asynchronous
         // (a copy from pageable memory is staged by the runtime and costs the caller ~10 us each)
@@ -2048,9 +2381,6 @@ struct Filter : FilterBase {
         sh_list.clear();
       }
     }
-    const int nb = NB();
-    int m = 2 * M + (plane ? 3 : 0), m_pad = round_up(m, nb);
-    const int npad_live = round_up(n, nb);
     // Blocked right-looking Cholesky of S in column chunks (a few block steps each).  Chunk g carries its
     // own identity block under S (the strip, rows m_pad..), which the same panel / trailing sweeps turn
     // into Z_gg = L_gg^-T: the inverse of the DIAGONAL chunk only.  As soon as the chain has left chunk g
@@ -2059,96 +2389,25 @@ struct Filter : FilterBase {
     //   W update    [W; nu^T][:, c1:] -= V_g L[c1:, c0:c1]^T         (right-looking, rank = chunk width)
     //   downdate    Sigma -= V_g V_g^T
     // so only the last chunk's solve + downdate are exposed after the chain.
-    const int nsteps = m_pad / nb;
-    int cend[8];
-    const int nchunks = plan_chunks(nsteps, cend);
-    int strip_rows = 0;
-    const ChunkTab tab = chunk_table(cend, nchunks, nb, &strip_rows);
-    // One diagonal block (2 M + 3 <= 128, the reference's operating point): the chunk inverse is the transposed
-    // Linv of the diagonal factor, so the panel launch, the solve and the state update are ONE launch
-    // (k_solve_state_oneblock; small maps: the downdate and the normalisation too, k_update_oneblock_small): the step is
-    // launch-bound there.
-    bool oneblock = false, allinone = false;                // (allinone: downdate + normalisation are in the launch too)
-    if constexpr (kIsF32)
-      oneblock = opt_fused && opt_mfma && nchunks == 1 && m_pad == 128 && nb == 128 && !prof_on(KID_SOLVE) &&
-                 !prof_on(KID_STATE_UPDATE) && !prof_on(KID_CHOL_PANEL);
-    const int* ip_list = cur_midx ? cur_midx : d_midx;    // the measured list (device memory), for the re-evaluations of W below
-    // Small map (n_pad <= 256: the reference's 20-35 features): W, S, the factor, the solve, the state update, the downdate
-    // and the normalisation as ONE launch (ekf_small.hpp) -- every workgroup forms W, S and the factor for itself
-    bool onelaunch = false;
-    int rc = EKF_OK;
-    if constexpr (kIsF32) {
-      const int nt64 = (npad_live / 64) * (npad_live / 64 + 1) / 2;
-      int small_rc = 0, small_nchunk = 0;
-      onelaunch = oneblock && opt_small_onelaunch && npad_live <= kSmallMaxRows && nt64 <= num_cus && ld % 4 == 0 &&
-                  small_chunking(n, round_up(m, 4), &small_rc, &small_nchunk) && M <= 62 && !prof_on(KID_SIGMA_HT) &&
-                  !prof_on(KID_INNOVATION_COV) && !prof_on(KID_CHOL_DIAG) && !prof_on(KID_DOWNDATE) && !prof_on(KID_NORMALIZE);
-      if (onelaunch) {
-        if (w_zeroed_n != n) {              // (what build_innovation keeps: pad rows of W and the rows behind nu are zero)
-          HIPCHK(hipMemsetAsync(d_W + (size_t)n * ldy, 0, (size_t)(npad_live - n + nb) * ldy * sizeof(T), stream));
-          w_zeroed_n = n;
-        }
-        counter_next = 0;
-        SmallUpdateArgs a{};
-        a.S = S(); a.ld = ld; a.n = n; a.npad = npad_live;
-        a.Hc = d_Hc; a.Hf = d_Hf; a.pos = d_pos; a.coding = d_coding; a.midx = ip_list;
-        a.M = M; a.plane = plane; a.nfeat = N;
-        a.z = cur_z ? cur_z : d_z; a.h = d_h; a.mu = mu();
-        a.r_pix = T(sigma_pixel_2); a.r_plane = T(0.00001);
-        a.W = d_W; a.ldw = ldy; a.Y = d_Y; a.ldy = ldy; a.Dinv = d_Dinv; a.V = d_V; a.ldv = ldy;
-        a.scr_qn = d_scr + SCR_QN; a.status = d_status;
-        a.gate = reinterpret_cast<unsigned*>(d_status + 9);
-        small_gate_total += (unsigned)(nt64 + 1);
-        a.gate_target = small_gate_total;
-        a.ntiles = nt64; a.wp = round_up(m, 4); a.stamps = d_small_stamps;
-        a.rc = small_rc; a.nchunk = small_nchunk;
-        ++launch_cnt[EKF_LAUNCH_UPDATE_ONELAUNCH];
-        k_update_small_onelaunch<<<nt64 + 1, 1024, 0, stream>>>(a);
-      }
-    }
-    if (!onelaunch) rc = build_innovation(M, plane, true, &m, &m_pad, &tab, strip_rows);
-    cur_z = nullptr;
-    cur_midx = nullptr;
+    const UpdatePlan p = plan_update(M, plane);
+    int rc = p.onelaunch ? launch_update_small(p, ux)
+                         : build_innovation(ux.z, ux.midx, M, plane, true, nullptr, nullptr, &p.tab, p.strip_rows);
     if (rc) return rc;
-    T* Y = d_Y;
-    T* Zs = d_Y + (size_t)m_pad * ldy;                     // the strip
-    const int tile = (kIsF32 && opt_mfma) ? 128 : 64;
-    const int ntr = (npad_live + nb) / tile, ntc = m_pad / tile;
-    rc = ensure_tilemap(npad_live / tile, ntr, ntc);
+    rc = ensure_tilemap(p.npad_live / p.tile, p.ntr, p.ntc);
     if (rc) return rc;
-
-    // EKF_OPT_W_RECOMPUTE (fp32 MFMA path, several chunks): the W columns of chunk g + 1 come from the downdated Sigma
-    // instead of the right-looking GEMM update (see the option's comment in ekf_monoslam.h)
-    const bool recompute = kIsF32 && opt_mfma && opt_wrecompute && nchunks > 1 && tile == 128 && !oneblock;
-    int step = 0;
+    rc = prepare_chain(p, ux, false);
+    if (rc) return rc;
+    const int nchunks = p.nchunks, m_pad = p.m_pad;
     bool b_inflight = false;
-    chain_diag_ahead = -1;
-    chain_pending.step = -1;
-    td_nblk = (td_nblk == nsteps) ? td_nblk : 0;
-    if (!oneblock && trail_diag_ok() && nb == 128 && nsteps >= 2) { rc = ensure_trail_diag_lists(nsteps, nchunks, cend); if (rc) return rc; }
-    sf_now = false;
-    if constexpr (kIsF32) {
-      if (opt_step_fused && opt_mfma && opt_fused && nb == 128 && nchunks == 1 && !oneblock && !prof_on(KID_CHOL_DIAG) &&
-          !prof_on(KID_CHOL_PANEL) && !prof_on(KID_CHOL_TRAILING)) {
-        rc = ensure_step_fused_lists(nsteps);
-        if (rc) return rc;
-        sf_now = true;
-      }
-    }
-    if (onelaunch) allinone = true;
-    for (int gi = 0; gi < (onelaunch ? 0 : nchunks); ++gi) {
-      const int c0 = step * nb, c1 = cend[gi] * nb;
+    for (int gi = 0; gi < (p.onelaunch ? 0 : nchunks); ++gi) {
+      const int c0 = p.c0(gi), c1 = p.c1(gi);
       // chunk 0 has the chip to itself; later chunks run beside the tile GEMMs of stream_b, on the reserved CUs
-      hipStream_t sc_ = stream;
-      chain_steps(step, cend[gi], c0, c1, m, m_pad, sc_, oneblock, opt_chain_defer && gi + 1 < nchunks);
-      step = cend[gi];
-      const int width = c1 - c0;
-      bool vimg_done = false;                       // this chunk's solve writes the plane image of V_g
-      // the last chunk has nothing left to overlap with: it runs on the main stream, on every CU
-      const bool overlap = (stream_b != nullptr) && (gi + 1 < nchunks);
+      chain_steps(ux, gi ? p.cend[gi - 1] : 0, p.cend[gi], c0, c1, p.m, m_pad, stream, p.oneblock,
+                  opt_chain_defer && gi + 1 < nchunks);
+      const bool overlap = chunk_overlaps(p, gi);
       hipStream_t ss = overlap ? stream_b : stream;
       if (!overlap && b_inflight) {
-        if (recompute) {                             // W of this chunk is re-evaluated from Sigma: every earlier downdate first
+        if (p.recompute) {                           // W of this chunk is re-evaluated from Sigma: every earlier downdate first
           HIPCHK(hipEventRecord(ev_b, stream_b));
           HIPCHK(hipStreamWaitEvent(stream, ev_b, 0));
           b_inflight = false;
@@ -2158,165 +2417,45 @@ struct Filter : FilterBase {
       }
       if (overlap) {
         b_inflight = true;
-        HIPCHK(hipEventRecord(ev_chain[gi], sc_));
+        HIPCHK(hipEventRecord(ev_chain[gi], stream));
         HIPCHK(hipStreamWaitEvent(stream_b, ev_chain[gi], 0));
       }
-      if (oneblock) {
-        if constexpr (kIsF32) {
-          const int nrb = npad_live / 64, nt64 = nrb * (nrb + 1) / 2;
-          // small map: downdate and normalisation congruence in the same launch, one 64 x 64 tile of Sigma per workgroup
-          allinone = nt64 <= num_cus && !prof_on(KID_DOWNDATE) && !prof_on(KID_NORMALIZE);
-          ++launch_cnt[allinone ? EKF_LAUNCH_UPDATE_ALLINONE : EKF_LAUNCH_UPDATE_ONEBLOCK];
-          if (allinone)
-            k_update_oneblock_small<<<nt64 + 1, 512, 0, ss>>>(d_W, ldy, d_Dinv, d_V, ldy, npad_live, mu(), n, d_scr + SCR_QOLD,
-                                                             d_scr + SCR_QN, Zs, ldy, S(), ld, nt64);
-          else
-            k_solve_state_oneblock<<<nrb + 1, 256, 0, ss>>>(d_W, ldy, d_Dinv, d_V, ldy, npad_live, mu(), n, d_scr + SCR_QN, Zs,
-                                                           ldy);
-        }
-      } else {
-        Scope sc(this, KID_SOLVE, ss);                    // column tiles of the chunk, heaviest first
-        solve_s2_now = want_solve_s2(width, npad_live);
-        const int wt = width / tile;
-        const int slots = 2 * (overlap ? num_cus - reserved_cus : num_cus);
-        if (kIsF32 && opt_mfma && 4 * wt * ntr < slots) { // small map: 64 x 64 tiles
-          const int* list = d_tilemap + solve6464_off + 2 * (2 * ntc - 2 * wt) * 2 * ntr;
-          gemm<ROLE_SOLVE, true, 64, 64>(d_W + c0, ldy, Zs + c0, ldy, d_V + c0, ldy, npad_live + nb, width, width, T(1),
-                                         T(0), 0, 0, 0, 1, 0, ss, list, 2 * wt * 2 * ntr);
-        } else if (kIsF32 && opt_mfma && !overlap && opt_solve_one_per_cu && wt * ntr < slots && wt * ntr > num_cus) {
-          // the last chunk's solve, alone on the chip, between one and two tiles of 128 x 128 per CU (N = 1000: 432 tiles with
-          // K = 128 .. 1152): ONE workgroup per CU drawing the tiles heaviest-first -- a workgroup that has its CU to itself
-          // runs a K step in 2.0 us against 3.2 us beside a second one, and with at most two per CU the heaviest tile bounds
-          // the launch either way; the light tiles then fill the CUs that finish first.  96 -> 86 us, bit-identical
-          // (round 4; 128 x 128 tiles on two workgroups per CU: 1.203 ms per step, 64 x 128 tiles: 1.149, this: 1.142)
-          solve_one_per_cu_now = true;
-          const int* list = d_tilemap + solve_off + 2 * (ntc - wt) * ntr;
-          gemm<ROLE_SOLVE, true>(d_W + c0, ldy, Zs + c0, ldy, d_V + c0, ldy, npad_live + nb, width, width, T(1), T(0), 0,
-                                 0, 0, 1, 0, ss, list, wt * ntr);
-          solve_one_per_cu_now = false;
-        } else if (kIsF32 && opt_mfma && wt * ntr < slots) {     // narrow chunk: 64-row tiles fill the chip
-          const int* list = d_tilemap + solve64_off + 2 * (ntc - wt) * 2 * ntr;
-          // (round 6: when the bf16x6 downdate follows, the tiles also write the plane image of V_g it reads)
-          void* vimg = nullptr;
-          if constexpr (kIsF32) {
-            if (opt_fuse_split && opt_split_bf16 && tile == 128 && tri_count >= num_cus && counter_next + 16 <= kQueueCounters) {
-              if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
-              vimg = d_Vimg;
-              vimg_done = true;
-            }
-          }
-          gemm<ROLE_SOLVE, true, 64, 128>(d_W + c0, ldy, Zs + c0, ldy, d_V + c0, ldy, npad_live + nb, width, width, T(1),
-                                          T(0), 0, 0, 0, 1, 0, ss, list, wt * 2 * ntr, 0, 0, vimg, ldy / 16, c0);
-        } else {
-          const int* list = d_tilemap + solve_off + 2 * (ntc - wt) * ntr;
-          gemm<ROLE_SOLVE, true>(d_W + c0, ldy, Zs + c0, ldy, d_V + c0, ldy, npad_live + nb, width, width, T(1), T(0), 0,
-                                 0, 0, 1, 0, ss, list, wt * ntr);
-        }
-      }
-      // W update and downdate of an overlapped chunk go out as ONE queued launch when both run on 128 x 128 tiles:
-      // they read the same V_g, and sharing a launch saves one ramp and one partially filled last round.  Not for
-      // the chunk before the last: the last solve starts on that chunk's W update, not on its downdate.
-      bool fuse = false;
-      if constexpr (kIsF32)
-        fuse = opt_fuse_wu && (opt_fuse_wu > 1 || recompute || gi + 2 < nchunks) && opt_mfma && overlap && c1 < m_pad &&
-               !opt_split_bf16 && tile == 128 && tri_count >= num_cus && counter_next + 8 <= kQueueCounters;
-      bool split_now = false;
-      if constexpr (kIsF32)
-        split_now = opt_split_bf16 && opt_mfma && tile == 128 && tri_count >= num_cus && counter_next + 8 <= kQueueCounters;
-      const bool row_rider = split_now && recompute && opt_row_gemv && c1 < m_pad && !fuse;   // rides in the k_syrk_bf16x6 launch below
-      if (row_rider) {
-        // (nothing here: the row goes with the downdate's launch)
-      } else if (c1 < m_pad && !fuse && recompute) {
-        launch_row_update(c0, c1, m_pad, ss, kIsF32 && opt_row_gemv);
-      } else if (c1 < m_pad && !fuse) {
-        Scope sc(this, KID_WUPDATE, ss);
-        ++launch_cnt[EKF_LAUNCH_W_UPDATE_GEMM];
-        const int slots = 2 * (overlap ? num_cus - reserved_cus : num_cus);
-        if (kIsF32 && opt_mfma && ((m_pad - c1) / 128) * ntr < slots)
-          gemm<ROLE_WUPDATE, false, 64, 128>(d_V + c0, ldy, Y + (size_t)c1 * ldy + c0, ldy, d_W + c1, ldy, npad_live + nb,
-                                             m_pad - c1, width, T(-1), T(1), 0, 0, 0, 0, 0, ss);
-        else
-          gemm<ROLE_WUPDATE, false>(d_V + c0, ldy, Y + (size_t)c1 * ldy + c0, ldy, d_W + c1, ldy, npad_live + nb, m_pad - c1,
-                                    width, T(-1), T(1), 0, 0, 0, 0, 0, ss);
-      }
-      if (overlap && c1 < m_pad && !fuse && !recompute) HIPCHK(hipEventRecord(ev_wu, stream_b));
+      bool vimg_done = false;                       // this chunk's solve writes the plane image of V_g
+      rc = solve_chunk(p, gi, ux, ss, &vimg_done);
+      if (rc) return rc;
+      const bool fuse = chunk_fuses(p, gi, ux);
+      wupdate_chunk(p, gi, ux, ss);
+      if (overlap && c1 < m_pad && !fuse && !p.recompute) HIPCHK(hipEventRecord(ev_wu, stream_b));
       if (!overlap && b_inflight) {                  // earlier downdates must be done before Sigma is touched again
         HIPCHK(hipEventRecord(ev_b, stream_b));
         HIPCHK(hipStreamWaitEvent(stream, ev_b, 0));
         b_inflight = false;
       }
-      // (round 6: when the last downdate is the bf16x6 kernel, its workgroups take the state update's rows when they run out of
-      // tiles -- Syrk6Args::su_*: no launch, no second stream, no events at the end of the step)
-      bool su_tail = false;
-      if constexpr (kIsF32) su_tail = opt_su_tail && !overlap && nchunks > 1 && split_now;
-      if (!overlap && nchunks > 1 && !su_tail) {
+      if (!overlap && nchunks > 1 && !chunk_su_tail(p, gi, ux)) {
         // every column of V and y = L^-1 nu exist now: the state update runs beside the last downdate
         HIPCHK(hipEventRecord(ev_chain[gi], stream));
         HIPCHK(hipStreamWaitEvent(stream_b, ev_chain[gi], 0));
-        Scope sc(this, KID_STATE_UPDATE, stream_b);
-        k_state_update<T><<<(n + 7) / 8, 512, 0, stream_b>>>(mu(), d_V, ldy, n, d_V + (size_t)npad_live * ldy, m_pad, d_scr + SCR_QN);   // + quaternion normalisation
+        launch_state_update(m_pad, stream_b);
         b_inflight = true;
       }
-      if (split_now) {
-        // the lower tiles of Sigma, downdated from LDS-DMA-fed records of the plane image (only the plain step counts its
-        // image launches)
-        if (!vimg_done) ++launch_cnt[EKF_LAUNCH_SPLIT_IMAGE];
-        rc = launch_downdate_bf16x6(c0, c1, m_pad, ss, !vimg_done, d_tilemap + tri6_off, tri_count, 0, 0, INT_MAX,
-                                    double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail);
-        if (rc) return rc;
-      }
-      if (fuse) {
-        if constexpr (kIsF32) {
-          Scope sc(this, KID_DOWNDATE, ss);               // W[:, c1:] -= V_g L[c1:, g]^T, then Sigma -= V_g V_g^T
-          // (recompute: of [W; nu^T] only the row tile that holds nu^T -- the rows of W are re-evaluated from Sigma)
-          const int nr2 = recompute ? 1 : (npad_live + nb) / 128, n2 = nr2 * ((m_pad - c1) / 128);
-          const int row2 = recompute ? npad_live / 128 : 0;
-          if (sc.on) {
-            const double w = std::min(c1, m) - std::min(c0, m);
-            prof_work[KID_DOWNDATE] += double(n) * n * w + 2.0 * (recompute ? 1 : n + 1) * std::max(0, m - c1) * w;
-          }
-          GemmArgs g{d_V + c0, ldy, d_V + c0, ldy, S(), ld, width, -1.0, 1.0, 2, 0, 0, 0, 0,
-                     d_tilemap, n2 + tri_count, d_counters + counter_next, 0, 0, 1,
-                     Y + (size_t)c1 * ldy + c0, ldy, d_W + c1, ldy, n2, nr2, row2};
-          counter_next += 8;
-          ++launch_cnt[EKF_LAUNCH_DOWNDATE_F32_FUSED_WU];
-          const int wgs = 2 * (num_cus - reserved_cus);
-          k_gemm_mfma<ROLE_DOWNDATE, false><<<std::min(g.ntiles, wgs), 256, 0, ss>>>(g);
-          if (!recompute) HIPCHK(hipEventRecord(ev_wu, stream_b));
-        }
-      } else if (!split_now && !allinone) {
-        Scope sc(this, KID_DOWNDATE, ss);                 // Sigma -= V_g V_g^T (lower tiles + mirror)
-        if (sc.on) prof_work[KID_DOWNDATE] += double(n) * n * (std::min(c1, m) - std::min(c0, m));   // symmetric half, 2 flop per MAC
-        const bool t64 = kIsF32 && opt_mfma && tri_count < num_cus;
-        const bool half_tail = !t64 && kIsF32 && opt_mfma && ss != stream_b && trih_count > tri_count &&
-                               counter_next + 8 <= kQueueCounters;
-        ++launch_cnt[t64 ? EKF_LAUNCH_DOWNDATE_F32_T64 : (half_tail ? EKF_LAUNCH_DOWNDATE_F32_HALF_TAIL : EKF_LAUNCH_DOWNDATE_F32)];
-        if (kIsF32 && opt_mfma && tri_count < num_cus)    // small map: 64 x 64 tiles, or most of the chip idles
-          gemm<ROLE_DOWNDATE, false, 64, 64>(d_V + c0, ldy, d_V + c0, ldy, S(), ld, npad_live, npad_live, width, T(-1), T(1),
-                                             2, 0, 0, 0, 0, ss, d_tilemap + tri64_off, tri64_count);
-        else if (kIsF32 && opt_mfma && ss != stream_b)   // half tiles at the end of the list: the launch on every CU only (128 x 128 MFMA kernel)
-          gemm<ROLE_DOWNDATE, false>(d_V + c0, ldy, d_V + c0, ldy, S(), ld, npad_live, npad_live, width, T(-1), T(1), 2, 0,
-                                     0, 0, 0, ss, d_tilemap + trih_off, trih_count);
-        else
-          gemm<ROLE_DOWNDATE, false>(d_V + c0, ldy, d_V + c0, ldy, S(), ld, npad_live, npad_live, width, T(-1), T(1), 2, 0,
-                                     0, 0, 0, ss, d_tilemap, tri_count);
-      }
-      if (recompute && gi + 1 < nchunks) {
+      rc = downdate_chunk(p, gi, ux, ss, vimg_done);
+      if (rc) return rc;
+      if (fuse && !p.recompute) HIPCHK(hipEventRecord(ev_wu, stream_b));
+      if (p.recompute && gi + 1 < nchunks) {
         // W[:, c1:c2) = Sigma' H^T for the features of the NEXT chunk, Sigma' = Sigma - sum_{g <= gi} V_g V_g^T (stream
         // order: right behind this chunk's downdate, in front of the wait for the chain): the sequential form of the
         // update.  Only these columns of Sigma' are read (a feature's six columns + the camera's), i.e. one more pass
         // over Sigma in all; the right-looking GEMM update W[:, c1:] -= V_g L[c1:, g]^T of every chunk
         // (2 n w_g (m - c1) flop) is not needed
-        launch_w_recompute(c1, cend[gi + 1] * nb, m_pad, ip_list, M, plane, ss, n);
+        launch_w_recompute(c1, p.c1(gi + 1), m_pad, ux.midx, M, plane, ss, n);
       }
     }
     if (b_inflight) {
       HIPCHK(hipEventRecord(ev_b, stream_b));
       HIPCHK(hipStreamWaitEvent(stream, ev_b, 0));
-      b_inflight = false;
     }
     // (several chunks: the state update ran beside the last downdate or inside it; one block: inside the fused launch)
-    return finish_update(nchunks, cend, recompute, m, m_pad, nchunks == 1 && !oneblock, !allinone);
+    return finish_update(p, nchunks == 1 && !p.oneblock, !p.allinone);
   }
 
   int innovation_covariance(const int* idx, int M, int plane, void* out) override {
@@ -2333,7 +2472,7 @@ struct Filter : FilterBase {
     if (sh_on) {
       rc = shard_build_ws(idx, M, plane, nullptr, &m, &m_pad);       // W rows {camera, own}, own rows of S, "reassemble S"
     } else {
-      rc = build_innovation(M, plane, false, &m, &m_pad);
+      rc = build_innovation(nullptr, d_midx, M, plane, false, &m, &m_pad);
     }
     if (rc) return rc;
     std::vector<T> tmp((size_t)m * m);
@@ -2374,12 +2513,17 @@ struct Filter : FilterBase {
       if (c1 < m_pad) {
         dim3 grid((w + 255) / 256, npad_live);
         k_copy2d<T><<<grid, 256, 0, stream>>>(d_V + c0, ldy, Tm, wmax, npad_live, w);
-        gemm<ROLE_GAIN, true>(d_K + c1, m_pad, d_Y + (size_t)c1 * ldy + c0, ldy, Tm, wmax, npad_live, w, m_pad - c1, T(-1),
-                              T(1), 0, 0, 0, 0);
+        GemmCall sub;                                       // Tm = V_g - K[:, c1:] L[c1:, c0:c1]
+        sub.A = d_K + c1; sub.lda = m_pad; sub.B = d_Y + (size_t)c1 * ldy + c0; sub.ldb = ldy; sub.C = Tm; sub.ldc = wmax;
+        sub.rows = npad_live; sub.cols = w; sub.K = m_pad - c1; sub.alpha = T(-1); sub.beta = T(1);
+        gemm<ROLE_GAIN, true>(sub);
         A = Tm;
         lda = wmax;
       }
-      gemm<ROLE_GAIN, false>(A, lda, Zs + c0, ldy, d_K + c0, m_pad, npad_live, w, w, T(1), T(0), 0, 0, 0, 0);
+      GemmCall kg;                                          // K_g = A Z_gg^T
+      kg.A = A; kg.lda = lda; kg.B = Zs + c0; kg.ldb = ldy; kg.C = d_K + c0; kg.ldc = m_pad;
+      kg.rows = npad_live; kg.cols = w; kg.K = w;
+      gemm<ROLE_GAIN, false>(kg);
     }
     std::vector<T> tmp((size_t)nn * m);
     HIPCHK(hipMemcpy2DAsync(tmp.data(), (size_t)m * sizeof(T), d_K, (size_t)m_pad * sizeof(T), (size_t)m * sizeof(T), nn,
@@ -2661,7 +2805,7 @@ struct Filter : FilterBase {
     ransac_mask_host = nullptr;
     { int rcs = ensure_sd(); if (rcs) return rcs; }
     if (sh_on) return shard_ransac(idx, M, thr, counts, inl, best);
-    int rc = build_innovation(M, 0, false, &m, &m_pad, nullptr, 0, true);       // W = Sigma H^T for the listed features
+    int rc = build_innovation(nullptr, d_midx, M, 0, false, &m, &m_pad, nullptr, 0, true);       // W = Sigma H^T for the listed features
     if (rc) return rc;
     have_update = false;
     if (!d_ibuf) HIPCHK(hipMalloc(&d_ibuf, (size_t)std::max(capN, 1) * 3 * sizeof(int)));
@@ -3039,14 +3183,14 @@ struct Filter : FilterBase {
   }
   // block steps [step0, step1) of the distributed chain on stream st (no deferral: a step ends with its trailing update,
   // which carries the factor of the next step when the rank's blocks fit one round of workgroups)
-  int dist_chain_steps(int step0, int step1, int m, int m_pad, hipStream_t st) {
+  int dist_chain_steps(UpdateCtx& ux, int step0, int step1, int m, int m_pad, hipStream_t st) {
     if constexpr (kIsF32) {
       T* Y = d_Y;
       const int nblk = dist.nblk;
       for (int step = step0; step < step1; ++step) {
         const int j = step * 128, r0 = j + 128;
         T* Dj = d_Dinv + (size_t)step * 128 * 128;
-        if (chain_diag_ahead != step) {
+        if (ux.diag_ahead != step) {
           Scope sc(this, KID_CHOL_DIAG, st);
           ++launch_cnt[EKF_LAUNCH_CHAIN_STEP];
           k_chol_diag_packed<><<<1, 1024, 0, st>>>(Y + (size_t)j * ldy + j, ldy, Dj, d_status, std::max(1, std::min(8, (m - j + 15) / 16)));
@@ -3080,13 +3224,15 @@ struct Filter : FilterBase {
           Scope sc(this, KID_CHOL_TRAILING, st);
           ++launch_cnt[EKF_LAUNCH_CHAIN_TRAIL_DIAG];
           k_trail_diag<<<a.nblocks + 1, 1024, kChainLds, st>>>(a);
-          chain_diag_ahead = step + 1;
+          ux.diag_ahead = step + 1;
         } else if (dist.tl_cnt[step] > 0) {
           Scope sc(this, KID_CHOL_TRAILING, st);
           ++launch_cnt[EKF_LAUNCH_CHAIN_STEP];
           const T* P = Y + (size_t)r0 * ldy + j;
-          GemmArgs g{P, ldy, P, ldy, Y + (size_t)r0 * ldy + r0, ldy, 128, -1.0, 1.0, 0, r0, r0, 0, 0,
-                     d_dist_lists + dist.tl_off[step], dist.tl_cnt[step], d_dist_counters + 8 * step, 0, 0, 0};
+          GemmArgs g{};                                    // the rank's tiles of Y[r0.., r0..] -= P P^T, as listed
+          g.A = P; g.lda = ldy; g.B = P; g.ldb = ldy; g.C = Y + (size_t)r0 * ldy + r0; g.ldc = ldy;
+          g.K = 128; g.alpha = -1.0; g.beta = 1.0; g.tri = TRI_ALL; g.row_off = r0; g.col_off = r0;
+          g.tile_map = d_dist_lists + dist.tl_off[step]; g.ntiles = dist.tl_cnt[step]; g.counter = d_dist_counters + 8 * step;
           k_gemm_mfma<ROLE_TRAILING, false, 64, 64><<<std::min(dist.tl_cnt[step], 2 * num_cus), 256, 0, st>>>(g);
         }
       }
@@ -3376,7 +3522,6 @@ struct Filter : FilterBase {
       Scope sc(this, KID_INNOVATION);
       k_innovation<T><<<(std::max(m_pad, 64) + 255) / 256, 256, 0, stream>>>(d_zz, d_h, d_midx, M, plane, mu(), nu_row, m_pad,
                                                                           d_counters, N, d_status);
-      counter_next = 0;
     }
     {
       Scope sc(this, KID_SIGMA_HT);                        // W rows {camera, own}
@@ -3413,8 +3558,8 @@ struct Filter : FilterBase {
     HIPCHK(hipGetLastError());
     int rc = exchange_rows(d_Y, ldy, stab, 0, m_pad, stream, KID_GATHER_S);     // "reassemble S"
     if (rc) return rc;
-    *m_out = m;
-    *m_pad_out = m_pad;
+    if (m_out) *m_out = m;
+    if (m_pad_out) *m_pad_out = m_pad;
     return EKF_OK;
   }
 
@@ -3640,6 +3785,100 @@ struct Filter : FilterBase {
     return launch_blur();                                  // predicted blur of every template (replicated, like the templates)
   }
 
+  // ---- the rank's launches of the sharded step, phase by phase ---------------------------
+  // The rank's rows of the solve V_g = [W_g; nu_g^T] Z_gg of chunk gi on stream ss
+  int shard_solve_chunk(const UpdatePlan& p, int gi, UpdateCtx& ux, hipStream_t ss) {
+    const int c0 = p.c0(gi), width = p.c1(gi) - c0;
+    const T* Zs = d_Y + (size_t)p.m_pad * ldy;
+    GemmCall c;
+    c.B = Zs + c0; c.ldb = ldy; c.lda = ldy; c.ldc = ldy;
+    c.cols = width; c.K = width; c.ktri = KTRI_UPPER;
+    c.two_groups = want_solve_s2(width, p.npad_live);
+    c.st = ss;
+    if constexpr (kIsF32) {
+      if (opt_mfma && p.nb == 128 && p.prows > 0 && ux.queue_room()) {
+        // camera block, own panel and innovation block as ONE queued launch of 64 x 128 tiles, heaviest column tiles first
+        // (row tiles relative to the panel's first row; any tile shape adds the same terms in the same order)
+        Scope sc(this, KID_SOLVE, ss);
+        int rc = ensure_shard_solve_list(p.p0, p.prows, p.npad_live, p.ranges[0].count > 0);
+        if (rc) return rc;
+        const int wt = width / 128;
+        const size_t off = (size_t)p.p0 * ldy;
+        c.A = d_W + off + c0; c.C = d_V + off + c0; c.rows = p.prows;
+        c.tile_list = d_shard_solve + 2 * (shard_ntc_max() - wt) * shard_solve_rows; c.ntiles = wt * shard_solve_rows;
+        c.counter = ux.take_queue();
+        gemm<ROLE_SOLVE, true, 64, 128>(c);
+        return EKF_OK;
+      }
+    }
+    for (const Rows& rr : p.ranges) {
+      if (rr.count == 0) continue;
+      const size_t off = (size_t)rr.r0 * ldy;
+      Scope sc(this, KID_SOLVE, ss);
+      c.A = d_W + off + c0; c.C = d_V + off + c0; c.rows = rr.count;
+      gemm<ROLE_SOLVE, true>(c);
+    }
+    return EKF_OK;
+  }
+
+  // The rank's rows of the W update of chunk gi (needs the OWN rows of V_g only)
+  void shard_wupdate_chunk(const UpdatePlan& p, int gi, hipStream_t ss) {
+    const int c0 = p.c0(gi), c1 = p.c1(gi);
+    for (const Rows& rr : p.ranges) {
+      if (rr.count == 0) continue;
+      const size_t off = (size_t)rr.r0 * ldy;
+      Scope sc(this, KID_WUPDATE, ss);
+      ++launch_cnt[EKF_LAUNCH_W_UPDATE_GEMM];
+      GemmCall c;
+      c.A = d_V + off + c0; c.lda = ldy; c.B = d_Y + (size_t)c1 * ldy + c0; c.ldb = ldy; c.C = d_W + off + c1; c.ldc = ldy;
+      c.rows = rr.count; c.cols = p.m_pad - c1; c.K = c1 - c0; c.alpha = T(-1); c.beta = T(1);
+      c.st = ss;
+      gemm<ROLE_WUPDATE, false>(c);
+    }
+  }
+
+  // The rank's rows of the downdate Sigma -= V_g V_g^T for columns [c0, c1) on stream ss (every row of V_g is here: the
+  // gather is done), with the innovation row update of the chunk where it is still pending (ux.row_pending)
+  int shard_downdate_chunk(const UpdatePlan& p, int c0, int c1, UpdateCtx& ux, hipStream_t ss) {
+    const int m = p.m, m_pad = p.m_pad;
+    const bool split = kIsF32 && p.shard_split && ux.queue_room();
+    if (ux.row_pending && !split) {
+      launch_row_update(c0, c1, m_pad, ss, true);
+      ux.row_pending = false;
+    }
+    if (split) {
+      // V_g -> plane image, then ONE launch over the canonical tiles that touch the camera block or an own block; each
+      // element pair is the same sum as on the plain path
+      const bool rider = ux.row_pending && shard_syrk_n > 0;
+      int rcd = launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, true, d_shard_syrk, shard_syrk_n, camera_dim, p.r0, p.r1,
+                                       2.0 * 128 * 128 * shard_syrk_n * double(std::min(c1, m) - std::min(c0, m)), rider, false);
+      if (rcd) return rcd;
+      if (ux.row_pending && !rider) launch_row_update(c0, c1, m_pad, ss, true);
+      ux.row_pending = false;
+      return EKF_OK;
+    }
+    for (int q = 0; q < 2; ++q) {                        // Sigma[rows, :] -= V_g[rows] V_g^T: camera tile, own panel
+      const Rows& rr = p.ranges[q];
+      if (rr.count == 0) continue;
+      Scope sc(this, KID_DOWNDATE, ss);
+      ++launch_cnt[EKF_LAUNCH_DOWNDATE_F32];
+      GemmCall c;
+      c.A = d_V + (size_t)rr.r0 * ldy + c0; c.lda = ldy; c.B = d_V + c0; c.ldb = ldy; c.C = S() + (size_t)rr.r0 * ld; c.ldc = ld;
+      c.rows = rr.count; c.cols = p.npad_live; c.K = c1 - c0; c.alpha = T(-1); c.beta = T(1);
+      c.st = ss;
+      if (q == 1 && p.sym_panel && ux.queue_room()) {
+        // the own panel as ONE queued launch over the listed tiles: interior x interior lower tiles + mirror, the rest plain
+        if (sc.on) prof_work[KID_DOWNDATE] += 2.0 * 128 * 128 * panel_ntiles * double(std::min(c1, m) - std::min(c0, m));
+        c.tri = TRI_LISTED; c.row_off = rr.r0;
+        c.tile_list = d_panel_tiles; c.ntiles = panel_ntiles; c.counter = ux.take_queue();
+      } else if (sc.on) {
+        prof_work[KID_DOWNDATE] += 2.0 * rr.count * double(n) * (std::min(c1, m) - std::min(c0, m));
+      }
+      gemm<ROLE_DOWNDATE, false>(c);
+    }
+    return EKF_OK;
+  }
+
   // The sharded EKF update block for the measured list `idx` (host, strictly ascending), z resident on the device.
   int shard_update(const void* dz, const int* idx, int M, int plane) override {
     HIPCHK(hipSetDevice(device));
@@ -3654,32 +3893,13 @@ struct Filter : FilterBase {
       sh_list.assign(idx, idx + M);
       HIPCHK(hipMemcpyAsync(d_midx, sh_list.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, stream));
     }
-    const T* d_zz = static_cast<const T*>(dz);
-    const int nb = NB();
-    int m = 0, m_pad = 0;
-    const int npad_live = round_up(n, nb);
+    UpdateCtx ux{static_cast<const T*>(dz), d_midx, d_counters};
+    const UpdatePlan p = plan_update(M, plane);
     if (dbg_sync & 4) HIPCHK(hipDeviceSynchronize());
     // nu (replicated), W rows {camera, own}, own rows of S, "reassemble S"
-    rc = shard_build_ws(idx, M, plane, d_zz, &m, &m_pad);
+    rc = shard_build_ws(idx, M, plane, ux.z, nullptr, nullptr);
     if (rc) return rc;
-    // own state rows, and the tile-padded panel [p0, p0 + prows) the tile GEMMs run on: it covers the own rows and,
-    // at its ends, a few foreign ones (whose results nobody reads and the next gather overwrites); it never reaches
-    // past the padded live block (row npad_live of W / V is the nu / y row)
-    const int f0 = own_f0(), f1 = own_f1();
-    const int r0 = row_of_feature(f0), r1 = row_of_feature(f1);
-    // (round 3: the panel starts on a tile boundary, so that the tiles that lie INSIDE the own rows on both sides -- the
-    // own x own block of Sigma minus its ragged ends -- are computed once, as lower tiles, and mirrored: both rows of a
-    // mirrored pair are then owned.  Per rank the downdate is rows x m x (2 n - rows) flop instead of 2 rows n m.)
-    int p0 = 0, prows = 0;
-    if (r1 > r0) {
-      p0 = r0 / nb * nb;
-      prows = round_up(r1, nb) - p0;
-    }
-    struct Rows { int r0, count; };
-    const Rows ranges[3] = {{0, p0 > 0 || prows == 0 ? nb : 0}, {p0, prows}, {npad_live, nb}};
-    bool sym_panel = false;
-    if constexpr (kIsF32) sym_panel = opt_mfma && nb == 128 && prows > 0 && opt_shard_sym;
-    if (sym_panel) { rc = ensure_panel_tiles(p0, prows, r0, r1, npad_live); if (rc) return rc; }
+    if (p.sym_panel) { rc = ensure_panel_tiles(p.p0, p.prows, p.r0, p.r1, p.npad_live); if (rc) return rc; }
 
     // Replicated chain in column chunks; the rank's share of every chunk beside it:
     //   second stream (CU-masked):  solve V_g rows, W update rows, ... downdate of the PREVIOUS chunk
@@ -3687,80 +3907,28 @@ struct Filter : FilterBase {
     // so a gather travels while the next chunk is being solved, and only the last chunk's solve -> gather -> downdate
     // is exposed after the chain.  With 1 / world of the GEMM work per rank many narrow chunks are affordable: the
     // exposed tail shrinks with the width of the last one.
-    const int nsteps = m_pad / nb;
-    int cend[8];
-    const int nchunks = plan_chunks(nsteps, cend);
-    int strip_rows = 0;
-    const ChunkTab tab = chunk_table(cend, nchunks, nb, &strip_rows);
-    T* Y = d_Y;
-    T* Zs = d_Y + (size_t)m_pad * ldy;
+    const int nchunks = p.nchunks, m_pad = p.m_pad;
     { Scope sc(this, KID_MISC);
-      dim3 grid((m_pad + 255) / 256, strip_rows);
-      k_set_identity_strip<T><<<grid, 256, 0, stream>>>(Zs, ldy, m_pad, tab); }
+      dim3 grid((m_pad + 255) / 256, p.strip_rows);
+      k_set_identity_strip<T><<<grid, 256, 0, stream>>>(d_Y + (size_t)m_pad * ldy, ldy, m_pad, p.tab); }
     const ShardTab rtab = row_tab();
-    bool shard_split = false;
-    if constexpr (kIsF32)                                  // (the plain path's rule: the lower tiles of the WHOLE matrix fill the chip)
-      shard_split = opt_split_bf16 && opt_mfma && nb == 128 && (npad_live / 128) * (npad_live / 128 + 1) / 2 >= num_cus;
-    if (shard_split) { rc = ensure_shard_syrk_list(r0, r1, npad_live); if (rc) return rc; }
-    bool sh_row_pending = false;                           // (sequential form) the innovation row still waits for chunk [c0, c1)
-    auto downdate_chunk = [&](int c0, int c1, hipStream_t ss) -> int {
-      const bool split = kIsF32 && shard_split && counter_next + 8 <= kQueueCounters;
-      if (sh_row_pending && !split) {
-        launch_row_update(c0, c1, m_pad, ss, true);
-        sh_row_pending = false;
-      }
-      if (split) {
-        // V_g (every row: the gather is done) -> plane image, then ONE launch over the canonical tiles that touch the camera
-        // block or an own block; each element pair is the same sum as on the plain path
-        const bool rider = sh_row_pending && shard_syrk_n > 0;
-        int rcd = launch_downdate_bf16x6(c0, c1, m_pad, ss, true, d_shard_syrk, shard_syrk_n, camera_dim, r0, r1,
-                                         2.0 * 128 * 128 * shard_syrk_n * double(std::min(c1, m) - std::min(c0, m)), rider, false);
-        if (rcd) return rcd;
-        if (sh_row_pending && !rider) launch_row_update(c0, c1, m_pad, ss, true);
-        sh_row_pending = false;
-        return EKF_OK;
-      }
-      for (int q = 0; q < 2; ++q) {                        // Sigma[rows, :] -= V_g[rows] V_g^T: camera tile, own panel
-        const Rows& rr = ranges[q];
-        if (rr.count == 0) continue;
-        Scope sc(this, KID_DOWNDATE, ss);
-        ++launch_cnt[EKF_LAUNCH_DOWNDATE_F32];
-        if (q == 1 && sym_panel && counter_next + 8 <= kQueueCounters) {
-          // the own panel as ONE queued launch over the listed tiles: interior x interior lower tiles + mirror, the rest plain
-          if (sc.on) prof_work[KID_DOWNDATE] += 2.0 * 128 * 128 * panel_ntiles * double(std::min(c1, m) - std::min(c0, m));
-          gemm<ROLE_DOWNDATE, false>(d_V + (size_t)rr.r0 * ldy + c0, ldy, d_V + c0, ldy, S() + (size_t)rr.r0 * ld, ld, rr.count,
-                                     npad_live, c1 - c0, T(-1), T(1), 3, rr.r0, 0, 0, 0, ss, d_panel_tiles, panel_ntiles);
-          continue;
-        }
-        if (sc.on) prof_work[KID_DOWNDATE] += 2.0 * rr.count * double(n) * (std::min(c1, m) - std::min(c0, m));
-        gemm<ROLE_DOWNDATE, false>(d_V + (size_t)rr.r0 * ldy + c0, ldy, d_V + c0, ldy, S() + (size_t)rr.r0 * ld, ld, rr.count,
-                                   npad_live, c1 - c0, T(-1), T(1), 0, 0, 0, 0, 0, ss);
-      }
-      return EKF_OK;
-    };
-    // Round 5: the SEQUENTIAL form of the chunked update on a rank too (EKF_OPT_W_RECOMPUTE): after the downdate of chunk g
-    // the rank re-evaluates ITS rows of W for chunk g + 1 from its downdated rows of Sigma (local: a rank holds every
-    // column of its rows), instead of the right-looking GEMM update of all later columns (0.40 of 1.56 ms per step at
-    // N = 1000 / world 1, 8.7 of 44 ms at N = 4000).  Per chunk the rank's second stream then runs solve -> gather of V_g
-    // -> downdate -> W' in series; that order is off the critical path as soon as the replicated chain is what a step
-    // waits for, which it is from two ranks on.
-    bool sh_rec = false;
-    if constexpr (kIsF32) sh_rec = opt_mfma && opt_wrecompute && nb == 128 && nchunks > 1;
-    int step = 0;
+    if (p.shard_split) { rc = ensure_shard_syrk_list(p.r0, p.r1, p.npad_live); if (rc) return rc; }
+    // Round 5: the SEQUENTIAL form of the chunked update on a rank too (EKF_OPT_W_RECOMPUTE, plan: recompute): after the
+    // downdate of chunk g the rank re-evaluates ITS rows of W for chunk g + 1 from its downdated rows of Sigma (local: a
+    // rank holds every column of its rows), instead of the right-looking GEMM update of all later columns (0.40 of 1.56 ms
+    // per step at N = 1000 / world 1, 8.7 of 44 ms at N = 4000).  Per chunk the rank's second stream then runs solve ->
+    // gather of V_g -> downdate -> W' in series; that order is off the critical path as soon as the replicated chain is
+    // what a step waits for, which it is from two ranks on.
+    const bool dchain = dist_chain_ok(p.nsteps);           // the factorisation distributed over the ranks (see dist_chain_steps)
+    if (dchain) { rc = ensure_dist_plan(p.nsteps, nchunks, p.cend); if (rc) return rc; }
+    rc = prepare_chain(p, ux, dchain);
+    if (rc) return rc;
     bool side_busy = false;
-    sf_now = false;                                        // (the fused block step is the plain path's)
-    const bool dchain = dist_chain_ok(nsteps);             // the factorisation distributed over the ranks (see dist_chain_steps)
-    if (dchain) { rc = ensure_dist_plan(nsteps, nchunks, cend); if (rc) return rc; }
-    chain_diag_ahead = -1;
-    chain_pending.step = -1;
-    td_nblk = (td_nblk == nsteps) ? td_nblk : 0;
-    if (!dchain && trail_diag_ok() && nb == 128 && nsteps >= 2) { rc = ensure_trail_diag_lists(nsteps, nchunks, cend); if (rc) return rc; }
-    int pend_c0 = -1, pend_c1 = -1, pend_g = -1;           // overlapped chunk whose downdate is still to be issued
+    int pend_g = -1;                                       // overlapped chunk whose downdate is still to be issued
     for (int gi = 0; gi < nchunks; ++gi) {
-      const int c0 = step * nb, c1 = cend[gi] * nb, width = c1 - c0;
-      if (dchain) { rc = dist_chain_steps(step, cend[gi], m, m_pad, stream); if (rc) return rc; }
-      else chain_steps(step, cend[gi], c0, c1, m, m_pad, stream, false, opt_chain_defer && gi + 1 < nchunks);
-      step = cend[gi];
+      const int c0 = p.c0(gi), c1 = p.c1(gi), width = c1 - c0, step0 = gi ? p.cend[gi - 1] : 0;
+      if (dchain) { rc = dist_chain_steps(ux, step0, p.cend[gi], p.m, m_pad, stream); if (rc) return rc; }
+      else chain_steps(ux, step0, p.cend[gi], c0, c1, p.m, m_pad, stream, false, opt_chain_defer && gi + 1 < nchunks);
       const bool overlap = (gi + 1 < nchunks);
       hipStream_t ss = overlap ? stream_b : stream;
       if (overlap) {
@@ -3772,59 +3940,33 @@ struct Filter : FilterBase {
         HIPCHK(hipEventRecord(ev_b, stream_b));
         HIPCHK(hipStreamWaitEvent(stream, ev_b, 0));
       }
-      bool solved = false;
-      if constexpr (kIsF32) {
-        if (opt_mfma && nb == 128 && prows > 0 && counter_next + 8 <= kQueueCounters) {
-          // camera block, own panel and innovation block as ONE queued launch of 64 x 128 tiles, heaviest column tiles first
-          // (row tiles relative to the panel's first row; any tile shape adds the same terms in the same order)
-          Scope sc(this, KID_SOLVE, ss);
-          solve_s2_now = want_solve_s2(width, npad_live);
-          rc = ensure_shard_solve_list(p0, prows, npad_live, ranges[0].count > 0);
+      rc = shard_solve_chunk(p, gi, ux, ss);
+      if (rc) return rc;
+      if (p.recompute) {
+        // solve -> gather -> innovation row -> downdate -> W' of the next chunk, in this order on the chunk's stream
+        if (overlap) {
+          HIPCHK(hipEventRecord(ev_solve[gi], stream_b));
+          HIPCHK(hipStreamWaitEvent(stream_g, ev_solve[gi], 0));
+          rc = exchange_rows(d_V, ldy, rtab, c0, width, stream_g, KID_GATHER_V);
           if (rc) return rc;
-          const int wt = width / 128;
-          const size_t off = (size_t)p0 * ldy;
-          const int* list = d_shard_solve + 2 * (shard_ntc_max() - wt) * shard_solve_rows;
-          gemm<ROLE_SOLVE, true, 64, 128>(d_W + off + c0, ldy, Zs + c0, ldy, d_V + off + c0, ldy, prows, width, width, T(1),
-                                          T(0), 0, 0, 0, 1, 0, ss, list, wt * shard_solve_rows);
-          solved = true;
-        }
-      }
-      for (int q = 0; q < 3 && !solved; ++q) {
-        const Rows& rr = ranges[q];
-        if (rr.count == 0) continue;
-        const size_t off = (size_t)rr.r0 * ldy;
-        Scope sc(this, KID_SOLVE, ss);
-        solve_s2_now = want_solve_s2(width, npad_live);
-        gemm<ROLE_SOLVE, true>(d_W + off + c0, ldy, Zs + c0, ldy, d_V + off + c0, ldy, rr.count, width, width, T(1), T(0),
-                               0, 0, 0, 1, 0, ss);
-      }
-      if (sh_rec) {
-        if constexpr (kIsF32) {
-          // solve -> gather -> innovation row -> downdate -> W' of the next chunk, in this order on the chunk's stream
-          if (overlap) {
-            HIPCHK(hipEventRecord(ev_solve[gi], stream_b));
-            HIPCHK(hipStreamWaitEvent(stream_g, ev_solve[gi], 0));
-            rc = exchange_rows(d_V, ldy, rtab, c0, width, stream_g, KID_GATHER_V);
-            if (rc) return rc;
-            HIPCHK(hipEventRecord(ev_gath[gi], stream_g));
-            HIPCHK(hipStreamWaitEvent(stream_b, ev_gath[gi], 0));
-          } else {
-            if (side_busy) {
-              HIPCHK(hipEventRecord(ev_g, stream_g));
-              HIPCHK(hipStreamWaitEvent(stream, ev_g, 0));
-            }
-            rc = exchange_rows(d_V, ldy, rtab, c0, width, stream, KID_GATHER_V);
-            if (rc) return rc;
+          HIPCHK(hipEventRecord(ev_gath[gi], stream_g));
+          HIPCHK(hipStreamWaitEvent(stream_b, ev_gath[gi], 0));
+        } else {
+          if (side_busy) {
+            HIPCHK(hipEventRecord(ev_g, stream_g));
+            HIPCHK(hipStreamWaitEvent(stream, ev_g, 0));
           }
-          // nu^T[c1:] -= y_g^T L[c1:, g]^T (replicated, every rank): rides in the downdate's launch when there is one
-          sh_row_pending = c1 < m_pad;
-          rc = downdate_chunk(c0, c1, ss);
+          rc = exchange_rows(d_V, ldy, rtab, c0, width, stream, KID_GATHER_V);
           if (rc) return rc;
-          // W'[rows, c1:c2) = Sigma'[rows, :] H^T, rows = camera + own
-          if (gi + 1 < nchunks) launch_w_recompute(c1, cend[gi + 1] * nb, m_pad, d_midx, M, plane, ss, camera_dim, r0, r1);
-          if (dbg_sync & 2) HIPCHK(hipDeviceSynchronize());
-          continue;
         }
+        // nu^T[c1:] -= y_g^T L[c1:, g]^T (replicated, every rank): rides in the downdate's launch when there is one
+        ux.row_pending = c1 < m_pad;
+        rc = shard_downdate_chunk(p, c0, c1, ux, ss);
+        if (rc) return rc;
+        // W'[rows, c1:c2) = Sigma'[rows, :] H^T, rows = camera + own
+        if (gi + 1 < nchunks) launch_w_recompute(c1, p.c1(gi + 1), m_pad, d_midx, M, plane, ss, camera_dim, p.r0, p.r1);
+        if (dbg_sync & 2) HIPCHK(hipDeviceSynchronize());
+        continue;
       }
       if (overlap) {
         // own rows of V_g are final: their gather starts now, on the gather stream ...
@@ -3834,24 +3976,15 @@ struct Filter : FilterBase {
         if (rc) return rc;
         HIPCHK(hipEventRecord(ev_gath[gi], stream_g));
       }
-      if (c1 < m_pad) {                                    // ... while the W update (needs the OWN rows of V_g only) goes on
-        for (const Rows& rr : ranges) {
-          if (rr.count == 0) continue;
-          const size_t off = (size_t)rr.r0 * ldy;
-          Scope sc(this, KID_WUPDATE, ss);
-          ++launch_cnt[EKF_LAUNCH_W_UPDATE_GEMM];
-          gemm<ROLE_WUPDATE, false>(d_V + off + c0, ldy, Y + (size_t)c1 * ldy + c0, ldy, d_W + off + c1, ldy, rr.count,
-                                    m_pad - c1, width, T(-1), T(1), 0, 0, 0, 0, 0, ss);
-        }
-      }
+      if (c1 < m_pad) shard_wupdate_chunk(p, gi, ss);      // ... while the W update goes on
       if (pend_g >= 0) {                                   // the downdate of the previous chunk, behind this chunk's solve
         HIPCHK(hipStreamWaitEvent(stream_b, ev_gath[pend_g], 0));
-        rc = downdate_chunk(pend_c0, pend_c1, stream_b);
+        rc = shard_downdate_chunk(p, p.c0(pend_g), p.c1(pend_g), ux, stream_b);
         if (rc) return rc;
         pend_g = -1;
       }
       if (overlap) {
-        pend_g = gi; pend_c0 = c0; pend_c1 = c1;
+        pend_g = gi;
       } else {
         // last chunk, everything on the main stream: gather (the staging buffers are free once the gather stream has
         // drained), then its downdate behind every earlier one
@@ -3865,12 +3998,12 @@ struct Filter : FilterBase {
           HIPCHK(hipEventRecord(ev_b, stream_b));
           HIPCHK(hipStreamWaitEvent(stream, ev_b, 0));
         }
-        rc = downdate_chunk(c0, c1, stream);
+        rc = shard_downdate_chunk(p, c0, c1, ux, stream);
         if (rc) return rc;
       }
     }
     HIPCHK(hipGetLastError());
-    rc = finish_update(nchunks, cend, sh_rec, m, m_pad, true, true);   // mu is replicated: every rank adds V y over all rows
+    rc = finish_update(p, true, true);                     // mu is replicated: every rank adds V y over all rows
     if (rc) return rc;
     if (dbg_sync & 1) HIPCHK(hipDeviceSynchronize());
     return EKF_OK;

@@ -439,6 +439,8 @@ __global__ void k_innovation_cov(const T* __restrict__ W, int ldy,
 // Dimensions are multiples of the tile (K of the K-step): no guards.
 // ---------------------------------------------------------------------------------------
 enum : int { ROLE_PANEL = 0, ROLE_TRAILING = 1, ROLE_DOWNDATE = 2, ROLE_SOLVE = 3, ROLE_GAIN = 4, ROLE_WUPDATE = 5 };
+enum : int { TRI_ALL = 0, TRI_LOWER = 1, TRI_LOWER_MIRROR = 2, TRI_LISTED = 3 };   // GemmArgs::tri, as defined above
+enum : int { KTRI_FULL = 0, KTRI_UPPER = 1 };                                     // GemmArgs::ktri
 
 struct GemmArgs {
   const void* A; int lda;

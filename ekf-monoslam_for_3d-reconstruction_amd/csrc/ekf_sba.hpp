@@ -734,8 +734,10 @@ inline void sba_chol_f64(double* A, int ld, int n, double* Dinv, int* status, hi
     if (rows <= 0) break;
     double* P = A + (size_t)r0 * ld + j;
     k_panel_direct_f64<<<(rows + 63) / 64, 256, 0, st>>>(P, ld, Dinv, rows);
-    GemmArgs g{P, ld, P, ld, A + (size_t)r0 * ld + r0, ld, 64, -1.0, 1.0, 1, r0, r0, 0, 0,
-               nullptr, 0, nullptr, 0, 0, 0};
+    GemmArgs g{};                                          // A[r0.., r0..] -= P P^T, lower tiles
+    g.A = P; g.lda = ld; g.B = P; g.ldb = ld; g.C = A + (size_t)r0 * ld + r0; g.ldc = ld;
+    g.K = 64; g.alpha = -1.0; g.beta = 1.0;
+    g.tri = TRI_LOWER; g.row_off = r0; g.col_off = r0;
     k_gemm_mfma_f64<ROLE_TRAILING, false><<<dim3(rows / 64, rows / 64), 256, 0, st>>>(g);
   }
 }
