@@ -76,7 +76,8 @@ static const char* kLaunchNames[EKF_LAUNCH_KINDS] = {
     "downdate_bf16x6", "downdate_f32", "downdate_f32_fused_wu", "downdate_f32_half_tail", "downdate_f32_t64",
     "row_rider", "row_gemv", "row_tile_gemm", "w_update_gemm", "w_recompute",
     "chain_step_launches", "chain_persistent", "solve", "solve_two_groups", "update_oneblock", "update_allinone",
-    "chain_trail_diag", "split_image", "state_update_tail", "update_onelaunch", "chain_dist_gather", "chain_step_fused"};
+    "chain_trail_diag", "split_image", "state_update_tail", "update_onelaunch", "chain_dist_gather", "chain_step_fused",
+    "downdate_mirror_bounds"};
 
 static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
@@ -315,6 +316,9 @@ struct Filter : FilterBase {
   unsigned long long* d_small_stamps = nullptr;         // EKF_SMALL_STAMPS=1: phase stamps of its workgroup 0 (ekf_peek_workspace, which = 3)
   unsigned small_gate_total = 0;                        // arrivals the gate word (d_status[9]) has seen when every launch so far is over
   int opt_su_tail = 1;                                  // EKF_SU_TAIL=0: k_state_update as its own launch on the second stream beside the last downdate (round 5)
+  // EKF_SYRK_MIRROR_SKIP=0: every k_syrk_bf16x6 launch stores every mirror (rounds 5-6; A/B and bit-identity check).  1: launches
+  // 0 .. G-2 of an update mirror only the tiles whose rows the re-evaluation of the next chunk reads as columns (Syrk6Args::mirror_rows)
+  int opt_syrk_mirror_skip = 1;
   int opt_fuse_split = 1;                               // EKF_FUSE_SPLIT=0: the plane image of V_g by its own launch behind the solve (rounds 5)
   int opt_chain_defer = 1;                              // EKF_CHAIN_DEFER=0: a chunk's event behind the trailing update of its last step (rounds 1-5)
   int td_min_blocks = 24;                               // EKF_TD_MIN_BLOCKS: steps with fewer blocks in their update keep the three launches
@@ -509,8 +513,9 @@ struct Filter : FilterBase {
     HIPCHK(hipMalloc(&d_status, 16 * sizeof(int)));         // [0] pivot <= 0, [1] bad device index list, [3] a bounded device-side wait gave up; [4..7] scratch of ekf_check_invariants; [8] arrival gate of k_predict_fused, [9] of k_update_small_onelaunch
     HIPCHK(hipMemsetAsync(d_status, 0, 16 * sizeof(int), stream));
     HIPCHK(hipMalloc(&d_tmp, 64 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_counters, kQueueCounters * sizeof(int)));
-    HIPCHK(hipMemset(d_counters, 0, kQueueCounters * sizeof(int)));
+    // (behind the queue heads: the row bounds of the mirror rule, written by the first launch of every update)
+    HIPCHK(hipMalloc(&d_counters, (kQueueCounters + kMirrorRowsInts) * sizeof(int)));
+    HIPCHK(hipMemset(d_counters, 0, (kQueueCounters + kMirrorRowsInts) * sizeof(int)));
     {
       hipDeviceProp_t prop;
       HIPCHK(hipGetDeviceProperties(&prop, device));
@@ -553,6 +558,7 @@ struct Filter : FilterBase {
       if (const char* e = getenv("EKF_CHAIN_FUSED_DIAG")) opt_chain_fused_diag = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_FUSE_SPLIT")) opt_fuse_split = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SU_TAIL")) opt_su_tail = atoi(e) ? 1 : 0;
+      if (const char* e = getenv("EKF_SYRK_MIRROR_SKIP")) opt_syrk_mirror_skip = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SMALL_ONELAUNCH")) opt_small_onelaunch = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_STEP_FUSED")) opt_step_fused = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SHARD_DIST_CHAIN")) opt_shard_dist_chain = atoi(e) ? 1 : 0;
@@ -1738,23 +1744,26 @@ struct Filter : FilterBase {
       const int extra = with_nu ? 1 : 0;
       const T* zq = with_nu ? zp : nullptr;
       T* nuq = with_nu ? nu_row : nullptr;
+      // the slab also writes the row bounds of the chunks' features (the mirror rule of the bf16x6 downdate)
+      const ChunkTab st = tab ? *tab : ChunkTab{0, {}};
+      int* mrows = (with_nu && tab) ? d_counters + kQueueCounters : nullptr;
       if (small) {
         constexpr int RB = 4;
         dim3 grid((m_pad / 2 + 255) / 256, (n + RB - 1) / RB + extra);
         k_sigma_ht<T, RB><<<grid, 256, 0, stream>>>(S(), ld, n, d_Hc, d_Hf, d_pos, d_coding, ip, M, plane, d_W, ldy,
-                                                  m_pad, 0, n, N, zq, d_h, mu(), nuq, d_counters, d_status, d_scr + SCR_QOLD);
+                                                  m_pad, 0, n, N, zq, d_h, mu(), nuq, d_counters, d_status, d_scr + SCR_QOLD, 0, 0, st, mrows);
       } else if constexpr (kIsF32) {
         // 128 slots x 8 rows per workgroup, the row segments staged through LDS (runs of neighbouring inverse-depth
         // features; other stretches of the list take k_sigma_ht's path inside the same launch): bit-identical sums
         constexpr int RB = 8;
         dim3 grid((m_pad / 2 + 127) / 128, (n + RB - 1) / RB + extra);
         k_sigma_ht_fast<RB><<<grid, 256, 0, stream>>>(S(), ld, n, d_Hc, d_Hf, d_pos, d_coding, ip, M, plane, d_W, ldy, m_pad, N,
-                                                      0, 0, zq, d_h, mu(), nuq, d_counters, d_status, d_scr + SCR_QOLD);
+                                                      0, 0, zq, d_h, mu(), nuq, d_counters, d_status, d_scr + SCR_QOLD, 0, st, mrows);
       } else {
         constexpr int RB = 32;
         dim3 grid((m_pad / 2 + 255) / 256, (n + RB - 1) / RB + extra);
         k_sigma_ht<T, RB><<<grid, 256, 0, stream>>>(S(), ld, n, d_Hc, d_Hf, d_pos, d_coding, ip, M, plane, d_W, ldy,
-                                                  m_pad, 0, n, N, zq, d_h, mu(), nuq, d_counters, d_status, d_scr + SCR_QOLD);
+                                                  m_pad, 0, n, N, zq, d_h, mu(), nuq, d_counters, d_status, d_scr + SCR_QOLD, 0, 0, st, mrows);
       }
     }
     if (!w_only) {                      // (the 1-point RANSAC reads W only)
@@ -1984,10 +1993,10 @@ struct Filter : FilterBase {
   // EKF_OPT_SPLIT_BF16: Sigma -= V_g V_g^T for chunk [c0, c1) on the bf16 matrix pipe at fp32 accuracy (ekf_syrk6.hpp), over
   // the `ntiles` canonical tiles of `tiles` (none: the image only).  `split`: V_g is split into the plane image first (three
   // bf16 per fp32, one 12 KB record per 128 rows x 16 columns; else the solve's tiles have written it).  Rows of Sigma valid
-  // here: [0, cam_rows) and [r0, r1).  `work`: the flop the launch adds to prof_work.  `rider`: the innovation row update of
+  // here: [0, cam_rows) and [r0, r1).  `mirror_rows`: Syrk6Args::mirror_rows (the plain step's launches before the last).  `work`: the flop the launch adds to prof_work.  `rider`: the innovation row update of
   // the chunk in the same launch (launch_row_update's sums); `su_tail`: the state update too (the last downdate of an update).
   int launch_downdate_bf16x6(UpdateCtx& ux, int c0, int c1, int m_pad, hipStream_t ss, bool split, const int* tiles, int ntiles, int cam_rows,
-                             int r0, int r1, double work, bool rider, bool su_tail) {
+                             int r0, int r1, double work, bool rider, bool su_tail, const int* mirror_rows = nullptr) {
     if constexpr (kIsF32) {
       const int npad_live = round_up(n, NB()), width = c1 - c0;
       if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
@@ -2011,6 +2020,10 @@ struct Filter : FilterBase {
         a.ry = d_V + (size_t)npad_live * ldy + c0; a.rL = d_Y + (size_t)c1 * ldy + c0; a.rldl = ldy;
         a.rnu = d_W + (size_t)npad_live * ldy + c1; a.rcols = m_pad - c1; a.rK = width; a.nrider = (m_pad - c1 + 255) / 256;
         ++launch_cnt[EKF_LAUNCH_ROW_RIDER];
+      }
+      if (mirror_rows) {
+        a.mirror_rows = mirror_rows;
+        ++launch_cnt[EKF_LAUNCH_DOWNDATE_MIRROR_BOUNDS];
       }
       ++launch_cnt[EKF_LAUNCH_DOWNDATE_BF16X6];
       const int wgs = 2 * (ss == stream_b ? num_cus - reserved_cus : num_cus);
@@ -2297,8 +2310,14 @@ struct Filter : FilterBase {
       // image launches)
       const bool row_rider = chunk_row_rider(p, gi, ux), su_tail = chunk_su_tail(p, gi, ux);
       if (!vimg_done) ++launch_cnt[EKF_LAUNCH_SPLIT_IMAGE];
+      // Every launch but the last of the update mirrors only what is read before the last launch -- which gets no bounds and
+      // restores every mirror -- overwrites it: the feature columns of the next chunk's re-evaluation (table entry gi + 1),
+      // nothing when W is updated right-looking (nobody reads Sigma between the launches: the empty entry)
+      const int* mirror_rows = nullptr;
+      if (opt_syrk_mirror_skip && gi + 1 < p.nchunks)
+        mirror_rows = d_counters + kQueueCounters + 2 * (p.recompute ? gi + 1 : kMirrorEmpty);
       return launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, !vimg_done, d_tilemap + tri6_off, tri_count, 0, 0, INT_MAX,
-                                    double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail);
+                                    double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail, mirror_rows);
     }
     if (chunk_fuses(p, gi, ux)) {
       if constexpr (kIsF32) {

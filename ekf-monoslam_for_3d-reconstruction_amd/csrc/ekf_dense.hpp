@@ -31,6 +31,48 @@ __device__ __forceinline__ void check_measured_entry(const int* __restrict__ mid
   if (status && (fi < 0 || fi >= nfeat || (k > 0 && midx[k - 1] >= fi))) status[1] = 1;
 }
 
+// Column chunks of the factorisation (see Filter::update): chunk g covers columns [end[g-1], end[g]).
+struct ChunkTab {
+  int n;
+  int end[8];
+};
+
+// Row bounds of the chunks' features, for the mirror rule of the bf16x6 downdate (Syrk6Args::mirror_rows).  Between the
+// downdate launches g and g + 1 of an update the only reader of Sigma is the re-evaluation of chunk g + 1's W columns, and it
+// reads, for EVERY row, the state columns of the features in the slots of chunk g + 1 (+ camera columns 0 .. 6, which lie in
+// column block 0 and so are never a mirror).  Table entry g = {lo_g, hi_g}: the smallest first row and the largest end row
+// (first row + 6 or 3) among those features -- whatever the list (a subset, any order, XYZ features) every column the
+// re-evaluation reads lies in [lo_g, hi_g), and the bounds only have to be conservative.  A chunk without a measured slot
+// (padding, or the plane rows alone: their columns 1 / 4 / 6 are camera columns) gets the empty range {0, 0}; entry
+// kMirrorEmpty is always {0, 0} (no reader between the launches at all: EKF_W_RECOMPUTE=0).  Run by ONE workgroup of the
+// slab that forms nu (the list lives in device memory: ekf_update_device), all of its threads.
+constexpr int kMirrorEmpty = 8;                  // table entry that is always the empty range
+constexpr int kMirrorRowsInts = 2 * (kMirrorEmpty + 1);
+__device__ __forceinline__ void mirror_rows_slab(const ChunkTab& tab, const int* __restrict__ midx, int M, int nfeat,
+                                                 const int* __restrict__ pos, const int* __restrict__ coding,
+                                                 int* __restrict__ mrows) {
+  __shared__ int s_lo[8], s_hi[8];
+  const int tid = threadIdx.x;
+  if (tid < 8) { s_lo[tid] = 0x7fffffff; s_hi[tid] = 0; }
+  __syncthreads();
+  for (int k = tid; k < M; k += blockDim.x) {
+    int g = 0;                                   // the chunk of column 2 k (past the last end: the last chunk)
+#pragma unroll
+    for (int u = 0; u < 7; ++u)
+      if (u + 1 < tab.n && 2 * k >= tab.end[u]) g = u + 1;
+    const int fi = clamp_feature(midx[k], nfeat);
+    const int p = pos[fi];
+    atomicMin(&s_lo[g], p);
+    atomicMax(&s_hi[g], p + (coding[fi] ? 3 : 6));
+  }
+  __syncthreads();
+  if (tid <= kMirrorEmpty) {
+    const bool some = tid < 8 && s_hi[tid & 7] > s_lo[tid & 7];
+    mrows[2 * tid] = some ? s_lo[tid] : 0;
+    mrows[2 * tid + 1] = some ? s_hi[tid] : 0;
+  }
+}
+
 template <typename T>
 __global__ void k_innovation(const T* __restrict__ z, const T* __restrict__ h, const int* __restrict__ midx,
                              int M, int plane, const T* __restrict__ mu, T* __restrict__ nu, int m_pad,
@@ -67,7 +109,8 @@ __global__ void k_sigma_ht(const T* __restrict__ S, int ld, int n,
                            const T* __restrict__ z = nullptr, const T* __restrict__ h = nullptr,
                            const T* __restrict__ mu = nullptr, T* __restrict__ nu = nullptr,
                            int* __restrict__ counters = nullptr, int* __restrict__ status = nullptr,
-                           T* __restrict__ q_old = nullptr, int slot0 = 0, int slot_end = 0) {
+                           T* __restrict__ q_old = nullptr, int slot0 = 0, int slot_end = 0,
+                           ChunkTab tab = ChunkTab{0, {}}, int* __restrict__ mirror_rows = nullptr) {
   // slots [slot0, slot_end) only (slot_end = 0: all of them): the columns of ONE column chunk of the factorisation,
   // re-evaluated from the downdated Sigma (Filter::update, EKF_W_RECOMPUTE)
   const int k = slot0 + blockIdx.x * blockDim.x + threadIdx.x;    // measurement slot
@@ -78,6 +121,7 @@ __global__ void k_sigma_ht(const T* __restrict__ S, int ld, int n,
     // launch: one launch less in front of the chain) and the reset of the work-queue heads of this update
     if (counters)
       for (int c = k; c < kQueueCounters; c += gridDim.x * blockDim.x) counters[c] = 0;
+    if (mirror_rows && blockIdx.x == 0) mirror_rows_slab(tab, midx, M, nfeat, pos, coding, mirror_rows);
     if (k >= nslots) return;
     if (k < M) check_measured_entry(midx, k, nfeat, status);
 #pragma unroll
@@ -181,7 +225,8 @@ k_sigma_ht_fast(const float* __restrict__ S, int ld, int n,
                 float* __restrict__ W, int ldy, int m_pad, int nfeat, int slot0, int slot_end,
                 const float* __restrict__ z, const float* __restrict__ h, const float* __restrict__ mu,
                 float* __restrict__ nu, int* __restrict__ counters, int* __restrict__ status, float* __restrict__ q_old,
-                int row_lo = 0) {     // rows [row_lo, n) of W (a rank of a sharded filter: its camera rows, its own rows)
+                int row_lo = 0,       // rows [row_lo, n) of W (a rank of a sharded filter: its camera rows, its own rows)
+                ChunkTab tab = ChunkTab{0, {}}, int* __restrict__ mirror_rows = nullptr) {   // the slab also writes the mirror-rule table
   constexpr int SL = 128, SEG = 6 * SL + 4;              // floats of a row segment: fp <= 3 in front, 768, the rest behind
   typedef float f4 __attribute__((ext_vector_type(4)));
   typedef float f2 __attribute__((ext_vector_type(2)));
@@ -196,6 +241,7 @@ k_sigma_ht_fast(const float* __restrict__ S, int ld, int n,
     if (q_old && k < 4) q_old[k] = mu[3 + k];
     if (counters)
       for (int c = k; c < kQueueCounters; c += gridDim.x * blockDim.x) counters[c] = 0;
+    if (mirror_rows && blockIdx.x == 0) mirror_rows_slab(tab, midx, M, nfeat, pos, coding, mirror_rows);
     if (k >= nslots) return;
     if (k < M) check_measured_entry(midx, k, nfeat, status);
 #pragma unroll
@@ -327,11 +373,7 @@ k_sigma_ht_fast(const float* __restrict__ S, int ld, int n,
 // features.  The 7 camera rows of W stay in registers across the features of the block.
 // Blocks past the feature blocks write the plane rows and the identity padding, 8 rows each.
 // ---------------------------------------------------------------------------------------
-// Column chunks of the factorisation (see Filter::update): chunk g covers columns [end[g-1], end[g]).
-struct ChunkTab {
-  int n;
-  int end[8];
-};
+// (ChunkTab, the column chunks of the factorisation: in front of k_sigma_ht)
 // Identity strip under S: chunk g keeps its own inverse Z_gg = L_gg^-T in rows [0, width_g) of the
 // strip, columns of the chunk: strip[i][c] = 1 where c - (first column of c's chunk) == i.
 __device__ __forceinline__ bool strip_is_one(const ChunkTab& t, int i, int c) {

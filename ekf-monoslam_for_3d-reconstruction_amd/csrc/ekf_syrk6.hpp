@@ -26,6 +26,7 @@
 // tile 145-190 (K = 384 .. 1152) against 100-118 for k_gemm_mfma on the same launches.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <climits>
 #include "ekf_dense.hpp"
 
 namespace ekf {
@@ -97,6 +98,13 @@ struct Syrk6Args {
   // slowest tiles, and the state update needs neither a launch nor a second stream.
   float* su_mu = nullptr; const float* su_V = nullptr; int su_ldy = 0, su_n = 0; const float* su_y = nullptr; int su_mpad = 0;
   float* su_qn = nullptr; int* su_counter = nullptr;
+  // Mirror rule (round 7, the plain filter's launches 0 .. G-2 of an update): {lo, hi} in device memory, the state rows the one
+  // reader of Sigma between this launch and the next -- the re-evaluation of the next chunk's W columns -- takes its feature
+  // columns from (mirror_rows_slab, ekf_dense.hpp).  A path-0 tile issues its mirror stores only if its row block
+  // [128 bi, 128 bi + 128) meets [lo, hi): every other mirror is overwritten by the update's last launch (nullptr: every tile
+  // mirrors, so Sigma is exactly symmetric again when the update returns) before anything reads it.  Diagonal and partly
+  // valid tiles (paths 1 and 2) always mirror.  nullptr: every tile mirrors, bit for bit the kernel of round 6.
+  const int* mirror_rows = nullptr;
 };
 
 // Every element pair {r, c}, r >= c, is computed ONCE, as element (r, c) of its canonical tile (A block = the block of r,
@@ -105,7 +113,8 @@ struct Syrk6Args {
 // sharded filter holds in its rows is bit-identical to what the plain filter computes: the list of a rank is simply every
 // canonical tile that touches one of its row blocks.
 // ABL (tools/syrk6_probe.hip only): 1 = no C traffic (the accumulators are kept live), 2 = no LDS-DMA (the ring keeps what it
-// has), 4 = every LDS-DMA reads the first record (always cache hits)
+// has), 4 = every LDS-DMA reads the first record (always cache hits), 8 = path 0 without its mirror stores (the ceiling of
+// what the mirror rule can save per launch)
 template <int ABL = 0>
 __global__ void __launch_bounds__(256, 2) k_syrk_bf16x6(Syrk6Args g) {
   constexpr int NS = 3, STG = 2 * kS6Rec;                      // ring stages; slots per stage (A record + B record)
@@ -116,6 +125,9 @@ __global__ void __launch_bounds__(256, 2) k_syrk_bf16x6(Syrk6Args g) {
   float* const C = g.C;
   const int ldc = g.ldc;
   const int nk = g.nk;
+  // rows whose columns the next reader of Sigma takes from the upper triangle (kernel argument -> scalar loads: wave-uniform)
+  int m_lo = 0, m_hi = INT_MAX;
+  if (g.mirror_rows != nullptr) { m_lo = g.mirror_rows[0]; m_hi = g.mirror_rows[1]; }
 
   // validity of the 128 rows of block b: 0 none, 1 all, 2 mixed
   auto block_class = [&](int b) {
@@ -246,7 +258,19 @@ __global__ void __launch_bounds__(256, 2) k_syrk_bf16x6(Syrk6Args g) {
     }
     // ---- epilogue: Sigma' = Sigma - acc (one rounding at the magnitude of Sigma) -------------------------------------------
     const bool diag = t.bi == t.bj;
-    epi_stores = (diag || (ABL & 1)) ? 0 : ((t.va == 1 ? 64 : 0) + (t.vb == 1 ? 16 : 0));
+    // does a path-0 tile mirror?  One decision per tile from wave-uniform values (t.bi came through readfirstlane, m_lo / m_hi
+    // through scalar loads): a scalar branch around the 16 mirror stores, no divergence in the epilogue
+    const bool mir = !(ABL & 8) && t.bi * 128 < m_hi && t.bi * 128 + 128 > m_lo;
+    // Stores per lane this epilogue is KNOWN to issue, for the counted waits of the next tile's steps 0 and 1.  At step s < 2
+    // the six loads of chunk s are followed in the queue by the six loads of chunk s + 1 (requested in the last two steps of
+    // this tile, resp. at step 0 of the next) and by E = epi_stores stores, so 6 + E operations may stay outstanding; vmcnt is
+    // a 6-bit field, so the wait is vmcnt(min(63, 6 + E)):
+    //   path 0, mirrored      E = 64 + 16 = 80 -> 86 -> vmcnt(63)
+    //   path 0, not mirrored  E = 64           -> 70 -> vmcnt(63)   (counting 80 here would still give 63: what must never
+    //                                                                 happen is a count ABOVE what was issued with E < 57)
+    //   path 1, B block valid E = 16           -> 22 -> vmcnt(22)
+    // From step 2 on the epilogue's stores are older than every chunk in flight and the plain vmcnt(6) covers them.
+    epi_stores = (diag || (ABL & 1)) ? 0 : ((t.va == 1 ? 64 : 0) + ((t.vb == 1 && (t.va != 1 || mir)) ? 16 : 0));
     const int path = (ABL & 1) ? 3 : ((t.va == 1 && !diag) ? 0 : ((t.va == 0 && !diag) ? 1 : 2));
     const int rb0 = t.bi * 128 + wr * 64 + 4 * h, cb0 = t.bj * 128 + wc * 64 + l31;
     if (path == 0) {
@@ -272,7 +296,7 @@ __global__ void __launch_bounds__(256, 2) k_syrk_bf16x6(Syrk6Args g) {
           for (int e = 0; e < 16; ++e) v[i][j][e] = v[i][j][e] - acc[i][j][e];
 #pragma unroll
           for (int e = 0; e < 16; ++e) Cd[(size_t)((e & 3) + 8 * (e >> 2)) * ldc] = v[i][j][e];
-          if (t.vb == 1 || (t.vb == 2 && valid(c))) {
+          if (mir && (t.vb == 1 || (t.vb == 2 && valid(c)))) {
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
               f32x4 o = {v[i][j][4 * gq], v[i][j][4 * gq + 1], v[i][j][4 * gq + 2], v[i][j][4 * gq + 3]};

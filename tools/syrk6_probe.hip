@@ -99,9 +99,35 @@ int main(int argc, char** argv) {
       hipFree(dtl);
     }
   }
+  // ---- the mirror rule (Syrk6Args::mirror_rows): the lower triangle and the diagonal tiles as the plain launch, an upper element
+  // (c, r) of a strictly lower tile stored only where the row block of r meets [lo, hi), every other one left as it was ---------
+  {
+    const int K = 384, c0 = 512;                          // r1: the plain result of this launch (the block above)
+    for (auto range : {std::pair<int, int>{14 + 6 * 300, 14 + 6 * 650}, std::pair<int, int>{0, 0}, std::pair<int, int>{127, 129}, std::pair<int, int>{0, INT_MAX}}) {
+      CK(hipMemcpy(S2, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+      const std::vector<int> hb = {range.first, range.second};
+      int* db = up(hb);
+      Syrk6Args b{img, nkc_total, c0 / 16, K / 16, S2, ld, dplain, (int)plain.size() / 2, counters + (cn++), 0, 0, INT_MAX};
+      b.mirror_rows = db;
+      k_syrk_bf16x6<0><<<448, 256>>>(b);
+      CK(hipDeviceSynchronize());
+      CK(hipMemcpy(r2.data(), S2, r2.size() * 4, hipMemcpyDeviceToHost));
+      size_t bad = 0, kept = 0, mirrored = 0;
+      for (int r = 0; r < n; ++r) for (int c = 0; c <= r; ++c) {
+        bad += (memcmp(&r1[(size_t)r * ld + c], &r2[(size_t)r * ld + c], 4) != 0);
+        if (r / 128 == c / 128) { bad += (memcmp(&r1[(size_t)c * ld + r], &r2[(size_t)c * ld + r], 4) != 0); continue; }
+        const bool in = (long long)(r / 128) * 128 < range.second && (r / 128) * 128 + 128 > range.first;
+        const float* want = in ? &r1[(size_t)c * ld + r] : &hs[(size_t)c * ld + r];
+        bad += (memcmp(want, &r2[(size_t)c * ld + r], 4) != 0);
+        (in ? mirrored : kept) += 1;
+      }
+      printf("mirror rows [%d,%d): %zu elements differ from the rule (%zu mirrors stored, %zu left untouched)\n", range.first, range.second, bad, mirrored, kept);
+      hipFree(db);
+    }
+  }
   // timing
   CK(hipMemset(S, 0, (size_t)n * ld * 4));
-  for (int K : {384, 512, 1152}) for (int wgs : {448, 512}) for (int var = 0; var < 7; ++var) {
+  for (int K : {384, 512, 592, 640, 1152}) for (int wgs : {448, 512}) for (int var = 0; var < 8; ++var) {
     float best = 1e9;
     for (int pass = 0; pass < 3; ++pass) {
       const int reps = 20;
@@ -115,13 +141,14 @@ int main(int argc, char** argv) {
           else if (var == 3) k_syrk_bf16x6<1><<<wgs, 256>>>(b);
           else if (var == 4) k_syrk_bf16x6<2><<<wgs, 256>>>(b);
           else if (var == 5) k_syrk_bf16x6<3><<<wgs, 256>>>(b);
-          else k_syrk_bf16x6<5><<<wgs, 256>>>(b);
+          else if (var == 6) k_syrk_bf16x6<5><<<wgs, 256>>>(b);
+          else k_syrk_bf16x6<8><<<wgs, 256>>>(b);
         }
       }
       hipEventRecord(eb); hipEventSynchronize(eb);
       float ms; hipEventElapsedTime(&ms, ea, eb); best = std::min(best, ms / reps);
     }
-    printf("K=%4d wgs=%3d %-22s %.1f us  %.1f TF fp32-equivalent\n", K, wgs, var == 0 ? "syrk3 (round 1)" : (var == 1 ? "syrk6 plain list" : (var == 2 ? "syrk6 half-tile tail" : (var == 3 ? "syrk6 half, no C" : (var == 4 ? "syrk6 half, no DMA" : (var == 5 ? "syrk6 half, no C no DMA" : "syrk6 half, no C, DMA hits"))))),
+    printf("K=%4d wgs=%3d %-22s %.1f us  %.1f TF fp32-equivalent\n", K, wgs, var == 0 ? "syrk3 (round 1)" : (var == 1 ? "syrk6 plain list" : (var == 2 ? "syrk6 half-tile tail" : (var == 3 ? "syrk6 half, no C" : (var == 4 ? "syrk6 half, no DMA" : (var == 5 ? "syrk6 half, no C no DMA" : (var == 6 ? "syrk6 half, no C, DMA hits" : "syrk6, no mirror stores")))))),
            best * 1e3, 2.0 * (plain.size() / 2) * 128 * 128 * K / best / 1e9);
   }
   // the image builder
