@@ -71,6 +71,9 @@ _PROTOS = {
     "ekf_update_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "ekf_rescue_high_innovation": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, _P]),
     "ekf_set_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "ekf_set_frame_raw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ekf_set_frame_raw_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ekf_get_frame": (C.c_int, [_P, _P, C.c_int]),
     "ekf_set_patch": (C.c_int, [_P, C.c_int, _P]),
     "ekf_get_patch": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ekf_get_blur_predictions": (C.c_int, [_P, _P]),
@@ -148,12 +151,14 @@ _PROTOS = {
     "ekf_sba_profile": (C.c_int, [_P, C.c_int]),
     "ekf_sba_get_profile": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
     "ekf_keyframe_create": (C.c_int, [_P, C.c_float, C.POINTER(_P)]),
+    "ekf_keyframe_create_raw": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "ekf_keyframe_destroy": (None, [_P]),
     "ekf_keyframe_last_error": (C.c_char_p, [_P]),
     "ekf_keyframe_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
     "ekf_keyframe_observe": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ekf_keyframe_get_emitted": (C.c_int, [_P, C.POINTER(C.c_int), _P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
     "ekf_keyframe_get_image": (C.c_int, [_P, _P, C.c_int]),
+    "ekf_keyframe_get_raw_image": (C.c_int, [_P, _P, C.c_int]),
     "ekf_keyframe_get_state": (C.c_int, [_P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "ekf_keyframe_reset": (C.c_int, [_P]),
 }

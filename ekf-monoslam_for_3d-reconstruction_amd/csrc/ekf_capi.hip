@@ -13,6 +13,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ekf_monoslam.h"
@@ -59,6 +60,8 @@ enum KernelId : int {
   KID_SEED_RESPONSE,
   KID_SEED_CANDIDATES,
   KID_SEED_SELECT,
+  KID_FRAME_UPLOAD,
+  KID_FRAME_INGEST,
   KID_COUNT
 };
 
@@ -68,7 +71,7 @@ static const char* kKernelNames[KID_COUNT] = {
     "chol_panel",      "chol_trailing",    "state_update",        "downdate_syrk",
     "solve_trmm",      "normalize_quat",  "add_feature",      "compact_transform",   "misc",
     "w_update", "allgather_h", "allgather_s", "allgather_v", "allgather_sigma",
-    "seed_mask", "seed_response", "seed_candidates", "seed_select"};
+    "seed_mask", "seed_response", "seed_candidates", "seed_select", "frame_upload", "frame_ingest"};
 
 // Which launch structure an update actually took (ekf_launch_count): host-side counters, always on, one increment per
 // launch.  The order is the ABI's `enum ekf_launch_kind`.
@@ -170,6 +173,8 @@ struct FilterBase {
   virtual int update_two_stage(const void*, const int*, int, int, unsigned int, double, double, unsigned char*,
                                unsigned char*, int*) = 0;
   virtual int set_frame(const unsigned char*, int, int, int) = 0;
+  virtual int set_frame_raw(const void*, int, int, int, int, bool) = 0;
+  virtual int get_frame(unsigned char*, int) = 0;
   virtual int set_patch(int, const unsigned char*) = 0;
   virtual int get_patch(int, int, unsigned char*) = 0;
   virtual int blur_predictions(void*) = 0;
@@ -294,6 +299,14 @@ struct Filter : FilterBase {
   size_t frame_cap = 0;
   int frame_w = 0, frame_h = 0;
   bool have_frame = false, have_blur = false;
+  // the camera's own frame: W x H x C bytes, tight, + kIngestSlack; d_frame is derived from it on the device
+  unsigned char* d_raw = nullptr;
+  size_t raw_cap = 0;
+  int raw_w = 0, raw_h = 0, raw_c = 0;
+  bool have_raw = false;
+  int4* d_ingest_tab = nullptr;                         // column records, then row records (ingest_tables)
+  size_t ingest_tab_cap = 0;
+  int ingest_tab_w = 0, ingest_tab_h = 0;               // the raw geometry the resident tables were computed for
   unsigned char *d_patch[2] = {nullptr, nullptr}, *d_mpatch[2] = {nullptr, nullptr};
   int cur_patch = 0;
   T* d_hb = nullptr;
@@ -377,7 +390,7 @@ struct Filter : FilterBase {
     void* ptrs[] = {d_pos, d_coding, d_mu[0], d_mu[1], d_S[0], d_S[1], d_scr, d_h, d_Hc, d_Hf, d_Sd,
                     d_flags, d_cflag, d_Jy, d_Yxyz, d_map_src, d_map_conv, d_Y, d_W, d_V, d_Dinv, d_z, d_midx,
                     d_status, d_tmp, d_K, d_tilemap, d_counters, d_ibuf, d_rmask, d_pts, d_tab,
-                    d_frame, d_patch[0], d_patch[1], d_mpatch[0], d_mpatch[1], d_hb, d_zm, d_found, d_score, d_keep,
+                    d_frame, d_raw, d_ingest_tab, d_patch[0], d_patch[1], d_mpatch[0], d_mpatch[1], d_hb, d_zm, d_found, d_score, d_keep,
                     d_Vimg, d_stage_send, d_stage_recv, d_archive, d_arch_idx, d_panel_tiles, d_shard_solve, d_shard_syrk,
                     d_td_blocks, d_small_stamps,
                     d_dist_lists, d_dist_counters, d_dist_send, d_dist_recv, d_sf_lists,
@@ -861,6 +874,91 @@ struct Filter : FilterBase {
     HIPCHK(hipStreamSynchronize(stream));            // the caller's buffer may be reused at once
     frame_w = width; frame_h = height;
     have_frame = true;
+    have_raw = false;                                // a key frame never pairs this frame with an older raw one
+    return EKF_OK;
+  }
+  // The camera's frame as it comes: one 2-D copy into d_raw, one k_frame_ingest launch into d_frame.
+  int set_frame_raw(const void* pixels, int width, int height, int channels, int stride, bool on_device) override {
+    if (!pixels || width <= 0 || height <= 0) FAIL(EKF_ERR_ARG, "bad raw frame");
+    if (channels != 1 && channels != 3) FAIL(EKF_ERR_ARG, "a raw frame has 1 (grey) or 3 (B, G, R) channels");
+    if ((long long)stride < (long long)width * channels) FAIL(EKF_ERR_ARG, "stride is shorter than width * channels");
+    if (cfg.scale < 1) FAIL(EKF_ERR_ARG, "ekf_config.scale must be >= 1 for a raw frame");
+    const int Wo = width / cfg.scale, Ho = height / cfg.scale;
+    if (Wo != cam.width || Ho != cam.height)
+      FAIL(EKF_ERR_ARG, "raw frame size / scale differs from ekf_config image_width / image_height");
+    const size_t row = (size_t)width * channels, need = row * height;
+    if (need >= ((size_t)1 << 31)) FAIL(EKF_ERR_UNSUPPORTED, "raw frames of 2 GiB or more are not supported");
+    HIPCHK(hipSetDevice(device));
+    int rc = ensure_image_buffers();
+    if (rc) return rc;
+    const size_t out = (size_t)Wo * Ho;
+    if (out > frame_cap) {
+      if (d_frame) HIPCHK(hipFree(d_frame));
+      d_frame = nullptr;
+      frame_cap = 0;
+      HIPCHK(hipMalloc(&d_frame, out));
+      frame_cap = out;
+    }
+    if (need > raw_cap) {
+      if (d_raw) HIPCHK(hipFree(d_raw));
+      d_raw = nullptr;
+      raw_cap = 0;
+      HIPCHK(hipMalloc(&d_raw, need + kIngestSlack));
+      raw_cap = need;
+    }
+    const int mode = (Wo == width && Ho == height) ? kIngestCopy
+                     : (width == 2 * Wo && height == 2 * Ho) ? kIngestArea2 : kIngestLinear;
+    if (mode == kIngestLinear && (ingest_tab_w != width || ingest_tab_h != height)) {
+      std::vector<int> tab;
+      ingest_tables(width, height, Wo, Ho, tab);
+      const size_t recs = (size_t)Wo + Ho;
+      if (recs > ingest_tab_cap) {
+        if (d_ingest_tab) HIPCHK(hipFree(d_ingest_tab));
+        d_ingest_tab = nullptr;
+        ingest_tab_cap = 0;
+        HIPCHK(hipMalloc(&d_ingest_tab, recs * sizeof(int4)));
+        ingest_tab_cap = recs;
+      }
+      ingest_tab_w = ingest_tab_h = 0;
+      HIPCHK(hipMemcpyAsync(d_ingest_tab, tab.data(), recs * sizeof(int4), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));          // (tab goes out of scope; once per geometry)
+      ingest_tab_w = width; ingest_tab_h = height;
+    }
+    have_raw = false;
+    {
+      Scope sc(this, KID_FRAME_UPLOAD);
+      HIPCHK(hipMemcpy2DAsync(d_raw, row, pixels, (size_t)stride, row, height,
+                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    }
+    {
+      Scope sc(this, KID_FRAME_INGEST);
+      IngestArgs a{d_raw, d_frame, d_ingest_tab, d_ingest_tab ? d_ingest_tab + Wo : nullptr, width, height, Wo, Ho};
+      // lanes per pass: copy 16 (C = 1) / 4 (C = 3) pixels each, area 4, linear 1; at most 1024 workgroups, then grid-stride
+      const size_t per = mode == kIngestCopy ? (channels == 1 ? 16 : 4) : (mode == kIngestArea2 ? 4 : 1);
+      const size_t lanes = mode == kIngestArea2 ? (size_t)((Wo + 3) / 4) * Ho : (out + per - 1) / per;
+      const int grid = (int)std::min<size_t>((lanes + 255) / 256, 1024);
+      auto go = [&](auto cc, auto mm) { k_frame_ingest<decltype(cc)::value, decltype(mm)::value><<<grid, 256, 0, stream>>>(a); };
+      using I1 = std::integral_constant<int, 1>; using I3 = std::integral_constant<int, 3>;
+      using M0 = std::integral_constant<int, kIngestCopy>; using M1 = std::integral_constant<int, kIngestArea2>;
+      using M2 = std::integral_constant<int, kIngestLinear>;
+      if (channels == 1) { if (mode == kIngestCopy) go(I1{}, M0{}); else if (mode == kIngestArea2) go(I1{}, M1{}); else go(I1{}, M2{}); }
+      else { if (mode == kIngestCopy) go(I3{}, M0{}); else if (mode == kIngestArea2) go(I3{}, M1{}); else go(I3{}, M2{}); }
+      HIPCHK(hipGetLastError());
+    }
+    if (!on_device) HIPCHK(hipStreamSynchronize(stream));     // the caller's buffer may be reused at once
+    frame_w = Wo; frame_h = Ho;
+    raw_w = width; raw_h = height; raw_c = channels;
+    have_frame = true;
+    have_raw = true;
+    return EKF_OK;
+  }
+  int get_frame(unsigned char* gray, int stride) override {
+    if (!gray || stride < frame_w) FAIL(EKF_ERR_ARG, "ekf_get_frame: gray must not be NULL and stride >= image_width");
+    if (!have_frame) FAIL(EKF_ERR_STATE, "ekf_get_frame: no frame was set");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipMemcpy2DAsync(gray, (size_t)stride, d_frame, (size_t)frame_w, (size_t)frame_w, frame_h, hipMemcpyDeviceToHost,
+                            stream));
+    HIPCHK(hipStreamSynchronize(stream));
     return EKF_OK;
   }
   int set_patch(int index, const unsigned char* data) override {
@@ -2993,6 +3091,11 @@ struct Filter : FilterBase {
     HIPCHK(hipMalloc(&k->d_rec, sizeof(KfRecord)));
     HIPCHK(hipMalloc(&k->d_cand, px));
     HIPCHK(hipMalloc(&k->d_emit, px));
+    if (k->raw_w > 0) {                                        // ekf_keyframe_create_raw: the two slots of the camera's own frame
+      const size_t rb = (size_t)k->raw_w * k->raw_h * k->raw_c;
+      HIPCHK(hipMalloc(&k->d_cand_raw, rb));
+      HIPCHK(hipMalloc(&k->d_emit_raw, rb));
+    }
     const KfState s0 = KfSelector::initial();
     HIPCHK(hipMemcpy(k->d_state, &s0, sizeof(s0), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(k->d_rec, 0, sizeof(KfRecord)));
@@ -3008,12 +3111,13 @@ struct Filter : FilterBase {
       else if (r[1] < 640 && r[2] < 480) rows.insert(rows.end(), r, r + 3);
     }
   }
-  // One probe on the filter's stream, the image grid when a frame is set, ONE read-back (record, status words and -- only
+  // One probe on the filter's stream, the image grid when a frame is set (a second one for the raw frame of a raw selector), ONE read-back (record, status words and -- only
   // when a predict / measure left them unread -- the track flags), then the host obeys the action word.
   int kf_observe(KfSelector* k, int frame_id, KfRecord* r) override {
     if (sh_on) FAIL(EKF_ERR_STATE, "ekf_keyframe_observe: the filter is sharded (Sigma[0:7,0:7] lives on one rank)");
     HIPCHK(hipSetDevice(device));
     const bool img = have_frame && frame_w == k->img_w && frame_h == k->img_h;
+    const bool raw = img && have_raw && k->d_cand_raw && raw_w == k->raw_w && raw_h == k->raw_h && raw_c == k->raw_c;
     k_keyframe_probe<T><<<1, 64, 0, stream>>>(mu(), S(), ld, frame_id, k->move_thresh, k->d_state + k->parity,
                                               k->d_state + (k->parity ^ 1), k->d_rec);
     if (img) {
@@ -3021,10 +3125,19 @@ struct Filter : FilterBase {
       const int grid = (int)std::min<size_t>((bytes / 16 + 255) / 256 + 1, 1024);
       k_keyframe_snapshot<<<grid, 256, 0, stream>>>(k->d_rec, d_frame, k->d_cand, k->d_emit, bytes);
     }
+    if (raw) {                                                 // the same action word moves the raw frame / the raw candidate
+      const size_t bytes = (size_t)raw_w * raw_h * raw_c;
+      const int grid = (int)std::min<size_t>((bytes / 16 + 255) / 256 + 1, 1024);
+      k_keyframe_snapshot<<<grid, 256, 0, stream>>>(k->d_rec, d_raw, k->d_cand_raw, k->d_emit_raw, bytes);
+    }
     // A failure from here on leaves the rule's state where it was (the roles are not flipped), but the image grid may have
     // run on a record nobody read: either slot may hold this frame now.  Both stop vouching for their image, so that a
     // later emit reports EKF_ERR_STATE from ekf_keyframe_get_image rather than pair an old id with a newer frame.
-    auto failed = [&](int rc) { if (img) k->cand_has_image = k->emit_has_image = false; return rc; };
+    auto failed = [&](int rc) {
+      if (img) k->cand_has_image = k->emit_has_image = false;
+      if (raw) k->cand_has_raw = k->emit_has_raw = false;
+      return rc;
+    };
     { const hipError_t launch = hipGetLastError(); if (launch != hipSuccess) failed(0); HIPCHK(launch); }
     { int rc = rb_add(r, k->d_rec, sizeof(KfRecord)); if (rc) return failed(rc); }
     std::vector<unsigned char> tb;
@@ -3037,16 +3150,19 @@ struct Filter : FilterBase {
       case kKfCandidate:
         kf_point4sba(k->cand_rows);
         k->cand_has_image = img;
+        k->cand_has_raw = raw;
         break;
       case kKfEmitCandidate:
         k->emit_rows = k->cand_rows;
         k->emit_has_image = img && k->cand_has_image;
+        k->emit_has_raw = raw && k->cand_has_raw;
         break;
       case kKfEmitCurrent:
       case kKfEmitFirst:
         if (k->keep_current) kf_point4sba(k->emit_rows);
         else k->emit_rows.assign(3, 0);                      // the literal "0  0  0" (monoslam_ransac.cpp:640, :672)
         k->emit_has_image = img;
+        k->emit_has_raw = raw;
         break;
       default: break;
     }
@@ -4717,6 +4833,15 @@ int ekf_set_frame(ekf_filter* f, const unsigned char* gray, int width, int heigh
   IMPL_OR_ARG(f);
   return f->impl->set_frame(gray, width, height, stride);
 }
+int ekf_set_frame_raw(ekf_filter* f, const unsigned char* pixels, int width, int height, int channels, int stride) {
+  IMPL_OR_ARG(f);
+  return f->impl->set_frame_raw(pixels, width, height, channels, stride, false);
+}
+int ekf_set_frame_raw_device(ekf_filter* f, const void* d_pixels, int width, int height, int channels, int stride) {
+  IMPL_OR_ARG(f);
+  return f->impl->set_frame_raw(d_pixels, width, height, channels, stride, true);
+}
+int ekf_get_frame(ekf_filter* f, unsigned char* gray, int stride) { IMPL_OR_ARG(f); return f->impl->get_frame(gray, stride); }
 int ekf_set_patch(ekf_filter* f, int index, const unsigned char* pixels) { IMPL_OR_ARG(f); return f->impl->set_patch(index, pixels); }
 int ekf_get_patch(ekf_filter* f, int index, int matching, unsigned char* out) {
   IMPL_OR_ARG(f);
@@ -5112,7 +5237,7 @@ int ekf_sba_get_profile(const ekf_sba* s, double* phase_ms, int max_iters, doubl
 // ---- key-frame selection -----------------------------------------------------------------------------
 struct ekf_keyframe { ekf::KfSelector* impl; };
 
-int ekf_keyframe_create(const ekf_filter* f, float move_thresh, ekf_keyframe** out) {
+static int keyframe_create(const ekf_filter* f, float move_thresh, int raw_w, int raw_h, int raw_c, ekf_keyframe** out) {
   if (!out) return EKF_ERR_ARG;
   *out = nullptr;
   if (!f || !(move_thresh > 0.f) || !std::isfinite(move_thresh)) {
@@ -5122,6 +5247,7 @@ int ekf_keyframe_create(const ekf_filter* f, float move_thresh, ekf_keyframe** o
   auto* k = new ekf::KfSelector();
   k->owner = f->impl;
   k->move_thresh = move_thresh;
+  k->raw_w = raw_w; k->raw_h = raw_h; k->raw_c = raw_c;
   const int rc = f->impl->kf_create(k);
   if (rc != EKF_OK) {
     ekf::g_create_error = f->impl->err;
@@ -5130,6 +5256,20 @@ int ekf_keyframe_create(const ekf_filter* f, float move_thresh, ekf_keyframe** o
   }
   *out = new ekf_keyframe{k};
   return EKF_OK;
+}
+
+int ekf_keyframe_create(const ekf_filter* f, float move_thresh, ekf_keyframe** out) {
+  return keyframe_create(f, move_thresh, 0, 0, 0, out);
+}
+
+int ekf_keyframe_create_raw(const ekf_filter* f, float move_thresh, int raw_width, int raw_height, int channels,
+                            ekf_keyframe** out) {
+  if (out && (raw_width <= 0 || raw_height <= 0 || (channels != 1 && channels != 3))) {
+    *out = nullptr;
+    ekf::g_create_error = "ekf_keyframe_create_raw: raw_width, raw_height > 0 and 1 or 3 channels";
+    return EKF_ERR_ARG;
+  }
+  return keyframe_create(f, move_thresh, raw_width, raw_height, channels, out);
 }
 
 void ekf_keyframe_destroy(ekf_keyframe* s) {
@@ -5214,6 +5354,25 @@ int ekf_keyframe_get_image(const ekf_keyframe* s, unsigned char* gray, int strid
   return EKF_OK;
 }
 
+int ekf_keyframe_get_raw_image(const ekf_keyframe* s, unsigned char* pixels, int stride) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  if (!pixels || stride < k->raw_w * k->raw_c) {
+    k->err = "ekf_keyframe_get_raw_image: pixels must not be NULL and stride >= raw_width * channels";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit || !k->emit_has_raw) {
+    k->err = "ekf_keyframe_get_raw_image: no emitted key frame with a raw image (ekf_keyframe_create_raw, and ekf_set_frame_raw "
+             "before ekf_keyframe_observe)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = k->err;
+  const size_t row = (size_t)k->raw_w * k->raw_c;
+  HIPCHK(hipSetDevice(k->device));
+  HIPCHK(hipMemcpy2D(pixels, (size_t)stride, k->d_emit_raw, row, row, (size_t)k->raw_h, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
 int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last_vrot3, float* min_cov, int* candidate_id) {
   if (!s) return EKF_ERR_ARG;
   auto* k = s->impl;
@@ -5238,6 +5397,7 @@ int ekf_keyframe_reset(ekf_keyframe* s) {
   k->cand_rows.clear();
   k->emit_rows.clear();
   k->cand_has_image = k->emit_has_image = k->have_emit = false;
+  k->cand_has_raw = k->emit_has_raw = false;
   k->emitted = ekf::KfRecord{};
   return EKF_OK;
 }

@@ -8,6 +8,11 @@
 // and spell the float / double operation order out.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
 #include "ekf_math.hpp"
 
 namespace ekf {
@@ -25,6 +30,145 @@ __global__ void k_capture_patch(const unsigned char* __restrict__ frame, int fw,
     patch[t] = v;
     mpatch[t] = v;
   }
+}
+
+// ---- raw frame -> matcher frame: captureNewFrame's cv::resize(INTER_LINEAR) by 1 / scale and
+// cvtColor(BGR2GRAY) (vR.cpp:235-245) as pinned integer arithmetic.  The host computes the coefficient tables once per
+// geometry (ingest_tables below); the device runs integers only.
+constexpr int kIngestCopy = 0, kIngestArea2 = 1, kIngestLinear = 2;
+constexpr int kIngestSlack = 64;      // bytes behind the raw frame that the area path may load (and never uses)
+
+struct IngestArgs {
+  const unsigned char* raw;           // H rows of W * C bytes, tight
+  unsigned char* gray;                // H' rows of W' bytes, tight
+  const int4* xtab;                   // per output column: sx, min(sx + 1, W - 1), a0, a1
+  const int4* ytab;                   // per output row: sy0, sy1 (clamped to [0, H - 1]), b0, b1
+  int W, H, Wo, Ho;
+};
+
+__device__ __forceinline__ unsigned bgr2gray(unsigned b, unsigned g, unsigned r) {
+  return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
+}
+
+// byte i of a little-endian word array (i is a compile-time constant after unrolling: one v_bfe_u32)
+__device__ __forceinline__ unsigned byte_of(const unsigned* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+
+// NW words from byte address p of any alignment: NW + 1 aligned dword loads (the compiler merges them into dwordx2 / x4:
+// a global load wider than a dword still only needs dword alignment) realigned with v_alignbyte.  Loads up to 4 bytes past
+// p + 4 NW: the caller keeps kIngestSlack bytes behind the buffer.
+template <int NW>
+__device__ __forceinline__ void load_unaligned_words(const unsigned char* p, unsigned* w) {
+  const unsigned sh = (unsigned)((size_t)p & 3);
+  const unsigned* q = reinterpret_cast<const unsigned*>(p - sh);
+  unsigned t[NW + 1];
+#pragma unroll
+  for (int k = 0; k <= NW; ++k) t[k] = q[k];
+#pragma unroll
+  for (int k = 0; k < NW; ++k) w[k] = __builtin_amdgcn_alignbyte(t[k + 1], t[k], sh);
+}
+
+// One launch, grid-stride, no LDS.  MODE is fixed by the geometry (§13):
+//   copy    (scale 1): the frame is one flat run of pixels; a lane takes 16 (C = 1, dwordx4 in and out) or 4 (C = 3: three
+//           dwords in, one out);
+//   area2   (W = 2 W' and H = 2 H'): a lane takes 4 adjacent output pixels = 8 C source bytes on each of two rows;
+//   linear  (everything else): a lane takes one output pixel and reads its 4 taps per channel; the output row is coalesced.
+template <int C, int MODE>
+__global__ void __launch_bounds__(256) k_frame_ingest(IngestArgs a) {
+  // (the host refuses frames of 2^31 bytes or more: pixel counts fit 32 bits, byte offsets are formed in size_t)
+  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned nthreads = gridDim.x * blockDim.x;
+  if (MODE == kIngestCopy) {
+    constexpr int P = C == 1 ? 16 : 4;                       // pixels per lane and step
+    const unsigned npix = (unsigned)a.Wo * a.Ho, nvec = npix / P;
+    for (unsigned i = tid; i < nvec; i += nthreads) {
+      if (C == 1) {
+        reinterpret_cast<uint4*>(a.gray)[i] = reinterpret_cast<const uint4*>(a.raw)[i];
+      } else {
+        const unsigned* s = reinterpret_cast<const unsigned*>(a.raw) + 3 * i;
+        const unsigned w[3] = {s[0], s[1], s[2]};
+        unsigned out = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out |= bgr2gray(byte_of(w, 3 * j), byte_of(w, 3 * j + 1), byte_of(w, 3 * j + 2)) << (8 * j);
+        reinterpret_cast<unsigned*>(a.gray)[i] = out;
+      }
+    }
+    for (unsigned i = nvec * P + tid; i < npix; i += nthreads)
+      a.gray[i] = C == 1 ? a.raw[i] : (unsigned char)bgr2gray(a.raw[3 * (size_t)i], a.raw[3 * (size_t)i + 1], a.raw[3 * (size_t)i + 2]);
+  } else if (MODE == kIngestArea2) {
+    constexpr int NW = 2 * C;                                // words per source row and lane: 4 outputs x 2 pixels x C bytes
+    const unsigned groups = (unsigned)(a.Wo + 3) >> 2;
+    const size_t pitch = (size_t)a.W * C;
+    const unsigned items = groups * (unsigned)a.Ho;
+    for (unsigned it = tid; it < items; it += nthreads) {
+      const int dy = (int)(it / groups), k = (int)(it % groups);
+      const unsigned char* p = a.raw + (size_t)(2 * dy) * pitch + (size_t)k * (4 * NW);
+      unsigned r0[NW], r1[NW];
+      load_unaligned_words<NW>(p, r0);
+      load_unaligned_words<NW>(p + pitch, r1);
+      unsigned out = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        unsigned ch[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+          ch[c] = (byte_of(r0, 2 * C * j + c) + byte_of(r0, 2 * C * j + C + c) + byte_of(r1, 2 * C * j + c) +
+                   byte_of(r1, 2 * C * j + C + c) + 2u) >> 2;
+        out |= (C == 1 ? ch[0] : bgr2gray(ch[0], ch[C > 1 ? 1 : 0], ch[C > 2 ? 2 : 0])) << (8 * j);
+      }
+      const size_t o = (size_t)dy * a.Wo + 4 * (size_t)k;
+      const int valid = min(4, a.Wo - 4 * k);               // the row's last group may be short; what it loaded beyond is dropped
+      if (valid == 4 && (o & 3) == 0) {
+        *reinterpret_cast<unsigned*>(a.gray + o) = out;
+      } else {
+        for (int j = 0; j < valid; ++j) a.gray[o + j] = (unsigned char)(out >> (8 * j));
+      }
+    }
+  } else {
+    const size_t pitch = (size_t)a.W * C;
+    const unsigned npix = (unsigned)a.Wo * a.Ho;
+    for (unsigned i = tid; i < npix; i += nthreads) {
+      const int dy = (int)(i / (unsigned)a.Wo), dx = (int)(i % (unsigned)a.Wo);
+      const int4 xt = a.xtab[dx], yt = a.ytab[dy];
+      const unsigned char* s0 = a.raw + (size_t)yt.x * pitch;
+      const unsigned char* s1 = a.raw + (size_t)yt.y * pitch;
+      const size_t x0 = (size_t)xt.x * C, x1 = (size_t)xt.y * C;     // (a1 = 0 wherever sx + 1 was clamped: the tap counts for nothing)
+      int ch[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int h0 = (int)s0[x0 + c] * xt.z + (int)s0[x1 + c] * xt.w;
+        const int h1 = (int)s1[x0 + c] * xt.z + (int)s1[x1 + c] * xt.w;
+        ch[c] = (((yt.z * (h0 >> 4)) >> 16) + ((yt.w * (h1 >> 4)) >> 16) + 2) >> 2;
+      }
+      a.gray[i] = (unsigned char)(C == 1 ? (unsigned)ch[0] : bgr2gray(ch[0], ch[C > 1 ? 1 : 0], ch[C > 2 ? 2 : 0]));
+    }
+  }
+}
+
+// xofs / alpha and yofs / beta of cv::resize's 8-bit INTER_LINEAR path (§13), on the host: fp32 / fp64 exactly as written,
+// nothing contracted.  tab: Wo column records, then Ho row records.
+inline void ingest_tables(int W, int H, int Wo, int Ho, std::vector<int>& tab) {
+#pragma clang fp contract(off)
+  tab.assign(4 * ((size_t)Wo + Ho), 0);
+  auto fill = [&](int n_src, int n_dst, int* out, bool zero_frac_at_border) {
+#pragma clang fp contract(off)
+    const double scale = (double)n_src / n_dst;
+    for (int d = 0; d < n_dst; ++d) {
+      float f = (float)((d + 0.5) * scale - 0.5);
+      int s = (int)floorf(f);
+      f -= (float)s;
+      if (zero_frac_at_border) {
+        if (s < 0) { s = 0; f = 0.f; }
+        if (s >= n_src - 1) { s = n_src - 1; f = 0.f; }
+      }
+      const float w0 = (1.f - f) * 2048.f, w1 = f * 2048.f;
+      out[4 * d + 0] = std::min(std::max(s, 0), n_src - 1);
+      out[4 * d + 1] = std::min(std::max(s + 1, 0), n_src - 1);
+      out[4 * d + 2] = (int)(short)lrintf(w0);              // cvRound: round half to even (the default rounding mode)
+      out[4 * d + 3] = (int)(short)lrintf(w1);
+    }
+  };
+  fill(W, Wo, tab.data(), true);
+  fill(H, Ho, tab.data() + 4 * (size_t)Wo, false);
 }
 
 // dst[k] = src[keep[k]] for the template stores after removeFeature (vR.cpp:373-421 erases patches[index]).

@@ -152,6 +152,10 @@ struct KfSelector {
   unsigned char *d_cand = nullptr, *d_emit = nullptr;
   int img_w = 0, img_h = 0;
   bool cand_has_image = false, emit_has_image = false, have_emit = false;
+  // ekf_keyframe_create_raw: the same two slots for the camera's own frame (raw_w x raw_h x raw_c bytes)
+  unsigned char *d_cand_raw = nullptr, *d_emit_raw = nullptr;
+  int raw_w = 0, raw_h = 0, raw_c = 0;
+  bool cand_has_raw = false, emit_has_raw = false;
   std::vector<int> cand_rows, emit_rows;                // 3 ints per row
   KfRecord emitted{};
 
@@ -161,12 +165,14 @@ struct KfSelector {
     return s;
   }
   ~KfSelector() {
-    if (!d_state && !d_rec && !d_cand && !d_emit) return;
+    if (!d_state && !d_rec && !d_cand && !d_emit && !d_cand_raw && !d_emit_raw) return;
     hipSetDevice(device);
     if (d_state) hipFree(d_state);
     if (d_rec) hipFree(d_rec);
     if (d_cand) hipFree(d_cand);
     if (d_emit) hipFree(d_emit);
+    if (d_cand_raw) hipFree(d_cand_raw);
+    if (d_emit_raw) hipFree(d_emit_raw);
   }
 };
 

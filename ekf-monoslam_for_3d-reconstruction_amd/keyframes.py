@@ -52,11 +52,20 @@ class KeyframeResult:
 class KeyframeSelector:
     """monoslam_ransac.cpp:585-687 for one (unsharded) filter."""
 
-    def __init__(self, filter, move_thresh: float = 18.0, keep_current_projections: bool = False):
+    def __init__(self, filter, move_thresh: float = 18.0, keep_current_projections: bool = False, raw_shape=None):
+        """``raw_shape`` = (H, W) or (H, W, 3) of the camera's own frame makes a raw selector: it also keeps the frame
+        given to ``VSlamFilter.setFrameRaw`` / ``captureNewFrame`` for the candidate and the emitted key frame."""
         self._lib = capi.load_library()
         self._filter = filter
         self._h = C.c_void_p()
-        rc = self._lib.ekf_keyframe_create(filter._h, float(move_thresh), C.byref(self._h))
+        self.raw_shape = None if raw_shape is None else tuple(int(v) for v in raw_shape)
+        if self.raw_shape is None:
+            rc = self._lib.ekf_keyframe_create(filter._h, float(move_thresh), C.byref(self._h))
+        else:
+            if len(self.raw_shape) not in (2, 3):
+                raise ValueError("raw_shape is (H, W) or (H, W, 3)")
+            rc = self._lib.ekf_keyframe_create_raw(filter._h, float(move_thresh), self.raw_shape[1], self.raw_shape[0],
+                                                   1 if len(self.raw_shape) == 2 else self.raw_shape[2], C.byref(self._h))
         if rc != 0:
             msg = self._lib.ekf_keyframe_last_error(None)
             raise EkfError(rc, msg.decode() if msg else "ekf_keyframe_create failed")
@@ -109,6 +118,14 @@ class KeyframeSelector:
         self._check(self._lib.ekf_keyframe_get_image(self._h, out.ctypes.data_as(C.c_void_p), out.strides[0]))
         return out
 
+    def emitted_raw_image(self) -> np.ndarray:
+        """The raw frame of the last emitted key frame, uint8 of ``raw_shape`` (B, G, R): a raw selector only."""
+        if self.raw_shape is None:
+            raise EkfError(4, "not a raw selector (KeyframeSelector(..., raw_shape=...))")
+        out = np.zeros(self.raw_shape, np.uint8)
+        self._check(self._lib.ekf_keyframe_get_raw_image(self._h, out.ctypes.data_as(C.c_void_p), out.strides[0]))
+        return out
+
     def state(self) -> dict:
         pose, vrot = np.zeros(7, np.float32), np.zeros(3, np.float32)
         mc, cid = C.c_float(0), C.c_int(0)
@@ -128,8 +145,20 @@ def write_pgm(path: str, gray) -> None:
         fh.write(g.tobytes())
 
 
+def write_ppm(path: str, bgr) -> None:
+    """Binary P6 from a (H, W, 3) image in B, G, R order (the channels are swapped to R, G, B)."""
+    a = np.asarray(bgr, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_ppm takes a (H, W, 3) image")
+    with open(path, "wb") as fh:
+        fh.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        fh.write(np.ascontiguousarray(a[:, :, ::-1]).tobytes())
+
+
 class KeyframeRecorder:
-    """What the node writes around the selector: ``observe()`` per frame, ``finish()`` at the end."""
+    """What the node writes around the selector: ``observe()`` per frame, ``finish()`` at the end.  With ``images`` a raw
+    selector's key frames are written at raw size, as the node saves them: ``<id>.ppm`` (3 channels) or ``<id>.pgm`` (1);
+    a plain selector's as the matcher's grey frame, ``<id>.pgm``."""
 
     def __init__(self, selector: KeyframeSelector, directory: str, images: bool = False):
         self.selector = selector
@@ -147,7 +176,13 @@ class KeyframeRecorder:
         res = self.selector.observe(frame_id)
         if res.emitted:
             self.append(res.record)
-            if self.images:
+            if self.images and getattr(self.selector, "raw_shape", None) is not None:
+                raw = self.selector.emitted_raw_image()
+                if raw.ndim == 3 and raw.shape[2] == 3:
+                    write_ppm(os.path.join(self.directory, "%d.ppm" % res.record.id), raw)
+                else:
+                    write_pgm(os.path.join(self.directory, "%d.pgm" % res.record.id), raw.reshape(raw.shape[0], raw.shape[1]))
+            elif self.images:
                 write_pgm(os.path.join(self.directory, "%d.pgm" % res.record.id), self.selector.emitted_image())
         return res
 

@@ -108,12 +108,18 @@ class VSlamFilter:
         self._check(self._lib.ekf_synchronize(self._h))
 
     # -- reference API ------------------------------------------------------------------------
-    def captureNewFrame(self, time_stamp: Optional[float] = None):
-        """Time-stamp half of captureNewFrame (vR.cpp:226-233): sets dT."""
+    def captureNewFrame(self, image=None, time_stamp: Optional[float] = None):
+        """captureNewFrame(img, time_stamp) (vR.cpp:226-245): dT from the time stamps first, then the camera's own frame
+        (``setFrameRaw``: resize by ``scale`` and grey conversion on the device).  Either half may be left
+        out; a single number is the time stamp (the call as it was before there was an image half)."""
+        if time_stamp is None and image is not None and np.isscalar(image):
+            image, time_stamp = None, image
         if time_stamp is not None:
             if self._old_ts > 0:
                 self.setDt(time_stamp - self._old_ts)
             self._old_ts = time_stamp
+        if image is not None:
+            self.setFrameRaw(image)
 
     def setDt(self, dT: float):
         self._check(self._lib.ekf_set_dt(self._h, float(dT)))
@@ -207,6 +213,39 @@ class VSlamFilter:
         if g.ndim != 2:
             raise ValueError("frame must be a single-channel 8-bit image")
         self._check(self._lib.ekf_set_frame(self._h, self._ptr(g), g.shape[1], g.shape[0], g.strides[0]))
+
+    def setFrameRaw(self, image):
+        """The camera's frame before resize / grayscale: a uint8 array (H, W) or (H, W, 3) in B, G, R order (rows may be
+        strided, pixels may not), or a ``torch.uint8`` tensor on the filter's device of the same shapes.  The tensor is
+        read on the filter's stream without a host synchronisation: keep it alive and unchanged until ``synchronize()``."""
+        if hasattr(image, "is_cuda"):                                    # a torch tensor
+            t = image
+            if not t.is_cuda:
+                image = t.numpy()
+            else:
+                import torch
+                if t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (1, 3)):
+                    raise ValueError("raw frame tensor must be uint8 of shape (H, W) or (H, W, 3)")
+                ch = 1 if t.dim() == 2 else int(t.shape[2])
+                st = t.stride()
+                if (t.dim() == 3 and st[2] != 1) or st[1] != ch or st[0] < int(t.shape[1]) * ch:
+                    raise ValueError("raw frame tensor must have contiguous pixels (only the rows may be strided)")
+                self._check(self._lib.ekf_set_frame_raw_device(self._h, C.c_void_p(t.data_ptr()), int(t.shape[1]),
+                                                               int(t.shape[0]), ch, int(st[0])))
+                return
+        a = np.asarray(image)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+            raise ValueError("raw frame must be uint8 of shape (H, W) or (H, W, 3)")
+        ch = 1 if a.ndim == 2 else int(a.shape[2])
+        if (a.ndim == 3 and a.strides[2] != 1) or a.strides[1] != ch or a.strides[0] < a.shape[1] * ch:
+            a = np.ascontiguousarray(a)
+        self._check(self._lib.ekf_set_frame_raw(self._h, self._ptr(a), a.shape[1], a.shape[0], ch, a.strides[0]))
+
+    def getFrame(self):
+        """The matcher frame as the device consumers see it: uint8 (image_height, image_width)."""
+        out = np.zeros((int(self._cfg.image_height), int(self._cfg.image_width)), np.uint8)
+        self._check(self._lib.ekf_get_frame(self._h, self._ptr(out), out.strides[0]))
+        return out
 
     def setPatch(self, index: int, pixels):
         p = np.ascontiguousarray(pixels, np.uint8).reshape(-1)

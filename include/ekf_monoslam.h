@@ -247,12 +247,32 @@ int ekf_update_two_stage(ekf_filter* f, const void* z, const int* indices, int M
                          unsigned char* is_low_innovation, unsigned char* is_high_innovation, int* hypotheses_drawn);
 
 /* ---- image side: what sits between predict() and the EKF update in the reference ----
- * captureNewFrame's image (vR.cpp:234-245) AFTER the node's resize / grayscale: 8-bit, single channel,
+ * captureNewFrame's image (vR.cpp:234-245) AFTER the node's resize / grayscale (ekf_set_frame_raw below takes the
+ * frame BEFORE them): 8-bit, single channel,
  * image_width x image_height of the config; `stride` = bytes per row.  The frame is copied to the device.
  * While a frame is set, ekf_add_feature also captures the feature's window_size^2 template at
  * ((int)(u - w/2), (int)(v - w/2)) (Patch::Patch in addFeature, vR.cpp:318) and removals keep the
  * templates aligned with their features (vR.cpp:1296-1299). */
 int ekf_set_frame(ekf_filter* f, const unsigned char* gray, int width, int height, int stride);
+/* The camera's own frame: 8-bit, `channels` = 1 (grey) or 3 (interleaved B, G, R), width x height,
+ * `stride` bytes per row.  The frame is copied once into a device buffer the filter owns and the matcher frame of
+ * ekf_set_frame is derived from it ON THE DEVICE by one launch: cv::resize(INTER_LINEAR) by 1 / ekf_config.scale, channel
+ * by channel, then cvtColor(BGR2GRAY), both restated as the integer arithmetic section 13 pins (vR.cpp:235-245).
+ * width / scale x height / scale (integer division) must be image_width x image_height of the config.  Every consumer
+ * (templates, NCC search, corner seeding, key-frame images) sees the derived frame as if ekf_set_frame had delivered it;
+ * a raw key-frame selector (ekf_keyframe_create_raw) additionally keeps the raw frame.  A later ekf_set_frame drops the
+ * raw frame.  On a sharded filter every rank is given the same frame and derives it itself (no collective).
+ * EKF_ERR_ARG, before the device is touched: pixels NULL, channels not 1 / 3, stride < width * channels, scale < 1,
+ * derived size != config size.
+ *  - ekf_set_frame_raw: `pixels` is host memory; the call synchronises (the buffer may be reused at once);
+ *  - ekf_set_frame_raw_device: `d_pixels` is device memory (a decoder's output, a tensor); the copy and the launch are
+ *    queued on the filter's stream and the host is NOT synchronised: the buffer must stay valid and unchanged until
+ *    ekf_synchronize (or any call that reads results back) returns;
+ *  - ekf_get_frame: the matcher frame as the consumers see it, image_height rows of image_width bytes, `stride` bytes
+ *    apart (inspection / tests).  EKF_ERR_STATE without a frame. */
+int ekf_set_frame_raw(ekf_filter* f, const unsigned char* pixels, int width, int height, int channels, int stride);
+int ekf_set_frame_raw_device(ekf_filter* f, const void* d_pixels, int width, int height, int channels, int stride);
+int ekf_get_frame(ekf_filter* f, unsigned char* gray, int stride);
 /* Patch::patch of feature `index`: window_size^2 bytes, row-major (test injection / inspection).
  * matching != 0 reads Patch::matching_patch (the blurred copy or the last matched window). */
 int ekf_set_patch(ekf_filter* f, int index, const unsigned char* pixels);
@@ -650,6 +670,14 @@ int ekf_sba_get_profile(const ekf_sba* s, double* phase_ms, int max_iters, doubl
  *    max_rows rows are written; every output may be NULL.  EKF_ERR_STATE before the first emit;
  *  - get_image: the emitted key frame's image, image_height rows of image_width bytes, `stride` bytes apart: the one
  *    copy an image makes to the host.  EKF_ERR_STATE when nothing was emitted or no frame had been set for it;
+ *  - create_raw: a selector that ALSO keeps the camera's own frame: two more device slots of
+ *    raw_height x raw_width x channels bytes, allocated here.  When the filter holds a raw frame of exactly that geometry
+ *    (ekf_set_frame_raw), observe moves it with a second image launch under the same action word: still one read-back
+ *    and one synchronisation.  Otherwise it behaves as a selector of ekf_keyframe_create;
+ *  - get_raw_image: the emitted key frame's raw image, raw_height rows of raw_width * channels bytes, `stride` bytes
+ *    apart (the node's cv_ptr->image / Selected_Pose, monoslam_ransac.cpp:599-679).  EKF_ERR_STATE when the emitted frame
+ *    has none: a plain selector, a frame set with ekf_set_frame, another geometry, or a failed observe in between (the
+ *    rule of get_image);
  *  - get_state: last_pose (7), last_vrot (3), min_cov and the candidate id (0: none yet), each may be NULL;
  *  - reset: back to the state after create (options kept).
  * Null handles and out-of-range arguments are EKF_ERR_ARG before the device is touched. */
@@ -671,7 +699,10 @@ int ekf_keyframe_set_option(ekf_keyframe* s, int option, int value);
 int ekf_keyframe_observe(ekf_keyframe* s, ekf_filter* f, int frame_id, int* action, float* dist, float* cov);
 int ekf_keyframe_get_emitted(const ekf_keyframe* s, int* id, double* pose7, double* cov49, int max_rows, int* prj_rows,
                              int* n_rows);
+int ekf_keyframe_create_raw(const ekf_filter* f, float move_thresh, int raw_width, int raw_height, int channels,
+                            ekf_keyframe** out);
 int ekf_keyframe_get_image(const ekf_keyframe* s, unsigned char* gray, int stride);
+int ekf_keyframe_get_raw_image(const ekf_keyframe* s, unsigned char* pixels, int stride);
 int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last_vrot3, float* min_cov, int* candidate_id);
 int ekf_keyframe_reset(ekf_keyframe* s);
 

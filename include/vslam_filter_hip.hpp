@@ -2,7 +2,7 @@
 // (mono-slam/src/vslamRansac.hpp:94-141) over the C ABI of ekf_monoslam.h.
 //
 // Same method names, argument meaning and return conventions as the reference, minus the
-// image-side methods (captureNewFrame(cv::Mat), findNewFeatures, drawing).  Eigen / OpenCV
+// drawing methods; captureNewFrame takes the camera's pixels instead of a cv::Mat.  Eigen / OpenCV
 // types are replaced by plain float arrays so that the header has no dependencies; a node
 // that has Eigen can `Eigen::Map<MatrixXf>` the column-major buffers directly.
 // Link: -lekfslam_hip (built by ekf-monoslam_for_3d-reconstruction_amd/csrc/Makefile).
@@ -32,6 +32,25 @@ class VSlamFilterHip {
   void captureNewFrame(double time_stamp) {
     if (old_ts_ > 0) check(ekf_set_dt(h_, time_stamp - old_ts_));
     old_ts_ = time_stamp;
+  }
+  // captureNewFrame(cv::Mat newFrame, double time_stamp) (vR.cpp:226-245) with the camera's own frame: dT first, then
+  // the image -- 8-bit, `channels` = 1 or 3 (B, G, R), `stride` bytes per row, width / scale x height / scale = the
+  // config's frame size.  The resize by `scale` and the grey conversion run on the device.
+  void captureNewFrame(const unsigned char* pixels, int width, int height, int channels, int stride, double time_stamp) {
+    captureNewFrame(time_stamp);
+    check(ekf_set_frame_raw(h_, pixels, width, height, channels, stride));
+  }
+  // the same from device memory, queued on the filter's stream without a host synchronisation: d_pixels must stay valid
+  // and unchanged until ekf_synchronize(handle())
+  void captureNewFrameDevice(const void* d_pixels, int width, int height, int channels, int stride, double time_stamp) {
+    captureNewFrame(time_stamp);
+    check(ekf_set_frame_raw_device(h_, d_pixels, width, height, channels, stride));
+  }
+  // the matcher frame as the device consumers see it: height rows of width bytes
+  std::vector<unsigned char> getFrame(int width, int height) {
+    std::vector<unsigned char> g((size_t)width * height);
+    check(ekf_get_frame(h_, g.data(), width));
+    return g;
   }
   double getDt() const { return ekf_get_dt(h_); }
 
@@ -339,6 +358,15 @@ class KeyframeSelectorHip {
       throw std::runtime_error(std::string("ekf_keyframe_create: ") + ekf_keyframe_last_error(nullptr));
     if (keep_current_projections) check(ekf_keyframe_set_option(h_, EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS, 1));
   }
+  // a raw selector: it also keeps the camera's own frame (raw_width x raw_height x channels, as given to
+  // VSlamFilterHip::captureNewFrame) of the candidate and of the emitted key frame -- the image the node saves
+  KeyframeSelectorHip(VSlamFilterHip& filter, int raw_width, int raw_height, int channels, float MoveThresh = 18.f,
+                      bool keep_current_projections = false)
+      : f_(filter.handle()) {
+    if (ekf_keyframe_create_raw(f_, MoveThresh, raw_width, raw_height, channels, &h_) != EKF_OK)
+      throw std::runtime_error(std::string("ekf_keyframe_create_raw: ") + ekf_keyframe_last_error(nullptr));
+    if (keep_current_projections) check(ekf_keyframe_set_option(h_, EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS, 1));
+  }
   ~KeyframeSelectorHip() { ekf_keyframe_destroy(h_); }
   KeyframeSelectorHip(const KeyframeSelectorHip&) = delete;
   KeyframeSelectorHip& operator=(const KeyframeSelectorHip&) = delete;
@@ -365,6 +393,12 @@ class KeyframeSelectorHip {
     std::vector<unsigned char> g((size_t)width * height);
     check(ekf_keyframe_get_image(h_, g.data(), width));
     return g;
+  }
+  // the emitted key frame's raw image (a raw selector): raw_height rows of raw_width * channels bytes
+  std::vector<unsigned char> emittedRawImage(int raw_width, int raw_height, int channels) {
+    std::vector<unsigned char> p((size_t)raw_width * raw_height * channels);
+    check(ekf_keyframe_get_raw_image(h_, p.data(), raw_width * channels));
+    return p;
   }
   void state(float last_pose[7], float last_vrot[3], float* min_cov, int* candidate_id) {
     check(ekf_keyframe_get_state(h_, last_pose, last_vrot, min_cov, candidate_id));
