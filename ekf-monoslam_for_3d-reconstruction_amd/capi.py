@@ -41,6 +41,11 @@ class EkfConfig(C.Structure):
     ]
 
 
+class EkfSbaCamera(C.Structure):
+    """ekf_sba_camera: the pinhole K = (fx, fy, cx, cy)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function the header declares (used by the ABI export test)."""
     text = open(header_path).read()
@@ -161,6 +166,11 @@ _PROTOS = {
     "ekf_keyframe_get_raw_image": (C.c_int, [_P, _P, C.c_int]),
     "ekf_keyframe_get_state": (C.c_int, [_P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "ekf_keyframe_reset": (C.c_int, [_P]),
+    "ekf_rectified_camera": (C.c_int, [_P, C.c_int, _P]),
+    "ekf_get_frame_rectified": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "ekf_undistort_pixels": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "ekf_keyframe_get_image_rectified": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "ekf_keyframe_get_emitted_rectified": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -27,6 +27,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_shard.hpp"
 #include "ekf_sba.hpp"
+#include "ekf_rectify.hpp"
 #include "ekf_keyframe.hpp"
 
 namespace ekf {
@@ -62,6 +63,7 @@ enum KernelId : int {
   KID_SEED_SELECT,
   KID_FRAME_UPLOAD,
   KID_FRAME_INGEST,
+  KID_FRAME_RECTIFY,
   KID_COUNT
 };
 
@@ -71,7 +73,7 @@ static const char* kKernelNames[KID_COUNT] = {
     "chol_panel",      "chol_trailing",    "state_update",        "downdate_syrk",
     "solve_trmm",      "normalize_quat",  "add_feature",      "compact_transform",   "misc",
     "w_update", "allgather_h", "allgather_s", "allgather_v", "allgather_sigma",
-    "seed_mask", "seed_response", "seed_candidates", "seed_select", "frame_upload", "frame_ingest"};
+    "seed_mask", "seed_response", "seed_candidates", "seed_select", "frame_upload", "frame_ingest", "frame_rectify"};
 
 // Which launch structure an update actually took (ekf_launch_count): host-side counters, always on, one increment per
 // launch.  The order is the ABI's `enum ekf_launch_kind`.
@@ -189,6 +191,9 @@ struct FilterBase {
   virtual int shard_rebalance() = 0;
   virtual int kf_create(KfSelector*) = 0;
   virtual int kf_observe(KfSelector*, int, KfRecord*) = 0;
+  virtual int rectified_camera(int, ekf_sba_camera*) = 0;
+  virtual int get_frame_rectified(int, unsigned char*, int) = 0;
+  virtual int undistort_pixels(int, const double*, int, double*) = 0;
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -304,6 +309,7 @@ struct Filter : FilterBase {
   size_t raw_cap = 0;
   int raw_w = 0, raw_h = 0, raw_c = 0;
   bool have_raw = false;
+  RectScratch rect;                                     // on-demand rectification: never touched per frame
   int4* d_ingest_tab = nullptr;                         // column records, then row records (ingest_tables)
   size_t ingest_tab_cap = 0;
   int ingest_tab_w = 0, ingest_tab_h = 0;               // the raw geometry the resident tables were computed for
@@ -396,6 +402,7 @@ struct Filter : FilterBase {
                     d_dist_lists, d_dist_counters, d_dist_send, d_dist_recv, d_sf_lists,
                     d_trk, d_seed_mask, d_seed_lam, d_seed_aux, d_seed_ckey, d_seed_cidx, d_seed_org, d_seed_out};
     for (void* p : ptrs) if (p) hipFree(p);
+    rect.release();
     mark("host memory");
     for (int s = 0; s < kInSlots; ++s) { if (h_in[s]) hipHostFree(h_in[s]); if (ev_in[s]) hipEventDestroy(ev_in[s]); }
     if (h_pred) hipHostFree(h_pred);
@@ -959,6 +966,40 @@ struct Filter : FilterBase {
     HIPCHK(hipMemcpy2DAsync(gray, (size_t)stride, d_frame, (size_t)frame_w, (size_t)frame_w, frame_h, hipMemcpyDeviceToHost,
                             stream));
     HIPCHK(hipStreamSynchronize(stream));
+    return EKF_OK;
+  }
+  // ---- rectification for pinhole consumers (kernels in ekf_rectify.hpp) ---------------------------------
+  // raw = 0: the matcher frame (s = 1); raw = 1: the raw frame (s = ekf_config.scale), whose geometry is known once a raw
+  // frame was set.  Nothing of the filter's state is read or written, and no launch kind is counted.
+  int rectified_camera(int raw, ekf_sba_camera* K) override {
+    if ((raw != 0 && raw != 1) || !K) FAIL(EKF_ERR_ARG, "ekf_rectified_camera: raw is 0 or 1 and K must not be NULL");
+    if (raw && raw_w <= 0) FAIL(EKF_ERR_STATE, "ekf_rectified_camera: no raw frame was set (the raw geometry is unknown)");
+    double k[4];
+    rect_camera(rect_cam(cam, raw ? cfg.scale : 1), k);
+    K->fx = k[0]; K->fy = k[1]; K->cx = k[2]; K->cy = k[3];
+    return EKF_OK;
+  }
+  int get_frame_rectified(int raw, unsigned char* out, int stride) override {
+    if ((raw != 0 && raw != 1) || !out) FAIL(EKF_ERR_ARG, "ekf_get_frame_rectified: raw is 0 or 1 and out must not be NULL");
+    if (!have_frame) FAIL(EKF_ERR_STATE, "ekf_get_frame_rectified: no frame was set");
+    if (raw && !have_raw) FAIL(EKF_ERR_STATE, "ekf_get_frame_rectified: no raw frame is held (ekf_set_frame_raw)");
+    const int W = raw ? raw_w : frame_w, H = raw ? raw_h : frame_h, Cn = raw ? raw_c : 1;
+    if ((long long)stride < (long long)W * Cn) FAIL(EKF_ERR_ARG, "ekf_get_frame_rectified: stride is shorter than a row");
+    HIPCHK(hipSetDevice(device));
+    {
+      Scope sc(this, KID_FRAME_RECTIFY);
+      HIPCHK(rectify_launch(rect, stream, raw ? d_raw : d_frame, W, H, Cn, rect_cam(cam, raw ? cfg.scale : 1)));
+    }
+    HIPCHK(rectified_to_host(rect, stream, W, H, Cn, out, (size_t)stride));
+    return EKF_OK;
+  }
+  int undistort_pixels(int raw, const double* uv, int n, double* out) override {
+    if ((raw != 0 && raw != 1) || n < 0 || (n > 0 && (!uv || !out)))
+      FAIL(EKF_ERR_ARG, "ekf_undistort_pixels: raw is 0 or 1, n >= 0, uv and out must not be NULL");
+    if (raw && raw_w <= 0) FAIL(EKF_ERR_STATE, "ekf_undistort_pixels: no raw frame was set (the raw geometry is unknown)");
+    if (n == 0) return EKF_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(undistort_to_host(rect, stream, uv, n, rect_cam(cam, raw ? cfg.scale : 1), out));
     return EKF_OK;
   }
   int set_patch(int index, const unsigned char* data) override {
@@ -3086,6 +3127,8 @@ struct Filter : FilterBase {
     k->device = device;
     k->img_w = cam.width;
     k->img_h = cam.height;
+    k->cam = cam;                                              // the lens model and scale its rectified getters use (§14)
+    k->scale = cfg.scale;
     const size_t px = (size_t)std::max(cam.width, 1) * std::max(cam.height, 1);
     HIPCHK(hipMalloc(&k->d_state, 2 * sizeof(KfState)));
     HIPCHK(hipMalloc(&k->d_rec, sizeof(KfRecord)));
@@ -3102,14 +3145,17 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
   // Point4sba (mono-slam vslamRansac.cpp:1319-1336) from the host's track state, as formats.point4sba_rows
-  void kf_point4sba(std::vector<int>& rows) const {
+  // uv: the float track centre behind every row (2 per row; none for the placeholder), for ekf_keyframe_get_emitted_rectified
+  void kf_point4sba(std::vector<int>& rows, std::vector<float>& uv) const {
     rows.assign(3, 0);
+    uv.clear();
     for (int i = 0; i < N; ++i) {
       if (!(in_innovation[i] && coding[i] == 1)) continue;
       const int r[3] = {real_index[i], (int)center[2 * i], (int)center[2 * i + 1]};
-      if (rows[0] == 0) std::copy(r, r + 3, rows.begin());
-      else if (r[1] < 640 && r[2] < 480) rows.insert(rows.end(), r, r + 3);
+      if (rows[0] == 0) { std::copy(r, r + 3, rows.begin()); uv.assign(&center[2 * i], &center[2 * i] + 2); }
+      else if (r[1] < 640 && r[2] < 480) { rows.insert(rows.end(), r, r + 3); uv.insert(uv.end(), &center[2 * i], &center[2 * i] + 2); }
     }
+    if (rows[0] == 0) uv.clear();
   }
   // One probe on the filter's stream, the image grid when a frame is set (a second one for the raw frame of a raw selector), ONE read-back (record, status words and -- only
   // when a predict / measure left them unread -- the track flags), then the host obeys the action word.
@@ -3148,19 +3194,20 @@ struct Filter : FilterBase {
     k->parity ^= 1;
     switch (r->action) {
       case kKfCandidate:
-        kf_point4sba(k->cand_rows);
+        kf_point4sba(k->cand_rows, k->cand_uv);
         k->cand_has_image = img;
         k->cand_has_raw = raw;
         break;
       case kKfEmitCandidate:
         k->emit_rows = k->cand_rows;
+        k->emit_uv = k->cand_uv;
         k->emit_has_image = img && k->cand_has_image;
         k->emit_has_raw = raw && k->cand_has_raw;
         break;
       case kKfEmitCurrent:
       case kKfEmitFirst:
-        if (k->keep_current) kf_point4sba(k->emit_rows);
-        else k->emit_rows.assign(3, 0);                      // the literal "0  0  0" (monoslam_ransac.cpp:640, :672)
+        if (k->keep_current) kf_point4sba(k->emit_rows, k->emit_uv);
+        else { k->emit_rows.assign(3, 0); k->emit_uv.clear(); }   // the literal "0  0  0" (monoslam_ransac.cpp:640, :672)
         k->emit_has_image = img;
         k->emit_has_raw = raw;
         break;
@@ -4842,6 +4889,15 @@ int ekf_set_frame_raw_device(ekf_filter* f, const void* d_pixels, int width, int
   return f->impl->set_frame_raw(d_pixels, width, height, channels, stride, true);
 }
 int ekf_get_frame(ekf_filter* f, unsigned char* gray, int stride) { IMPL_OR_ARG(f); return f->impl->get_frame(gray, stride); }
+int ekf_rectified_camera(const ekf_filter* f, int raw, ekf_sba_camera* K) { IMPL_OR_ARG(f); return f->impl->rectified_camera(raw, K); }
+int ekf_get_frame_rectified(ekf_filter* f, int raw, unsigned char* out, int stride) {
+  IMPL_OR_ARG(f);
+  return f->impl->get_frame_rectified(raw, out, stride);
+}
+int ekf_undistort_pixels(ekf_filter* f, int raw, const double* uv, int n, double* out) {
+  IMPL_OR_ARG(f);
+  return f->impl->undistort_pixels(raw, uv, n, out);
+}
 int ekf_set_patch(ekf_filter* f, int index, const unsigned char* pixels) { IMPL_OR_ARG(f); return f->impl->set_patch(index, pixels); }
 int ekf_get_patch(ekf_filter* f, int index, int matching, unsigned char* out) {
   IMPL_OR_ARG(f);
@@ -5373,6 +5429,59 @@ int ekf_keyframe_get_raw_image(const ekf_keyframe* s, unsigned char* pixels, int
   return EKF_OK;
 }
 
+// The rectified getters of a selector run on the default stream, as the copies of get_image / get_raw_image
+// do: the selector may outlive its filter, and observe has synchronised the launch that filled the emit slots.
+int ekf_keyframe_get_image_rectified(const ekf_keyframe* s, int raw, unsigned char* out, int stride) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  const int W = raw ? k->raw_w : k->img_w, H = raw ? k->raw_h : k->img_h, Cn = raw ? k->raw_c : 1;
+  if ((raw != 0 && raw != 1) || !out || (W > 0 && (long long)stride < (long long)W * Cn)) {
+    k->err = "ekf_keyframe_get_image_rectified: raw is 0 or 1, out must not be NULL and stride >= a row of that resolution";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit || !(raw ? k->emit_has_raw : k->emit_has_image) || (raw && k->scale < 1)) {
+    k->err = raw ? "ekf_keyframe_get_image_rectified: no emitted key frame with a raw image (ekf_keyframe_create_raw, and "
+                   "ekf_set_frame_raw before ekf_keyframe_observe)"
+                 : "ekf_keyframe_get_image_rectified: no emitted key frame with an image (ekf_set_frame before ekf_keyframe_observe)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = k->err;
+  HIPCHK(hipSetDevice(k->device));
+  HIPCHK(ekf::rectify_launch(k->rect, nullptr, raw ? k->d_emit_raw : k->d_emit, W, H, Cn, ekf::rect_cam(k->cam, raw ? k->scale : 1)));
+  HIPCHK(ekf::rectified_to_host(k->rect, nullptr, W, H, Cn, out, (size_t)stride));
+  return EKF_OK;
+}
+
+int ekf_keyframe_get_emitted_rectified(const ekf_keyframe* s, int raw, int max_rows, double* uv, int* rows) {
+  if (!s) return EKF_ERR_ARG;
+  auto* k = s->impl;
+  if ((raw != 0 && raw != 1) || max_rows < 0 || (max_rows > 0 && !uv)) {
+    k->err = "ekf_keyframe_get_emitted_rectified: raw is 0 or 1, max_rows >= 0, and uv with it";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit) {
+    k->err = "ekf_keyframe_get_emitted_rectified: no key frame was emitted yet";
+    return EKF_ERR_STATE;
+  }
+  if (raw && (k->raw_w <= 0 || k->scale < 1)) {
+    k->err = "ekf_keyframe_get_emitted_rectified: not a raw selector (ekf_keyframe_create_raw): the raw geometry is unknown";
+    return EKF_ERR_STATE;
+  }
+  const int total = (int)k->emit_uv.size() / 2;             // the "0 0 0" placeholder carries no coordinates: 0 rows
+  if (rows) *rows = total;
+  const int n = std::min(total, max_rows);
+  if (n == 0) return EKF_OK;
+  std::vector<double> in(k->emit_uv.begin(), k->emit_uv.begin() + 2 * (size_t)n);
+  if (raw) {                                                 // the track centres are matcher pixels: X = (u + 0.5) s - 0.5
+#pragma clang fp contract(off)
+    for (double& x : in) x = (x + 0.5) * (double)k->scale - 0.5;
+  }
+  std::string& err = k->err;
+  HIPCHK(hipSetDevice(k->device));
+  HIPCHK(ekf::undistort_to_host(k->rect, nullptr, in.data(), n, ekf::rect_cam(k->cam, raw ? k->scale : 1), uv));
+  return EKF_OK;
+}
+
 int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last_vrot3, float* min_cov, int* candidate_id) {
   if (!s) return EKF_ERR_ARG;
   auto* k = s->impl;
@@ -5396,6 +5505,8 @@ int ekf_keyframe_reset(ekf_keyframe* s) {
   HIPCHK(hipMemcpy(k->d_state + k->parity, &s0, sizeof(s0), hipMemcpyHostToDevice));
   k->cand_rows.clear();
   k->emit_rows.clear();
+  k->cand_uv.clear();
+  k->emit_uv.clear();
   k->cand_has_image = k->emit_has_image = k->have_emit = false;
   k->cand_has_raw = k->emit_has_raw = false;
   k->emitted = ekf::KfRecord{};

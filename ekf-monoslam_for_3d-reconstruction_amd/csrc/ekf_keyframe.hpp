@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "ekf_rectify.hpp"
+
 namespace ekf {
 
 // enum ekf_keyframe_action of include/ekf_monoslam.h
@@ -157,6 +159,12 @@ struct KfSelector {
   int raw_w = 0, raw_h = 0, raw_c = 0;
   bool cand_has_raw = false, emit_has_raw = false;
   std::vector<int> cand_rows, emit_rows;                // 3 ints per row
+  // rectified getters: the float track centre behind every row (2 per row, none for the "0 0 0" placeholder),
+  // the filter's lens model and scale as they were at create, and the scratch of the on-demand launches
+  std::vector<float> cand_uv, emit_uv;
+  CamParams cam{};
+  int scale = 1;
+  mutable RectScratch rect;
   KfRecord emitted{};
 
   static KfState initial() {
@@ -165,8 +173,9 @@ struct KfSelector {
     return s;
   }
   ~KfSelector() {
-    if (!d_state && !d_rec && !d_cand && !d_emit && !d_cand_raw && !d_emit_raw) return;
+    if (!d_state && !d_rec && !d_cand && !d_emit && !d_cand_raw && !d_emit_raw && !rect.d_img && !rect.d_pts) return;
     hipSetDevice(device);
+    rect.release();
     if (d_state) hipFree(d_state);
     if (d_rec) hipFree(d_rec);
     if (d_cand) hipFree(d_cand);

@@ -8,6 +8,7 @@ for the host side of the HIP path.  The node streams Eigen objects with the defa
                         projections (``Point4sba``, vR.cpp:1319-1336: real_index, u, v as ints) or
                         the literal ``0  0  0`` line
   cams_cov.txt          per kept pose: the 7x7 camera covariance block
+  camera.txt            (not the reference's; a rectifying recorder only) ``fx fy cx cy``
 
 Eigen's default format: coefficients written with the stream's precision (6 significant digits,
 ``%g`` style), right-aligned to the widest coefficient of the matrix, one space between columns,
@@ -140,6 +141,22 @@ def read_nodes_out(path_or_file):
         ids.append(int(lines[i][1:]))
         poses.append([float(lines[i + 1 + k]) for k in range(7)])
     return ids, np.array(poses, dtype=np.float64).reshape(-1, 7)
+
+
+def write_camera(path_or_file, K) -> None:
+    """camera.txt of a rectifying recorder (no reference counterpart): ``fx fy cx cy`` of the pinhole camera
+    that the record's images and projection rows belong to, one line, round-trip precision."""
+    k = np.asarray(K, dtype=np.float64).reshape(-1)
+    if k.size != 4:
+        raise ValueError("K = (fx, fy, cx, cy)")
+    _write(path_or_file, " ".join("%.17g" % v for v in k) + "\n")
+
+
+def read_camera(path_or_file):
+    vals = [float(t) for t in _read(path_or_file).split()]
+    if len(vals) != 4:
+        raise ValueError("camera.txt holds fx fy cx cy")
+    return tuple(vals)
 
 
 def point4sba_rows(real_index, in_innovation, coding, center) -> np.ndarray:

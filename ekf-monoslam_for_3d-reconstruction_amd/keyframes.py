@@ -126,6 +126,40 @@ class KeyframeSelector:
         self._check(self._lib.ekf_keyframe_get_raw_image(self._h, out.ctypes.data_as(C.c_void_p), out.strides[0]))
         return out
 
+    # ---- rectified for pinhole consumers ----
+    def rectified_camera(self, raw: bool = False) -> np.ndarray:
+        """(fx, fy, cx, cy) that ``emitted_image_rectified(raw)`` and ``emitted_rows_rectified(raw)`` belong to."""
+        return self._filter.rectifiedCamera(raw) if not raw else self._raw_camera()
+
+    def _raw_camera(self) -> np.ndarray:
+        if self.raw_shape is None:
+            raise EkfError(4, "not a raw selector (KeyframeSelector(..., raw_shape=...))")
+        cfg = self._filter._cfg
+        s = np.float64(int(cfg.scale))
+        fx, fy, u0, v0 = (np.float64(np.float32(v)) for v in (cfg.fx, cfg.fy, cfg.u0, cfg.v0))
+        return np.array([fx * s, fy * s, (u0 + 0.5) * s - 0.5, (v0 + 0.5) * s - 0.5], np.float64)
+
+    def emitted_image_rectified(self, raw: bool = False) -> np.ndarray:
+        """The last emitted key frame's image with the lens distortion removed, on the device from the kept copy: the
+        matcher's grey frame, or with ``raw`` the raw frame of a raw selector."""
+        if raw and self.raw_shape is None:
+            raise EkfError(4, "not a raw selector (KeyframeSelector(..., raw_shape=...))")
+        out = np.zeros(self.raw_shape if raw else self.image_shape, np.uint8)
+        self._check(self._lib.ekf_keyframe_get_image_rectified(self._h, 1 if raw else 0, out.ctypes.data_as(C.c_void_p),
+                                                               out.strides[0]))
+        return out
+
+    def emitted_rows_rectified(self, raw: bool = False) -> np.ndarray:
+        """(k, 2) float64: the undistorted track centres behind the rows of ``emitted().projections``, same order, in
+        matcher or (``raw``) raw pixels; k = 0 when the record carries the ``0 0 0`` placeholder."""
+        n = C.c_int(0)
+        self._check(self._lib.ekf_keyframe_get_emitted_rectified(self._h, 1 if raw else 0, 0, None, C.byref(n)))
+        uv = np.zeros((n.value, 2), np.float64)
+        if n.value:
+            self._check(self._lib.ekf_keyframe_get_emitted_rectified(self._h, 1 if raw else 0, n.value,
+                                                                     uv.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return uv[:n.value]
+
     def state(self) -> dict:
         pose, vrot = np.zeros(7, np.float32), np.zeros(3, np.float32)
         mc, cid = C.c_float(0), C.c_int(0)
@@ -158,12 +192,19 @@ def write_ppm(path: str, bgr) -> None:
 class KeyframeRecorder:
     """What the node writes around the selector: ``observe()`` per frame, ``finish()`` at the end.  With ``images`` a raw
     selector's key frames are written at raw size, as the node saves them: ``<id>.ppm`` (3 channels) or ``<id>.pgm`` (1);
-    a plain selector's as the matcher's grey frame, ``<id>.pgm``."""
+    a plain selector's as the matcher's grey frame, ``<id>.pgm``.
 
-    def __init__(self, selector: KeyframeSelector, directory: str, images: bool = False):
+    ``rectify=True`` records for a pinhole consumer: the images are the rectified ones (same names and
+    sizes), the projection rows are the undistorted track centres at the resolution of the images, rounded to the nearest
+    integer (``floor(x + 0.5)``, so the reference's ``int u, v`` reader still reads them), and ``camera.txt`` holds the
+    ``fx fy cx cy`` that both belong to.  The default writes what it always wrote, byte for byte."""
+
+    def __init__(self, selector: KeyframeSelector, directory: str, images: bool = False, rectify: bool = False):
         self.selector = selector
         self.directory = directory
         self.images = bool(images)
+        self.rectify = bool(rectify)
+        self.raw = getattr(selector, "raw_shape", None) is not None    # the resolution of the images and, rectified, of the rows
         os.makedirs(directory, exist_ok=True)
         self.nodes_path = os.path.join(directory, "nodes_and_prjcts.txt")
         self.covs_path = os.path.join(directory, "cams_cov.txt")
@@ -171,10 +212,15 @@ class KeyframeRecorder:
         open(self.nodes_path, "w").close()
         open(self.covs_path, "w").close()
         self.ids = []
+        if self.rectify:
+            self.camera_path = os.path.join(directory, "camera.txt")
+            formats.write_camera(self.camera_path, selector.rectified_camera(self.raw))
 
     def observe(self, frame_id: int) -> KeyframeResult:
         res = self.selector.observe(frame_id)
-        if res.emitted:
+        if res.emitted and self.rectify:
+            self._append_rectified(res.record)
+        elif res.emitted:
             self.append(res.record)
             if self.images and getattr(self.selector, "raw_shape", None) is not None:
                 raw = self.selector.emitted_raw_image()
@@ -185,6 +231,21 @@ class KeyframeRecorder:
             elif self.images:
                 write_pgm(os.path.join(self.directory, "%d.pgm" % res.record.id), self.selector.emitted_image())
         return res
+
+    def _append_rectified(self, record: KeyframeRecord) -> None:
+        prj = record.projections
+        uv = self.selector.emitted_rows_rectified(self.raw)
+        if len(uv):                                                   # same rows, same order: only the coordinates change
+            prj = prj.copy()
+            prj[:, 1:] = np.floor(uv + 0.5).astype(np.int64)
+        self.append(KeyframeRecord(record.id, record.pose, record.sigma, prj))
+        if not self.images:
+            return
+        img = self.selector.emitted_image_rectified(self.raw)
+        if img.ndim == 3 and img.shape[2] == 3:
+            write_ppm(os.path.join(self.directory, "%d.ppm" % record.id), img)
+        else:
+            write_pgm(os.path.join(self.directory, "%d.pgm" % record.id), img.reshape(img.shape[0], img.shape[1]))
 
     def append(self, record: KeyframeRecord) -> None:
         prj = record.projections

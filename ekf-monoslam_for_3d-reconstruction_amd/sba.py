@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 
 import numpy as np
 
@@ -259,6 +260,9 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
     system the single-workgroup triangular solve holds; more raise EkfError (EKF_ERR_ARG) when the handle is created.
     `solver="pcg"` has no such limit; `cg_tol` and `cg_max_iters` are doSBA's initTol and maxCGiters.
 
+    `camera` is (fx, fy, cx, cy) or the ``camera.txt`` a rectifying ``KeyframeRecorder`` wrote beside the three files
+    (DESIGN.md §14): its rows are undistorted, so the pinhole model of the adjuster fits them.
+
     `huber` (pixels) is set on the handle before the first run (SysSBA::huber; the reference driver leaves it 0).
     With `prune_dist` every call of the RMS wrapper is followed by remove_bad(prune_dist) and, if that removed
     anything, reduce_tracks() and one more run(10, 1e-4).  The reference driver has no such option (the library
@@ -268,6 +272,8 @@ def sba_add(points, nodes_and_prjcts, cams_cov=None, camera=REFERENCE_SBA_CAMERA
     stay zero), the refined nodes (x y z qw qx qy qz) and their ids.  Writes Points_Out.txt / Nodes_Out.txt when
     `points_out` / `nodes_out` are given.
     """
+    if isinstance(camera, (str, os.PathLike)) or hasattr(camera, "read"):
+        camera = formats.read_camera(camera)
     table = points if isinstance(points, np.ndarray) else formats.read_points(points)
     table = np.asarray(table, dtype=np.float32)
     records = nodes_and_prjcts if isinstance(nodes_and_prjcts, list) else formats.read_pose_records(nodes_and_prjcts)

@@ -70,6 +70,7 @@ class VSlamFilter:
             raise EkfError(rc, msg.decode() if msg else "ekf_create failed")
         self.camera_dim = camera_dim
         self._old_ts = -1.0
+        self._raw_shape = None                                       # of the raw frame the filter holds (setFrameRaw)
 
     # -- plumbing ---------------------------------------------------------------------------
     def close(self):
@@ -213,6 +214,7 @@ class VSlamFilter:
         if g.ndim != 2:
             raise ValueError("frame must be a single-channel 8-bit image")
         self._check(self._lib.ekf_set_frame(self._h, self._ptr(g), g.shape[1], g.shape[0], g.strides[0]))
+        self._raw_shape = None                                       # the library drops the raw frame
 
     def setFrameRaw(self, image):
         """The camera's frame before resize / grayscale: a uint8 array (H, W) or (H, W, 3) in B, G, R order (rows may be
@@ -232,6 +234,7 @@ class VSlamFilter:
                     raise ValueError("raw frame tensor must have contiguous pixels (only the rows may be strided)")
                 self._check(self._lib.ekf_set_frame_raw_device(self._h, C.c_void_p(t.data_ptr()), int(t.shape[1]),
                                                                int(t.shape[0]), ch, int(st[0])))
+                self._raw_shape = tuple(int(v) for v in t.shape)
                 return
         a = np.asarray(image)
         if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
@@ -240,11 +243,40 @@ class VSlamFilter:
         if (a.ndim == 3 and a.strides[2] != 1) or a.strides[1] != ch or a.strides[0] < a.shape[1] * ch:
             a = np.ascontiguousarray(a)
         self._check(self._lib.ekf_set_frame_raw(self._h, self._ptr(a), a.shape[1], a.shape[0], ch, a.strides[0]))
+        self._raw_shape = tuple(int(v) for v in a.shape)
 
     def getFrame(self):
         """The matcher frame as the device consumers see it: uint8 (image_height, image_width)."""
         out = np.zeros((int(self._cfg.image_height), int(self._cfg.image_width)), np.uint8)
         self._check(self._lib.ekf_get_frame(self._h, self._ptr(out), out.strides[0]))
+        return out
+
+    # ---- rectification for pinhole consumers (DESIGN.md §14) ---------------------------------------
+    def rectifiedCamera(self, raw: bool = False):
+        """(fx, fy, cx, cy) of the pinhole camera that the rectified images and pixels of one resolution belong to:
+        the matcher frame, or with ``raw`` the raw frame (known once ``setFrameRaw`` was called)."""
+        K = capi.EkfSbaCamera()
+        self._check(self._lib.ekf_rectified_camera(self._h, 1 if raw else 0, C.byref(K)))
+        return np.array([K.fx, K.fy, K.cx, K.cy], np.float64)
+
+    def getFrameRectified(self, raw: bool = False):
+        """The held frame with the lens distortion removed on the device: uint8 (image_height, image_width), or with
+        ``raw`` the shape of the raw frame given to ``setFrameRaw``.  A position the lens never imaged is 0."""
+        if raw:
+            if self._raw_shape is None:
+                raise EkfError(4, "getFrameRectified(raw=True): no raw frame is held (setFrameRaw)")
+            out = np.zeros(self._raw_shape, np.uint8)
+        else:
+            out = np.zeros((int(self._cfg.image_height), int(self._cfg.image_width)), np.uint8)
+        self._check(self._lib.ekf_get_frame_rectified(self._h, 1 if raw else 0, self._ptr(out), out.strides[0]))
+        return out
+
+    def undistortPixels(self, uv, raw: bool = False):
+        """(n, 2) pixels of the distorted image -> (n, 2) float64 pixels of the rectified one, same resolution (device
+        arithmetic in fp64: the filter's own 50-iteration camera model).  A non-finite row gives NaN."""
+        a = np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2))
+        out = np.zeros_like(a)
+        self._check(self._lib.ekf_undistort_pixels(self._h, 1 if raw else 0, self._ptr(a), a.shape[0], self._ptr(out)))
         return out
 
     def setPatch(self, index: int, pixels):

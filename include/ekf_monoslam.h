@@ -706,6 +706,39 @@ int ekf_keyframe_get_raw_image(const ekf_keyframe* s, unsigned char* pixels, int
 int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last_vrot3, float* min_cov, int* candidate_id);
 int ekf_keyframe_reset(ekf_keyframe* s);
 
+/* ---- rectification for pinhole consumers ------------------------------------------------------
+ * The filter models lens distortion (k1 k2 k3 p1 p2 of ekf_config); ekf_sba_* and any dense step are pinhole.  These
+ * entry points deliver, on demand, images, pixel coordinates and ONE pinhole K that agree.  The reference has no
+ * counterpart (its key frames and Point4sba rows stay distorted).  Nothing here runs per frame, changes the filter or
+ * counts as a launch kind; ekf_abi_version() stays 6 (additions only).
+ *  - `raw` selects the resolution: 0 = the matcher frame (image_width x image_height, factor s = 1), 1 = the raw frame
+ *    of ekf_set_frame_raw / ekf_keyframe_create_raw (width x height x channels, s = ekf_config.scale).  Matcher pixel u
+ *    and raw pixel X: u = (X + 0.5) / s - 0.5.  Any other value is EKF_ERR_ARG;
+ *  - ekf_rectified_camera: K(raw = 0) = (fx, fy, u0, v0) of the config; K(raw = 1) = (fx s, fy s, (u0 + 0.5) s - 0.5,
+ *    (v0 + 0.5) s - 0.5).  raw = 1 before any raw frame was set is EKF_ERR_STATE (the raw geometry is unknown);
+ *  - ekf_get_frame_rectified: the frame the filter holds, undistorted by ONE launch on the filter's stream (fp64 map,
+ *    5-bit bilinear weights, a source position outside the image gives 0: DESIGN.md §14 pins every operation), rows of
+ *    width * channels bytes, `stride` bytes apart.  EKF_ERR_STATE without a frame, or for raw = 1 without a raw frame
+ *    (a later ekf_set_frame drops it);
+ *  - ekf_undistort_pixels: n pixels (u, v) of resolution `raw` (host, 2 doubles each) -> where the pinhole K of that
+ *    resolution sees the same ray: the 50 fixed-point iterations of the filter's own camera model, in fp64 on the
+ *    device.  A non-finite input gives NaN, NaN.  n = 0 is a no-op; raw = 1 as for ekf_rectified_camera;
+ *  - ekf_keyframe_get_image_rectified: the last emitted key frame's image (raw = 0) or raw image (raw = 1), rectified
+ *    on the device from the emit slot.  EKF_ERR_STATE whenever ekf_keyframe_get_image / ekf_keyframe_get_raw_image
+ *    refuse;
+ *  - ekf_keyframe_get_emitted_rectified: the rows of ekf_keyframe_get_emitted, same selection and order, as the
+ *    undistorted FLOAT track centres (not the truncated ints) in resolution `raw`: 2 doubles per row.  *rows = their
+ *    number (at most max_rows are written); the "0 0 0" placeholder row is zero rows of coordinates.  EKF_ERR_STATE
+ *    before the first emit, and for raw = 1 on a selector that is not a raw one.
+ * The selector's two getters use the lens model and scale its filter had at create and run on the default stream (the
+ * selector may outlive the filter).  A sharded filter is allowed everywhere: every rank holds the frame, there is no
+ * collective.  Argument errors are EKF_ERR_ARG before the device is touched. */
+int ekf_rectified_camera(const ekf_filter* f, int raw, ekf_sba_camera* K);
+int ekf_get_frame_rectified(ekf_filter* f, int raw, unsigned char* out, int stride);
+int ekf_undistort_pixels(ekf_filter* f, int raw, const double* uv, int n, double* out);
+int ekf_keyframe_get_image_rectified(const ekf_keyframe* s, int raw, unsigned char* out, int stride);
+int ekf_keyframe_get_emitted_rectified(const ekf_keyframe* s, int raw, int max_rows, double* uv, int* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,25 @@ class VSlamFilterHip {
     check(ekf_get_frame(h_, g.data(), width));
     return g;
   }
+  // ---- rectification for pinhole consumers: raw = false the matcher frame, true the raw frame ----
+  // K = (fx, fy, cx, cy) of the pinhole camera that the rectified images and pixels of that resolution belong to
+  ekf_sba_camera rectifiedCamera(bool raw = false) {
+    ekf_sba_camera K = {0, 0, 0, 0};
+    check(ekf_rectified_camera(h_, raw ? 1 : 0, &K));
+    return K;
+  }
+  // the held frame with the lens distortion removed on the device: height rows of width * channels bytes
+  std::vector<unsigned char> getFrameRectified(int width, int height, int channels = 1, bool raw = false) {
+    std::vector<unsigned char> g((size_t)width * height * channels);
+    check(ekf_get_frame_rectified(h_, raw ? 1 : 0, g.data(), width * channels));
+    return g;
+  }
+  // pixels (u, v) of the distorted image -> pixels of the rectified one, same resolution; 2 doubles per point
+  std::vector<double> undistortPixels(const std::vector<double>& uv, bool raw = false) {
+    std::vector<double> out(uv.size());
+    check(ekf_undistort_pixels(h_, raw ? 1 : 0, uv.data(), (int)(uv.size() / 2), out.data()));
+    return out;
+  }
   double getDt() const { return ekf_get_dt(h_); }
 
   int addFeature(float u, float v) { return count(ekf_add_feature(h_, u, v)); }   // cv::Point2f pf
@@ -399,6 +418,22 @@ class KeyframeSelectorHip {
     std::vector<unsigned char> p((size_t)raw_width * raw_height * channels);
     check(ekf_keyframe_get_raw_image(h_, p.data(), raw_width * channels));
     return p;
+  }
+  // the emitted key frame's image with the lens distortion removed: the grey frame, or with `raw`
+  // the raw frame of a raw selector; height rows of width * channels bytes
+  std::vector<unsigned char> emittedImageRectified(int width, int height, int channels = 1, bool raw = false) {
+    std::vector<unsigned char> g((size_t)width * height * channels);
+    check(ekf_keyframe_get_image_rectified(h_, raw ? 1 : 0, g.data(), width * channels));
+    return g;
+  }
+  // the undistorted track centres behind the rows of emitted().projections, same order, 2 doubles per row (none for the
+  // 0 0 0 placeholder), in matcher or (`raw`) raw pixels
+  std::vector<double> emittedRowsRectified(bool raw = false) {
+    int n = 0;
+    check(ekf_keyframe_get_emitted_rectified(h_, raw ? 1 : 0, 0, nullptr, &n));
+    std::vector<double> uv(2 * (size_t)n);
+    if (n) check(ekf_keyframe_get_emitted_rectified(h_, raw ? 1 : 0, n, uv.data(), &n));
+    return uv;
   }
   void state(float last_pose[7], float last_vrot[3], float* min_cov, int* candidate_id) {
     check(ekf_keyframe_get_state(h_, last_pose, last_vrot, min_cov, candidate_id));
