@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ekf_monoslam.h"
+#include "ekf_buffers.hpp"
 #include "ekf_dense.hpp"
 #include "ekf_image.hpp"
 #include "ekf_features.hpp"
@@ -237,44 +238,40 @@ struct Filter : FilterBase {
   std::vector<int> n_tot;
   std::vector<float> center;                            // u, v per feature
   std::vector<unsigned char> in_innovation, remove_flag;
-  unsigned char* d_trk = nullptr;
+  DevBuf<unsigned char> d_trk;
   bool trk_dirty = false;
   // corner seeding (ekf_features.hpp): mask, lambda, [max bits | candidate count], candidates, square origins, selection
-  unsigned char* d_seed_mask = nullptr;
-  double* d_seed_lam = nullptr;
-  unsigned long long* d_seed_aux = nullptr;
-  unsigned long long* d_seed_ckey = nullptr;
-  int *d_seed_cidx = nullptr, *d_seed_org = nullptr, *d_seed_out = nullptr;
+  DevBuf<unsigned char> d_seed_mask;
+  DevBuf<double> d_seed_lam;
+  DevBuf<unsigned long long> d_seed_aux, d_seed_ckey;
+  DevBuf<int> d_seed_cidx, d_seed_org, d_seed_out;
   bool have_seed_lam = false;
   std::vector<int> arch_real;
-  T* d_archive = nullptr;
-  size_t arch_cap = 0;
-  int* d_arch_idx = nullptr;
-  size_t arch_idx_cap = 0;
+  DevBuf<T> d_archive;                                  // 12 scalars per archived patch
+  DevBuf<int> d_arch_idx;
   bool layout_dirty = true;
-  int *d_pos = nullptr, *d_coding = nullptr;
-  T* d_mu[2] = {nullptr, nullptr};
+  DevBuf<int> d_pos, d_coding;
+  DevBuf<T> d_mu[2];
   int cur_mu = 0;
-  T* d_S[2] = {nullptr, nullptr};
+  DevBuf<T> d_S[2];
   int cur = 0;
   int extent[2] = {0, 0};                              // largest n ever written per Sigma buffer
-  T* d_scr = nullptr;
-  T *d_h = nullptr, *d_Hc = nullptr, *d_Hf = nullptr, *d_Sd = nullptr;
-  unsigned char *d_flags = nullptr, *d_cflag = nullptr;
-  T *d_Jy = nullptr, *d_Yxyz = nullptr;
-  int *d_map_src = nullptr, *d_map_conv = nullptr;
+  DevBuf<T> d_scr;
+  DevBuf<T> d_h, d_Hc, d_Hf, d_Sd;
+  DevBuf<unsigned char> d_flags, d_cflag;
+  DevBuf<T> d_Jy, d_Yxyz;
+  DevBuf<int> d_map_src, d_map_conv;
   // update workspace
   int m_cap = 0, ldy = 0, w_rows = 0;
-  T* d_Y = nullptr;                                     // [S; Z], 2 ldy rows
-  T* d_W = nullptr;                                     // [W; nu block], n_pad + 128 rows
-  T* d_V = nullptr;                                     // [V; y block]
-  T* d_Dinv = nullptr;
-  T* d_z = nullptr;
-  int* d_midx = nullptr;
-  int* d_status = nullptr;
-  T* d_tmp = nullptr;                                   // small D2H staging (>= 16 T)
-  T* d_K = nullptr;                                     // lazily allocated gain buffer
-  size_t K_elems = 0;
+  DevBuf<T> d_Y;                                        // [S; Z], 2 ldy rows
+  DevBuf<T> d_W;                                        // [W; nu block], n_pad + 128 rows
+  DevBuf<T> d_V;                                        // [V; y block]
+  DevBuf<T> d_Dinv;
+  DevBuf<T> d_z;
+  DevBuf<int> d_midx;
+  DevBuf<int> d_status;
+  DevBuf<T> d_tmp;                                      // small D2H staging (>= 16 T)
+  DevBuf<T> d_K;                                        // lazily allocated gain buffer
   int last_m = 0, last_m_pad = 0, last_n = 0;
   bool have_meas = false;
   bool have_sd = false;                                  // 2x2 St blocks of the current h/H evaluated?
@@ -297,29 +294,27 @@ struct Filter : FilterBase {
   int opt_split_tail = -1;
   double opt_feature_noise = 0.0;                       // EKF_OPT_FEATURE_NOISE: variance added to every feature state per predict
   int opt_split_bf16 = 1;                               // EKF_OPT_SPLIT_BF16 (default on, round 5): downdate of large maps on the bf16 matrix pipe, 3 x bf16 per operand, six products (ekf_syrk6.hpp)
-  s6_u32x4* d_Vimg = nullptr;                           // plane image of V: (n_pad + 128) / 128 row blocks x ldy / 16 records of 12 KB
+  DevBuf<s6_u32x4> d_Vimg;                              // plane image of V: (n_pad + 128) / 128 row blocks x ldy / 16 records of 12 KB
+  // (six bf16 planes of 2 bytes per element of V = 6 * ldy / 8 records of 16 bytes per row; allocated at the first bf16x6 downdate)
+  hipError_t ensure_vimg() { return d_Vimg.reserve((size_t)(n_pad + 128) * ldy * 6 / sizeof(s6_u32x4)); }
   int last_nchunks = 1, last_cend[8] = {};
   // image side (8f4): current frame, templates (original / matching), blur-pose predictions, match results
-  unsigned char* d_frame = nullptr;
-  size_t frame_cap = 0;
+  DevBuf<unsigned char> d_frame;
   int frame_w = 0, frame_h = 0;
   bool have_frame = false, have_blur = false;
   // the camera's own frame: W x H x C bytes, tight, + kIngestSlack; d_frame is derived from it on the device
-  unsigned char* d_raw = nullptr;
-  size_t raw_cap = 0;
+  DevBuf<unsigned char> d_raw;
   int raw_w = 0, raw_h = 0, raw_c = 0;
   bool have_raw = false;
   RectScratch rect;                                     // on-demand rectification: never touched per frame
-  int4* d_ingest_tab = nullptr;                         // column records, then row records (ingest_tables)
-  size_t ingest_tab_cap = 0;
+  DevBuf<int4> d_ingest_tab;                            // column records, then row records (ingest_tables)
   int ingest_tab_w = 0, ingest_tab_h = 0;               // the raw geometry the resident tables were computed for
-  unsigned char *d_patch[2] = {nullptr, nullptr}, *d_mpatch[2] = {nullptr, nullptr};
+  DevBuf<unsigned char> d_patch[2], d_mpatch[2];
   int cur_patch = 0;
-  T* d_hb = nullptr;
-  T* d_zm = nullptr;
-  unsigned char* d_found = nullptr;
-  float* d_score = nullptr;
-  int* d_keep = nullptr;
+  DevBuf<T> d_hb, d_zm;
+  DevBuf<unsigned char> d_found;
+  DevBuf<float> d_score;
+  DevBuf<int> d_keep;
   int opt_panel_direct = 1;                             // EKF_PANEL_DIRECT=0: panel through the general tile GEMM
   // the trailing update of step j and the diagonal factor of step j + 1 as ONE launch (k_trail_diag, ekf_chain.hpp);
   // EKF_CHAIN_FUSED_DIAG=0: diag -> panel -> trailing, three launches per block step (rounds 1-5; A/B and bit-identity check)
@@ -330,9 +325,9 @@ struct Filter : FilterBase {
   // a block step of the chain (factor, panel, trailing update) as ONE launch where the step has fewer workgroups than the chip has
   // CUs and the chain runs alone (one column chunk: N up to ~230; k_chain_step_fused, ekf_step.hpp); EKF_STEP_FUSED=0: three launches
   int opt_step_fused = 1;
-  struct StepPlan { int nblk = 0, s1 = 0; std::vector<int> off, cnt; } sfp;
-  int* d_sf_lists = nullptr;
-  unsigned long long* d_small_stamps = nullptr;         // EKF_SMALL_STAMPS=1: phase stamps of its workgroup 0 (ekf_peek_workspace, which = 3)
+  struct StepPlan { std::vector<int> off, cnt; } sfp;   // per block step of the plan sf_lists was built for (sf_lists.first() steps)
+  WorkList sf_lists{{0}, {}};                           // key (nblk); as the parent: a plan of no steps needs no list
+  DevBuf<unsigned long long> d_small_stamps;            // EKF_SMALL_STAMPS=1: phase stamps of its workgroup 0 (ekf_peek_workspace, which = 3)
   unsigned small_gate_total = 0;                        // arrivals the gate word (d_status[9]) has seen when every launch so far is over
   int opt_su_tail = 1;                                  // EKF_SU_TAIL=0: k_state_update as its own launch on the second stream beside the last downdate (round 5)
   // EKF_SYRK_MIRROR_SKIP=0: every k_syrk_bf16x6 launch stores every mirror (rounds 5-6; A/B and bit-identity check).  1: launches
@@ -342,9 +337,8 @@ struct Filter : FilterBase {
   int opt_chain_defer = 1;                              // EKF_CHAIN_DEFER=0: a chunk's event behind the trailing update of its last step (rounds 1-5)
   int td_min_blocks = 24;                               // EKF_TD_MIN_BLOCKS: steps with fewer blocks in their update keep the three launches
   int td_max_blocks = 1 << 30;                          // EKF_TD_MAX_BLOCKS: ... and so do steps with more (many rounds of blocks: the 64 x 64 tile kernel's occupancy wins)
-  int* d_td_blocks = nullptr;
-  std::vector<int> td_off, td_cnt;                      // per block step: its list of (I, K) blocks inside d_td_blocks
-  int td_nblk = 0, td_nchunks = 0, td_cend[8] = {};
+  WorkList td_blocks;                                   // key (nblk, nchunks, chunk ends)
+  std::vector<int> td_off, td_cnt;                      // per block step: its list of (I, K) blocks inside td_blocks.d
   // EKF_SYRK_STAGGER="h,m": de-phasing of the bf16x6 downdate's workgroups (Syrk6Args).  Round 6, N = 1000, knob A/B: every
   // (0, m) with m = 1 .. 6 measures 0.897-0.903 ms per step against 0.917-0.922 without; a late second half (h > 0) gains nothing
   int opt_syrk_stag_half = 0, opt_syrk_stag_mod4 = 2;
@@ -362,10 +356,10 @@ struct Filter : FilterBase {
   int opt_fuse_wu = 1;                                  // EKF_FUSE_WU: 0 never, 1 every overlapped chunk but the one before the last, 2 every overlapped chunk
   int env_chunks[8] = {}, env_nchunks = 0;               // EKF_CHUNKS="5,10,14,16": tuning knob (block steps)
   int opt_pipeline = -1;                                 // -1 auto: on when the chain has >= 8 block steps
-  int* d_tilemap = nullptr;                             // work lists: [lower-tri super-tiles | solve heavy-first]
-  int tilemap_nt = 0, tilemap_ntc = 0, tri_count = 0, solve_off = 0;
+  WorkList tilemap{{0, 0}, {}};                         // work lists: [lower-tri super-tiles | solve heavy-first], key (nt, ntc)
+  int tri_count = 0, solve_off = 0;
   int w_zeroed_n = -1;                                   // n for which the pad rows of W were last cleared
-  int* d_counters = nullptr;                            // one work-queue head per queued launch of an update
+  DevBuf<int> d_counters;                               // one work-queue head per queued launch of an update
   int num_cus = 256, reserved_cus = 32;
   // profiling
   struct Pending { int kid; hipEvent_t a, b; };
@@ -380,6 +374,9 @@ struct Filter : FilterBase {
   static constexpr bool kIsF32 = sizeof(T) == 4;
   int NB() const { return (kIsF32 && opt_mfma) ? 128 : 64; }
 
+  // What is about ordering is spelled out here: the streams are drained, then events and streams go.  The device and pinned
+  // buffers are members (DevBuf / PinnedBuf) and are released after this body, i.e. after the streams are gone -- sound, because
+  // every stream that could touch them was synchronised first (the device set here stays current for those frees).
   ~Filter() override {
     const bool dbg = getenv("EKF_DEBUG_DTOR") != nullptr;       // (diagnostics: which call of the tear-down a stall sits in)
     auto mark = [&](const char* what) { if (dbg) { fprintf(stderr, "[ekf dtor %p] %s\n", (void*)this, what); fflush(stderr); } };
@@ -392,23 +389,7 @@ struct Filter : FilterBase {
     mark("events");
     for (auto& p : pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : pool) hipEventDestroy(e);
-    mark("device memory");
-    void* ptrs[] = {d_pos, d_coding, d_mu[0], d_mu[1], d_S[0], d_S[1], d_scr, d_h, d_Hc, d_Hf, d_Sd,
-                    d_flags, d_cflag, d_Jy, d_Yxyz, d_map_src, d_map_conv, d_Y, d_W, d_V, d_Dinv, d_z, d_midx,
-                    d_status, d_tmp, d_K, d_tilemap, d_counters, d_ibuf, d_rmask, d_pts, d_tab,
-                    d_frame, d_raw, d_ingest_tab, d_patch[0], d_patch[1], d_mpatch[0], d_mpatch[1], d_hb, d_zm, d_found, d_score, d_keep,
-                    d_Vimg, d_stage_send, d_stage_recv, d_archive, d_arch_idx, d_panel_tiles, d_shard_solve, d_shard_syrk,
-                    d_td_blocks, d_small_stamps,
-                    d_dist_lists, d_dist_counters, d_dist_send, d_dist_recv, d_sf_lists,
-                    d_trk, d_seed_mask, d_seed_lam, d_seed_aux, d_seed_ckey, d_seed_cidx, d_seed_org, d_seed_out};
-    for (void* p : ptrs) if (p) hipFree(p);
-    rect.release();
-    mark("host memory");
-    for (int s = 0; s < kInSlots; ++s) { if (h_in[s]) hipHostFree(h_in[s]); if (ev_in[s]) hipEventDestroy(ev_in[s]); }
-    if (h_pred) hipHostFree(h_pred);
-    if (h_ransac) hipHostFree(h_ransac);
-    if (h_gate) hipHostFree(h_gate);
-    if (h_rb) hipHostFree(h_rb);
+    for (auto e : ev_in) if (e) hipEventDestroy(e);
     mark("streams");
     if (own_stream && stream) hipStreamDestroy(stream);
     mark("stream b");
@@ -497,44 +478,44 @@ struct Filter : FilterBase {
     HIPCHK(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&ev_wu, hipEventDisableTiming));
     const size_t sig = (size_t)n_pad * ld;
-    HIPCHK(hipMalloc(&d_S[0], sig * sizeof(T)));
-    HIPCHK(hipMalloc(&d_S[1], sig * sizeof(T)));
+    HIPCHK(d_S[0].reserve(sig));
+    HIPCHK(d_S[1].reserve(sig));
     HIPCHK(hipMemsetAsync(d_S[0], 0, sig * sizeof(T), stream));
     HIPCHK(hipMemsetAsync(d_S[1], 0, sig * sizeof(T), stream));
-    HIPCHK(hipMalloc(&d_mu[0], (size_t)n_pad * sizeof(T)));
-    HIPCHK(hipMalloc(&d_mu[1], (size_t)n_pad * sizeof(T)));
+    HIPCHK(d_mu[0].reserve((size_t)n_pad));
+    HIPCHK(d_mu[1].reserve((size_t)n_pad));
     HIPCHK(hipMemsetAsync(d_mu[0], 0, (size_t)n_pad * sizeof(T), stream));
     HIPCHK(hipMemsetAsync(d_mu[1], 0, (size_t)n_pad * sizeof(T), stream));
-    HIPCHK(hipMalloc(&d_scr, SCR_SIZE * sizeof(T)));
+    HIPCHK(d_scr.reserve(SCR_SIZE));
     const size_t cn = (size_t)std::max(capN, 1);
-    HIPCHK(hipMalloc(&d_pos, cn * sizeof(int)));
-    HIPCHK(hipMalloc(&d_coding, cn * sizeof(int)));
-    HIPCHK(hipMalloc(&d_h, cn * 2 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_Hc, cn * 14 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_Hf, cn * 12 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_Sd, cn * 4 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_flags, cn));
-    HIPCHK(hipMalloc(&d_cflag, cn));
-    HIPCHK(hipMalloc(&d_trk, cn));
+    HIPCHK(d_pos.reserve(cn));
+    HIPCHK(d_coding.reserve(cn));
+    HIPCHK(d_h.reserve(cn * 2));
+    HIPCHK(d_Hc.reserve(cn * 14));
+    HIPCHK(d_Hf.reserve(cn * 12));
+    HIPCHK(d_Sd.reserve(cn * 4));
+    HIPCHK(d_flags.reserve(cn));
+    HIPCHK(d_cflag.reserve(cn));
+    HIPCHK(d_trk.reserve(cn));
     HIPCHK(hipMemsetAsync(d_trk, 0, cn, stream));
-    HIPCHK(hipMalloc(&d_Jy, cn * 18 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_Yxyz, cn * 3 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_map_src, (size_t)n_pad * sizeof(int)));
-    HIPCHK(hipMalloc(&d_map_conv, (size_t)n_pad * sizeof(int)));
-    HIPCHK(hipMalloc(&d_Y, (size_t)2 * ldy * ldy * sizeof(T)));
+    HIPCHK(d_Jy.reserve(cn * 18));
+    HIPCHK(d_Yxyz.reserve(cn * 3));
+    HIPCHK(d_map_src.reserve((size_t)n_pad));
+    HIPCHK(d_map_conv.reserve((size_t)n_pad));
+    HIPCHK(d_Y.reserve((size_t)2 * ldy * ldy));
     HIPCHK(hipMemsetAsync(d_Y, 0, (size_t)2 * ldy * ldy * sizeof(T), stream));
-    HIPCHK(hipMalloc(&d_W, (size_t)w_rows * ldy * sizeof(T)));
+    HIPCHK(d_W.reserve((size_t)w_rows * ldy));
     HIPCHK(hipMemsetAsync(d_W, 0, (size_t)w_rows * ldy * sizeof(T), stream));
-    HIPCHK(hipMalloc(&d_V, (size_t)w_rows * ldy * sizeof(T)));
+    HIPCHK(d_V.reserve((size_t)w_rows * ldy));
     HIPCHK(hipMemsetAsync(d_V, 0, (size_t)w_rows * ldy * sizeof(T), stream));
-    HIPCHK(hipMalloc(&d_Dinv, (size_t)(ldy / 64) * 128 * 128 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_z, (size_t)ldy * sizeof(T)));
-    HIPCHK(hipMalloc(&d_midx, cn * sizeof(int)));
-    HIPCHK(hipMalloc(&d_status, 16 * sizeof(int)));         // [0] pivot <= 0, [1] bad device index list, [3] a bounded device-side wait gave up; [4..7] scratch of ekf_check_invariants; [8] arrival gate of k_predict_fused, [9] of k_update_small_onelaunch
+    HIPCHK(d_Dinv.reserve((size_t)(ldy / 64) * 128 * 128));
+    HIPCHK(d_z.reserve((size_t)ldy));
+    HIPCHK(d_midx.reserve(cn));
+    HIPCHK(d_status.reserve(16));         // [0] pivot <= 0, [1] bad device index list, [3] a bounded device-side wait gave up; [4..7] scratch of ekf_check_invariants; [8] arrival gate of k_predict_fused, [9] of k_update_small_onelaunch
     HIPCHK(hipMemsetAsync(d_status, 0, 16 * sizeof(int), stream));
-    HIPCHK(hipMalloc(&d_tmp, 64 * sizeof(T)));
+    HIPCHK(d_tmp.reserve(64));
     // (behind the queue heads: the row bounds of the mirror rule, written by the first launch of every update)
-    HIPCHK(hipMalloc(&d_counters, (kQueueCounters + kMirrorRowsInts) * sizeof(int)));
+    HIPCHK(d_counters.reserve(kQueueCounters + kMirrorRowsInts));
     HIPCHK(hipMemset(d_counters, 0, (kQueueCounters + kMirrorRowsInts) * sizeof(int)));
     {
       hipDeviceProp_t prop;
@@ -584,7 +565,7 @@ struct Filter : FilterBase {
       if (const char* e = getenv("EKF_SHARD_DIST_CHAIN")) opt_shard_dist_chain = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SHARD_DIST_MIN_BLOCKS")) shard_dist_min_blocks = std::max(2, atoi(e));
       if (const char* e = getenv("EKF_SMALL_STAMPS")) {
-        if (atoi(e)) { HIPCHK(hipMalloc(&d_small_stamps, 16 * sizeof(unsigned long long))); HIPCHK(hipMemset(d_small_stamps, 0, 16 * sizeof(unsigned long long))); }
+        if (atoi(e)) { HIPCHK(d_small_stamps.reserve(16)); HIPCHK(hipMemset(d_small_stamps, 0, 16 * sizeof(unsigned long long))); }
       }
       if (const char* e = getenv("EKF_CHAIN_DEFER")) opt_chain_defer = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_TD_MIN_BLOCKS")) td_min_blocks = std::max(1, atoi(e));
@@ -643,28 +624,28 @@ struct Filter : FilterBase {
 
   // z (2 M scalars) and the index list (M ints) of a host caller -> d_z / d_midx through pinned slot `in_slot`
   static constexpr int kInSlots = 4;
-  void* h_in[kInSlots] = {nullptr, nullptr, nullptr, nullptr};
+  PinnedBuf<char> h_in[kInSlots];
   hipEvent_t ev_in[kInSlots] = {nullptr, nullptr, nullptr, nullptr};
   bool in_used[kInSlots] = {false, false, false, false};
   int in_slot = 0;
-  void* h_pred = nullptr;                               // host-mapped read-back buffer of ekf_get_predictions
-  void* h_ransac = nullptr;                             // ... of ekf_ransac_1point: counts, camera pose, small inlier masks
+  PinnedBuf<char> h_pred;                               // host-mapped read-back buffer of ekf_get_predictions
+  PinnedBuf<unsigned char> h_ransac;                    // ... of ekf_ransac_1point: counts, camera pose, small inlier masks
   static constexpr size_t kRansacMaskBytes = 65536;
   const unsigned char* ransac_mask_host = nullptr;      // the mask of the last ransac() call, if it came back with the counts
   int ransac_mask_M = 0;
   double ransac_cam[7] = {0, 0, 0, 0, 0, 0, 0};
   bool ransac_cam_valid = false;
-  void* h_gate = nullptr;                               // host-mapped gate flags of ekf_rescue_high_innovation
+  PinnedBuf<unsigned char> h_gate;                      // host-mapped gate flags of ekf_rescue_high_innovation
   int stage_inputs(const void* z, const int* idx, int M, const void* cam7 = nullptr) {
     const size_t zb = (size_t)2 * M * sizeof(T), ib = (size_t)M * sizeof(int);
     const int s = in_slot;
     in_slot = (in_slot + 1) % kInSlots;
     if (!h_in[s]) {
-      HIPCHK(hipHostMalloc(&h_in[s], (size_t)capN * (2 * sizeof(T) + sizeof(int)) + 8 * sizeof(T) + 64, hipHostMallocDefault));
+      HIPCHK(h_in[s].reserve((size_t)capN * (2 * sizeof(T) + sizeof(int)) + 8 * sizeof(T) + 64));
       HIPCHK(hipEventCreateWithFlags(&ev_in[s], hipEventDisableTiming));
     }
     if (in_used[s]) HIPCHK(hipEventSynchronize(ev_in[s]));      // the copies that last used this slot are long done
-    char* base = static_cast<char*>(h_in[s]);
+    char* base = h_in[s];
     memcpy(base, z, zb);
     memcpy(base + (size_t)2 * capN * sizeof(T), idx, ib);
     HIPCHK(hipMemcpyAsync(d_z, base, zb, hipMemcpyHostToDevice, stream));
@@ -682,12 +663,12 @@ struct Filter : FilterBase {
   // Small device -> host reads of the getters: through ONE pinned bounce buffer, several pieces and the status words per
   // synchronisation (a copy into pageable memory is staged by the runtime and costs ~25 us; every getter used to pay that
   // twice, once for its data and once for the status words).
-  void* h_rb = nullptr;
-  size_t rb_cap = 0, rb_off = 0;
+  PinnedBuf<char> h_rb;
+  size_t rb_off = 0;
   struct RbPiece { void* dst; size_t off, bytes; };
   std::vector<RbPiece> rb_pend;
   int rb_reserve(size_t bytes) {
-    if (rb_off + bytes + 64 <= rb_cap) return EKF_OK;
+    if (rb_off + bytes + 64 <= h_rb.capacity()) return EKF_OK;
     if (!rb_pend.empty()) {                            // pieces already queued: deliver them before the buffer moves
       hipError_t e = hipStreamSynchronize(stream);
       if (e == hipSuccess)
@@ -695,13 +676,9 @@ struct Filter : FilterBase {
       rb_pend.clear();
       rb_off = 0;
       HIPCHK(e);
-      if (bytes + 64 <= rb_cap) return EKF_OK;
+      if (bytes + 64 <= h_rb.capacity()) return EKF_OK;
     }
-    const size_t want = std::max<size_t>(1 << 16, 2 * (bytes + 64));
-    if (h_rb) HIPCHK(hipHostFree(h_rb));
-    h_rb = nullptr;
-    HIPCHK(hipHostMalloc(&h_rb, want, hipHostMallocDefault));
-    rb_cap = want;
+    HIPCHK(h_rb.reserve(bytes + 64, std::max<size_t>(1 << 16, 2 * (bytes + 64))));
     rb_off = 0;
     return EKF_OK;
   }
@@ -850,16 +827,17 @@ struct Filter : FilterBase {
     if (w < 1 || w > kMaxWindow) FAIL(EKF_ERR_UNSUPPORTED, "window_size outside [1, 32] for the device matcher");
     const size_t bytes = (size_t)std::max(capN, 1) * w * w;
     for (int b = 0; b < 2; ++b) {
-      HIPCHK(hipMalloc(&d_patch[b], bytes));
-      HIPCHK(hipMalloc(&d_mpatch[b], bytes));
+      HIPCHK(d_patch[b].reserve(bytes));
+      HIPCHK(d_mpatch[b].reserve(bytes));
       HIPCHK(hipMemsetAsync(d_patch[b], 0, bytes, stream));
       HIPCHK(hipMemsetAsync(d_mpatch[b], 0, bytes, stream));
     }
-    HIPCHK(hipMalloc(&d_hb, (size_t)std::max(capN, 1) * 2 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_zm, (size_t)std::max(capN, 1) * 2 * sizeof(T)));
-    HIPCHK(hipMalloc(&d_found, (size_t)std::max(capN, 1)));
-    HIPCHK(hipMalloc(&d_score, (size_t)std::max(capN, 1) * sizeof(float)));
-    HIPCHK(hipMalloc(&d_keep, (size_t)std::max(capN, 1) * sizeof(int)));
+    const size_t cn = (size_t)std::max(capN, 1);
+    HIPCHK(d_hb.reserve(cn * 2));
+    HIPCHK(d_zm.reserve(cn * 2));
+    HIPCHK(d_found.reserve(cn));
+    HIPCHK(d_score.reserve(cn));
+    HIPCHK(d_keep.reserve(cn));
     return EKF_OK;
   }
   int set_frame(const unsigned char* gray, int width, int height, int stride) override {
@@ -869,13 +847,7 @@ struct Filter : FilterBase {
       FAIL(EKF_ERR_ARG, "frame size differs from ekf_config image_width / image_height");
     int rc = ensure_image_buffers();
     if (rc) return rc;
-    const size_t need = (size_t)width * height;
-    if (need > frame_cap) {
-      if (d_frame) HIPCHK(hipFree(d_frame));
-      d_frame = nullptr;
-      HIPCHK(hipMalloc(&d_frame, need));
-      frame_cap = need;
-    }
+    HIPCHK(d_frame.reserve((size_t)width * height));
     HIPCHK(hipMemcpy2DAsync(d_frame, (size_t)width, gray, (size_t)stride, (size_t)width, height, hipMemcpyHostToDevice,
                             stream));
     HIPCHK(hipStreamSynchronize(stream));            // the caller's buffer may be reused at once
@@ -899,34 +871,16 @@ struct Filter : FilterBase {
     int rc = ensure_image_buffers();
     if (rc) return rc;
     const size_t out = (size_t)Wo * Ho;
-    if (out > frame_cap) {
-      if (d_frame) HIPCHK(hipFree(d_frame));
-      d_frame = nullptr;
-      frame_cap = 0;
-      HIPCHK(hipMalloc(&d_frame, out));
-      frame_cap = out;
-    }
-    if (need > raw_cap) {
-      if (d_raw) HIPCHK(hipFree(d_raw));
-      d_raw = nullptr;
-      raw_cap = 0;
-      HIPCHK(hipMalloc(&d_raw, need + kIngestSlack));
-      raw_cap = need;
-    }
+    HIPCHK(d_frame.reserve(out));
+    HIPCHK(d_raw.reserve(need + kIngestSlack));
     const int mode = (Wo == width && Ho == height) ? kIngestCopy
                      : (width == 2 * Wo && height == 2 * Ho) ? kIngestArea2 : kIngestLinear;
     if (mode == kIngestLinear && (ingest_tab_w != width || ingest_tab_h != height)) {
       std::vector<int> tab;
       ingest_tables(width, height, Wo, Ho, tab);
       const size_t recs = (size_t)Wo + Ho;
-      if (recs > ingest_tab_cap) {
-        if (d_ingest_tab) HIPCHK(hipFree(d_ingest_tab));
-        d_ingest_tab = nullptr;
-        ingest_tab_cap = 0;
-        HIPCHK(hipMalloc(&d_ingest_tab, recs * sizeof(int4)));
-        ingest_tab_cap = recs;
-      }
       ingest_tab_w = ingest_tab_h = 0;
+      HIPCHK(d_ingest_tab.reserve(recs));
       HIPCHK(hipMemcpyAsync(d_ingest_tab, tab.data(), recs * sizeof(int4), hipMemcpyHostToDevice, stream));
       HIPCHK(hipStreamSynchronize(stream));          // (tab goes out of scope; once per geometry)
       ingest_tab_w = width; ingest_tab_h = height;
@@ -1147,13 +1101,13 @@ struct Filter : FilterBase {
     const int W = frame_w, H = frame_h, w = cfg.window_size;
     const size_t px = (size_t)W * H;
     if (!d_seed_mask) {
-      HIPCHK(hipMalloc(&d_seed_mask, px));
-      HIPCHK(hipMalloc(&d_seed_lam, px * sizeof(double)));
-      HIPCHK(hipMalloc(&d_seed_aux, 2 * sizeof(unsigned long long)));
-      HIPCHK(hipMalloc(&d_seed_ckey, px * sizeof(unsigned long long)));
-      HIPCHK(hipMalloc(&d_seed_cidx, px * sizeof(int)));
-      HIPCHK(hipMalloc(&d_seed_org, (size_t)std::max(capN, 1) * 2 * sizeof(int)));
-      HIPCHK(hipMalloc(&d_seed_out, (px + 1) * sizeof(int)));          // (more corners than pixels cannot be accepted)
+      HIPCHK(d_seed_mask.reserve(px));
+      HIPCHK(d_seed_lam.reserve(px));
+      HIPCHK(d_seed_aux.reserve(2));
+      HIPCHK(d_seed_ckey.reserve(px));
+      HIPCHK(d_seed_cidx.reserve(px));
+      HIPCHK(d_seed_org.reserve((size_t)std::max(capN, 1) * 2));
+      HIPCHK(d_seed_out.reserve(px + 1));                               // (more corners than pixels cannot be accepted)
     }
     int rc = pull_track();
     if (rc) return rc;
@@ -1293,14 +1247,7 @@ struct Filter : FilterBase {
   }
 
   // ---- a13 / a14: one out-of-place pass for a set of removals and conversions -------------
-  int ensure_arch_idx(size_t count) {
-    if (count <= arch_idx_cap) return EKF_OK;
-    if (d_arch_idx) HIPCHK(hipFree(d_arch_idx));
-    d_arch_idx = nullptr;
-    arch_idx_cap = std::max<size_t>(2 * count, 256);
-    HIPCHK(hipMalloc(&d_arch_idx, arch_idx_cap * sizeof(int)));
-    return EKF_OK;
-  }
+  hipError_t ensure_arch_idx(size_t count) { return d_arch_idx.reserve(count, std::max<size_t>(2 * count, 256)); }
 
   // vR.cpp:394-404: a removed XYZ feature that was found more than 5 times is kept (XYZ_pos, cov_4_delete, real_index)
   int archive_removed(const std::vector<char>& rm) {
@@ -1314,19 +1261,14 @@ struct Filter : FilterBase {
     diag_synced = false;                                     // the removal that follows compacts Sigma
     if (rc) return rc;
     const size_t have = arch_real.size(), need = have + ap.size();
-    if (need > arch_cap) {
-      const size_t cap = std::max<size_t>(2 * need, 256);
-      T* nbuf = nullptr;
-      HIPCHK(hipMalloc(&nbuf, cap * 12 * sizeof(T)));
-      hipError_t e1 = have ? hipMemcpyAsync(nbuf, d_archive, have * 12 * sizeof(T), hipMemcpyDeviceToDevice, stream) : hipSuccess;
-      if (e1 == hipSuccess) e1 = hipStreamSynchronize(stream);
-      if (e1 != hipSuccess) { hipFree(nbuf); HIPCHK(e1); }
-      if (d_archive) HIPCHK(hipFree(d_archive));
-      d_archive = nbuf;
-      arch_cap = cap;
+    if (need * 12 > d_archive.capacity()) {                  // the one growth that keeps its contents: new, copy, swap
+      DevBuf<T> nbuf;
+      HIPCHK(nbuf.reserve(std::max<size_t>(2 * need, 256) * 12));
+      if (have) HIPCHK(hipMemcpyAsync(nbuf, d_archive, have * 12 * sizeof(T), hipMemcpyDeviceToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      d_archive = std::move(nbuf);
     }
-    rc = ensure_arch_idx(ap.size());
-    if (rc) return rc;
+    HIPCHK(ensure_arch_idx(ap.size()));
     HIPCHK(hipMemcpyAsync(d_arch_idx, ap.data(), ap.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     k_archive_points<T><<<((int)ap.size() * 12 + 255) / 256, 256, 0, stream>>>(mu(), S(), ld, d_arch_idx, (int)ap.size(),
                                                                              d_archive + have * 12);
@@ -1570,11 +1512,8 @@ struct Filter : FilterBase {
     if (N == 0) return EKF_OK;
     // h, flags and the 2x2 blocks come back through ONE host-mapped pinned buffer the device writes (k_pack_predictions):
     // one launch + one synchronisation per frame for the drop-in caller, instead of three staged copies
-    if (!h_pred) {
-      const size_t bytes = (size_t)capN * (6 * sizeof(T) + 1) + 64;
-      HIPCHK(hipHostMalloc(&h_pred, bytes, hipHostMallocDefault));
-    }
-    T* ph = reinterpret_cast<T*>(h_pred);
+    HIPCHK(h_pred.reserve((size_t)capN * (6 * sizeof(T) + 1) + 64));
+    T* ph = reinterpret_cast<T*>(static_cast<char*>(h_pred));
     T* psd = ph + (size_t)2 * capN;
     unsigned char* pfl = reinterpret_cast<unsigned char*>(psd + (size_t)4 * capN);
     std::vector<T> vhc, vhf;
@@ -1727,7 +1666,8 @@ struct Filter : FilterBase {
   // Work lists for the queued GEMMs: (1) lower-triangular tiles of an nt x nt grid in 8x8
   // super-tiles; (2) the ntr x ntc tiles of the triangular solve, heaviest (largest bj) first.
   int ensure_tilemap(int nt, int ntr, int ntc) {
-    if (tilemap_nt == nt && tilemap_ntc == ntc) return EKF_OK;
+    const std::vector<int> key = {nt, ntc};
+    if (tilemap.current(key)) return EKF_OK;
     std::vector<int> tm;
     const int SB = 8;
     const int ns = (nt + SB - 1) / SB;
@@ -1770,12 +1710,7 @@ struct Filter : FilterBase {
     }
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipStreamSynchronize(stream_b));
-    if (d_tilemap) HIPCHK(hipFree(d_tilemap));
-    d_tilemap = nullptr;
-    HIPCHK(hipMalloc(&d_tilemap, tm.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(d_tilemap, tm.data(), tm.size() * sizeof(int), hipMemcpyHostToDevice));
-    tilemap_nt = nt;
-    tilemap_ntc = ntc;
+    HIPCHK(tilemap.upload(key, tm));
     return EKF_OK;
   }
 
@@ -1934,9 +1869,9 @@ struct Filter : FilterBase {
   // per block step j of the chunk plan: the 128 x 128 blocks of its trailing update except (j + 1, j + 1) -- the S blocks
   // (I >= K > j) and the strip blocks of the step's chunk (row blocks nblk + t, t <= j - s0, columns K in (j, s1))
   int ensure_trail_diag_lists(int nblk, int nchunks, const int* cend) {
-    bool same = td_nblk == nblk && td_nchunks == nchunks;
-    for (int g = 0; same && g < nchunks; ++g) same = td_cend[g] == cend[g];
-    if (same) return EKF_OK;
+    std::vector<int> key = {nblk, nchunks};
+    key.insert(key.end(), cend, cend + nchunks);
+    if (td_blocks.current(key)) return EKF_OK;
     std::vector<int> all;
     td_off.assign(nblk, 0);
     td_cnt.assign(nblk, 0);
@@ -1957,17 +1892,13 @@ struct Filter : FilterBase {
     }
     HIPCHK(hipStreamSynchronize(stream));
     if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
-    if (d_td_blocks) HIPCHK(hipFree(d_td_blocks));
-    d_td_blocks = nullptr;
-    HIPCHK(hipMalloc(&d_td_blocks, std::max<size_t>(all.size(), 2) * sizeof(int)));
-    if (!all.empty()) HIPCHK(hipMemcpy(d_td_blocks, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
-    td_nblk = nblk; td_nchunks = nchunks;
-    for (int g = 0; g < nchunks; ++g) td_cend[g] = cend[g];
+    HIPCHK(td_blocks.upload(key, all, 2));
     return EKF_OK;
   }
   // true: launched (and the factor of step + 1 is done); false: this step keeps the separate launches
   bool launch_trail_diag(UpdateCtx& ux, int step, int m, hipStream_t sc_) {
     if constexpr (kIsF32) {
+      const int td_nblk = td_blocks.first();               // (0: no lists, or those of another plan -- prepare_chain)
       if (!trail_diag_ok() || NB() != 128 || td_nblk == 0 || step + 1 >= td_nblk || td_cnt[step] < td_min_blocks ||
           td_cnt[step] > td_max_blocks)
         return false;
@@ -1975,7 +1906,7 @@ struct Filter : FilterBase {
       a.Y = d_Y; a.ldy = ldy; a.y_bytes = (unsigned)((size_t)2 * ldy * ldy * sizeof(T));
       a.Dinv = d_Dinv; a.dinv_bytes = (unsigned)((size_t)(ldy / 64) * 128 * 128 * sizeof(T));
       a.status = d_status; a.m = m; a.j = step;
-      a.blocks = d_td_blocks + td_off[step]; a.nblocks = td_cnt[step]; a.do_diag = 1;
+      a.blocks = td_blocks.d + td_off[step]; a.nblocks = td_cnt[step]; a.do_diag = 1;
       Scope sc(this, KID_CHOL_TRAILING, sc_);
       ++launch_cnt[EKF_LAUNCH_CHAIN_TRAIL_DIAG];
       k_trail_diag<<<a.nblocks + 1, 1024, kChainLds, sc_>>>(a);
@@ -1992,7 +1923,8 @@ struct Filter : FilterBase {
   // launch earlier: the second stream starts on the chunk while this update is still running)
   // ---- a whole block step as one launch (ekf_step.hpp): the work lists of a ONE-chunk plan of nblk steps -------------------
   int ensure_step_fused_lists(int nblk) {
-    if (sfp.nblk == nblk) return EKF_OK;
+    const std::vector<int> key = {nblk};
+    if (sf_lists.current(key)) return EKF_OK;
     std::vector<int> all;
     sfp.off.assign(nblk, 0);
     sfp.cnt.assign(nblk, 0);
@@ -2013,19 +1945,15 @@ struct Filter : FilterBase {
       all[sfp.off[j] + 2] |= SF_WRITE_DIAG;                 // (a step always has a workgroup: the strip rows)
     }
     HIPCHK(hipStreamSynchronize(stream));
-    if (d_sf_lists) HIPCHK(hipFree(d_sf_lists));
-    d_sf_lists = nullptr;
-    HIPCHK(hipMalloc(&d_sf_lists, all.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(d_sf_lists, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
-    sfp.nblk = nblk; sfp.s1 = s1;
+    HIPCHK(sf_lists.upload(key, all));
     return EKF_OK;
   }
   bool launch_step_fused(const UpdateCtx& ux, int step, int m, hipStream_t sc_) {
     if constexpr (kIsF32) {
-      if (!ux.step_fused || sfp.nblk == 0 || step >= sfp.nblk || sfp.cnt[step] > num_cus / 2 || sc_ != stream) return false;   // (every workgroup resident, with room to spare)
+      if (!ux.step_fused || step >= sf_lists.first() || sfp.cnt[step] > num_cus / 2 || sc_ != stream) return false;   // (every workgroup resident, with room to spare)
       StepFusedArgs a{};
       a.Y = d_Y; a.ldy = ldy; a.Dj = d_Dinv + (size_t)step * 128 * 128; a.status = d_status; a.m = m; a.j = step;
-      a.wl = d_sf_lists + sfp.off[step]; a.nwg = sfp.cnt[step];
+      a.wl = sf_lists.d + sfp.off[step]; a.nwg = sfp.cnt[step];
       a.gate = reinterpret_cast<unsigned*>(d_status + 9);
       small_gate_total += (unsigned)a.nwg;
       a.gate_target = small_gate_total;
@@ -2138,7 +2066,7 @@ struct Filter : FilterBase {
                              int r0, int r1, double work, bool rider, bool su_tail, const int* mirror_rows = nullptr) {
     if constexpr (kIsF32) {
       const int npad_live = round_up(n, NB()), width = c1 - c0;
-      if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
+      HIPCHK(ensure_vimg());
       if (split) {
         Scope sc(this, KID_MISC, ss);
         dim3 grid(npad_live / 128, width / 16);
@@ -2278,7 +2206,7 @@ struct Filter : FilterBase {
   // The chain's cached work lists for this plan: the blocks of k_trail_diag, and for a one-chunk plan of the plain step
   // those of the fused block step (`dist`: the distributed chain of the sharded step has lists of its own)
   int prepare_chain(const UpdatePlan& p, UpdateCtx& ux, bool dist) {
-    if (td_nblk != p.nsteps) td_nblk = 0;                  // lists of another plan: launch_trail_diag must not take them
+    if (td_blocks.first() != p.nsteps) td_blocks.key.clear();   // lists of another plan: launch_trail_diag must not take them
     if (!p.oneblock && !dist && trail_diag_ok() && p.nb == 128 && p.nsteps >= 2) {
       int rc = ensure_trail_diag_lists(p.nsteps, p.nchunks, p.cend);
       if (rc) return rc;
@@ -2387,12 +2315,12 @@ struct Filter : FilterBase {
     c.st = ss;
     switch (solve_shape(p, gi)) {
       case SOLVE_64X64:
-        c.tile_list = d_tilemap + solve6464_off + 2 * (2 * ntc - 2 * wt) * 2 * ntr; c.ntiles = 2 * wt * 2 * ntr;
+        c.tile_list = tilemap.d + solve6464_off + 2 * (2 * ntc - 2 * wt) * 2 * ntr; c.ntiles = 2 * wt * 2 * ntr;
         c.counter = ux.take_queue();
         gemm<ROLE_SOLVE, true, 64, 64>(c);
         break;
       case SOLVE_128_ONE_PER_CU:
-        c.tile_list = d_tilemap + solve_off + 2 * (ntc - wt) * ntr; c.ntiles = wt * ntr;
+        c.tile_list = tilemap.d + solve_off + 2 * (ntc - wt) * ntr; c.ntiles = wt * ntr;
         c.counter = ux.take_queue();
         c.one_per_cu = true;
         gemm<ROLE_SOLVE, true>(c);
@@ -2400,16 +2328,16 @@ struct Filter : FilterBase {
       case SOLVE_64X128:
         // (round 6: when the bf16x6 downdate follows, the tiles also write the plane image of V_g it reads)
         if (kIsF32 && opt_fuse_split && opt_split_bf16 && p.tile == 128 && tri_count >= num_cus && ux.queue_room(16)) {
-          if (!d_Vimg) HIPCHK(hipMalloc(&d_Vimg, (size_t)(n_pad + 128) * ldy * 6));
+          HIPCHK(ensure_vimg());
           c.img = d_Vimg; c.img_nkc = ldy / 16; c.img_c0 = c0;
           *vimg_done = true;
         }
-        c.tile_list = d_tilemap + solve64_off + 2 * (ntc - wt) * 2 * ntr; c.ntiles = wt * 2 * ntr;
+        c.tile_list = tilemap.d + solve64_off + 2 * (ntc - wt) * 2 * ntr; c.ntiles = wt * 2 * ntr;
         c.counter = ux.take_queue();
         gemm<ROLE_SOLVE, true, 64, 128>(c);
         break;
       case SOLVE_128:
-        c.tile_list = d_tilemap + solve_off + 2 * (ntc - wt) * ntr; c.ntiles = wt * ntr;
+        c.tile_list = tilemap.d + solve_off + 2 * (ntc - wt) * ntr; c.ntiles = wt * ntr;
         c.counter = ux.take_queue();
         gemm<ROLE_SOLVE, true>(c);
         break;
@@ -2455,7 +2383,7 @@ struct Filter : FilterBase {
       const int* mirror_rows = nullptr;
       if (opt_syrk_mirror_skip && gi + 1 < p.nchunks)
         mirror_rows = d_counters + kQueueCounters + 2 * (p.recompute ? gi + 1 : kMirrorEmpty);
-      return launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, !vimg_done, d_tilemap + tri6_off, tri_count, 0, 0, INT_MAX,
+      return launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, !vimg_done, tilemap.d + tri6_off, tri_count, 0, 0, INT_MAX,
                                     double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail, mirror_rows);
     }
     if (chunk_fuses(p, gi, ux)) {
@@ -2470,7 +2398,7 @@ struct Filter : FilterBase {
         GemmArgs g{};
         g.A = d_V + c0; g.lda = ldy; g.B = d_V + c0; g.ldb = ldy; g.C = S(); g.ldc = ld;
         g.K = width; g.alpha = -1.0; g.beta = 1.0; g.tri = TRI_LOWER_MIRROR;
-        g.tile_map = d_tilemap; g.ntiles = n2 + tri_count; g.counter = ux.take_queue(); g.stagger = 1;
+        g.tile_map = tilemap.d; g.ntiles = n2 + tri_count; g.counter = ux.take_queue(); g.stagger = 1;
         g.B2 = d_Y + (size_t)c1 * ldy + c0; g.ldb2 = ldy; g.C2 = d_W + c1; g.ldc2 = ldy;
         g.n2 = n2; g.nr2 = nr2; g.row2 = p.recompute ? npad_live / 128 : 0;
         ++launch_cnt[EKF_LAUNCH_DOWNDATE_F32_FUSED_WU];
@@ -2492,13 +2420,13 @@ struct Filter : FilterBase {
     c.counter = ux.take_queue();
     c.st = ss;
     if (t64) {                                        // small map: 64 x 64 tiles, or most of the chip idles
-      c.tile_list = d_tilemap + tri64_off; c.ntiles = tri64_count;
+      c.tile_list = tilemap.d + tri64_off; c.ntiles = tri64_count;
       gemm<ROLE_DOWNDATE, false, 64, 64>(c);
     } else if (mf && ss != stream_b) {                // half tiles at the end of the list: the launch on every CU only (128 x 128 MFMA kernel)
-      c.tile_list = d_tilemap + trih_off; c.ntiles = trih_count;
+      c.tile_list = tilemap.d + trih_off; c.ntiles = trih_count;
       gemm<ROLE_DOWNDATE, false>(c);
     } else {
-      c.tile_list = d_tilemap; c.ntiles = tri_count;
+      c.tile_list = tilemap.d; c.ntiles = tri_count;
       gemm<ROLE_DOWNDATE, false>(c);
     }
     return EKF_OK;
@@ -2651,12 +2579,7 @@ struct Filter : FilterBase {
     const int nb = NB();
     const int npad_live = round_up(nn, nb);
     const size_t need = (size_t)npad_live * m_pad * 2;     // K and the scratch of the back-substitution
-    if (need > K_elems) {
-      if (d_K) HIPCHK(hipFree(d_K));
-      d_K = nullptr;
-      HIPCHK(hipMalloc(&d_K, need * sizeof(T)));
-      K_elems = need;
-    }
+    HIPCHK(d_K.reserve(need));
     // K = V L^-1 by block back-substitution over the chunks of the factorisation (only the diagonal
     // inverses Z_gg = L_gg^-T exist):  K_g = (V_g - K[:, c1:] L[c1:, c0:c1]) Z_gg^T,  last chunk first.
     // One chunk: K = V Z^T.
@@ -2818,9 +2741,11 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
   // ---- f2 / f1: search ellipses and 1-point RANSAC hypotheses -------------------------------------
-  int* d_ibuf = nullptr;                 // 3 N ints (ellipses) / M ints (counts)
-  unsigned char* d_rmask = nullptr;      // M x M inlier mask
-  size_t rmask_bytes = 0;
+  DevBuf<int> d_ibuf;                    // 3 N ints (ellipses) / M ints (counts)
+  DevBuf<unsigned char> d_rmask;         // M x M inlier mask
+  hipError_t ensure_ibuf() { return d_ibuf.reserve((size_t)std::max(capN, 1) * 3); }
+  hipError_t ensure_rmask(int M) { return d_rmask.reserve((size_t)M * M); }
+  hipError_t ensure_gate() { return h_gate.reserve((size_t)std::max(capN, 1) + 64); }
 
   int rescue(const void* cam_before, const void* z, const int* idx, int M, double thr, unsigned char* out) override {
     HIPCHK(hipSetDevice(device));
@@ -2833,10 +2758,10 @@ struct Filter : FilterBase {
     rc = stage_inputs(z, idx, M, cam_before);          // pinned staging ring -> d_z / d_midx / d_tmp
     if (rc) return rc;
     sh_list.clear();
-    if (!d_ibuf) HIPCHK(hipMalloc(&d_ibuf, (size_t)std::max(capN, 1) * 3 * sizeof(int)));
+    HIPCHK(ensure_ibuf());
     // the gate flags go straight into host-mapped pinned memory (one synchronisation, no staged copy)
-    if (!h_gate) HIPCHK(hipHostMalloc(&h_gate, (size_t)std::max(capN, 1) + 64, hipHostMallocDefault));
-    unsigned char* d_out = static_cast<unsigned char*>(h_gate);
+    HIPCHK(ensure_gate());
+    unsigned char* d_out = h_gate;
     {
       Scope sc(this, KID_MEASURE);
       k_measure<T><<<(M + 63) / 64, 64, 0, stream>>>(mu(), d_pos, d_coding, 0, N, cam, d_h, d_Hc, d_Hf, d_flags, d_midx, M,
@@ -2865,15 +2790,14 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
 
-  T* d_pts = nullptr;
-  T* d_tab = nullptr;                    // table of ekf_export_points_table (grow-only)
-  size_t tab_rows_cap = 0;
+  DevBuf<T> d_pts;
+  DevBuf<T> d_tab;                       // table of ekf_export_points_table (grow-only), 12 scalars per row
   int export_points(void* out, int convert) override {
     HIPCHK(hipSetDevice(device));
     if (N == 0) return EKF_OK;
     int rc = sync_layout();
     if (rc) return rc;
-    if (!d_pts) HIPCHK(hipMalloc(&d_pts, (size_t)std::max(capN, 1) * 12 * sizeof(T)));
+    HIPCHK(d_pts.reserve((size_t)std::max(capN, 1) * 12));
     rc = shard_sync_diag_blocks();                                      // sharded: every feature's own block from its owner
     if (rc) return rc;
     const T* scale_ptr = (camera_dim == 14) ? mu() + 13 : nullptr;      // the map scale is read on the device
@@ -2895,20 +2819,14 @@ struct Filter : FilterBase {
     if (rc) return rc;
     rc = shard_sync_diag_blocks();                                      // sharded: every feature's own block from its owner
     if (rc) return rc;
-    if ((size_t)rows > tab_rows_cap) {                                  // grow-only table buffer (freed with the filter)
+    if ((size_t)rows * 12 > d_tab.capacity()) {                         // grow-only table buffer
       HIPCHK(hipStreamSynchronize(stream));
-      if (d_tab) HIPCHK(hipFree(d_tab));
-      d_tab = nullptr;
-      tab_rows_cap = 0;
-      const size_t cap = std::max<size_t>(2 * (size_t)rows, 256);
-      HIPCHK(hipMalloc(&d_tab, cap * 12 * sizeof(T)));
-      tab_rows_cap = cap;
+      HIPCHK(d_tab.reserve((size_t)rows * 12, std::max<size_t>(2 * (size_t)rows, 256) * 12));
     }
     HIPCHK(hipMemsetAsync(d_tab, 0, (size_t)rows * 12 * sizeof(T), stream));
     const T* scale_ptr = (camera_dim == 14) ? mu() + 13 : nullptr;      // the map scale is read on the device
     const size_t na = arch_real.size();
-    rc = ensure_arch_idx((size_t)N + na);
-    if (rc) return rc;
+    HIPCHK(ensure_arch_idx((size_t)N + na));
     HIPCHK(hipMemcpyAsync(d_arch_idx, real_index.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, stream));
     if (na) HIPCHK(hipMemcpyAsync(d_arch_idx + N, arch_real.data(), na * sizeof(int), hipMemcpyHostToDevice, stream));
     k_export_points<T><<<(N + 63) / 64, 64, 0, stream>>>(mu(), S(), ld, d_pos, d_coding, N, T(1), 0, d_tab, d_arch_idx, rows,
@@ -2945,7 +2863,7 @@ struct Filter : FilterBase {
     if (!have_meas) FAIL(EKF_ERR_STATE, "ekf_get_search_ellipses needs ekf_predict / ekf_measure first");
     if (N == 0) return EKF_OK;
     { int rcs = ensure_sd(); if (rcs) return rcs; }
-    if (!d_ibuf) HIPCHK(hipMalloc(&d_ibuf, (size_t)std::max(capN, 1) * 3 * sizeof(int)));
+    HIPCHK(ensure_ibuf());
     k_search_ellipses<T><<<(N + 127) / 128, 128, 0, stream>>>(d_Sd, N, sigma_size, d_ibuf);
     HIPCHK(hipGetLastError());
     { int rc = rb_add(out, d_ibuf, (size_t)N * 3 * sizeof(int)); if (rc) return rc; }
@@ -2966,13 +2884,8 @@ struct Filter : FilterBase {
     int rc = build_innovation(nullptr, d_midx, M, 0, false, &m, &m_pad, nullptr, 0, true);       // W = Sigma H^T for the listed features
     if (rc) return rc;
     have_update = false;
-    if (!d_ibuf) HIPCHK(hipMalloc(&d_ibuf, (size_t)std::max(capN, 1) * 3 * sizeof(int)));
-    if ((size_t)M * M > rmask_bytes) {
-      if (d_rmask) HIPCHK(hipFree(d_rmask));
-      d_rmask = nullptr;
-      HIPCHK(hipMalloc(&d_rmask, (size_t)M * M));
-      rmask_bytes = (size_t)M * M;
-    }
+    HIPCHK(ensure_ibuf());
+    HIPCHK(ensure_rmask(M));
     {
       Scope sc(this, KID_MISC);
       dim3 grid((M + 127) / 128, M);
@@ -2983,10 +2896,10 @@ struct Filter : FilterBase {
     // ONE read-back: counts, the camera pose and -- up to 64 KiB -- the whole inlier mask through a host-mapped pinned
     // buffer the device writes (k_pack_ransac), one synchronisation
     const size_t counts_bytes = ((size_t)capN * sizeof(int) + 15) / 16 * 16;   // the pose behind the counts stays 16-byte aligned
-    if (!h_ransac) HIPCHK(hipHostMalloc(&h_ransac, counts_bytes + 8 * sizeof(T) + kRansacMaskBytes + 64,
-                                        hipHostMallocDefault));
-    int* pc = reinterpret_cast<int*>(h_ransac);
-    T* pcam = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(h_ransac) + counts_bytes);
+    HIPCHK(h_ransac.reserve(counts_bytes + 8 * sizeof(T) + kRansacMaskBytes + 64));
+    unsigned char* hr = h_ransac;
+    int* pc = reinterpret_cast<int*>(hr);
+    T* pcam = reinterpret_cast<T*>(hr + counts_bytes);
     unsigned char* pmask = reinterpret_cast<unsigned char*>(pcam + 8);
     const int with_mask = ((size_t)M * M <= kRansacMaskBytes) ? 1 : 0;
     k_pack_ransac<T><<<with_mask ? std::max(1, std::min(64, (M * M + 255) / 256)) : (M + 255) / 256, 256, 0, stream>>>(
@@ -3130,14 +3043,14 @@ struct Filter : FilterBase {
     k->cam = cam;                                              // the lens model and scale its rectified getters use (§14)
     k->scale = cfg.scale;
     const size_t px = (size_t)std::max(cam.width, 1) * std::max(cam.height, 1);
-    HIPCHK(hipMalloc(&k->d_state, 2 * sizeof(KfState)));
-    HIPCHK(hipMalloc(&k->d_rec, sizeof(KfRecord)));
-    HIPCHK(hipMalloc(&k->d_cand, px));
-    HIPCHK(hipMalloc(&k->d_emit, px));
+    HIPCHK(k->d_state.reserve(2));
+    HIPCHK(k->d_rec.reserve(1));
+    HIPCHK(k->d_cand.reserve(px));
+    HIPCHK(k->d_emit.reserve(px));
     if (k->raw_w > 0) {                                        // ekf_keyframe_create_raw: the two slots of the camera's own frame
       const size_t rb = (size_t)k->raw_w * k->raw_h * k->raw_c;
-      HIPCHK(hipMalloc(&k->d_cand_raw, rb));
-      HIPCHK(hipMalloc(&k->d_emit_raw, rb));
+      HIPCHK(k->d_cand_raw.reserve(rb));
+      HIPCHK(k->d_emit_raw.reserve(rb));
     }
     const KfState s0 = KfSelector::initial();
     HIPCHK(hipMemcpy(k->d_state, &s0, sizeof(s0), hipMemcpyHostToDevice));
@@ -3227,8 +3140,7 @@ struct Filter : FilterBase {
   std::vector<int> sh_fb;                                  // feature boundaries of the ranks, world + 1 entries
   ekf_allgather_fn sh_ag = nullptr;
   void* sh_ctx = nullptr;
-  T *d_stage_send = nullptr, *d_stage_recv = nullptr;
-  size_t stage_slot = 0;                                   // scalars per slot the staging buffers hold
+  DevBuf<T> d_stage_send, d_stage_recv;                    // one slot of scalars, and sh_world of them
   int sh_rebalances = 0;
   bool sh_force = false;                                   // world 1 with a callback and EKF_SHARD_FORCE_COLLECTIVE=1: every exchange still runs (profiling the collective path on one GPU)
   std::vector<int> sh_list;                                // host copy of the measured list resident in d_midx
@@ -3267,23 +3179,20 @@ struct Filter : FilterBase {
   // ~35 us of gather where the replicated one pays the whole trailing update; measured on one rank (profiles/
   // r6_shard_world1_dist_chain.txt) the two meet at 32 steps for 8 ranks (2.1 ms each) and the distributed one wins above
   int shard_dist_min_blocks = 40;
-  struct DistPlan {
-    int nblk = 0, nchunks = 0, cend[8] = {0, 0, 0, 0, 0, 0, 0, 0}, world = 0, rank = -1;
+  struct DistPlan {                                      // of the plan dist_lists was built for (dist_lists.first() block steps)
     std::vector<int> pb_off, pb_own, pb_cnt, tl_off, tl_cnt, slot_blocks;
     std::vector<int> tb_off, tb_cnt;                     // the same update as (I, K) pairs of 128 x 128 blocks, without (j + 1, j + 1): k_trail_diag
   } dist;
-  int* d_dist_lists = nullptr;
-  int* d_dist_counters = nullptr;
-  int dist_counters_cap = 0;
-  T *d_dist_send = nullptr, *d_dist_recv = nullptr;
-  size_t dist_slot = 0;
+  WorkList dist_lists;                                   // key (nblk, nchunks, world, rank, chunk ends)
+  DevBuf<int> d_dist_counters;
+  DevBuf<T> d_dist_send, d_dist_recv;
   bool dist_chain_ok(int nsteps) const {
     return kIsF32 && opt_mfma && opt_shard_dist_chain && sh_on && exchanges() && NB() == 128 && nsteps >= shard_dist_min_blocks;
   }
   int ensure_dist_plan(int nblk, int nchunks, const int* cend) {
-    bool same = dist.nblk == nblk && dist.nchunks == nchunks && dist.world == sh_world && dist.rank == sh_rank;
-    for (int g = 0; same && g < nchunks; ++g) same = dist.cend[g] == cend[g];
-    if (!same) {
+    std::vector<int> key = {nblk, nchunks, sh_world, sh_rank};
+    key.insert(key.end(), cend, cend + nchunks);
+    if (!dist_lists.current(key)) {
       std::vector<int> all;
       dist.pb_off.assign(nblk, 0); dist.pb_own.assign(nblk, 0); dist.pb_cnt.assign(nblk, 0);
       dist.tl_off.assign(nblk, 0); dist.tl_cnt.assign(nblk, 0); dist.slot_blocks.assign(nblk, 0);
@@ -3338,27 +3247,11 @@ struct Filter : FilterBase {
       }
       HIPCHK(hipStreamSynchronize(stream));
       if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
-      if (d_dist_lists) HIPCHK(hipFree(d_dist_lists));
-      d_dist_lists = nullptr;
-      HIPCHK(hipMalloc(&d_dist_lists, std::max<size_t>(all.size(), 1) * sizeof(int)));
-      HIPCHK(hipMemcpy(d_dist_lists, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
-      if (nblk * 8 > dist_counters_cap) {
-        if (d_dist_counters) HIPCHK(hipFree(d_dist_counters));
-        d_dist_counters = nullptr;
-        dist_counters_cap = nblk * 8;
-        HIPCHK(hipMalloc(&d_dist_counters, (size_t)dist_counters_cap * sizeof(int)));
-      }
+      HIPCHK(d_dist_counters.reserve((size_t)nblk * 8));
       const size_t slot = (size_t)std::max(maxslot, 1) * 128 * 128;
-      if (slot > dist_slot) {
-        if (d_dist_send) HIPCHK(hipFree(d_dist_send));
-        if (d_dist_recv) HIPCHK(hipFree(d_dist_recv));
-        d_dist_send = d_dist_recv = nullptr;
-        HIPCHK(hipMalloc(&d_dist_send, slot * sizeof(T)));
-        HIPCHK(hipMalloc(&d_dist_recv, slot * sizeof(T) * sh_world));
-        dist_slot = slot;
-      }
-      dist.nblk = nblk; dist.nchunks = nchunks; dist.world = sh_world; dist.rank = sh_rank;
-      for (int g = 0; g < nchunks; ++g) dist.cend[g] = cend[g];
+      HIPCHK(d_dist_send.reserve(slot));
+      HIPCHK(d_dist_recv.reserve(slot * sh_world));
+      HIPCHK(dist_lists.upload(key, all));
     }
     HIPCHK(hipMemsetAsync(d_dist_counters, 0, (size_t)nblk * 8 * sizeof(int), stream));
     return EKF_OK;
@@ -3368,7 +3261,7 @@ struct Filter : FilterBase {
   int dist_chain_steps(UpdateCtx& ux, int step0, int step1, int m, int m_pad, hipStream_t st) {
     if constexpr (kIsF32) {
       T* Y = d_Y;
-      const int nblk = dist.nblk;
+      const int nblk = dist_lists.first();
       for (int step = step0; step < step1; ++step) {
         const int j = step * 128, r0 = j + 128;
         T* Dj = d_Dinv + (size_t)step * 128 * 128;
@@ -3377,7 +3270,7 @@ struct Filter : FilterBase {
           ++launch_cnt[EKF_LAUNCH_CHAIN_STEP];
           k_chol_diag_packed<><<<1, 1024, 0, st>>>(Y + (size_t)j * ldy + j, ldy, Dj, d_status, std::max(1, std::min(8, (m - j + 15) / 16)));
         }
-        const int* pb = d_dist_lists + dist.pb_off[step];
+        const int* pb = dist_lists.d + dist.pb_off[step];
         if (dist.pb_cnt[step] > 0) {
           Scope sc(this, KID_CHOL_PANEL, st);
           ++launch_cnt[EKF_LAUNCH_CHAIN_STEP];
@@ -3402,7 +3295,7 @@ struct Filter : FilterBase {
           a.Y = d_Y; a.ldy = ldy; a.y_bytes = (unsigned)((size_t)2 * ldy * ldy * sizeof(T));
           a.Dinv = d_Dinv; a.dinv_bytes = (unsigned)((size_t)(ldy / 64) * 128 * 128 * sizeof(T));
           a.status = d_status; a.m = m; a.j = step;
-          a.blocks = d_dist_lists + dist.tb_off[step]; a.nblocks = dist.tb_cnt[step]; a.do_diag = 1;
+          a.blocks = dist_lists.d + dist.tb_off[step]; a.nblocks = dist.tb_cnt[step]; a.do_diag = 1;
           Scope sc(this, KID_CHOL_TRAILING, st);
           ++launch_cnt[EKF_LAUNCH_CHAIN_TRAIL_DIAG];
           k_trail_diag<<<a.nblocks + 1, 1024, kChainLds, st>>>(a);
@@ -3414,7 +3307,7 @@ struct Filter : FilterBase {
           GemmArgs g{};                                    // the rank's tiles of Y[r0.., r0..] -= P P^T, as listed
           g.A = P; g.lda = ldy; g.B = P; g.ldb = ldy; g.C = Y + (size_t)r0 * ldy + r0; g.ldc = ldy;
           g.K = 128; g.alpha = -1.0; g.beta = 1.0; g.tri = TRI_ALL; g.row_off = r0; g.col_off = r0;
-          g.tile_map = d_dist_lists + dist.tl_off[step]; g.ntiles = dist.tl_cnt[step]; g.counter = d_dist_counters + 8 * step;
+          g.tile_map = dist_lists.d + dist.tl_off[step]; g.ntiles = dist.tl_cnt[step]; g.counter = d_dist_counters + 8 * step;
           k_gemm_mfma<ROLE_TRAILING, false, 64, 64><<<std::min(dist.tl_cnt[step], 2 * num_cus), 256, 0, st>>>(g);
         }
       }
@@ -3425,17 +3318,13 @@ struct Filter : FilterBase {
   }
 
   int ensure_stage(size_t slot_elems) {
-    if (slot_elems <= stage_slot) return EKF_OK;
+    if (slot_elems <= d_stage_send.capacity() && slot_elems * sh_world <= d_stage_recv.capacity()) return EKF_OK;
     HIPCHK(hipStreamSynchronize(stream));
     if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
     if (stream_g) HIPCHK(hipStreamSynchronize(stream_g));
-    if (d_stage_send) HIPCHK(hipFree(d_stage_send));
-    if (d_stage_recv) HIPCHK(hipFree(d_stage_recv));
-    d_stage_send = d_stage_recv = nullptr;
     slot_elems = (slot_elems + 63) / 64 * 64;
-    HIPCHK(hipMalloc(&d_stage_send, slot_elems * sizeof(T)));
-    HIPCHK(hipMalloc(&d_stage_recv, slot_elems * sizeof(T) * sh_world));
-    stage_slot = slot_elems;
+    HIPCHK(d_stage_send.reserve(slot_elems));
+    HIPCHK(d_stage_recv.reserve(slot_elems * sh_world));
     return EKF_OK;
   }
 
@@ -3492,13 +3381,11 @@ struct Filter : FilterBase {
   int opt_shard_sym = 1;                                   // EKF_SHARD_SYM=0: the plain row panel (A/B)
   int dbg_sync = 0;                                        // EKF_DEBUG_SYNC (bisecting an ordering problem): device synchronisation at 1 the end of
                                                            // the sharded update, 2 the end of every chunk, 4 its start, 8 the end of the sharded predict
-  int* d_panel_tiles = nullptr;
-  size_t panel_tiles_cap = 0;
+  WorkList panel_tiles;
   int panel_ntiles = 0;
-  std::vector<int> panel_key;
   int ensure_panel_tiles(int p0, int prows, int r0, int r1, int npad_live) {
-    std::vector<int> key = {p0, prows, r0, r1, npad_live};
-    if (key == panel_key) return EKF_OK;
+    const std::vector<int> key = {p0, prows, r0, r1, npad_live};
+    if (panel_tiles.current(key)) return EKF_OK;
     std::vector<int> tl;
     const int t0 = p0 / 128, nt = prows / 128, nc = npad_live / 128;
     auto interior = [&](int T_) { return 128 * T_ >= r0 && 128 * T_ + 128 <= r1; };
@@ -3517,28 +3404,19 @@ struct Filter : FilterBase {
     }
     HIPCHK(hipStreamSynchronize(stream));
     if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
-    if (tl.size() > panel_tiles_cap) {
-      if (d_panel_tiles) HIPCHK(hipFree(d_panel_tiles));
-      d_panel_tiles = nullptr;
-      HIPCHK(hipMalloc(&d_panel_tiles, tl.size() * sizeof(int)));
-      panel_tiles_cap = tl.size();
-    }
-    HIPCHK(hipMemcpy(d_panel_tiles, tl.data(), tl.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(panel_tiles.upload(key, tl));
     panel_ntiles = (int)tl.size() / 2;
-    panel_key = key;
     return EKF_OK;
   }
 
   // Canonical tiles (bi >= bj) of the bf16x6 downdate that touch a row block with a valid row of this rank (the camera
   // block and the blocks of the own rows [r0, r1)), diagonal tiles first, then the plain path's super-tile order.  What
   // each tile reads and stores is decided in the kernel, row by row (k_syrk_bf16x6: cam, v_lo, v_hi).
-  int* d_shard_syrk = nullptr;
-  size_t shard_syrk_cap = 0;
+  WorkList shard_syrk;
   int shard_syrk_n = 0;
-  std::vector<int> shard_syrk_key;
   int ensure_shard_syrk_list(int r0, int r1, int npad_live) {
-    std::vector<int> key = {r0, r1, npad_live, camera_dim};
-    if (key == shard_syrk_key) return EKF_OK;
+    const std::vector<int> key = {r0, r1, npad_live, camera_dim};
+    if (shard_syrk.current(key)) return EKF_OK;
     const int nt = npad_live / 128, SB = 8, ns = (nt + SB - 1) / SB;
     auto touched = [&](int b) { return b * 128 < camera_dim || (r1 > r0 && b * 128 < r1 && b * 128 + 128 > r0); };
     std::vector<int> tl;
@@ -3550,15 +3428,8 @@ struct Filter : FilterBase {
             if (j < i && (touched(i) || touched(j))) { tl.push_back(i); tl.push_back(j); }
     HIPCHK(hipStreamSynchronize(stream));
     if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
-    if (tl.size() > shard_syrk_cap) {
-      if (d_shard_syrk) HIPCHK(hipFree(d_shard_syrk));
-      d_shard_syrk = nullptr;
-      HIPCHK(hipMalloc(&d_shard_syrk, std::max<size_t>(tl.size(), 2) * sizeof(int)));
-      shard_syrk_cap = tl.size();
-    }
-    if (!tl.empty()) HIPCHK(hipMemcpy(d_shard_syrk, tl.data(), tl.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(shard_syrk.upload(key, tl, 2));
     shard_syrk_n = (int)tl.size() / 2;
-    shard_syrk_key = key;
     return EKF_OK;
   }
 
@@ -3566,9 +3437,8 @@ struct Filter : FilterBase {
   // path's list: column tile ntc - 1 first, every row tile of the panel per column tile).  Round 4: the sharded solve ran
   // as a plain 2-D grid of 128 x 128 tiles, whose static placement pairs the heavy tiles of a column on the same CUs:
   // 0.50 ms of solves per step at N = 1000 / world 1 against 0.16 on the plain path.
-  int* d_shard_solve = nullptr;
+  WorkList shard_solve;
   int shard_solve_rows = 0;                                // row tiles per column tile of the list
-  std::vector<int> shard_solve_key;
   int shard_ntc_max() const { return ldy / 128; }
   // The list covers every column tile the workspace can hold (ldy / 128), last column tile first; a chunk of wt column tiles
   // starts at entry (ntc_max - wt) * rows (the entries are relative to the chunk: bj = wt - 1 .. 0), so the list depends on
@@ -3578,8 +3448,8 @@ struct Filter : FilterBase {
   // (negative for the camera block): one queued launch per chunk instead of three launches, two of them a single
   // latency-bound tile row (0.31 -> 0.2 ms of solves per step at N = 1000 / world 1).
   int ensure_shard_solve_list(int p0, int prows, int npad_live, bool with_cam) {
-    std::vector<int> key = {p0, prows, npad_live, with_cam ? 1 : 0, ldy};
-    if (key == shard_solve_key) return EKF_OK;
+    const std::vector<int> key = {p0, prows, npad_live, with_cam ? 1 : 0, ldy};
+    if (shard_solve.current(key)) return EKF_OK;
     std::vector<int> rows;
     if (with_cam) { rows.push_back(-p0 / 64); rows.push_back(-p0 / 64 + 1); }
     for (int i = 0; i < prows / 64; ++i) rows.push_back(i);
@@ -3592,13 +3462,8 @@ struct Filter : FilterBase {
       for (int bi : rows) { tl.push_back(bi); tl.push_back(j); }
     HIPCHK(hipStreamSynchronize(stream));
     if (stream_b) HIPCHK(hipStreamSynchronize(stream_b));
-    if (d_shard_solve) HIPCHK(hipFree(d_shard_solve));
-    d_shard_solve = nullptr;
-    shard_solve_key.clear();
-    HIPCHK(hipMalloc(&d_shard_solve, tl.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(d_shard_solve, tl.data(), tl.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(shard_solve.upload(key, tl));
     shard_solve_rows = (int)rows.size();
-    shard_solve_key = key;
     return EKF_OK;
   }
 
@@ -3774,13 +3639,8 @@ struct Filter : FilterBase {
       }
     }
     have_update = false;
-    if (!d_ibuf) HIPCHK(hipMalloc(&d_ibuf, (size_t)std::max(capN, 1) * 3 * sizeof(int)));
-    if ((size_t)M * M > rmask_bytes) {
-      if (d_rmask) HIPCHK(hipFree(d_rmask));
-      d_rmask = nullptr;
-      HIPCHK(hipMalloc(&d_rmask, (size_t)M * M));
-      rmask_bytes = (size_t)M * M;
-    }
+    HIPCHK(ensure_ibuf());
+    HIPCHK(ensure_rmask(M));
     const ShardTab lt = list_tab(idx, M);
     const int k0 = lt.start[sh_rank], kc = lt.count[sh_rank];
     {
@@ -3821,7 +3681,7 @@ struct Filter : FilterBase {
     if (!sh_on) {
       // a large mask stayed on the device: its column is packed there (a strided 2-D copy of M one-byte rows takes
       // milliseconds at M = 1000) and comes back through pinned memory
-      if (!h_gate) HIPCHK(hipHostMalloc(&h_gate, (size_t)std::max(capN, 1) + 64, hipHostMallocDefault));
+      HIPCHK(ensure_gate());
       k_pack_mask_col<<<(M + 255) / 256, 256, 0, stream>>>(d_rmask, M, sel, 0, M, static_cast<unsigned char*>(h_gate));
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(stream));
@@ -3835,7 +3695,7 @@ struct Filter : FilterBase {
     const size_t slot_bytes = (size_t)std::max(mx, 1);
     int rc = ensure_stage((slot_bytes + sizeof(T) - 1) / sizeof(T));
     if (rc) return rc;
-    unsigned char* d_col = reinterpret_cast<unsigned char*>(d_ibuf) + (size_t)M * sizeof(int);   // behind the counts
+    unsigned char* d_col = reinterpret_cast<unsigned char*>(d_ibuf + M);            // behind the counts
     if (kc > 0) k_pack_mask_col<<<(kc + 255) / 256, 256, 0, stream>>>(d_rmask, M, sel, k0, kc, d_col);
     HIPCHK(hipGetLastError());
     std::vector<unsigned char> host;
@@ -3987,7 +3847,7 @@ struct Filter : FilterBase {
         const int wt = width / 128;
         const size_t off = (size_t)p.p0 * ldy;
         c.A = d_W + off + c0; c.C = d_V + off + c0; c.rows = p.prows;
-        c.tile_list = d_shard_solve + 2 * (shard_ntc_max() - wt) * shard_solve_rows; c.ntiles = wt * shard_solve_rows;
+        c.tile_list = shard_solve.d + 2 * (shard_ntc_max() - wt) * shard_solve_rows; c.ntiles = wt * shard_solve_rows;
         c.counter = ux.take_queue();
         gemm<ROLE_SOLVE, true, 64, 128>(c);
         return EKF_OK;
@@ -4032,7 +3892,7 @@ struct Filter : FilterBase {
       // V_g -> plane image, then ONE launch over the canonical tiles that touch the camera block or an own block; each
       // element pair is the same sum as on the plain path
       const bool rider = ux.row_pending && shard_syrk_n > 0;
-      int rcd = launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, true, d_shard_syrk, shard_syrk_n, camera_dim, p.r0, p.r1,
+      int rcd = launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, true, shard_syrk.d, shard_syrk_n, camera_dim, p.r0, p.r1,
                                        2.0 * 128 * 128 * shard_syrk_n * double(std::min(c1, m) - std::min(c0, m)), rider, false);
       if (rcd) return rcd;
       if (ux.row_pending && !rider) launch_row_update(c0, c1, m_pad, ss, true);
@@ -4052,7 +3912,7 @@ struct Filter : FilterBase {
         // the own panel as ONE queued launch over the listed tiles: interior x interior lower tiles + mirror, the rest plain
         if (sc.on) prof_work[KID_DOWNDATE] += 2.0 * 128 * 128 * panel_ntiles * double(std::min(c1, m) - std::min(c0, m));
         c.tri = TRI_LISTED; c.row_off = rr.r0;
-        c.tile_list = d_panel_tiles; c.ntiles = panel_ntiles; c.counter = ux.take_queue();
+        c.tile_list = panel_tiles.d; c.ntiles = panel_ntiles; c.counter = ux.take_queue();
       } else if (sc.on) {
         prof_work[KID_DOWNDATE] += 2.0 * rr.count * double(n) * (std::min(c1, m) - std::min(c0, m));
       }
@@ -4296,31 +4156,25 @@ struct SbaSystem {
   std::vector<double> iter_ms;
   hipEvent_t ev[6] = {};
   // device
-  struct Buf { void* p = nullptr; size_t bytes = 0; };
   enum { B_NODES, B_OLDN, B_NM, B_PTS, B_OLDP, B_POFF, B_PNODE, B_PPOINT, B_UV, B_VALID, B_PRJ, B_TPS, B_COFF, B_CPRJ,
          B_PAIR_AB, B_PAIR_OFF, B_ITEMS, B_EMPTY, B_A, B_L, B_B, B_X, B_R, B_DX, B_DINV, B_PART, B_RES,
          B_PAIR_SLOT, B_BLK, B_J, B_ADJ_OFF, B_ADJ, B_Q, B_S, B_PART_DQ, B_PART_RS, B_COUNT };
-  Buf buf[B_COUNT];
+  DevBuf<unsigned char> buf[B_COUNT];                        // sized in bytes
   int npairs = 0, nfree = 0, npad = 0, noff = 0;
   static constexpr int kCgChunk = 256;                       // CG rounds enqueued between two reads of the CG state
   bool pcg() const { return solver == EKF_SBA_SOLVER_BPCG; }
   SbaCg* dcg() { return reinterpret_cast<SbaCg*>(dp<SbaResult>(B_RES) + 1); }
 
+  // (the buffers are members and go after this body, behind the stream: it is drained first)
   ~SbaSystem() {
     hipSetDevice(device);
-    for (auto& b : buf) if (b.p) hipFree(b.p);
+    if (stream) hipStreamSynchronize(stream);
     for (auto& e : ev) if (e) hipEventDestroy(e);
     if (stream) hipStreamDestroy(stream);
   }
-  template <typename T> T* dp(int i) { return static_cast<T*>(buf[i].p); }
+  template <typename T> T* dp(int i) { return reinterpret_cast<T*>(static_cast<unsigned char*>(buf[i])); }
   int ensure(int i, size_t bytes) {
-    if (bytes == 0) bytes = 8;
-    if (buf[i].bytes >= bytes) return EKF_OK;
-    if (buf[i].p) HIPCHK(hipFree(buf[i].p));
-    buf[i].p = nullptr;
-    buf[i].bytes = 0;
-    HIPCHK(hipMalloc(&buf[i].p, bytes));
-    buf[i].bytes = bytes;
+    HIPCHK(buf[i].reserve(bytes ? bytes : 8));
     return EKF_OK;
   }
   int init(const ekf_sba_camera* cam, int cn, int cp, int cj, int dev, int slv) {
@@ -4331,8 +4185,7 @@ struct SbaSystem {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipMalloc(&buf[B_RES].p, sizeof(SbaResult) + sizeof(SbaCg)));     // the CG state sits behind the result
-    buf[B_RES].bytes = sizeof(SbaResult) + sizeof(SbaCg);
+    HIPCHK(buf[B_RES].reserve(sizeof(SbaResult) + sizeof(SbaCg)));           // the CG state sits behind the result
     return EKF_OK;
   }
   int nn() const { return (int)nodes.size() / 7; }
@@ -4432,7 +4285,7 @@ struct SbaSystem {
       return rc;
     }
     auto up = [&](int i, const void* src, size_t bytes) -> int {
-      if (bytes) HIPCHK(hipMemcpyAsync(buf[i].p, src, bytes, hipMemcpyHostToDevice, stream));
+      if (bytes) HIPCHK(hipMemcpyAsync(buf[i], src, bytes, hipMemcpyHostToDevice, stream));
       return EKF_OK;
     };
     if ((rc = up(B_POFF, poff.data(), I * poff.size())) || (rc = up(B_PNODE, pnode.data(), I * P)) ||
@@ -4451,9 +4304,9 @@ struct SbaSystem {
   int upload_state() {
     int rc;
     if (dirty && (rc = build())) return rc;
-    HIPCHK(hipMemcpyAsync(buf[B_NODES].p, nodes.data(), sizeof(double) * nodes.size(), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(buf[B_NODES], nodes.data(), sizeof(double) * nodes.size(), hipMemcpyHostToDevice, stream));
     if (!points.empty())
-      HIPCHK(hipMemcpyAsync(buf[B_PTS].p, points.data(), sizeof(double) * points.size(), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(buf[B_PTS], points.data(), sizeof(double) * points.size(), hipMemcpyHostToDevice, stream));
     return EKF_OK;
   }
   static int blocks(int n, int t = 256) { return (n + t - 1) / t; }
@@ -4471,16 +4324,16 @@ struct SbaSystem {
   }
   int read_result(SbaResult* r, SbaCg* cg = nullptr) {
     struct { SbaResult r; SbaCg cg; } both;        // one copy: the CG state sits behind the result
-    HIPCHK(hipMemcpyAsync(&both, buf[B_RES].p, cg ? sizeof(both) : sizeof(SbaResult), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&both, buf[B_RES], cg ? sizeof(both) : sizeof(SbaResult), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     *r = both.r;
     if (cg) *cg = both.cg;
     return EKF_OK;
   }
   int download_state() {
-    HIPCHK(hipMemcpyAsync(nodes.data(), buf[B_NODES].p, sizeof(double) * nodes.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(nodes.data(), buf[B_NODES], sizeof(double) * nodes.size(), hipMemcpyDeviceToHost, stream));
     if (!points.empty())
-      HIPCHK(hipMemcpyAsync(points.data(), buf[B_PTS].p, sizeof(double) * points.size(), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(points.data(), buf[B_PTS], sizeof(double) * points.size(), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     return EKF_OK;
   }
@@ -4518,7 +4371,7 @@ struct SbaSystem {
     *n = (int)r.cost;
     if (mark_them && *n > 0) {
       std::vector<unsigned char> valid(P);
-      HIPCHK(hipMemcpyAsync(valid.data(), buf[B_VALID].p, P, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(valid.data(), buf[B_VALID], P, hipMemcpyDeviceToHost, stream));
       HIPCHK(hipStreamSynchronize(stream));
       int k = 0;
       for (auto& e : prj) e.second.valid = valid[k++] != 0;
@@ -4634,7 +4487,7 @@ struct SbaSystem {
                                                   dp<int>(B_PNODE), dp<double>(B_UV), dp<unsigned char>(B_VALID), huber, M,
                                                   K, lam, dp<double>(B_PRJ), dp<double>(B_TPS));
       mark(2);
-      if (!pcg()) HIPCHK(hipMemsetAsync(buf[B_A].p, 0, sizeof(double) * npad * npad, stream));
+      if (!pcg()) HIPCHK(hipMemsetAsync(buf[B_A], 0, sizeof(double) * npad * npad, stream));
       k_sba_rhs<<<blocks(n6), 256, 0, stream>>>(dp<int>(B_COFF), dp<int>(B_CPRJ), dp<int>(B_PPOINT), dp<double>(B_PRJ),
                                                 dp<double>(B_TPS), nfree, dp<double>(B_B));
       if (pcg()) {
@@ -4649,7 +4502,7 @@ struct SbaSystem {
           k_sba_pairs<<<npairs, 64, 0, stream>>>(dp<int>(B_PAIR_AB), dp<int>(B_PAIR_OFF), dp<int>(B_ITEMS), dp<double>(B_PRJ),
                                                  dp<double>(B_A), npad);
         k_sba_diag<<<blocks(npad), 256, 0, stream>>>(dp<double>(B_A), npad, n6, npad, dp<int>(B_EMPTY), lam);
-        HIPCHK(hipMemcpyAsync(buf[B_L].p, buf[B_A].p, sizeof(double) * npad * npad, hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemcpyAsync(buf[B_L], buf[B_A], sizeof(double) * npad * npad, hipMemcpyDeviceToDevice, stream));
         mark(3);
         sba_chol_f64(dp<double>(B_L), npad, npad, dp<double>(B_DINV), &dp<SbaResult>(B_RES)->status, stream);
         k_sba_trsv<<<1, 1024, 0, stream>>>(dp<double>(B_L), npad, n6, dp<double>(B_B), dp<double>(B_X));
@@ -4698,8 +4551,8 @@ struct SbaSystem {
       } else {
         lambda *= laminc;
         laminc *= 2.0;
-        HIPCHK(hipMemcpyAsync(buf[B_NODES].p, buf[B_OLDN].p, sizeof(double) * 7 * N, hipMemcpyDeviceToDevice, stream));
-        HIPCHK(hipMemcpyAsync(buf[B_PTS].p, buf[B_OLDP].p, sizeof(double) * 3 * M, hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemcpyAsync(buf[B_NODES], buf[B_OLDN], sizeof(double) * 7 * N, hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemcpyAsync(buf[B_PTS], buf[B_OLDP], sizeof(double) * 3 * M, hipMemcpyDeviceToDevice, stream));
         acc = 0;                                   // the restored state's cost is `cost` (same kernels, same data)
       }
       const double row[5] = {before, newcost, lambda, double(acc), r.x2};

@@ -148,14 +148,14 @@ struct KfSelector {
   int device = 0;
   float move_thresh = 18.f;             // MoveThresh (monoslam_ransac.cpp:195)
   int keep_current = 0;                 // EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS
-  KfState* d_state = nullptr;           // two copies; `parity` is the live one
-  KfRecord* d_rec = nullptr;
+  DevBuf<KfState> d_state;              // two copies; `parity` is the live one
+  DevBuf<KfRecord> d_rec;
   int parity = 0;
-  unsigned char *d_cand = nullptr, *d_emit = nullptr;
+  DevBuf<unsigned char> d_cand, d_emit;
   int img_w = 0, img_h = 0;
   bool cand_has_image = false, emit_has_image = false, have_emit = false;
   // ekf_keyframe_create_raw: the same two slots for the camera's own frame (raw_w x raw_h x raw_c bytes)
-  unsigned char *d_cand_raw = nullptr, *d_emit_raw = nullptr;
+  DevBuf<unsigned char> d_cand_raw, d_emit_raw;
   int raw_w = 0, raw_h = 0, raw_c = 0;
   bool cand_has_raw = false, emit_has_raw = false;
   std::vector<int> cand_rows, emit_rows;                // 3 ints per row
@@ -172,17 +172,8 @@ struct KfSelector {
     s.min_cov = kKfMinCovInit;
     return s;
   }
-  ~KfSelector() {
-    if (!d_state && !d_rec && !d_cand && !d_emit && !d_cand_raw && !d_emit_raw && !rect.d_img && !rect.d_pts) return;
-    hipSetDevice(device);
-    rect.release();
-    if (d_state) hipFree(d_state);
-    if (d_rec) hipFree(d_rec);
-    if (d_cand) hipFree(d_cand);
-    if (d_emit) hipFree(d_emit);
-    if (d_cand_raw) hipFree(d_cand_raw);
-    if (d_emit_raw) hipFree(d_emit_raw);
-  }
+  // (the buffers are members and go after this body, on the selector's device; d_state is the first one create allocates)
+  ~KfSelector() { if (d_state) hipSetDevice(device); }
 };
 
 }  // namespace ekf

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstddef>
 
+#include "ekf_buffers.hpp"
 #include "ekf_math.hpp"
 
 namespace ekf {
@@ -135,30 +136,15 @@ __global__ void __launch_bounds__(64) k_undistort_pixels(const double* __restric
 // Grow-only device scratch of one owner (a filter, a key-frame selector): the rectified image before its one copy to the
 // host, and the points on their way in and out.  Allocated by the first call that needs it, never per frame.
 struct RectScratch {
-  unsigned char* d_img = nullptr;
-  size_t img_cap = 0;
-  double* d_pts = nullptr;            // n inputs, then n outputs (2 doubles each)
-  size_t pts_cap = 0;                 // points
-  void release() {
-    if (d_img) hipFree(d_img);
-    if (d_pts) hipFree(d_pts);
-    d_img = nullptr; d_pts = nullptr;
-    img_cap = pts_cap = 0;
-  }
+  DevBuf<unsigned char> d_img;
+  DevBuf<double> d_pts;               // n inputs, then n outputs (2 doubles each)
 };
 
 // src (W x H x C, tight, device) -> rectified, in rs.d_img: the one launch, on `stream`.
 inline hipError_t rectify_launch(RectScratch& rs, hipStream_t stream, const unsigned char* d_src, int W, int H, int C,
                                  const RectCam& c) {
-  const size_t bytes = (size_t)W * C * H;
-  hipError_t e;
-  if (bytes > rs.img_cap) {
-    if (rs.d_img) { if ((e = hipFree(rs.d_img)) != hipSuccess) return e; }
-    rs.d_img = nullptr;
-    rs.img_cap = 0;
-    if ((e = hipMalloc(&rs.d_img, bytes)) != hipSuccess) return e;
-    rs.img_cap = bytes;
-  }
+  const hipError_t e = rs.d_img.reserve((size_t)W * C * H);
+  if (e != hipSuccess) return e;
   const RectifyArgs a{d_src, rs.d_img, W, H, c};
   const size_t npix = (size_t)W * H;
   const int grid = (int)std::min<size_t>((npix + 255) / 256, 1024);
@@ -178,13 +164,7 @@ inline hipError_t rectified_to_host(RectScratch& rs, hipStream_t stream, int W, 
 inline hipError_t undistort_to_host(RectScratch& rs, hipStream_t stream, const double* uv, int n, const RectCam& c, double* out) {
   if (n <= 0) return hipSuccess;
   hipError_t e;
-  if ((size_t)n > rs.pts_cap) {
-    if (rs.d_pts) { if ((e = hipFree(rs.d_pts)) != hipSuccess) return e; }
-    rs.d_pts = nullptr;
-    rs.pts_cap = 0;
-    if ((e = hipMalloc(&rs.d_pts, (size_t)n * 4 * sizeof(double))) != hipSuccess) return e;
-    rs.pts_cap = (size_t)n;
-  }
+  if ((e = rs.d_pts.reserve((size_t)n * 4)) != hipSuccess) return e;
   double* d_in = rs.d_pts;
   double* d_out = rs.d_pts + 2 * (size_t)n;
   const size_t bytes = (size_t)n * 2 * sizeof(double);
