@@ -13,3 +13,4 @@ from .capi import (EkfConfig, EkfError, LIB_PATH, declared_symbols, load_library
 from .vslam_filter import VSlamFilter, kinect_config, sim_config  # noqa: F401
 from .sba import BundleAdjuster, REFERENCE_SBA_CAMERA, sba_add  # noqa: F401
 from .keyframes import KeyframeSelector, KeyframeRecorder, KeyframeRecord, KeyframeResult  # noqa: F401
+from .dense import DenseStereo, DepthMap, depth_maps_from_recording  # noqa: F401

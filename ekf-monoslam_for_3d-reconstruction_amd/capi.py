@@ -171,6 +171,20 @@ _PROTOS = {
     "ekf_undistort_pixels": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "ekf_keyframe_get_image_rectified": (C.c_int, [_P, C.c_int, _P, C.c_int]),
     "ekf_keyframe_get_emitted_rectified": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
+    "ekf_dense_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "ekf_dense_destroy": (None, [_P]),
+    "ekf_dense_last_error": (C.c_char_p, [_P]),
+    "ekf_dense_set_view": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    "ekf_dense_set_view_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    "ekf_dense_set_view_from_keyframe": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "ekf_dense_set_pose": (C.c_int, [_P, C.c_int, _P]),
+    "ekf_dense_get_view": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    "ekf_dense_sweep": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "ekf_dense_filter": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_int]),
+    "ekf_dense_get_depth": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "ekf_dense_get_points": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "ekf_dense_profile": (C.c_int, [_P, C.c_int]),
+    "ekf_dense_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -30,6 +30,7 @@
 #include "ekf_sba.hpp"
 #include "ekf_rectify.hpp"
 #include "ekf_keyframe.hpp"
+#include "ekf_dense_stereo.hpp"
 
 namespace ekf {
 
@@ -5363,6 +5364,290 @@ int ekf_keyframe_reset(ekf_keyframe* s) {
   k->cand_has_image = k->emit_has_image = k->have_emit = false;
   k->cand_has_raw = k->emit_has_raw = false;
   k->emitted = ekf::KfRecord{};
+  return EKF_OK;
+}
+
+
+// ---- dense plane-sweep depth maps ----------------------------------------------------------------------
+struct ekf_dense { ekf::DenseStereo* impl; };
+
+int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense** out) {
+  if (!out) return EKF_ERR_ARG;
+  *out = nullptr;
+  if (width < 1 || height < 1 || width > ekf::kDenseMaxDim || height > ekf::kDenseMaxDim || max_views < 1 ||
+      max_views > ekf::kDenseMaxViews) {
+    ekf::g_create_error = "ekf_dense_create: 1 <= width, height <= 8192 and 1 <= max_views <= 16";
+    return EKF_ERR_ARG;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    ekf::g_create_error = "ekf_dense_create: no HIP device (this library has no CPU fallback)";
+    return EKF_ERR_DEVICE;
+  }
+  auto* d = new ekf::DenseStereo();
+  d->device = device;
+  d->W = width;
+  d->H = height;
+  hipError_t e = hipSetDevice(device);
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&d->ev[i]);
+  if (e != hipSuccess) {
+    ekf::g_create_error = std::string("ekf_dense_create: ") + hipGetErrorString(e);
+    delete d;
+    return EKF_ERR_DEVICE;
+  }
+  d->max_views = max_views;
+  d->v.resize((size_t)max_views);
+  *out = new ekf_dense{d};
+  return EKF_OK;
+}
+
+void ekf_dense_destroy(ekf_dense* h) {
+  if (!h) return;
+  delete h->impl;
+  delete h;
+}
+
+const char* ekf_dense_last_error(const ekf_dense* h) {
+  if (!h) return ekf::g_create_error.c_str();
+  return h->impl->err.c_str();
+}
+
+// slot in range, K finite with fx, fy > 0 (when given), pose7 a pose: what every set_view* checks before the device
+static int dense_view_args(ekf::DenseStereo* d, const char* who, int slot, const double* K, const double* pose7, double t[3],
+                           double R[9], double q[4]) {
+  if (slot < 0 || slot >= d->max_views || !pose7 || !ekf::dense_pose(pose7, t, R, q) ||
+      (K && !(sba_finite(K, 4) && K[0] > 0.0 && K[1] > 0.0))) {
+    d->err = std::string(who) + ": slot in 0..max_views-1, K finite with fx, fy > 0, pose7 finite with q != 0";
+    return EKF_ERR_ARG;
+  }
+  return EKF_OK;
+}
+
+static void dense_commit(ekf::DenseView& v, const double* K, const double t[3], const double R[9], const double q[4]) {
+  if (K) std::copy(K, K + 4, v.K);
+  std::copy(q, q + 4, v.q);
+  std::copy(t, t + 3, v.t);
+  std::copy(R, R + 9, v.R);
+  v.swept = v.filtered = false;
+}
+
+static int dense_set_view(ekf_dense* h, const char* who, int slot, const void* img, int pitch, const double* K,
+                          const double* pose7, bool device_src) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  double t[3], R[9], q[4];
+  if (!img || !K || pitch < d->W) {
+    d->err = std::string(who) + ": img and K must not be NULL and pitch >= width";
+    return EKF_ERR_ARG;
+  }
+  const int rc = dense_view_args(d, who, slot, K, pose7, t, R, q);
+  if (rc != EKF_OK) return rc;
+  std::string& err = d->err;
+  ekf::DenseView& v = d->v[slot];
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(v.img.reserve(d->npix()));
+  v.set = false;
+  if (device_src)
+    HIPCHK(hipMemcpy2DAsync(v.img, (size_t)d->W, img, (size_t)pitch, (size_t)d->W, (size_t)d->H, hipMemcpyDeviceToDevice, nullptr));
+  else
+    HIPCHK(hipMemcpy2D(v.img, (size_t)d->W, img, (size_t)pitch, (size_t)d->W, (size_t)d->H, hipMemcpyHostToDevice));
+  dense_commit(v, K, t, R, q);
+  v.set = true;
+  return EKF_OK;
+}
+
+int ekf_dense_set_view(ekf_dense* h, int slot, const unsigned char* img, int pitch, const double* K, const double* pose7) {
+  return dense_set_view(h, "ekf_dense_set_view", slot, img, pitch, K, pose7, false);
+}
+
+int ekf_dense_set_view_device(ekf_dense* h, int slot, const void* d_img, int pitch, const double* K, const double* pose7) {
+  return dense_set_view(h, "ekf_dense_set_view_device", slot, d_img, pitch, K, pose7, true);
+}
+
+int ekf_dense_set_view_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, int raw, const double* pose7) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  double t[3], R[9], q[4];
+  if (!selector || (raw != 0 && raw != 1)) {
+    d->err = "ekf_dense_set_view_from_keyframe: a selector, and raw is 0 or 1";
+    return EKF_ERR_ARG;
+  }
+  const int rc = dense_view_args(d, "ekf_dense_set_view_from_keyframe", slot, nullptr, pose7, t, R, q);
+  if (rc != EKF_OK) return rc;
+  auto* k = selector->impl;
+  const int W = raw ? k->raw_w : k->img_w, H = raw ? k->raw_h : k->img_h;
+  if (W != d->W || H != d->H || (raw && k->raw_c != 1) || k->device != d->device) {
+    d->err = "ekf_dense_set_view_from_keyframe: the selector's image at that resolution must have the handle's size, one channel "
+             "and the handle's device";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit || !(raw ? k->emit_has_raw : k->emit_has_image) || (raw && k->scale < 1)) {
+    d->err = "ekf_dense_set_view_from_keyframe: no emitted key frame with such an image (the rules of ekf_keyframe_get_image / "
+             "ekf_keyframe_get_raw_image)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  ekf::DenseView& v = d->v[slot];
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(v.img.reserve(d->npix()));
+  v.set = false;
+  const ekf::RectCam c = ekf::rect_cam(k->cam, raw ? k->scale : 1);
+  const ekf::RectifyArgs a{raw ? k->d_emit_raw : k->d_emit, v.img, W, H, c};
+  const int grid = (int)std::min<size_t>((d->npix() + 255) / 256, 1024);
+  ekf::k_frame_rectify<1><<<grid, 256, 0, nullptr>>>(a);
+  HIPCHK(hipGetLastError());
+  double K[4];
+  ekf::rect_camera(c, K);
+  dense_commit(v, K, t, R, q);
+  v.set = true;
+  return EKF_OK;
+}
+
+int ekf_dense_set_pose(ekf_dense* h, int slot, const double* pose7) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  double t[3], R[9], q[4];
+  const int rc = dense_view_args(d, "ekf_dense_set_pose", slot, nullptr, pose7, t, R, q);
+  if (rc != EKF_OK) return rc;
+  if (!d->v[slot].set) {
+    d->err = "ekf_dense_set_pose: the slot is not set";
+    return EKF_ERR_ARG;
+  }
+  dense_commit(d->v[slot], nullptr, t, R, q);
+  return EKF_OK;
+}
+
+int ekf_dense_get_view(const ekf_dense* h, int slot, unsigned char* img, int pitch, double* K, double* pose7) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (slot < 0 || slot >= d->max_views || (img && pitch < d->W)) {
+    d->err = "ekf_dense_get_view: slot in 0..max_views-1 and pitch >= width";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set) {
+    d->err = "ekf_dense_get_view: the slot is not set";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  if (img) {
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipMemcpy2D(img, (size_t)pitch, v.img, (size_t)d->W, (size_t)d->W, (size_t)d->H, hipMemcpyDeviceToHost));
+  }
+  if (K) std::copy(v.K, v.K + 4, K);
+  if (pose7) {
+    std::copy(v.t, v.t + 3, pose7);
+    std::copy(v.q, v.q + 4, pose7 + 3);
+  }
+  return EKF_OK;
+}
+
+// ref and src[]: in range, set, ref not among src, no slot named twice, 1 <= n_src <= 8
+static bool dense_slots_ok(const ekf::DenseStereo* d, int ref, const int* src, int n_src) {
+  if (ref < 0 || ref >= d->max_views || !d->v[ref].set || !src || n_src < 1 || n_src > ekf::kDenseMaxSrc) return false;
+  for (int i = 0; i < n_src; ++i) {
+    if (src[i] < 0 || src[i] >= d->max_views || src[i] == ref || !d->v[src[i]].set) return false;
+    for (int j = 0; j < i; ++j)
+      if (src[j] == src[i]) return false;
+  }
+  return true;
+}
+
+int ekf_dense_sweep(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                    int trunc) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (!dense_slots_ok(d, ref, src, n_src) || planes < 2 || planes > ekf::kDenseMaxPlanes || radius < 0 ||
+      radius > ekf::kDenseMaxRadius || trunc < 1 || trunc > 255 || !std::isfinite(w_min) || !std::isfinite(w_max) ||
+      !(w_min > 0.0) || !(w_min < w_max)) {
+    d->err = "ekf_dense_sweep: ref and 1..8 other, distinct source slots, all set; planes 2..1024, radius 0..4, trunc 1..255, "
+             "0 < w_min < w_max finite";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(d->sweep(ref, src, n_src, w_min, w_max, planes, radius, trunc));
+  return EKF_OK;
+}
+
+int ekf_dense_filter(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (!dense_slots_ok(d, ref, src, n_src) || !std::isfinite(rel_tol) || rel_tol < 0.0 || min_agree < 1 || min_agree > n_src) {
+    d->err = "ekf_dense_filter: ref and 1..8 other, distinct source slots, all set; rel_tol finite and >= 0, min_agree 1..n_src";
+    return EKF_ERR_ARG;
+  }
+  bool swept = d->v[ref].swept;
+  for (int i = 0; i < n_src; ++i) swept = swept && d->v[src[i]].swept;
+  if (!swept) {
+    d->err = "ekf_dense_filter: a named slot has not been swept since its image or pose last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(d->filter_points(ref, src, n_src, rel_tol, min_agree, false, false));
+  return EKF_OK;
+}
+
+// slot in range with the asked-for map: EKF_OK, or the code with the message set
+static int dense_map_ok(ekf::DenseStereo* d, const char* who, int slot, int filtered) {
+  if (slot < 0 || slot >= d->max_views || (filtered != 0 && filtered != 1)) {
+    d->err = std::string(who) + ": slot in 0..max_views-1 and filtered is 0 or 1";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set || !v.swept || (filtered && !v.filtered)) {
+    d->err = std::string(who) + ": the slot has no such map (ekf_dense_sweep, and ekf_dense_filter for filtered = 1, after the "
+             "last change of its image or pose)";
+    return EKF_ERR_STATE;
+  }
+  return EKF_OK;
+}
+
+int ekf_dense_get_depth(ekf_dense* h, int slot, int filtered, float* depth, int* plane, unsigned int* cost,
+                        unsigned char* views) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  const int rc = dense_map_ok(d, "ekf_dense_get_depth", slot, filtered);
+  if (rc != EKF_OK) return rc;
+  std::string& err = d->err;
+  const ekf::DenseView& v = d->v[slot];
+  const size_t n = d->npix();
+  HIPCHK(hipSetDevice(d->device));
+  if (depth) HIPCHK(hipMemcpy(depth, filtered ? v.fdepth : v.depth, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (plane) HIPCHK(hipMemcpy(plane, filtered ? v.fplane : v.plane, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (cost) HIPCHK(hipMemcpy(cost, v.cost, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (views) HIPCHK(hipMemcpy(views, v.nviews, n, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_dense_get_points(ekf_dense* h, int slot, int filtered, double* xyz) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (!xyz) {
+    d->err = "ekf_dense_get_points: xyz must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const int rc = dense_map_ok(d, "ekf_dense_get_points", slot, filtered);
+  if (rc != EKF_OK) return rc;
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(d->filter_points(slot, nullptr, 0, 0.0, 0, filtered != 0, true));
+  HIPCHK(hipMemcpy(xyz, d->d_xyz, d->npix() * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_dense_profile(ekf_dense* h, int enable) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  d->profile = enable != 0;
+  for (int i = 0; i < 2; ++i) { d->prof_ms[i] = 0.0; d->prof_cnt[i] = 0; }
+  return EKF_OK;
+}
+
+int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  for (int i = 0; i < 2; ++i) { kernel_ms[i] = h->impl->prof_ms[i]; launches[i] = h->impl->prof_cnt[i]; }
   return EKF_OK;
 }
 

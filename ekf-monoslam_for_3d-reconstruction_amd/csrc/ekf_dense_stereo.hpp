@@ -1,0 +1,368 @@
+// Dense plane-sweep depth maps for key frames: up to 16 posed pinhole views of one size on the device, a
+// sweep of D fronto-parallel planes (uniform in inverse depth) of a reference view against 1..8 source views, a geometric
+// consistency filter over the swept maps, and the back-projection to world points.  The reference has no counterpart (its
+// README defers the dense step to a second program); the arithmetic is pinned here and restated in numpy by
+// tests/dense_oracle.py:
+//   - every coordinate operation is fp64, rounded once, in the written left-to-right order; contraction is off in every
+//     function below (host and device), as in ekf_rectify.hpp;
+//   - the image sample is the 5-bit bilinear blend of §14.1; costs are integers, every sum has one fixed order, no atomics.
+// Nothing here touches a filter, counts as a launch kind or runs a collective.
+#pragma once
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <string>
+#include <vector>
+
+// EKF_DENSE_KERNELS_ONLY: the structs, the two kernel bodies and dense_pose alone, for tools/dense_host_check.cpp, which
+// runs the kernels lane by lane on the host and supplies threadIdx, __syncthreads and the like itself.
+#ifndef EKF_DENSE_KERNELS_ONLY
+#include <hip/hip_runtime.h>
+
+#include "ekf_buffers.hpp"
+#endif
+
+namespace ekf {
+
+constexpr int kDenseMaxViews = 16, kDenseMaxSrc = 8, kDenseMaxPlanes = 1024, kDenseMaxRadius = 4, kDenseMaxDim = 8192;
+// The output tile of one workgroup and its halo.  32 x 16 on 256 lanes: a lane owns the two pixels (tx, ty) and (tx, ty + 8),
+// a row of the tile is one half-wave (the LDS passes below read 32 consecutive words per half-wave: conflict-free), and
+// the halo of radius 4 costs 960 / 512 = 1.9 warps per output pixel where a 16 x 16 tile would cost 2.25.
+constexpr int kDenseTW = 32, kDenseTH = 16;
+constexpr int kDenseHW = kDenseTW + 2 * kDenseMaxRadius, kDenseHH = kDenseTH + 2 * kDenseMaxRadius;
+constexpr int kDenseHaloPerLane = (kDenseHW * kDenseHH + 255) / 256;      // 4
+
+struct DenseSrc {
+  const unsigned char* img;           // H rows of W bytes, tight
+  const float* depth;                 // the source's swept depth (the filter only)
+  double fx, fy, cx, cy;
+  double A[9];                        // R_v^T R_r, row-major
+  double b[3];                        // R_v^T (t_r - t_v)
+};
+
+struct SweepArgs {
+  const unsigned char* ref;
+  float* depth;
+  int* plane;
+  unsigned* cost;
+  unsigned char* views;
+  int W, H, D, radius, trunc, n_src;
+  double fx, fy, cx, cy;              // the reference view's K
+  double w_min, step;
+  DenseSrc s[kDenseMaxSrc];
+};
+
+// One launch per depth map, one workgroup per 32 x 16 tile.  A halo pixel belongs to one lane for the whole launch, so the
+// reference tile with its halo stays in that lane's registers (grey value and ray), not in LDS.  Per plane: every lane
+// warps its (at most 4) halo pixels into every source view and writes the truncated absolute
+// differences, summed over the views, to LDS as one word (the count of valid warps in the upper half); a horizontal and a
+// vertical pass give the window sum.  The pixel costs are integers, so summing over the views before the window gives the
+// number that a window sum per view would, with one pair of LDS passes per plane, not one per view.  Registers carry, per
+// owned pixel, C of the previous plane, the best C with its plane, its C- and C+ and its count of valid views: the cost
+// volume never leaves the CU.
+__global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) {
+#pragma clang fp contract(off)
+  __shared__ int s_c[kDenseHH][kDenseHW + 1];
+  __shared__ int s_h[kDenseHH][kDenseTW + 1];
+  const int tid = threadIdx.x;
+  const int r = a.radius, hw = kDenseTW + 2 * r, hh = kDenseTH + 2 * r, nh = hw * hh;
+  const int x0 = (int)blockIdx.x * kDenseTW - r, y0 = (int)blockIdx.y * kDenseTH - r;
+  const int W = a.W, H = a.H;
+  const double qx_max = (double)(32 * (W - 1)), qy_max = (double)(32 * (H - 1));
+
+  // the lane's halo pixels: position in the halo, ray and reference grey value, fixed for the launch
+  int h_off[kDenseHaloPerLane], h_ref[kDenseHaloPerLane];                 // h_off < 0: none, or outside the image
+  double h_x[kDenseHaloPerLane], h_y[kDenseHaloPerLane];
+#pragma unroll
+  for (int i = 0; i < kDenseHaloPerLane; ++i) {
+    const int h = tid + 256 * i;
+    const int hy = h / hw, hx = h - hy * hw;
+    const int X = x0 + hx, Y = y0 + hy;
+    const bool in = h < nh && X >= 0 && X < W && Y >= 0 && Y < H;
+    h_off[i] = h < nh ? (in ? hy * (kDenseHW + 1) + hx : -1 - (hy * (kDenseHW + 1) + hx)) : INT_MIN;
+    h_ref[i] = in ? (int)a.ref[(size_t)Y * W + X] : 0;
+    h_x[i] = ((double)X - a.cx) / a.fx;
+    h_y[i] = ((double)Y - a.cy) / a.fy;
+  }
+  const int tx = tid & 31, ty = tid >> 5;
+  int* const sc = &s_c[0][0];
+
+  int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
+  for (int k = 0; k < a.D; ++k) {
+    const double z = 1.0 / (a.w_min + (double)k * a.step);
+#pragma unroll
+    for (int i = 0; i < kDenseHaloPerLane; ++i) {
+      if (h_off[i] == INT_MIN) continue;
+      if (h_off[i] < 0) {                                                   // a window position outside the image: nothing
+        sc[-1 - h_off[i]] = 0;
+        continue;
+      }
+      int csum = 0, nv = 0;
+      for (int v = 0; v < a.n_src; ++v) {
+        const DenseSrc& s = a.s[v];
+        const double a0 = s.A[0] * h_x[i] + s.A[1] * h_y[i] + s.A[2];
+        const double a1 = s.A[3] * h_x[i] + s.A[4] * h_y[i] + s.A[5];
+        const double a2 = s.A[6] * h_x[i] + s.A[7] * h_y[i] + s.A[8];
+        const double Q0 = z * a0 + s.b[0];
+        const double Q1 = z * a1 + s.b[1];
+        const double Q2 = z * a2 + s.b[2];
+        int c = a.trunc;
+        if (Q2 > 0.0) {
+          const double sx = s.fx * (Q0 / Q2) + s.cx;
+          const double sy = s.fy * (Q1 / Q2) + s.cy;
+          const double fqx = floor(sx * 32.0 + 0.5), fqy = floor(sy * 32.0 + 0.5);
+          if (fqx >= 0.0 && fqx <= qx_max && fqy >= 0.0 && fqy <= qy_max) {   // (a NaN fails)
+            const int qx = (int)fqx, qy = (int)fqy;
+            const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;   // ix in [0, W - 1], iy in [0, H - 1]
+            const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);       // weight 0 where clamped (ax = 0 there)
+            const unsigned char* r0 = s.img + (size_t)iy * W;
+            const unsigned char* r1 = s.img + (size_t)iy1 * W;
+            const int g = ((32 - ax) * (32 - ay) * (int)r0[ix] + ax * (32 - ay) * (int)r0[ix1] + (32 - ax) * ay * (int)r1[ix] +
+                           ax * ay * (int)r1[ix1] + 512) >> 10;
+            c = min(abs(h_ref[i] - g), a.trunc);
+            ++nv;
+          }
+        }
+        csum += c;
+      }
+      sc[h_off[i]] = csum | (nv << 16);                                     // csum <= 8 * 255
+    }
+    __syncthreads();
+    // horizontal pass over the hh halo rows, 32 columns each; the valid count of the owned pixels is read here, before the
+    // barrier after which other lanes may overwrite s_c for the next plane
+    for (int e = tid; e < hh * kDenseTW; e += 256) {
+      const int row = e >> 5, col = e & 31;
+      int sum = 0;
+      for (int d = 0; d <= 2 * r; ++d) sum += s_c[row][col + d] & 0xffff;
+      s_h[row][col] = sum;
+    }
+    const int nv0 = s_c[ty + r][tx + r] >> 16, nv1 = s_c[ty + 8 + r][tx + r] >> 16;
+    __syncthreads();
+    // vertical pass: the two owned pixels (the next write of s_h comes after the next plane's first barrier)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int oy = ty + 8 * j;
+      int C = 0;
+      for (int d = 0; d <= 2 * r; ++d) C += s_h[oy + d][tx];
+      // selects, not branches: the plane after the best one delivers its C+ (bestK = -2 before plane 0: never pending),
+      // a strictly smaller C takes over (bestC starts at INT_MAX, so plane 0 always does)
+      const bool pending = bestK[j] == k - 1, better = C < bestC[j];
+      bestP[j] = (pending || better) ? C : bestP[j];
+      bestM[j] = better ? prevC[j] : bestM[j];
+      bestV[j] = better ? (j == 0 ? nv0 : nv1) : bestV[j];
+      bestK[j] = better ? k : bestK[j];
+      bestC[j] = better ? C : bestC[j];
+      prevC[j] = C;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
+    if (X >= W || Y >= H) continue;
+    const int ks = bestK[j];
+    double delta = 0.0;
+    if (ks > 0 && ks < a.D - 1) {
+      const int den = bestM[j] - 2 * bestC[j] + bestP[j];                   // |.| <= 4 * 81 * 8 * 255
+      if (den > 0) delta = (double)(bestM[j] - bestP[j]) / (2.0 * (double)den);
+    }
+    const double w = a.w_min + ((double)ks + delta) * a.step;
+    const bool none = bestV[j] == 0;
+    const size_t o = (size_t)Y * W + X;
+    a.depth[o] = none ? 0.f : (float)(1.0 / w);
+    a.plane[o] = none ? -1 : ks;
+    a.cost[o] = (unsigned)bestC[j];
+    a.views[o] = (unsigned char)bestV[j];
+  }
+}
+
+struct FilterArgs {
+  const float* depth;                 // the reference view's depth (swept, or filtered for the points of a filtered map)
+  const int* plane;
+  float* out_depth;                   // NULL: no filter output
+  int* out_plane;
+  double* xyz;                        // NULL: no points
+  int W, H, n_src, min_agree;         // n_src = 0: the depth passes through
+  double rel_tol;
+  double fx, fy, cx, cy;
+  double R[9], t[3];                  // the reference view's pose (the points only)
+  DenseSrc s[kDenseMaxSrc];
+};
+
+// One lane per pixel: the geometric filter against the swept depths of the sources, and / or the back-projection.
+__global__ void __launch_bounds__(256) k_depth_filter_points(FilterArgs a) {
+#pragma clang fp contract(off)
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned npix = (unsigned)a.W * (unsigned)a.H;
+  if (i >= npix) return;
+  const int Y = (int)(i / (unsigned)a.W), X = (int)(i % (unsigned)a.W);
+  const float zf = a.depth[i];
+  const double z = (double)zf;
+  const double x = ((double)X - a.cx) / a.fx;
+  const double y = ((double)Y - a.cy) / a.fy;
+  bool keep = zf > 0.f;
+  if (keep && a.n_src > 0) {
+    int agree = 0;
+    for (int v = 0; v < a.n_src; ++v) {
+      const DenseSrc& s = a.s[v];
+      const double a0 = s.A[0] * x + s.A[1] * y + s.A[2];
+      const double a1 = s.A[3] * x + s.A[4] * y + s.A[5];
+      const double a2 = s.A[6] * x + s.A[7] * y + s.A[8];
+      const double Q0 = z * a0 + s.b[0];
+      const double Q1 = z * a1 + s.b[1];
+      const double Q2 = z * a2 + s.b[2];
+      if (!(Q2 > 0.0)) continue;
+      const double sx = s.fx * (Q0 / Q2) + s.cx;
+      const double sy = s.fy * (Q1 / Q2) + s.cy;
+      const double fjx = floor(sx + 0.5), fjy = floor(sy + 0.5);
+      if (!(fjx >= 0.0 && fjx <= (double)(a.W - 1) && fjy >= 0.0 && fjy <= (double)(a.H - 1))) continue;
+      const double zs = (double)s.depth[(size_t)(int)fjy * a.W + (int)fjx];
+      if (zs != 0.0 && fabs(Q2 - zs) <= a.rel_tol * Q2) ++agree;
+    }
+    keep = agree >= a.min_agree;
+  }
+  if (a.out_depth) {
+    a.out_depth[i] = keep ? zf : 0.f;
+    a.out_plane[i] = keep ? a.plane[i] : -1;
+  }
+  if (a.xyz) {
+    const double nan = __builtin_nan("");
+    const double p0 = z * x, p1 = z * y, p2 = z;
+    double* o = a.xyz + (size_t)i * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = keep ? a.R[3 * c] * p0 + a.R[3 * c + 1] * p1 + a.R[3 * c + 2] * p2 + a.t[c] : nan;
+  }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+// pose7 = (t, q = (w x y z)) -> t, R (camera to world, x_cam = R^T (X - t)) and q / |q|.  false: non-finite, or q = 0.
+inline bool dense_pose(const double* p, double t[3], double R[9], double q[4]) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < 7; ++i)
+    if (!std::isfinite(p[i])) return false;
+  const double n = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+  if (!(n > 0.0) || !std::isfinite(n)) return false;
+  const double w = p[3] / n, x = p[4] / n, y = p[5] / n, z = p[6] / n;
+  t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
+  q[0] = w; q[1] = x; q[2] = y; q[3] = z;
+  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w);       R[2] = 2.0 * (x * z + y * w);
+  R[3] = 2.0 * (x * y + z * w);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
+  R[6] = 2.0 * (x * z - y * w);       R[7] = 2.0 * (y * z + x * w);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+  return true;
+}
+
+#ifndef EKF_DENSE_KERNELS_ONLY
+struct DenseView {
+  DevBuf<unsigned char> img;
+  DevBuf<float> depth, fdepth;
+  DevBuf<int> plane, fplane;
+  DevBuf<unsigned> cost;
+  DevBuf<unsigned char> nviews;
+  double K[4] = {}, t[3] = {}, R[9] = {}, q[4] = {};
+  bool set = false;                   // an image, K and a pose
+  bool swept = false;                 // swept since the image or the pose last changed
+  bool filtered = false;              // filtered since it was last swept
+};
+
+// Host side of one handle (`ekf_dense`).  Everything runs on the default stream of the handle's device, as the rectified
+// getters of a key-frame selector do (§14.4): a view may come from a selector that outlives its filter.
+struct DenseStereo {
+  std::string err;
+  int device = 0, W = 0, H = 0, max_views = 0;
+  std::vector<DenseView> v;
+  DevBuf<double> d_xyz;               // the points on their way to the host (allocated by the first ekf_dense_get_points)
+  bool profile = false;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double prof_ms[2] = {0.0, 0.0};     // k_plane_sweep, k_depth_filter_points
+  long long prof_cnt[2] = {0, 0};
+
+  size_t npix() const { return (size_t)W * H; }
+  ~DenseStereo() {
+    if (max_views) hipSetDevice(device);
+    for (hipEvent_t e : ev)
+      if (e) hipEventDestroy(e);
+  }
+
+  // A (row-major) and b of source view s seen from reference view r
+  void relative(const DenseView& r, const DenseView& s, DenseSrc& o) const {
+#pragma clang fp contract(off)
+    const double d[3] = {r.t[0] - s.t[0], r.t[1] - s.t[1], r.t[2] - s.t[2]};
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) o.A[3 * i + j] = s.R[i] * r.R[j] + s.R[3 + i] * r.R[3 + j] + s.R[6 + i] * r.R[6 + j];
+      o.b[i] = s.R[i] * d[0] + s.R[3 + i] * d[1] + s.R[6 + i] * d[2];
+    }
+    o.fx = s.K[0]; o.fy = s.K[1]; o.cx = s.K[2]; o.cy = s.K[3];
+    o.img = s.img;
+    o.depth = s.depth;
+  }
+
+  hipError_t timed_begin() { return profile ? hipEventRecord(ev[0], nullptr) : hipSuccess; }
+  hipError_t timed_end(int which) {
+    if (!profile) return hipSuccess;
+    hipError_t e = hipEventRecord(ev[1], nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e == hipSuccess) { prof_ms[which] += ms; prof_cnt[which] += 1; }
+    return e;
+  }
+
+  hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc) {
+#pragma clang fp contract(off)
+    DenseView& r = v[ref];
+    hipError_t e;
+    const size_t n = npix();
+    if ((e = r.depth.reserve(n)) != hipSuccess || (e = r.plane.reserve(n)) != hipSuccess ||
+        (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess)
+      return e;
+    SweepArgs a{};
+    a.ref = r.img; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
+    a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
+    a.fx = r.K[0]; a.fy = r.K[1]; a.cx = r.K[2]; a.cy = r.K[3];
+    a.w_min = w_min;
+    a.step = (w_max - w_min) / (double)(D - 1);
+    for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
+    r.swept = r.filtered = false;
+    const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
+    if ((e = timed_begin()) != hipSuccess) return e;
+    k_plane_sweep<<<grid, 256, 0, nullptr>>>(a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = timed_end(0)) != hipSuccess) return e;
+    r.swept = true;
+    return hipSuccess;
+  }
+
+  // The one launch of k_depth_filter_points.  n_src > 0: the filter of view `ref` (swept -> filtered); xyz: the points of
+  // its swept or filtered map, into d_xyz.
+  hipError_t filter_points(int ref, const int* src, int n_src, double rel_tol, int min_agree, bool from_filtered, bool xyz) {
+    DenseView& r = v[ref];
+    hipError_t e;
+    const size_t n = npix();
+    FilterArgs a{};
+    a.depth = from_filtered ? r.fdepth : r.depth;
+    a.plane = from_filtered ? r.fplane : r.plane;
+    if (n_src > 0) {
+      if ((e = r.fdepth.reserve(n)) != hipSuccess || (e = r.fplane.reserve(n)) != hipSuccess) return e;
+      a.out_depth = r.fdepth;
+      a.out_plane = r.fplane;
+      r.filtered = false;
+    }
+    if (xyz) {
+      if ((e = d_xyz.reserve(n * 3)) != hipSuccess) return e;
+      a.xyz = d_xyz;
+    }
+    a.W = W; a.H = H; a.n_src = n_src; a.min_agree = min_agree; a.rel_tol = rel_tol;
+    a.fx = r.K[0]; a.fy = r.K[1]; a.cx = r.K[2]; a.cy = r.K[3];
+    for (int i = 0; i < 9; ++i) a.R[i] = r.R[i];
+    for (int i = 0; i < 3; ++i) a.t[i] = r.t[i];
+    for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
+    if ((e = timed_begin()) != hipSuccess) return e;
+    k_depth_filter_points<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = timed_end(1)) != hipSuccess) return e;
+    if (n_src > 0) r.filtered = true;
+    return hipSuccess;
+  }
+};
+#endif  // EKF_DENSE_KERNELS_ONLY
+
+}  // namespace ekf

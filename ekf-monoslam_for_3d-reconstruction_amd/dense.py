@@ -1,0 +1,232 @@
+"""Dense plane-sweep depth maps for key frames: posed, rectified key frames in, depth maps and world
+points out.  ``DenseStereo`` mirrors the ``ekf_dense_*`` functions; ``depth_maps_from_recording`` drives it over what a
+rectifying ``KeyframeRecorder`` wrote, with the poses ``sba.sba_add`` refined when its ``Nodes_Out.txt`` is given.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import capi, formats
+from .capi import EkfError
+
+MAX_VIEWS, MAX_SOURCES = 16, 8
+
+
+@dataclass
+class DepthMap:
+    """One key frame's result of ``depth_maps_from_recording``."""
+    id: int
+    pose: np.ndarray               # (7,) float64: t, q (w x y z) as it was set
+    sources: tuple                 # ids of the key frames it was swept against
+    depth: np.ndarray              # (H, W) float32, filtered; 0 = none
+    plane: np.ndarray              # (H, W) int32, filtered; -1 = none
+    swept_depth: np.ndarray        # (H, W) float32, before the filter
+    cost: np.ndarray               # (H, W) uint32
+    views: np.ndarray              # (H, W) uint8
+    points: np.ndarray             # (H, W, 3) float64 of the filtered map, NaN where there is no depth
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class DenseStereo:
+    """Up to ``max_views`` (<= 16) pinhole views of one size on the device; slots are 0 .. max_views - 1."""
+
+    def __init__(self, width: int, height: int, max_views: int = MAX_VIEWS, device: int = 0):
+        self._lib = capi.load_library()
+        self._h = C.c_void_p()
+        rc = self._lib.ekf_dense_create(int(width), int(height), int(max_views), int(device), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.ekf_dense_last_error(None)
+            raise EkfError(rc, msg.decode() if msg else "ekf_dense_create failed")
+        self.width, self.height, self.max_views, self.device = int(width), int(height), int(max_views), int(device)
+        self.shape = (self.height, self.width)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.ekf_dense_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = self._lib.ekf_dense_last_error(self._h)
+            raise EkfError(rc, msg.decode() if msg else "")
+
+    # ---- views ----
+    def set_view(self, slot: int, image, K, pose7):
+        """``image``: (height, width) uint8 on the host, or a CUDA/HIP ``torch`` tensor of that shape (no host round trip)."""
+        K = np.ascontiguousarray(K, np.float64).reshape(4)
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
+            if tuple(image.shape) != self.shape or str(image.dtype) != "torch.uint8" or image.stride(1) != 1 or image.stride(0) < self.width:
+                raise ValueError("a device image is (height, width) uint8 with unit column stride and rows at least a width apart")
+            if (image.device.index or 0) != self.device:
+                raise ValueError("the device image lives on device %r, the handle on device %d" % (image.device.index, self.device))
+            self._check(self._lib.ekf_dense_set_view_device(self._h, int(slot), C.c_void_p(image.data_ptr()),
+                                                            int(image.stride(0)), _ptr(K), _ptr(pose)))
+            return
+        img = np.ascontiguousarray(image, np.uint8)
+        if img.shape != self.shape:
+            raise ValueError("image must be (height, width) = %r" % (self.shape,))
+        self._check(self._lib.ekf_dense_set_view(self._h, int(slot), _ptr(img), img.strides[0], _ptr(K), _ptr(pose)))
+
+    def set_view_from_keyframe(self, slot: int, selector, pose7, raw: bool = False):
+        """The selector's last emitted key frame, rectified on the device straight into the slot; K is the selector's
+        rectified camera of that resolution."""
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        self._check(self._lib.ekf_dense_set_view_from_keyframe(self._h, int(slot), selector._h, 1 if raw else 0, _ptr(pose)))
+
+    def set_pose(self, slot: int, pose7):
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        self._check(self._lib.ekf_dense_set_pose(self._h, int(slot), _ptr(pose)))
+
+    def view(self, slot: int):
+        """(image, K, pose7) a set slot holds; q is normalised."""
+        img, K, pose = np.zeros(self.shape, np.uint8), np.zeros(4, np.float64), np.zeros(7, np.float64)
+        self._check(self._lib.ekf_dense_get_view(self._h, int(slot), _ptr(img), img.strides[0], _ptr(K), _ptr(pose)))
+        return img, K, pose
+
+    # ---- the two launches ----
+    def sweep(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 2,
+              trunc: int = 40):
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._check(self._lib.ekf_dense_sweep(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes),
+                                              int(radius), int(trunc)))
+
+    def filter(self, ref: int, sources: Sequence[int], rel_tol: float = 0.01, min_agree: int = 1):
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        self._check(self._lib.ekf_dense_filter(self._h, int(ref), _ptr(src), len(src), float(rel_tol), int(min_agree)))
+
+    # ---- results ----
+    def depth(self, slot: int, filtered: bool = False) -> dict:
+        """depth float32 (0 = none), plane int32 (-1 = none), and of the sweep cost uint32 and views uint8."""
+        out = dict(depth=np.zeros(self.shape, np.float32), plane=np.zeros(self.shape, np.int32),
+                   cost=np.zeros(self.shape, np.uint32), views=np.zeros(self.shape, np.uint8))
+        self._check(self._lib.ekf_dense_get_depth(self._h, int(slot), 1 if filtered else 0, _ptr(out["depth"]), _ptr(out["plane"]),
+                                                  _ptr(out["cost"]), _ptr(out["views"])))
+        return out
+
+    def points(self, slot: int, filtered: bool = False) -> np.ndarray:
+        """(height, width, 3) float64 world points; NaN where there is no depth."""
+        xyz = np.zeros(self.shape + (3,), np.float64)
+        self._check(self._lib.ekf_dense_get_points(self._h, int(slot), 1 if filtered else 0, _ptr(xyz)))
+        return xyz
+
+    def write_ply(self, path: str, slot: int, filtered: bool = True) -> int:
+        """ASCII PLY of the finite points of a slot with the grey value of their pixel; returns their number."""
+        xyz = self.points(slot, filtered)
+        grey = self.view(slot)[0]
+        ok = np.isfinite(xyz).all(axis=2)
+        pts, g = xyz[ok], grey[ok]
+        with open(path, "w") as fh:
+            fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
+                     "property uchar intensity\nend_header\n" % len(pts))
+            for (x, y, z), v in zip(pts, g):
+                fh.write("%.17g %.17g %.17g %d\n" % (x, y, z, int(v)))
+        return len(pts)
+
+    def profile(self, enable: bool = True):
+        self._check(self._lib.ekf_dense_profile(self._h, 1 if enable else 0))
+
+    def get_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the two kernels since the last ``profile()``."""
+        ms, cnt = np.zeros(2, np.float64), np.zeros(2, np.int64)
+        self._check(self._lib.ekf_dense_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {"k_plane_sweep": (float(ms[0]), int(cnt[0])), "k_depth_filter_points": (float(ms[1]), int(cnt[1]))}
+
+
+def read_ply(path: str):
+    """What ``write_ply`` wrote: ((n, 3) float64 points, (n,) uint8 grey values)."""
+    with open(path) as fh:
+        lines = fh.read().splitlines()
+    end = lines.index("end_header")
+    n = int([ln for ln in lines[:end] if ln.startswith("element vertex")][0].split()[2])
+    rows = [ln.split() for ln in lines[end + 1:end + 1 + n]]
+    return (np.array([[float(t) for t in r[:3]] for r in rows], np.float64).reshape(-1, 3),
+            np.array([int(r[3]) for r in rows], np.uint8))
+
+
+def read_pgm(path: str) -> np.ndarray:
+    """Binary P5, 8 bit (what ``keyframes.write_pgm`` writes)."""
+    data = open(path, "rb").read()
+    m = re.match(rb"P5\s+(\d+)\s+(\d+)\s+255\s", data)
+    if not m:
+        raise ValueError("%s is not an 8-bit binary PGM" % path)
+    w, h = int(m.group(1)), int(m.group(2))
+    return np.frombuffer(data[m.end():m.end() + w * h], np.uint8).reshape(h, w).copy()
+
+
+def read_recording(directory: str, nodes_out=None):
+    """(K, ids, poses (n, 7) float64, images) of a recording of ``KeyframeRecorder(rectify=True, images=True)``; the poses
+    are those of ``nodes_and_prjcts.txt`` (float32 widened) unless ``nodes_out`` (``Nodes_Out.txt`` of ``sba_add``) has the id."""
+    K = np.array(formats.read_camera(os.path.join(directory, "camera.txt")), np.float64)
+    records = formats.read_pose_records(os.path.join(directory, "nodes_and_prjcts.txt"))
+    ids = [int(r[0]) for r in records]
+    poses = np.array([np.asarray(r[1], np.float32).astype(np.float64) for r in records], np.float64).reshape(-1, 7)
+    if nodes_out is not None:
+        oid, opose = formats.read_nodes_out(nodes_out)
+        adjusted = {int(i): p for i, p in zip(oid, opose)}
+        for k, i in enumerate(ids):
+            if i in adjusted:
+                poses[k] = adjusted[i]
+    images = []
+    for i in ids:
+        path = os.path.join(directory, "%d.pgm" % i)
+        if not os.path.exists(path):
+            raise ValueError("%s is missing: the dense step takes 1-channel key frames (colour is out of scope)" % path)
+        images.append(read_pgm(path))
+    return K, ids, poses, images
+
+
+def neighbours_of(i: int, n: int, neighbours: int):
+    """The indices of the `neighbours` nearest key frames on each side of i in file order."""
+    return [j for j in range(i - neighbours, i + neighbours + 1) if j != i and 0 <= j < n]
+
+
+def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, neighbours: int = 2, w_min: float = 0.05,
+                              w_max: float = 2.0, planes: int = 64, radius: int = 2, trunc: int = 40, rel_tol: float = 0.01,
+                              min_agree: int = 1, device: int = 0):
+    """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
+    order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
+    The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
+    neighbourhoods away) and the recording may be of any length >= 2."""
+    if not 1 <= int(neighbours) <= 3:
+        raise ValueError("neighbours is 1 .. 3")
+    K, ids, poses, images = read_recording(directory, nodes_out)
+    n = len(ids)
+    if n < 2:
+        raise ValueError("a depth map needs at least two key frames")
+    h, w = images[0].shape
+    ds = DenseStereo(w, h, min(MAX_VIEWS, n), device)
+    ring = ds.max_views
+    loaded = swept = 0                                             # key frames [0, loaded) are in their slots, [0, swept) swept
+    out = []
+    try:
+        for i in range(n):
+            while loaded < min(n, i + 2 * neighbours + 1):
+                ds.set_view(loaded % ring, images[loaded], K, poses[loaded])
+                loaded += 1
+            while swept < min(n, i + neighbours + 1):
+                ds.sweep(swept % ring, [j % ring for j in neighbours_of(swept, n, neighbours)], w_min, w_max, planes, radius, trunc)
+                swept += 1
+            src = neighbours_of(i, n, neighbours)
+            ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)))
+            raw, flt = ds.depth(i % ring, False), ds.depth(i % ring, True)
+            out.append(DepthMap(ids[i], poses[i].copy(), tuple(ids[j] for j in src), flt["depth"], flt["plane"], raw["depth"],
+                                raw["cost"], raw["views"], ds.points(i % ring, True)))
+    finally:
+        ds.close()
+    return out

@@ -707,7 +707,7 @@ int ekf_keyframe_get_state(const ekf_keyframe* s, float* last_pose7, float* last
 int ekf_keyframe_reset(ekf_keyframe* s);
 
 /* ---- rectification for pinhole consumers ------------------------------------------------------
- * The filter models lens distortion (k1 k2 k3 p1 p2 of ekf_config); ekf_sba_* and any dense step are pinhole.  These
+ * The filter models lens distortion (k1 k2 k3 p1 p2 of ekf_config); ekf_sba_* and the dense step (ekf_dense_*) are pinhole.  These
  * entry points deliver, on demand, images, pixel coordinates and ONE pinhole K that agree.  The reference has no
  * counterpart (its key frames and Point4sba rows stay distorted).  Nothing here runs per frame, changes the filter or
  * counts as a launch kind; ekf_abi_version() stays 6 (additions only).
@@ -738,6 +738,58 @@ int ekf_get_frame_rectified(ekf_filter* f, int raw, unsigned char* out, int stri
 int ekf_undistort_pixels(ekf_filter* f, int raw, const double* uv, int n, double* out);
 int ekf_keyframe_get_image_rectified(const ekf_keyframe* s, int raw, unsigned char* out, int stride);
 int ekf_keyframe_get_emitted_rectified(const ekf_keyframe* s, int raw, int max_rows, double* uv, int* rows);
+
+/* ---- dense plane-sweep depth maps for key frames ----------------------------------------------
+ * Multi-view plane-sweep stereo on rectified key frames: one handle holds up to max_views (<= 16) views of one size
+ * width x height, each an 8-bit grey pinhole image, K = (fx, fy, cx, cy) and a pose in the bundle adjuster's node
+ * convention (camera centre t, q = (w, x, y, z), normalised on entry; x_cam = R^T (X - t)).  The reference has no
+ * counterpart.  DESIGN.md §15.1 pins every operation (fp64 coordinates, integer costs); tests/dense_oracle.py restates
+ * it.  Nothing here touches a filter, counts as a launch kind or runs a collective; ekf_abi_version() stays 6
+ * (additions only).  Everything runs on the default stream of the handle's device.
+ *  - create: 1 <= width, height <= 8192, 1 <= max_views <= 16;
+ *  - set_view: `img` = height rows of width bytes, `pitch` (>= width) bytes apart, on the host; K finite with fx, fy > 0;
+ *    pose7 finite with q != 0.  set_view_device: the same from device memory, enqueued without a host synchronisation.
+ *    set_view_from_keyframe: the selector's last emitted key frame, rectified by one k_frame_rectify launch straight
+ *    into the slot, with the selector's rectified camera of resolution `raw` as K; the selector's image size at that
+ *    resolution must be the handle's and a raw selector must be 1-channel (otherwise EKF_ERR_ARG); EKF_ERR_STATE
+ *    whenever ekf_keyframe_get_image / ekf_keyframe_get_raw_image would refuse.  set_pose: a new pose for a set slot
+ *    (after bundle adjustment), no upload.  Each of them invalidates the slot's swept and filtered maps.  get_view: what
+ *    a set slot holds: the image (`pitch` bytes per row), K and the pose with q normalised; each output may be NULL;
+ *  - sweep: the depth map of view `ref` against the n_src views src[]: `planes` fronto-parallel planes of the
+ *    reference camera, uniform in inverse depth from w_min to w_max; truncated absolute differences (`trunc`) summed
+ *    over the sources and a (2 radius + 1)^2 window; the first plane of least cost wins, refined by a parabola through
+ *    its neighbours.  One launch.  Limits (EKF_ERR_ARG before the device is touched): planes 2..1024, radius 0..4,
+ *    trunc 1..255, n_src 1..8, 0 < w_min < w_max finite, ref not among src, no slot twice in src, every slot in range
+ *    and set;
+ *  - filter: keeps a pixel of `ref` whose swept depth, projected into each source, lands within rel_tol (relative) of
+ *    that source's swept depth in at least min_agree (1..n_src) sources; reads swept maps only and writes the separate
+ *    filtered map of `ref`, so the order of calls does not matter.  EKF_ERR_STATE when a named slot has not been swept
+ *    since its image or pose last changed;
+ *  - get_depth: the swept (filtered = 0) or filtered (1) map of a slot, tight rows: depth float32 (0 = none), plane
+ *    int32 (-1 = none), and of the sweep cost uint32 and views uint8; every output may be NULL.  get_points: height x
+ *    width x 3 doubles, the world points of that map, NaN where there is no depth.  EKF_ERR_STATE without that map;
+ *  - profile / get_profile: HIP-event milliseconds and launch counts of k_plane_sweep ([0]) and
+ *    k_depth_filter_points ([1]) since the last ekf_dense_profile (each timed launch is synchronised).  The kernel of
+ *    [1] also does the back-projection: every ekf_dense_get_points made while profiling adds its launch and its time
+ *    to [1], so fetch points outside the profiled span when [1] is to be read as the filter's time alone. */
+typedef struct ekf_dense ekf_dense;
+int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense** out);
+void ekf_dense_destroy(ekf_dense* h);
+/* Message of the last failure (h may be NULL: last failure of ekf_dense_create). */
+const char* ekf_dense_last_error(const ekf_dense* h);
+int ekf_dense_set_view(ekf_dense* h, int slot, const unsigned char* img, int pitch, const double* K, const double* pose7);
+int ekf_dense_set_view_device(ekf_dense* h, int slot, const void* d_img, int pitch, const double* K, const double* pose7);
+int ekf_dense_set_view_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, int raw, const double* pose7);
+int ekf_dense_set_pose(ekf_dense* h, int slot, const double* pose7);
+int ekf_dense_get_view(const ekf_dense* h, int slot, unsigned char* img, int pitch, double* K, double* pose7);
+int ekf_dense_sweep(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                    int trunc);
+int ekf_dense_filter(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree);
+int ekf_dense_get_depth(ekf_dense* h, int slot, int filtered, float* depth, int* plane, unsigned int* cost,
+                        unsigned char* views);
+int ekf_dense_get_points(ekf_dense* h, int slot, int filtered, double* xyz);
+int ekf_dense_profile(ekf_dense* h, int enable);
+int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
 #ifdef __cplusplus
 }

@@ -446,3 +446,72 @@ class KeyframeSelectorHip {
   ekf_filter* f_ = nullptr;
   ekf_keyframe* h_ = nullptr;
 };
+
+// DenseStereoHip -- header-only mirror of the dense plane-sweep step over the ekf_dense_* functions
+// of ekf_monoslam.h: up to 16 posed pinhole views of one size on the device, sweep() = one k_plane_sweep launch per depth
+// map, filter() = the geometric consistency check against the swept maps of the sources.  Values are plain arrays.
+class DenseStereoHip {
+ public:
+  struct Depth {
+    std::vector<float> depth;            // 0 = none
+    std::vector<int> plane;              // -1 = none
+    std::vector<unsigned int> cost;
+    std::vector<unsigned char> views;
+  };
+
+  DenseStereoHip(int width, int height, int max_views = 16, int device = 0) : w_(width), h_(height) {
+    if (ekf_dense_create(width, height, max_views, device, &d_) != EKF_OK)
+      throw std::runtime_error(std::string("ekf_dense_create: ") + ekf_dense_last_error(nullptr));
+  }
+  ~DenseStereoHip() { ekf_dense_destroy(d_); }
+  DenseStereoHip(const DenseStereoHip&) = delete;
+  DenseStereoHip& operator=(const DenseStereoHip&) = delete;
+
+  // height rows of width bytes, `pitch` bytes apart (0: tight); K = fx fy cx cy; pose7 = x y z qw qx qy qz
+  void setView(int slot, const unsigned char* gray, const double K[4], const double pose7[7], int pitch = 0) {
+    check(ekf_dense_set_view(d_, slot, gray, pitch ? pitch : w_, K, pose7));
+  }
+  void setViewDevice(int slot, const void* d_gray, const double K[4], const double pose7[7], int pitch = 0) {
+    check(ekf_dense_set_view_device(d_, slot, d_gray, pitch ? pitch : w_, K, pose7));
+  }
+  // the selector's last emitted key frame, rectified on the device straight into the slot
+  void setViewFromKeyframe(int slot, KeyframeSelectorHip& selector, const double pose7[7], bool raw = false) {
+    check(ekf_dense_set_view_from_keyframe(d_, slot, selector.handle(), raw ? 1 : 0, pose7));
+  }
+  void setPose(int slot, const double pose7[7]) { check(ekf_dense_set_pose(d_, slot, pose7)); }
+  std::vector<unsigned char> viewImage(int slot) {
+    std::vector<unsigned char> g(pixels());
+    check(ekf_dense_get_view(d_, slot, g.data(), w_, nullptr, nullptr));
+    return g;
+  }
+  void sweep(int ref, const std::vector<int>& src, double w_min, double w_max, int planes = 64, int radius = 2, int trunc = 40) {
+    check(ekf_dense_sweep(d_, ref, src.data(), (int)src.size(), w_min, w_max, planes, radius, trunc));
+  }
+  void filter(int ref, const std::vector<int>& src, double rel_tol = 0.01, int min_agree = 1) {
+    check(ekf_dense_filter(d_, ref, src.data(), (int)src.size(), rel_tol, min_agree));
+  }
+  Depth depth(int slot, bool filtered = false) {
+    Depth r;
+    r.depth.resize(pixels()); r.plane.resize(pixels()); r.cost.resize(pixels()); r.views.resize(pixels());
+    check(ekf_dense_get_depth(d_, slot, filtered ? 1 : 0, r.depth.data(), r.plane.data(), r.cost.data(), r.views.data()));
+    return r;
+  }
+  // height x width x 3 world points, NaN where there is no depth
+  std::vector<double> points(int slot, bool filtered = false) {
+    std::vector<double> xyz(3 * pixels());
+    check(ekf_dense_get_points(d_, slot, filtered ? 1 : 0, xyz.data()));
+    return xyz;
+  }
+  void profile(bool enable) { check(ekf_dense_profile(d_, enable ? 1 : 0)); }
+  // HIP-event milliseconds and launch counts of k_plane_sweep ([0]) and k_depth_filter_points ([1])
+  void getProfile(double kernel_ms[2], long long launches[2]) { check(ekf_dense_get_profile(d_, kernel_ms, launches)); }
+  int width() const { return w_; }
+  int height() const { return h_; }
+  ekf_dense* handle() { return d_; }
+
+ private:
+  size_t pixels() const { return (size_t)w_ * (size_t)h_; }
+  void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_dense_last_error(d_)); }
+  int w_, h_;
+  ekf_dense* d_ = nullptr;
+};
