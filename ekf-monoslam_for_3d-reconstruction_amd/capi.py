@@ -185,6 +185,18 @@ _PROTOS = {
     "ekf_dense_get_points": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ekf_dense_profile": (C.c_int, [_P, C.c_int]),
     "ekf_dense_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_fusion_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
+    "ekf_fusion_destroy": (None, [_P]),
+    "ekf_fusion_last_error": (C.c_char_p, [_P]),
+    "ekf_fusion_integrate": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "ekf_fusion_integrate_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ekf_fusion_reset": (C.c_int, [_P]),
+    "ekf_fusion_get_volume": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ekf_fusion_set_volume": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "ekf_fusion_extract": (C.c_int, [_P, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "ekf_fusion_get_mesh": (C.c_int, [_P, _P, _P, _P, C.c_ulonglong]),
+    "ekf_fusion_profile": (C.c_int, [_P, C.c_int]),
+    "ekf_fusion_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

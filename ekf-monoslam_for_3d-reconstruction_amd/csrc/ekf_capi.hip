@@ -31,6 +31,7 @@
 #include "ekf_rectify.hpp"
 #include "ekf_keyframe.hpp"
 #include "ekf_dense_stereo.hpp"
+#include "ekf_fusion.hpp"
 
 namespace ekf {
 
@@ -5648,6 +5649,201 @@ int ekf_dense_profile(ekf_dense* h, int enable) {
 int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   for (int i = 0; i < 2; ++i) { kernel_ms[i] = h->impl->prof_ms[i]; launches[i] = h->impl->prof_cnt[i]; }
+  return EKF_OK;
+}
+
+// ---- TSDF fusion of depth maps and mesh extraction -----------------------------------------------------
+struct ekf_fusion { ekf::TsdfFusion* impl; };
+
+int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out) {
+  if (!out) return EKF_ERR_ARG;
+  *out = nullptr;
+  const bool dims_ok = nx >= 2 && ny >= 2 && nz >= 2 && nx <= ekf::kFusionMaxDim && ny <= ekf::kFusionMaxDim &&
+                       nz <= ekf::kFusionMaxDim && (long long)nx * ny * nz <= ekf::kFusionMaxVoxels;
+  if (!dims_ok || !origin || !sba_finite(origin, 3) || !std::isfinite(voxel) || !(voxel > 0.0) || !std::isfinite(trunc) ||
+      !(trunc > 0.0)) {
+    ekf::g_create_error = "ekf_fusion_create: 2 <= nx, ny, nz <= 1024, nx ny nz <= 2^28, origin finite, voxel and trunc finite and > 0";
+    return EKF_ERR_ARG;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    ekf::g_create_error = "ekf_fusion_create: no HIP device (this library has no CPU fallback)";
+    return EKF_ERR_DEVICE;
+  }
+  auto* f = new ekf::TsdfFusion();
+  f->device = device;
+  f->g.nx = nx; f->g.ny = ny; f->g.nz = nz;
+  std::copy(origin, origin + 3, f->g.origin);
+  f->g.voxel = voxel;
+  f->trunc = trunc;
+  hipError_t e = hipSetDevice(device);
+  f->created = e == hipSuccess;
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&f->ev[i]);
+  if (e == hipSuccess) e = f->sum.reserve(f->nvox());
+  if (e == hipSuccess) e = f->cnt.reserve(f->nvox());
+  if (e == hipSuccess) e = f->gsum.reserve(f->nvox());
+  if (e == hipSuccess) e = f->clear();
+  if (e != hipSuccess) {
+    ekf::g_create_error = std::string("ekf_fusion_create: ") + hipGetErrorString(e);
+    (void)hipGetLastError();
+    delete f;
+    return EKF_ERR_DEVICE;
+  }
+  *out = new ekf_fusion{f};
+  return EKF_OK;
+}
+
+void ekf_fusion_destroy(ekf_fusion* h) {
+  if (!h) return;
+  delete h->impl;
+  delete h;
+}
+
+const char* ekf_fusion_last_error(const ekf_fusion* h) {
+  if (!h) return ekf::g_create_error.c_str();
+  return h->impl->err.c_str();
+}
+
+static int fusion_room(ekf::TsdfFusion* f, const char* who) {
+  if (f->maps >= ekf::kFusionMaxMaps) {
+    f->err = std::string(who) + ": the handle has integrated 65535 maps (the count of a voxel is 16 bits); nothing was changed";
+    return EKF_ERR_CAPACITY;
+  }
+  return EKF_OK;
+}
+
+int ekf_fusion_integrate(ekf_fusion* h, ekf_dense* dense, int slot, int filtered) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!dense || dense->impl->device != f->device) {
+    f->err = "ekf_fusion_integrate: a dense handle on the volume's device";
+    return EKF_ERR_ARG;
+  }
+  auto* d = dense->impl;
+  const int rc = dense_map_ok(d, "ekf_fusion_integrate", slot, filtered);
+  if (rc != EKF_OK) {
+    f->err = d->err;
+    return rc;
+  }
+  const int room = fusion_room(f, "ekf_fusion_integrate");
+  if (room != EKF_OK) return room;
+  std::string& err = f->err;
+  const ekf::DenseView& v = d->v[slot];
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(f->integrate(filtered ? v.fdepth : v.depth, v.img, d->W, d->H, v.K, v.R, v.t));
+  return EKF_OK;
+}
+
+int ekf_fusion_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* img, int pitch, int width, int height,
+                              const double* K, const double* pose7) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  double t[3], R[9], q[4];
+  if (!depth || !img || !K || !pose7 || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
+      height > ekf::kFusionMaxMapDim || pitch < width || !(sba_finite(K, 4) && K[0] > 0.0 && K[1] > 0.0) ||
+      !ekf::dense_pose(pose7, t, R, q)) {
+    f->err = "ekf_fusion_integrate_host: depth, img, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= width; K finite "
+             "with fx, fy > 0; pose7 finite with q != 0";
+    return EKF_ERR_ARG;
+  }
+  const int room = fusion_room(f, "ekf_fusion_integrate_host");
+  if (room != EKF_OK) return room;
+  std::string& err = f->err;
+  const size_t n = (size_t)width * height;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(f->d_depth.reserve(n));
+  HIPCHK(f->d_img.reserve(n));
+  HIPCHK(hipMemcpy(f->d_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy2D(f->d_img, (size_t)width, img, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
+  HIPCHK(f->integrate(f->d_depth, f->d_img, width, height, K, R, t));
+  return EKF_OK;
+}
+
+int ekf_fusion_reset(ekf_fusion* h) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(f->clear());
+  return EKF_OK;
+}
+
+int ekf_fusion_get_volume(ekf_fusion* h, float* sum, unsigned short* cnt, unsigned int* gsum, int* maps) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  std::string& err = f->err;
+  const size_t n = f->nvox();
+  HIPCHK(hipSetDevice(f->device));
+  if (sum) HIPCHK(hipMemcpy(sum, f->sum, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (cnt) HIPCHK(hipMemcpy(cnt, f->cnt, n * sizeof(unsigned short), hipMemcpyDeviceToHost));
+  if (gsum) HIPCHK(hipMemcpy(gsum, f->gsum, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (maps) *maps = f->maps;
+  return EKF_OK;
+}
+
+int ekf_fusion_set_volume(ekf_fusion* h, const float* sum, const unsigned short* cnt, const unsigned int* gsum, int maps) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (maps < -1 || maps > ekf::kFusionMaxMaps) {
+    f->err = "ekf_fusion_set_volume: maps is -1 (keep the counter) or 0..65535";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t n = f->nvox();
+  int most = maps >= 0 ? maps : f->maps;
+  if (cnt)                                       // the counter never falls below a voxel's count: cnt + 1 cannot wrap
+    for (size_t i = 0; i < n; ++i) most = std::max(most, (int)cnt[i]);
+  HIPCHK(hipSetDevice(f->device));
+  f->mesh_valid = false;
+  if (sum) HIPCHK(hipMemcpy(f->sum, sum, n * sizeof(float), hipMemcpyHostToDevice));
+  if (cnt) HIPCHK(hipMemcpy(f->cnt, cnt, n * sizeof(unsigned short), hipMemcpyHostToDevice));
+  if (gsum) HIPCHK(hipMemcpy(f->gsum, gsum, n * sizeof(unsigned), hipMemcpyHostToDevice));
+  f->maps = most;
+  return EKF_OK;
+}
+
+int ekf_fusion_extract(ekf_fusion* h, int min_count, unsigned long long* n_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (min_count < 1 || min_count > ekf::kFusionMaxMaps || !n_tri) {
+    f->err = "ekf_fusion_extract: min_count 1..65535 and n_tri not NULL";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(f->extract(min_count));
+  *n_tri = f->n_tri;
+  return EKF_OK;
+}
+
+int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, unsigned char* grey, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!f->mesh_valid) {
+    f->err = "ekf_fusion_get_mesh: no ekf_fusion_extract since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(f->n_tri, max_tri) * 3;
+  if (nv == 0) return EKF_OK;
+  HIPCHK(hipSetDevice(f->device));
+  if (xyz) HIPCHK(hipMemcpy(xyz, f->m_xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (key) HIPCHK(hipMemcpy(key, f->m_key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (grey) HIPCHK(hipMemcpy(grey, f->m_grey, nv, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_fusion_profile(ekf_fusion* h, int enable) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  f->profile = enable != 0;
+  for (int i = 0; i < 4; ++i) { f->prof_ms[i] = 0.0; f->prof_cnt[i] = 0; }
+  return EKF_OK;
+}
+
+int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  for (int i = 0; i < 4; ++i) { kernel_ms[i] = h->impl->prof_ms[i]; launches[i] = h->impl->prof_cnt[i]; }
   return EKF_OK;
 }
 

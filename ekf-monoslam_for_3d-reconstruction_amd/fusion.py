@@ -1,0 +1,211 @@
+"""Fusion of key-frame depth maps into a TSDF volume and a triangle mesh: ``TsdfVolume`` mirrors the
+``ekf_fusion_*`` functions, ``weld`` joins the triangle soup by its vertex keys on the host, ``write_mesh_ply`` /
+``read_mesh_ply`` store the result, and ``mesh_from_recording`` drives ``dense.depth_maps_from_recording`` and the volume
+over a rectified recording.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import capi, dense
+from .capi import EkfError
+
+MAX_DIM, MAX_VOXELS, MAX_MAPS = 1024, 1 << 28, 65535
+KERNELS = ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+@dataclass
+class Mesh:
+    """The triangle soup of ``TsdfVolume.extract`` in its fixed order."""
+    xyz: np.ndarray                # (n, 3, 3) float64
+    key: np.ndarray                # (n, 3) uint64: equal keys are bit-equal vertices
+    grey: np.ndarray               # (n, 3) uint8
+
+
+@dataclass
+class RecordingMesh:
+    """What ``mesh_from_recording`` returns: the welded mesh and the grid it was fused on."""
+    vertices: np.ndarray           # (m, 3) float64
+    faces: np.ndarray              # (n, 3) int64 into vertices
+    grey: np.ndarray               # (m,) uint8
+    origin: np.ndarray
+    dims: tuple
+    voxel: float
+    trunc: float
+    maps: list                     # the DepthMaps that were fused
+
+
+class TsdfVolume:
+    """``dims`` = (nx, ny, nz) voxels of side ``voxel`` on the device; the centre of voxel (i, j, k) is origin + (i, j, k) voxel.
+    The planes are numpy arrays of shape (nz, ny, nx): x fastest."""
+
+    def __init__(self, dims, origin, voxel: float, trunc: float, device: int = 0):
+        self._lib = capi.load_library()
+        self._h = C.c_void_p()
+        nx, ny, nz = (int(v) for v in dims)
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        rc = self._lib.ekf_fusion_create(nx, ny, nz, _ptr(o), float(voxel), float(trunc), int(device), C.byref(self._h))
+        if rc != 0:
+            msg = self._lib.ekf_fusion_last_error(None)
+            raise EkfError(rc, msg.decode() if msg else "ekf_fusion_create failed")
+        self.dims, self.origin, self.voxel, self.trunc, self.device = (nx, ny, nz), o, float(voxel), float(trunc), int(device)
+        self.shape = (nz, ny, nx)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.ekf_fusion_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = self._lib.ekf_fusion_last_error(self._h)
+            raise EkfError(rc, msg.decode() if msg else "")
+
+    def integrate(self, dense_stereo, slot: int, filtered: bool = True):
+        """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""
+        self._check(self._lib.ekf_fusion_integrate(self._h, dense_stereo._h, int(slot), 1 if filtered else 0))
+
+    def integrate_host(self, depth, image, K, pose7):
+        """``depth``: (H, W) float32, 0 = none; ``image``: (H, W) uint8; any size up to 8192 x 8192."""
+        d = np.ascontiguousarray(depth, np.float32)
+        img = np.ascontiguousarray(image, np.uint8)
+        if d.ndim != 2 or img.shape != d.shape:
+            raise ValueError("depth and image are (H, W) arrays of one shape")
+        K = np.ascontiguousarray(K, np.float64).reshape(4)
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        self._check(self._lib.ekf_fusion_integrate_host(self._h, _ptr(d), _ptr(img), img.strides[0], d.shape[1], d.shape[0],
+                                                        _ptr(K), _ptr(pose)))
+
+    def reset(self):
+        self._check(self._lib.ekf_fusion_reset(self._h))
+
+    def volume(self) -> dict:
+        """sum float32, cnt uint16, gsum uint32, each (nz, ny, nx), and maps: the number of maps integrated."""
+        out = dict(sum=np.zeros(self.shape, np.float32), cnt=np.zeros(self.shape, np.uint16), gsum=np.zeros(self.shape, np.uint32))
+        maps = C.c_int(0)
+        self._check(self._lib.ekf_fusion_get_volume(self._h, _ptr(out["sum"]), _ptr(out["cnt"]), _ptr(out["gsum"]), C.byref(maps)))
+        out["maps"] = int(maps.value)
+        return out
+
+    def set_volume(self, sum=None, cnt=None, gsum=None, maps: int = -1):
+        """Writes the given planes (tests).  ``maps`` = -1 keeps the map counter; it is raised to the largest count given."""
+        arrs = []
+        for a, t in ((sum, np.float32), (cnt, np.uint16), (gsum, np.uint32)):
+            if a is not None:
+                a = np.ascontiguousarray(a, t)
+                if a.shape != self.shape:
+                    raise ValueError("a plane is (nz, ny, nx) = %r" % (self.shape,))
+            arrs.append(a)
+        self._check(self._lib.ekf_fusion_set_volume(self._h, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), int(maps)))
+
+    def extract(self, min_count: int = 1) -> Mesh:
+        n = C.c_ulonglong(0)
+        self._check(self._lib.ekf_fusion_extract(self._h, int(min_count), C.byref(n)))
+        n = int(n.value)
+        m = Mesh(np.zeros((n, 3, 3), np.float64), np.zeros((n, 3), np.uint64), np.zeros((n, 3), np.uint8))
+        self._check(self._lib.ekf_fusion_get_mesh(self._h, _ptr(m.xyz), _ptr(m.key), _ptr(m.grey), n))
+        return m
+
+    def profile(self, enable: bool = True):
+        self._check(self._lib.ekf_fusion_profile(self._h, 1 if enable else 0))
+
+    def get_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the four kernels since the last ``profile()``."""
+        ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
+        self._check(self._lib.ekf_fusion_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(KERNELS)}
+
+
+def weld(mesh: Mesh):
+    """(vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8): one vertex per distinct key (ascending), exact because
+    equal keys carry bit-equal coordinates."""
+    _, first, inverse = np.unique(mesh.key.reshape(-1), return_index=True, return_inverse=True)
+    return mesh.xyz.reshape(-1, 3)[first], inverse.reshape(-1, 3).astype(np.int64), mesh.grey.reshape(-1)[first]
+
+
+def write_mesh_ply(path: str, vertices, faces, grey) -> None:
+    """ASCII PLY: vertices ``x y z`` as doubles with ``intensity``, faces as ``list uchar int vertex_indices``."""
+    with open(path, "w") as fh:
+        fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
+                 "property uchar intensity\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                 % (len(vertices), len(faces)))
+        for (x, y, z), g in zip(vertices, grey):
+            fh.write("%.17g %.17g %.17g %d\n" % (x, y, z, int(g)))
+        for a, b, c in faces:
+            fh.write("3 %d %d %d\n" % (a, b, c))
+
+
+def read_mesh_ply(path: str):
+    """What ``write_mesh_ply`` wrote: (vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8)."""
+    with open(path) as fh:
+        lines = fh.read().splitlines()
+    end = lines.index("end_header")
+    count = lambda what: int([ln for ln in lines[:end] if ln.startswith("element " + what)][0].split()[2])
+    nv, nf = count("vertex"), count("face")
+    rows = [ln.split() for ln in lines[end + 1:end + 1 + nv]]
+    faces = [ln.split() for ln in lines[end + 1 + nv:end + 1 + nv + nf]]
+    return (np.array([[float(t) for t in r[:3]] for r in rows], np.float64).reshape(-1, 3),
+            np.array([[int(t) for t in r[1:4]] for r in faces], np.int64).reshape(-1, 3),
+            np.array([int(r[3]) for r in rows], np.uint8))
+
+
+def auto_grid(points, voxel: Optional[float] = None, bounds=None, trunc: Optional[float] = None):
+    """(origin, dims, voxel, trunc) of ``mesh_from_recording``.  The box is ``bounds`` = (lo, hi), or the
+    box of all finite ``points`` padded by trunc; voxel = its longest side before the padding / 128, doubled until the
+    limits of a volume hold; trunc = 4 voxel; a side of n = ceil(extent / voxel) + 1 >= 2 voxels."""
+    if bounds is None:
+        pts = np.concatenate([np.asarray(p, np.float64).reshape(-1, 3) for p in points])
+        pts = pts[np.isfinite(pts).all(axis=1)]
+        if not len(pts):
+            raise ValueError("no depth map has a point: nothing to bound the volume with")
+        lo, hi = pts.min(axis=0), pts.max(axis=0)
+    else:
+        lo, hi = np.asarray(bounds[0], np.float64).reshape(3), np.asarray(bounds[1], np.float64).reshape(3)
+    auto = voxel is None
+    vx = np.float64((hi - lo).max()) / 128.0 if auto else np.float64(voxel)
+    if not (np.isfinite(vx) and vx > 0.0):
+        raise ValueError("the box has no extent")
+    while True:
+        tr = 4.0 * vx if trunc is None else np.float64(trunc)
+        a, b = (lo - tr, hi + tr) if bounds is None else (lo, hi)
+        dims = np.maximum(np.ceil((b - a) / vx).astype(np.int64) + 1, 2)
+        if dims.max() <= MAX_DIM and int(dims[0]) * int(dims[1]) * int(dims[2]) <= MAX_VOXELS:
+            return a, tuple(int(v) for v in dims), float(vx), float(tr)
+        if not auto:
+            raise ValueError("the volume exceeds 1024 voxels a side or 2^28 in all")
+        vx = vx * 2.0
+
+
+def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
+                        trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
+                        **sweep_kwargs) -> RecordingMesh:
+    """``dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)``, then every filtered map with its key
+    frame's image into one volume (``auto_grid`` where voxel / bounds / trunc are None), extract, weld.  ``trunc`` is the
+    truncation distance of the volume; the sweep's cost truncation, also called ``trunc`` there, is ``sweep_trunc`` here."""
+    if sweep_trunc is not None:
+        sweep_kwargs["trunc"] = sweep_trunc
+    maps = dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)
+    K, ids, poses, images = dense.read_recording(directory, nodes_out)
+    origin, dims, vx, tr = auto_grid([m.points for m in maps], voxel, bounds, trunc)
+    vol = TsdfVolume(dims, origin, vx, tr, int(sweep_kwargs.get("device", 0)))
+    try:
+        for m, img in zip(maps, images):
+            vol.integrate_host(m.depth, img, K, m.pose)
+        vertices, faces, grey = weld(vol.extract(min_count))
+    finally:
+        vol.close()
+    return RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps)

@@ -791,6 +791,52 @@ int ekf_dense_get_points(ekf_dense* h, int slot, int filtered, double* xyz);
 int ekf_dense_profile(ekf_dense* h, int enable);
 int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
+/* ---- fusion of depth maps into a TSDF volume and a triangle mesh -------------------------------
+ * The last stage of the reconstruction: the depth maps of the key frames (ekf_dense_*, or any host arrays) are
+ * integrated into one truncated signed distance volume on the device, and an oriented, watertight triangle mesh is
+ * extracted from it by marching tetrahedra.  The reference has no counterpart.  DESIGN.md §16.1 pins every operation
+ * (fp64 coordinates rounded once in the written order, one fp32 add per voxel and map, no atomics, a fixed output
+ * order); tests/fusion_oracle.py restates it.  Nothing here touches a filter, counts as a launch kind or runs a
+ * collective; ekf_abi_version() stays 6 (additions only).  Everything runs on the default stream of the handle's device.
+ *  - create: nx x ny x nz voxels; the centre of voxel (i, j, k) is origin + (i, j, k) voxel; linear index
+ *    i + nx (j + ny k).  Each voxel holds sum (float), cnt (unsigned short) and gsum (unsigned int).  EKF_ERR_ARG before
+ *    the device is touched: a dimension outside 2..1024, nx ny nz > 2^28, voxel or trunc not finite or <= 0, origin
+ *    not finite;
+ *  - integrate: the swept (filtered = 0) or filtered (1) map of a slot of a dense handle, straight from its device
+ *    buffers, with the slot's image, K and pose.  A dense handle on another device is EKF_ERR_ARG; a slot without that
+ *    map is EKF_ERR_STATE by the rules of ekf_dense_get_depth.  integrate_host: `depth` = height tight rows of width
+ *    floats (0 = none), `img` = height rows of width bytes `pitch` (>= width) bytes apart, 1 <= width, height <= 8192,
+ *    K = (fx, fy, cx, cy) finite with fx, fy > 0, pose7 as for ekf_dense_set_view.  One k_tsdf_integrate launch each.
+ *    A handle integrates at most 65535 maps; the next one is EKF_ERR_CAPACITY and changes nothing;
+ *  - reset: clears the three planes and the map counter;
+ *  - get_volume / set_volume: the three planes (nx ny nz elements each) and the map counter; every pointer may be
+ *    NULL.  They exist for tests, as ekf_set_state does.  set_volume: `maps` = -1 keeps the counter, 0..65535 sets it;
+ *    the counter is then raised to the largest count given, so that a voxel's count cannot wrap;
+ *  - extract: marching tetrahedra over every cell whose eight corners have cnt >= min_count (1..65535); reports the
+ *    number of triangles.  Three launches (k_tsdf_count, k_tsdf_scan, k_tsdf_emit) and one 8-byte read-back; a failed
+ *    allocation of the mesh buffers is EKF_ERR_DEVICE and leaves the previous mesh and the volume as they were;
+ *  - get_mesh: the first min(n_tri, max_tri) triangles in the fixed order (cells by linear index of their corner 0,
+ *    tetrahedra 0..5, table order): xyz = 3 x 3 doubles a triangle, key = 3 vertex keys (equal keys: bit-equal
+ *    vertices), grey = 3 bytes; every pointer may be NULL.  EKF_ERR_STATE before an extract or after the volume changed
+ *    since the last one (integrate, reset, set_volume);
+ *  - profile / get_profile: HIP-event milliseconds and launch counts of k_tsdf_integrate ([0]), k_tsdf_count ([1]),
+ *    k_tsdf_scan ([2]) and k_tsdf_emit ([3]) since the last ekf_fusion_profile (each timed launch is synchronised). */
+typedef struct ekf_fusion ekf_fusion;
+int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out);
+void ekf_fusion_destroy(ekf_fusion* h);
+/* Message of the last failure (h may be NULL: last failure of ekf_fusion_create). */
+const char* ekf_fusion_last_error(const ekf_fusion* h);
+int ekf_fusion_integrate(ekf_fusion* h, ekf_dense* dense, int slot, int filtered);
+int ekf_fusion_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* img, int pitch, int width, int height,
+                              const double* K, const double* pose7);
+int ekf_fusion_reset(ekf_fusion* h);
+int ekf_fusion_get_volume(ekf_fusion* h, float* sum, unsigned short* cnt, unsigned int* gsum, int* maps);
+int ekf_fusion_set_volume(ekf_fusion* h, const float* sum, const unsigned short* cnt, const unsigned int* gsum, int maps);
+int ekf_fusion_extract(ekf_fusion* h, int min_count, unsigned long long* n_tri);
+int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, unsigned char* grey, unsigned long long max_tri);
+int ekf_fusion_profile(ekf_fusion* h, int enable);
+int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

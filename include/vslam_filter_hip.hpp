@@ -515,3 +515,65 @@ class DenseStereoHip {
   int w_, h_;
   ekf_dense* d_ = nullptr;
 };
+
+// TsdfVolumeHip -- header-only mirror of the fusion step over the ekf_fusion_* functions of
+// ekf_monoslam.h: depth maps (of a DenseStereoHip slot, or host arrays) integrated into one truncated signed distance volume
+// on the device, extract() = marching tetrahedra into a triangle soup in a fixed order.  Values are plain arrays.
+class TsdfVolumeHip {
+ public:
+  struct Mesh {
+    std::vector<double> xyz;                   // 9 per triangle
+    std::vector<unsigned long long> key;       // 3 per triangle: equal keys are bit-equal vertices
+    std::vector<unsigned char> grey;           // 3 per triangle
+    size_t triangles() const { return key.size() / 3; }
+  };
+  struct Volume {
+    std::vector<float> sum;
+    std::vector<unsigned short> cnt;
+    std::vector<unsigned int> gsum;
+    int maps = 0;
+  };
+
+  TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0)
+      : n_((size_t)nx * (size_t)ny * (size_t)nz) {
+    if (ekf_fusion_create(nx, ny, nz, origin, voxel, trunc, device, &f_) != EKF_OK)
+      throw std::runtime_error(std::string("ekf_fusion_create: ") + ekf_fusion_last_error(nullptr));
+  }
+  ~TsdfVolumeHip() { ekf_fusion_destroy(f_); }
+  TsdfVolumeHip(const TsdfVolumeHip&) = delete;
+  TsdfVolumeHip& operator=(const TsdfVolumeHip&) = delete;
+
+  // the swept or filtered map of a slot, straight from the dense handle's device buffers
+  void integrate(DenseStereoHip& dense, int slot, bool filtered = true) {
+    check(ekf_fusion_integrate(f_, dense.handle(), slot, filtered ? 1 : 0));
+  }
+  // height tight rows of width floats (0 = none); height rows of width bytes, `pitch` bytes apart (0: tight)
+  void integrateHost(const float* depth, const unsigned char* gray, int width, int height, const double K[4],
+                     const double pose7[7], int pitch = 0) {
+    check(ekf_fusion_integrate_host(f_, depth, gray, pitch ? pitch : width, width, height, K, pose7));
+  }
+  void reset() { check(ekf_fusion_reset(f_)); }
+  Volume volume() {
+    Volume v;
+    v.sum.resize(n_); v.cnt.resize(n_); v.gsum.resize(n_);
+    check(ekf_fusion_get_volume(f_, v.sum.data(), v.cnt.data(), v.gsum.data(), &v.maps));
+    return v;
+  }
+  Mesh extract(int min_count = 1) {
+    unsigned long long n = 0;
+    check(ekf_fusion_extract(f_, min_count, &n));
+    Mesh m;
+    m.xyz.resize((size_t)n * 9); m.key.resize((size_t)n * 3); m.grey.resize((size_t)n * 3);
+    check(ekf_fusion_get_mesh(f_, m.xyz.data(), m.key.data(), m.grey.data(), n));
+    return m;
+  }
+  void profile(bool enable) { check(ekf_fusion_profile(f_, enable ? 1 : 0)); }
+  // HIP-event milliseconds and launch counts of k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit
+  void getProfile(double kernel_ms[4], long long launches[4]) { check(ekf_fusion_get_profile(f_, kernel_ms, launches)); }
+  ekf_fusion* handle() { return f_; }
+
+ private:
+  void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_fusion_last_error(f_)); }
+  size_t n_;
+  ekf_fusion* f_ = nullptr;
+};
