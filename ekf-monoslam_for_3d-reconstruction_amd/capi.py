@@ -197,6 +197,10 @@ _PROTOS = {
     "ekf_fusion_get_mesh": (C.c_int, [_P, _P, _P, _P, C.c_ulonglong]),
     "ekf_fusion_profile": (C.c_int, [_P, C.c_int]),
     "ekf_fusion_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_raycast_render": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int]),
+    "ekf_raycast_render_view": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int]),
+    "ekf_raycast_get": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ekf_raycast_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -32,6 +32,7 @@
 #include "ekf_keyframe.hpp"
 #include "ekf_dense_stereo.hpp"
 #include "ekf_fusion.hpp"
+#include "ekf_raycast.hpp"
 
 namespace ekf {
 
@@ -5653,7 +5654,10 @@ int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* laun
 }
 
 // ---- TSDF fusion of depth maps and mesh extraction -----------------------------------------------------
-struct ekf_fusion { ekf::TsdfFusion* impl; };
+struct ekf_fusion {
+  ekf::TsdfFusion* impl;
+  ekf::TsdfRaycast rc;                // the last render of the volume (ekf_raycast_*)
+};
 
 int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out) {
   if (!out) return EKF_ERR_ARG;
@@ -5695,6 +5699,8 @@ int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel
 
 void ekf_fusion_destroy(ekf_fusion* h) {
   if (!h) return;
+  if (h->impl->created) hipSetDevice(h->impl->device);
+  h->rc = ekf::TsdfRaycast();
   delete h->impl;
   delete h;
 }
@@ -5795,6 +5801,7 @@ int ekf_fusion_set_volume(ekf_fusion* h, const float* sum, const unsigned short*
     for (size_t i = 0; i < n; ++i) most = std::max(most, (int)cnt[i]);
   HIPCHK(hipSetDevice(f->device));
   f->mesh_valid = false;
+  ++f->changes;
   if (sum) HIPCHK(hipMemcpy(f->sum, sum, n * sizeof(float), hipMemcpyHostToDevice));
   if (cnt) HIPCHK(hipMemcpy(f->cnt, cnt, n * sizeof(unsigned short), hipMemcpyHostToDevice));
   if (gsum) HIPCHK(hipMemcpy(f->gsum, gsum, n * sizeof(unsigned), hipMemcpyHostToDevice));
@@ -5838,12 +5845,101 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   auto* f = h->impl;
   f->profile = enable != 0;
   for (int i = 0; i < 4; ++i) { f->prof_ms[i] = 0.0; f->prof_cnt[i] = 0; }
+  for (int i = 0; i < 2; ++i) { h->rc.prof_ms[i] = 0.0; h->rc.prof_cnt[i] = 0; }
   return EKF_OK;
 }
 
 int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   for (int i = 0; i < 4; ++i) { kernel_ms[i] = h->impl->prof_ms[i]; launches[i] = h->impl->prof_cnt[i]; }
+  return EKF_OK;
+}
+
+// ---- ray casting of the volume ---------------------------------------------------------------------------
+// Everything but the handle and the pose: EKF_OK with N set, or EKF_ERR_ARG with the message set.
+static int raycast_args(ekf::TsdfFusion* f, const char* who, int width, int height, const double* K, double z_near, double z_far,
+                        double step, int min_count, int* N) {
+  bool ok = width >= 1 && height >= 1 && width <= ekf::kRaycastMaxDim && height <= ekf::kRaycastMaxDim && K && sba_finite(K, 4) &&
+            K[0] != 0.0 && K[1] != 0.0 && std::isfinite(step) && step > 0.0 && std::isfinite(z_near) && std::isfinite(z_far) &&
+            z_near >= 0.0 && z_near < z_far && min_count >= 1 && min_count <= ekf::kFusionMaxMaps;
+  if (ok) {
+    const double n = std::floor((z_far - z_near) / step) + 1.0;
+    ok = n <= (double)ekf::kRaycastMaxSamples;
+    if (ok) *N = (int)n;
+  }
+  if (!ok) {
+    f->err = std::string(who) + ": 1 <= width, height <= 8192; K finite with fx, fy != 0; pose7 finite with q != 0; step finite "
+             "and > 0; 0 <= z_near < z_far finite; floor((z_far - z_near) / step) + 1 <= 65536 samples; min_count 1..65535";
+    return EKF_ERR_ARG;
+  }
+  return EKF_OK;
+}
+
+int ekf_raycast_render(ekf_fusion* h, int width, int height, const double* K, const double* pose7, double z_near, double z_far,
+                       double step, int min_count) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  double t[3], R[9], q[4];
+  int N = 0;
+  const int rc = raycast_args(f, "ekf_raycast_render", width, height, K, z_near, z_far, step, min_count, &N);
+  if (rc != EKF_OK) return rc;
+  if (!pose7 || !ekf::dense_pose(pose7, t, R, q)) {
+    f->err = "ekf_raycast_render: pose7 finite with q != 0";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->rc.render(*f, width, height, K, R, t, z_near, step, N, min_count));
+  return EKF_OK;
+}
+
+int ekf_raycast_render_view(ekf_fusion* h, ekf_dense* dense, int slot, double z_near, double z_far, double step, int min_count) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!dense || dense->impl->device != f->device) {
+    f->err = "ekf_raycast_render_view: a dense handle on the volume's device";
+    return EKF_ERR_ARG;
+  }
+  auto* d = dense->impl;
+  if (slot < 0 || slot >= d->max_views) {
+    f->err = "ekf_raycast_render_view: slot in 0..max_views-1";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set) {
+    f->err = "ekf_raycast_render_view: the slot is not set";
+    return EKF_ERR_STATE;
+  }
+  int N = 0;
+  const int rc = raycast_args(f, "ekf_raycast_render_view", d->W, d->H, v.K, z_near, z_far, step, min_count, &N);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->rc.render(*f, d->W, d->H, v.K, v.R, v.t, z_near, step, N, min_count));
+  return EKF_OK;
+}
+
+int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, int* width, int* height) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!h->rc.current(*f)) {
+    f->err = "ekf_raycast_get: no ekf_raycast_render since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  const size_t n = (size_t)h->rc.W * h->rc.H;
+  HIPCHK(hipSetDevice(f->device));
+  if (depth) HIPCHK(hipMemcpy(depth, h->rc.depth, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (normal) HIPCHK(hipMemcpy(normal, h->rc.normal, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (grey) HIPCHK(hipMemcpy(grey, h->rc.grey, n, hipMemcpyDeviceToHost));
+  if (width) *width = h->rc.W;
+  if (height) *height = h->rc.H;
+  return EKF_OK;
+}
+
+int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  for (int i = 0; i < 2; ++i) { kernel_ms[i] = h->rc.prof_ms[i]; launches[i] = h->rc.prof_cnt[i]; }
   return EKF_OK;
 }
 

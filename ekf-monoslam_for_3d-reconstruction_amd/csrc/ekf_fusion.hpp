@@ -279,6 +279,7 @@ struct TsdfFusion {
   DevBuf<unsigned char> m_grey;
   unsigned long long n_tri = 0;
   bool mesh_valid = false;            // an extract since the volume last changed
+  unsigned long long changes = 0;     // counts the changes of the volume (integrate, reset, ekf_fusion_set_volume): ekf_raycast.hpp
   int maps = 0;                       // maps integrated since the last reset (or what ekf_fusion_set_volume said)
   bool profile = false;
   hipEvent_t ev[2] = {nullptr, nullptr};
@@ -309,6 +310,7 @@ struct TsdfFusion {
     if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, nvox() * sizeof(unsigned short), nullptr);
     if (e == hipSuccess) e = hipMemsetAsync(gsum, 0, nvox() * sizeof(unsigned), nullptr);
     mesh_valid = false;
+    ++changes;
     if (e == hipSuccess) maps = 0;
     return e;
   }
@@ -324,6 +326,7 @@ struct TsdfFusion {
     for (int i = 0; i < 9; ++i) a.R[i] = R[i];
     for (int i = 0; i < 3; ++i) a.t[i] = t[i];
     mesh_valid = false;
+    ++changes;
     hipError_t e;
     if ((e = timed_begin()) != hipSuccess) return e;
     k_tsdf_integrate<<<(unsigned)((nvox() + kFusionBlock - 1) / kFusionBlock), kFusionBlock, 0, nullptr>>>(a);

@@ -1,7 +1,9 @@
 """Fusion of key-frame depth maps into a TSDF volume and a triangle mesh: ``TsdfVolume`` mirrors the
 ``ekf_fusion_*`` functions, ``weld`` joins the triangle soup by its vertex keys on the host, ``write_mesh_ply`` /
 ``read_mesh_ply`` store the result, and ``mesh_from_recording`` drives ``dense.depth_maps_from_recording`` and the volume
-over a rectified recording.
+over a rectified recording.  ``TsdfVolume.raycast`` / ``raycast_view`` mirror ``ekf_raycast_*`` (§17): the volume seen from a
+pose as a depth, a normal and a grey image; ``shade`` turns one into a picture and ``audit_recording`` compares the
+reconstruction of a recording with its own key frames.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from .capi import EkfError
 
 MAX_DIM, MAX_VOXELS, MAX_MAPS = 1024, 1 << 28, 65535
 KERNELS = ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")
+RAYCAST_KERNELS = ("k_tsdf_mean", "k_tsdf_raycast")
 
 
 def _ptr(a):
@@ -28,6 +31,34 @@ class Mesh:
     xyz: np.ndarray                # (n, 3, 3) float64
     key: np.ndarray                # (n, 3) uint64: equal keys are bit-equal vertices
     grey: np.ndarray               # (n, 3) uint8
+
+
+@dataclass
+class Render:
+    """What ``TsdfVolume.raycast`` returns; a pixel without a hit has depth 0, normal 0 and grey 0."""
+    depth: np.ndarray              # (H, W) float32: camera-z depth of the surface
+    normal: np.ndarray             # (H, W, 3) float32: unit, world frame, towards free space
+    grey: np.ndarray               # (H, W) uint8
+
+
+@dataclass
+class FrameAudit:
+    """One key frame of ``audit_recording``: the volume rendered at its pose against its filtered depth map and image."""
+    id: int
+    render: Render
+    overlap: float                 # share of the pixels where the render and the filtered map both have depth
+    median: float                  # of |render - filtered| / filtered over those pixels (NaN if there are none)
+    p90: float                     # its 90th percentile
+    grey_error: float              # mean |grey - image| over the pixels the render hit (NaN if there are none)
+
+
+@dataclass
+class RecordingAudit:
+    mesh: "RecordingMesh"
+    frames: list                   # one FrameAudit per key frame, in file order
+    z_near: float
+    z_far: float
+    step: float
 
 
 @dataclass
@@ -120,8 +151,41 @@ class TsdfVolume:
         self._check(self._lib.ekf_fusion_get_mesh(self._h, _ptr(m.xyz), _ptr(m.key), _ptr(m.grey), n))
         return m
 
+    def _render(self) -> Render:
+        w, h = C.c_int(0), C.c_int(0)
+        self._check(self._lib.ekf_raycast_get(self._h, None, None, None, C.byref(w), C.byref(h)))
+        r = Render(np.zeros((h.value, w.value), np.float32), np.zeros((h.value, w.value, 3), np.float32),
+                   np.zeros((h.value, w.value), np.uint8))
+        self._check(self._lib.ekf_raycast_get(self._h, _ptr(r.depth), _ptr(r.normal), _ptr(r.grey), None, None))
+        return r
+
+    def raycast(self, shape, K, pose7, z_near: float, z_far: float, step: Optional[float] = None, min_count: int = 1) -> Render:
+        """The volume seen by a pinhole camera of ``shape`` = (width, height) pixels, ``K`` = (fx, fy, cx, cy), at ``pose7``:
+        samples of the camera-z depth at z_near + n step up to z_far (``step`` None: voxel / 2) over the voxels with at
+        least ``min_count`` maps.  The mesh of the last ``extract`` stays valid."""
+        K = np.ascontiguousarray(K, np.float64).reshape(4)
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        step = self.voxel / 2.0 if step is None else float(step)
+        self._check(self._lib.ekf_raycast_render(self._h, int(shape[0]), int(shape[1]), _ptr(K), _ptr(pose), float(z_near),
+                                                 float(z_far), step, int(min_count)))
+        return self._render()
+
+    def raycast_view(self, dense_stereo, slot: int, z_near: float, z_far: float, step: Optional[float] = None,
+                     min_count: int = 1) -> Render:
+        """``raycast`` with the size, K and pose of a set slot of a ``DenseStereo``."""
+        step = self.voxel / 2.0 if step is None else float(step)
+        self._check(self._lib.ekf_raycast_render_view(self._h, dense_stereo._h, int(slot), float(z_near), float(z_far), step,
+                                                      int(min_count)))
+        return self._render()
+
     def profile(self, enable: bool = True):
         self._check(self._lib.ekf_fusion_profile(self._h, 1 if enable else 0))
+
+    def get_raycast_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of k_tsdf_mean and k_tsdf_raycast since the last ``profile()``."""
+        ms, cnt = np.zeros(2, np.float64), np.zeros(2, np.int64)
+        self._check(self._lib.ekf_raycast_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(RAYCAST_KERNELS)}
 
     def get_profile(self) -> dict:
         """HIP-event milliseconds and launch counts of the four kernels since the last ``profile()``."""
@@ -190,6 +254,21 @@ def auto_grid(points, voxel: Optional[float] = None, bounds=None, trunc: Optiona
         vx = vx * 2.0
 
 
+def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
+    """The steps of ``mesh_from_recording`` up to the filled volume: (vol, maps, K, images, origin, dims, voxel, trunc)."""
+    maps = dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)
+    K, ids, poses, images = dense.read_recording(directory, nodes_out)
+    origin, dims, vx, tr = auto_grid([m.points for m in maps], voxel, bounds, trunc)
+    vol = TsdfVolume(dims, origin, vx, tr, int(sweep_kwargs.get("device", 0)))
+    try:
+        for m, img in zip(maps, images):
+            vol.integrate_host(m.depth, img, K, m.pose)
+    except Exception:
+        vol.close()
+        raise
+    return vol, maps, K, images, origin, dims, vx, tr
+
+
 def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                         trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
                         **sweep_kwargs) -> RecordingMesh:
@@ -198,14 +277,57 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     truncation distance of the volume; the sweep's cost truncation, also called ``trunc`` there, is ``sweep_trunc`` here."""
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
-    maps = dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)
-    K, ids, poses, images = dense.read_recording(directory, nodes_out)
-    origin, dims, vx, tr = auto_grid([m.points for m in maps], voxel, bounds, trunc)
-    vol = TsdfVolume(dims, origin, vx, tr, int(sweep_kwargs.get("device", 0)))
+    vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        for m, img in zip(maps, images):
-            vol.integrate_host(m.depth, img, K, m.pose)
         vertices, faces, grey = weld(vol.extract(min_count))
     finally:
         vol.close()
     return RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps)
+
+
+def shade(render: Render, light=(0.0, 0.0, -1.0)) -> np.ndarray:
+    """An 8-bit Lambert image of a render, on the host: floor(255 max(0, n . l / |l|) + 0.5) where the render has depth, 0
+    elsewhere.  ``light`` is the direction towards the light in the world frame."""
+    l = np.asarray(light, np.float64).reshape(3)
+    l = l / np.sqrt(l @ l)
+    lam = np.maximum(render.normal.astype(np.float64) @ l, 0.0)
+    return np.where(render.depth > 0, np.floor(255.0 * lam + 0.5), 0.0).astype(np.uint8)
+
+
+def audit_range(maps, trunc: float):
+    """(z_near, z_far) of ``audit_recording``: the smallest and largest depth of the filtered maps, widened by trunc."""
+    z = np.concatenate([m.depth[m.depth > 0].astype(np.float64) for m in maps])
+    if not len(z):
+        raise ValueError("no depth map has a depth: nothing to render")
+    return max(0.0, float(z.min()) - float(trunc)), float(z.max()) + float(trunc)
+
+
+def audit_frame(kid: int, render: Render, depth, image) -> FrameAudit:
+    """The figures of one key frame from its render, its filtered depth map and its image."""
+    both = (render.depth > 0) & (depth > 0)
+    hit = render.depth > 0
+    rel = np.abs(render.depth[both].astype(np.float64) - depth[both].astype(np.float64)) / depth[both].astype(np.float64)
+    nan = float("nan")
+    return FrameAudit(int(kid), render, float(both.mean()), float(np.median(rel)) if len(rel) else nan,
+                      float(np.percentile(rel, 90)) if len(rel) else nan,
+                      float(np.abs(render.grey[hit].astype(np.float64) - image[hit].astype(np.float64)).mean()) if hit.any() else nan)
+
+
+def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
+                    trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
+                    **sweep_kwargs) -> RecordingAudit:
+    """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
+    recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
+    frame's filtered depth map and image: the only end-to-end check that needs no ground truth."""
+    if sweep_trunc is not None:
+        sweep_kwargs["trunc"] = sweep_trunc
+    vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
+    try:
+        vertices, faces, grey = weld(vol.extract(min_count))
+        z_near, z_far = audit_range(maps, tr)
+        h, w = images[0].shape
+        frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)
+                  for m, img in zip(maps, images)]
+    finally:
+        vol.close()
+    return RecordingAudit(RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps), frames, z_near, z_far, vx / 2.0)

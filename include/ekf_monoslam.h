@@ -837,6 +837,33 @@ int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, uns
 int ekf_fusion_profile(ekf_fusion* h, int enable);
 int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- ray casting of the TSDF volume into depth, normal and grey images ------------------------------
+ * The view of the fused surface from any pinhole pose: per pixel the camera-z depth of the first outside-to-inside
+ * crossing of the trilinearly interpolated volume, the unit normal there (world frame, towards free space) and the
+ * interpolated grey value; depth 0, normal 0, grey 0 where the ray finds none.  The functions take an ekf_fusion handle.
+ * DESIGN.md §17.1 pins every operation (fp64 coordinates rounded once in the written order, samples at
+ * z_near + n step, no atomics); tests/raycast_oracle.py restates it.  Additions only: ekf_abi_version() stays 6.
+ *  - render: a width x height view with K = (fx, fy, cx, cy) and pose7 as for ekf_dense_set_view, samples
+ *    n = 0 .. floor((z_far - z_near) / step) of the camera-z depth, over the voxels with cnt >= min_count.  The images
+ *    stay in device buffers of the handle (grow-only).  One k_tsdf_raycast launch, and one k_tsdf_mean launch before it
+ *    when the volume or min_count changed since the last render.  The mesh of the last extract stays valid.
+ *    EKF_ERR_ARG before the device is touched: width or height outside 1..8192, K not finite or fx, fy = 0, a pose that
+ *    ekf_dense_set_view would refuse, step not finite or <= 0, not 0 <= z_near < z_far finite, more than 65536 samples,
+ *    min_count outside 1..65535.  A failed allocation is EKF_ERR_DEVICE; either leaves the volume, the mesh and the
+ *    previous render as they were;
+ *  - render_view: the same with the size, K and pose of a slot of a dense handle.  A dense handle on another device is
+ *    EKF_ERR_ARG; a slot that was never set is EKF_ERR_STATE;
+ *  - get: depth = height tight rows of width floats, normal = 3 floats a pixel, grey = one byte a pixel; every pointer
+ *    may be NULL.  EKF_ERR_STATE before a render or after the volume changed since the last one (integrate, reset,
+ *    set_volume);
+ *  - get_profile: HIP-event milliseconds and launch counts of k_tsdf_mean ([0]) and k_tsdf_raycast ([1]) since the last
+ *    ekf_fusion_profile, which switches them on and off with the four entries of ekf_fusion_get_profile. */
+int ekf_raycast_render(ekf_fusion* h, int width, int height, const double* K, const double* pose7, double z_near, double z_far,
+                       double step, int min_count);
+int ekf_raycast_render_view(ekf_fusion* h, ekf_dense* dense, int slot, double z_near, double z_far, double step, int min_count);
+int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, int* width, int* height);
+int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -518,7 +518,8 @@ class DenseStereoHip {
 
 // TsdfVolumeHip -- header-only mirror of the fusion step over the ekf_fusion_* functions of
 // ekf_monoslam.h: depth maps (of a DenseStereoHip slot, or host arrays) integrated into one truncated signed distance volume
-// on the device, extract() = marching tetrahedra into a triangle soup in a fixed order.  Values are plain arrays.
+// on the device, extract() = marching tetrahedra into a triangle soup in a fixed order.  raycast() / raycastView() mirror
+// ekf_raycast_* (section 17): the volume seen from a pose as a depth, a normal and a grey image.  Values are plain arrays.
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -532,6 +533,12 @@ class TsdfVolumeHip {
     std::vector<unsigned short> cnt;
     std::vector<unsigned int> gsum;
     int maps = 0;
+  };
+  struct Render {                              // a pixel without a hit: depth 0, normal 0, grey 0
+    int width = 0, height = 0;
+    std::vector<float> depth;                  // camera-z depth, height rows of width
+    std::vector<float> normal;                 // 3 per pixel: unit, world frame, towards free space
+    std::vector<unsigned char> grey;
   };
 
   TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0)
@@ -567,6 +574,20 @@ class TsdfVolumeHip {
     check(ekf_fusion_get_mesh(f_, m.xyz.data(), m.key.data(), m.grey.data(), n));
     return m;
   }
+  // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
+  // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
+  Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
+                 int min_count = 1) {
+    check(ekf_raycast_render(f_, width, height, K, pose7, z_near, z_far, step, min_count));
+    return render();
+  }
+  // the same with the size, K and pose of a set slot of a dense handle
+  Render raycastView(DenseStereoHip& dense, int slot, double z_near, double z_far, double step, int min_count = 1) {
+    check(ekf_raycast_render_view(f_, dense.handle(), slot, z_near, z_far, step, min_count));
+    return render();
+  }
+  // HIP-event milliseconds and launch counts of k_tsdf_mean, k_tsdf_raycast (switched by profile())
+  void getRaycastProfile(double kernel_ms[2], long long launches[2]) { check(ekf_raycast_get_profile(f_, kernel_ms, launches)); }
   void profile(bool enable) { check(ekf_fusion_profile(f_, enable ? 1 : 0)); }
   // HIP-event milliseconds and launch counts of k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit
   void getProfile(double kernel_ms[4], long long launches[4]) { check(ekf_fusion_get_profile(f_, kernel_ms, launches)); }
@@ -574,6 +595,14 @@ class TsdfVolumeHip {
 
  private:
   void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_fusion_last_error(f_)); }
+  Render render() {
+    Render r;
+    check(ekf_raycast_get(f_, nullptr, nullptr, nullptr, &r.width, &r.height));
+    const size_t n = (size_t)r.width * (size_t)r.height;
+    r.depth.resize(n); r.normal.resize(n * 3); r.grey.resize(n);
+    check(ekf_raycast_get(f_, r.depth.data(), r.normal.data(), r.grey.data(), nullptr, nullptr));
+    return r;
+  }
   size_t n_;
   ekf_fusion* f_ = nullptr;
 };

@@ -1,0 +1,102 @@
+// The two kernels of csrc/ekf_raycast.hpp run lane by lane on the host: neither has a barrier or
+// LDS, so the lanes of a workgroup and the workgroups run one after another.  It reads the case files
+// tools/raycast_host_check.py writes (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs) and
+// compares bit for bit.  Build with the sanitizers on:
+//   clang++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined tools/raycast_host_check.cpp -o raycast_host_check
+// Usage: raycast_host_check case.bin [...]; prints "ok" when every case is equal.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+struct Idx3 { unsigned x, y, z; };
+static Idx3 threadIdx, blockIdx, blockDim = {256, 1, 1};
+#define __global__
+#define __device__
+#define __forceinline__ inline
+#define __shared__ static
+#define __launch_bounds__(...)
+#define __restrict__
+#define __syncthreads()
+using std::max;
+using std::min;
+#define EKF_DENSE_KERNELS_ONLY
+#define EKF_FUSION_KERNELS_ONLY
+#define EKF_RAYCAST_KERNELS_ONLY
+#include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_stereo.hpp"
+#include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_raycast.hpp"
+
+template <typename F>
+static void launch(unsigned gx, unsigned gy, F body) {
+  for (unsigned by = 0; by < gy; ++by)
+    for (unsigned bx = 0; bx < gx; ++bx)
+      for (unsigned t = 0; t < 256; ++t) {
+        threadIdx = {t, 0, 0};
+        blockIdx = {bx, by, 0};
+        body();
+      }
+}
+
+template <typename T>
+static std::vector<T> take(FILE* f, size_t n) {
+  std::vector<T> v(n);
+  if (n && fread(v.data(), sizeof(T), n, f) != n) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
+  return v;
+}
+
+template <typename T>
+static int differs(const char* what, const std::vector<T>& got, const std::vector<T>& want) {
+  size_t n = got.size() != want.size();
+  for (size_t i = 0; i < std::min(got.size(), want.size()); ++i) n += std::memcmp(&got[i], &want[i], sizeof(T)) != 0;
+  if (n) std::printf("  %s: %zu of %zu differ\n", what, n, want.size());
+  return n != 0;
+}
+
+static int run(const char* path) {
+  FILE* f = std::fopen(path, "rb");
+  if (!f) { std::perror(path); return 2; }
+  const auto hdr = take<int>(f, 7);
+  const auto par = take<double>(f, 17);
+  ekf::TsdfGrid g{hdr[0], hdr[1], hdr[2], {par[0], par[1], par[2]}, par[3]};
+  const int W = hdr[3], H = hdr[4], N = hdr[5], min_count = hdr[6];
+  const size_t nvox = (size_t)g.nx * g.ny * g.nz, npix = (size_t)W * H;
+  const auto sum = take<float>(f, nvox);
+  const auto cnt = take<unsigned short>(f, nvox);
+  const auto gsum = take<unsigned>(f, nvox);
+  const auto w_mean = take<float>(f, nvox);
+  const auto w_depth = take<float>(f, npix);
+  const auto w_normal = take<float>(f, npix * 3);
+  const auto w_grey = take<unsigned char>(f, npix);
+  std::fclose(f);
+
+  std::vector<float> mean(nvox, 1.f), depth(npix, -1.f), normal(npix * 3, -1.f);
+  std::vector<unsigned char> grey(npix, 0xA5);
+  const ekf::MeanArgs m{sum.data(), cnt.data(), mean.data(), (unsigned)nvox, min_count};
+  launch((unsigned)((nvox + 255) / 256), 1, [&] { ekf::k_tsdf_mean(m); });
+
+  ekf::RaycastArgs a{};
+  a.mean = mean.data(); a.cnt = cnt.data(); a.gsum = gsum.data();
+  a.depth = depth.data(); a.normal = normal.data(); a.grey = grey.data();
+  a.W = W; a.H = H; a.g = g; a.inv = 1.0 / g.voxel;
+  a.fx = par[4]; a.fy = par[5]; a.cx = par[6]; a.cy = par[7];
+  double q[4];
+  if (!ekf::dense_pose(&par[8], a.t, a.R, q)) return 2;
+  a.z_near = par[15]; a.step = par[16]; a.N = N;
+  launch((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), [&] { ekf::k_tsdf_raycast(a); });
+
+  size_t hits = 0;
+  for (float d : depth) hits += d > 0.f;
+  const int bad = differs("mean", mean, w_mean) + differs("depth", depth, w_depth) + differs("normal", normal, w_normal) +
+                  differs("grey", grey, w_grey);
+  std::printf("%s: %d x %d x %d, view %d x %d, %d samples, min_count %d, %zu hits: %s\n", path, g.nx, g.ny, g.nz, W, H, N, min_count,
+              hits, bad ? "DIFFERS" : "equal");
+  return bad ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
+  int rc = argc > 1 ? 0 : 64;
+  for (int i = 1; i < argc; ++i) rc |= run(argv[i]);
+  if (rc == 0) std::printf("ok\n");
+  return rc;
+}
