@@ -206,6 +206,43 @@ _PROTOS = {
 _lib = None
 
 
+def ptr(a):
+    """The data of a numpy array as void*; None stays NULL."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class Handle:
+    """Base of the wrapper classes: one handle of the family ``_family`` (``ekf``, ``ekf_sba``, ``ekf_keyframe``, ``ekf_dense``
+    or ``ekf_fusion``), which names its ``<family>_destroy`` and ``<family>_last_error``.  ``close`` may be called twice, and
+    an object whose constructor raised is deleted without harm."""
+    _family = "ekf"
+
+    def _create(self, create, *args):
+        """``<create>(*args, &handle)``; raises with the message the library keeps for a failed create."""
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        rc = getattr(self._lib, create)(*args, C.byref(self._h))
+        if rc != 0:
+            msg = getattr(self._lib, self._family + "_last_error")(None)
+            raise EkfError(rc, msg.decode() if msg else create + " failed")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            getattr(self._lib, self._family + "_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = getattr(self._lib, self._family + "_last_error")(self._h)
+            raise EkfError(rc, msg.decode() if msg else "")
+
+
 def load_library(path: str = LIB_PATH):
     """dlopen the HIP library and attach prototypes.  Fails loudly when it is missing."""
     global _lib

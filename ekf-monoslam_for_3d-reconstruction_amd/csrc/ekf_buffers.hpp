@@ -66,6 +66,55 @@ class Buf {
 template <typename T> using DevBuf = Buf<T, DeviceAlloc>;
 template <typename T> using PinnedBuf = Buf<T, PinnedAlloc>;
 
+// Per-kernel times of N kinds of launch on the null stream of the owner's device, behind a switch.  Off: run() makes no
+// event call at all.  On: it records round the launch, waits for the second event and adds the time to the kind's pair.
+// The first failing HIP call's error is returned and nothing is added.  The timer is a member of its owner: like the
+// buffers it is destroyed after the owner's destructor body, which selects the device the events were made on.
+template <int N>
+class KernelTimer {
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  bool on_ = false;
+  double ms_[N] = {};
+  long long cnt_[N] = {};
+
+ public:
+  KernelTimer() = default;
+  KernelTimer(const KernelTimer&) = delete;
+  KernelTimer& operator=(const KernelTimer&) = delete;
+  ~KernelTimer() {
+    for (hipEvent_t e : ev_)
+      if (e) (void)hipEventDestroy(e);
+  }
+
+  hipError_t create() {                 // on the current device; an event that exists is kept
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i)
+      if (!ev_[i]) e = hipEventCreate(&ev_[i]);
+    return e;
+  }
+  void enable(bool on) {                // on or off, the counters start from zero
+    on_ = on;
+    for (int i = 0; i < N; ++i) { ms_[i] = 0.0; cnt_[i] = 0; }
+  }
+  void read(double* ms, long long* cnt, int first, int count) const {
+    for (int i = 0; i < count; ++i) { ms[i] = ms_[first + i]; cnt[i] = cnt_[first + i]; }
+  }
+  // begin (if on) -> launch() -> hipGetLastError -> end (if on)
+  template <typename F>
+  hipError_t run(int which, F launch) {
+    hipError_t e;
+    if (on_ && (e = hipEventRecord(ev_[0], nullptr)) != hipSuccess) return e;
+    launch();
+    if ((e = hipGetLastError()) != hipSuccess || !on_) return e;
+    e = hipEventRecord(ev_[1], nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev_[1]);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev_[0], ev_[1]);
+    if (e == hipSuccess) { ms_[which] += ms; cnt_[which] += 1; }
+    return e;
+  }
+};
+
 // A device list of ints that is rebuilt when the key it was built for changes.  The caller drains the streams that may
 // still read the old list before it calls upload().  The key is the ONLY record of what the list holds: an owner that has to
 // know (first() is the leading key element, by convention the block-step count of a plan) reads it from here, and one that

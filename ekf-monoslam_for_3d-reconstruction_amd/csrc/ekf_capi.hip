@@ -4595,6 +4595,25 @@ void ekf_config_default(ekf_config* c) {
 
 int ekf_abi_version(void) { return EKF_ABI_VERSION; }
 
+static bool sba_finite(const double* v, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+// K = (fx, fy, cx, cy): finite with fx, fy > 0
+static bool pinhole_ok(const double* K) { return sba_finite(K, 4) && K[0] > 0.0 && K[1] > 0.0; }
+
+// What every create checks before it makes a handle: `device` names a HIP device.
+static int create_device(const char* who, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    ekf::g_create_error = std::string(who) + ": no HIP device (this library has no CPU fallback)";
+    return EKF_ERR_DEVICE;
+  }
+  return EKF_OK;
+}
+
 int ekf_create(const ekf_config* cfg, int camera_dim, int capacity_features, int dtype, int device,
                ekf_filter** out) {
   if (!out) return EKF_ERR_ARG;
@@ -4604,13 +4623,9 @@ int ekf_create(const ekf_config* cfg, int camera_dim, int capacity_features, int
     ekf::g_create_error = "ekf_create: bad argument";
     return EKF_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    ekf::g_create_error = "ekf_create: no HIP device (this library has no CPU fallback)";
-    return EKF_ERR_DEVICE;
-  }
+  int rc = create_device("ekf_create", device);
+  if (rc != EKF_OK) return rc;
   FilterBase* impl = nullptr;
-  int rc;
   if (dtype == EKF_F32) {
     auto* f = new ekf::Filter<float>();
     rc = f->init(cfg, camera_dim, capacity_features, device);
@@ -4820,12 +4835,6 @@ struct ekf_sba {
   ekf::SbaSystem* impl;
 };
 
-static bool sba_finite(const double* v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 // The node capacity of a PCG handle: 64 * capacity_nodes (above the 52 doubles of node matrices per node and the 6
 // rows per node) must fit in int; the block and vector offsets themselves are size_t.
 static const int kSbaMaxNodesPcg = INT_MAX / 64;
@@ -4839,19 +4848,16 @@ static int sba_create(const char* who, const ekf_sba_camera* K, int capacity_nod
     return EKF_ERR_ARG;
   }
   const int max_nodes = solver == EKF_SBA_SOLVER_BPCG ? kSbaMaxNodesPcg : ekf::kSbaMaxN / 6;
-  if (!K || !sba_finite(&K->fx, 4) || !(K->fx > 0.0) || !(K->fy > 0.0) || capacity_nodes < 1 ||
-      capacity_nodes > max_nodes || capacity_points < 1 || capacity_projections < 1) {
+  if (!K || !pinhole_ok(&K->fx) || capacity_nodes < 1 || capacity_nodes > max_nodes || capacity_points < 1 ||
+      capacity_projections < 1) {
     ekf::g_create_error = std::string(who) + ": bad argument (K finite with fx, fy > 0; 1 <= capacity_nodes <= " +
                           std::to_string(max_nodes) + "; capacities >= 1)";
     return EKF_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    ekf::g_create_error = std::string(who) + ": no HIP device (this library has no CPU fallback)";
-    return EKF_ERR_DEVICE;
-  }
+  int rc = create_device(who, device);
+  if (rc != EKF_OK) return rc;
   auto* s = new ekf::SbaSystem();
-  const int rc = s->init(K, capacity_nodes, capacity_points, capacity_projections, device, solver);
+  rc = s->init(K, capacity_nodes, capacity_points, capacity_projections, device, solver);
   if (rc != EKF_OK) {
     ekf::g_create_error = s->err;
     delete s;
@@ -5381,17 +5387,14 @@ int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense
     ekf::g_create_error = "ekf_dense_create: 1 <= width, height <= 8192 and 1 <= max_views <= 16";
     return EKF_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    ekf::g_create_error = "ekf_dense_create: no HIP device (this library has no CPU fallback)";
-    return EKF_ERR_DEVICE;
-  }
+  const int rc = create_device("ekf_dense_create", device);
+  if (rc != EKF_OK) return rc;
   auto* d = new ekf::DenseStereo();
   d->device = device;
   d->W = width;
   d->H = height;
   hipError_t e = hipSetDevice(device);
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&d->ev[i]);
+  if (e == hipSuccess) e = d->timer.create();
   if (e != hipSuccess) {
     ekf::g_create_error = std::string("ekf_dense_create: ") + hipGetErrorString(e);
     delete d;
@@ -5417,8 +5420,7 @@ const char* ekf_dense_last_error(const ekf_dense* h) {
 // slot in range, K finite with fx, fy > 0 (when given), pose7 a pose: what every set_view* checks before the device
 static int dense_view_args(ekf::DenseStereo* d, const char* who, int slot, const double* K, const double* pose7, double t[3],
                            double R[9], double q[4]) {
-  if (slot < 0 || slot >= d->max_views || !pose7 || !ekf::dense_pose(pose7, t, R, q) ||
-      (K && !(sba_finite(K, 4) && K[0] > 0.0 && K[1] > 0.0))) {
+  if (slot < 0 || slot >= d->max_views || !pose7 || !ekf::dense_pose(pose7, t, R, q) || (K && !pinhole_ok(K))) {
     d->err = std::string(who) + ": slot in 0..max_views-1, K finite with fx, fy > 0, pose7 finite with q != 0";
     return EKF_ERR_ARG;
   }
@@ -5641,15 +5643,13 @@ int ekf_dense_get_points(ekf_dense* h, int slot, int filtered, double* xyz) {
 
 int ekf_dense_profile(ekf_dense* h, int enable) {
   if (!h) return EKF_ERR_ARG;
-  auto* d = h->impl;
-  d->profile = enable != 0;
-  for (int i = 0; i < 2; ++i) { d->prof_ms[i] = 0.0; d->prof_cnt[i] = 0; }
+  h->impl->timer.enable(enable != 0);
   return EKF_OK;
 }
 
 int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  for (int i = 0; i < 2; ++i) { kernel_ms[i] = h->impl->prof_ms[i]; launches[i] = h->impl->prof_cnt[i]; }
+  h->impl->timer.read(kernel_ms, launches, 0, 2);
   return EKF_OK;
 }
 
@@ -5669,11 +5669,8 @@ int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel
     ekf::g_create_error = "ekf_fusion_create: 2 <= nx, ny, nz <= 1024, nx ny nz <= 2^28, origin finite, voxel and trunc finite and > 0";
     return EKF_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    ekf::g_create_error = "ekf_fusion_create: no HIP device (this library has no CPU fallback)";
-    return EKF_ERR_DEVICE;
-  }
+  const int rc = create_device("ekf_fusion_create", device);
+  if (rc != EKF_OK) return rc;
   auto* f = new ekf::TsdfFusion();
   f->device = device;
   f->g.nx = nx; f->g.ny = ny; f->g.nz = nz;
@@ -5682,7 +5679,7 @@ int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel
   f->trunc = trunc;
   hipError_t e = hipSetDevice(device);
   f->created = e == hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&f->ev[i]);
+  if (e == hipSuccess) e = f->timer.create();
   if (e == hipSuccess) e = f->sum.reserve(f->nvox());
   if (e == hipSuccess) e = f->cnt.reserve(f->nvox());
   if (e == hipSuccess) e = f->gsum.reserve(f->nvox());
@@ -5746,8 +5743,7 @@ int ekf_fusion_integrate_host(ekf_fusion* h, const float* depth, const unsigned 
   auto* f = h->impl;
   double t[3], R[9], q[4];
   if (!depth || !img || !K || !pose7 || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
-      height > ekf::kFusionMaxMapDim || pitch < width || !(sba_finite(K, 4) && K[0] > 0.0 && K[1] > 0.0) ||
-      !ekf::dense_pose(pose7, t, R, q)) {
+      height > ekf::kFusionMaxMapDim || pitch < width || !pinhole_ok(K) || !ekf::dense_pose(pose7, t, R, q)) {
     f->err = "ekf_fusion_integrate_host: depth, img, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= width; K finite "
              "with fx, fy > 0; pose7 finite with q != 0";
     return EKF_ERR_ARG;
@@ -5842,16 +5838,13 @@ int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, uns
 
 int ekf_fusion_profile(ekf_fusion* h, int enable) {
   if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  f->profile = enable != 0;
-  for (int i = 0; i < 4; ++i) { f->prof_ms[i] = 0.0; f->prof_cnt[i] = 0; }
-  for (int i = 0; i < 2; ++i) { h->rc.prof_ms[i] = 0.0; h->rc.prof_cnt[i] = 0; }
+  h->impl->timer.enable(enable != 0);   // the four kinds of the fusion and the two of the ray caster
   return EKF_OK;
 }
 
 int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  for (int i = 0; i < 4; ++i) { kernel_ms[i] = h->impl->prof_ms[i]; launches[i] = h->impl->prof_cnt[i]; }
+  h->impl->timer.read(kernel_ms, launches, 0, 4);
   return EKF_OK;
 }
 
@@ -5939,7 +5932,7 @@ int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* g
 
 int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  for (int i = 0; i < 2; ++i) { kernel_ms[i] = h->rc.prof_ms[i]; launches[i] = h->rc.prof_cnt[i]; }
+  h->impl->timer.read(kernel_ms, launches, 4, 2);
   return EKF_OK;
 }
 

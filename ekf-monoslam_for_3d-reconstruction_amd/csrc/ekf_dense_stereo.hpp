@@ -14,9 +14,9 @@
 #include <string>
 #include <vector>
 
-// EKF_DENSE_KERNELS_ONLY: the structs, the two kernel bodies and dense_pose alone, for tools/dense_host_check.cpp, which
-// runs the kernels lane by lane on the host and supplies threadIdx, __syncthreads and the like itself.
-#ifndef EKF_DENSE_KERNELS_ONLY
+// EKF_KERNELS_ONLY: the structs, the two kernel bodies and dense_pose alone, for tools/dense_host_check.cpp, which runs
+// the kernels lane by lane on the host; tools/host_kernels.hpp supplies threadIdx, __syncthreads and the like.
+#ifndef EKF_KERNELS_ONLY
 #include <hip/hip_runtime.h>
 
 #include "ekf_buffers.hpp"
@@ -250,7 +250,7 @@ inline bool dense_pose(const double* p, double t[3], double R[9], double q[4]) {
   return true;
 }
 
-#ifndef EKF_DENSE_KERNELS_ONLY
+#ifndef EKF_KERNELS_ONLY
 struct DenseView {
   DevBuf<unsigned char> img;
   DevBuf<float> depth, fdepth;
@@ -270,16 +270,11 @@ struct DenseStereo {
   int device = 0, W = 0, H = 0, max_views = 0;
   std::vector<DenseView> v;
   DevBuf<double> d_xyz;               // the points on their way to the host (allocated by the first ekf_dense_get_points)
-  bool profile = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double prof_ms[2] = {0.0, 0.0};     // k_plane_sweep, k_depth_filter_points
-  long long prof_cnt[2] = {0, 0};
+  KernelTimer<2> timer;               // k_plane_sweep, k_depth_filter_points
 
   size_t npix() const { return (size_t)W * H; }
-  ~DenseStereo() {
+  ~DenseStereo() {                    // the members (events, buffers) go after this body, on the handle's device
     if (max_views) hipSetDevice(device);
-    for (hipEvent_t e : ev)
-      if (e) hipEventDestroy(e);
   }
 
   // A (row-major) and b of source view s seen from reference view r
@@ -293,17 +288,6 @@ struct DenseStereo {
     o.fx = s.K[0]; o.fy = s.K[1]; o.cx = s.K[2]; o.cy = s.K[3];
     o.img = s.img;
     o.depth = s.depth;
-  }
-
-  hipError_t timed_begin() { return profile ? hipEventRecord(ev[0], nullptr) : hipSuccess; }
-  hipError_t timed_end(int which) {
-    if (!profile) return hipSuccess;
-    hipError_t e = hipEventRecord(ev[1], nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (e == hipSuccess) { prof_ms[which] += ms; prof_cnt[which] += 1; }
-    return e;
   }
 
   hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc) {
@@ -323,10 +307,7 @@ struct DenseStereo {
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
     r.swept = r.filtered = false;
     const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
-    if ((e = timed_begin()) != hipSuccess) return e;
-    k_plane_sweep<<<grid, 256, 0, nullptr>>>(a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = timed_end(0)) != hipSuccess) return e;
+    if ((e = timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); })) != hipSuccess) return e;
     r.swept = true;
     return hipSuccess;
   }
@@ -355,14 +336,11 @@ struct DenseStereo {
     for (int i = 0; i < 9; ++i) a.R[i] = r.R[i];
     for (int i = 0; i < 3; ++i) a.t[i] = r.t[i];
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
-    if ((e = timed_begin()) != hipSuccess) return e;
-    k_depth_filter_points<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = timed_end(1)) != hipSuccess) return e;
+    if ((e = timer.run(1, [&] { k_depth_filter_points<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(a); })) != hipSuccess) return e;
     if (n_src > 0) r.filtered = true;
     return hipSuccess;
   }
 };
-#endif  // EKF_DENSE_KERNELS_ONLY
+#endif  // EKF_KERNELS_ONLY
 
 }  // namespace ekf

@@ -14,9 +14,9 @@
 #include <string>
 #include <utility>
 
-// EKF_FUSION_KERNELS_ONLY: the structs and the kernel bodies alone, for tools/fusion_host_check.cpp, which runs the
-// kernels lane by lane on the host and supplies threadIdx, __syncthreads and the like itself.
-#ifndef EKF_FUSION_KERNELS_ONLY
+// EKF_KERNELS_ONLY: the structs and the kernel bodies alone, for tools/fusion_host_check.cpp, which runs the kernels lane
+// by lane on the host; tools/host_kernels.hpp supplies threadIdx, __syncthreads and the like.
+#ifndef EKF_KERNELS_ONLY
 #include <hip/hip_runtime.h>
 
 #include "ekf_buffers.hpp"
@@ -258,7 +258,7 @@ __global__ void __launch_bounds__(256) k_tsdf_emit(ExtractArgs a) {
   }
 }
 
-#ifndef EKF_FUSION_KERNELS_ONLY
+#ifndef EKF_KERNELS_ONLY
 // Host side of one handle (`ekf_fusion`).  Everything runs on the default stream of the handle's device, as ekf_dense_* does
 // (§15.4 (2)): a map may come straight from the device buffers of a dense handle.
 struct TsdfFusion {
@@ -281,28 +281,12 @@ struct TsdfFusion {
   bool mesh_valid = false;            // an extract since the volume last changed
   unsigned long long changes = 0;     // counts the changes of the volume (integrate, reset, ekf_fusion_set_volume): ekf_raycast.hpp
   int maps = 0;                       // maps integrated since the last reset (or what ekf_fusion_set_volume said)
-  bool profile = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double prof_ms[4] = {0.0, 0.0, 0.0, 0.0};       // k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit
-  long long prof_cnt[4] = {0, 0, 0, 0};
+  KernelTimer<6> timer;               // k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit; 4, 5: ekf_raycast.hpp
 
   size_t nvox() const { return (size_t)g.nx * g.ny * g.nz; }
   unsigned ncell() const { return (unsigned)((size_t)(g.nx - 1) * (g.ny - 1) * (g.nz - 1)); }
-  ~TsdfFusion() {
+  ~TsdfFusion() {                     // the members (events, buffers) go after this body, on the handle's device
     if (created) hipSetDevice(device);
-    for (hipEvent_t e : ev)
-      if (e) hipEventDestroy(e);
-  }
-
-  hipError_t timed_begin() { return profile ? hipEventRecord(ev[0], nullptr) : hipSuccess; }
-  hipError_t timed_end(int which) {
-    if (!profile) return hipSuccess;
-    hipError_t e = hipEventRecord(ev[1], nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (e == hipSuccess) { prof_ms[which] += ms; prof_cnt[which] += 1; }
-    return e;
   }
 
   hipError_t clear() {
@@ -327,11 +311,9 @@ struct TsdfFusion {
     for (int i = 0; i < 3; ++i) a.t[i] = t[i];
     mesh_valid = false;
     ++changes;
-    hipError_t e;
-    if ((e = timed_begin()) != hipSuccess) return e;
-    k_tsdf_integrate<<<(unsigned)((nvox() + kFusionBlock - 1) / kFusionBlock), kFusionBlock, 0, nullptr>>>(a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = timed_end(0)) != hipSuccess) return e;
+    const unsigned nblk = (unsigned)((nvox() + kFusionBlock - 1) / kFusionBlock);
+    const hipError_t e = timer.run(0, [&] { k_tsdf_integrate<<<nblk, kFusionBlock, 0, nullptr>>>(a); });
+    if (e != hipSuccess) return e;
     ++maps;
     return hipSuccess;
   }
@@ -345,14 +327,8 @@ struct TsdfFusion {
     ExtractArgs a{};
     a.sum = sum; a.cnt = cnt; a.gsum = gsum; a.g = g; a.min_count = min_count; a.ncell = nc;
     a.blk_tot = blk_tot; a.blk_off = blk_off;
-    if ((e = timed_begin()) != hipSuccess) return e;
-    k_tsdf_count<<<nblk, kFusionBlock, 0, nullptr>>>(a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = timed_end(1)) != hipSuccess) return e;
-    if ((e = timed_begin()) != hipSuccess) return e;
-    k_tsdf_scan<<<1, kFusionBlock, 0, nullptr>>>(blk_tot, blk_off, nblk);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = timed_end(2)) != hipSuccess) return e;
+    if ((e = timer.run(1, [&] { k_tsdf_count<<<nblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
+    if ((e = timer.run(2, [&] { k_tsdf_scan<<<1, kFusionBlock, 0, nullptr>>>(blk_tot, blk_off, nblk); })) != hipSuccess) return e;
     unsigned long long total = 0;
     if ((e = hipMemcpy(&total, blk_off + nblk, sizeof(total), hipMemcpyDeviceToHost)) != hipSuccess) return e;
     const size_t nv = (size_t)total * 3;
@@ -371,16 +347,13 @@ struct TsdfFusion {
     mesh_valid = false;
     if (total > 0) {
       a.xyz = m_xyz; a.key = m_key; a.grey = m_grey;
-      if ((e = timed_begin()) != hipSuccess) return e;
-      k_tsdf_emit<<<nblk, kFusionBlock, 0, nullptr>>>(a);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      if ((e = timed_end(3)) != hipSuccess) return e;
+      if ((e = timer.run(3, [&] { k_tsdf_emit<<<nblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
     }
     n_tri = total;
     mesh_valid = true;
     return hipSuccess;
   }
 };
-#endif  // EKF_FUSION_KERNELS_ONLY
+#endif  // EKF_KERNELS_ONLY
 
 }  // namespace ekf

@@ -11,8 +11,8 @@
 #include <cmath>
 #include <cstddef>
 
-// EKF_RAYCAST_KERNELS_ONLY: the structs and the kernel bodies alone, for tools/raycast_host_check.cpp, which runs the
-// kernels lane by lane on the host and supplies threadIdx and blockIdx itself.
+// EKF_KERNELS_ONLY: the structs and the kernel bodies alone, for tools/raycast_host_check.cpp, which runs the kernels lane
+// by lane on the host; tools/host_kernels.hpp supplies threadIdx, blockIdx and the like.
 #include "ekf_fusion.hpp"
 
 namespace ekf {
@@ -209,9 +209,10 @@ __global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
   a.grey[pix] = grey;
 }
 
-#ifndef EKF_RAYCAST_KERNELS_ONLY
+#ifndef EKF_KERNELS_ONLY
 // Host side: the buffers of a render, owned by the fusion handle they belong to.  The mean plane is made at the first render
-// and kept until the volume changes (TsdfFusion::changes) or min_count differs.
+// and kept until the volume changes (TsdfFusion::changes) or min_count differs.  The two launches are kinds 4 (k_tsdf_mean)
+// and 5 (k_tsdf_raycast) of the fusion handle's timer.
 struct TsdfRaycast {
   DevBuf<float> mean;
   DevBuf<float> depth, normal;
@@ -220,20 +221,8 @@ struct TsdfRaycast {
   unsigned long long mean_changes = 0, render_changes = 0;      // TsdfFusion::changes when the plane and the render were made
   int W = 0, H = 0;
   bool valid = false;                 // a render exists (of the volume as it was at render_changes)
-  double prof_ms[2] = {0.0, 0.0};     // k_tsdf_mean, k_tsdf_raycast
-  long long prof_cnt[2] = {0, 0};
 
   bool current(const TsdfFusion& f) const { return valid && render_changes == f.changes; }
-
-  static hipError_t timed_end(TsdfFusion& f, double& ms_sum, long long& count) {
-    if (!f.profile) return hipSuccess;
-    hipError_t e = hipEventRecord(f.ev[1], nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(f.ev[1]);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, f.ev[0], f.ev[1]);
-    if (e == hipSuccess) { ms_sum += ms; count += 1; }
-    return e;
-  }
 
   // (mean plane) -> grow the images -> march.  A failed allocation leaves the previous render (the new images replace the old
   // ones only when all three exist), the mesh and the volume as they were.
@@ -260,10 +249,8 @@ struct TsdfRaycast {
     if (mean_count != min_count || mean_changes != f.changes) {
       mean_count = 0;
       const MeanArgs m{f.sum, f.cnt, mean, (unsigned)f.nvox(), min_count};
-      if ((e = f.timed_begin()) != hipSuccess) return e;
-      k_tsdf_mean<<<(unsigned)((f.nvox() + kFusionBlock - 1) / kFusionBlock), kFusionBlock, 0, nullptr>>>(m);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      if ((e = timed_end(f, prof_ms[0], prof_cnt[0])) != hipSuccess) return e;
+      const unsigned nblk = (unsigned)((f.nvox() + kFusionBlock - 1) / kFusionBlock);
+      if ((e = f.timer.run(4, [&] { k_tsdf_mean<<<nblk, kFusionBlock, 0, nullptr>>>(m); })) != hipSuccess) return e;
       mean_count = min_count;
       mean_changes = f.changes;
     }
@@ -277,11 +264,8 @@ struct TsdfRaycast {
     for (int i = 0; i < 3; ++i) a.t[i] = t[i];
     a.z_near = z_near; a.step = step; a.N = N;
     valid = false;
-    if ((e = f.timed_begin()) != hipSuccess) return e;
     const dim3 grid((unsigned)((width + kRaycastTile - 1) / kRaycastTile), (unsigned)((height + kRaycastTile - 1) / kRaycastTile));
-    k_tsdf_raycast<<<grid, kRaycastTile * kRaycastTile, 0, nullptr>>>(a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = timed_end(f, prof_ms[1], prof_cnt[1])) != hipSuccess) return e;
+    if ((e = f.timer.run(5, [&] { k_tsdf_raycast<<<grid, kRaycastTile * kRaycastTile, 0, nullptr>>>(a); })) != hipSuccess) return e;
     W = width;
     H = height;
     render_changes = f.changes;
@@ -289,6 +273,6 @@ struct TsdfRaycast {
     return hipSuccess;
   }
 };
-#endif  // EKF_RAYCAST_KERNELS_ONLY
+#endif  // EKF_KERNELS_ONLY
 
 }  // namespace ekf

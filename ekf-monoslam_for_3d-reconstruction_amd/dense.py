@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import capi, formats
-from .capi import EkfError
+from .capi import ptr as _ptr
 
 MAX_VIEWS, MAX_SOURCES = 16, 8
 
@@ -32,38 +32,14 @@ class DepthMap:
     points: np.ndarray             # (H, W, 3) float64 of the filtered map, NaN where there is no depth
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class DenseStereo:
+class DenseStereo(capi.Handle):
     """Up to ``max_views`` (<= 16) pinhole views of one size on the device; slots are 0 .. max_views - 1."""
+    _family = "ekf_dense"
 
     def __init__(self, width: int, height: int, max_views: int = MAX_VIEWS, device: int = 0):
-        self._lib = capi.load_library()
-        self._h = C.c_void_p()
-        rc = self._lib.ekf_dense_create(int(width), int(height), int(max_views), int(device), C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.ekf_dense_last_error(None)
-            raise EkfError(rc, msg.decode() if msg else "ekf_dense_create failed")
+        self._create("ekf_dense_create", int(width), int(height), int(max_views), int(device))
         self.width, self.height, self.max_views, self.device = int(width), int(height), int(max_views), int(device)
         self.shape = (self.height, self.width)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.ekf_dense_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.ekf_dense_last_error(self._h)
-            raise EkfError(rc, msg.decode() if msg else "")
 
     # ---- views ----
     def set_view(self, slot: int, image, K, pose7):

@@ -14,15 +14,11 @@ from typing import Optional
 import numpy as np
 
 from . import capi, dense
-from .capi import EkfError
+from .capi import ptr as _ptr
 
 MAX_DIM, MAX_VOXELS, MAX_MAPS = 1024, 1 << 28, 65535
 KERNELS = ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")
 RAYCAST_KERNELS = ("k_tsdf_mean", "k_tsdf_raycast")
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 @dataclass
@@ -74,37 +70,17 @@ class RecordingMesh:
     maps: list                     # the DepthMaps that were fused
 
 
-class TsdfVolume:
+class TsdfVolume(capi.Handle):
     """``dims`` = (nx, ny, nz) voxels of side ``voxel`` on the device; the centre of voxel (i, j, k) is origin + (i, j, k) voxel.
     The planes are numpy arrays of shape (nz, ny, nx): x fastest."""
+    _family = "ekf_fusion"
 
     def __init__(self, dims, origin, voxel: float, trunc: float, device: int = 0):
-        self._lib = capi.load_library()
-        self._h = C.c_void_p()
         nx, ny, nz = (int(v) for v in dims)
         o = np.ascontiguousarray(origin, np.float64).reshape(3)
-        rc = self._lib.ekf_fusion_create(nx, ny, nz, _ptr(o), float(voxel), float(trunc), int(device), C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.ekf_fusion_last_error(None)
-            raise EkfError(rc, msg.decode() if msg else "ekf_fusion_create failed")
+        self._create("ekf_fusion_create", nx, ny, nz, _ptr(o), float(voxel), float(trunc), int(device))
         self.dims, self.origin, self.voxel, self.trunc, self.device = (nx, ny, nz), o, float(voxel), float(trunc), int(device)
         self.shape = (nz, ny, nx)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.ekf_fusion_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.ekf_fusion_last_error(self._h)
-            raise EkfError(rc, msg.decode() if msg else "")
 
     def integrate(self, dense_stereo, slot: int, filtered: bool = True):
         """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""

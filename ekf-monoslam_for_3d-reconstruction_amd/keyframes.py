@@ -49,46 +49,26 @@ class KeyframeResult:
         return ACTION_NAMES.get(self.action, str(self.action))
 
 
-class KeyframeSelector:
+class KeyframeSelector(capi.Handle):
     """monoslam_ransac.cpp:585-687 for one (unsharded) filter."""
+    _family = "ekf_keyframe"
 
     def __init__(self, filter, move_thresh: float = 18.0, keep_current_projections: bool = False, raw_shape=None):
         """``raw_shape`` = (H, W) or (H, W, 3) of the camera's own frame makes a raw selector: it also keeps the frame
         given to ``VSlamFilter.setFrameRaw`` / ``captureNewFrame`` for the candidate and the emitted key frame."""
-        self._lib = capi.load_library()
         self._filter = filter
-        self._h = C.c_void_p()
         self.raw_shape = None if raw_shape is None else tuple(int(v) for v in raw_shape)
         if self.raw_shape is None:
-            rc = self._lib.ekf_keyframe_create(filter._h, float(move_thresh), C.byref(self._h))
+            self._create("ekf_keyframe_create", filter._h, float(move_thresh))
         else:
             if len(self.raw_shape) not in (2, 3):
                 raise ValueError("raw_shape is (H, W) or (H, W, 3)")
-            rc = self._lib.ekf_keyframe_create_raw(filter._h, float(move_thresh), self.raw_shape[1], self.raw_shape[0],
-                                                   1 if len(self.raw_shape) == 2 else self.raw_shape[2], C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.ekf_keyframe_last_error(None)
-            raise EkfError(rc, msg.decode() if msg else "ekf_keyframe_create failed")
+            self._create("ekf_keyframe_create_raw", filter._h, float(move_thresh), self.raw_shape[1], self.raw_shape[0],
+                         1 if len(self.raw_shape) == 2 else self.raw_shape[2])
         self.move_thresh = float(move_thresh)
         self.image_shape = (int(filter._cfg.image_height), int(filter._cfg.image_width))
         if keep_current_projections:
             self._check(self._lib.ekf_keyframe_set_option(self._h, capi.EKF_KF_OPT_KEEP_CURRENT_PROJECTIONS, 1))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.ekf_keyframe_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.ekf_keyframe_last_error(self._h)
-            raise EkfError(rc, msg.decode() if msg else "")
 
     def observe(self, frame_id: int) -> KeyframeResult:
         """Call after the frame's update.  On EMIT_* the result carries the emitted record."""

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import formats
-from .capi import EkfError, load_library
+from .capi import Handle, ptr as _ptr
 
 REFERENCE_SBA_CAMERA = (2217.0187, 2217.0187, 1280.5, 960.5)     # sba_add.cpp:206-211 (fx, fy, cx, cy)
 SOLVERS = {"cholesky": 0, "pcg": 3}                              # doSBA's useCSparse (SBA_BLOCK_JACOBIAN_PCG = 3)
@@ -28,46 +28,22 @@ class SbaCamera(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-class BundleAdjuster:
+class BundleAdjuster(Handle):
     """One bundle-adjustment problem on the GPU (SysSBA restricted to what sba_add uses)."""
+    _family = "ekf_sba"
 
     def __init__(self, camera=REFERENCE_SBA_CAMERA, capacity_nodes=256, capacity_points=65536,
                  capacity_projections=262144, device=0, solver="cholesky", cg_tol=1e-8, cg_max_iters=100):
         if solver not in SOLVERS:
             raise ValueError("solver must be 'cholesky' or 'pcg'")
-        self._lib = load_library()
-        self._h = C.c_void_p()
         cam = SbaCamera(*[float(c) for c in camera])
+        caps = (C.byref(cam), int(capacity_nodes), int(capacity_points), int(capacity_projections), int(device))
         if solver == "cholesky":
-            rc = self._lib.ekf_sba_create(C.byref(cam), int(capacity_nodes), int(capacity_points),
-                                          int(capacity_projections), int(device), C.byref(self._h))
+            self._create("ekf_sba_create", *caps)
         else:
-            rc = self._lib.ekf_sba_create_solver(C.byref(cam), int(capacity_nodes), int(capacity_points),
-                                                 int(capacity_projections), int(device), SOLVERS[solver],
-                                                 C.byref(self._h))
-        if rc:
-            raise EkfError(rc, self._lib.ekf_sba_last_error(None).decode())
+            self._create("ekf_sba_create_solver", *caps, SOLVERS[solver])
         self.camera = tuple(float(c) for c in camera)
         self.set_cg(cg_tol, cg_max_iters)
-
-    def close(self):
-        if self._h:
-            self._lib.ekf_sba_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc:
-            raise EkfError(rc, self._lib.ekf_sba_last_error(self._h).decode())
 
     # --- building ---------------------------------------------------------------------------------------
     def add_nodes(self, pose7):

@@ -51,44 +51,22 @@ def sim_config() -> dict:
                 k1=0.0, k2=0.0, k3=0.0, p1=0.0, p2=0.0, image_width=256, image_height=192)
 
 
-class VSlamFilter:
+class VSlamFilter(capi.Handle):
     """Drop-in shaped like the reference `VSlamFilter` (math methods only)."""
 
     def __init__(self, config: Optional[dict] = None, capacity_features: int = 1024,
                  dtype=np.float32, camera_dim: int = STATE_DIM, device: int = 0):
-        self._lib = capi.load_library()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise EkfError(1, "dtype must be float32 or float64")
         self._cfg = _cfg_from(**(config or {}))
-        self._h = C.c_void_p()
-        rc = self._lib.ekf_create(C.byref(self._cfg), camera_dim, capacity_features,
-                                  capi.EKF_F32 if self.dtype == np.float32 else capi.EKF_F64,
-                                  device, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.ekf_last_error(None)
-            raise EkfError(rc, msg.decode() if msg else "ekf_create failed")
+        self._create("ekf_create", C.byref(self._cfg), camera_dim, capacity_features,
+                     capi.EKF_F32 if self.dtype == np.float32 else capi.EKF_F64, device)
         self.camera_dim = camera_dim
         self._old_ts = -1.0
         self._raw_shape = None                                       # of the raw frame the filter holds (setFrameRaw)
 
     # -- plumbing ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.ekf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.ekf_last_error(self._h)
-            raise EkfError(rc, msg.decode() if msg else "")
-
     def _count(self, rc):
         if rc < 0:
             msg = self._lib.ekf_last_error(self._h)
@@ -97,7 +75,7 @@ class VSlamFilter:
 
     @staticmethod
     def _ptr(a):
-        return a.ctypes.data_as(C.c_void_p)
+        return capi.ptr(a)
 
     def set_option(self, option: int, value: int):
         self._check(self._lib.ekf_set_option(self._h, option, value))

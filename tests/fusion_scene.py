@@ -29,6 +29,9 @@ SPHERE_DIMS = (17, 15, 13)
 SPHERE_VOXEL, SPHERE_TRUNC, SPHERE_RADIUS = 0.25, 0.5, 1.25
 SPHERE_ORIGIN = np.array([-2.0, -1.75, -1.5], np.float64)          # the centre (0, 0, 0) is voxel (8, 7, 6)
 
+# the cases tools/fusion_host_check.py writes: the main volume at three min_count, the one-cell volume, the sphere, no maps
+HOST_CHECK_CASES = ("main_min1", "main_min2", "main_min4", "tiny", "sphere", "empty")
+
 
 def synthetic_map(n):
     """(depth float32 with holes, image uint8, K, pose) of map n = 0, 1, 2."""

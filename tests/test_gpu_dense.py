@@ -213,7 +213,12 @@ def test_error_paths_leave_the_results_readable(pkg):
     prof = d.get_profile()
     print("profile", prof)
     assert prof["k_plane_sweep"][1] == 1 and prof["k_depth_filter_points"][1] == 1 and prof["k_plane_sweep"][0] > 0
+    d.profile(True)                                                 # a second profile(True) starts from zero
+    assert set(d.get_profile().values()) == {(0.0, 0)}
     d.profile(False)
+    d.sweep(0, src, ds.W_MIN, ds.W_MAX, D, radius, trunc)           # switched off, launches leave the counts where they were
+    d.filter(0, src, REL_TOL, 2)
+    assert set(d.get_profile().values()) == {(0.0, 0)}
     d.close()
 
 

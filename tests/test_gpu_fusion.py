@@ -234,7 +234,12 @@ def test_error_paths_leave_the_volume_and_the_mesh_readable(pkg):
     prof = v.get_profile()
     print("profile", prof)
     assert [prof[k][1] for k in ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")] == [1, 1, 1, 1] and prof["k_tsdf_integrate"][0] > 0
+    v.profile(True)                                                 # a second profile(True) starts from zero
+    assert set(v.get_profile().values()) == {(0.0, 0)}
     v.profile(False)
+    v.integrate_host(*o["maps"][0])                                 # switched off, launches leave the counts where they were
+    v.extract(1)
+    assert set(v.get_profile().values()) == {(0.0, 0)}
     d.close()
     v.close()
 

@@ -119,7 +119,11 @@ def test_second_render_is_identical_and_the_mean_plane_cache_follows_min_count(p
     print("profile", prof)
     assert prof["k_tsdf_raycast"][1] == 5 and prof["k_tsdf_mean"][1] == 3 and prof["k_tsdf_raycast"][0] > 0      # 1, (1), (1), 2, 1
     assert [v.get_profile()[k][1] for k in ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")] == [0, 0, 0, 0]
+    v.profile(True)                                                 # a second profile(True) starts from zero
+    assert set(v.get_raycast_profile().values()) == {(0.0, 0)}
     v.profile(False)
+    assert _bytes(_cast(v, c[2])) == _bytes(seq[1])                 # switched off, launches leave the counts where they were
+    assert set(v.get_raycast_profile().values()) == {(0.0, 0)} and set(v.get_profile().values()) == {(0.0, 0)}
     for got, mc in zip(seq, (1, 2, 1)):
         fresh = _main(pkg)
         assert _bytes(got) == _bytes(_cast(fresh, c[mc])) and _same(got, _cases()["main_0_min%d" % mc][1]), mc

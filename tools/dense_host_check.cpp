@@ -1,60 +1,9 @@
-// The two kernels of csrc/ekf_dense_stereo.hpp run lane by lane on the host: one host thread per
-// lane, a pthread barrier for __syncthreads, `static` arrays for LDS, the workgroups one after another.  It reads the case
-// files tools/dense_host_check.py writes (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs)
-// and compares bit for bit.  Build with the sanitizers on:
-//   clang++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -pthread tools/dense_host_check.cpp -o dense_host_check
-// Usage: dense_host_check case.bin [...]; prints "ok" when every case is equal.
-#include <pthread.h>
+// The two kernels of csrc/ekf_dense_stereo.hpp run lane by lane on the host by host_kernels.hpp,
+// which says how to build and run this.  It reads the case files tools/dense_host_check.py writes (inputs in buffers of
+// exactly the device's sizes, and the numpy oracle's outputs) and compares bit for bit.
+#include "host_kernels.hpp"
 
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-
-struct Idx3 { unsigned x, y, z; };
-static thread_local Idx3 threadIdx, blockIdx;
-static Idx3 blockDim = {256, 1, 1};
-static pthread_barrier_t g_barrier;
-#define __global__
-#define __shared__ static
-#define __launch_bounds__(...)
-#define __restrict__
-#define __syncthreads() pthread_barrier_wait(&g_barrier)
-using std::max;
-using std::min;
-#define EKF_DENSE_KERNELS_ONLY
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_stereo.hpp"
-
-template <typename Args>
-static void launch(void (*kernel)(Args), Idx3 grid, const Args& a) {
-  for (unsigned by = 0; by < grid.y; ++by)
-    for (unsigned bx = 0; bx < grid.x; ++bx) {
-      std::vector<std::thread> lanes;
-      for (unsigned t = 0; t < 256; ++t)
-        lanes.emplace_back([=] {
-          threadIdx = {t, 0, 0};
-          blockIdx = {bx, by, 0};
-          kernel(a);
-        });
-      for (auto& l : lanes) l.join();
-    }
-}
-
-template <typename T>
-static std::vector<T> take(FILE* f, size_t n) {
-  std::vector<T> v(n);
-  if (n && fread(v.data(), sizeof(T), n, f) != n) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
-  return v;
-}
-
-template <typename T>
-static int differs(const char* what, const std::vector<T>& got, const std::vector<T>& want) {
-  size_t n = 0;
-  for (size_t i = 0; i < got.size(); ++i) n += std::memcmp(&got[i], &want[i], sizeof(T)) != 0;
-  if (n) std::printf("  %s: %zu of %zu differ\n", what, n, got.size());
-  return n != 0;
-}
 
 // case file: ints W H D radius trunc n_src min_agree; doubles w_min w_max rel_tol; per view (0 = reference, then the
 // sources) 4 + 7 doubles (K, pose) and W H bytes; the sources' swept depths; then the oracle: depth plane cost views of the
@@ -115,7 +64,7 @@ static int run(const char* path) {
   a.w_min = par[0];
   a.step = (par[1] - par[0]) / (double)(D - 1);
   for (int v = 1; v <= n_src; ++v) relative(v, a.s[v - 1]);
-  launch(ekf::k_plane_sweep, Idx3{(unsigned)((W + ekf::kDenseTW - 1) / ekf::kDenseTW), (unsigned)((H + ekf::kDenseTH - 1) / ekf::kDenseTH), 1}, a);
+  launch({(unsigned)((W + ekf::kDenseTW - 1) / ekf::kDenseTW), (unsigned)((H + ekf::kDenseTH - 1) / ekf::kDenseTH), 1}, [&] { ekf::k_plane_sweep(a); });
 
   ekf::FilterArgs fa{};
   fa.depth = depth.data(); fa.plane = plane.data(); fa.out_depth = fdepth.data(); fa.out_plane = fplane.data(); fa.xyz = nullptr;
@@ -125,24 +74,16 @@ static int run(const char* path) {
   std::copy(&t[0], &t[3], fa.t);
   for (int v = 1; v <= n_src; ++v) relative(v, fa.s[v - 1]);
   const Idx3 grid1 = {(unsigned)((n + 255) / 256), 1, 1};
-  launch(ekf::k_depth_filter_points, grid1, fa);
+  launch(grid1, [&] { ekf::k_depth_filter_points(fa); });
   fa.n_src = 0; fa.out_depth = nullptr; fa.out_plane = nullptr;
   fa.xyz = pts.data();
-  launch(ekf::k_depth_filter_points, grid1, fa);
+  launch(grid1, [&] { ekf::k_depth_filter_points(fa); });
   fa.depth = fdepth.data(); fa.plane = fplane.data(); fa.xyz = fpts.data();
-  launch(ekf::k_depth_filter_points, grid1, fa);
+  launch(grid1, [&] { ekf::k_depth_filter_points(fa); });
 
   const int bad = differs("depth", depth, w_depth) + differs("plane", plane, w_plane) + differs("cost", cost, w_cost) +
                   differs("views", views, w_views) + differs("filtered depth", fdepth, w_fdepth) +
                   differs("filtered plane", fplane, w_fplane) + differs("points", pts, w_pts) + differs("filtered points", fpts, w_fpts);
   std::printf("%s: %d x %d, D %d, radius %d, trunc %d, %d sources: %s\n", path, W, H, D, radius, trunc, n_src, bad ? "DIFFERS" : "equal");
   return bad ? 1 : 0;
-}
-
-int main(int argc, char** argv) {
-  pthread_barrier_init(&g_barrier, nullptr, 256);
-  int rc = argc > 1 ? 0 : 64;
-  for (int i = 1; i < argc; ++i) rc |= run(argv[i]);
-  if (rc == 0) std::printf("ok\n");
-  return rc;
 }

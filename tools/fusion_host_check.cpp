@@ -1,64 +1,10 @@
-// The four kernels of csrc/ekf_fusion.hpp run lane by lane on the host: one host thread per lane,
-// a pthread barrier for __syncthreads, `static` arrays for LDS, the workgroups one after another.  It reads the case files
-// tools/fusion_host_check.py writes (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs) and
-// compares bit for bit.  Build with the sanitizers on:
-//   clang++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -pthread tools/fusion_host_check.cpp -o fusion_host_check
-// Usage: fusion_host_check case.bin [...]; prints "ok" when every case is equal.
-#include <pthread.h>
+// The four kernels of csrc/ekf_fusion.hpp run lane by lane on the host by host_kernels.hpp, which
+// says how to build and run this.  It reads the case files tools/fusion_host_check.py writes (inputs in buffers of exactly
+// the device's sizes, and the numpy oracle's outputs) and compares bit for bit.
+#include "host_kernels.hpp"
 
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-struct Idx3 { unsigned x, y, z; };
-static thread_local Idx3 threadIdx, blockIdx;
-static Idx3 blockDim = {256, 1, 1};
-static pthread_barrier_t g_barrier;
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(...)
-#define __restrict__
-#define __syncthreads() pthread_barrier_wait(&g_barrier)
-using std::max;
-using std::min;
-#define EKF_DENSE_KERNELS_ONLY
-#define EKF_FUSION_KERNELS_ONLY
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_stereo.hpp"
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_fusion.hpp"
-
-template <typename F>
-static void launch(unsigned nblk, F body) {
-  for (unsigned bx = 0; bx < nblk; ++bx) {
-    std::vector<std::thread> lanes;
-    for (unsigned t = 0; t < 256; ++t)
-      lanes.emplace_back([=] {
-        threadIdx = {t, 0, 0};
-        blockIdx = {bx, 0, 0};
-        body();
-      });
-    for (auto& l : lanes) l.join();
-  }
-}
-
-template <typename T>
-static std::vector<T> take(FILE* f, size_t n) {
-  std::vector<T> v(n);
-  if (n && fread(v.data(), sizeof(T), n, f) != n) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
-  return v;
-}
-
-template <typename T>
-static int differs(const char* what, const std::vector<T>& got, const std::vector<T>& want) {
-  size_t n = got.size() != want.size();
-  for (size_t i = 0; i < std::min(got.size(), want.size()); ++i) n += std::memcmp(&got[i], &want[i], sizeof(T)) != 0;
-  if (n) std::printf("  %s: %zu of %zu differ\n", what, n, want.size());
-  return n != 0;
-}
 
 static int run(const char* path) {
   FILE* f = std::fopen(path, "rb");
@@ -97,7 +43,7 @@ static int run(const char* path) {
     a.fx = mp.K[0]; a.fy = mp.K[1]; a.cx = mp.K[2]; a.cy = mp.K[3];
     double q[4];
     if (!ekf::dense_pose(mp.pose.data(), a.t, a.R, q)) return 2;
-    launch((unsigned)((nvox + 255) / 256), [&] { ekf::k_tsdf_integrate(a); });
+    launch({(unsigned)((nvox + 255) / 256), 1, 1}, [&] { ekf::k_tsdf_integrate(a); });
   }
 
   const unsigned ncell = (unsigned)((size_t)(g.nx - 1) * (g.ny - 1) * (g.nz - 1)), nblk = (ncell + 255) / 256;
@@ -106,26 +52,18 @@ static int run(const char* path) {
   ekf::ExtractArgs e{};
   e.sum = sum.data(); e.cnt = cnt.data(); e.gsum = gsum.data(); e.g = g; e.min_count = min_count; e.ncell = ncell;
   e.blk_tot = tot.data(); e.blk_off = off.data();
-  launch(nblk, [&] { ekf::k_tsdf_count(e); });
-  launch(1, [&] { ekf::k_tsdf_scan(tot.data(), off.data(), nblk); });
+  launch({nblk, 1, 1}, [&] { ekf::k_tsdf_count(e); });
+  launch({1, 1, 1}, [&] { ekf::k_tsdf_scan(tot.data(), off.data(), nblk); });
   const size_t n_tri = (size_t)off[nblk];
   std::vector<double> xyz(n_tri * 9);
   std::vector<unsigned long long> key(n_tri * 3);
   std::vector<unsigned char> grey(n_tri * 3);
   e.xyz = xyz.data(); e.key = key.data(); e.grey = grey.data();
-  if (n_tri) launch(nblk, [&] { ekf::k_tsdf_emit(e); });
+  if (n_tri) launch({nblk, 1, 1}, [&] { ekf::k_tsdf_emit(e); });
 
   const int bad = differs("sum", sum, w_sum) + differs("cnt", cnt, w_cnt) + differs("gsum", gsum, w_gsum) +
                   differs("xyz", xyz, w_xyz) + differs("key", key, w_key) + differs("grey", grey, w_grey);
   std::printf("%s: %d x %d x %d, %d maps, min_count %d, %zu triangles (oracle %zu): %s\n", path, g.nx, g.ny, g.nz, n_maps,
               min_count, n_tri, n_want, bad ? "DIFFERS" : "equal");
   return bad ? 1 : 0;
-}
-
-int main(int argc, char** argv) {
-  pthread_barrier_init(&g_barrier, nullptr, 256);
-  int rc = argc > 1 ? 0 : 64;
-  for (int i = 1; i < argc; ++i) rc |= run(argv[i]);
-  if (rc == 0) std::printf("ok\n");
-  return rc;
 }

@@ -1,57 +1,10 @@
-// The two kernels of csrc/ekf_raycast.hpp run lane by lane on the host: neither has a barrier or
-// LDS, so the lanes of a workgroup and the workgroups run one after another.  It reads the case files
-// tools/raycast_host_check.py writes (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs) and
-// compares bit for bit.  Build with the sanitizers on:
-//   clang++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined tools/raycast_host_check.cpp -o raycast_host_check
-// Usage: raycast_host_check case.bin [...]; prints "ok" when every case is equal.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+// The two kernels of csrc/ekf_raycast.hpp run lane by lane on the host by host_kernels.hpp, which
+// says how to build and run this.  It reads the case files tools/raycast_host_check.py writes (inputs in buffers of exactly
+// the device's sizes, and the numpy oracle's outputs) and compares bit for bit.
+#include "host_kernels.hpp"
 
-struct Idx3 { unsigned x, y, z; };
-static Idx3 threadIdx, blockIdx, blockDim = {256, 1, 1};
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(...)
-#define __restrict__
-#define __syncthreads()
-using std::max;
-using std::min;
-#define EKF_DENSE_KERNELS_ONLY
-#define EKF_FUSION_KERNELS_ONLY
-#define EKF_RAYCAST_KERNELS_ONLY
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_stereo.hpp"
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_raycast.hpp"
-
-template <typename F>
-static void launch(unsigned gx, unsigned gy, F body) {
-  for (unsigned by = 0; by < gy; ++by)
-    for (unsigned bx = 0; bx < gx; ++bx)
-      for (unsigned t = 0; t < 256; ++t) {
-        threadIdx = {t, 0, 0};
-        blockIdx = {bx, by, 0};
-        body();
-      }
-}
-
-template <typename T>
-static std::vector<T> take(FILE* f, size_t n) {
-  std::vector<T> v(n);
-  if (n && fread(v.data(), sizeof(T), n, f) != n) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
-  return v;
-}
-
-template <typename T>
-static int differs(const char* what, const std::vector<T>& got, const std::vector<T>& want) {
-  size_t n = got.size() != want.size();
-  for (size_t i = 0; i < std::min(got.size(), want.size()); ++i) n += std::memcmp(&got[i], &want[i], sizeof(T)) != 0;
-  if (n) std::printf("  %s: %zu of %zu differ\n", what, n, want.size());
-  return n != 0;
-}
 
 static int run(const char* path) {
   FILE* f = std::fopen(path, "rb");
@@ -73,7 +26,7 @@ static int run(const char* path) {
   std::vector<float> mean(nvox, 1.f), depth(npix, -1.f), normal(npix * 3, -1.f);
   std::vector<unsigned char> grey(npix, 0xA5);
   const ekf::MeanArgs m{sum.data(), cnt.data(), mean.data(), (unsigned)nvox, min_count};
-  launch((unsigned)((nvox + 255) / 256), 1, [&] { ekf::k_tsdf_mean(m); });
+  launch({(unsigned)((nvox + 255) / 256), 1, 1}, [&] { ekf::k_tsdf_mean(m); });
 
   ekf::RaycastArgs a{};
   a.mean = mean.data(); a.cnt = cnt.data(); a.gsum = gsum.data();
@@ -83,7 +36,7 @@ static int run(const char* path) {
   double q[4];
   if (!ekf::dense_pose(&par[8], a.t, a.R, q)) return 2;
   a.z_near = par[15]; a.step = par[16]; a.N = N;
-  launch((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), [&] { ekf::k_tsdf_raycast(a); });
+  launch({(unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), 1}, [&] { ekf::k_tsdf_raycast(a); });
 
   size_t hits = 0;
   for (float d : depth) hits += d > 0.f;
@@ -92,11 +45,4 @@ static int run(const char* path) {
   std::printf("%s: %d x %d x %d, view %d x %d, %d samples, min_count %d, %zu hits: %s\n", path, g.nx, g.ny, g.nz, W, H, N, min_count,
               hits, bad ? "DIFFERS" : "equal");
   return bad ? 1 : 0;
-}
-
-int main(int argc, char** argv) {
-  int rc = argc > 1 ? 0 : 64;
-  for (int i = 1; i < argc; ++i) rc |= run(argv[i]);
-  if (rc == 0) std::printf("ok\n");
-  return rc;
 }
