@@ -201,6 +201,18 @@ _PROTOS = {
     "ekf_raycast_render_view": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int]),
     "ekf_raycast_get": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ekf_raycast_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_dense_set_view_colour": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    "ekf_dense_set_view_colour_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    "ekf_dense_set_view_colour_from_keyframe": (C.c_int, [_P, C.c_int, _P, _P]),
+    "ekf_dense_get_view_colour": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "ekf_colour_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
+    "ekf_colour_has": (C.c_int, [_P]),
+    "ekf_colour_integrate_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ekf_colour_get_volume": (C.c_int, [_P, _P]),
+    "ekf_colour_set_volume": (C.c_int, [_P, _P]),
+    "ekf_colour_get_mesh": (C.c_int, [_P, _P, C.c_ulonglong]),
+    "ekf_colour_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_colour_get_render": (C.c_int, [_P, _P]),
 }
 
 _lib = None

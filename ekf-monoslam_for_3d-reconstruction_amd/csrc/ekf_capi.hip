@@ -5450,7 +5450,7 @@ static int dense_set_view(ekf_dense* h, const char* who, int slot, const void* i
   ekf::DenseView& v = d->v[slot];
   HIPCHK(hipSetDevice(d->device));
   HIPCHK(v.img.reserve(d->npix()));
-  v.set = false;
+  v.set = v.colour = false;
   if (device_src)
     HIPCHK(hipMemcpy2DAsync(v.img, (size_t)d->W, img, (size_t)pitch, (size_t)d->W, (size_t)d->H, hipMemcpyDeviceToDevice, nullptr));
   else
@@ -5494,7 +5494,7 @@ int ekf_dense_set_view_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe*
   ekf::DenseView& v = d->v[slot];
   HIPCHK(hipSetDevice(d->device));
   HIPCHK(v.img.reserve(d->npix()));
-  v.set = false;
+  v.set = v.colour = false;
   const ekf::RectCam c = ekf::rect_cam(k->cam, raw ? k->scale : 1);
   const ekf::RectifyArgs a{raw ? k->d_emit_raw : k->d_emit, v.img, W, H, c};
   const int grid = (int)std::min<size_t>((d->npix() + 255) / 256, 1024);
@@ -5504,6 +5504,104 @@ int ekf_dense_set_view_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe*
   ekf::rect_camera(c, K);
   dense_commit(v, K, t, R, q);
   v.set = true;
+  return EKF_OK;
+}
+
+// ---- colour views: the slot keeps the B, G, R image, its grey image is k_bgr_to_grey of it
+static int dense_set_view_colour(ekf_dense* h, const char* who, int slot, const void* bgr, int pitch, const double* K,
+                                 const double* pose7, bool device_src) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  double t[3], R[9], q[4];
+  if (!bgr || !K || pitch < 3 * d->W) {
+    d->err = std::string(who) + ": bgr and K must not be NULL and pitch >= 3 width";
+    return EKF_ERR_ARG;
+  }
+  const int rc = dense_view_args(d, who, slot, K, pose7, t, R, q);
+  if (rc != EKF_OK) return rc;
+  std::string& err = d->err;
+  ekf::DenseView& v = d->v[slot];
+  const size_t row = 3 * (size_t)d->W;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(v.img.reserve(d->npix()));
+  HIPCHK(v.bgr.reserve(3 * d->npix()));
+  v.set = v.colour = false;
+  if (device_src)
+    HIPCHK(hipMemcpy2DAsync(v.bgr, row, bgr, (size_t)pitch, row, (size_t)d->H, hipMemcpyDeviceToDevice, nullptr));
+  else
+    HIPCHK(hipMemcpy2D(v.bgr, row, bgr, (size_t)pitch, row, (size_t)d->H, hipMemcpyHostToDevice));
+  HIPCHK(d->grey_from_colour(v));
+  dense_commit(v, K, t, R, q);
+  v.set = v.colour = true;
+  return EKF_OK;
+}
+
+int ekf_dense_set_view_colour(ekf_dense* h, int slot, const unsigned char* bgr, int pitch, const double* K, const double* pose7) {
+  return dense_set_view_colour(h, "ekf_dense_set_view_colour", slot, bgr, pitch, K, pose7, false);
+}
+
+int ekf_dense_set_view_colour_device(ekf_dense* h, int slot, const void* d_bgr, int pitch, const double* K, const double* pose7) {
+  return dense_set_view_colour(h, "ekf_dense_set_view_colour_device", slot, d_bgr, pitch, K, pose7, true);
+}
+
+int ekf_dense_set_view_colour_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, const double* pose7) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  double t[3], R[9], q[4];
+  if (!selector) {
+    d->err = "ekf_dense_set_view_colour_from_keyframe: a selector";
+    return EKF_ERR_ARG;
+  }
+  const int rc = dense_view_args(d, "ekf_dense_set_view_colour_from_keyframe", slot, nullptr, pose7, t, R, q);
+  if (rc != EKF_OK) return rc;
+  auto* k = selector->impl;
+  if (k->raw_w != d->W || k->raw_h != d->H || k->raw_c != 3 || k->device != d->device) {
+    d->err = "ekf_dense_set_view_colour_from_keyframe: the selector's raw image must have the handle's size, three channels and "
+             "the handle's device";
+    return EKF_ERR_ARG;
+  }
+  if (!k->have_emit || !k->emit_has_raw || k->scale < 1) {
+    d->err = "ekf_dense_set_view_colour_from_keyframe: no emitted key frame with a raw image (the rules of "
+             "ekf_keyframe_get_raw_image)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  ekf::DenseView& v = d->v[slot];
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(v.img.reserve(d->npix()));
+  HIPCHK(v.bgr.reserve(3 * d->npix()));
+  v.set = v.colour = false;
+  const ekf::RectCam c = ekf::rect_cam(k->cam, k->scale);
+  const ekf::RectifyArgs a{k->d_emit_raw, v.bgr, d->W, d->H, c};
+  const int grid = (int)std::min<size_t>((d->npix() + 255) / 256, 1024);
+  ekf::k_frame_rectify<3><<<grid, 256, 0, nullptr>>>(a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(d->grey_from_colour(v));
+  double K[4];
+  ekf::rect_camera(c, K);
+  dense_commit(v, K, t, R, q);
+  v.set = v.colour = true;
+  return EKF_OK;
+}
+
+int ekf_dense_get_view_colour(const ekf_dense* h, int slot, unsigned char* bgr, int pitch) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (slot < 0 || slot >= d->max_views || (bgr && pitch < 3 * d->W)) {
+    d->err = "ekf_dense_get_view_colour: slot in 0..max_views-1 and pitch >= 3 width";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set || !v.colour) {
+    d->err = "ekf_dense_get_view_colour: the slot holds no colour image";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  if (bgr) {
+    const size_t row = 3 * (size_t)d->W;
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipMemcpy2D(bgr, (size_t)pitch, v.bgr, row, row, (size_t)d->H, hipMemcpyDeviceToHost));
+  }
   return EKF_OK;
 }
 
@@ -5659,7 +5757,8 @@ struct ekf_fusion {
   ekf::TsdfRaycast rc;                // the last render of the volume (ekf_raycast_*)
 };
 
-int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out) {
+static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
+                         ekf_fusion** out) {
   if (!out) return EKF_ERR_ARG;
   *out = nullptr;
   const bool dims_ok = nx >= 2 && ny >= 2 && nz >= 2 && nx <= ekf::kFusionMaxDim && ny <= ekf::kFusionMaxDim &&
@@ -5683,6 +5782,8 @@ int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel
   if (e == hipSuccess) e = f->sum.reserve(f->nvox());
   if (e == hipSuccess) e = f->cnt.reserve(f->nvox());
   if (e == hipSuccess) e = f->gsum.reserve(f->nvox());
+  if (e == hipSuccess && colour) e = f->csum.reserve(3 * f->nvox());
+  f->colour = colour;
   if (e == hipSuccess) e = f->clear();
   if (e != hipSuccess) {
     ekf::g_create_error = std::string("ekf_fusion_create: ") + hipGetErrorString(e);
@@ -5693,6 +5794,16 @@ int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel
   *out = new ekf_fusion{f};
   return EKF_OK;
 }
+
+int ekf_fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out) {
+  return fusion_create(nx, ny, nz, origin, voxel, trunc, device, false, out);
+}
+
+int ekf_colour_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out) {
+  return fusion_create(nx, ny, nz, origin, voxel, trunc, device, true, out);
+}
+
+int ekf_colour_has(const ekf_fusion* h) { return h && h->impl->colour ? 1 : 0; }
 
 void ekf_fusion_destroy(ekf_fusion* h) {
   if (!h) return;
@@ -5733,7 +5844,7 @@ int ekf_fusion_integrate(ekf_fusion* h, ekf_dense* dense, int slot, int filtered
   std::string& err = f->err;
   const ekf::DenseView& v = d->v[slot];
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(f->integrate(filtered ? v.fdepth : v.depth, v.img, d->W, d->H, v.K, v.R, v.t));
+  HIPCHK(f->integrate(filtered ? v.fdepth : v.depth, v.img, d->W, d->H, v.K, v.R, v.t, d->colour_of(slot)));
   return EKF_OK;
 }
 
@@ -5758,6 +5869,73 @@ int ekf_fusion_integrate_host(ekf_fusion* h, const float* depth, const unsigned 
   HIPCHK(hipMemcpy(f->d_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy2D(f->d_img, (size_t)width, img, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
   HIPCHK(f->integrate(f->d_depth, f->d_img, width, height, K, R, t));
+  return EKF_OK;
+}
+
+// A call that only a colour volume answers: EKF_OK, or EKF_ERR_STATE with the message set (nothing else is touched).
+static int fusion_colour_only(ekf::TsdfFusion* f, const char* who) {
+  if (!f->colour) {
+    f->err = std::string(who) + ": the handle is a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_STATE;
+  }
+  return EKF_OK;
+}
+
+int ekf_colour_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* bgr, int pitch, int width, int height,
+                              const double* K, const double* pose7) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  double t[3], R[9], q[4];
+  if (!depth || !bgr || !K || !pose7 || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
+      height > ekf::kFusionMaxMapDim || pitch < 3 * width || !pinhole_ok(K) || !ekf::dense_pose(pose7, t, R, q)) {
+    f->err = "ekf_colour_integrate_host: depth, bgr, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= 3 width; "
+             "K finite with fx, fy > 0; pose7 finite with q != 0";
+    return EKF_ERR_ARG;
+  }
+  const int kind = fusion_colour_only(f, "ekf_colour_integrate_host");
+  if (kind != EKF_OK) return kind;
+  const int room = fusion_room(f, "ekf_colour_integrate_host");
+  if (room != EKF_OK) return room;
+  std::string& err = f->err;
+  const size_t n = (size_t)width * height, row = 3 * (size_t)width;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(f->d_depth.reserve(n));
+  HIPCHK(f->d_bgr.reserve(3 * n));
+  HIPCHK(hipMemcpy(f->d_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy2D(f->d_bgr, row, bgr, (size_t)pitch, row, (size_t)height, hipMemcpyHostToDevice));
+  HIPCHK(f->integrate(f->d_depth, nullptr, width, height, K, R, t, f->d_bgr));
+  return EKF_OK;
+}
+
+int ekf_colour_get_volume(ekf_fusion* h, unsigned int* csum) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!csum) {
+    f->err = "ekf_colour_get_volume: csum must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const int kind = fusion_colour_only(f, "ekf_colour_get_volume");
+  if (kind != EKF_OK) return kind;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(hipMemcpy(csum, f->csum, 3 * f->nvox() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_colour_set_volume(ekf_fusion* h, const unsigned int* csum) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!csum) {
+    f->err = "ekf_colour_set_volume: csum must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const int kind = fusion_colour_only(f, "ekf_colour_set_volume");
+  if (kind != EKF_OK) return kind;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  f->mesh_valid = false;
+  ++f->changes;
+  HIPCHK(hipMemcpy(f->csum, csum, 3 * f->nvox() * sizeof(unsigned), hipMemcpyHostToDevice));
   return EKF_OK;
 }
 
@@ -5836,15 +6014,38 @@ int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, uns
   return EKF_OK;
 }
 
+int ekf_colour_get_mesh(ekf_fusion* h, unsigned char* bgr, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const int kind = fusion_colour_only(f, "ekf_colour_get_mesh");
+  if (kind != EKF_OK) return kind;
+  if (!f->mesh_valid) {
+    f->err = "ekf_colour_get_mesh: no ekf_fusion_extract since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(f->n_tri, max_tri) * 3;
+  if (nv == 0 || !bgr) return EKF_OK;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(hipMemcpy(bgr, f->m_bgr, nv * 3, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
 int ekf_fusion_profile(ekf_fusion* h, int enable) {
   if (!h) return EKF_ERR_ARG;
-  h->impl->timer.enable(enable != 0);   // the four kinds of the fusion and the two of the ray caster
+  h->impl->timer.enable(enable != 0);   // the four kinds of the fusion, the two of the ray caster and the three of colour
   return EKF_OK;
 }
 
 int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->impl->timer.read(kernel_ms, launches, 0, 4);
+  return EKF_OK;
+}
+
+int ekf_colour_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->impl->timer.read(kernel_ms, launches, 6, 3);
   return EKF_OK;
 }
 
@@ -5927,6 +6128,22 @@ int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* g
   if (grey) HIPCHK(hipMemcpy(grey, h->rc.grey, n, hipMemcpyDeviceToHost));
   if (width) *width = h->rc.W;
   if (height) *height = h->rc.H;
+  return EKF_OK;
+}
+
+int ekf_colour_get_render(ekf_fusion* h, unsigned char* bgr) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const int kind = fusion_colour_only(f, "ekf_colour_get_render");
+  if (kind != EKF_OK) return kind;
+  if (!h->rc.current(*f)) {
+    f->err = "ekf_colour_get_render: no ekf_raycast_render since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  if (!bgr) return EKF_OK;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(hipMemcpy(bgr, h->rc.bgr, (size_t)h->rc.W * h->rc.H * 3, hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 

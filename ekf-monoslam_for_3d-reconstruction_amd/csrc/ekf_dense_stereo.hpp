@@ -21,6 +21,7 @@
 
 #include "ekf_buffers.hpp"
 #endif
+#include "ekf_pixel.hpp"
 
 namespace ekf {
 
@@ -233,6 +234,32 @@ __global__ void __launch_bounds__(256) k_depth_filter_points(FilterArgs a) {
   }
 }
 
+// ---- colour views --------------------------------------------------------------------------------------------
+struct GreyArgs {
+  const unsigned char* bgr;           // npix x 3 bytes, tight, 4-byte aligned: B, G, R
+  unsigned char* grey;                // npix bytes, tight, 4-byte aligned
+  unsigned npix;
+};
+
+// The grey image the sweep reads, from a slot's colour image: one lane takes 4 consecutive pixels (three dword loads, one
+// dword store: the image is one flat run of pixels), the lane after the last full group takes the up to 3 pixels that are
+// left byte by byte.  No byte beyond 3 npix is read: the last word load ends at byte 12 (npix / 4) <= 3 npix.
+__global__ void __launch_bounds__(256) k_bgr_to_grey(GreyArgs a) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  const unsigned nvec = a.npix >> 2;
+  if (i < nvec) {
+    const unsigned* s = reinterpret_cast<const unsigned*>(a.bgr) + 3 * (size_t)i;
+    const unsigned w[3] = {s[0], s[1], s[2]};
+    unsigned out = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out |= bgr2gray(byte_of(w, 3 * j), byte_of(w, 3 * j + 1), byte_of(w, 3 * j + 2)) << (8 * j);
+    reinterpret_cast<unsigned*>(a.grey)[i] = out;
+  } else if (i == nvec) {
+    for (unsigned p = nvec * 4u; p < a.npix; ++p)
+      a.grey[p] = (unsigned char)bgr2gray(a.bgr[3 * (size_t)p], a.bgr[3 * (size_t)p + 1], a.bgr[3 * (size_t)p + 2]);
+  }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 // pose7 = (t, q = (w x y z)) -> t, R (camera to world, x_cam = R^T (X - t)) and q / |q|.  false: non-finite, or q = 0.
 inline bool dense_pose(const double* p, double t[3], double R[9], double q[4]) {
@@ -253,12 +280,14 @@ inline bool dense_pose(const double* p, double t[3], double R[9], double q[4]) {
 #ifndef EKF_KERNELS_ONLY
 struct DenseView {
   DevBuf<unsigned char> img;
+  DevBuf<unsigned char> bgr;          // W x H x 3, tight: the colour image `img` was derived from (colour = true only)
   DevBuf<float> depth, fdepth;
   DevBuf<int> plane, fplane;
   DevBuf<unsigned> cost;
   DevBuf<unsigned char> nviews;
   double K[4] = {}, t[3] = {}, R[9] = {}, q[4] = {};
   bool set = false;                   // an image, K and a pose
+  bool colour = false;                // `bgr` holds the slot's image in colour (§18): every grey setter drops it
   bool swept = false;                 // swept since the image or the pose last changed
   bool filtered = false;              // filtered since it was last swept
 };
@@ -273,6 +302,15 @@ struct DenseStereo {
   KernelTimer<2> timer;               // k_plane_sweep, k_depth_filter_points
 
   size_t npix() const { return (size_t)W * H; }
+  const unsigned char* colour_of(int slot) const { return v[slot].colour ? (const unsigned char*)v[slot].bgr : nullptr; }
+
+  // v.bgr -> v.img: the one launch of k_bgr_to_grey, enqueued on the default stream.
+  hipError_t grey_from_colour(DenseView& vw) {
+    const GreyArgs a{vw.bgr, vw.img, (unsigned)npix()};
+    const unsigned groups = a.npix / 4u + 1u;
+    k_bgr_to_grey<<<(groups + 255u) / 256u, 256, 0, nullptr>>>(a);
+    return hipGetLastError();
+  }
   ~DenseStereo() {                    // the members (events, buffers) go after this body, on the handle's device
     if (max_views) hipSetDevice(device);
   }

@@ -7,6 +7,8 @@
 //     function below (host and device), as in ekf_dense_stereo.hpp; poses go through dense_pose unchanged;
 //   - no atomics: a voxel belongs to one lane, and the mesh is written at offsets of a two-level exclusive scan, so the
 //     output order is fixed (cells by lin of their corner 0, tetrahedra 0..5, table order).
+// A colour volume keeps three more uint32 planes, the sums of the B, G and R values, and has two kernels of
+// its own: k_tsdf_integrate_colour and k_tsdf_colour_vertices; tests/colour_oracle.py restates them.
 // Nothing here touches a filter, counts as a launch kind or runs a collective.
 #pragma once
 #include <cmath>
@@ -21,6 +23,7 @@
 
 #include "ekf_buffers.hpp"
 #endif
+#include "ekf_pixel.hpp"
 
 namespace ekf {
 
@@ -46,13 +49,13 @@ struct IntegrateArgs {
   double R[9], t[3];                  // the map's pose: x_cam = R^T (X - t)
 };
 
-// One lane per voxel, x along the lanes: the loads and stores of the three planes are contiguous across a wave, and a voxel
-// that is skipped (behind the camera, outside the image, no depth, more than trunc behind the surface) touches none of them.
-__global__ void __launch_bounds__(256) k_tsdf_integrate(IntegrateArgs a) {
+// The voxel of a lane against the map: false where the voxel is skipped (past the volume, behind the camera, outside the
+// image, no depth, more than trunc behind the surface), otherwise the pixel it samples and its truncated distance, rounded to
+// fp32 once as the sum takes it.  The one body of both integration kernels.
+__device__ __forceinline__ bool tsdf_sample(const IntegrateArgs& a, unsigned lin, size_t& pix, float& tau) {
 #pragma clang fp contract(off)
-  const unsigned lin = blockIdx.x * (unsigned)kFusionBlock + threadIdx.x;
   const unsigned nx = (unsigned)a.g.nx, ny = (unsigned)a.g.ny;
-  if (lin >= nx * ny * (unsigned)a.g.nz) return;
+  if (lin >= nx * ny * (unsigned)a.g.nz) return false;
   const unsigned row = lin / nx, i = lin - row * nx;
   const unsigned k = row / ny, j = row - k * ny;
   const double d0 = (a.g.origin[0] + (double)i * a.g.voxel) - a.t[0];
@@ -61,20 +64,62 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate(IntegrateArgs a) {
   const double p0 = a.R[0] * d0 + a.R[3] * d1 + a.R[6] * d2;
   const double p1 = a.R[1] * d0 + a.R[4] * d1 + a.R[7] * d2;
   const double p2 = a.R[2] * d0 + a.R[5] * d1 + a.R[8] * d2;
-  if (!(p2 > 0.0)) return;
+  if (!(p2 > 0.0)) return false;
   const double sx = a.fx * (p0 / p2) + a.cx;
   const double sy = a.fy * (p1 / p2) + a.cy;
   const double fjx = floor(sx + 0.5), fjy = floor(sy + 0.5);
-  if (!(fjx >= 0.0 && fjx <= (double)(a.W - 1) && fjy >= 0.0 && fjy <= (double)(a.H - 1))) return;   // (a NaN fails)
-  const size_t pix = (size_t)(int)fjy * (size_t)a.W + (size_t)(int)fjx;
+  if (!(fjx >= 0.0 && fjx <= (double)(a.W - 1) && fjy >= 0.0 && fjy <= (double)(a.H - 1))) return false;   // (a NaN fails)
+  pix = (size_t)(int)fjy * (size_t)a.W + (size_t)(int)fjx;
   const double zs = (double)a.depth[pix];
-  if (zs == 0.0) return;
+  if (zs == 0.0) return false;
   const double s = zs - p2;
-  if (s < -a.trunc) return;
-  const double tau = (s >= a.trunc) ? 1.0 : s / a.trunc;
-  a.sum[lin] = a.sum[lin] + (float)tau;
+  if (s < -a.trunc) return false;
+  tau = (float)((s >= a.trunc) ? 1.0 : s / a.trunc);
+  return true;
+}
+
+// One lane per voxel, x along the lanes: the loads and stores of the three planes are contiguous across a wave, and a voxel
+// that is skipped (behind the camera, outside the image, no depth, more than trunc behind the surface) touches none of them.
+__global__ void __launch_bounds__(256) k_tsdf_integrate(IntegrateArgs a) {
+  const unsigned lin = blockIdx.x * (unsigned)kFusionBlock + threadIdx.x;
+  size_t pix;
+  float tau;
+  if (!tsdf_sample(a, lin, pix, tau)) return;
+  a.sum[lin] = a.sum[lin] + tau;
   a.cnt[lin] = (unsigned short)(a.cnt[lin] + 1);
   a.gsum[lin] = a.gsum[lin] + (unsigned)a.img[pix];
+}
+
+// ---- colour volumes ------------------------------------------------------------------------------------------
+struct IntegrateColourArgs {
+  IntegrateArgs g;                    // g.img is read only where bgr is NULL
+  const unsigned char* bgr;           // H rows of W x 3 bytes, tight: B, G, R; NULL = a map without colour
+  unsigned* csum;                     // three planes of nvox back to back: the sums of B, G and R
+  size_t nvox;
+};
+
+// k_tsdf_integrate for a colour volume: the same voxels, the same sum and cnt; gsum takes bgr2gray of the pixel and csum[c] its
+// channel c (exactly three byte reads at 3 pix).  A map without colour (a uniform branch: bgr is a kernel argument) adds its
+// grey value to all three colour planes, so that the one count plane serves all four sums.
+__global__ void __launch_bounds__(256) k_tsdf_integrate_colour(IntegrateColourArgs c) {
+  const unsigned lin = blockIdx.x * (unsigned)kFusionBlock + threadIdx.x;
+  size_t pix;
+  float tau;
+  if (!tsdf_sample(c.g, lin, pix, tau)) return;
+  unsigned b, g, r, grey;
+  if (c.bgr) {
+    const unsigned char* p = c.bgr + 3 * pix;
+    b = p[0]; g = p[1]; r = p[2];
+    grey = bgr2gray(b, g, r);
+  } else {
+    b = g = r = grey = (unsigned)c.g.img[pix];
+  }
+  c.g.sum[lin] = c.g.sum[lin] + tau;
+  c.g.cnt[lin] = (unsigned short)(c.g.cnt[lin] + 1);
+  c.g.gsum[lin] = c.g.gsum[lin] + grey;
+  c.csum[lin] = c.csum[lin] + b;
+  c.csum[c.nvox + lin] = c.csum[c.nvox + lin] + g;
+  c.csum[2 * c.nvox + lin] = c.csum[2 * c.nvox + lin] + r;
 }
 
 // ---- extraction ------------------------------------------------------------------------------------------------------------
@@ -258,6 +303,38 @@ __global__ void __launch_bounds__(256) k_tsdf_emit(ExtractArgs a) {
   }
 }
 
+struct ColourVertexArgs {
+  const float* sum;
+  const unsigned short* cnt;
+  const unsigned* csum;               // three planes of nvox back to back
+  const unsigned long long* key;      // the keys k_tsdf_emit wrote
+  unsigned char* bgr;                 // three bytes a vertex
+  unsigned long long nv;              // 3 n_tri
+  size_t nvox;
+  unsigned nx, ny;
+};
+
+// The colours of the vertices of a mesh (§18.1), after k_tsdf_emit and from its keys alone, one lane per vertex: key =
+// 8 la + d, and since every Kuhn edge runs componentwise upwards the bits of d = cb - ca are the steps to the edge's other
+// end.  na, nb, va, vb and u are tsdf_vertex's, operation for operation; a channel is blended and rounded as its grey is.
+__global__ void __launch_bounds__(256) k_tsdf_colour_vertices(ColourVertexArgs a) {
+#pragma clang fp contract(off)
+  const unsigned long long v = (unsigned long long)blockIdx.x * (unsigned long long)kFusionBlock + threadIdx.x;
+  if (v >= a.nv) return;
+  const unsigned long long key = a.key[v];
+  const unsigned la = (unsigned)(key >> 3), d = (unsigned)(key & 7ull);
+  const unsigned lb = la + (d & 1u) + ((d >> 1) & 1u) * a.nx + (d >> 2) * (a.nx * a.ny);
+  const double na = (double)a.cnt[la], nb = (double)a.cnt[lb];
+  const double va = (double)a.sum[la] / na, vb = (double)a.sum[lb] / nb;
+  const double u = va / (va - vb);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double Ca = (double)a.csum[c * a.nvox + la] / na, Cb = (double)a.csum[c * a.nvox + lb] / nb;
+    const double cv = Ca + u * (Cb - Ca);
+    a.bgr[v * 3 + c] = (unsigned char)(int)floor(cv + 0.5);
+  }
+}
+
 #ifndef EKF_KERNELS_ONLY
 // Host side of one handle (`ekf_fusion`).  Everything runs on the default stream of the handle's device, as ekf_dense_* does
 // (§15.4 (2)): a map may come straight from the device buffers of a dense handle.
@@ -270,18 +347,22 @@ struct TsdfFusion {
   DevBuf<float> sum;
   DevBuf<unsigned short> cnt;
   DevBuf<unsigned> gsum;
+  bool colour = false;                // a colour volume (§18): csum exists, the colour kernels run
+  DevBuf<unsigned> csum;              // the sums of B, G and R: three planes of nvox back to back
   DevBuf<float> d_depth;              // a host map on its way in
-  DevBuf<unsigned char> d_img;
+  DevBuf<unsigned char> d_img, d_bgr;
   DevBuf<unsigned> blk_tot;
   DevBuf<unsigned long long> blk_off;
   DevBuf<double> m_xyz;               // the mesh of the last extract (grow-only)
   DevBuf<unsigned long long> m_key;
-  DevBuf<unsigned char> m_grey;
+  DevBuf<unsigned char> m_grey, m_bgr;          // m_bgr: three bytes a vertex, colour volumes only
   unsigned long long n_tri = 0;
   bool mesh_valid = false;            // an extract since the volume last changed
   unsigned long long changes = 0;     // counts the changes of the volume (integrate, reset, ekf_fusion_set_volume): ekf_raycast.hpp
   int maps = 0;                       // maps integrated since the last reset (or what ekf_fusion_set_volume said)
-  KernelTimer<6> timer;               // k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit; 4, 5: ekf_raycast.hpp
+  // k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit; 4, 5: ekf_raycast.hpp; 6, 7, 8: k_tsdf_integrate_colour,
+  // k_tsdf_colour_vertices, k_tsdf_raycast_colour (§18)
+  KernelTimer<9> timer;
 
   size_t nvox() const { return (size_t)g.nx * g.ny * g.nz; }
   unsigned ncell() const { return (unsigned)((size_t)(g.nx - 1) * (g.ny - 1) * (g.nz - 1)); }
@@ -293,15 +374,17 @@ struct TsdfFusion {
     hipError_t e = hipMemsetAsync(sum, 0, nvox() * sizeof(float), nullptr);
     if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, nvox() * sizeof(unsigned short), nullptr);
     if (e == hipSuccess) e = hipMemsetAsync(gsum, 0, nvox() * sizeof(unsigned), nullptr);
+    if (e == hipSuccess && colour) e = hipMemsetAsync(csum, 0, 3 * nvox() * sizeof(unsigned), nullptr);
     mesh_valid = false;
     ++changes;
     if (e == hipSuccess) maps = 0;
     return e;
   }
 
-  // One launch of k_tsdf_integrate over device buffers of W x H (tight rows).
+  // One launch of k_tsdf_integrate over device buffers of W x H (tight rows); of k_tsdf_integrate_colour for a colour volume,
+  // where bgr (W x H x 3, tight) may be NULL (a map without colour) and img is read only then.
   hipError_t integrate(const float* depth, const unsigned char* img, int W, int H, const double K[4], const double R[9],
-                       const double t[3]) {
+                       const double t[3], const unsigned char* bgr = nullptr) {
     IntegrateArgs a{};
     a.sum = sum; a.cnt = cnt; a.gsum = gsum;
     a.depth = depth; a.img = img; a.W = W; a.H = H;
@@ -312,14 +395,21 @@ struct TsdfFusion {
     mesh_valid = false;
     ++changes;
     const unsigned nblk = (unsigned)((nvox() + kFusionBlock - 1) / kFusionBlock);
-    const hipError_t e = timer.run(0, [&] { k_tsdf_integrate<<<nblk, kFusionBlock, 0, nullptr>>>(a); });
+    hipError_t e;
+    if (colour) {
+      const IntegrateColourArgs c{a, bgr, csum, nvox()};
+      e = timer.run(6, [&] { k_tsdf_integrate_colour<<<nblk, kFusionBlock, 0, nullptr>>>(c); });
+    } else {
+      e = timer.run(0, [&] { k_tsdf_integrate<<<nblk, kFusionBlock, 0, nullptr>>>(a); });
+    }
     if (e != hipSuccess) return e;
     ++maps;
     return hipSuccess;
   }
 
-  // count -> scan -> one 8-byte read-back -> (grow the mesh buffers) -> emit.  A failed allocation leaves the previous mesh
-  // (the new buffers replace the old ones only when all three exist) and the volume as they were.
+  // count -> scan -> one 8-byte read-back -> (grow the mesh buffers) -> emit (-> the vertex colours of a colour volume).  A
+  // failed allocation leaves the previous mesh (the new buffers replace the old ones only when all of them exist) and the
+  // volume as they were.
   hipError_t extract(int min_count) {
     const unsigned nc = ncell(), nblk = (nc + kFusionBlock - 1) / kFusionBlock;
     hipError_t e;
@@ -332,22 +422,29 @@ struct TsdfFusion {
     unsigned long long total = 0;
     if ((e = hipMemcpy(&total, blk_off + nblk, sizeof(total), hipMemcpyDeviceToHost)) != hipSuccess) return e;
     const size_t nv = (size_t)total * 3;
-    if (nv > m_key.capacity() || nv > m_grey.capacity() || nv * 3 > m_xyz.capacity()) {
+    if (nv > m_key.capacity() || nv > m_grey.capacity() || nv * 3 > m_xyz.capacity() || (colour && nv * 3 > m_bgr.capacity())) {
       DevBuf<double> x;
       DevBuf<unsigned long long> k;
-      DevBuf<unsigned char> gr;
-      if ((e = x.reserve(nv * 3)) != hipSuccess || (e = k.reserve(nv)) != hipSuccess || (e = gr.reserve(nv)) != hipSuccess) {
+      DevBuf<unsigned char> gr, co;
+      if ((e = x.reserve(nv * 3)) != hipSuccess || (e = k.reserve(nv)) != hipSuccess || (e = gr.reserve(nv)) != hipSuccess ||
+          (colour && (e = co.reserve(nv * 3)) != hipSuccess)) {
         (void)hipGetLastError();
         return e;
       }
       m_xyz = std::move(x);
       m_key = std::move(k);
       m_grey = std::move(gr);
+      m_bgr = std::move(co);
     }
     mesh_valid = false;
     if (total > 0) {
       a.xyz = m_xyz; a.key = m_key; a.grey = m_grey;
       if ((e = timer.run(3, [&] { k_tsdf_emit<<<nblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
+      if (colour) {
+        const ColourVertexArgs c{sum, cnt, csum, m_key, m_bgr, (unsigned long long)nv, nvox(), (unsigned)g.nx, (unsigned)g.ny};
+        const unsigned vblk = (unsigned)((nv + kFusionBlock - 1) / kFusionBlock);
+        if ((e = timer.run(7, [&] { k_tsdf_colour_vertices<<<vblk, kFusionBlock, 0, nullptr>>>(c); })) != hipSuccess) return e;
+      }
     }
     n_tri = total;
     mesh_valid = true;

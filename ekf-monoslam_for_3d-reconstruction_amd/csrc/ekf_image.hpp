@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ekf_math.hpp"
+#include "ekf_pixel.hpp"
 
 namespace ekf {
 
@@ -46,12 +47,7 @@ struct IngestArgs {
   int W, H, Wo, Ho;
 };
 
-__device__ __forceinline__ unsigned bgr2gray(unsigned b, unsigned g, unsigned r) {
-  return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
-
-// byte i of a little-endian word array (i is a compile-time constant after unrolling: one v_bfe_u32)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+// (bgr2gray and byte_of: ekf_pixel.hpp)
 
 // NW words from byte address p of any alignment: NW + 1 aligned dword loads (the compiler merges them into dwordx2 / x4:
 // a global load wider than a dword still only needs dword alignment) realigned with v_alignbyte.  Loads up to 4 bytes past

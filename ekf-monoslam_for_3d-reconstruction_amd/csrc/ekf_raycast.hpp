@@ -6,6 +6,7 @@
 //     sample's validity and value, and ends at the first pair of valid samples that goes from v >= 0 to v < 0;
 //   - every coordinate operation is fp64, rounded once, in the written left-to-right order; contraction is off in every
 //     function below (host and device), as in ekf_fusion.hpp; poses go through dense_pose unchanged.
+//   - k_tsdf_raycast_colour is the same march for a colour volume: it also writes the B, G, R of the hit.
 // No atomics, no LDS: a pixel belongs to one lane.  Nothing here touches a filter, counts as a launch kind or runs a collective.
 #pragma once
 #include <cmath>
@@ -209,6 +210,88 @@ __global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
   a.grey[pix] = grey;
 }
 
+// What the march of a colour volume has beside RaycastArgs.
+struct RaycastColour {
+  const unsigned* csum;               // three planes of nvox back to back
+  unsigned char* bgr;                 // H rows of W x 3 bytes: B, G, R; 0, 0, 0 = no hit
+  size_t nvox;
+};
+
+// The one launch of a colour volume: k_tsdf_raycast's march, statement for statement, with depth, normal and grey as it writes
+// them; at the hit it also blends the eight corners' csum[c] / cnt with the grey's rc_trilinear and fractions, rounds the same
+// way and writes B, G, R.  It has a body of its own, not a template shared with k_tsdf_raycast, so that the grey kernel's
+// source and code object stay what they were; a change to the march is made in both, and
+// tests/test_gpu_colour.py holds the depth, normal and grey of the two kernels against each other bit for bit.
+__global__ void __launch_bounds__(256) k_tsdf_raycast_colour(RaycastArgs a, RaycastColour k) {
+#pragma clang fp contract(off)
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int px = (int)(blockIdx.x * (unsigned)kRaycastTile + (wave & 1) * 8 + (lane & 7));
+  const int py = (int)(blockIdx.y * (unsigned)kRaycastTile + (wave >> 1) * 8 + (lane >> 3));
+  if (px >= a.W || py >= a.H) return;
+  const double dc0 = ((double)px - a.cx) / a.fx, dc1 = ((double)py - a.cy) / a.fy;
+  const double dw[3] = {a.R[0] * dc0 + a.R[1] * dc1 + a.R[2], a.R[3] * dc0 + a.R[4] * dc1 + a.R[5],
+                        a.R[6] * dc0 + a.R[7] * dc1 + a.R[8]};
+  int n, n_hi;
+  rc_range(a, dw, n, n_hi);
+  float depth = 0.f, nrm0 = 0.f, nrm1 = 0.f, nrm2 = 0.f;
+  unsigned char grey = 0, col[3] = {0, 0, 0};
+  bool pok = false;                   // the previous sample was valid, and its value
+  double pv = 0.0;
+  for (; n <= n_hi; ++n) {
+    const double z = a.z_near + (double)n * a.step;
+    unsigned lin0;
+    double f0, f1, f2, v[8];
+    bool ok = rc_locate(a, a.t[0] + z * dw[0], a.t[1] + z * dw[1], a.t[2] + z * dw[2], lin0, f0, f1, f2);
+    double val = 0.0;
+    if (ok) {
+      ok = rc_means(a, lin0, v);
+      val = rc_trilinear(v, f0, f1, f2);
+    }
+    if (ok && pok && pv >= 0.0 && val < 0.0) {
+      const double u = pv / (pv - val);
+      const double zs = (a.z_near + (double)(n - 1) * a.step) + u * a.step;
+      if (rc_locate(a, a.t[0] + zs * dw[0], a.t[1] + zs * dw[1], a.t[2] + zs * dw[2], lin0, f0, f1, f2) && rc_means(a, lin0, v)) {
+        const double gx = rc_bilinear(v[1] - v[0], v[3] - v[2], v[5] - v[4], v[7] - v[6], f1, f2);
+        const double gy = rc_bilinear(v[2] - v[0], v[3] - v[1], v[6] - v[4], v[7] - v[5], f0, f2);
+        const double gz = rc_bilinear(v[4] - v[0], v[5] - v[1], v[6] - v[2], v[7] - v[3], f0, f1);
+        const double len = sqrt((gx * gx + gy * gy) + gz * gz);
+        if (len > 0.0) {
+          nrm0 = (float)(gx / len);
+          nrm1 = (float)(gy / len);
+          nrm2 = (float)(gz / len);
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const unsigned l = rc_corner(a, lin0, c);
+          v[c] = (double)a.gsum[l] / (double)a.cnt[l];
+        }
+        grey = (unsigned char)(int)floor(rc_trilinear(v, f0, f1, f2) + 0.5);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const unsigned l = rc_corner(a, lin0, c);
+            v[c] = (double)k.csum[ch * k.nvox + l] / (double)a.cnt[l];
+          }
+          col[ch] = (unsigned char)(int)floor(rc_trilinear(v, f0, f1, f2) + 0.5);
+        }
+        depth = (float)zs;
+        break;
+      }
+    }
+    pok = ok;
+    pv = val;
+  }
+  const size_t pix = (size_t)py * (size_t)a.W + (size_t)px;
+  a.depth[pix] = depth;
+  a.normal[pix * 3 + 0] = nrm0;
+  a.normal[pix * 3 + 1] = nrm1;
+  a.normal[pix * 3 + 2] = nrm2;
+  a.grey[pix] = grey;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) k.bgr[pix * 3 + ch] = col[ch];
+}
+
 #ifndef EKF_KERNELS_ONLY
 // Host side: the buffers of a render, owned by the fusion handle they belong to.  The mean plane is made at the first render
 // and kept until the volume changes (TsdfFusion::changes) or min_count differs.  The two launches are kinds 4 (k_tsdf_mean)
@@ -216,7 +299,7 @@ __global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
 struct TsdfRaycast {
   DevBuf<float> mean;
   DevBuf<float> depth, normal;
-  DevBuf<unsigned char> grey;
+  DevBuf<unsigned char> grey, bgr;    // bgr: colour volumes only
   int mean_count = 0;                 // the min_count of the plane in `mean`; 0 = none
   unsigned long long mean_changes = 0, render_changes = 0;      // TsdfFusion::changes when the plane and the render were made
   int W = 0, H = 0;
@@ -225,7 +308,7 @@ struct TsdfRaycast {
   bool current(const TsdfFusion& f) const { return valid && render_changes == f.changes; }
 
   // (mean plane) -> grow the images -> march.  A failed allocation leaves the previous render (the new images replace the old
-  // ones only when all three exist), the mesh and the volume as they were.
+  // ones only when all of them exist), the mesh and the volume as they were.
   hipError_t render(TsdfFusion& f, int width, int height, const double K[4], const double R[9], const double t[3],
                     double z_near, double step, int N, int min_count) {
     hipError_t e;
@@ -234,16 +317,18 @@ struct TsdfRaycast {
       (void)hipGetLastError();
       return e;
     }
-    if (npix > depth.capacity() || npix * 3 > normal.capacity() || npix > grey.capacity()) {
+    if (npix > depth.capacity() || npix * 3 > normal.capacity() || npix > grey.capacity() || (f.colour && npix * 3 > bgr.capacity())) {
       DevBuf<float> d, nr;
-      DevBuf<unsigned char> gr;
-      if ((e = d.reserve(npix)) != hipSuccess || (e = nr.reserve(npix * 3)) != hipSuccess || (e = gr.reserve(npix)) != hipSuccess) {
+      DevBuf<unsigned char> gr, co;
+      if ((e = d.reserve(npix)) != hipSuccess || (e = nr.reserve(npix * 3)) != hipSuccess || (e = gr.reserve(npix)) != hipSuccess ||
+          (f.colour && (e = co.reserve(npix * 3)) != hipSuccess)) {
         (void)hipGetLastError();
         return e;
       }
       depth = std::move(d);
       normal = std::move(nr);
       grey = std::move(gr);
+      bgr = std::move(co);
       valid = false;
     }
     if (mean_count != min_count || mean_changes != f.changes) {
@@ -265,7 +350,13 @@ struct TsdfRaycast {
     a.z_near = z_near; a.step = step; a.N = N;
     valid = false;
     const dim3 grid((unsigned)((width + kRaycastTile - 1) / kRaycastTile), (unsigned)((height + kRaycastTile - 1) / kRaycastTile));
-    if ((e = f.timer.run(5, [&] { k_tsdf_raycast<<<grid, kRaycastTile * kRaycastTile, 0, nullptr>>>(a); })) != hipSuccess) return e;
+    if (f.colour) {
+      const RaycastColour k{f.csum, bgr, f.nvox()};
+      e = f.timer.run(8, [&] { k_tsdf_raycast_colour<<<grid, kRaycastTile * kRaycastTile, 0, nullptr>>>(a, k); });
+    } else {
+      e = f.timer.run(5, [&] { k_tsdf_raycast<<<grid, kRaycastTile * kRaycastTile, 0, nullptr>>>(a); });
+    }
+    if (e != hipSuccess) return e;
     W = width;
     H = height;
     render_changes = f.changes;

@@ -43,10 +43,22 @@ class DenseStereo(capi.Handle):
 
     # ---- views ----
     def set_view(self, slot: int, image, K, pose7):
-        """``image``: (height, width) uint8 on the host, or a CUDA/HIP ``torch`` tensor of that shape (no host round trip)."""
+        """``image``: (height, width) uint8 on the host, or a CUDA/HIP ``torch`` tensor of that shape (no host round trip).
+        A (height, width, 3) image in B, G, R order, from either place, makes a colour view: the slot keeps
+        it and sweeps its grey conversion."""
         K = np.ascontiguousarray(K, np.float64).reshape(4)
         pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
         if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
+            if image.dim() == 3:
+                if (tuple(image.shape) != self.shape + (3,) or str(image.dtype) != "torch.uint8" or image.stride(2) != 1
+                        or image.stride(1) != 3 or image.stride(0) < 3 * self.width):
+                    raise ValueError("a device colour image is (height, width, 3) uint8 with unit channel stride, pixel stride 3 "
+                                     "and rows at least 3 widths apart")
+                if (image.device.index or 0) != self.device:
+                    raise ValueError("the device image lives on device %r, the handle on device %d" % (image.device.index, self.device))
+                self._check(self._lib.ekf_dense_set_view_colour_device(self._h, int(slot), C.c_void_p(image.data_ptr()),
+                                                                       int(image.stride(0)), _ptr(K), _ptr(pose)))
+                return
             if tuple(image.shape) != self.shape or str(image.dtype) != "torch.uint8" or image.stride(1) != 1 or image.stride(0) < self.width:
                 raise ValueError("a device image is (height, width) uint8 with unit column stride and rows at least a width apart")
             if (image.device.index or 0) != self.device:
@@ -55,14 +67,20 @@ class DenseStereo(capi.Handle):
                                                             int(image.stride(0)), _ptr(K), _ptr(pose)))
             return
         img = np.ascontiguousarray(image, np.uint8)
+        if img.shape == self.shape + (3,):
+            self._check(self._lib.ekf_dense_set_view_colour(self._h, int(slot), _ptr(img), img.strides[0], _ptr(K), _ptr(pose)))
+            return
         if img.shape != self.shape:
-            raise ValueError("image must be (height, width) = %r" % (self.shape,))
+            raise ValueError("image must be (height, width) = %r, or (height, width, 3) for colour" % (self.shape,))
         self._check(self._lib.ekf_dense_set_view(self._h, int(slot), _ptr(img), img.strides[0], _ptr(K), _ptr(pose)))
 
-    def set_view_from_keyframe(self, slot: int, selector, pose7, raw: bool = False):
+    def set_view_from_keyframe(self, slot: int, selector, pose7, raw: bool = False, colour: bool = False):
         """The selector's last emitted key frame, rectified on the device straight into the slot; K is the selector's
-        rectified camera of that resolution."""
+        rectified camera of that resolution.  ``colour``: the raw key frame of a 3-channel raw selector, as a colour view."""
         pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        if colour:
+            self._check(self._lib.ekf_dense_set_view_colour_from_keyframe(self._h, int(slot), selector._h, _ptr(pose)))
+            return
         self._check(self._lib.ekf_dense_set_view_from_keyframe(self._h, int(slot), selector._h, 1 if raw else 0, _ptr(pose)))
 
     def set_pose(self, slot: int, pose7):
@@ -74,6 +92,15 @@ class DenseStereo(capi.Handle):
         img, K, pose = np.zeros(self.shape, np.uint8), np.zeros(4, np.float64), np.zeros(7, np.float64)
         self._check(self._lib.ekf_dense_get_view(self._h, int(slot), _ptr(img), img.strides[0], _ptr(K), _ptr(pose)))
         return img, K, pose
+
+    def has_colour(self, slot: int) -> bool:
+        return self._lib.ekf_dense_get_view_colour(self._h, int(slot), None, 0) == 0
+
+    def view_colour(self, slot: int) -> np.ndarray:
+        """The (height, width, 3) B, G, R image of a colour view; an error for a slot that holds none."""
+        bgr = np.zeros(self.shape + (3,), np.uint8)
+        self._check(self._lib.ekf_dense_get_view_colour(self._h, int(slot), _ptr(bgr), bgr.strides[0]))
+        return bgr
 
     # ---- the two launches ----
     def sweep(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 2,
@@ -145,9 +172,20 @@ def read_pgm(path: str) -> np.ndarray:
     return np.frombuffer(data[m.end():m.end() + w * h], np.uint8).reshape(h, w).copy()
 
 
+def read_ppm(path: str) -> np.ndarray:
+    """Binary P6, 8 bit (what ``keyframes.write_ppm`` writes), as a (H, W, 3) image swapped back to B, G, R order."""
+    data = open(path, "rb").read()
+    m = re.match(rb"P6\s+(\d+)\s+(\d+)\s+255\s", data)
+    if not m:
+        raise ValueError("%s is not an 8-bit binary PPM" % path)
+    w, h = int(m.group(1)), int(m.group(2))
+    return np.ascontiguousarray(np.frombuffer(data[m.end():m.end() + 3 * w * h], np.uint8).reshape(h, w, 3)[:, :, ::-1])
+
+
 def read_recording(directory: str, nodes_out=None):
     """(K, ids, poses (n, 7) float64, images) of a recording of ``KeyframeRecorder(rectify=True, images=True)``; the poses
-    are those of ``nodes_and_prjcts.txt`` (float32 widened) unless ``nodes_out`` (``Nodes_Out.txt`` of ``sba_add``) has the id."""
+    are those of ``nodes_and_prjcts.txt`` (float32 widened) unless ``nodes_out`` (``Nodes_Out.txt`` of ``sba_add``) has the id.
+    A key frame is ``<id>.pgm``, a (H, W) image, or where that is absent ``<id>.ppm``, a (H, W, 3) image in B, G, R order."""
     K = np.array(formats.read_camera(os.path.join(directory, "camera.txt")), np.float64)
     records = formats.read_pose_records(os.path.join(directory, "nodes_and_prjcts.txt"))
     ids = [int(r[0]) for r in records]
@@ -161,9 +199,13 @@ def read_recording(directory: str, nodes_out=None):
     images = []
     for i in ids:
         path = os.path.join(directory, "%d.pgm" % i)
-        if not os.path.exists(path):
-            raise ValueError("%s is missing: the dense step takes 1-channel key frames (colour is out of scope)" % path)
-        images.append(read_pgm(path))
+        if os.path.exists(path):
+            images.append(read_pgm(path))
+            continue
+        colour = os.path.join(directory, "%d.ppm" % i)
+        if not os.path.exists(colour):
+            raise ValueError("%s is missing, and so is %s" % (path, colour))
+        images.append(read_ppm(colour))
     return K, ids, poses, images
 
 
@@ -178,14 +220,14 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
     """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
     order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
     The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
-    neighbourhoods away) and the recording may be of any length >= 2."""
+    neighbourhoods away) and the recording may be of any length >= 2.  Colour key frames become colour views."""
     if not 1 <= int(neighbours) <= 3:
         raise ValueError("neighbours is 1 .. 3")
     K, ids, poses, images = read_recording(directory, nodes_out)
     n = len(ids)
     if n < 2:
         raise ValueError("a depth map needs at least two key frames")
-    h, w = images[0].shape
+    h, w = images[0].shape[:2]
     ds = DenseStereo(w, h, min(MAX_VIEWS, n), device)
     ring = ds.max_views
     loaded = swept = 0                                             # key frames [0, loaded) are in their slots, [0, swept) swept

@@ -3,7 +3,8 @@
 ``read_mesh_ply`` store the result, and ``mesh_from_recording`` drives ``dense.depth_maps_from_recording`` and the volume
 over a rectified recording.  ``TsdfVolume.raycast`` / ``raycast_view`` mirror ``ekf_raycast_*`` (§17): the volume seen from a
 pose as a depth, a normal and a grey image; ``shade`` turns one into a picture and ``audit_recording`` compares the
-reconstruction of a recording with its own key frames.
+reconstruction of a recording with its own key frames.  ``TsdfVolume(..., colour=True)`` is a colour volume (§18): meshes,
+renders and audits then carry B, G, R beside the grey.
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ from .capi import ptr as _ptr
 MAX_DIM, MAX_VOXELS, MAX_MAPS = 1024, 1 << 28, 65535
 KERNELS = ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")
 RAYCAST_KERNELS = ("k_tsdf_mean", "k_tsdf_raycast")
+COLOUR_KERNELS = ("k_tsdf_integrate_colour", "k_tsdf_colour_vertices", "k_tsdf_raycast_colour")
 
 
 @dataclass
@@ -27,6 +29,7 @@ class Mesh:
     xyz: np.ndarray                # (n, 3, 3) float64
     key: np.ndarray                # (n, 3) uint64: equal keys are bit-equal vertices
     grey: np.ndarray               # (n, 3) uint8
+    colour: Optional[np.ndarray] = None       # (n, 3, 3) uint8, B G R of each vertex: colour volumes only
 
 
 @dataclass
@@ -35,6 +38,7 @@ class Render:
     depth: np.ndarray              # (H, W) float32: camera-z depth of the surface
     normal: np.ndarray             # (H, W, 3) float32: unit, world frame, towards free space
     grey: np.ndarray               # (H, W) uint8
+    colour: Optional[np.ndarray] = None       # (H, W, 3) uint8, B G R: colour volumes only
 
 
 @dataclass
@@ -46,6 +50,7 @@ class FrameAudit:
     median: float                  # of |render - filtered| / filtered over those pixels (NaN if there are none)
     p90: float                     # its 90th percentile
     grey_error: float              # mean |grey - image| over the pixels the render hit (NaN if there are none)
+    colour_error: float = float("nan")        # the mean over those pixels of the mean |channel - image channel|; NaN for grey
 
 
 @dataclass
@@ -68,17 +73,20 @@ class RecordingMesh:
     voxel: float
     trunc: float
     maps: list                     # the DepthMaps that were fused
+    colour: Optional[np.ndarray] = None       # (m, 3) uint8, B G R: colour recordings only
 
 
 class TsdfVolume(capi.Handle):
     """``dims`` = (nx, ny, nz) voxels of side ``voxel`` on the device; the centre of voxel (i, j, k) is origin + (i, j, k) voxel.
-    The planes are numpy arrays of shape (nz, ny, nx): x fastest."""
+    The planes are numpy arrays of shape (nz, ny, nx): x fastest.  ``colour``: a colour volume, which also sums B, G and R."""
     _family = "ekf_fusion"
 
-    def __init__(self, dims, origin, voxel: float, trunc: float, device: int = 0):
+    def __init__(self, dims, origin, voxel: float, trunc: float, device: int = 0, colour: bool = False):
         nx, ny, nz = (int(v) for v in dims)
         o = np.ascontiguousarray(origin, np.float64).reshape(3)
-        self._create("ekf_fusion_create", nx, ny, nz, _ptr(o), float(voxel), float(trunc), int(device))
+        self._create("ekf_colour_create" if colour else "ekf_fusion_create", nx, ny, nz, _ptr(o), float(voxel),
+                     float(trunc), int(device))
+        self.colour = bool(colour)
         self.dims, self.origin, self.voxel, self.trunc, self.device = (nx, ny, nz), o, float(voxel), float(trunc), int(device)
         self.shape = (nz, ny, nx)
 
@@ -87,13 +95,18 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_fusion_integrate(self._h, dense_stereo._h, int(slot), 1 if filtered else 0))
 
     def integrate_host(self, depth, image, K, pose7):
-        """``depth``: (H, W) float32, 0 = none; ``image``: (H, W) uint8; any size up to 8192 x 8192."""
+        """``depth``: (H, W) float32, 0 = none; ``image``: (H, W) uint8, or (H, W, 3) in B, G, R order for a colour volume;
+        any size up to 8192 x 8192."""
         d = np.ascontiguousarray(depth, np.float32)
         img = np.ascontiguousarray(image, np.uint8)
-        if d.ndim != 2 or img.shape != d.shape:
-            raise ValueError("depth and image are (H, W) arrays of one shape")
         K = np.ascontiguousarray(K, np.float64).reshape(4)
         pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        if d.ndim == 2 and img.shape == d.shape + (3,):
+            self._check(self._lib.ekf_colour_integrate_host(self._h, _ptr(d), _ptr(img), img.strides[0], d.shape[1],
+                                                                   d.shape[0], _ptr(K), _ptr(pose)))
+            return
+        if d.ndim != 2 or img.shape != d.shape:
+            raise ValueError("depth and image are (H, W) arrays of one shape, or the image is (H, W, 3)")
         self._check(self._lib.ekf_fusion_integrate_host(self._h, _ptr(d), _ptr(img), img.strides[0], d.shape[1], d.shape[0],
                                                         _ptr(K), _ptr(pose)))
 
@@ -101,15 +114,25 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_fusion_reset(self._h))
 
     def volume(self) -> dict:
-        """sum float32, cnt uint16, gsum uint32, each (nz, ny, nx), and maps: the number of maps integrated."""
+        """sum float32, cnt uint16, gsum uint32, each (nz, ny, nx), and maps: the number of maps integrated; of a colour
+        volume also csum uint32 (3, nz, ny, nx): the sums of B, G and R."""
         out = dict(sum=np.zeros(self.shape, np.float32), cnt=np.zeros(self.shape, np.uint16), gsum=np.zeros(self.shape, np.uint32))
         maps = C.c_int(0)
         self._check(self._lib.ekf_fusion_get_volume(self._h, _ptr(out["sum"]), _ptr(out["cnt"]), _ptr(out["gsum"]), C.byref(maps)))
         out["maps"] = int(maps.value)
+        if self.colour:
+            out["csum"] = np.zeros((3,) + self.shape, np.uint32)
+            self._check(self._lib.ekf_colour_get_volume(self._h, _ptr(out["csum"])))
         return out
 
-    def set_volume(self, sum=None, cnt=None, gsum=None, maps: int = -1):
-        """Writes the given planes (tests).  ``maps`` = -1 keeps the map counter; it is raised to the largest count given."""
+    def set_volume(self, sum=None, cnt=None, gsum=None, maps: int = -1, csum=None):
+        """Writes the given planes (tests).  ``maps`` = -1 keeps the map counter; it is raised to the largest count given.
+        ``csum``: the (3, nz, ny, nx) colour planes of a colour volume."""
+        if csum is not None:
+            csum = np.ascontiguousarray(csum, np.uint32)
+            if csum.shape != (3,) + self.shape:
+                raise ValueError("csum is (3, nz, ny, nx) = %r" % ((3,) + self.shape,))
+            self._check(self._lib.ekf_colour_set_volume(self._h, _ptr(csum)))
         arrs = []
         for a, t in ((sum, np.float32), (cnt, np.uint16), (gsum, np.uint32)):
             if a is not None:
@@ -125,6 +148,9 @@ class TsdfVolume(capi.Handle):
         n = int(n.value)
         m = Mesh(np.zeros((n, 3, 3), np.float64), np.zeros((n, 3), np.uint64), np.zeros((n, 3), np.uint8))
         self._check(self._lib.ekf_fusion_get_mesh(self._h, _ptr(m.xyz), _ptr(m.key), _ptr(m.grey), n))
+        if self.colour:
+            m.colour = np.zeros((n, 3, 3), np.uint8)
+            self._check(self._lib.ekf_colour_get_mesh(self._h, _ptr(m.colour), n))
         return m
 
     def _render(self) -> Render:
@@ -133,6 +159,9 @@ class TsdfVolume(capi.Handle):
         r = Render(np.zeros((h.value, w.value), np.float32), np.zeros((h.value, w.value, 3), np.float32),
                    np.zeros((h.value, w.value), np.uint8))
         self._check(self._lib.ekf_raycast_get(self._h, _ptr(r.depth), _ptr(r.normal), _ptr(r.grey), None, None))
+        if self.colour:
+            r.colour = np.zeros((h.value, w.value, 3), np.uint8)
+            self._check(self._lib.ekf_colour_get_render(self._h, _ptr(r.colour)))
         return r
 
     def raycast(self, shape, K, pose7, z_near: float, z_far: float, step: Optional[float] = None, min_count: int = 1) -> Render:
@@ -163,6 +192,12 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_raycast_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(RAYCAST_KERNELS)}
 
+    def get_colour_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the three colour kernels since the last ``profile()``."""
+        ms, cnt = np.zeros(3, np.float64), np.zeros(3, np.int64)
+        self._check(self._lib.ekf_colour_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(COLOUR_KERNELS)}
+
     def get_profile(self) -> dict:
         """HIP-event milliseconds and launch counts of the four kernels since the last ``profile()``."""
         ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
@@ -170,27 +205,40 @@ class TsdfVolume(capi.Handle):
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(KERNELS)}
 
 
-def weld(mesh: Mesh):
+def weld(mesh: Mesh, colour: bool = False):
     """(vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8): one vertex per distinct key (ascending), exact because
-    equal keys carry bit-equal coordinates."""
+    equal keys carry bit-equal coordinates.  ``colour``: a fourth array, (m, 3) uint8 in B, G, R order (equal keys carry
+    equal colours too: a colour is a function of the key)."""
     _, first, inverse = np.unique(mesh.key.reshape(-1), return_index=True, return_inverse=True)
-    return mesh.xyz.reshape(-1, 3)[first], inverse.reshape(-1, 3).astype(np.int64), mesh.grey.reshape(-1)[first]
+    out = mesh.xyz.reshape(-1, 3)[first], inverse.reshape(-1, 3).astype(np.int64), mesh.grey.reshape(-1)[first]
+    if not colour:
+        return out
+    if mesh.colour is None:
+        raise ValueError("the mesh has no colour: it was not extracted from a colour volume")
+    return out + (mesh.colour.reshape(-1, 3)[first],)
 
 
-def write_mesh_ply(path: str, vertices, faces, grey) -> None:
-    """ASCII PLY: vertices ``x y z`` as doubles with ``intensity``, faces as ``list uchar int vertex_indices``."""
+def write_mesh_ply(path: str, vertices, faces, grey, colour=None) -> None:
+    """ASCII PLY: vertices ``x y z`` as doubles with ``intensity``, faces as ``list uchar int vertex_indices``.  ``colour``
+    ((m, 3), B, G, R) adds ``red green blue`` after the intensity."""
+    rgb = "" if colour is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     with open(path, "w") as fh:
         fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
-                 "property uchar intensity\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n"
-                 % (len(vertices), len(faces)))
-        for (x, y, z), g in zip(vertices, grey):
-            fh.write("%.17g %.17g %.17g %d\n" % (x, y, z, int(g)))
+                 "property uchar intensity\n%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                 % (len(vertices), rgb, len(faces)))
+        if colour is None:
+            for (x, y, z), g in zip(vertices, grey):
+                fh.write("%.17g %.17g %.17g %d\n" % (x, y, z, int(g)))
+        else:
+            for (x, y, z), g, (b, gr, r) in zip(vertices, grey, colour):
+                fh.write("%.17g %.17g %.17g %d %d %d %d\n" % (x, y, z, int(g), int(r), int(gr), int(b)))
         for a, b, c in faces:
             fh.write("3 %d %d %d\n" % (a, b, c))
 
 
-def read_mesh_ply(path: str):
-    """What ``write_mesh_ply`` wrote: (vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8)."""
+def read_mesh_ply(path: str, colour: bool = False):
+    """What ``write_mesh_ply`` wrote: (vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8), and with ``colour`` the
+    (m, 3) uint8 colours swapped back to B, G, R order."""
     with open(path) as fh:
         lines = fh.read().splitlines()
     end = lines.index("end_header")
@@ -198,9 +246,14 @@ def read_mesh_ply(path: str):
     nv, nf = count("vertex"), count("face")
     rows = [ln.split() for ln in lines[end + 1:end + 1 + nv]]
     faces = [ln.split() for ln in lines[end + 1 + nv:end + 1 + nv + nf]]
-    return (np.array([[float(t) for t in r[:3]] for r in rows], np.float64).reshape(-1, 3),
-            np.array([[int(t) for t in r[1:4]] for r in faces], np.int64).reshape(-1, 3),
-            np.array([int(r[3]) for r in rows], np.uint8))
+    out = (np.array([[float(t) for t in r[:3]] for r in rows], np.float64).reshape(-1, 3),
+           np.array([[int(t) for t in r[1:4]] for r in faces], np.int64).reshape(-1, 3),
+           np.array([int(r[3]) for r in rows], np.uint8))
+    if not colour:
+        return out
+    if "property uchar red" not in lines[:end]:
+        raise ValueError("%s has no colour" % path)
+    return out + (np.array([[int(r[6]), int(r[5]), int(r[4])] for r in rows], np.uint8).reshape(-1, 3),)
 
 
 def auto_grid(points, voxel: Optional[float] = None, bounds=None, trunc: Optional[float] = None):
@@ -231,11 +284,12 @@ def auto_grid(points, voxel: Optional[float] = None, bounds=None, trunc: Optiona
 
 
 def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
-    """The steps of ``mesh_from_recording`` up to the filled volume: (vol, maps, K, images, origin, dims, voxel, trunc)."""
+    """The steps of ``mesh_from_recording`` up to the filled volume: (vol, maps, K, images, origin, dims, voxel, trunc).  A
+    recording with colour key frames fills a colour volume."""
     maps = dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)
     K, ids, poses, images = dense.read_recording(directory, nodes_out)
     origin, dims, vx, tr = auto_grid([m.points for m in maps], voxel, bounds, trunc)
-    vol = TsdfVolume(dims, origin, vx, tr, int(sweep_kwargs.get("device", 0)))
+    vol = TsdfVolume(dims, origin, vx, tr, int(sweep_kwargs.get("device", 0)), colour=any(img.ndim == 3 for img in images))
     try:
         for m, img in zip(maps, images):
             vol.integrate_host(m.depth, img, K, m.pose)
@@ -255,18 +309,30 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey = weld(vol.extract(min_count))
+        welded = _welded(vol, min_count)
     finally:
         vol.close()
-    return RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps)
+    return RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
 
 
-def shade(render: Render, light=(0.0, 0.0, -1.0)) -> np.ndarray:
+def _welded(vol: TsdfVolume, min_count: int):
+    """(vertices, faces, grey, colour or None) of the volume's mesh."""
+    mesh = vol.extract(min_count)
+    return weld(mesh, True) if vol.colour else weld(mesh) + (None,)
+
+
+def shade(render: Render, light=(0.0, 0.0, -1.0), albedo: bool = False) -> np.ndarray:
     """An 8-bit Lambert image of a render, on the host: floor(255 max(0, n . l / |l|) + 0.5) where the render has depth, 0
-    elsewhere.  ``light`` is the direction towards the light in the world frame."""
+    elsewhere.  ``light`` is the direction towards the light in the world frame.  ``albedo``: the (H, W, 3) picture
+    floor(colour max(0, n . l / |l|) + 0.5) of a colour render."""
     l = np.asarray(light, np.float64).reshape(3)
     l = l / np.sqrt(l @ l)
     lam = np.maximum(render.normal.astype(np.float64) @ l, 0.0)
+    if albedo:
+        if render.colour is None:
+            raise ValueError("the render has no colour: it was not made from a colour volume")
+        lit = np.floor(render.colour.astype(np.float64) * lam[:, :, None] + 0.5)
+        return np.where((render.depth > 0)[:, :, None], lit, 0.0).astype(np.uint8)
     return np.where(render.depth > 0, np.floor(255.0 * lam + 0.5), 0.0).astype(np.uint8)
 
 
@@ -279,14 +345,29 @@ def audit_range(maps, trunc: float):
 
 
 def audit_frame(kid: int, render: Render, depth, image) -> FrameAudit:
-    """The figures of one key frame from its render, its filtered depth map and its image."""
+    """The figures of one key frame from its render, its filtered depth map and its image ((H, W), or (H, W, 3) in B, G, R
+    order with a colour render: the grey error is then taken against ``grey_image`` of it)."""
     both = (render.depth > 0) & (depth > 0)
     hit = render.depth > 0
     rel = np.abs(render.depth[both].astype(np.float64) - depth[both].astype(np.float64)) / depth[both].astype(np.float64)
     nan = float("nan")
+    image = np.asarray(image)
+    grey = grey_image(image) if image.ndim == 3 else image
+    colour_error = nan
+    if image.ndim == 3 and render.colour is not None and hit.any():
+        colour_error = float(np.abs(render.colour[hit].astype(np.float64) - image[hit].astype(np.float64)).mean(axis=1).mean())
     return FrameAudit(int(kid), render, float(both.mean()), float(np.median(rel)) if len(rel) else nan,
                       float(np.percentile(rel, 90)) if len(rel) else nan,
-                      float(np.abs(render.grey[hit].astype(np.float64) - image[hit].astype(np.float64)).mean()) if hit.any() else nan)
+                      float(np.abs(render.grey[hit].astype(np.float64) - grey[hit].astype(np.float64)).mean()) if hit.any() else nan,
+                      colour_error)
+
+
+def grey_image(bgr) -> np.ndarray:
+    """(H, W) uint8 from a (H, W, 3) B, G, R image: (b 1868 + g 9617 + r 4899 + 8192) >> 14, the library's conversion on the
+    host, for the audit.  It must track ``bgr2gray`` of ``csrc/ekf_pixel.hpp``; ``tests/test_oracle_colour.py`` holds it against
+    the oracle."""
+    a = np.asarray(bgr, np.uint8).astype(np.uint32)
+    return ((a[..., 0] * 1868 + a[..., 1] * 9617 + a[..., 2] * 4899 + 8192) >> 14).astype(np.uint8)
 
 
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
@@ -299,11 +380,11 @@ def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Opti
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey = weld(vol.extract(min_count))
+        vertices, faces, grey, colour = _welded(vol, min_count)
         z_near, z_far = audit_range(maps, tr)
-        h, w = images[0].shape
+        h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)
                   for m, img in zip(maps, images)]
     finally:
         vol.close()
-    return RecordingAudit(RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps), frames, z_near, z_far, vx / 2.0)
+    return RecordingAudit(RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps, colour), frames, z_near, z_far, vx / 2.0)

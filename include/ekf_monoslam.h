@@ -864,6 +864,55 @@ int ekf_raycast_render_view(ekf_fusion* h, ekf_dense* dense, int slot, double z_
 int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, int* width, int* height);
 int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- colour through the dense chain ----------------------------------------------------------------
+ * The three stages above carry one grey value a sample; these additions carry the camera's colour beside it.  Channel
+ * order is B, G, R everywhere (as ekf_set_frame_raw).  DESIGN.md §18.1 pins every operation (integer colour sums, fp64
+ * blends rounded as the grey ones, no atomics); tests/colour_oracle.py restates it.  No grey result, launch or prototype
+ * above changes; ekf_abi_version() stays 6 (additions only).  The ekf_colour_* functions take an ekf_fusion handle: they
+ * are what a colour volume adds to ekf_fusion_* and ekf_raycast_*, in a family of their own so that those two lists stay
+ * as they are.
+ *  - ekf_dense_set_view_colour / _device: as ekf_dense_set_view / _device with `bgr` = height rows of width x 3 bytes,
+ *    `pitch` (>= 3 width) bytes apart.  The slot keeps the colour image; the grey image the sweep reads is made from it on
+ *    the device by one k_bgr_to_grey launch: (b 1868 + g 9617 + r 4899 + 8192) >> 14 a pixel, the conversion of
+ *    ekf_set_frame_raw.  ekf_dense_set_view_colour_from_keyframe: the last emitted raw key frame of a 3-channel raw
+ *    selector, rectified by one k_frame_rectify launch straight into the slot's colour image, K the selector's raw
+ *    rectified camera; any other selector is EKF_ERR_ARG, and EKF_ERR_STATE whenever ekf_keyframe_get_raw_image would
+ *    refuse (ekf_dense_set_view_from_keyframe keeps refusing three channels).  Each of them invalidates the slot's maps;
+ *    ekf_dense_set_view, _device and _from_keyframe drop the slot's colour;
+ *  - ekf_dense_get_view_colour: the colour image of a slot (`pitch` bytes per row); bgr = NULL only asks whether the slot
+ *    has one.  EKF_ERR_STATE if it has none;
+ *  - ekf_colour_create: ekf_fusion_create for a colour volume, which keeps three more planes of unsigned int: the
+ *    sums of B, G and R (65535 maps x 255 < 2^32).  ekf_colour_has: 1 for such a handle, otherwise 0.
+ *    ekf_fusion_integrate on a colour volume runs k_tsdf_integrate_colour: the same voxels, sum and cnt; gsum takes the
+ *    grey of the pixel, the colour planes its channels.  A slot without colour and ekf_fusion_integrate_host add their
+ *    grey value to all three colour planes.  A plain volume behaves as before whatever the slot holds;
+ *  - ekf_colour_integrate_host: ekf_fusion_integrate_host with `bgr` = height rows of width x 3 bytes `pitch`
+ *    (>= 3 width) bytes apart; gsum takes the conversion above of each pixel;
+ *  - ekf_colour_get_volume / ekf_colour_set_volume: the three colour planes back to back (3 nx ny nz elements);
+ *  - ekf_fusion_extract on a colour volume launches k_tsdf_colour_vertices after k_tsdf_emit (not for an empty mesh);
+ *    ekf_colour_get_mesh: 3 x 3 bytes a triangle, B, G, R of each vertex, in the order of ekf_fusion_get_mesh,
+ *    which still delivers the grey; EKF_ERR_STATE by its rules;
+ *  - ekf_raycast_render / _render_view on a colour volume make one k_tsdf_raycast_colour launch in place of
+ *    k_tsdf_raycast: the same depth, normal and grey, and a colour image; ekf_colour_get_render: 3 bytes a pixel, 0 0 0
+ *    without a hit; EKF_ERR_STATE by the rules of ekf_raycast_get;
+ *  - every function that only a colour volume answers is EKF_ERR_STATE on a plain volume (after the argument checks) and
+ *    leaves all earlier results readable;
+ *  - ekf_colour_get_profile: HIP-event milliseconds and launch counts of k_tsdf_integrate_colour ([0]),
+ *    k_tsdf_colour_vertices ([1]) and k_tsdf_raycast_colour ([2]) since the last ekf_fusion_profile. */
+int ekf_dense_set_view_colour(ekf_dense* h, int slot, const unsigned char* bgr, int pitch, const double* K, const double* pose7);
+int ekf_dense_set_view_colour_device(ekf_dense* h, int slot, const void* d_bgr, int pitch, const double* K, const double* pose7);
+int ekf_dense_set_view_colour_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, const double* pose7);
+int ekf_dense_get_view_colour(const ekf_dense* h, int slot, unsigned char* bgr, int pitch);
+int ekf_colour_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, ekf_fusion** out);
+int ekf_colour_has(const ekf_fusion* h);
+int ekf_colour_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* bgr, int pitch, int width, int height,
+                              const double* K, const double* pose7);
+int ekf_colour_get_volume(ekf_fusion* h, unsigned int* csum);
+int ekf_colour_set_volume(ekf_fusion* h, const unsigned int* csum);
+int ekf_colour_get_mesh(ekf_fusion* h, unsigned char* bgr, unsigned long long max_tri);
+int ekf_colour_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+int ekf_colour_get_render(ekf_fusion* h, unsigned char* bgr);
+
 #ifdef __cplusplus
 }
 #endif

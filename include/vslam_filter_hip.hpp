@@ -478,6 +478,24 @@ class DenseStereoHip {
   void setViewFromKeyframe(int slot, KeyframeSelectorHip& selector, const double pose7[7], bool raw = false) {
     check(ekf_dense_set_view_from_keyframe(d_, slot, selector.handle(), raw ? 1 : 0, pose7));
   }
+  // colour views: height rows of width x 3 bytes in B, G, R order, `pitch` bytes apart (0: tight); the
+  // slot keeps the colour image and sweeps its grey conversion
+  void setViewColour(int slot, const unsigned char* bgr, const double K[4], const double pose7[7], int pitch = 0) {
+    check(ekf_dense_set_view_colour(d_, slot, bgr, pitch ? pitch : 3 * w_, K, pose7));
+  }
+  void setViewColourDevice(int slot, const void* d_bgr, const double K[4], const double pose7[7], int pitch = 0) {
+    check(ekf_dense_set_view_colour_device(d_, slot, d_bgr, pitch ? pitch : 3 * w_, K, pose7));
+  }
+  // the last emitted raw key frame of a 3-channel raw selector
+  void setViewColourFromKeyframe(int slot, KeyframeSelectorHip& selector, const double pose7[7]) {
+    check(ekf_dense_set_view_colour_from_keyframe(d_, slot, selector.handle(), pose7));
+  }
+  bool hasColour(int slot) const { return ekf_dense_get_view_colour(d_, slot, nullptr, 0) == EKF_OK; }
+  std::vector<unsigned char> viewColour(int slot) {
+    std::vector<unsigned char> c(3 * pixels());
+    check(ekf_dense_get_view_colour(d_, slot, c.data(), 3 * w_));
+    return c;
+  }
   void setPose(int slot, const double pose7[7]) { check(ekf_dense_set_pose(d_, slot, pose7)); }
   std::vector<unsigned char> viewImage(int slot) {
     std::vector<unsigned char> g(pixels());
@@ -520,18 +538,21 @@ class DenseStereoHip {
 // ekf_monoslam.h: depth maps (of a DenseStereoHip slot, or host arrays) integrated into one truncated signed distance volume
 // on the device, extract() = marching tetrahedra into a triangle soup in a fixed order.  raycast() / raycastView() mirror
 // ekf_raycast_* (section 17): the volume seen from a pose as a depth, a normal and a grey image.  Values are plain arrays.
+// A colour volume (the constructor's `colour`, section 18, ekf_colour_*) also fills the `colour` arrays: B, G, R.
 class TsdfVolumeHip {
  public:
   struct Mesh {
     std::vector<double> xyz;                   // 9 per triangle
     std::vector<unsigned long long> key;       // 3 per triangle: equal keys are bit-equal vertices
     std::vector<unsigned char> grey;           // 3 per triangle
+    std::vector<unsigned char> colour;         // 9 per triangle, B G R of each vertex: colour volumes only
     size_t triangles() const { return key.size() / 3; }
   };
   struct Volume {
     std::vector<float> sum;
     std::vector<unsigned short> cnt;
     std::vector<unsigned int> gsum;
+    std::vector<unsigned int> csum;            // the sums of B, G and R, three planes back to back: colour volumes only
     int maps = 0;
   };
   struct Render {                              // a pixel without a hit: depth 0, normal 0, grey 0
@@ -539,13 +560,15 @@ class TsdfVolumeHip {
     std::vector<float> depth;                  // camera-z depth, height rows of width
     std::vector<float> normal;                 // 3 per pixel: unit, world frame, towards free space
     std::vector<unsigned char> grey;
+    std::vector<unsigned char> colour;         // 3 per pixel, B G R: colour volumes only
   };
 
-  TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0)
-      : n_((size_t)nx * (size_t)ny * (size_t)nz) {
-    if (ekf_fusion_create(nx, ny, nz, origin, voxel, trunc, device, &f_) != EKF_OK)
+  TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0, bool colour = false)
+      : n_((size_t)nx * (size_t)ny * (size_t)nz), colour_(colour) {
+    if ((colour ? ekf_colour_create : ekf_fusion_create)(nx, ny, nz, origin, voxel, trunc, device, &f_) != EKF_OK)
       throw std::runtime_error(std::string("ekf_fusion_create: ") + ekf_fusion_last_error(nullptr));
   }
+  bool hasColour() const { return colour_; }
   ~TsdfVolumeHip() { ekf_fusion_destroy(f_); }
   TsdfVolumeHip(const TsdfVolumeHip&) = delete;
   TsdfVolumeHip& operator=(const TsdfVolumeHip&) = delete;
@@ -559,11 +582,20 @@ class TsdfVolumeHip {
                      const double pose7[7], int pitch = 0) {
     check(ekf_fusion_integrate_host(f_, depth, gray, pitch ? pitch : width, width, height, K, pose7));
   }
+  // a colour volume only: height rows of width x 3 bytes in B, G, R order, `pitch` bytes apart (0: tight)
+  void integrateHostColour(const float* depth, const unsigned char* bgr, int width, int height, const double K[4],
+                           const double pose7[7], int pitch = 0) {
+    check(ekf_colour_integrate_host(f_, depth, bgr, pitch ? pitch : 3 * width, width, height, K, pose7));
+  }
   void reset() { check(ekf_fusion_reset(f_)); }
   Volume volume() {
     Volume v;
     v.sum.resize(n_); v.cnt.resize(n_); v.gsum.resize(n_);
     check(ekf_fusion_get_volume(f_, v.sum.data(), v.cnt.data(), v.gsum.data(), &v.maps));
+    if (colour_) {
+      v.csum.resize(3 * n_);
+      check(ekf_colour_get_volume(f_, v.csum.data()));
+    }
     return v;
   }
   Mesh extract(int min_count = 1) {
@@ -572,6 +604,10 @@ class TsdfVolumeHip {
     Mesh m;
     m.xyz.resize((size_t)n * 9); m.key.resize((size_t)n * 3); m.grey.resize((size_t)n * 3);
     check(ekf_fusion_get_mesh(f_, m.xyz.data(), m.key.data(), m.grey.data(), n));
+    if (colour_) {
+      m.colour.resize((size_t)n * 9);
+      check(ekf_colour_get_mesh(f_, m.colour.data(), n));
+    }
     return m;
   }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
@@ -591,6 +627,8 @@ class TsdfVolumeHip {
   void profile(bool enable) { check(ekf_fusion_profile(f_, enable ? 1 : 0)); }
   // HIP-event milliseconds and launch counts of k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit
   void getProfile(double kernel_ms[4], long long launches[4]) { check(ekf_fusion_get_profile(f_, kernel_ms, launches)); }
+  // ... and of k_tsdf_integrate_colour, k_tsdf_colour_vertices, k_tsdf_raycast_colour
+  void getColourProfile(double kernel_ms[3], long long launches[3]) { check(ekf_colour_get_profile(f_, kernel_ms, launches)); }
   ekf_fusion* handle() { return f_; }
 
  private:
@@ -601,8 +639,13 @@ class TsdfVolumeHip {
     const size_t n = (size_t)r.width * (size_t)r.height;
     r.depth.resize(n); r.normal.resize(n * 3); r.grey.resize(n);
     check(ekf_raycast_get(f_, r.depth.data(), r.normal.data(), r.grey.data(), nullptr, nullptr));
+    if (colour_) {
+      r.colour.resize(n * 3);
+      check(ekf_colour_get_render(f_, r.colour.data()));
+    }
     return r;
   }
   size_t n_;
+  bool colour_;
   ekf_fusion* f_ = nullptr;
 };
