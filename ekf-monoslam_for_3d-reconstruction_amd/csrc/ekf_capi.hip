@@ -5435,174 +5435,160 @@ static void dense_commit(ekf::DenseView& v, const double* K, const double t[3], 
   v.swept = v.filtered = false;
 }
 
-static int dense_set_view(ekf_dense* h, const char* who, int slot, const void* img, int pitch, const double* K,
+// ---- setting a view, grey (C = 1) or colour (C = 3; DESIGN.md §18.1: the slot keeps the B, G, R image, its grey image is
+// k_bgr_to_grey of it).  What every setter does to its slot round the fill.  dense_view_begin: the device, the buffers, the
+// slot unset, where the fill goes.  dense_view_end: the grey image of a colour one, K and the pose, the slot set.
+static hipError_t dense_view_begin(ekf::DenseStereo* d, ekf::DenseView& v, int C, unsigned char** dst) {
+  hipError_t e = hipSetDevice(d->device);
+  if (e == hipSuccess) e = v.img.reserve(d->npix());
+  if (e == hipSuccess && C == 3) e = v.bgr.reserve(3 * d->npix());
+  if (e != hipSuccess) return e;
+  v.set = v.colour = false;
+  *dst = C == 3 ? (unsigned char*)v.bgr : (unsigned char*)v.img;
+  return hipSuccess;
+}
+
+static hipError_t dense_view_end(ekf::DenseStereo* d, ekf::DenseView& v, int C, const double* K, const double t[3], const double R[9],
+                                 const double q[4]) {
+  const hipError_t e = C == 3 ? d->grey_from_colour(v) : hipSuccess;
+  if (e != hipSuccess) return e;
+  dense_commit(v, K, t, R, q);
+  v.set = true;
+  v.colour = C == 3;
+  return hipSuccess;
+}
+
+// An image from the host, or from the device without a host synchronisation: rows of C W bytes, `pitch` apart.
+static int dense_set_view(ekf_dense* h, const char* who, int C, int slot, const void* img, int pitch, const double* K,
                           const double* pose7, bool device_src) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
   double t[3], R[9], q[4];
-  if (!img || !K || pitch < d->W) {
-    d->err = std::string(who) + ": img and K must not be NULL and pitch >= width";
+  if (!img || !K || pitch < C * d->W) {
+    d->err = std::string(who) + (C == 3 ? ": bgr and K must not be NULL and pitch >= 3 width"
+                                        : ": img and K must not be NULL and pitch >= width");
     return EKF_ERR_ARG;
   }
   const int rc = dense_view_args(d, who, slot, K, pose7, t, R, q);
   if (rc != EKF_OK) return rc;
   std::string& err = d->err;
   ekf::DenseView& v = d->v[slot];
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(v.img.reserve(d->npix()));
-  v.set = v.colour = false;
+  const size_t row = (size_t)C * d->W;
+  unsigned char* dst;
+  HIPCHK(dense_view_begin(d, v, C, &dst));
   if (device_src)
-    HIPCHK(hipMemcpy2DAsync(v.img, (size_t)d->W, img, (size_t)pitch, (size_t)d->W, (size_t)d->H, hipMemcpyDeviceToDevice, nullptr));
+    HIPCHK(hipMemcpy2DAsync(dst, row, img, (size_t)pitch, row, (size_t)d->H, hipMemcpyDeviceToDevice, nullptr));
   else
-    HIPCHK(hipMemcpy2D(v.img, (size_t)d->W, img, (size_t)pitch, (size_t)d->W, (size_t)d->H, hipMemcpyHostToDevice));
-  dense_commit(v, K, t, R, q);
-  v.set = true;
+    HIPCHK(hipMemcpy2D(dst, row, img, (size_t)pitch, row, (size_t)d->H, hipMemcpyHostToDevice));
+  HIPCHK(dense_view_end(d, v, C, K, t, R, q));
   return EKF_OK;
 }
 
 int ekf_dense_set_view(ekf_dense* h, int slot, const unsigned char* img, int pitch, const double* K, const double* pose7) {
-  return dense_set_view(h, "ekf_dense_set_view", slot, img, pitch, K, pose7, false);
+  return dense_set_view(h, "ekf_dense_set_view", 1, slot, img, pitch, K, pose7, false);
 }
 
 int ekf_dense_set_view_device(ekf_dense* h, int slot, const void* d_img, int pitch, const double* K, const double* pose7) {
-  return dense_set_view(h, "ekf_dense_set_view_device", slot, d_img, pitch, K, pose7, true);
-}
-
-int ekf_dense_set_view_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, int raw, const double* pose7) {
-  if (!h) return EKF_ERR_ARG;
-  auto* d = h->impl;
-  double t[3], R[9], q[4];
-  if (!selector || (raw != 0 && raw != 1)) {
-    d->err = "ekf_dense_set_view_from_keyframe: a selector, and raw is 0 or 1";
-    return EKF_ERR_ARG;
-  }
-  const int rc = dense_view_args(d, "ekf_dense_set_view_from_keyframe", slot, nullptr, pose7, t, R, q);
-  if (rc != EKF_OK) return rc;
-  auto* k = selector->impl;
-  const int W = raw ? k->raw_w : k->img_w, H = raw ? k->raw_h : k->img_h;
-  if (W != d->W || H != d->H || (raw && k->raw_c != 1) || k->device != d->device) {
-    d->err = "ekf_dense_set_view_from_keyframe: the selector's image at that resolution must have the handle's size, one channel "
-             "and the handle's device";
-    return EKF_ERR_ARG;
-  }
-  if (!k->have_emit || !(raw ? k->emit_has_raw : k->emit_has_image) || (raw && k->scale < 1)) {
-    d->err = "ekf_dense_set_view_from_keyframe: no emitted key frame with such an image (the rules of ekf_keyframe_get_image / "
-             "ekf_keyframe_get_raw_image)";
-    return EKF_ERR_STATE;
-  }
-  std::string& err = d->err;
-  ekf::DenseView& v = d->v[slot];
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(v.img.reserve(d->npix()));
-  v.set = v.colour = false;
-  const ekf::RectCam c = ekf::rect_cam(k->cam, raw ? k->scale : 1);
-  const ekf::RectifyArgs a{raw ? k->d_emit_raw : k->d_emit, v.img, W, H, c};
-  const int grid = (int)std::min<size_t>((d->npix() + 255) / 256, 1024);
-  ekf::k_frame_rectify<1><<<grid, 256, 0, nullptr>>>(a);
-  HIPCHK(hipGetLastError());
-  double K[4];
-  ekf::rect_camera(c, K);
-  dense_commit(v, K, t, R, q);
-  v.set = true;
-  return EKF_OK;
-}
-
-// ---- colour views: the slot keeps the B, G, R image, its grey image is k_bgr_to_grey of it
-static int dense_set_view_colour(ekf_dense* h, const char* who, int slot, const void* bgr, int pitch, const double* K,
-                                 const double* pose7, bool device_src) {
-  if (!h) return EKF_ERR_ARG;
-  auto* d = h->impl;
-  double t[3], R[9], q[4];
-  if (!bgr || !K || pitch < 3 * d->W) {
-    d->err = std::string(who) + ": bgr and K must not be NULL and pitch >= 3 width";
-    return EKF_ERR_ARG;
-  }
-  const int rc = dense_view_args(d, who, slot, K, pose7, t, R, q);
-  if (rc != EKF_OK) return rc;
-  std::string& err = d->err;
-  ekf::DenseView& v = d->v[slot];
-  const size_t row = 3 * (size_t)d->W;
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(v.img.reserve(d->npix()));
-  HIPCHK(v.bgr.reserve(3 * d->npix()));
-  v.set = v.colour = false;
-  if (device_src)
-    HIPCHK(hipMemcpy2DAsync(v.bgr, row, bgr, (size_t)pitch, row, (size_t)d->H, hipMemcpyDeviceToDevice, nullptr));
-  else
-    HIPCHK(hipMemcpy2D(v.bgr, row, bgr, (size_t)pitch, row, (size_t)d->H, hipMemcpyHostToDevice));
-  HIPCHK(d->grey_from_colour(v));
-  dense_commit(v, K, t, R, q);
-  v.set = v.colour = true;
-  return EKF_OK;
+  return dense_set_view(h, "ekf_dense_set_view_device", 1, slot, d_img, pitch, K, pose7, true);
 }
 
 int ekf_dense_set_view_colour(ekf_dense* h, int slot, const unsigned char* bgr, int pitch, const double* K, const double* pose7) {
-  return dense_set_view_colour(h, "ekf_dense_set_view_colour", slot, bgr, pitch, K, pose7, false);
+  return dense_set_view(h, "ekf_dense_set_view_colour", 3, slot, bgr, pitch, K, pose7, false);
 }
 
 int ekf_dense_set_view_colour_device(ekf_dense* h, int slot, const void* d_bgr, int pitch, const double* K, const double* pose7) {
-  return dense_set_view_colour(h, "ekf_dense_set_view_colour_device", slot, d_bgr, pitch, K, pose7, true);
+  return dense_set_view(h, "ekf_dense_set_view_colour_device", 3, slot, d_bgr, pitch, K, pose7, true);
 }
 
-int ekf_dense_set_view_colour_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, const double* pose7) {
+// The emitted key frame of a selector, rectified straight into the slot: its image (raw = 0) or its raw image (raw = 1) of one
+// channel, or its raw image of three (C = 3, where raw is 1).  K is the rectified camera at that resolution.
+static int dense_set_view_from_keyframe(ekf_dense* h, int C, int slot, const ekf_keyframe* selector, int raw, const double* pose7) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
+  const bool colour = C == 3;
+  const char* who = colour ? "ekf_dense_set_view_colour_from_keyframe" : "ekf_dense_set_view_from_keyframe";
   double t[3], R[9], q[4];
-  if (!selector) {
-    d->err = "ekf_dense_set_view_colour_from_keyframe: a selector";
+  if (!selector || (raw != 0 && raw != 1)) {
+    d->err = std::string(who) + (colour ? ": a selector" : ": a selector, and raw is 0 or 1");
     return EKF_ERR_ARG;
   }
-  const int rc = dense_view_args(d, "ekf_dense_set_view_colour_from_keyframe", slot, nullptr, pose7, t, R, q);
+  const int rc = dense_view_args(d, who, slot, nullptr, pose7, t, R, q);
   if (rc != EKF_OK) return rc;
   auto* k = selector->impl;
-  if (k->raw_w != d->W || k->raw_h != d->H || k->raw_c != 3 || k->device != d->device) {
-    d->err = "ekf_dense_set_view_colour_from_keyframe: the selector's raw image must have the handle's size, three channels and "
-             "the handle's device";
+  const int W = raw ? k->raw_w : k->img_w, H = raw ? k->raw_h : k->img_h;
+  if (W != d->W || H != d->H || (raw && k->raw_c != C) || k->device != d->device) {
+    d->err = std::string(who) + (colour ? ": the selector's raw image must have the handle's size, three channels and the handle's device"
+                                        : ": the selector's image at that resolution must have the handle's size, one channel and the "
+                                          "handle's device");
     return EKF_ERR_ARG;
   }
-  if (!k->have_emit || !k->emit_has_raw || k->scale < 1) {
-    d->err = "ekf_dense_set_view_colour_from_keyframe: no emitted key frame with a raw image (the rules of "
-             "ekf_keyframe_get_raw_image)";
+  if (!k->have_emit || !(raw ? k->emit_has_raw : k->emit_has_image) || (raw && k->scale < 1)) {
+    d->err = std::string(who) + (colour ? ": no emitted key frame with a raw image (the rules of ekf_keyframe_get_raw_image)"
+                                        : ": no emitted key frame with such an image (the rules of ekf_keyframe_get_image / "
+                                          "ekf_keyframe_get_raw_image)");
     return EKF_ERR_STATE;
   }
   std::string& err = d->err;
   ekf::DenseView& v = d->v[slot];
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(v.img.reserve(d->npix()));
-  HIPCHK(v.bgr.reserve(3 * d->npix()));
-  v.set = v.colour = false;
-  const ekf::RectCam c = ekf::rect_cam(k->cam, k->scale);
-  const ekf::RectifyArgs a{k->d_emit_raw, v.bgr, d->W, d->H, c};
+  unsigned char* dst;
+  HIPCHK(dense_view_begin(d, v, C, &dst));
+  const ekf::RectCam c = ekf::rect_cam(k->cam, raw ? k->scale : 1);
+  const ekf::RectifyArgs a{raw ? k->d_emit_raw : k->d_emit, dst, W, H, c};
   const int grid = (int)std::min<size_t>((d->npix() + 255) / 256, 1024);
-  ekf::k_frame_rectify<3><<<grid, 256, 0, nullptr>>>(a);
+  if (colour)
+    ekf::k_frame_rectify<3><<<grid, 256, 0, nullptr>>>(a);
+  else
+    ekf::k_frame_rectify<1><<<grid, 256, 0, nullptr>>>(a);
   HIPCHK(hipGetLastError());
-  HIPCHK(d->grey_from_colour(v));
   double K[4];
   ekf::rect_camera(c, K);
-  dense_commit(v, K, t, R, q);
-  v.set = v.colour = true;
+  HIPCHK(dense_view_end(d, v, C, K, t, R, q));
   return EKF_OK;
 }
 
-int ekf_dense_get_view_colour(const ekf_dense* h, int slot, unsigned char* bgr, int pitch) {
+int ekf_dense_set_view_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, int raw, const double* pose7) {
+  return dense_set_view_from_keyframe(h, 1, slot, selector, raw, pose7);
+}
+
+int ekf_dense_set_view_colour_from_keyframe(ekf_dense* h, int slot, const ekf_keyframe* selector, const double* pose7) {
+  return dense_set_view_from_keyframe(h, 3, slot, selector, 1, pose7);
+}
+
+// The slot's grey image with K and pose (C = 1) or its colour image (C = 3; K and pose7 NULL).  out == NULL only asks.
+static int dense_get_view(const ekf_dense* h, int C, int slot, unsigned char* out, int pitch, double* K, double* pose7) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
-  if (slot < 0 || slot >= d->max_views || (bgr && pitch < 3 * d->W)) {
-    d->err = "ekf_dense_get_view_colour: slot in 0..max_views-1 and pitch >= 3 width";
+  const bool colour = C == 3;
+  if (slot < 0 || slot >= d->max_views || (out && pitch < C * d->W)) {
+    d->err = colour ? "ekf_dense_get_view_colour: slot in 0..max_views-1 and pitch >= 3 width"
+                    : "ekf_dense_get_view: slot in 0..max_views-1 and pitch >= width";
     return EKF_ERR_ARG;
   }
   const ekf::DenseView& v = d->v[slot];
-  if (!v.set || !v.colour) {
-    d->err = "ekf_dense_get_view_colour: the slot holds no colour image";
+  if (!v.set || (colour && !v.colour)) {
+    d->err = colour ? "ekf_dense_get_view_colour: the slot holds no colour image" : "ekf_dense_get_view: the slot is not set";
     return EKF_ERR_STATE;
   }
   std::string& err = d->err;
-  if (bgr) {
-    const size_t row = 3 * (size_t)d->W;
+  if (out) {
+    const size_t row = (size_t)C * d->W;
     HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipMemcpy2D(bgr, (size_t)pitch, v.bgr, row, row, (size_t)d->H, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(out, (size_t)pitch, colour ? v.bgr : v.img, row, row, (size_t)d->H, hipMemcpyDeviceToHost));
+  }
+  if (K) std::copy(v.K, v.K + 4, K);
+  if (pose7) {
+    std::copy(v.t, v.t + 3, pose7);
+    std::copy(v.q, v.q + 4, pose7 + 3);
   }
   return EKF_OK;
+}
+
+int ekf_dense_get_view(const ekf_dense* h, int slot, unsigned char* img, int pitch, double* K, double* pose7) {
+  return dense_get_view(h, 1, slot, img, pitch, K, pose7);
+}
+
+int ekf_dense_get_view_colour(const ekf_dense* h, int slot, unsigned char* bgr, int pitch) {
+  return dense_get_view(h, 3, slot, bgr, pitch, nullptr, nullptr);
 }
 
 int ekf_dense_set_pose(ekf_dense* h, int slot, const double* pose7) {
@@ -5616,31 +5602,6 @@ int ekf_dense_set_pose(ekf_dense* h, int slot, const double* pose7) {
     return EKF_ERR_ARG;
   }
   dense_commit(d->v[slot], nullptr, t, R, q);
-  return EKF_OK;
-}
-
-int ekf_dense_get_view(const ekf_dense* h, int slot, unsigned char* img, int pitch, double* K, double* pose7) {
-  if (!h) return EKF_ERR_ARG;
-  auto* d = h->impl;
-  if (slot < 0 || slot >= d->max_views || (img && pitch < d->W)) {
-    d->err = "ekf_dense_get_view: slot in 0..max_views-1 and pitch >= width";
-    return EKF_ERR_ARG;
-  }
-  const ekf::DenseView& v = d->v[slot];
-  if (!v.set) {
-    d->err = "ekf_dense_get_view: the slot is not set";
-    return EKF_ERR_STATE;
-  }
-  std::string& err = d->err;
-  if (img) {
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipMemcpy2D(img, (size_t)pitch, v.img, (size_t)d->W, (size_t)d->W, (size_t)d->H, hipMemcpyDeviceToHost));
-  }
-  if (K) std::copy(v.K, v.K + 4, K);
-  if (pose7) {
-    std::copy(v.t, v.t + 3, pose7);
-    std::copy(v.q, v.q + 4, pose7 + 3);
-  }
   return EKF_OK;
 }
 
@@ -5848,30 +5809,6 @@ int ekf_fusion_integrate(ekf_fusion* h, ekf_dense* dense, int slot, int filtered
   return EKF_OK;
 }
 
-int ekf_fusion_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* img, int pitch, int width, int height,
-                              const double* K, const double* pose7) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  double t[3], R[9], q[4];
-  if (!depth || !img || !K || !pose7 || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
-      height > ekf::kFusionMaxMapDim || pitch < width || !pinhole_ok(K) || !ekf::dense_pose(pose7, t, R, q)) {
-    f->err = "ekf_fusion_integrate_host: depth, img, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= width; K finite "
-             "with fx, fy > 0; pose7 finite with q != 0";
-    return EKF_ERR_ARG;
-  }
-  const int room = fusion_room(f, "ekf_fusion_integrate_host");
-  if (room != EKF_OK) return room;
-  std::string& err = f->err;
-  const size_t n = (size_t)width * height;
-  HIPCHK(hipSetDevice(f->device));
-  HIPCHK(f->d_depth.reserve(n));
-  HIPCHK(f->d_img.reserve(n));
-  HIPCHK(hipMemcpy(f->d_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy2D(f->d_img, (size_t)width, img, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
-  HIPCHK(f->integrate(f->d_depth, f->d_img, width, height, K, R, t));
-  return EKF_OK;
-}
-
 // A call that only a colour volume answers: EKF_OK, or EKF_ERR_STATE with the message set (nothing else is touched).
 static int fusion_colour_only(ekf::TsdfFusion* f, const char* who) {
   if (!f->colour) {
@@ -5881,30 +5818,46 @@ static int fusion_colour_only(ekf::TsdfFusion* f, const char* who) {
   return EKF_OK;
 }
 
-int ekf_colour_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* bgr, int pitch, int width, int height,
-                              const double* K, const double* pose7) {
+// A map from the host with a grey image (C = 1) or a colour one (C = 3, a colour volume only): rows of C width bytes.
+static int fusion_integrate_host(ekf_fusion* h, int C, const float* depth, const unsigned char* img, int pitch, int width, int height,
+                                 const double* K, const double* pose7) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
+  const bool colour = C == 3;
+  const char* who = colour ? "ekf_colour_integrate_host" : "ekf_fusion_integrate_host";
   double t[3], R[9], q[4];
-  if (!depth || !bgr || !K || !pose7 || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
-      height > ekf::kFusionMaxMapDim || pitch < 3 * width || !pinhole_ok(K) || !ekf::dense_pose(pose7, t, R, q)) {
-    f->err = "ekf_colour_integrate_host: depth, bgr, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= 3 width; "
+  if (!depth || !img || !K || !pose7 || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
+      height > ekf::kFusionMaxMapDim || pitch < C * width || !pinhole_ok(K) || !ekf::dense_pose(pose7, t, R, q)) {
+    f->err = std::string(who) + (colour ? ": depth, bgr, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= 3 width; "
+                                        : ": depth, img, K and pose7 not NULL; 1 <= width, height <= 8192; pitch >= width; ") +
              "K finite with fx, fy > 0; pose7 finite with q != 0";
     return EKF_ERR_ARG;
   }
-  const int kind = fusion_colour_only(f, "ekf_colour_integrate_host");
+  const int kind = colour ? fusion_colour_only(f, who) : EKF_OK;
   if (kind != EKF_OK) return kind;
-  const int room = fusion_room(f, "ekf_colour_integrate_host");
+  const int room = fusion_room(f, who);
   if (room != EKF_OK) return room;
   std::string& err = f->err;
-  const size_t n = (size_t)width * height, row = 3 * (size_t)width;
+  const size_t n = (size_t)width * height, row = (size_t)C * width;
+  ekf::DevBuf<unsigned char>& d_img = colour ? f->d_bgr : f->d_img;
   HIPCHK(hipSetDevice(f->device));
   HIPCHK(f->d_depth.reserve(n));
-  HIPCHK(f->d_bgr.reserve(3 * n));
+  HIPCHK(d_img.reserve(C * n));
   HIPCHK(hipMemcpy(f->d_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy2D(f->d_bgr, row, bgr, (size_t)pitch, row, (size_t)height, hipMemcpyHostToDevice));
-  HIPCHK(f->integrate(f->d_depth, nullptr, width, height, K, R, t, f->d_bgr));
+  HIPCHK(hipMemcpy2D(d_img, row, img, (size_t)pitch, row, (size_t)height, hipMemcpyHostToDevice));
+  HIPCHK(f->integrate(f->d_depth, colour ? nullptr : (const unsigned char*)d_img, width, height, K, R, t,
+                      colour ? (const unsigned char*)d_img : nullptr));
   return EKF_OK;
+}
+
+int ekf_fusion_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* img, int pitch, int width, int height,
+                              const double* K, const double* pose7) {
+  return fusion_integrate_host(h, 1, depth, img, pitch, width, height, K, pose7);
+}
+
+int ekf_colour_integrate_host(ekf_fusion* h, const float* depth, const unsigned char* bgr, int pitch, int width, int height,
+                              const double* K, const double* pose7) {
+  return fusion_integrate_host(h, 3, depth, bgr, pitch, width, height, K, pose7);
 }
 
 int ekf_colour_get_volume(ekf_fusion* h, unsigned int* csum) {
@@ -5997,38 +5950,35 @@ int ekf_fusion_extract(ekf_fusion* h, int min_count, unsigned long long* n_tri) 
   return EKF_OK;
 }
 
-int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, unsigned char* grey, unsigned long long max_tri) {
+// The mesh of the last extract: positions, keys and grey (ekf_fusion_get_mesh), or the vertex colours of a colour volume
+// (ekf_colour_get_mesh: bgr alone, which may be NULL).  A NULL array is not copied.
+static int fusion_get_mesh(ekf_fusion* h, const char* who, bool colour, double* xyz, unsigned long long* key, unsigned char* grey,
+                           unsigned char* bgr, unsigned long long max_tri) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
+  const int kind = colour ? fusion_colour_only(f, who) : EKF_OK;
+  if (kind != EKF_OK) return kind;
   if (!f->mesh_valid) {
-    f->err = "ekf_fusion_get_mesh: no ekf_fusion_extract since the volume last changed";
+    f->err = std::string(who) + ": no ekf_fusion_extract since the volume last changed";
     return EKF_ERR_STATE;
   }
   std::string& err = f->err;
   const size_t nv = (size_t)std::min(f->n_tri, max_tri) * 3;
-  if (nv == 0) return EKF_OK;
+  if (nv == 0 || (colour && !bgr)) return EKF_OK;
   HIPCHK(hipSetDevice(f->device));
   if (xyz) HIPCHK(hipMemcpy(xyz, f->m_xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
   if (key) HIPCHK(hipMemcpy(key, f->m_key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   if (grey) HIPCHK(hipMemcpy(grey, f->m_grey, nv, hipMemcpyDeviceToHost));
+  if (bgr) HIPCHK(hipMemcpy(bgr, f->m_bgr, nv * 3, hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 
+int ekf_fusion_get_mesh(ekf_fusion* h, double* xyz, unsigned long long* key, unsigned char* grey, unsigned long long max_tri) {
+  return fusion_get_mesh(h, "ekf_fusion_get_mesh", false, xyz, key, grey, nullptr, max_tri);
+}
+
 int ekf_colour_get_mesh(ekf_fusion* h, unsigned char* bgr, unsigned long long max_tri) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  const int kind = fusion_colour_only(f, "ekf_colour_get_mesh");
-  if (kind != EKF_OK) return kind;
-  if (!f->mesh_valid) {
-    f->err = "ekf_colour_get_mesh: no ekf_fusion_extract since the volume last changed";
-    return EKF_ERR_STATE;
-  }
-  std::string& err = f->err;
-  const size_t nv = (size_t)std::min(f->n_tri, max_tri) * 3;
-  if (nv == 0 || !bgr) return EKF_OK;
-  HIPCHK(hipSetDevice(f->device));
-  HIPCHK(hipMemcpy(bgr, f->m_bgr, nv * 3, hipMemcpyDeviceToHost));
-  return EKF_OK;
+  return fusion_get_mesh(h, "ekf_colour_get_mesh", true, nullptr, nullptr, nullptr, bgr, max_tri);
 }
 
 int ekf_fusion_profile(ekf_fusion* h, int enable) {
@@ -6113,38 +6063,37 @@ int ekf_raycast_render_view(ekf_fusion* h, ekf_dense* dense, int slot, double z_
   return EKF_OK;
 }
 
-int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, int* width, int* height) {
+// The last render: depth, normal, grey and size (ekf_raycast_get), or the colour image of a colour volume
+// (ekf_colour_get_render: bgr alone, which may be NULL).  A NULL array is not copied.
+static int raycast_get(ekf_fusion* h, const char* who, bool colour, float* depth, float* normal, unsigned char* grey,
+                       unsigned char* bgr, int* width, int* height) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
+  const int kind = colour ? fusion_colour_only(f, who) : EKF_OK;
+  if (kind != EKF_OK) return kind;
   if (!h->rc.current(*f)) {
-    f->err = "ekf_raycast_get: no ekf_raycast_render since the volume last changed";
+    f->err = std::string(who) + ": no ekf_raycast_render since the volume last changed";
     return EKF_ERR_STATE;
   }
   std::string& err = f->err;
   const size_t n = (size_t)h->rc.W * h->rc.H;
+  if (colour && !bgr) return EKF_OK;
   HIPCHK(hipSetDevice(f->device));
   if (depth) HIPCHK(hipMemcpy(depth, h->rc.depth, n * sizeof(float), hipMemcpyDeviceToHost));
   if (normal) HIPCHK(hipMemcpy(normal, h->rc.normal, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
   if (grey) HIPCHK(hipMemcpy(grey, h->rc.grey, n, hipMemcpyDeviceToHost));
+  if (bgr) HIPCHK(hipMemcpy(bgr, h->rc.bgr, n * 3, hipMemcpyDeviceToHost));
   if (width) *width = h->rc.W;
   if (height) *height = h->rc.H;
   return EKF_OK;
 }
 
+int ekf_raycast_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, int* width, int* height) {
+  return raycast_get(h, "ekf_raycast_get", false, depth, normal, grey, nullptr, width, height);
+}
+
 int ekf_colour_get_render(ekf_fusion* h, unsigned char* bgr) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  const int kind = fusion_colour_only(f, "ekf_colour_get_render");
-  if (kind != EKF_OK) return kind;
-  if (!h->rc.current(*f)) {
-    f->err = "ekf_colour_get_render: no ekf_raycast_render since the volume last changed";
-    return EKF_ERR_STATE;
-  }
-  std::string& err = f->err;
-  if (!bgr) return EKF_OK;
-  HIPCHK(hipSetDevice(f->device));
-  HIPCHK(hipMemcpy(bgr, h->rc.bgr, (size_t)h->rc.W * h->rc.H * 3, hipMemcpyDeviceToHost));
-  return EKF_OK;
+  return raycast_get(h, "ekf_colour_get_render", true, nullptr, nullptr, nullptr, bgr, nullptr, nullptr);
 }
 
 int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {

@@ -316,7 +316,8 @@ struct ColourVertexArgs {
 
 // The colours of the vertices of a mesh (§18.1), after k_tsdf_emit and from its keys alone, one lane per vertex: key =
 // 8 la + d, and since every Kuhn edge runs componentwise upwards the bits of d = cb - ca are the steps to the edge's other
-// end.  na, nb, va, vb and u are tsdf_vertex's, operation for operation; a channel is blended and rounded as its grey is.
+// end.  na, nb, va, vb and u are tsdf_vertex's, operation for operation; a channel is blended and rounded as its grey is.  They
+// are restated, not shared: a function for them reorders the instructions of k_tsdf_emit.
 __global__ void __launch_bounds__(256) k_tsdf_colour_vertices(ColourVertexArgs a) {
 #pragma clang fp contract(off)
   const unsigned long long v = (unsigned long long)blockIdx.x * (unsigned long long)kFusionBlock + threadIdx.x;

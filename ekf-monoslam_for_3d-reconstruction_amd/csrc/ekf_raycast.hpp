@@ -6,7 +6,8 @@
 //     sample's validity and value, and ends at the first pair of valid samples that goes from v >= 0 to v < 0;
 //   - every coordinate operation is fp64, rounded once, in the written left-to-right order; contraction is off in every
 //     function below (host and device), as in ekf_fusion.hpp; poses go through dense_pose unchanged.
-//   - k_tsdf_raycast_colour is the same march for a colour volume: it also writes the B, G, R of the hit.
+//   - k_tsdf_raycast_colour runs the same march, rc_march, for a colour volume: it also writes the B, G, R of
+//     the hit.
 // No atomics, no LDS: a pixel belongs to one lane.  Nothing here touches a filter, counts as a launch kind or runs a collective.
 #pragma once
 #include <cmath>
@@ -148,22 +149,25 @@ __device__ __forceinline__ void rc_range(const RaycastArgs& a, const double dw[3
   if (empty) n_lo = a.N;
 }
 
-// One lane per pixel.  A wave owns an 8 x 8 tile of pixels and a workgroup 16 x 16, so that the rays of a wave walk
-// neighbouring voxels and its 8 corner loads fall in few cache lines.  The loop of a wave ends when each of its lanes has hit
-// or run out of samples; a lane that is done is masked off and loads nothing.
-__global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
+// What the march of a colour volume has beside RaycastArgs (DESIGN.md §18.1).
+struct RaycastColour {
+  const unsigned* csum;               // three planes of nvox back to back
+  unsigned char* bgr;                 // H rows of W x 3 bytes: B, G, R; 0, 0, 0 = no hit
+  size_t nvox;
+};
+
+// The march of pixel (px, py) over the samples n .. n_hi of rc_range, and its stores: the one body of both ray-cast kernels.
+// The loop of a wave ends when each of its lanes has hit or run out of samples; a lane that is done is masked off and loads
+// nothing.  A hit gives 1 + C bytes: byte 0 from gsum and, for C = 3, one from each plane of k->csum (k is not read for C = 0);
+// each is plane / cnt at the eight corners of the hit's cell, blended as the means are and rounded half up.  Each kernel keeps
+// its own prologue (the pixel, the off-image return, dw and rc_range): with the prologue in here too, k_tsdf_raycast compiles
+// to other instructions than it did with a body of its own.
+template <int C>
+__device__ __forceinline__ void rc_march(const RaycastArgs& a, const RaycastColour* k, int px, int py, const double dw[3], int n,
+                                         int n_hi) {
 #pragma clang fp contract(off)
-  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int px = (int)(blockIdx.x * (unsigned)kRaycastTile + (wave & 1) * 8 + (lane & 7));
-  const int py = (int)(blockIdx.y * (unsigned)kRaycastTile + (wave >> 1) * 8 + (lane >> 3));
-  if (px >= a.W || py >= a.H) return;
-  const double dc0 = ((double)px - a.cx) / a.fx, dc1 = ((double)py - a.cy) / a.fy;
-  const double dw[3] = {a.R[0] * dc0 + a.R[1] * dc1 + a.R[2], a.R[3] * dc0 + a.R[4] * dc1 + a.R[5],
-                        a.R[6] * dc0 + a.R[7] * dc1 + a.R[8]};
-  int n, n_hi;
-  rc_range(a, dw, n, n_hi);
   float depth = 0.f, nrm0 = 0.f, nrm1 = 0.f, nrm2 = 0.f;
-  unsigned char grey = 0;
+  unsigned char byte[1 + C] = {};
   bool pok = false;                   // the previous sample was valid, and its value
   double pv = 0.0;
   for (; n <= n_hi; ++n) {
@@ -190,11 +194,15 @@ __global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
           nrm2 = (float)(gz / len);
         }
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const unsigned l = rc_corner(a, lin0, c);
-          v[c] = (double)a.gsum[l] / (double)a.cnt[l];
+        for (int p = 0; p <= C; ++p) {
+          const unsigned* plane = p == 0 ? a.gsum : k->csum + (p - 1) * k->nvox;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const unsigned l = rc_corner(a, lin0, c);
+            v[c] = (double)plane[l] / (double)a.cnt[l];
+          }
+          byte[p] = (unsigned char)(int)floor(rc_trilinear(v, f0, f1, f2) + 0.5);
         }
-        grey = (unsigned char)(int)floor(rc_trilinear(v, f0, f1, f2) + 0.5);
         depth = (float)zs;
         break;
       }
@@ -207,20 +215,28 @@ __global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
   a.normal[pix * 3 + 0] = nrm0;
   a.normal[pix * 3 + 1] = nrm1;
   a.normal[pix * 3 + 2] = nrm2;
-  a.grey[pix] = grey;
+  a.grey[pix] = byte[0];
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) k->bgr[pix * 3 + ch] = byte[1 + ch];
 }
 
-// What the march of a colour volume has beside RaycastArgs (DESIGN.md §18.1).
-struct RaycastColour {
-  const unsigned* csum;               // three planes of nvox back to back
-  unsigned char* bgr;                 // H rows of W x 3 bytes: B, G, R; 0, 0, 0 = no hit
-  size_t nvox;
-};
+// One lane per pixel.  A wave owns an 8 x 8 tile of pixels and a workgroup 16 x 16, so that the rays of a wave walk
+// neighbouring voxels and its 8 corner loads fall in few cache lines.
+__global__ void __launch_bounds__(256) k_tsdf_raycast(RaycastArgs a) {
+#pragma clang fp contract(off)
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int px = (int)(blockIdx.x * (unsigned)kRaycastTile + (wave & 1) * 8 + (lane & 7));
+  const int py = (int)(blockIdx.y * (unsigned)kRaycastTile + (wave >> 1) * 8 + (lane >> 3));
+  if (px >= a.W || py >= a.H) return;
+  const double dc0 = ((double)px - a.cx) / a.fx, dc1 = ((double)py - a.cy) / a.fy;
+  const double dw[3] = {a.R[0] * dc0 + a.R[1] * dc1 + a.R[2], a.R[3] * dc0 + a.R[4] * dc1 + a.R[5],
+                        a.R[6] * dc0 + a.R[7] * dc1 + a.R[8]};
+  int n, n_hi;
+  rc_range(a, dw, n, n_hi);
+  rc_march<0>(a, nullptr, px, py, dw, n, n_hi);
+}
 
-// The one launch of a colour volume: k_tsdf_raycast's march, statement for statement, with depth, normal and grey as it writes
-// them; at the hit it also blends the eight corners' csum[c] / cnt with the grey's rc_trilinear and fractions, rounds the same
-// way and writes B, G, R.  It has a body of its own, not a template shared with k_tsdf_raycast, so that the grey kernel's
-// source and code object stay what they were; a change to the march is made in both, and
+// The one launch of a colour volume: k_tsdf_raycast with the B, G, R of the hit beside its depth, normal and grey.
 // tests/test_gpu_colour.py holds the depth, normal and grey of the two kernels against each other bit for bit.
 __global__ void __launch_bounds__(256) k_tsdf_raycast_colour(RaycastArgs a, RaycastColour k) {
 #pragma clang fp contract(off)
@@ -233,63 +249,7 @@ __global__ void __launch_bounds__(256) k_tsdf_raycast_colour(RaycastArgs a, Rayc
                         a.R[6] * dc0 + a.R[7] * dc1 + a.R[8]};
   int n, n_hi;
   rc_range(a, dw, n, n_hi);
-  float depth = 0.f, nrm0 = 0.f, nrm1 = 0.f, nrm2 = 0.f;
-  unsigned char grey = 0, col[3] = {0, 0, 0};
-  bool pok = false;                   // the previous sample was valid, and its value
-  double pv = 0.0;
-  for (; n <= n_hi; ++n) {
-    const double z = a.z_near + (double)n * a.step;
-    unsigned lin0;
-    double f0, f1, f2, v[8];
-    bool ok = rc_locate(a, a.t[0] + z * dw[0], a.t[1] + z * dw[1], a.t[2] + z * dw[2], lin0, f0, f1, f2);
-    double val = 0.0;
-    if (ok) {
-      ok = rc_means(a, lin0, v);
-      val = rc_trilinear(v, f0, f1, f2);
-    }
-    if (ok && pok && pv >= 0.0 && val < 0.0) {
-      const double u = pv / (pv - val);
-      const double zs = (a.z_near + (double)(n - 1) * a.step) + u * a.step;
-      if (rc_locate(a, a.t[0] + zs * dw[0], a.t[1] + zs * dw[1], a.t[2] + zs * dw[2], lin0, f0, f1, f2) && rc_means(a, lin0, v)) {
-        const double gx = rc_bilinear(v[1] - v[0], v[3] - v[2], v[5] - v[4], v[7] - v[6], f1, f2);
-        const double gy = rc_bilinear(v[2] - v[0], v[3] - v[1], v[6] - v[4], v[7] - v[5], f0, f2);
-        const double gz = rc_bilinear(v[4] - v[0], v[5] - v[1], v[6] - v[2], v[7] - v[3], f0, f1);
-        const double len = sqrt((gx * gx + gy * gy) + gz * gz);
-        if (len > 0.0) {
-          nrm0 = (float)(gx / len);
-          nrm1 = (float)(gy / len);
-          nrm2 = (float)(gz / len);
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const unsigned l = rc_corner(a, lin0, c);
-          v[c] = (double)a.gsum[l] / (double)a.cnt[l];
-        }
-        grey = (unsigned char)(int)floor(rc_trilinear(v, f0, f1, f2) + 0.5);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            const unsigned l = rc_corner(a, lin0, c);
-            v[c] = (double)k.csum[ch * k.nvox + l] / (double)a.cnt[l];
-          }
-          col[ch] = (unsigned char)(int)floor(rc_trilinear(v, f0, f1, f2) + 0.5);
-        }
-        depth = (float)zs;
-        break;
-      }
-    }
-    pok = ok;
-    pv = val;
-  }
-  const size_t pix = (size_t)py * (size_t)a.W + (size_t)px;
-  a.depth[pix] = depth;
-  a.normal[pix * 3 + 0] = nrm0;
-  a.normal[pix * 3 + 1] = nrm1;
-  a.normal[pix * 3 + 2] = nrm2;
-  a.grey[pix] = grey;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) k.bgr[pix * 3 + ch] = col[ch];
+  rc_march<3>(a, &k, px, py, dw, n, n_hi);
 }
 
 #ifndef EKF_KERNELS_ONLY

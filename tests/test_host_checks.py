@@ -1,6 +1,8 @@
-"""The kernel bodies of the dense, fusion and ray-casting headers run lane by lane on the host under AddressSanitizer and
-UBSan (tools/host_kernels.hpp and tools/*_host_check.*).  CPU only."""
+"""The kernel bodies of the dense, fusion and ray-casting headers, the colour kernels among them, run lane by lane on the host
+under AddressSanitizer and UBSan (tools/host_kernels.hpp and tools/*_host_check.*).  CPU
+only."""
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -8,13 +10,15 @@ import time
 
 import pytest
 
+import colour_scene as cs
 import dense_scene as ds
 import fusion_scene as fs
 import raycast_scene as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the cases the writer of each check is to produce, as its scene module names them
-CASES = {"dense": lambda: [c[0] for c in ds.CASES], "fusion": lambda: list(fs.HOST_CHECK_CASES), "raycast": lambda: list(rs.cases())}
+CASES = {"colour": lambda: list(cs.HOST_CHECK_CASES), "dense": lambda: [c[0] for c in ds.CASES],
+         "fusion": lambda: list(fs.HOST_CHECK_CASES), "raycast": lambda: list(rs.cases())}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -44,3 +48,8 @@ def test_kernel_bodies_on_the_host_equal_the_oracle_under_sanitizers(name, tmp_p
     print("%s: %d cases in %.1f s" % (name, len(files), time.perf_counter() - t0))
     assert run.returncode == 0 and run.stdout.strip().endswith("ok") and "DIFFERS" not in run.stdout, run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "Sanitizer" not in run.stderr, run.stderr
+    if name == "colour":
+        # every kernel had work: some case has triangles, some view hits, and the images of k_bgr_to_grey were all seen
+        seen = [tuple(int(v) for v in m) for m in re.findall(r"(\d+) triangles \(oracle \d+\), (\d+) views with (\d+) hits, (\d+) images", run.stdout)]
+        assert len(seen) == len(files) and max(s[0] for s in seen) > 0 and max(s[2] for s in seen) > 0
+        assert max(s[3] for s in seen) == len(cs.GREY_SHAPES + cs.TINY_GREY_SHAPES)

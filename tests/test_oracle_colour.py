@@ -1,6 +1,6 @@
 """The colour contract of the dense chain on the numpy oracle alone, and what of the library can be checked
 without a device: the ABI table, the argument errors, the identities that tie the colour planes to the grey ones, that the GPU
-test shapes contain every case, and the file formats (the kernel bodies on the host: tests/test_host_check_colour.py).
+test shapes contain every case, and the file formats (the kernel bodies on the host: tests/test_host_checks.py).
 CPU only."""
 import ctypes as C
 import os

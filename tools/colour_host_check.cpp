@@ -2,10 +2,7 @@
 //  by host_kernels.hpp, which says how to build and run this.  It reads the case files
 // tools/colour_host_check.py writes (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs) and
 // compares bit for bit.  The keys the vertex colours are made from come from the grey extraction kernels, run here as well.
-#include "host_kernels.hpp"
-
-#include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_stereo.hpp"
-#include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_raycast.hpp"
+#include "host_tsdf.hpp"
 
 static int run(const char* path) {
   FILE* f = std::fopen(path, "rb");
@@ -54,22 +51,11 @@ static int run(const char* path) {
   bad += differs("sum", sum, w_sum) + differs("cnt", cnt, w_cnt) + differs("gsum", gsum, w_gsum) + differs("csum", csum, w_csum);
 
   // the grey extraction for its keys, then k_tsdf_colour_vertices
-  const unsigned ncell = (unsigned)((size_t)(g.nx - 1) * (g.ny - 1) * (g.nz - 1)), nblk = (ncell + 255) / 256;
-  std::vector<unsigned> tot(nblk);
-  std::vector<unsigned long long> off((size_t)nblk + 1);
-  ekf::ExtractArgs e{};
-  e.sum = sum.data(); e.cnt = cnt.data(); e.gsum = gsum.data(); e.g = g; e.min_count = min_count; e.ncell = ncell;
-  e.blk_tot = tot.data(); e.blk_off = off.data();
-  launch({nblk, 1, 1}, [&] { ekf::k_tsdf_count(e); });
-  launch({1, 1, 1}, [&] { ekf::k_tsdf_scan(tot.data(), off.data(), nblk); });
-  const size_t n_tri = (size_t)off[nblk], nv = n_tri * 3;
-  std::vector<double> xyz(n_tri * 9);
-  std::vector<unsigned long long> key(nv);
-  std::vector<unsigned char> grey(nv), vcol(nv * 3, 0xA5);
-  e.xyz = xyz.data(); e.key = key.data(); e.grey = grey.data();
+  const HostMesh mesh = host_extract(sum, cnt, gsum, g, min_count);
+  const size_t n_tri = mesh.n_tri, nv = n_tri * 3;
+  std::vector<unsigned char> vcol(nv * 3, 0xA5);
   if (n_tri) {
-    launch({nblk, 1, 1}, [&] { ekf::k_tsdf_emit(e); });
-    const ekf::ColourVertexArgs c{sum.data(), cnt.data(), csum.data(), key.data(), vcol.data(), (unsigned long long)nv, nvox,
+    const ekf::ColourVertexArgs c{sum.data(), cnt.data(), csum.data(), mesh.key.data(), vcol.data(), (unsigned long long)nv, nvox,
                                   (unsigned)g.nx, (unsigned)g.ny};
     launch({(unsigned)((nv + 255) / 256), 1, 1}, [&] { ekf::k_tsdf_colour_vertices(c); });
   }
@@ -91,14 +77,9 @@ static int run(const char* path) {
     const auto w_col = take<unsigned char>(f, npix * 3);
     std::vector<float> depth(npix, -1.f), normal(npix * 3, -1.f);
     std::vector<unsigned char> rgrey(npix, 0xA5), col(npix * 3, 0xA5);
-    ekf::RaycastArgs a{};
-    a.mean = mean.data(); a.cnt = cnt.data(); a.gsum = gsum.data();
-    a.depth = depth.data(); a.normal = normal.data(); a.grey = rgrey.data();
-    a.W = W; a.H = H; a.g = g; a.inv = 1.0 / g.voxel;
-    a.fx = vp[0]; a.fy = vp[1]; a.cx = vp[2]; a.cy = vp[3];
-    double q[4];
-    if (!ekf::dense_pose(&vp[4], a.t, a.R, q)) return 2;
-    a.z_near = vp[11]; a.step = vp[12]; a.N = whn[2];
+    ekf::RaycastArgs a;
+    if (!host_raycast_args(a, mean.data(), cnt.data(), gsum.data(), depth.data(), normal.data(), rgrey.data(), g, W, H, whn[2], vp.data()))
+      return 2;
     const ekf::RaycastColour k{csum.data(), col.data(), nvox};
     launch({(unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), 1}, [&] { ekf::k_tsdf_raycast_colour(a, k); });
     for (float d : depth) hits += d > 0.f;
