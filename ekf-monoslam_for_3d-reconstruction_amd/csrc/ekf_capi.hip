@@ -18,6 +18,7 @@
 
 #include "../../include/ekf_monoslam.h"
 #include "ekf_buffers.hpp"
+#include "ekf_feature_table.hpp"
 #include "ekf_dense.hpp"
 #include "ekf_image.hpp"
 #include "ekf_features.hpp"
@@ -229,18 +230,11 @@ struct Filter : FilterBase {
   double dT = 1.0;                                     // vR.cpp:155
   double vmax[6];
   int sigma_pixel_2 = 4;
-  std::vector<int> pos, coding;
-  // Patch::real_index (= patchnumbre at creation, vR.cpp:148, 318-319) and Patch::n_find (Patch.cpp:86, 145) per feature;
-  // the patches archived at removal (vR.cpp:394-404): real_index on the host, XYZ + 3x3 covariance on the device
-  std::vector<int> real_index, n_find;
-  int patchnumbre = 1;
-  // the rest of a Patch's track state (Patch.cpp:85-93, 115-125, 218, 253, 279-281): n_tot, center, isInInnovation and
-  // the sticky removeFlag.  ekf_predict / ekf_measure fold their visibility / rho <= 0 flags into d_trk on the device
-  // (bit 0: visible at the last one, bit 1: rho <= 0 since the last read-back); pull_track() folds that into the host
-  // vectors before anything reads them or reorders the features (d_trk is all zero whenever trk_dirty is false)
-  std::vector<int> n_tot;
-  std::vector<float> center;                            // u, v per feature
-  std::vector<unsigned char> in_innovation, remove_flag;
+  // the host records of the features, one per feature (ekf_feature_table.hpp); N == ft.size() at all times.  Of a Patch's track
+  // state, ekf_predict / ekf_measure fold their visibility / rho <= 0 flags into d_trk on the device (bit 0: visible at the
+  // last one, bit 1: rho <= 0 since the last read-back); pull_track() folds that into the table before anything reads it
+  // or reorders the features (d_trk is all zero whenever trk_dirty is false)
+  FeatureTable ft;
   DevBuf<unsigned char> d_trk;
   bool trk_dirty = false;
   // corner seeding (ekf_features.hpp): mask, lambda, [max bits | candidate count], candidates, square origins, selection
@@ -249,6 +243,7 @@ struct Filter : FilterBase {
   DevBuf<unsigned long long> d_seed_aux, d_seed_ckey;
   DevBuf<int> d_seed_cidx, d_seed_org, d_seed_out;
   bool have_seed_lam = false;
+  // the patches archived at removal (vR.cpp:394-404): real_index on the host, XYZ + 3x3 covariance on the device
   std::vector<int> arch_real;
   DevBuf<T> d_archive;                                  // 12 scalars per archived patch
   DevBuf<int> d_arch_idx;
@@ -280,7 +275,7 @@ struct Filter : FilterBase {
   bool have_sd = false;                                  // 2x2 St blocks of the current h/H evaluated?
   bool have_update = false;
   // options
-  int opt_streaming = 0, opt_mfma = 1, opt_profile = 0;
+  int opt_streaming = 0, opt_mfma = 1;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipStream_t stream_b = nullptr;                       // solve pieces / downdate pieces, overlapped with the chain
@@ -365,14 +360,7 @@ struct Filter : FilterBase {
   DevBuf<int> d_counters;                               // one work-queue head per queued launch of an update
   int num_cus = 256, reserved_cus = 32;
   // profiling
-  struct Pending { int kid; hipEvent_t a, b; };
-  std::vector<Pending> pending;
-  std::vector<hipEvent_t> pool;
-  static constexpr int kProfileSamplePeriod = 8;
-  long long frame_seq = 0;                              // updates since the last profile reset (EKF_OPT_PROFILE = 3 samples on it)
-  double prof_ms[KID_COUNT];
-  long long prof_cnt[KID_COUNT];
-  double prof_work[KID_COUNT];                          // algorithmic flop of the timed launches (downdate only)
+  LaunchProfiler<KID_COUNT> prof{KID_DOWNDATE, KID_PROPAGATE_STREAMING};   // mode: EKF_OPT_PROFILE; work[]: downdate only
 
   static constexpr bool kIsF32 = sizeof(T) == 4;
   int NB() const { return (kIsF32 && opt_mfma) ? 128 : 64; }
@@ -390,9 +378,8 @@ struct Filter : FilterBase {
     if (stream_b) hipStreamSynchronize(stream_b);
     if (stream_g) hipStreamSynchronize(stream_g);
     mark("events");
-    for (auto& p : pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
-    for (auto e : pool) hipEventDestroy(e);
-    for (auto e : ev_in) if (e) hipEventDestroy(e);
+    prof.release();                            // the pending pairs, the pool,
+    in_ring.release();                         // ... the slots' events: here, so that the members' destructors find nothing left
     mark("streams");
     if (own_stream && stream) hipStreamDestroy(stream);
     mark("stream b");
@@ -412,41 +399,11 @@ struct Filter : FilterBase {
   }
 
   // ---- profiling helpers ---------------------------------------------------------------
-  bool prof_on(int kid) const {
-    if (opt_profile == 2) return true;
-    const bool dominant = (kid == KID_DOWNDATE || kid == KID_PROPAGATE_STREAMING);
-    if (opt_profile == 1) return dominant;
-    if (opt_profile == 3) return dominant && (frame_seq % kProfileSamplePeriod == 0);   // every 8th frame: an event pair costs ~6 us of queue time
-    return false;
-  }
-  hipEvent_t get_event() {
-    if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-    hipEvent_t e;
-    hipEventCreate(&e);
-    return e;
-  }
-  struct Scope {
-    Filter* f; int kid; hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
-    Scope(Filter* f_, int kid_, hipStream_t st_ = nullptr)
-        : f(f_), kid(kid_), on(f_->prof_on(kid_)), st(st_ ? st_ : f_->stream) {
-      if (on) { a = f->get_event(); b = f->get_event(); hipEventRecord(a, st); }
-    }
-    ~Scope() {
-      if (on) { hipEventRecord(b, st); f->pending.push_back({kid, a, b}); }
-    }
+  // a launch site's `Scope sc(this, KID_X[, stream])`: the profiler's scope on the filter's stream unless one is named
+  struct Scope : LaunchProfiler<KID_COUNT>::Scope {
+    Scope(Filter* f, int kid, hipStream_t st = nullptr) : LaunchProfiler<KID_COUNT>::Scope(f->prof, kid, st ? st : f->stream) {}
   };
-  void resolve_profile() {
-    if (pending.empty()) return;
-    hipStreamSynchronize(stream);
-    hipStreamSynchronize(stream_b);
-    if (stream_g) hipStreamSynchronize(stream_g);
-    for (auto& p : pending) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { prof_ms[p.kid] += ms; prof_cnt[p.kid] += 1; }
-      pool.push_back(p.a); pool.push_back(p.b);
-    }
-    pending.clear();
-  }
+  void resolve_profile() { prof.resolve(stream, stream_b, stream_g); }
 
   // ---- construction ---------------------------------------------------------------------
   int init(const ekf_config* c, int cdim, int capacity, int dev) {
@@ -460,9 +417,7 @@ struct Filter : FilterBase {
     m_cap = 2 * capN + 3;
     ldy = round_up(m_cap, 128);
     w_rows = n_pad + 128;
-    memset(prof_ms, 0, sizeof(prof_ms));
-    memset(prof_cnt, 0, sizeof(prof_cnt));
-    memset(prof_work, 0, sizeof(prof_work));
+    in_ring.configure(sizeof(T), (size_t)capN);
     cam.fx = c->fx; cam.fy = c->fy; cam.u0 = c->u0; cam.v0 = c->v0;
     cam.k1 = c->k1; cam.k2 = c->k2; cam.k3 = c->k3; cam.p1 = c->p1; cam.p2 = c->p2;
     cam.width = c->image_width; cam.height = c->image_height; cam.half_window = c->window_size / 2;
@@ -617,20 +572,15 @@ struct Filter : FilterBase {
   int sync_layout() {
     if (!layout_dirty) return EKF_OK;
     if (N > 0) {
-      HIPCHK(hipMemcpyAsync(d_pos, pos.data(), N * sizeof(int), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(d_coding, coding.data(), N * sizeof(int), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_pos, ft.columns().pos.data(), N * sizeof(int), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_coding, ft.columns().coding.data(), N * sizeof(int), hipMemcpyHostToDevice, stream));
       HIPCHK(hipStreamSynchronize(stream));   // host vectors may change right after
     }
     layout_dirty = false;
     return EKF_OK;
   }
 
-  // z (2 M scalars) and the index list (M ints) of a host caller -> d_z / d_midx through pinned slot `in_slot`
-  static constexpr int kInSlots = 4;
-  PinnedBuf<char> h_in[kInSlots];
-  hipEvent_t ev_in[kInSlots] = {nullptr, nullptr, nullptr, nullptr};
-  bool in_used[kInSlots] = {false, false, false, false};
-  int in_slot = 0;
+  InputRing in_ring;                                    // z, the index list and the rescue's camera pose of a host caller -> d_z / d_midx / d_tmp
   PinnedBuf<char> h_pred;                               // host-mapped read-back buffer of ekf_get_predictions
   PinnedBuf<unsigned char> h_ransac;                    // ... of ekf_ransac_1point: counts, camera pose, small inlier masks
   static constexpr size_t kRansacMaskBytes = 65536;
@@ -640,84 +590,26 @@ struct Filter : FilterBase {
   bool ransac_cam_valid = false;
   PinnedBuf<unsigned char> h_gate;                      // host-mapped gate flags of ekf_rescue_high_innovation
   int stage_inputs(const void* z, const int* idx, int M, const void* cam7 = nullptr) {
-    const size_t zb = (size_t)2 * M * sizeof(T), ib = (size_t)M * sizeof(int);
-    const int s = in_slot;
-    in_slot = (in_slot + 1) % kInSlots;
-    if (!h_in[s]) {
-      HIPCHK(h_in[s].reserve((size_t)capN * (2 * sizeof(T) + sizeof(int)) + 8 * sizeof(T) + 64));
-      HIPCHK(hipEventCreateWithFlags(&ev_in[s], hipEventDisableTiming));
-    }
-    if (in_used[s]) HIPCHK(hipEventSynchronize(ev_in[s]));      // the copies that last used this slot are long done
-    char* base = h_in[s];
-    memcpy(base, z, zb);
-    memcpy(base + (size_t)2 * capN * sizeof(T), idx, ib);
-    HIPCHK(hipMemcpyAsync(d_z, base, zb, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_midx, base + (size_t)2 * capN * sizeof(T), ib, hipMemcpyHostToDevice, stream));
-    if (cam7) {                                         // (the rescue's camera pose of the state before the first update)
-      char* pc7 = base + (size_t)capN * (2 * sizeof(T) + sizeof(int));
-      memcpy(pc7, cam7, 7 * sizeof(T));
-      HIPCHK(hipMemcpyAsync(d_tmp, pc7, 7 * sizeof(T), hipMemcpyHostToDevice, stream));
-    }
-    HIPCHK(hipEventRecord(ev_in[s], stream));
-    in_used[s] = true;
+    HIPCHK(in_ring.stage(stream, M, d_z, z, d_midx, idx, d_tmp, cam7));   // (cam7: the state before the first update)
     return EKF_OK;
   }
 
   // Small device -> host reads of the getters: through ONE pinned bounce buffer, several pieces and the status words per
   // synchronisation (a copy into pageable memory is staged by the runtime and costs ~25 us; every getter used to pay that
   // twice, once for its data and once for the status words).
-  PinnedBuf<char> h_rb;
-  size_t rb_off = 0;
-  struct RbPiece { void* dst; size_t off, bytes; };
-  std::vector<RbPiece> rb_pend;
-  int rb_reserve(size_t bytes) {
-    if (rb_off + bytes + 64 <= h_rb.capacity()) return EKF_OK;
-    if (!rb_pend.empty()) {                            // pieces already queued: deliver them before the buffer moves
-      hipError_t e = hipStreamSynchronize(stream);
-      if (e == hipSuccess)
-        for (const RbPiece& p : rb_pend) memcpy(p.dst, static_cast<const char*>(h_rb) + p.off, p.bytes);
-      rb_pend.clear();
-      rb_off = 0;
-      HIPCHK(e);
-      if (bytes + 64 <= h_rb.capacity()) return EKF_OK;
-    }
-    HIPCHK(h_rb.reserve(bytes + 64, std::max<size_t>(1 << 16, 2 * (bytes + 64))));
-    rb_off = 0;
-    return EKF_OK;
-  }
+  ReadBack rb;
   // queue `bytes` from device `src` for host `dst` (copied out by rb_finish)
-  int rb_add(void* dst, const void* src, size_t bytes) {
-    int rc = rb_reserve(bytes);
-    if (rc) { rb_pend.clear(); rb_off = 0; return rc; }    // (a failed batch leaves nothing queued behind)
-    hipError_t e = hipMemcpyAsync(static_cast<char*>(h_rb) + rb_off, src, bytes, hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) { rb_pend.clear(); rb_off = 0; }
-    HIPCHK(e);
-    rb_pend.push_back({dst, rb_off, bytes});
-    rb_off += (bytes + 15) & ~size_t(15);
-    return EKF_OK;
-  }
+  int rb_add(void* dst, const void* src, size_t bytes) { HIPCHK(rb.add(dst, src, bytes, stream)); return EKF_OK; }
   // queue a rows x cols block (device pitch in bytes), packed row-major at dst
   int rb_add_2d(void* dst, const void* src, size_t pitch, size_t row_bytes, int rows) {
-    int rc = rb_reserve(row_bytes * rows);
-    if (rc) { rb_pend.clear(); rb_off = 0; return rc; }
-    hipError_t e = hipMemcpy2DAsync(static_cast<char*>(h_rb) + rb_off, row_bytes, src, pitch, row_bytes, rows,
-                                    hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) { rb_pend.clear(); rb_off = 0; }
-    HIPCHK(e);
-    rb_pend.push_back({dst, rb_off, row_bytes * rows});
-    rb_off += (row_bytes * rows + 15) & ~size_t(15);
+    HIPCHK(rb.add_2d(dst, src, pitch, row_bytes, rows, stream));
     return EKF_OK;
   }
   // one synchronisation for everything queued (+ the status words when asked for), then the pieces go to their places
   int rb_finish(bool with_status) {
     int st[4] = {0, 0, 0, 0};
-    if (with_status) { int rc = rb_add(st, d_status, sizeof(st)); if (rc) { rb_pend.clear(); rb_off = 0; return rc; } }
-    hipError_t e = hipStreamSynchronize(stream);
-    if (e == hipSuccess)
-      for (const RbPiece& p : rb_pend) memcpy(p.dst, static_cast<const char*>(h_rb) + p.off, p.bytes);
-    rb_pend.clear();
-    rb_off = 0;
-    HIPCHK(e);
+    if (with_status) { int rc = rb_add(st, d_status, sizeof(st)); if (rc) return rc; }
+    HIPCHK(rb.finish(stream));
     return with_status ? eval_status(st) : EKF_OK;
   }
   int eval_status(const int* st) {
@@ -758,7 +650,7 @@ struct Filter : FilterBase {
     switch (o) {
       case EKF_OPT_PROPAGATE_STREAMING: opt_streaming = v ? 1 : 0; return EKF_OK;
       case EKF_OPT_USE_MFMA: opt_mfma = v ? 1 : 0; w_zeroed_n = -1; return EKF_OK;   // tile size changes the pads
-      case EKF_OPT_PROFILE: resolve_profile(); opt_profile = v; return EKF_OK;
+      case EKF_OPT_PROFILE: resolve_profile(); prof.mode = v; return EKF_OK;
       case EKF_OPT_PIPELINE: opt_pipeline = (v < 0) ? -1 : v; return EKF_OK;
       case EKF_OPT_SPLIT_BF16: opt_split_bf16 = v ? 1 : 0; return EKF_OK;
       case EKF_OPT_FEATURE_NOISE: opt_feature_noise = (v > 0) ? 1e-12 * v : 0.0; return EKF_OK;
@@ -776,7 +668,7 @@ struct Filter : FilterBase {
   int state_dim() const override { return n; }
   int last_rows() const override { return last_m; }
   int get_layout(int* p, int* c) const override {
-    for (int i = 0; i < N; ++i) { if (p) p[i] = pos[i]; if (c) c[i] = coding[i]; }
+    for (int i = 0; i < N; ++i) { if (p) p[i] = ft.pos(i); if (c) c[i] = ft.coding(i); }
     return EKF_OK;
   }
   // (the caller may write through these pointers: the gathered diagonal blocks of a sharded filter are stale from here on)
@@ -805,15 +697,7 @@ struct Filter : FilterBase {
       k_capture_patch<<<1, 256, 0, stream>>>(d_frame, frame_w, frame_h, x0, y0, w,
                                             d_patch[cur_patch] + (size_t)N * w * w, d_mpatch[cur_patch] + (size_t)N * w * w);
     }
-    pos.push_back(n);
-    coding.push_back(0);
-    real_index.push_back(patchnumbre++);
-    n_find.push_back(1);
-    n_tot.push_back(1);                                   // Patch.cpp:85-93
-    center.push_back(float(u));
-    center.push_back(float(v));
-    in_innovation.push_back(0);
-    remove_flag.push_back(0);
+    ft.add(n, float(u), float(v));
     N += 1;
     n += 6;
     shard_after_add();
@@ -1035,13 +919,8 @@ struct Filter : FilterBase {
     if (found) memcpy(found, fd.data(), fd.size());
     // Patch::findMatch of every searched (= visible) feature: n_tot + 1 (Patch.cpp:218), the centre becomes the matched
     // pixel or (-1, -1) (:253, 279), a failed search clears isInInnovation (:281)
-    for (int i = 0; i < N; ++i) {
-      if (!in_innovation[i]) continue;
-      n_tot[i] += 1;
-      center[2 * i] = fd[i] ? float(zm[2 * i]) : -1.f;
-      center[2 * i + 1] = fd[i] ? float(zm[2 * i + 1]) : -1.f;
-      if (!fd[i]) in_innovation[i] = 0;
-    }
+    for (int i = 0; i < N; ++i)
+      if (ft.in_innovation(i)) ft.searched(i, fd[i] != 0, float(zm[2 * i]), float(zm[2 * i + 1]));
     return EKF_OK;
   }
 
@@ -1055,10 +934,7 @@ struct Filter : FilterBase {
     return EKF_OK;
   }
   void apply_track(const std::vector<unsigned char>& b) {
-    for (int i = 0; i < N; ++i) {
-      in_innovation[i] = b[i] & 1;
-      remove_flag[i] |= (b[i] >> 1) & 1;
-    }
+    ft.fold_track(b);
     trk_dirty = false;
   }
   int pull_track() {
@@ -1079,10 +955,10 @@ struct Filter : FilterBase {
     int rc = pull_track();
     if (rc) return rc;
     for (int i = 0; i < N; ++i) {
-      if (nt) nt[i] = n_tot[i];
-      if (inn) inn[i] = in_innovation[i];
-      if (cen) { cen[2 * i] = center[2 * i]; cen[2 * i + 1] = center[2 * i + 1]; }
-      if (rem) rem[i] = remove_flag[i];
+      if (nt) nt[i] = ft.n_tot(i);
+      if (inn) inn[i] = ft.in_innovation(i);
+      if (cen) { cen[2 * i] = ft.center(i)[0]; cen[2 * i + 1] = ft.center(i)[1]; }
+      if (rem) rem[i] = ft.remove_flag(i);
     }
     return EKF_OK;
   }
@@ -1091,10 +967,7 @@ struct Filter : FilterBase {
     if (index < 0 || index >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
     int rc = pull_track();
     if (rc) return rc;
-    if (nt >= 0) n_tot[index] = nt;
-    if (inn >= 0) in_innovation[index] = inn ? 1 : 0;
-    if (cen) { center[2 * index] = cen[0]; center[2 * index + 1] = cen[1]; }
-    if (rem >= 0) remove_flag[index] = rem ? 1 : 0;
+    ft.set_track(index, nt, inn, cen, rem);
     return EKF_OK;
   }
 
@@ -1117,7 +990,7 @@ struct Filter : FilterBase {
     // the squares of the existing patches (vR.cpp:795-817): float compares, (int) truncation of the origin
     std::vector<int> org;
     for (int i = 0; i < N; ++i) {
-      const float cx = center[2 * i], cy = center[2 * i + 1];
+      const float cx = ft.center(i)[0], cy = ft.center(i)[1];
       if (cx > (float)w && cy > (float)w && cx < (float)(W - w) && cy < (float)(H - w)) {
         org.push_back((int)(cx - (float)w));
         org.push_back((int)(cy - (float)w));
@@ -1202,9 +1075,9 @@ struct Filter : FilterBase {
     // update_quality_index (Patch.cpp:143-150; n_find was counted by ekf_update_two_stage) and removal in descending order
     std::vector<int> rm;
     for (int i = N - 1; i >= 0; --i) {
-      const float q = (float)(n_tot[i] - n_find[i]) / ((float)n_find[i]);
-      if (q > matching_ratio) remove_flag[i] = 1;
-      if (remove_flag[i]) rm.push_back(i);
+      const float q = (float)(ft.n_tot(i) - ft.n_find(i)) / ((float)ft.n_find(i));
+      if (q > matching_ratio) ft.flag_removal(i);
+      if (ft.remove_flag(i)) rm.push_back(i);
     }
     if (removed) for (size_t k = 0; k < rm.size(); ++k) removed[k] = rm[k];
     if (n_removed) *n_removed = (int)rm.size();
@@ -1213,7 +1086,7 @@ struct Filter : FilterBase {
       if (rc) return rc;
     }
     int vis = 0;                                                       // :1301-1302
-    for (int i = 0; i < N; ++i) vis += in_innovation[i] ? 1 : 0;
+    for (int i = 0; i < N; ++i) vis += ft.in_innovation(i) ? 1 : 0;
     if (n_visible) *n_visible = vis;
     if (vis < cfg.min_features) {                                      // :1311-1315
       if (N > cfg.max_features) {
@@ -1256,7 +1129,7 @@ struct Filter : FilterBase {
   int archive_removed(const std::vector<char>& rm) {
     std::vector<int> ap, ar;
     for (int i = 0; i < N; ++i)
-      if (rm[i] && coding[i] != 0 && n_find[i] > 5) { ap.push_back(pos[i]); ar.push_back(real_index[i]); }
+      if (rm[i] && ft.coding(i) != 0 && ft.n_find(i) > 5) { ap.push_back(ft.pos(i)); ar.push_back(ft.real_index(i)); }
     if (ap.empty()) return EKF_OK;
     // sharded: the 3 x 3 block of a removed feature is valid on its owner only -- gathered first, so that every rank
     // archives the same 12 scalars (the list above is the same on every rank: host metadata is replicated)
@@ -1284,30 +1157,8 @@ struct Filter : FilterBase {
   int compact(const std::vector<char>& rm, const std::vector<char>& cv) {
     { int rct = pull_track(); if (rct) return rct; }
     { int rca = archive_removed(rm); if (rca) return rca; }
-    std::vector<int> msrc, mconv, npos, ncoding, nreal, nfind, ntot;
-    std::vector<float> ncen;
-    std::vector<unsigned char> ninn, nrem;
-    msrc.reserve(n); mconv.reserve(n);
-    for (int i = 0; i < camera_dim; ++i) { msrc.push_back(i); mconv.push_back(-1); }
-    for (int i = 0; i < N; ++i) {
-      if (rm[i]) continue;
-      const int fs = coding[i] ? 3 : 6;
-      npos.push_back((int)msrc.size());
-      nreal.push_back(real_index[i]);
-      nfind.push_back(n_find[i]);
-      ntot.push_back(n_tot[i]);
-      ncen.push_back(center[2 * i]);
-      ncen.push_back(center[2 * i + 1]);
-      ninn.push_back(in_innovation[i]);
-      nrem.push_back(remove_flag[i]);
-      if (cv[i]) {
-        for (int e = 0; e < 3; ++e) { msrc.push_back(pos[i]); mconv.push_back(i * 3 + e); }
-        ncoding.push_back(1);
-      } else {
-        for (int e = 0; e < fs; ++e) { msrc.push_back(pos[i] + e); mconv.push_back(-1); }
-        ncoding.push_back(coding[i]);
-      }
-    }
+    FeatureTable::Compaction next = ft.compacted(rm, cv, camera_dim);
+    const std::vector<int>&msrc = next.msrc, &mconv = next.mconv;
     const int n_new = (int)msrc.size();
     HIPCHK(hipMemcpyAsync(d_map_src, msrc.data(), n_new * sizeof(int), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_map_conv, mconv.data(), n_new * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -1337,10 +1188,8 @@ struct Filter : FilterBase {
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(stream));        // host map vectors go out of scope
     cur = dst; cur_mu = dmu;
-    pos.swap(npos); coding.swap(ncoding);
-    real_index.swap(nreal); n_find.swap(nfind);
-    n_tot.swap(ntot); center.swap(ncen); in_innovation.swap(ninn); remove_flag.swap(nrem);
-    N = (int)pos.size();
+    ft.adopt(std::move(next.cols));
+    N = ft.size();
     n = n_new;
     shard_after_compact(rm);
     layout_dirty = true;
@@ -1373,7 +1222,7 @@ struct Filter : FilterBase {
     int cnt = 0;
     for (int i = 0; i < N; ++i) {
       if (!all && i != index) continue;
-      if (fl[i] && coding[i] == 0) { cv[i] = 1; ++cnt; }
+      if (fl[i] && ft.coding(i) == 0) { cv[i] = 1; ++cnt; }
     }
     if (cnt == 0) return 0;
     rc = compact(rm, cv);
@@ -1439,8 +1288,8 @@ struct Filter : FilterBase {
     HIPCHK(hipSetDevice(device));
     if (sh_on) return shard_predict(tc, rc_, vcontrol);
     const MotionArgs a = motion_args(tc, rc_, vcontrol);
-    if (opt_fused && !opt_streaming && !(opt_feature_noise > 0.0) && N > 0 && !prof_on(KID_PREDICT_CAMERA) &&
-        !prof_on(KID_PROPAGATE_STRIPS) && !prof_on(KID_MEASURE)) {
+    if (opt_fused && !opt_streaming && !(opt_feature_noise > 0.0) && N > 0 && !prof.on(KID_PREDICT_CAMERA) &&
+        !prof.on(KID_PROPAGATE_STRIPS) && !prof.on(KID_MEASURE)) {
       // camera step, strip congruence and the per-feature h / H as ONE launch (k_predict_fused): same arithmetic,
       // two launches less per frame
       int rc = sync_layout();
@@ -2063,7 +1912,7 @@ struct Filter : FilterBase {
   // EKF_OPT_SPLIT_BF16: Sigma -= V_g V_g^T for chunk [c0, c1) on the bf16 matrix pipe at fp32 accuracy (ekf_syrk6.hpp), over
   // the `ntiles` canonical tiles of `tiles` (none: the image only).  `split`: V_g is split into the plane image first (three
   // bf16 per fp32, one 12 KB record per 128 rows x 16 columns; else the solve's tiles have written it).  Rows of Sigma valid
-  // here: [0, cam_rows) and [r0, r1).  `mirror_rows`: Syrk6Args::mirror_rows (the plain step's launches before the last).  `work`: the flop the launch adds to prof_work.  `rider`: the innovation row update of
+  // here: [0, cam_rows) and [r0, r1).  `mirror_rows`: Syrk6Args::mirror_rows (the plain step's launches before the last).  `work`: the flop the launch adds to prof.work.  `rider`: the innovation row update of
   // the chunk in the same launch (launch_row_update's sums); `su_tail`: the state update too (the last downdate of an update).
   int launch_downdate_bf16x6(UpdateCtx& ux, int c0, int c1, int m_pad, hipStream_t ss, bool split, const int* tiles, int ntiles, int cam_rows,
                              int r0, int r1, double work, bool rider, bool su_tail, const int* mirror_rows = nullptr) {
@@ -2077,7 +1926,7 @@ struct Filter : FilterBase {
       }
       if (ntiles == 0) return EKF_OK;
       Scope sc(this, KID_DOWNDATE, ss);
-      if (sc.on) prof_work[KID_DOWNDATE] += work;
+      if (sc.on) prof.work[KID_DOWNDATE] += work;
       int* head = ux.take_queue();                        // (the callers have checked queue_room())
       Syrk6Args a{d_Vimg, ldy / 16, c0 / 16, width / 16, S(), ld, tiles, ntiles, head, cam_rows, r0, r1};
       a.stag_half = opt_syrk_stag_half; a.stag_mod4 = opt_syrk_stag_mod4;
@@ -2143,7 +1992,7 @@ struct Filter : FilterBase {
     last_m = p.m; last_m_pad = p.m_pad; last_n = n;
     have_update = true;
     have_meas = false;                                    // h/H belong to the pre-update state
-    ++frame_seq;
+    ++prof.frame_seq;
     return EKF_OK;
   }
 
@@ -2192,16 +2041,16 @@ struct Filter : FilterBase {
       // Linv of the diagonal factor, so the panel launch, the solve and the state update are ONE launch
       // (k_solve_state_oneblock; small maps: the downdate and the normalisation too, k_update_oneblock_small): the step is
       // launch-bound there.
-      p.oneblock = opt_fused && opt_mfma && p.nchunks == 1 && p.m_pad == 128 && p.nb == 128 && !prof_on(KID_SOLVE) &&
-                   !prof_on(KID_STATE_UPDATE) && !prof_on(KID_CHOL_PANEL);
+      p.oneblock = opt_fused && opt_mfma && p.nchunks == 1 && p.m_pad == 128 && p.nb == 128 && !prof.on(KID_SOLVE) &&
+                   !prof.on(KID_STATE_UPDATE) && !prof.on(KID_CHOL_PANEL);
       // small map: downdate and normalisation congruence in the same launch, one 64 x 64 tile of Sigma per workgroup
       p.small_nt64 = (p.npad_live / 64) * (p.npad_live / 64 + 1) / 2;
-      p.allinone = p.oneblock && p.small_nt64 <= num_cus && !prof_on(KID_DOWNDATE) && !prof_on(KID_NORMALIZE);
+      p.allinone = p.oneblock && p.small_nt64 <= num_cus && !prof.on(KID_DOWNDATE) && !prof.on(KID_NORMALIZE);
       // Small map (n_pad <= 256: the reference's 20-35 features): W, S, the factor, the solve, the state update, the downdate
       // and the normalisation as ONE launch (ekf_small.hpp) -- every workgroup forms W, S and the factor for itself
       p.onelaunch = p.oneblock && opt_small_onelaunch && p.npad_live <= kSmallMaxRows && p.small_nt64 <= num_cus && ld % 4 == 0 &&
-                    small_chunking(n, round_up(p.m, 4), &p.small_rc, &p.small_nchunk) && M <= 62 && !prof_on(KID_SIGMA_HT) &&
-                    !prof_on(KID_INNOVATION_COV) && !prof_on(KID_CHOL_DIAG) && !prof_on(KID_DOWNDATE) && !prof_on(KID_NORMALIZE);
+                    small_chunking(n, round_up(p.m, 4), &p.small_rc, &p.small_nchunk) && M <= 62 && !prof.on(KID_SIGMA_HT) &&
+                    !prof.on(KID_INNOVATION_COV) && !prof.on(KID_CHOL_DIAG) && !prof.on(KID_DOWNDATE) && !prof.on(KID_NORMALIZE);
       p.allinone = p.allinone || p.onelaunch;
     }
     return p;
@@ -2216,7 +2065,7 @@ struct Filter : FilterBase {
     }
     if constexpr (kIsF32) {                                // (the fused block step is the plain path's)
       if (!sh_on && opt_step_fused && opt_mfma && opt_fused && p.nb == 128 && p.nchunks == 1 && !p.oneblock &&
-          !prof_on(KID_CHOL_DIAG) && !prof_on(KID_CHOL_PANEL) && !prof_on(KID_CHOL_TRAILING)) {
+          !prof.on(KID_CHOL_DIAG) && !prof.on(KID_CHOL_PANEL) && !prof.on(KID_CHOL_TRAILING)) {
         int rc = ensure_step_fused_lists(p.nsteps);
         if (rc) return rc;
         ux.step_fused = true;
@@ -2396,7 +2245,7 @@ struct Filter : FilterBase {
         const int nr2 = p.recompute ? 1 : (npad_live + p.nb) / 128, n2 = nr2 * ((m_pad - c1) / 128);
         if (sc.on) {
           const double w = std::min(c1, m) - std::min(c0, m);
-          prof_work[KID_DOWNDATE] += double(n) * n * w + 2.0 * (p.recompute ? 1 : n + 1) * std::max(0, m - c1) * w;
+          prof.work[KID_DOWNDATE] += double(n) * n * w + 2.0 * (p.recompute ? 1 : n + 1) * std::max(0, m - c1) * w;
         }
         GemmArgs g{};
         g.A = d_V + c0; g.lda = ldy; g.B = d_V + c0; g.ldb = ldy; g.C = S(); g.ldc = ld;
@@ -2412,7 +2261,7 @@ struct Filter : FilterBase {
     }
     if (p.allinone) return EKF_OK;
     Scope sc(this, KID_DOWNDATE, ss);                 // Sigma -= V_g V_g^T (lower tiles + mirror)
-    if (sc.on) prof_work[KID_DOWNDATE] += double(n) * n * (std::min(c1, m) - std::min(c0, m));   // symmetric half, 2 flop per MAC
+    if (sc.on) prof.work[KID_DOWNDATE] += double(n) * n * (std::min(c1, m) - std::min(c0, m));   // symmetric half, 2 flop per MAC
     const bool mf = kIsF32 && opt_mfma;
     const bool t64 = mf && tri_count < num_cus;
     const bool half_tail = !t64 && mf && ss != stream_b && trih_count > tri_count && ux.queue_room();
@@ -2734,7 +2583,7 @@ struct Filter : FilterBase {
     HIPCHK(hipSetDevice(device));
     if (index < 0 || index >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
     { int rcs = shard_sync_diag_blocks(); if (rcs) return rcs; }      // sharded: the owner's block of the feature (collective)
-    k_feature_xyz<T><<<1, 64, 0, stream>>>(mu(), S(), ld, pos[index], coding[index], d_tmp);
+    k_feature_xyz<T><<<1, 64, 0, stream>>>(mu(), S(), ld, ft.pos(index), ft.coding(index), d_tmp);
     T o[12];
     { int rc = rb_add(o, d_tmp, sizeof(o)); if (rc) return rc; rc = rb_finish(false); if (rc) return rc; }
     T* x = static_cast<T*>(xyz);
@@ -2814,7 +2663,7 @@ struct Filter : FilterBase {
   // RosVSLAM::getPointsFeatures with its real_index row order and the archived patches (RosVSLAMRansac.cpp:340-418)
   int export_points_table(void* out, int max_rows, int* rows_out) override {
     HIPCHK(hipSetDevice(device));
-    const int rows = N ? real_index[N - 1] + 1 : 0;             // :350-352
+    const int rows = N ? ft.real_index(N - 1) + 1 : 0;            // :350-352
     if (rows_out) *rows_out = rows;
     if (!out || rows == 0) return EKF_OK;
     if (max_rows < rows) FAIL(EKF_ERR_ARG, "ekf_export_points_table: the buffer holds fewer rows than the table");
@@ -2830,7 +2679,7 @@ struct Filter : FilterBase {
     const T* scale_ptr = (camera_dim == 14) ? mu() + 13 : nullptr;      // the map scale is read on the device
     const size_t na = arch_real.size();
     HIPCHK(ensure_arch_idx((size_t)N + na));
-    HIPCHK(hipMemcpyAsync(d_arch_idx, real_index.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_arch_idx, ft.columns().real_index.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, stream));
     if (na) HIPCHK(hipMemcpyAsync(d_arch_idx + N, arch_real.data(), na * sizeof(int), hipMemcpyHostToDevice, stream));
     k_export_points<T><<<(N + 63) / 64, 64, 0, stream>>>(mu(), S(), ld, d_pos, d_coding, N, T(1), 0, d_tab, d_arch_idx, rows,
                                                         scale_ptr);
@@ -2850,13 +2699,12 @@ struct Filter : FilterBase {
     return rcs;
   }
   int feature_ids(int* ri, int* nf) const override {
-    for (int i = 0; i < N; ++i) { if (ri) ri[i] = real_index[i]; if (nf) nf[i] = n_find[i]; }
+    for (int i = 0; i < N; ++i) { if (ri) ri[i] = ft.real_index(i); if (nf) nf[i] = ft.n_find(i); }
     return EKF_OK;
   }
   int set_feature_meta(int index, int ri, int nf) override {
     if (index < 0 || index >= N) FAIL(EKF_ERR_ARG, "feature index out of range");
-    if (ri >= 0) real_index[index] = ri;
-    if (nf >= 0) n_find[index] = nf;
+    ft.set_meta(index, ri, nf);
     return EKF_OK;
   }
   int num_archived() const override { return (int)arch_real.size(); }
@@ -3029,7 +2877,7 @@ struct Filter : FilterBase {
       if (rc) return rc;
     }
     for (int k = 0; k < M; ++k)                                  // update_quality_index (vR.cpp:1297, Patch.cpp:145)
-      if (li[k] || hi[k]) n_find[idx[k]] += 1;
+      if (li[k] || hi[k]) ft.count_found(idx[k]);
     if (is_li) memcpy(is_li, li.data(), M);
     if (is_hi) memcpy(is_hi, hi.data(), M);
     if (hyp_drawn) *hyp_drawn = drawn;
@@ -3066,10 +2914,11 @@ struct Filter : FilterBase {
     rows.assign(3, 0);
     uv.clear();
     for (int i = 0; i < N; ++i) {
-      if (!(in_innovation[i] && coding[i] == 1)) continue;
-      const int r[3] = {real_index[i], (int)center[2 * i], (int)center[2 * i + 1]};
-      if (rows[0] == 0) { std::copy(r, r + 3, rows.begin()); uv.assign(&center[2 * i], &center[2 * i] + 2); }
-      else if (r[1] < 640 && r[2] < 480) { rows.insert(rows.end(), r, r + 3); uv.insert(uv.end(), &center[2 * i], &center[2 * i] + 2); }
+      if (!(ft.in_innovation(i) && ft.coding(i) == 1)) continue;
+      const float* c = ft.center(i);
+      const int r[3] = {ft.real_index(i), (int)c[0], (int)c[1]};
+      if (rows[0] == 0) { std::copy(r, r + 3, rows.begin()); uv.assign(c, c + 2); }
+      else if (r[1] < 640 && r[2] < 480) { rows.insert(rows.end(), r, r + 3); uv.insert(uv.end(), c, c + 2); }
     }
     if (rows[0] == 0) uv.clear();
   }
@@ -3151,7 +3000,7 @@ struct Filter : FilterBase {
 
   int own_f0() const { return sh_fb[sh_rank]; }
   int own_f1() const { return sh_fb[sh_rank + 1]; }
-  int row_of_feature(int f) const { return f < N ? pos[f] : n; }
+  int row_of_feature(int f) const { return f < N ? ft.pos(f) : n; }
 
   // boundaries that balance the ROWS (6 per inverse-depth, 3 per XYZ feature) of the current map
   void partition_by_rows() {
@@ -3161,7 +3010,7 @@ struct Filter : FilterBase {
     int f = 0;
     for (int g = 1; g < sh_world; ++g) {
       const long long target = rows * g / sh_world;
-      while (f < N && (long long)(pos[f] - camera_dim) < target) ++f;
+      while (f < N && (long long)(ft.pos(f) - camera_dim) < target) ++f;
       sh_fb[g] = f;
     }
   }
@@ -3913,11 +3762,11 @@ struct Filter : FilterBase {
       c.st = ss;
       if (q == 1 && p.sym_panel && ux.queue_room()) {
         // the own panel as ONE queued launch over the listed tiles: interior x interior lower tiles + mirror, the rest plain
-        if (sc.on) prof_work[KID_DOWNDATE] += 2.0 * 128 * 128 * panel_ntiles * double(std::min(c1, m) - std::min(c0, m));
+        if (sc.on) prof.work[KID_DOWNDATE] += 2.0 * 128 * 128 * panel_ntiles * double(std::min(c1, m) - std::min(c0, m));
         c.tri = TRI_LISTED; c.row_off = rr.r0;
         c.tile_list = panel_tiles.d; c.ntiles = panel_ntiles; c.counter = ux.take_queue();
       } else if (sc.on) {
-        prof_work[KID_DOWNDATE] += 2.0 * rr.count * double(n) * (std::min(c1, m) - std::min(c0, m));
+        prof.work[KID_DOWNDATE] += 2.0 * rr.count * double(n) * (std::min(c1, m) - std::min(c0, m));
       }
       gemm<ROLE_DOWNDATE, false>(c);
     }
@@ -4081,7 +3930,7 @@ struct Filter : FilterBase {
     int cnt = 0;
     for (int i = 0; i < N; ++i) {
       if (!all && i != index) continue;
-      if (fl[i] && coding[i] == 0) { cv[i] = 1; ++cnt; }
+      if (fl[i] && ft.coding(i) == 0) { cv[i] = 1; ++cnt; }
     }
     if (cnt == 0) return 0;
     rc = compact(rm, cv);
@@ -4093,8 +3942,7 @@ struct Filter : FilterBase {
     if (kid < 0 || kid >= KID_COUNT) FAIL(EKF_ERR_ARG, "kernel id out of range");
     hipSetDevice(device);
     resolve_profile();
-    if (ms) *ms = prof_ms[kid];
-    if (cnt) *cnt = prof_cnt[kid];
+    prof.read(kid, ms, cnt);
     return EKF_OK;
   }
   bool last_recompute = false;
@@ -4107,16 +3955,13 @@ struct Filter : FilterBase {
   }
   int profile_work(int kid, double* flop) override {
     if (kid < 0 || kid >= KID_COUNT) FAIL(EKF_ERR_ARG, "kernel id out of range");
-    if (flop) *flop = prof_work[kid];
+    if (flop) *flop = prof.work[kid];
     return EKF_OK;
   }
   int profile_reset() override {
     hipSetDevice(device);
     resolve_profile();
-    frame_seq = 0;
-    memset(prof_ms, 0, sizeof(prof_ms));
-    memset(prof_cnt, 0, sizeof(prof_cnt));
-    memset(prof_work, 0, sizeof(prof_work));
+    prof.reset();
     memset(launch_cnt, 0, sizeof(launch_cnt));
     return EKF_OK;
   }

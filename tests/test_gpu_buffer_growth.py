@@ -266,6 +266,31 @@ def test_trail_diag_lists_survive_a_small_update(pkg):
     g.close(); fresh.close()
 
 
+def test_readback_delivers_pending_pieces_at_the_edge(pkg):
+    """The pinned read-back buffer (ReadBack, csrc/ekf_buffers.hpp) starts at 64 KiB.  fp32, 81 features (n = 500): the block
+    Sigma[0:33, 0:496] is 33 * 496 * 4 = 65472 bytes and fills the buffer to its 64 bytes of slack, so the status words queued
+    behind it find no room and the block is delivered mid-batch; the full matrix (1 MB) then makes the buffer grow, and the
+    same block is read again out of the larger one.  Both block reads equal the slice of the full matrix, and a fresh filter
+    with the same inputs agrees on every read, bit for bit."""
+    px, z = _stream(pkg, 81, 1, F32)
+    idx = np.arange(81, dtype=np.int32)
+
+    def reads():
+        f = _ekf_filter(pkg, F32, px, 81)
+        f.predict()
+        f.update(z[0].reshape(-1), idx, plane_constraint=False)
+        assert f.stateDim() == 500
+        out = (f.getFullState(), f.getSigmaBlock(0, 0, 33, 496), f.getFullSigma(), f.getSigmaBlock(0, 0, 33, 496))
+        f.close()
+        return out
+
+    mu, edge, full, again = reads()
+    assert edge.shape == (33, 496) and edge.nbytes == 65472 and np.isfinite(full).all() and full.any()
+    assert same(edge, full[:33, :496]) and same(again, full[:33, :496])
+    for got, want in zip((mu, edge, full), reads()[:3]):
+        assert same(got, want)
+
+
 # ---- 4. bundle adjustment ---------------------------------------------------------------------------------------------------------
 def test_bundle_adjuster_grows_between_runs(pkg):
     """3 nodes / 20 points, a run, then 40 more points and their projections, a second run -- against an adjuster that is

@@ -255,6 +255,70 @@ def test_sticky_remove_flag_from_rho():
     g.close()
 
 
+def test_feature_records_follow_a_python_model():
+    """The host records of the features (FeatureTable, csrc/ekf_feature_table.hpp) through the C ABI against the plain Python
+    model the host check replays (tools/filter_host_check.py): additions, distinct meta and track values, a removal at both
+    ends and in the middle, additions behind it, two forced conversions and the removal of a converted feature.  Ids, track
+    state and layout are compared after every operation."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    from filter_host_check import FeatureModel
+    g = _filter(load_package().kinect_config(), capacity=16)
+    m = FeatureModel(g.camera_dim)
+    px = o.synthetic_pixels(o.Config.kinect(), 14)
+
+    def compare():
+        N = g.numOfFeatures()
+        assert N == len(m) and g.stateDim() == m.n
+        ri, nf = g.featureIds()
+        nt, inn, cen, rem = g.featureTrack()
+        pos, cod = g.featureLayout()
+        assert list(ri) == m.real_index and list(nf) == m.n_find and list(nt) == m.n_tot
+        assert list(inn) == [bool(x) for x in m.inn] and list(rem) == [bool(x) for x in m.rem]
+        assert np.array_equal(cen, np.asarray(m.center, np.float32).reshape(N, 2))
+        assert list(pos) == m.pos and list(cod) == m.coding
+
+    def add(k):
+        assert g.addFeature(px[k]) == 1
+        m.add(float(px[k][0]), float(px[k][1]))
+        compare()
+
+    compare()
+    for k in range(12):
+        add(k)
+    for i in range(12):
+        meta = dict(real_index=200 + 7 * i, n_find=3 + i)
+        track = dict(n_tot=20 + 2 * i, in_innovation=(i + 1) % 2, center=(10.5 + i, 99.25 - 3 * i), remove_flag=int(i % 4 == 1))
+        g.setFeatureMeta(i, **meta)
+        m.set_meta(i, **meta)
+        compare()
+        g.setFeatureTrack(i, **track)
+        m.set_track(i, **track)
+        compare()
+    g.removeFeatures([0, 5, 11])
+    m.compact(remove=[0, 5, 11])
+    compare()
+    add(12)
+    add(13)
+    assert m.real_index[-2:] == [13, 14]                               # the counter went on behind the removed features
+    pos, _ = g.featureLayout()
+    n = g.stateDim()
+    for fi in (1, 4):                                                  # a known depth: the feature passes the linearity test
+        r = int(pos[fi]) + 5
+        g.setSigmaBlock(np.zeros((1, n), np.float32), r, 0)
+        g.setSigmaBlock(np.zeros((n, 1), np.float32), 0, r)
+        g.setSigmaBlock(np.array([[1e-9]], np.float32), r, r)
+    assert g.convert2XYZ_ifLinearAll() == 2
+    m.compact(convert=[1, 4])
+    compare()
+    assert m.coding.count(1) == 2 and m.n == g.camera_dim + 6 * 9 + 3 * 2
+    g.removeFeatures([1])                                              # a converted feature goes
+    m.compact(remove=[1])
+    compare()
+    g.close()
+
+
 # ---------------------------------------------------------------------------------------------
 # the frame stream: set frame -> predict -> find matches -> two-stage update -> end of update
 # ---------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """The kernel bodies of the dense, fusion and ray-casting headers, the colour kernels among them, run lane by lane on the host
-under AddressSanitizer and UBSan (tools/host_kernels.hpp and tools/*_host_check.*).  CPU
-only."""
+under AddressSanitizer and UBSan (tools/host_kernels.hpp and tools/*_host_check.*), and
+so does the filter's host bookkeeping (tools/filter_host_check.*, DESIGN.md §2: the feature table against its Python model;
+read-back queue, input ring and launch profiler against stand-in HIP calls, with the runtime's API header for the types
+only and no HIP library).  CPU only."""
 import os
 import re
 import shutil
@@ -18,7 +20,10 @@ import raycast_scene as rs
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the cases the writer of each check is to produce, as its scene module names them
 CASES = {"colour": lambda: list(cs.HOST_CHECK_CASES), "dense": lambda: [c[0] for c in ds.CASES],
-         "fusion": lambda: list(fs.HOST_CHECK_CASES), "raycast": lambda: list(rs.cases())}
+         "fusion": lambda: list(fs.HOST_CHECK_CASES), "raycast": lambda: list(rs.cases()),
+         "filter": lambda: list(__import__("filter_host_check").SEQUENCES)}
+# (the filter check reads the runtime's API header for its types; the others include no HIP header and build as they did)
+HIP_TYPES = {"filter": ["-D__HIP_PLATFORM_AMD__", "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")]}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -32,7 +37,8 @@ def test_kernel_bodies_on_the_host_equal_the_oracle_under_sanitizers(name, tmp_p
     for cxx in ("/opt/rocm/llvm/bin/clang++", "clang++", "g++"):
         if os.path.exists(cxx) or shutil.which(cxx):
             b = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
-                                "-fno-sanitize-recover=undefined", "-pthread", os.path.join(ROOT, "tools", name + "_host_check.cpp"),
+                                "-fno-sanitize-recover=undefined", "-pthread"] + HIP_TYPES.get(name, []) +
+                               [os.path.join(ROOT, "tools", name + "_host_check.cpp"),
                                 "-o", exe], capture_output=True, text=True)
             err += b.stderr
             if b.returncode == 0:
