@@ -6,15 +6,24 @@
 // The image arithmetic of the reference is float / double regardless of the filter's scalar type:
 // the kernels that restate it switch FMA contraction off (the reference is built with -msse4: no FMA)
 // and spell the float / double operation order out.
+//
+// EKF_KERNELS_ONLY: the constants and the bodies of k_blur_templates and k_ncc_search (with k_capture_patch,
+// k_gather_patches and ingest_tables, which need nothing else) alone, for tools/image_host_check.cpp, which runs the two
+// kernels lane by lane on the host; tools/host_kernels.hpp supplies threadIdx, __syncthreads and the like, the check itself
+// the three device builtins the search uses.
 #pragma once
+#ifndef EKF_KERNELS_ONLY
 #include <hip/hip_runtime.h>
+#endif
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#ifndef EKF_KERNELS_ONLY
 #include "ekf_math.hpp"
 #include "ekf_pixel.hpp"
+#endif
 
 namespace ekf {
 
@@ -39,6 +48,7 @@ __global__ void k_capture_patch(const unsigned char* __restrict__ frame, int fw,
 constexpr int kIngestCopy = 0, kIngestArea2 = 1, kIngestLinear = 2;
 constexpr int kIngestSlack = 64;      // bytes behind the raw frame that the area path may load (and never uses)
 
+#ifndef EKF_KERNELS_ONLY
 struct IngestArgs {
   const unsigned char* raw;           // H rows of W * C bytes, tight
   unsigned char* gray;                // H' rows of W' bytes, tight
@@ -139,6 +149,7 @@ __global__ void __launch_bounds__(256) k_frame_ingest(IngestArgs a) {
     }
   }
 }
+#endif  // EKF_KERNELS_ONLY
 
 // xofs / alpha and yofs / beta of cv::resize's 8-bit INTER_LINEAR path (§13), on the host: fp32 / fp64 exactly as written,
 // nothing contracted.  tab: Wo column records, then Ho row records.
@@ -176,6 +187,7 @@ __global__ void k_gather_patches(const unsigned char* __restrict__ src, unsigned
   for (int t = threadIdx.x; t < w2; t += blockDim.x) d[t] = s[t];
 }
 
+#ifndef EKF_KERNELS_ONLY
 // Prediction of every feature at the blur pose r + v T_camera dT, q (x) quat(w T_camera dT) (vR.cpp:496-500, 546, 575).
 template <typename T>
 __global__ void k_blur_points(const T* __restrict__ mu, const int* __restrict__ pos, const int* __restrict__ coding,
@@ -210,6 +222,7 @@ __global__ void k_blur_points(const T* __restrict__ mu, const int* __restrict__ 
   hb[2 * i] = hd[0];
   hb[2 * i + 1] = hd[1];
 }
+#endif  // EKF_KERNELS_ONLY
 
 // cv::borderInterpolate(p, len, BORDER_REFLECT_101)
 __device__ __forceinline__ int reflect101(int p, int len) {
@@ -251,16 +264,18 @@ k_blur_templates(const T* __restrict__ h, const T* __restrict__ hb, const unsign
     int blur = nrm > (float)kernel_min_size;
     int cnt = 0, rows = 1, cols = 1;
     if (blur) {
-      cols = (int)((fabsf(dx)) + (1.f));                 // "height" = |dx| + 1 = kernel columns
-      rows = (int)((fabsf(dy)) + (1.f));                 // "width"  = |dy| + 1 = kernel rows
       const double theta = (double)atan2f(dy, dx);
       const double length = sqrt((double)dx * dx + (double)dy * dy);   // cv::norm(Point2f)
-      const double c = cos(theta), s = sin(theta);
-      const int x0 = (int)(s < 0 ? -s * length : 0.0);
-      const int y0 = (int)(c < 0 ? -c * length : 0.0);
       if (length >= (double)kMaxTaps) {
         blur = 0;                                            // not representable here: keep the sharp template
       } else {
+        // (only here: |dx|, |dy| <= length < kMaxTaps, so every float -> int conversion below is defined; a blur pose that
+        // projects billions of pixels away -- finite, and reachable: image_scene.py blur_fallback -- never converts)
+        cols = (int)((fabsf(dx)) + (1.f));               // "height" = |dx| + 1 = kernel columns
+        rows = (int)((fabsf(dy)) + (1.f));               // "width"  = |dy| + 1 = kernel rows
+        const double c = cos(theta), s = sin(theta);
+        const int x0 = (int)(s < 0 ? -s * length : 0.0);
+        const int y0 = (int)(c < 0 ? -c * length : 0.0);
         int prev = -1;
         for (int k = 0; (double)k < length; ++k) {
           int x = (int)(k * s + x0), y = (int)(k * c + y0);

@@ -1,5 +1,6 @@
-"""The kernel bodies of the dense, fusion and ray-casting headers, the colour kernels among them, run lane by lane on the host
-under AddressSanitizer and UBSan (tools/host_kernels.hpp and tools/*_host_check.*), and
+"""The kernel bodies of the dense, fusion and ray-casting headers, the colour kernels among them, and the patch matcher and
+template blur of the image header run lane by lane on the host under AddressSanitizer and UBSan (tools/host_kernels.hpp and
+tools/*_host_check.*), and
 so does the filter's host bookkeeping (tools/filter_host_check.*, DESIGN.md §2: the feature table against its Python model;
 read-back queue, input ring and launch profiler against stand-in HIP calls, with the runtime's API header for the types
 only and no HIP library).  CPU only."""
@@ -15,12 +16,13 @@ import pytest
 import colour_scene as cs
 import dense_scene as ds
 import fusion_scene as fs
+import image_scene as isc
 import raycast_scene as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the cases the writer of each check is to produce, as its scene module names them
 CASES = {"colour": lambda: list(cs.HOST_CHECK_CASES), "dense": lambda: [c[0] for c in ds.CASES],
-         "fusion": lambda: list(fs.HOST_CHECK_CASES), "raycast": lambda: list(rs.cases()),
+         "fusion": lambda: list(fs.HOST_CHECK_CASES), "image": lambda: list(isc.HOST_CHECK_CASES), "raycast": lambda: list(rs.cases()),
          "filter": lambda: list(__import__("filter_host_check").SEQUENCES)}
 # (the filter check reads the runtime's API header for its types; the others include no HIP header and build as they did)
 HIP_TYPES = {"filter": ["-D__HIP_PLATFORM_AMD__", "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")]}
