@@ -205,6 +205,10 @@ _PROTOS = {
     "ekf_dense_set_view_colour_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
     "ekf_dense_set_view_colour_from_keyframe": (C.c_int, [_P, C.c_int, _P, _P]),
     "ekf_dense_get_view_colour": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "ekf_dense_sweep_sgm": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int]),
+    "ekf_dense_get_volume": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "ekf_dense_get_sgm_profile": (C.c_int, [_P, _P, _P]),
     "ekf_colour_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "ekf_colour_has": (C.c_int, [_P]),
     "ekf_colour_integrate_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -32,6 +32,7 @@
 #include "ekf_rectify.hpp"
 #include "ekf_keyframe.hpp"
 #include "ekf_dense_stereo.hpp"
+#include "ekf_dense_sgm.hpp"
 #include "ekf_fusion.hpp"
 #include "ekf_raycast.hpp"
 
@@ -5222,7 +5223,10 @@ int ekf_keyframe_reset(ekf_keyframe* s) {
 
 
 // ---- dense plane-sweep depth maps ----------------------------------------------------------------------
-struct ekf_dense { ekf::DenseStereo* impl; };
+struct ekf_dense {
+  ekf::DenseStereo* impl;
+  ekf::DenseSgm sgm;                  // the cost volumes of the semi-global sweep
+};
 
 int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense** out) {
   if (!out) return EKF_ERR_ARG;
@@ -5240,14 +5244,17 @@ int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense
   d->H = height;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = d->timer.create();
+  auto* h = new ekf_dense{d, {}};
+  if (e == hipSuccess) e = h->sgm.timer.create();
   if (e != hipSuccess) {
     ekf::g_create_error = std::string("ekf_dense_create: ") + hipGetErrorString(e);
+    delete h;
     delete d;
     return EKF_ERR_DEVICE;
   }
   d->max_views = max_views;
   d->v.resize((size_t)max_views);
-  *out = new ekf_dense{d};
+  *out = h;
   return EKF_OK;
 }
 
@@ -5277,7 +5284,7 @@ static void dense_commit(ekf::DenseView& v, const double* K, const double t[3], 
   std::copy(q, q + 4, v.q);
   std::copy(t, t + 3, v.t);
   std::copy(R, R + 9, v.R);
-  v.swept = v.filtered = false;
+  v.swept = v.filtered = v.sgm = false;
 }
 
 // ---- setting a view, grey (C = 1) or colour (C = 3; DESIGN.md §18.1: the slot keeps the B, G, R image, its grey image is
@@ -5288,7 +5295,7 @@ static hipError_t dense_view_begin(ekf::DenseStereo* d, ekf::DenseView& v, int C
   if (e == hipSuccess) e = v.img.reserve(d->npix());
   if (e == hipSuccess && C == 3) e = v.bgr.reserve(3 * d->npix());
   if (e != hipSuccess) return e;
-  v.set = v.colour = false;
+  v.set = v.colour = v.sgm = false;
   *dst = C == 3 ? (unsigned char*)v.bgr : (unsigned char*)v.img;
   return hipSuccess;
 }
@@ -5461,13 +5468,19 @@ static bool dense_slots_ok(const ekf::DenseStereo* d, int ref, const int* src, i
   return true;
 }
 
+// the limits of §15.1, which the semi-global sweep shares
+static bool dense_sweep_ok(const ekf::DenseStereo* d, int ref, const int* src, int n_src, double w_min, double w_max, int planes,
+                           int radius, int trunc) {
+  return dense_slots_ok(d, ref, src, n_src) && planes >= 2 && planes <= ekf::kDenseMaxPlanes && radius >= 0 &&
+         radius <= ekf::kDenseMaxRadius && trunc >= 1 && trunc <= 255 && std::isfinite(w_min) && std::isfinite(w_max) &&
+         w_min > 0.0 && w_min < w_max;
+}
+
 int ekf_dense_sweep(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
                     int trunc) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
-  if (!dense_slots_ok(d, ref, src, n_src) || planes < 2 || planes > ekf::kDenseMaxPlanes || radius < 0 ||
-      radius > ekf::kDenseMaxRadius || trunc < 1 || trunc > 255 || !std::isfinite(w_min) || !std::isfinite(w_max) ||
-      !(w_min > 0.0) || !(w_min < w_max)) {
+  if (!dense_sweep_ok(d, ref, src, n_src, w_min, w_max, planes, radius, trunc)) {
     d->err = "ekf_dense_sweep: ref and 1..8 other, distinct source slots, all set; planes 2..1024, radius 0..4, trunc 1..255, "
              "0 < w_min < w_max finite";
     return EKF_ERR_ARG;
@@ -5548,12 +5561,57 @@ int ekf_dense_get_points(ekf_dense* h, int slot, int filtered, double* xyz) {
 int ekf_dense_profile(ekf_dense* h, int enable) {
   if (!h) return EKF_ERR_ARG;
   h->impl->timer.enable(enable != 0);
+  h->sgm.timer.enable(enable != 0);
   return EKF_OK;
 }
 
 int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->impl->timer.read(kernel_ms, launches, 0, 2);
+  return EKF_OK;
+}
+
+// ---- semi-global cost aggregation ---------------------------------------------------------------------------
+int ekf_dense_sweep_sgm(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                        int trunc, int p1, int p2, int paths) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (!dense_sweep_ok(d, ref, src, n_src, w_min, w_max, planes, radius, trunc) || p1 < 1 || p1 > p2 || p2 > ekf::kSgmMaxPenalty ||
+      (paths != 4 && paths != 8) || (long long)d->W * d->H * planes > ekf::kSgmMaxElems) {
+    d->err = "ekf_dense_sweep_sgm: the arguments of ekf_dense_sweep; 1 <= p1 <= p2 <= 2^20, paths 4 or 8, "
+             "width x height x planes <= 2^28";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths));
+  return EKF_OK;
+}
+
+int ekf_dense_get_volume(ekf_dense* h, int slot, int aggregated, unsigned int* out) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (slot < 0 || slot >= d->max_views || (aggregated != 0 && aggregated != 1) || !out) {
+    d->err = "ekf_dense_get_volume: slot in 0..max_views-1, aggregated is 0 or 1, out must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set || !v.swept || !v.sgm) {
+    d->err = "ekf_dense_get_volume: the volumes are not those of this slot (the handle's last ekf_dense_sweep_sgm, with no "
+             "setter or sweep of the slot since)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  std::vector<unsigned> vol(d->npix() * (size_t)h->sgm.D);       // the device keeps the planes of a pixel side by side
+  HIPCHK(hipMemcpy(vol.data(), aggregated ? h->sgm.S : h->sgm.C, vol.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  ekf::sgm_volume_to_planes(vol.data(), out, d->npix(), h->sgm.D);
+  return EKF_OK;
+}
+
+int ekf_dense_get_sgm_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->sgm.timer.read(kernel_ms, launches, 0, ekf::kSgmKinds);
   return EKF_OK;
 }
 

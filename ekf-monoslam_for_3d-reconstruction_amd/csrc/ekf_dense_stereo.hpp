@@ -61,7 +61,32 @@ struct SweepArgs {
 // number that a window sum per view would, with one pair of LDS passes per plane, not one per view.  Registers carry, per
 // owned pixel, C of the previous plane, the best C with its plane, its C- and C+ and its count of valid views: the cost
 // volume never leaves the CU.
-__global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) {
+//
+// VOLUME (the first stage of the semi-global sweep, §19; ekf_dense_sgm.hpp): the same per-plane cost, but C_k and V_k of the
+// owned pixels go to the volumes `vol` and no winner is kept or written.
+struct SweepVolume {
+  unsigned* C;                        // H x W x D, the planes of a pixel side by side: element (Y W + X) D + k
+  unsigned char* V;                   // D x H x W, plane-major: element k W H + Y W + X
+};
+
+// depth, plane, cost and views of pixel `o` from the winner ks, its cost c0, its neighbours' cm / cp and its valid views
+__device__ __forceinline__ void sweep_write_winner(const SweepArgs& a, size_t o, int ks, int cm, int c0, int cp, int nv) {
+#pragma clang fp contract(off)
+  double delta = 0.0;
+  if (ks > 0 && ks < a.D - 1) {
+    const int den = cm - 2 * c0 + cp;                                       // |.| <= 4 * 81 * 8 * 255 (4 * 2^24 aggregated)
+    if (den > 0) delta = (double)(cm - cp) / (2.0 * (double)den);
+  }
+  const double w = a.w_min + ((double)ks + delta) * a.step;
+  const bool none = nv == 0;
+  a.depth[o] = none ? 0.f : (float)(1.0 / w);
+  a.plane[o] = none ? -1 : ks;
+  a.cost[o] = (unsigned)c0;
+  a.views[o] = (unsigned char)nv;
+}
+
+template <bool VOLUME>
+__device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const SweepVolume& vol) {
 #pragma clang fp contract(off)
   __shared__ int s_c[kDenseHH][kDenseHW + 1];
   __shared__ int s_h[kDenseHH][kDenseTW + 1];
@@ -88,6 +113,14 @@ __global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) {
   const int tx = tid & 31, ty = tid >> 5;
   int* const sc = &s_c[0][0];
 
+  // VOLUME: where the two owned pixels go in a plane of the volume (-1: outside the image)
+  long own[2] = {-1, -1};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
+    if (VOLUME && X < W && Y < H) own[j] = (long)Y * W + X;
+  }
+  const size_t plane_elems = (size_t)W * H;
   int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
   for (int k = 0; k < a.D; ++k) {
     const double z = 1.0 / (a.w_min + (double)k * a.step);
@@ -145,6 +178,13 @@ __global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) {
       const int oy = ty + 8 * j;
       int C = 0;
       for (int d = 0; d <= 2 * r; ++d) C += s_h[oy + d][tx];
+      if constexpr (VOLUME) {
+        if (own[j] >= 0) {
+          vol.C[(size_t)own[j] * (size_t)a.D + (size_t)k] = (unsigned)C;
+          vol.V[(size_t)k * plane_elems + (size_t)own[j]] = (unsigned char)(j == 0 ? nv0 : nv1);
+        }
+        continue;
+      }
       // selects, not branches: the plane after the best one delivers its C+ (bestK = -2 before plane 0: never pending),
       // a strictly smaller C takes over (bestC starts at INT_MAX, so plane 0 always does)
       const bool pending = bestK[j] == k - 1, better = C < bestC[j];
@@ -156,25 +196,16 @@ __global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) {
       prevC[j] = C;
     }
   }
+  if constexpr (VOLUME) return;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
     if (X >= W || Y >= H) continue;
-    const int ks = bestK[j];
-    double delta = 0.0;
-    if (ks > 0 && ks < a.D - 1) {
-      const int den = bestM[j] - 2 * bestC[j] + bestP[j];                   // |.| <= 4 * 81 * 8 * 255
-      if (den > 0) delta = (double)(bestM[j] - bestP[j]) / (2.0 * (double)den);
-    }
-    const double w = a.w_min + ((double)ks + delta) * a.step;
-    const bool none = bestV[j] == 0;
-    const size_t o = (size_t)Y * W + X;
-    a.depth[o] = none ? 0.f : (float)(1.0 / w);
-    a.plane[o] = none ? -1 : ks;
-    a.cost[o] = (unsigned)bestC[j];
-    a.views[o] = (unsigned char)bestV[j];
+    sweep_write_winner(a, (size_t)Y * W + X, bestK[j], bestM[j], bestC[j], bestP[j], bestV[j]);
   }
 }
+
+__global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) { plane_sweep_body<false>(a, SweepVolume{nullptr, nullptr}); }
 
 struct FilterArgs {
   const float* depth;                 // the reference view's depth (swept, or filtered for the points of a filtered map)
@@ -290,6 +321,7 @@ struct DenseView {
   bool colour = false;                // `bgr` holds the slot's image in colour (§18): every grey setter drops it
   bool swept = false;                 // swept since the image or the pose last changed
   bool filtered = false;              // filtered since it was last swept
+  bool sgm = false;                   // the handle's cost volumes are those of this slot's maps (§19: DenseSgm)
 };
 
 // Host side of one handle (`ekf_dense`).  Everything runs on the default stream of the handle's device, as the rectified
@@ -343,7 +375,7 @@ struct DenseStereo {
     a.w_min = w_min;
     a.step = (w_max - w_min) / (double)(D - 1);
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
-    r.swept = r.filtered = false;
+    r.swept = r.filtered = r.sgm = false;
     const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
     if ((e = timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); })) != hipSuccess) return e;
     r.swept = true;

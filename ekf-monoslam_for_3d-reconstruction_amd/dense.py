@@ -109,6 +109,26 @@ class DenseStereo(capi.Handle):
         self._check(self._lib.ekf_dense_sweep(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes),
                                               int(radius), int(trunc)))
 
+    def sweep_sgm(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 1,
+                  trunc: int = 40, p1: Optional[int] = None, p2: Optional[int] = None, paths: int = 8):
+        """The sweep with semi-global cost aggregation: the slot's swept map, for ``filter``, ``depth``,
+        ``points`` and the fusion exactly as after ``sweep``.  With n = (2 radius + 1)^2 len(sources), ``None`` means
+        p1 = 2 n and p2 = 16 n: the values of the synthetic flat-patch scenes, not measured on real imagery."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        n = (2 * int(radius) + 1) ** 2 * len(src)
+        p1 = 2 * n if p1 is None else int(p1)
+        p2 = 16 * n if p2 is None else int(p2)
+        self._check(self._lib.ekf_dense_sweep_sgm(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes),
+                                                  int(radius), int(trunc), p1, p2, int(paths)))
+        self._sgm_planes = int(planes)
+
+    def volume(self, slot: int, aggregated: bool = True) -> np.ndarray:
+        """(planes, height, width) uint32: the aggregated or the raw cost volume of the last ``sweep_sgm``, whose slot
+        ``slot`` must be, with no setter or sweep of it since."""
+        out = np.zeros((getattr(self, "_sgm_planes", 1),) + self.shape, np.uint32)
+        self._check(self._lib.ekf_dense_get_volume(self._h, int(slot), 1 if aggregated else 0, _ptr(out)))
+        return out
+
     def filter(self, ref: int, sources: Sequence[int], rel_tol: float = 0.01, min_agree: int = 1):
         src = np.ascontiguousarray(sources, np.int32).reshape(-1)
         self._check(self._lib.ekf_dense_filter(self._h, int(ref), _ptr(src), len(src), float(rel_tol), int(min_agree)))
@@ -149,6 +169,15 @@ class DenseStereo(capi.Handle):
         ms, cnt = np.zeros(2, np.float64), np.zeros(2, np.int64)
         self._check(self._lib.ekf_dense_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {"k_plane_sweep": (float(ms[0]), int(cnt[0])), "k_depth_filter_points": (float(ms[1]), int(cnt[1]))}
+
+
+    def get_sgm_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the kernels of ``sweep_sgm`` since the last ``profile()``:
+        ``k_sweep_volume``, ``k_sgm_path[0]`` .. ``k_sgm_path[7]`` (one per direction) and ``k_sgm_winner``."""
+        ms, cnt = np.zeros(10, np.float64), np.zeros(10, np.int64)
+        self._check(self._lib.ekf_dense_get_sgm_profile(self._h, _ptr(ms), _ptr(cnt)))
+        names = ["k_sweep_volume"] + ["k_sgm_path[%d]" % i for i in range(8)] + ["k_sgm_winner"]
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(names)}
 
 
 def read_ply(path: str):
@@ -216,11 +245,14 @@ def neighbours_of(i: int, n: int, neighbours: int):
 
 def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, neighbours: int = 2, w_min: float = 0.05,
                               w_max: float = 2.0, planes: int = 64, radius: int = 2, trunc: int = 40, rel_tol: float = 0.01,
-                              min_agree: int = 1, device: int = 0):
+                              min_agree: int = 1, device: int = 0, sgm=None):
     """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
     order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
     The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
-    neighbourhoods away) and the recording may be of any length >= 2.  Colour key frames become colour views."""
+    neighbourhoods away) and the recording may be of any length >= 2.  Colour key frames become colour views.
+    ``sgm``: ``None`` sweeps with ``sweep``; ``True`` or a dict of ``p1`` / ``p2`` / ``paths`` with ``sweep_sgm`` (§19)."""
+    if sgm is not None and sgm is not True and not (isinstance(sgm, dict) and set(sgm) <= {"p1", "p2", "paths"}):
+        raise ValueError("sgm is None, True or a dict of p1 / p2 / paths")
     if not 1 <= int(neighbours) <= 3:
         raise ValueError("neighbours is 1 .. 3")
     K, ids, poses, images = read_recording(directory, nodes_out)
@@ -238,7 +270,11 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
                 ds.set_view(loaded % ring, images[loaded], K, poses[loaded])
                 loaded += 1
             while swept < min(n, i + neighbours + 1):
-                ds.sweep(swept % ring, [j % ring for j in neighbours_of(swept, n, neighbours)], w_min, w_max, planes, radius, trunc)
+                src = [j % ring for j in neighbours_of(swept, n, neighbours)]
+                if sgm is None:
+                    ds.sweep(swept % ring, src, w_min, w_max, planes, radius, trunc)
+                else:
+                    ds.sweep_sgm(swept % ring, src, w_min, w_max, planes, radius, trunc, **({} if sgm is True else sgm))
                 swept += 1
             src = neighbours_of(i, n, neighbours)
             ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)))

@@ -913,6 +913,33 @@ int ekf_colour_get_mesh(ekf_fusion* h, unsigned char* bgr, unsigned long long ma
 int ekf_colour_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 int ekf_colour_get_render(ekf_fusion* h, unsigned char* bgr);
 
+/* ---- semi-global cost aggregation for the dense sweep ------------------------------------------------
+ * An opt-in second sweep beside ekf_dense_sweep for images with textureless regions, where every plane costs the same and
+ * the pixel-wise winner is plane 0: the windowed cost volume C of §15.1 is written to device memory, path costs
+ *   L_r(p, d) = C_d(p) + min(L_r(p-r, d), L_r(p-r, d-1) + p1, L_r(p-r, d+1) + p1, m + p2) - m,  m = min_i L_r(p-r, i)
+ * (L_r = C where p - r lies outside the image) are summed over the directions r = (dx, dy) = (1,0) (-1,0) (0,1) (0,-1)
+ * (1,1) (-1,-1) (1,-1) (-1,1) -- paths = 4 takes the first four -- and the winner of the sum S is taken by the rules of
+ * ekf_dense_sweep (first plane of least S, the parabola on S, views = valid warps of the pixel at the winning plane).
+ * Integers throughout; tests/sgm_oracle.py restates it.  No other result, launch or prototype changes; ekf_abi_version()
+ * stays 6 (additions only).
+ *  - ekf_dense_sweep_sgm: writes the swept map of `ref` (depth, plane, cost = S of the winner, views) and marks the slot
+ *    swept and not filtered, exactly as ekf_dense_sweep does, so ekf_dense_filter, ekf_dense_get_depth / _get_points,
+ *    ekf_fusion_integrate and ekf_raycast_render_view consume it unchanged.  Launches: k_sweep_volume, one k_sgm_path per
+ *    direction, k_sgm_winner.  EKF_ERR_ARG before the device is touched: everything ekf_dense_sweep refuses, not
+ *    1 <= p1 <= p2 <= 2^20, paths other than 4 or 8, width x height x planes > 2^28.  The handle keeps one raw and one
+ *    aggregated volume (4 bytes an element each, and 1 byte an element of valid-view counts), grow-only; a failed
+ *    allocation is EKF_ERR_DEVICE and leaves the slot's earlier maps readable;
+ *  - ekf_dense_get_volume: planes x height x width values, plane-major, of the raw (aggregated = 0) or the aggregated
+ *    (1) volume.  EKF_ERR_STATE unless `slot` is the slot of the handle's last successful ekf_dense_sweep_sgm and no
+ *    setter or sweep of that slot came after it;
+ *  - ekf_dense_get_sgm_profile: HIP-event milliseconds and launch counts of 10 kinds since the last ekf_dense_profile:
+ *    k_sweep_volume ([0]), k_sgm_path of direction r0 .. r7 ([1] .. [8]) and k_sgm_winner ([9]).  ekf_dense_get_profile
+ *    keeps its two kinds: a semi-global sweep adds nothing to them. */
+int ekf_dense_sweep_sgm(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                        int trunc, int p1, int p2, int paths);
+int ekf_dense_get_volume(ekf_dense* h, int slot, int aggregated, unsigned int* out);
+int ekf_dense_get_sgm_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -505,6 +505,24 @@ class DenseStereoHip {
   void sweep(int ref, const std::vector<int>& src, double w_min, double w_max, int planes = 64, int radius = 2, int trunc = 40) {
     check(ekf_dense_sweep(d_, ref, src.data(), (int)src.size(), w_min, w_max, planes, radius, trunc));
   }
+  // the sweep with semi-global cost aggregation: the same swept map for filter / depth / points and the
+  // fusion.  p1, p2 <= 0: 2 n and 16 n with n = (2 radius + 1)^2 src.size(), the values of the synthetic flat-patch scenes
+  // (not measured on real imagery); paths is 4 or 8
+  void sweepSgm(int ref, const std::vector<int>& src, double w_min, double w_max, int planes = 64, int radius = 1, int trunc = 40,
+                int p1 = 0, int p2 = 0, int paths = 8) {
+    const int n = (2 * radius + 1) * (2 * radius + 1) * (int)src.size();
+    check(ekf_dense_sweep_sgm(d_, ref, src.data(), (int)src.size(), w_min, w_max, planes, radius, trunc, p1 > 0 ? p1 : 2 * n,
+                              p2 > 0 ? p2 : 16 * n, paths));
+    sgm_planes_ = planes;
+  }
+  // planes x height x width values of the last sweepSgm, whose slot `slot` must be: the aggregated or the raw cost volume
+  std::vector<unsigned int> volume(int slot, bool aggregated = true) {
+    std::vector<unsigned int> v((size_t)sgm_planes_ * pixels());
+    check(ekf_dense_get_volume(d_, slot, aggregated ? 1 : 0, v.data()));
+    return v;
+  }
+  // HIP-event milliseconds and launch counts of k_sweep_volume ([0]), k_sgm_path of direction 0 .. 7 ([1] .. [8]), k_sgm_winner ([9])
+  void getSgmProfile(double kernel_ms[10], long long launches[10]) { check(ekf_dense_get_sgm_profile(d_, kernel_ms, launches)); }
   void filter(int ref, const std::vector<int>& src, double rel_tol = 0.01, int min_agree = 1) {
     check(ekf_dense_filter(d_, ref, src.data(), (int)src.size(), rel_tol, min_agree));
   }
@@ -531,6 +549,7 @@ class DenseStereoHip {
   size_t pixels() const { return (size_t)w_ * (size_t)h_; }
   void check(int rc) { if (rc != EKF_OK) throw std::runtime_error(ekf_dense_last_error(d_)); }
   int w_, h_;
+  int sgm_planes_ = 0;
   ekf_dense* d_ = nullptr;
 };
 

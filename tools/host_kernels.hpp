@@ -1,4 +1,4 @@
-// What the host checks of the reconstruction kernels share (DESIGN.md sections 15.5, 16.5, 17.5): stand-ins for the HIP
+// What the host checks of the reconstruction kernels share (DESIGN.md sections 15.5, 16.5, 17.5, 19.5): stand-ins for the HIP
 // names a kernel body uses, a launch that runs the 256 lanes of a workgroup as host threads (a pthread barrier for
 // __syncthreads, `static` arrays for LDS, the workgroups one after another), the case-file reader's take, the bit-for-bit
 // differs and main.  Include it before the csrc headers, which then give their structs and kernel bodies alone, and define
@@ -30,6 +30,19 @@ static pthread_barrier_t g_barrier;
 using std::max;
 using std::min;
 #define EKF_KERNELS_ONLY
+
+// A kernel that reads another lane's register (csrc/ekf_dense_sgm.hpp: wave_read, the device's __shfl) gets exactly that
+// here: an exchange array and a barrier per wave of 64 lanes.  Every lane of the wave must make the call.
+static pthread_barrier_t g_wave_barrier[4];
+static int g_wave_xch[4][64];
+static inline int wave_read(int v, int src) {
+  const unsigned w = threadIdx.x >> 6;
+  g_wave_xch[w][threadIdx.x & 63] = v;
+  pthread_barrier_wait(&g_wave_barrier[w]);
+  const int got = g_wave_xch[w][src & 63];
+  pthread_barrier_wait(&g_wave_barrier[w]);
+  return got;
+}
 
 // body() once per lane of every workgroup of `grid`.  The barrier after a workgroup keeps its LDS from the next one's lanes.
 template <typename F>
@@ -67,6 +80,7 @@ static int run(const char* path);
 
 int main(int argc, char** argv) {
   pthread_barrier_init(&g_barrier, nullptr, 256);
+  for (auto& w : g_wave_barrier) pthread_barrier_init(&w, nullptr, 64);
   int rc = argc > 1 ? 0 : 64;
   for (int i = 1; i < argc; ++i) rc |= run(argv[i]);
   if (rc == 0) std::printf("ok\n");
