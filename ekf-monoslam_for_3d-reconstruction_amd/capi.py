@@ -209,6 +209,11 @@ _PROTOS = {
                                       C.c_int, C.c_int]),
     "ekf_dense_get_volume": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ekf_dense_get_sgm_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_dense_sweep_census": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "ekf_dense_sweep_sgm_census": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int]),
+    "ekf_dense_get_census": (C.c_int, [_P, C.c_int, _P]),
+    "ekf_dense_get_census_profile": (C.c_int, [_P, _P, _P]),
     "ekf_colour_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "ekf_colour_has": (C.c_int, [_P]),
     "ekf_colour_integrate_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -5244,6 +5244,7 @@ int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense
   d->H = height;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = d->timer.create();
+  if (e == hipSuccess) e = d->census_timer.create();
   auto* h = new ekf_dense{d, {}};
   if (e == hipSuccess) e = h->sgm.timer.create();
   if (e != hipSuccess) {
@@ -5295,7 +5296,7 @@ static hipError_t dense_view_begin(ekf::DenseStereo* d, ekf::DenseView& v, int C
   if (e == hipSuccess) e = v.img.reserve(d->npix());
   if (e == hipSuccess && C == 3) e = v.bgr.reserve(3 * d->npix());
   if (e != hipSuccess) return e;
-  v.set = v.colour = v.sgm = false;
+  v.set = v.colour = v.sgm = v.census_valid = false;
   *dst = C == 3 ? (unsigned char*)v.bgr : (unsigned char*)v.img;
   return hipSuccess;
 }
@@ -5476,19 +5477,25 @@ static bool dense_sweep_ok(const ekf::DenseStereo* d, int ref, const int* src, i
          w_min > 0.0 && w_min < w_max;
 }
 
-int ekf_dense_sweep(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
-                    int trunc) {
+// ekf_dense_sweep, and with the census cost ekf_dense_sweep_census: one set of checks and state rules
+static int dense_sweep(ekf_dense* h, const char* who, bool census, int ref, const int* src, int n_src, double w_min, double w_max,
+                       int planes, int radius, int trunc) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
   if (!dense_sweep_ok(d, ref, src, n_src, w_min, w_max, planes, radius, trunc)) {
-    d->err = "ekf_dense_sweep: ref and 1..8 other, distinct source slots, all set; planes 2..1024, radius 0..4, trunc 1..255, "
+    d->err = std::string(who) + ": ref and 1..8 other, distinct source slots, all set; planes 2..1024, radius 0..4, trunc 1..255, "
              "0 < w_min < w_max finite";
     return EKF_ERR_ARG;
   }
   std::string& err = d->err;
   HIPCHK(hipSetDevice(d->device));
-  HIPCHK(d->sweep(ref, src, n_src, w_min, w_max, planes, radius, trunc));
+  HIPCHK(d->sweep(ref, src, n_src, w_min, w_max, planes, radius, trunc, census));
   return EKF_OK;
+}
+
+int ekf_dense_sweep(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                    int trunc) {
+  return dense_sweep(h, "ekf_dense_sweep", false, ref, src, n_src, w_min, w_max, planes, radius, trunc);
 }
 
 int ekf_dense_filter(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree) {
@@ -5561,6 +5568,7 @@ int ekf_dense_get_points(ekf_dense* h, int slot, int filtered, double* xyz) {
 int ekf_dense_profile(ekf_dense* h, int enable) {
   if (!h) return EKF_ERR_ARG;
   h->impl->timer.enable(enable != 0);
+  h->impl->census_timer.enable(enable != 0);
   h->sgm.timer.enable(enable != 0);
   return EKF_OK;
 }
@@ -5572,20 +5580,26 @@ int ekf_dense_get_profile(const ekf_dense* h, double* kernel_ms, long long* laun
 }
 
 // ---- semi-global cost aggregation ---------------------------------------------------------------------------
-int ekf_dense_sweep_sgm(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
-                        int trunc, int p1, int p2, int paths) {
+// ekf_dense_sweep_sgm, and with the census cost (§20) ekf_dense_sweep_sgm_census
+static int dense_sweep_sgm(ekf_dense* h, const char* who, bool census, int ref, const int* src, int n_src, double w_min, double w_max,
+                           int planes, int radius, int trunc, int p1, int p2, int paths) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
   if (!dense_sweep_ok(d, ref, src, n_src, w_min, w_max, planes, radius, trunc) || p1 < 1 || p1 > p2 || p2 > ekf::kSgmMaxPenalty ||
       (paths != 4 && paths != 8) || (long long)d->W * d->H * planes > ekf::kSgmMaxElems) {
-    d->err = "ekf_dense_sweep_sgm: the arguments of ekf_dense_sweep; 1 <= p1 <= p2 <= 2^20, paths 4 or 8, "
+    d->err = std::string(who) + ": the arguments of ekf_dense_sweep; 1 <= p1 <= p2 <= 2^20, paths 4 or 8, "
              "width x height x planes <= 2^28";
     return EKF_ERR_ARG;
   }
   std::string& err = d->err;
   HIPCHK(hipSetDevice(d->device));
-  HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths));
+  HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths, census));
   return EKF_OK;
+}
+
+int ekf_dense_sweep_sgm(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                        int trunc, int p1, int p2, int paths) {
+  return dense_sweep_sgm(h, "ekf_dense_sweep_sgm", false, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths);
 }
 
 int ekf_dense_get_volume(ekf_dense* h, int slot, int aggregated, unsigned int* out) {
@@ -5612,6 +5626,42 @@ int ekf_dense_get_volume(ekf_dense* h, int slot, int aggregated, unsigned int* o
 int ekf_dense_get_sgm_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->sgm.timer.read(kernel_ms, launches, 0, ekf::kSgmKinds);
+  return EKF_OK;
+}
+
+// ---- census matching cost -----------------------------------------------------------------------------------
+int ekf_dense_sweep_census(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                           int trunc) {
+  return dense_sweep(h, "ekf_dense_sweep_census", true, ref, src, n_src, w_min, w_max, planes, radius, trunc);
+}
+
+int ekf_dense_sweep_sgm_census(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                               int trunc, int p1, int p2, int paths) {
+  return dense_sweep_sgm(h, "ekf_dense_sweep_sgm_census", true, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths);
+}
+
+int ekf_dense_get_census(ekf_dense* h, int slot, unsigned long long* out) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (slot < 0 || slot >= d->max_views || !out) {
+    d->err = "ekf_dense_get_census: slot in 0..max_views-1, out must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  if (!d->v[slot].set) {
+    d->err = "ekf_dense_get_census: the slot is not set";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(d->census_reserve(slot, nullptr, 0));
+  HIPCHK(d->census_update(slot));
+  HIPCHK(hipMemcpy(out, d->v[slot].census, d->npix() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_dense_get_census_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->impl->census_timer.read(kernel_ms, launches, 0, 3);
   return EKF_OK;
 }
 

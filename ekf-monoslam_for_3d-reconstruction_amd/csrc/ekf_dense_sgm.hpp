@@ -22,6 +22,7 @@ constexpr int kSgmKinds = 10;                    // timed kinds: the volume swee
 constexpr int kSgmDir[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, -1}, {1, -1}, {-1, 1}};
 
 __global__ void __launch_bounds__(256) k_sweep_volume(SweepArgs a, SweepVolume vol) { plane_sweep_body<true>(a, vol); }
+__global__ void __launch_bounds__(256) k_sweep_volume_census(SweepArgs a, SweepVolume vol) { plane_sweep_body<true, true>(a, vol); }
 
 // What a lane of k_sgm_path takes from other lanes of its wave (every lane of the wave makes each call):
 //   wave_read(v, src)  v of lane src (ds_bpermute; once a launch, for the longest line of the wave);
@@ -213,7 +214,7 @@ struct DenseSgm {
   KernelTimer<kSgmKinds> timer;
 
   hipError_t sweep(DenseStereo& d, int ref, const int* src, int n_src, double w_min, double w_max, int D_, int radius, int trunc,
-                   int p1, int p2, int paths) {
+                   int p1, int p2, int paths, bool census = false) {
 #pragma clang fp contract(off)
     DenseView& r = d.v[ref];
     hipError_t e;
@@ -225,8 +226,9 @@ struct DenseSgm {
       (void)hipGetLastError();                                              // the slot's maps are as they were
       return e;
     }
+    if (census && ((e = d.census_reserve(ref, src, n_src)) != hipSuccess || (e = d.census_update(ref, src, n_src)) != hipSuccess)) return e;
     SweepArgs a{};
-    a.ref = r.img; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
+    a.ref = r.img; a.ref_census = r.census; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
     a.W = d.W; a.H = d.H; a.D = D_; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
     a.fx = r.K[0]; a.fy = r.K[1]; a.cx = r.K[2]; a.cy = r.K[3];
     a.w_min = w_min;
@@ -235,7 +237,10 @@ struct DenseSgm {
     r.swept = r.filtered = false;
     const SweepVolume vol{C, V};
     const dim3 grid((unsigned)((d.W + kDenseTW - 1) / kDenseTW), (unsigned)((d.H + kDenseTH - 1) / kDenseTH));
-    if ((e = timer.run(0, [&] { k_sweep_volume<<<grid, 256, 0, nullptr>>>(a, vol); })) != hipSuccess) return e;
+    // the census volume (§20) counts under the census profile, its directions and winner below like any other
+    e = census ? d.census_timer.run(2, [&] { k_sweep_volume_census<<<grid, 256, 0, nullptr>>>(a, vol); })
+               : timer.run(0, [&] { k_sweep_volume<<<grid, 256, 0, nullptr>>>(a, vol); });
+    if (e != hipSuccess) return e;
     for (int i = 0; i < paths; ++i) {
       const SgmPathArgs p{C, S, d.W, d.H, D_, p1, p2, kSgmDir[i][0], kSgmDir[i][1]};
       const bool diag = p.dx != 0 && p.dy != 0;

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstddef>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // EKF_KERNELS_ONLY: the structs, the two kernel bodies and dense_pose alone, for tools/dense_host_check.cpp, which runs
@@ -35,6 +36,7 @@ constexpr int kDenseHaloPerLane = (kDenseHW * kDenseHH + 255) / 256;      // 4
 
 struct DenseSrc {
   const unsigned char* img;           // H rows of W bytes, tight
+  const unsigned long long* census;   // W H descriptors of img (the census sweeps only, §20)
   const float* depth;                 // the source's swept depth (the filter only)
   double fx, fy, cx, cy;
   double A[9];                        // R_v^T R_r, row-major
@@ -43,6 +45,7 @@ struct DenseSrc {
 
 struct SweepArgs {
   const unsigned char* ref;
+  const unsigned long long* ref_census;   // W H descriptors of ref (the census sweeps only, §20)
   float* depth;
   int* plane;
   unsigned* cost;
@@ -85,7 +88,62 @@ __device__ __forceinline__ void sweep_write_winner(const SweepArgs& a, size_t o,
   a.views[o] = (unsigned char)nv;
 }
 
-template <bool VOLUME>
+// ---- census descriptors ----------------------------------------------------------------------------------
+// T(X, Y) of an 8-bit image: bit b = 0 .. 61 for the offsets (dx, dy), dy = -3 .. 3 outer, dx = -4 .. 4 inner, (0, 0)
+// skipped, is 1 iff (X + dx, Y + dy) lies inside the image and I there < I(X, Y).  Bits 62 and 63 are 0.
+constexpr int kCensusRX = 4, kCensusRY = 3;
+constexpr int kCensusHW = kDenseTW + 2 * kCensusRX, kCensusHH = kDenseTH + 2 * kCensusRY;      // 40 x 22
+
+struct CensusArgs {
+  const unsigned char* img;           // H rows of W bytes, tight
+  unsigned long long* out;            // W H descriptors
+  int W, H;
+};
+
+// One workgroup per 32 x 16 tile.  The tile and its 4 x 3 halo go to LDS once, one byte a lane and turn (every image byte is
+// read from global memory once per tile); positions outside the image are filled with 255, where `neighbour < centre` is
+// never true, so the 62 comparisons need no flag.  A lane owns the pixels (tx, ty) and (tx, ty + 8), as in the sweep: a row
+// of the tile is one half-wave, its 32 byte reads of one offset fall into 8 or 9 consecutive LDS words (lanes that share a
+// word are served by one broadcast) and its stores of the descriptors are 256 contiguous bytes.
+__global__ void __launch_bounds__(256) k_census(CensusArgs a) {
+  __shared__ unsigned char s_t[kCensusHH][kCensusHW];
+  const int tid = threadIdx.x;
+  const int x0 = (int)blockIdx.x * kDenseTW - kCensusRX, y0 = (int)blockIdx.y * kDenseTH - kCensusRY;
+  for (int h = tid; h < kCensusHW * kCensusHH; h += 256) {
+    const int hy = h / kCensusHW, hx = h - hy * kCensusHW;
+    const int X = x0 + hx, Y = y0 + hy;
+    const bool in = X >= 0 && X < a.W && Y >= 0 && Y < a.H;
+    s_t[hy][hx] = in ? a.img[(size_t)Y * a.W + X] : (unsigned char)255;
+  }
+  __syncthreads();
+  const int tx = tid & 31, ty = tid >> 5;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int oy = ty + 8 * j;
+    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + oy;
+    if (X >= a.W || Y >= a.H) continue;
+    const unsigned c = s_t[oy + kCensusRY][tx + kCensusRX];
+    unsigned lo = 0, hi = 0;                                                // bits 0 .. 31 and 32 .. 61
+    int b = 0;
+#pragma unroll
+    for (int dy = 0; dy <= 2 * kCensusRY; ++dy)
+#pragma unroll
+      for (int dx = 0; dx <= 2 * kCensusRX; ++dx) {
+        if (dy == kCensusRY && dx == kCensusRX) continue;
+        const unsigned bit = (unsigned)s_t[oy + dy][tx + dx] < c ? 1u : 0u;
+        if (b < 32) lo |= bit << b;
+        else hi |= bit << (b - 32);
+        ++b;
+      }
+    a.out[(size_t)Y * a.W + X] = ((unsigned long long)hi << 32) | lo;
+  }
+}
+
+// CENSUS (§20; a second template parameter, so the fp64 warp is written once): the matching cost is the Hamming distance of
+// census descriptors, not the absolute grey difference.  A halo pixel's register value is then its 64-bit descriptor, and
+// per source the four byte gathers and the blend become one 8-byte load at the nearest pixel and a popcount.  The warp, the
+// window, the winner and the volume stores are the same lines.
+template <bool VOLUME, bool CENSUS = false>
 __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const SweepVolume& vol) {
 #pragma clang fp contract(off)
   __shared__ int s_c[kDenseHH][kDenseHW + 1];
@@ -97,7 +155,8 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
   const double qx_max = (double)(32 * (W - 1)), qy_max = (double)(32 * (H - 1));
 
   // the lane's halo pixels: position in the halo, ray and reference grey value, fixed for the launch
-  int h_off[kDenseHaloPerLane], h_ref[kDenseHaloPerLane];                 // h_off < 0: none, or outside the image
+  int h_off[kDenseHaloPerLane];                                           // h_off < 0: none, or outside the image
+  typename std::conditional<CENSUS, unsigned long long, int>::type h_ref[kDenseHaloPerLane];
   double h_x[kDenseHaloPerLane], h_y[kDenseHaloPerLane];
 #pragma unroll
   for (int i = 0; i < kDenseHaloPerLane; ++i) {
@@ -106,7 +165,10 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
     const int X = x0 + hx, Y = y0 + hy;
     const bool in = h < nh && X >= 0 && X < W && Y >= 0 && Y < H;
     h_off[i] = h < nh ? (in ? hy * (kDenseHW + 1) + hx : -1 - (hy * (kDenseHW + 1) + hx)) : INT_MIN;
-    h_ref[i] = in ? (int)a.ref[(size_t)Y * W + X] : 0;
+    if constexpr (CENSUS)
+      h_ref[i] = in ? a.ref_census[(size_t)Y * W + X] : 0ull;
+    else
+      h_ref[i] = in ? (int)a.ref[(size_t)Y * W + X] : 0;
     h_x[i] = ((double)X - a.cx) / a.fx;
     h_y[i] = ((double)Y - a.cy) / a.fy;
   }
@@ -147,13 +209,18 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
           const double fqx = floor(sx * 32.0 + 0.5), fqy = floor(sy * 32.0 + 0.5);
           if (fqx >= 0.0 && fqx <= qx_max && fqy >= 0.0 && fqy <= qy_max) {   // (a NaN fails)
             const int qx = (int)fqx, qy = (int)fqy;
-            const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;   // ix in [0, W - 1], iy in [0, H - 1]
-            const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);       // weight 0 where clamped (ax = 0 there)
-            const unsigned char* r0 = s.img + (size_t)iy * W;
-            const unsigned char* r1 = s.img + (size_t)iy1 * W;
-            const int g = ((32 - ax) * (32 - ay) * (int)r0[ix] + ax * (32 - ay) * (int)r0[ix1] + (32 - ax) * ay * (int)r1[ix] +
-                           ax * ay * (int)r1[ix1] + 512) >> 10;
-            c = min(abs(h_ref[i] - g), a.trunc);
+            if constexpr (CENSUS) {
+              const int jx = (qx + 16) >> 5, jy = (qy + 16) >> 5;               // the nearest pixel: jx <= W - 1, jy <= H - 1
+              c = min(__builtin_popcountll(h_ref[i] ^ s.census[(size_t)jy * W + jx]), a.trunc);
+            } else {
+              const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;   // ix in [0, W - 1], iy in [0, H - 1]
+              const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);       // weight 0 where clamped (ax = 0 there)
+              const unsigned char* r0 = s.img + (size_t)iy * W;
+              const unsigned char* r1 = s.img + (size_t)iy1 * W;
+              const int g = ((32 - ax) * (32 - ay) * (int)r0[ix] + ax * (32 - ay) * (int)r0[ix1] + (32 - ax) * ay * (int)r1[ix] +
+                             ax * ay * (int)r1[ix1] + 512) >> 10;
+              c = min(abs(h_ref[i] - g), a.trunc);
+            }
             ++nv;
           }
         }
@@ -206,6 +273,9 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
 }
 
 __global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) { plane_sweep_body<false>(a, SweepVolume{nullptr, nullptr}); }
+__global__ void __launch_bounds__(256) k_plane_sweep_census(SweepArgs a) {
+  plane_sweep_body<false, true>(a, SweepVolume{nullptr, nullptr});
+}
 
 struct FilterArgs {
   const float* depth;                 // the reference view's depth (swept, or filtered for the points of a filtered map)
@@ -316,12 +386,14 @@ struct DenseView {
   DevBuf<int> plane, fplane;
   DevBuf<unsigned> cost;
   DevBuf<unsigned char> nviews;
+  DevBuf<unsigned long long> census;  // W x H descriptors of `img` (§20), allocated by the slot's first census sweep or getter
   double K[4] = {}, t[3] = {}, R[9] = {}, q[4] = {};
   bool set = false;                   // an image, K and a pose
   bool colour = false;                // `bgr` holds the slot's image in colour (§18): every grey setter drops it
   bool swept = false;                 // swept since the image or the pose last changed
   bool filtered = false;              // filtered since it was last swept
   bool sgm = false;                   // the handle's cost volumes are those of this slot's maps (§19: DenseSgm)
+  bool census_valid = false;          // `census` is that of `img`: every setter of the image clears it, a new pose does not
 };
 
 // Host side of one handle (`ekf_dense`).  Everything runs on the default stream of the handle's device, as the rectified
@@ -332,6 +404,7 @@ struct DenseStereo {
   std::vector<DenseView> v;
   DevBuf<double> d_xyz;               // the points on their way to the host (allocated by the first ekf_dense_get_points)
   KernelTimer<2> timer;               // k_plane_sweep, k_depth_filter_points
+  KernelTimer<3> census_timer;        // k_census, k_plane_sweep_census, k_sweep_volume_census (§20)
 
   size_t npix() const { return (size_t)W * H; }
   const unsigned char* colour_of(int slot) const { return v[slot].colour ? (const unsigned char*)v[slot].bgr : nullptr; }
@@ -357,10 +430,37 @@ struct DenseStereo {
     }
     o.fx = s.K[0]; o.fy = s.K[1]; o.cx = s.K[2]; o.cy = s.K[3];
     o.img = s.img;
+    o.census = s.census;
     o.depth = s.depth;
   }
 
-  hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc) {
+  // The descriptor buffers of a census sweep (§20), before anything is marked stale: a failed allocation leaves every map.
+  hipError_t census_reserve(int ref, const int* src, int n_src) {
+    hipError_t e = v[ref].census.reserve(npix());
+    for (int i = 0; i < n_src && e == hipSuccess; ++i) e = v[src[i]].census.reserve(npix());
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+  }
+
+  // The slot's descriptors, if they are not those of its image: one launch of k_census (the buffer exists).
+  hipError_t census_update(int slot) {
+    DenseView& vw = v[slot];
+    if (vw.census_valid) return hipSuccess;
+    const CensusArgs a{vw.img, vw.census, W, H};
+    const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
+    const hipError_t e = census_timer.run(0, [&] { k_census<<<grid, 256, 0, nullptr>>>(a); });
+    vw.census_valid = e == hipSuccess;
+    return e;
+  }
+
+  // ... of the reference and then of every source, in their order
+  hipError_t census_update(int ref, const int* src, int n_src) {
+    hipError_t e = census_update(ref);
+    for (int i = 0; i < n_src && e == hipSuccess; ++i) e = census_update(src[i]);
+    return e;
+  }
+
+  hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc, bool census = false) {
 #pragma clang fp contract(off)
     DenseView& r = v[ref];
     hipError_t e;
@@ -368,8 +468,9 @@ struct DenseStereo {
     if ((e = r.depth.reserve(n)) != hipSuccess || (e = r.plane.reserve(n)) != hipSuccess ||
         (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess)
       return e;
+    if (census && ((e = census_reserve(ref, src, n_src)) != hipSuccess || (e = census_update(ref, src, n_src)) != hipSuccess)) return e;
     SweepArgs a{};
-    a.ref = r.img; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
+    a.ref = r.img; a.ref_census = r.census; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
     a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
     a.fx = r.K[0]; a.fy = r.K[1]; a.cx = r.K[2]; a.cy = r.K[3];
     a.w_min = w_min;
@@ -377,7 +478,9 @@ struct DenseStereo {
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
     r.swept = r.filtered = r.sgm = false;
     const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
-    if ((e = timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); })) != hipSuccess) return e;
+    e = census ? census_timer.run(1, [&] { k_plane_sweep_census<<<grid, 256, 0, nullptr>>>(a); })
+               : timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); });
+    if (e != hipSuccess) return e;
     r.swept = true;
     return hipSuccess;
   }

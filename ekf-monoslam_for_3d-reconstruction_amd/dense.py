@@ -104,22 +104,26 @@ class DenseStereo(capi.Handle):
 
     # ---- the two launches ----
     def sweep(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 2,
-              trunc: int = 40):
+              trunc: int = 40, cost: str = "ad"):
+        """``cost``: ``"ad"``, the truncated absolute grey difference, or ``"census"``, the truncated
+        Hamming distance of 9 x 7 census descriptors (§20), for key frames whose exposure or gain differ."""
+        fn = _cost_entry(self._lib, cost, "ekf_dense_sweep")
         src = np.ascontiguousarray(sources, np.int32).reshape(-1)
-        self._check(self._lib.ekf_dense_sweep(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes),
-                                              int(radius), int(trunc)))
+        self._check(fn(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes), int(radius), int(trunc)))
 
     def sweep_sgm(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 1,
-                  trunc: int = 40, p1: Optional[int] = None, p2: Optional[int] = None, paths: int = 8):
+                  trunc: int = 40, p1: Optional[int] = None, p2: Optional[int] = None, paths: int = 8, cost: str = "ad"):
         """The sweep with semi-global cost aggregation: the slot's swept map, for ``filter``, ``depth``,
         ``points`` and the fusion exactly as after ``sweep``.  With n = (2 radius + 1)^2 len(sources), ``None`` means
-        p1 = 2 n and p2 = 16 n: the values of the synthetic flat-patch scenes, not measured on real imagery."""
+        p1 = 2 n and p2 = 16 n: the values of the synthetic flat-patch scenes, not measured on real imagery -- with
+        ``cost="census"`` (§20) as with ``"ad"``."""
+        fn = _cost_entry(self._lib, cost, "ekf_dense_sweep_sgm")
         src = np.ascontiguousarray(sources, np.int32).reshape(-1)
         n = (2 * int(radius) + 1) ** 2 * len(src)
         p1 = 2 * n if p1 is None else int(p1)
         p2 = 16 * n if p2 is None else int(p2)
-        self._check(self._lib.ekf_dense_sweep_sgm(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes),
-                                                  int(radius), int(trunc), p1, p2, int(paths)))
+        self._check(fn(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes), int(radius), int(trunc),
+                       p1, p2, int(paths)))
         self._sgm_planes = int(planes)
 
     def volume(self, slot: int, aggregated: bool = True) -> np.ndarray:
@@ -127,6 +131,12 @@ class DenseStereo(capi.Handle):
         ``slot`` must be, with no setter or sweep of it since."""
         out = np.zeros((getattr(self, "_sgm_planes", 1),) + self.shape, np.uint32)
         self._check(self._lib.ekf_dense_get_volume(self._h, int(slot), 1 if aggregated else 0, _ptr(out)))
+        return out
+
+    def census(self, slot: int) -> np.ndarray:
+        """(height, width) uint64: the census descriptors of a set slot's image (bits 0 .. 61)."""
+        out = np.zeros(self.shape, np.uint64)
+        self._check(self._lib.ekf_dense_get_census(self._h, int(slot), _ptr(out)))
         return out
 
     def filter(self, ref: int, sources: Sequence[int], rel_tol: float = 0.01, min_agree: int = 1):
@@ -178,6 +188,19 @@ class DenseStereo(capi.Handle):
         self._check(self._lib.ekf_dense_get_sgm_profile(self._h, _ptr(ms), _ptr(cnt)))
         names = ["k_sweep_volume"] + ["k_sgm_path[%d]" % i for i in range(8)] + ["k_sgm_winner"]
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(names)}
+
+    def get_census_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the kernels of the census cost (§20) since the last ``profile()``."""
+        ms, cnt = np.zeros(3, np.float64), np.zeros(3, np.int64)
+        self._check(self._lib.ekf_dense_get_census_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(("k_census", "k_plane_sweep_census", "k_sweep_volume_census"))}
+
+
+def _cost_entry(lib, cost, name):
+    """The C function of a sweep for the matching cost ``cost``."""
+    if cost not in ("ad", "census"):
+        raise ValueError('cost is "ad" or "census"')
+    return getattr(lib, name if cost == "ad" else name + "_census")
 
 
 def read_ply(path: str):
@@ -245,12 +268,15 @@ def neighbours_of(i: int, n: int, neighbours: int):
 
 def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, neighbours: int = 2, w_min: float = 0.05,
                               w_max: float = 2.0, planes: int = 64, radius: int = 2, trunc: int = 40, rel_tol: float = 0.01,
-                              min_agree: int = 1, device: int = 0, sgm=None):
+                              min_agree: int = 1, device: int = 0, sgm=None, cost: str = "ad"):
     """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
     order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
     The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
     neighbourhoods away) and the recording may be of any length >= 2.  Colour key frames become colour views.
-    ``sgm``: ``None`` sweeps with ``sweep``; ``True`` or a dict of ``p1`` / ``p2`` / ``paths`` with ``sweep_sgm`` (§19)."""
+    ``sgm``: ``None`` sweeps with ``sweep``; ``True`` or a dict of ``p1`` / ``p2`` / ``paths`` with ``sweep_sgm`` (§19).
+    ``cost``: ``"ad"`` or ``"census"`` (§20), the matching cost of either sweep."""
+    if cost not in ("ad", "census"):
+        raise ValueError('cost is "ad" or "census"')
     if sgm is not None and sgm is not True and not (isinstance(sgm, dict) and set(sgm) <= {"p1", "p2", "paths"}):
         raise ValueError("sgm is None, True or a dict of p1 / p2 / paths")
     if not 1 <= int(neighbours) <= 3:
@@ -272,9 +298,9 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
             while swept < min(n, i + neighbours + 1):
                 src = [j % ring for j in neighbours_of(swept, n, neighbours)]
                 if sgm is None:
-                    ds.sweep(swept % ring, src, w_min, w_max, planes, radius, trunc)
+                    ds.sweep(swept % ring, src, w_min, w_max, planes, radius, trunc, cost=cost)
                 else:
-                    ds.sweep_sgm(swept % ring, src, w_min, w_max, planes, radius, trunc, **({} if sgm is True else sgm))
+                    ds.sweep_sgm(swept % ring, src, w_min, w_max, planes, radius, trunc, cost=cost, **({} if sgm is True else sgm))
                 swept += 1
             src = neighbours_of(i, n, neighbours)
             ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)))

@@ -940,6 +940,37 @@ int ekf_dense_sweep_sgm(ekf_dense* h, int ref, const int* src, int n_src, double
 int ekf_dense_get_volume(ekf_dense* h, int slot, int aggregated, unsigned int* out);
 int ekf_dense_get_sgm_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
+/* ---- census matching cost for the dense sweeps --------------------------------------------------------
+ * An opt-in matching cost for key frames whose exposure or gain differ, where the absolute grey difference of §15.1 fails:
+ * the Hamming distance of census descriptors.  The descriptor T(X, Y) of an 8-bit image is a 64-bit word: for the offsets
+ * (dx, dy) with dy = -3 .. 3 outer and dx = -4 .. 4 inner, (0, 0) skipped, bit b = 0 .. 61 in that order is 1 iff
+ * (X + dx, Y + dy) lies inside the image and I(X + dx, Y + dy) < I(X, Y); bits 62 and 63 are 0.  The warp, its validity
+ * test and (qx, qy) are those of ekf_dense_sweep; the source's descriptor is read at the nearest pixel jx = (qx + 16) >> 5,
+ * jy = (qy + 16) >> 5, and c = min(popcount(T_r(X, Y) xor T_v(jx, jy)), trunc), an invalid warp costing trunc.  Everything
+ * after c -- the sum over the views, the window, the valid-view count, the winner, its refinement, views = 0, the limits,
+ * and for the semi-global sweep the path costs -- is that of ekf_dense_sweep / ekf_dense_sweep_sgm.  Integers throughout;
+ * tests/census_oracle.py restates it.  The default cost stays the absolute difference: no other result, launch, profile
+ * count or prototype changes; ekf_abi_version() stays 6 (additions only).
+ *  - ekf_dense_sweep_census: ekf_dense_sweep with the census cost: the same arguments, argument checks, state rules and
+ *    maps.  Each slot keeps a descriptor buffer (8 bytes a pixel, allocated on first use) that every setter of the slot's
+ *    image invalidates and ekf_dense_set_pose does not; the call first launches k_census for the reference and for every
+ *    source whose descriptors are stale, then k_plane_sweep_census.  A failed allocation is EKF_ERR_DEVICE and leaves the
+ *    slot's earlier maps readable;
+ *  - ekf_dense_sweep_sgm_census: ekf_dense_sweep_sgm with the census cost (k_sweep_volume_census, then the unchanged
+ *    k_sgm_path and k_sgm_winner); ekf_dense_get_volume works after it;
+ *  - ekf_dense_get_census: the width x height descriptors of a set slot, computed first if they are stale.  EKF_ERR_STATE
+ *    for a slot that is not set;
+ *  - ekf_dense_get_census_profile: HIP-event milliseconds and launch counts of 3 kinds since the last ekf_dense_profile:
+ *    k_census ([0]), k_plane_sweep_census ([1]) and k_sweep_volume_census ([2]).  ekf_dense_get_profile keeps its two kinds
+ *    and ekf_dense_get_sgm_profile its ten: a census sweep adds nothing to the former, and a semi-global census sweep counts
+ *    its directions and its winner under the latter ([1] .. [9]) and nothing under k_sweep_volume ([0]). */
+int ekf_dense_sweep_census(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes, int radius,
+                           int trunc);
+int ekf_dense_sweep_sgm_census(ekf_dense* h, int ref, const int* src, int n_src, double w_min, double w_max, int planes,
+                               int radius, int trunc, int p1, int p2, int paths);
+int ekf_dense_get_census(ekf_dense* h, int slot, unsigned long long* out);
+int ekf_dense_get_census_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

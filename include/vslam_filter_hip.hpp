@@ -523,6 +523,27 @@ class DenseStereoHip {
   }
   // HIP-event milliseconds and launch counts of k_sweep_volume ([0]), k_sgm_path of direction 0 .. 7 ([1] .. [8]), k_sgm_winner ([9])
   void getSgmProfile(double kernel_ms[10], long long launches[10]) { check(ekf_dense_get_sgm_profile(d_, kernel_ms, launches)); }
+  // the two sweeps with the census matching cost, for key frames whose exposure or gain differ: the
+  // same maps for filter / depth / points and the fusion; here trunc bounds a Hamming distance of 62 bits
+  void sweepCensus(int ref, const std::vector<int>& src, double w_min, double w_max, int planes = 64, int radius = 2, int trunc = 40) {
+    check(ekf_dense_sweep_census(d_, ref, src.data(), (int)src.size(), w_min, w_max, planes, radius, trunc));
+  }
+  // p1, p2 <= 0: the 2 n and 16 n of sweepSgm, not measured on real imagery
+  void sweepSgmCensus(int ref, const std::vector<int>& src, double w_min, double w_max, int planes = 64, int radius = 1, int trunc = 40,
+                      int p1 = 0, int p2 = 0, int paths = 8) {
+    const int n = (2 * radius + 1) * (2 * radius + 1) * (int)src.size();
+    check(ekf_dense_sweep_sgm_census(d_, ref, src.data(), (int)src.size(), w_min, w_max, planes, radius, trunc, p1 > 0 ? p1 : 2 * n,
+                                     p2 > 0 ? p2 : 16 * n, paths));
+    sgm_planes_ = planes;
+  }
+  // height x width census descriptors of a set slot (bits 0 .. 61), computed first if its image changed since
+  std::vector<unsigned long long> census(int slot) {
+    std::vector<unsigned long long> t(pixels());
+    check(ekf_dense_get_census(d_, slot, t.data()));
+    return t;
+  }
+  // HIP-event milliseconds and launch counts of k_census ([0]), k_plane_sweep_census ([1]), k_sweep_volume_census ([2])
+  void getCensusProfile(double kernel_ms[3], long long launches[3]) { check(ekf_dense_get_census_profile(d_, kernel_ms, launches)); }
   void filter(int ref, const std::vector<int>& src, double rel_tol = 0.01, int min_agree = 1) {
     check(ekf_dense_filter(d_, ref, src.data(), (int)src.size(), rel_tol, min_agree));
   }
