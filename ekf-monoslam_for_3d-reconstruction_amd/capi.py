@@ -214,6 +214,9 @@ _PROTOS = {
                                              C.c_int, C.c_int]),
     "ekf_dense_get_census": (C.c_int, [_P, C.c_int, _P]),
     "ekf_dense_get_census_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_dense_sweep_best": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int]),
+    "ekf_dense_get_best_profile": (C.c_int, [_P, _P, _P]),
     "ekf_colour_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "ekf_colour_has": (C.c_int, [_P]),
     "ekf_colour_integrate_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

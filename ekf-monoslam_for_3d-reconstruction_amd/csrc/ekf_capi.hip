@@ -5245,6 +5245,7 @@ int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = d->timer.create();
   if (e == hipSuccess) e = d->census_timer.create();
+  if (e == hipSuccess) e = d->best_timer.create();
   auto* h = new ekf_dense{d, {}};
   if (e == hipSuccess) e = h->sgm.timer.create();
   if (e != hipSuccess) {
@@ -5569,6 +5570,7 @@ int ekf_dense_profile(ekf_dense* h, int enable) {
   if (!h) return EKF_ERR_ARG;
   h->impl->timer.enable(enable != 0);
   h->impl->census_timer.enable(enable != 0);
+  h->impl->best_timer.enable(enable != 0);
   h->sgm.timer.enable(enable != 0);
   return EKF_OK;
 }
@@ -5662,6 +5664,34 @@ int ekf_dense_get_census(ekf_dense* h, int slot, unsigned long long* out) {
 int ekf_dense_get_census_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->impl->census_timer.read(kernel_ms, launches, 0, 3);
+  return EKF_OK;
+}
+
+// ---- best-K source selection ----------------------------------------------------------------------------------
+int ekf_dense_sweep_best(ekf_dense* h, int ref, const int* src, int n_src, int n_best, double w_min, double w_max, int planes,
+                         int radius, int trunc, int census, int paths, int p1, int p2) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  const bool sgm = paths != 0;
+  if (!dense_sweep_ok(d, ref, src, n_src, w_min, w_max, planes, radius, trunc) || n_best < 1 || n_best > n_src ||
+      (census != 0 && census != 1) || (paths != 0 && paths != 4 && paths != 8) || (!sgm && (p1 != 0 || p2 != 0)) ||
+      (sgm && (p1 < 1 || p1 > p2 || p2 > ekf::kSgmMaxPenalty || (long long)d->W * d->H * planes > ekf::kSgmMaxElems))) {
+    d->err = "ekf_dense_sweep_best: the arguments of ekf_dense_sweep; 1 <= n_best <= n_src, census 0 or 1, paths 0, 4 or 8; "
+             "paths 0: p1 = p2 = 0; otherwise 1 <= p1 <= p2 <= 2^20 and width x height x planes <= 2^28";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  if (sgm)
+    HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths, census != 0, n_best));
+  else
+    HIPCHK(d->sweep(ref, src, n_src, w_min, w_max, planes, radius, trunc, census != 0, n_best));
+  return EKF_OK;
+}
+
+int ekf_dense_get_best_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->impl->best_timer.read(kernel_ms, launches, 0, 4);
   return EKF_OK;
 }
 

@@ -214,7 +214,7 @@ struct DenseSgm {
   KernelTimer<kSgmKinds> timer;
 
   hipError_t sweep(DenseStereo& d, int ref, const int* src, int n_src, double w_min, double w_max, int D_, int radius, int trunc,
-                   int p1, int p2, int paths, bool census = false) {
+                   int p1, int p2, int paths, bool census = false, int n_best = 0) {
 #pragma clang fp contract(off)
     DenseView& r = d.v[ref];
     hipError_t e;
@@ -238,8 +238,13 @@ struct DenseSgm {
     const SweepVolume vol{C, V};
     const dim3 grid((unsigned)((d.W + kDenseTW - 1) / kDenseTW), (unsigned)((d.H + kDenseTH - 1) / kDenseTH));
     // the census volume (§20) counts under the census profile, its directions and winner below like any other
-    e = census ? d.census_timer.run(2, [&] { k_sweep_volume_census<<<grid, 256, 0, nullptr>>>(a, vol); })
-               : timer.run(0, [&] { k_sweep_volume<<<grid, 256, 0, nullptr>>>(a, vol); });
+    // and the volume of the n_best cheapest sources (§21; n_best = 0: of all of them) under the best profile
+    if (n_best > 0)
+      e = census ? d.best_timer.run(3, [&] { k_sweep_volume_best_census<<<grid, 256, 0, nullptr>>>(a, vol, n_best); })
+                 : d.best_timer.run(2, [&] { k_sweep_volume_best<<<grid, 256, 0, nullptr>>>(a, vol, n_best); });
+    else
+      e = census ? d.census_timer.run(2, [&] { k_sweep_volume_census<<<grid, 256, 0, nullptr>>>(a, vol); })
+                 : timer.run(0, [&] { k_sweep_volume<<<grid, 256, 0, nullptr>>>(a, vol); });
     if (e != hipSuccess) return e;
     for (int i = 0; i < paths; ++i) {
       const SgmPathArgs p{C, S, d.W, d.H, D_, p1, p2, kSgmDir[i][0], kSgmDir[i][1]};

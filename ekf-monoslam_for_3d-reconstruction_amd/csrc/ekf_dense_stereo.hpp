@@ -139,6 +139,46 @@ __global__ void __launch_bounds__(256) k_census(CensusArgs a) {
   }
 }
 
+// The cost c_v of one halo pixel (ray (hx, hy), reference value or descriptor `ref`) on the plane of depth z in the source
+// view s: §15.1's warp and validity test, then the truncated absolute difference of the 5-bit bilinear sample or (CENSUS, §20)
+// the truncated Hamming distance at the nearest pixel.  An invalid warp costs trunc; a valid one adds 1 to nv.  Written once
+// for plane_sweep_body and plane_sweep_best_body (§21).
+template <bool CENSUS, typename Ref>
+__device__ __forceinline__ int sweep_view_cost(const SweepArgs& a, const DenseSrc& s, double hx, double hy, double z, Ref ref,
+                                               double qx_max, double qy_max, int& nv) {
+#pragma clang fp contract(off)
+  const int W = a.W, H = a.H;
+  const double a0 = s.A[0] * hx + s.A[1] * hy + s.A[2];
+  const double a1 = s.A[3] * hx + s.A[4] * hy + s.A[5];
+  const double a2 = s.A[6] * hx + s.A[7] * hy + s.A[8];
+  const double Q0 = z * a0 + s.b[0];
+  const double Q1 = z * a1 + s.b[1];
+  const double Q2 = z * a2 + s.b[2];
+  int c = a.trunc;
+  if (Q2 > 0.0) {
+    const double sx = s.fx * (Q0 / Q2) + s.cx;
+    const double sy = s.fy * (Q1 / Q2) + s.cy;
+    const double fqx = floor(sx * 32.0 + 0.5), fqy = floor(sy * 32.0 + 0.5);
+    if (fqx >= 0.0 && fqx <= qx_max && fqy >= 0.0 && fqy <= qy_max) {       // (a NaN fails)
+      const int qx = (int)fqx, qy = (int)fqy;
+      if constexpr (CENSUS) {
+        const int jx = (qx + 16) >> 5, jy = (qy + 16) >> 5;                   // the nearest pixel: jx <= W - 1, jy <= H - 1
+        c = min(__builtin_popcountll(ref ^ s.census[(size_t)jy * W + jx]), a.trunc);
+      } else {
+        const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;       // ix in [0, W - 1], iy in [0, H - 1]
+        const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);           // weight 0 where clamped (ax = 0 there)
+        const unsigned char* r0 = s.img + (size_t)iy * W;
+        const unsigned char* r1 = s.img + (size_t)iy1 * W;
+        const int g = ((32 - ax) * (32 - ay) * (int)r0[ix] + ax * (32 - ay) * (int)r0[ix1] + (32 - ax) * ay * (int)r1[ix] +
+                       ax * ay * (int)r1[ix1] + 512) >> 10;
+        c = min(abs(ref - g), a.trunc);
+      }
+      ++nv;
+    }
+  }
+  return c;
+}
+
 // CENSUS (§20; a second template parameter, so the fp64 warp is written once): the matching cost is the Hamming distance of
 // census descriptors, not the absolute grey difference.  A halo pixel's register value is then its 64-bit descriptor, and
 // per source the four byte gathers and the blend become one 8-byte load at the nearest pixel and a popcount.  The warp, the
@@ -194,38 +234,7 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
         continue;
       }
       int csum = 0, nv = 0;
-      for (int v = 0; v < a.n_src; ++v) {
-        const DenseSrc& s = a.s[v];
-        const double a0 = s.A[0] * h_x[i] + s.A[1] * h_y[i] + s.A[2];
-        const double a1 = s.A[3] * h_x[i] + s.A[4] * h_y[i] + s.A[5];
-        const double a2 = s.A[6] * h_x[i] + s.A[7] * h_y[i] + s.A[8];
-        const double Q0 = z * a0 + s.b[0];
-        const double Q1 = z * a1 + s.b[1];
-        const double Q2 = z * a2 + s.b[2];
-        int c = a.trunc;
-        if (Q2 > 0.0) {
-          const double sx = s.fx * (Q0 / Q2) + s.cx;
-          const double sy = s.fy * (Q1 / Q2) + s.cy;
-          const double fqx = floor(sx * 32.0 + 0.5), fqy = floor(sy * 32.0 + 0.5);
-          if (fqx >= 0.0 && fqx <= qx_max && fqy >= 0.0 && fqy <= qy_max) {   // (a NaN fails)
-            const int qx = (int)fqx, qy = (int)fqy;
-            if constexpr (CENSUS) {
-              const int jx = (qx + 16) >> 5, jy = (qy + 16) >> 5;               // the nearest pixel: jx <= W - 1, jy <= H - 1
-              c = min(__builtin_popcountll(h_ref[i] ^ s.census[(size_t)jy * W + jx]), a.trunc);
-            } else {
-              const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;   // ix in [0, W - 1], iy in [0, H - 1]
-              const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);       // weight 0 where clamped (ax = 0 there)
-              const unsigned char* r0 = s.img + (size_t)iy * W;
-              const unsigned char* r1 = s.img + (size_t)iy1 * W;
-              const int g = ((32 - ax) * (32 - ay) * (int)r0[ix] + ax * (32 - ay) * (int)r0[ix1] + (32 - ax) * ay * (int)r1[ix] +
-                             ax * ay * (int)r1[ix1] + 512) >> 10;
-              c = min(abs(h_ref[i] - g), a.trunc);
-            }
-            ++nv;
-          }
-        }
-        csum += c;
-      }
+      for (int v = 0; v < a.n_src; ++v) csum += sweep_view_cost<CENSUS>(a, a.s[v], h_x[i], h_y[i], z, h_ref[i], qx_max, qy_max, nv);
       sc[h_off[i]] = csum | (nv << 16);                                     // csum <= 8 * 255
     }
     __syncthreads();
@@ -275,6 +284,182 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
 __global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) { plane_sweep_body<false>(a, SweepVolume{nullptr, nullptr}); }
 __global__ void __launch_bounds__(256) k_plane_sweep_census(SweepArgs a) {
   plane_sweep_body<false, true>(a, SweepVolume{nullptr, nullptr});
+}
+
+// ---- best-K source selection ------------------------------------------------------------------------------
+// Per pixel and plane the cost is the sum of the n_best smallest per-view window sums C_k^v, not the sum of all of them: a
+// selection does not commute with the window sum, so the windowed cost must exist per view and the one pair of LDS passes of
+// plane_sweep_body becomes one per PAIR of views.  Two views share an LDS word as 16-bit halves: a pixel cost is <= 255, a
+// horizontal sum <= 9 * 255 = 2295 and a window sum <= 81 * 255 = 20 655 < 2^16, so no carry crosses the halves and one
+// integer add serves both.  All kBestPairs planes of words stay in LDS at once (4 * 7104 = 28 416 B), so a plane of the sweep
+// still costs two barriers whatever n_src is (§21.2 has the reasons).  The count of valid warps, whose place in the upper
+// half is now taken, rides in the top byte of the first pair's word of s_c (bits 8 .. 15 and 24 .. 31 of a pair of pixel costs
+// are free); the horizontal pass masks it off.  The tile, the halo in registers, the grid and the winner are plane_sweep_body's.
+constexpr int kBestPairs = kDenseMaxSrc / 2;
+constexpr int kBestNone = 0xffff;                 // no view: more than any window sum
+
+// The n_best smallest of up to 8 values, in registers: a list s[0 .. 7], sorted, that starts as kBestNone eight times;
+// best_insert lets x sink to its place by min / max, the larger value moving on (the largest of the nine drops out), and
+// best_take sums the first n_best entries.  Every index is a compile-time constant, so the list never goes to scratch.
+__device__ __forceinline__ void best_insert(int (&s)[kDenseMaxSrc], int x) {
+#pragma unroll
+  for (int i = 0; i < kDenseMaxSrc; ++i) {
+    const int lo = min(s[i], x);
+    x = max(s[i], x);
+    s[i] = lo;
+  }
+}
+// (predicated on i < n_best by a limit of 0, one SGPR each, not by a comparison, which would hold a pair of SGPRs each)
+__device__ __forceinline__ int best_take(const int (&s)[kDenseMaxSrc], int n_best) {
+  int sum = s[0];                                                           // n_best >= 1
+#pragma unroll
+  for (int i = 1; i < kDenseMaxSrc; ++i) sum += min(s[i], i < n_best ? kBestNone : 0);
+  return sum;
+}
+
+template <bool VOLUME, bool CENSUS>
+__device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const SweepVolume& vol, int n_best) {
+#pragma clang fp contract(off)
+  __shared__ int s_c[kBestPairs][kDenseHH][kDenseHW + 1];
+  __shared__ int s_h[kBestPairs][kDenseHH][kDenseTW + 1];
+  const int tid = threadIdx.x;
+  const int r = a.radius, hw = kDenseTW + 2 * r, hh = kDenseTH + 2 * r, nh = hw * hh;
+  const int x0 = (int)blockIdx.x * kDenseTW - r, y0 = (int)blockIdx.y * kDenseTH - r;
+  const int W = a.W, H = a.H;
+  const int n_pairs = (a.n_src + 1) >> 1;                                   // a kernel argument: uniform
+  // what ekf_dense_sweep_best has checked: without it every loop below gets a guard, kept as a lane mask in two SGPRs
+  __builtin_assume(r >= 0 && r <= kDenseMaxRadius);
+  __builtin_assume(a.n_src >= 1 && a.n_src <= kDenseMaxSrc);
+  __builtin_assume(a.D >= 1);
+  const double qx_max = (double)(32 * (W - 1)), qy_max = (double)(32 * (H - 1));
+
+  // the lane's halo pixels, as in plane_sweep_body
+  int h_off[kDenseHaloPerLane];                                           // h_off < 0: none, or outside the image
+  typename std::conditional<CENSUS, unsigned long long, int>::type h_ref[kDenseHaloPerLane];
+  double h_x[kDenseHaloPerLane], h_y[kDenseHaloPerLane];
+#pragma unroll
+  for (int i = 0; i < kDenseHaloPerLane; ++i) {
+    const int h = tid + 256 * i;
+    const int hy = h / hw, hx = h - hy * hw;
+    const int X = x0 + hx, Y = y0 + hy;
+    const bool in = h < nh && X >= 0 && X < W && Y >= 0 && Y < H;
+    h_off[i] = h < nh ? (in ? hy * (kDenseHW + 1) + hx : -1 - (hy * (kDenseHW + 1) + hx)) : INT_MIN;
+    if constexpr (CENSUS)
+      h_ref[i] = in ? a.ref_census[(size_t)Y * W + X] : 0ull;
+    else
+      h_ref[i] = in ? (int)a.ref[(size_t)Y * W + X] : 0;
+    h_x[i] = ((double)X - a.cx) / a.fx;
+    h_y[i] = ((double)Y - a.cy) / a.fy;
+  }
+  const int tx = tid & 31, ty = tid >> 5;
+  constexpr int pair_words = kDenseHH * (kDenseHW + 1);
+  static_assert(kDenseTW * kDenseTH >= 512, "halo positions 0 .. 511 exist at every radius");
+  int* const sc = &s_c[0][0][0];
+
+  // VOLUME: where plane 0 of the two owned pixels goes in the volumes (NULL: outside the image); kept per lane, so the
+  // plane loop holds no base pointer in SGPRs
+  unsigned* own_C[2] = {nullptr, nullptr};
+  unsigned char* own_V[2] = {nullptr, nullptr};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
+    if (VOLUME && X < W && Y < H) {
+      own_C[j] = vol.C + ((size_t)Y * W + X) * (size_t)a.D;
+      own_V[j] = vol.V + ((size_t)Y * W + X);
+    }
+  }
+  const size_t plane_elems = (size_t)W * H;
+  int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
+  for (int k = 0; k < a.D; ++k) {
+    const double z = 1.0 / (a.w_min + (double)k * a.step);
+#pragma unroll
+    for (int i = 0; i < kDenseHaloPerLane; ++i) {
+      if (i >= 2 && h_off[i] == INT_MIN) continue;                          // (the first 512 halo positions always exist)
+      if (h_off[i] < 0) {                                                   // a window position outside the image: nothing
+        for (int p = 0; p < n_pairs; ++p) sc[p * pair_words - 1 - h_off[i]] = 0;
+        continue;
+      }
+      // one view a turn, as in plane_sweep_body (the view's 38 words of kernel arguments sit in SGPRs; unrolled by two, the
+      // compiler keeps two views' and spills): an even view opens a word, an odd one or the last one closes it.  The upper
+      // half of an odd n_src's last word keeps trunc, the cost of a view whose every warp is invalid: no real view's window
+      // sum is larger, so it sorts last and is never among the n_best <= n_src smallest.  The branches are uniform.
+      int nv = 0, word = 0, word0 = 0;
+#pragma unroll 1
+      for (int v = 0; v < a.n_src; ++v) {
+        const int c = sweep_view_cost<CENSUS>(a, a.s[v], h_x[i], h_y[i], z, h_ref[i], qx_max, qy_max, nv);
+        word = (v & 1) ? (word & 0xffff) | (c << 16) : c | (a.trunc << 16);  // each half <= 255
+        if ((v & 1) || v == a.n_src - 1) {
+          if (v < 2) word0 = word;                                          // waits for the count of all views
+          else sc[(v >> 1) * pair_words + h_off[i]] = word;
+        }
+      }
+      sc[h_off[i]] = word0 | (nv << 24);                                    // nv <= 8
+    }
+    __syncthreads();
+    // horizontal pass over the hh halo rows, 32 columns each, of every pair; the valid count of the owned pixels is read
+    // here, before the barrier after which other lanes may overwrite s_c for the next plane
+    for (int e = tid; e < hh * kDenseTW; e += 256) {
+      const int row = e >> 5, col = e & 31;
+      for (int p = 0; p < n_pairs; ++p) {
+        int sum = 0;
+        for (int d = 0; d <= 2 * r; ++d) sum += s_c[p][row][col + d] & 0x00ff00ff;
+        s_h[p][row][col] = sum;                                             // each half <= 2295
+      }
+    }
+    const int nv0 = s_c[0][ty + r][tx + r] >> 24, nv1 = s_c[0][ty + 8 + r][tx + r] >> 24;
+    __syncthreads();
+    // vertical pass and selection: the two owned pixels (the next write of s_h comes after the next plane's first barrier)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int oy = ty + 8 * j;
+      int best[kDenseMaxSrc];
+#pragma unroll
+      for (int i = 0; i < kDenseMaxSrc; ++i) best[i] = kBestNone;
+#pragma unroll 1
+      for (int p = 0; p < n_pairs; ++p) {
+        unsigned word = 0;
+        for (int d = 0; d <= 2 * r; ++d) word += (unsigned)s_h[p][oy + d][tx];     // each half <= 20 655
+        best_insert(best, (int)(word & 0xffffu));
+        best_insert(best, (int)(word >> 16));                               // (an odd n_src's last: the all-trunc view)
+      }
+      const int C = best_take(best, n_best);
+      if constexpr (VOLUME) {
+        if (own_C[j]) {
+          own_C[j][k] = (unsigned)C;
+          own_V[j][(size_t)k * plane_elems] = (unsigned char)(j == 0 ? nv0 : nv1);
+        }
+        continue;
+      }
+      // the winner selects of plane_sweep_body
+      const bool pending = bestK[j] == k - 1, better = C < bestC[j];
+      bestP[j] = (pending || better) ? C : bestP[j];
+      bestM[j] = better ? prevC[j] : bestM[j];
+      bestV[j] = better ? (j == 0 ? nv0 : nv1) : bestV[j];
+      bestK[j] = better ? k : bestK[j];
+      bestC[j] = better ? C : bestC[j];
+      prevC[j] = C;
+    }
+  }
+  if constexpr (VOLUME) return;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
+    if (X >= W || Y >= H) continue;
+    sweep_write_winner(a, (size_t)Y * W + X, bestK[j], bestM[j], bestC[j], bestP[j], bestV[j]);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_plane_sweep_best(SweepArgs a, int n_best) {
+  plane_sweep_best_body<false, false>(a, SweepVolume{nullptr, nullptr}, n_best);
+}
+__global__ void __launch_bounds__(256) k_plane_sweep_best_census(SweepArgs a, int n_best) {
+  plane_sweep_best_body<false, true>(a, SweepVolume{nullptr, nullptr}, n_best);
+}
+__global__ void __launch_bounds__(256) k_sweep_volume_best(SweepArgs a, SweepVolume vol, int n_best) {
+  plane_sweep_best_body<true, false>(a, vol, n_best);
+}
+__global__ void __launch_bounds__(256) k_sweep_volume_best_census(SweepArgs a, SweepVolume vol, int n_best) {
+  plane_sweep_best_body<true, true>(a, vol, n_best);
 }
 
 struct FilterArgs {
@@ -405,6 +590,7 @@ struct DenseStereo {
   DevBuf<double> d_xyz;               // the points on their way to the host (allocated by the first ekf_dense_get_points)
   KernelTimer<2> timer;               // k_plane_sweep, k_depth_filter_points
   KernelTimer<3> census_timer;        // k_census, k_plane_sweep_census, k_sweep_volume_census (§20)
+  KernelTimer<4> best_timer;          // k_plane_sweep_best, .._best_census, k_sweep_volume_best, .._best_census (§21)
 
   size_t npix() const { return (size_t)W * H; }
   const unsigned char* colour_of(int slot) const { return v[slot].colour ? (const unsigned char*)v[slot].bgr : nullptr; }
@@ -460,7 +646,10 @@ struct DenseStereo {
     return e;
   }
 
-  hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc, bool census = false) {
+  // n_best = 0: the sum over all sources (k_plane_sweep, k_plane_sweep_census); 1 .. n_src: the n_best cheapest sources per
+  // pixel and plane (§21: k_plane_sweep_best, k_plane_sweep_best_census, also for n_best = n_src).
+  hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc, bool census = false,
+                   int n_best = 0) {
 #pragma clang fp contract(off)
     DenseView& r = v[ref];
     hipError_t e;
@@ -478,8 +667,12 @@ struct DenseStereo {
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
     r.swept = r.filtered = r.sgm = false;
     const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
-    e = census ? census_timer.run(1, [&] { k_plane_sweep_census<<<grid, 256, 0, nullptr>>>(a); })
-               : timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); });
+    if (n_best > 0)
+      e = census ? best_timer.run(1, [&] { k_plane_sweep_best_census<<<grid, 256, 0, nullptr>>>(a, n_best); })
+                 : best_timer.run(0, [&] { k_plane_sweep_best<<<grid, 256, 0, nullptr>>>(a, n_best); });
+    else
+      e = census ? census_timer.run(1, [&] { k_plane_sweep_census<<<grid, 256, 0, nullptr>>>(a); })
+                 : timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); });
     if (e != hipSuccess) return e;
     r.swept = true;
     return hipSuccess;

@@ -104,24 +104,37 @@ class DenseStereo(capi.Handle):
 
     # ---- the two launches ----
     def sweep(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 2,
-              trunc: int = 40, cost: str = "ad"):
+              trunc: int = 40, cost: str = "ad", best: Optional[int] = None):
         """``cost``: ``"ad"``, the truncated absolute grey difference, or ``"census"``, the truncated
-        Hamming distance of 9 x 7 census descriptors (§20), for key frames whose exposure or gain differ."""
+        Hamming distance of 9 x 7 census descriptors (§20), for key frames whose exposure or gain differ.
+        ``best``: ``None`` sums the cost over all sources; an int keeps, per pixel and plane, that many cheapest sources
+        (§21), for sources that do not all see every pixel of ``ref``."""
         fn = _cost_entry(self._lib, cost, "ekf_dense_sweep")
         src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        if best is not None:
+            self._check(self._lib.ekf_dense_sweep_best(self._h, int(ref), _ptr(src), len(src), int(best), float(w_min), float(w_max),
+                                                       int(planes), int(radius), int(trunc), int(cost == "census"), 0, 0, 0))
+            return
         self._check(fn(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes), int(radius), int(trunc)))
 
     def sweep_sgm(self, ref: int, sources: Sequence[int], w_min: float, w_max: float, planes: int = 64, radius: int = 1,
-                  trunc: int = 40, p1: Optional[int] = None, p2: Optional[int] = None, paths: int = 8, cost: str = "ad"):
+                  trunc: int = 40, p1: Optional[int] = None, p2: Optional[int] = None, paths: int = 8, cost: str = "ad",
+                  best: Optional[int] = None):
         """The sweep with semi-global cost aggregation: the slot's swept map, for ``filter``, ``depth``,
         ``points`` and the fusion exactly as after ``sweep``.  With n = (2 radius + 1)^2 len(sources), ``None`` means
         p1 = 2 n and p2 = 16 n: the values of the synthetic flat-patch scenes, not measured on real imagery -- with
-        ``cost="census"`` (§20) as with ``"ad"``."""
+        ``cost="census"`` (§20) as with ``"ad"``.  ``best``: as in ``sweep`` (§21); an int takes its place in n, which is
+        then (2 radius + 1)^2 best."""
         fn = _cost_entry(self._lib, cost, "ekf_dense_sweep_sgm")
         src = np.ascontiguousarray(sources, np.int32).reshape(-1)
-        n = (2 * int(radius) + 1) ** 2 * len(src)
+        n = (2 * int(radius) + 1) ** 2 * (len(src) if best is None else int(best))
         p1 = 2 * n if p1 is None else int(p1)
         p2 = 16 * n if p2 is None else int(p2)
+        if best is not None:
+            self._check(self._lib.ekf_dense_sweep_best(self._h, int(ref), _ptr(src), len(src), int(best), float(w_min), float(w_max),
+                                                       int(planes), int(radius), int(trunc), int(cost == "census"), int(paths), p1, p2))
+            self._sgm_planes = int(planes)
+            return
         self._check(fn(self._h, int(ref), _ptr(src), len(src), float(w_min), float(w_max), int(planes), int(radius), int(trunc),
                        p1, p2, int(paths)))
         self._sgm_planes = int(planes)
@@ -194,6 +207,14 @@ class DenseStereo(capi.Handle):
         ms, cnt = np.zeros(3, np.float64), np.zeros(3, np.int64)
         self._check(self._lib.ekf_dense_get_census_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(("k_census", "k_plane_sweep_census", "k_sweep_volume_census"))}
+
+    def get_best_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the four kernels of the best-K selection (§21) since the last
+        ``profile()``."""
+        ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
+        self._check(self._lib.ekf_dense_get_best_profile(self._h, _ptr(ms), _ptr(cnt)))
+        names = ("k_plane_sweep_best", "k_plane_sweep_best_census", "k_sweep_volume_best", "k_sweep_volume_best_census")
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(names)}
 
 
 def _cost_entry(lib, cost, name):
@@ -268,13 +289,18 @@ def neighbours_of(i: int, n: int, neighbours: int):
 
 def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, neighbours: int = 2, w_min: float = 0.05,
                               w_max: float = 2.0, planes: int = 64, radius: int = 2, trunc: int = 40, rel_tol: float = 0.01,
-                              min_agree: int = 1, device: int = 0, sgm=None, cost: str = "ad"):
+                              min_agree: int = 1, device: int = 0, sgm=None, cost: str = "ad",
+                              best: Optional[int] = None):
     """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
     order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
     The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
     neighbourhoods away) and the recording may be of any length >= 2.  Colour key frames become colour views.
     ``sgm``: ``None`` sweeps with ``sweep``; ``True`` or a dict of ``p1`` / ``p2`` / ``paths`` with ``sweep_sgm`` (§19).
-    ``cost``: ``"ad"`` or ``"census"`` (§20), the matching cost of either sweep."""
+    ``cost``: ``"ad"`` or ``"census"`` (§20), the matching cost of either sweep.
+    ``best``: ``None``, or the number of cheapest sources either sweep keeps per pixel and plane (§21); a key frame with fewer
+    sources than that keeps them all, as with ``min_agree``."""
+    if best is not None and int(best) < 1:
+        raise ValueError("best is None or an int >= 1")
     if cost not in ("ad", "census"):
         raise ValueError('cost is "ad" or "census"')
     if sgm is not None and sgm is not True and not (isinstance(sgm, dict) and set(sgm) <= {"p1", "p2", "paths"}):
@@ -297,10 +323,12 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
                 loaded += 1
             while swept < min(n, i + neighbours + 1):
                 src = [j % ring for j in neighbours_of(swept, n, neighbours)]
+                keep = None if best is None else min(int(best), len(src))
                 if sgm is None:
-                    ds.sweep(swept % ring, src, w_min, w_max, planes, radius, trunc, cost=cost)
+                    ds.sweep(swept % ring, src, w_min, w_max, planes, radius, trunc, cost=cost, best=keep)
                 else:
-                    ds.sweep_sgm(swept % ring, src, w_min, w_max, planes, radius, trunc, cost=cost, **({} if sgm is True else sgm))
+                    ds.sweep_sgm(swept % ring, src, w_min, w_max, planes, radius, trunc, cost=cost, best=keep,
+                                 **({} if sgm is True else sgm))
                 swept += 1
             src = neighbours_of(i, n, neighbours)
             ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)))

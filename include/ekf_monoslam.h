@@ -971,6 +971,34 @@ int ekf_dense_sweep_sgm_census(ekf_dense* h, int ref, const int* src, int n_src,
 int ekf_dense_get_census(ekf_dense* h, int slot, unsigned long long* out);
 int ekf_dense_get_census_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
+/* ---- best-K source selection for the dense sweeps ------------------------------------------------------
+ * The sweeps above sum the matching cost over ALL sources, an invalid warp costing trunc: at the image border of a moving
+ * camera, behind a depth step, or with a source that looks elsewhere, planes on which the warps are valid then beat planes on
+ * which they match.  This opt-in sweep keeps, per pixel and plane, the n_best cheapest sources (Kang & Szeliski).  The warp,
+ * its validity test, (qx, qy), the per-pixel cost c_v of source v (absolute difference, or census Hamming distance; an invalid
+ * warp costs trunc), the planes and the limits are those of ekf_dense_sweep / ekf_dense_sweep_census.  Then
+ *   C_k^v(p) = the sum of c_v over the (2 radius + 1)^2 window around p, positions outside the image contributing nothing
+ *              (<= 81 * 255 = 20 655);
+ *   C_k(p)   = the sum of the n_best smallest of C_k^0(p) .. C_k^{n_src - 1}(p)  (only the sum is defined: ties need no rule);
+ * for n_best = n_src, C_k(p) is the value of the existing sweeps, element for element.  views stays the number of sources
+ * whose warp of p itself is valid on the winning plane.  Everything after C is the existing path on the new numbers: the first
+ * plane of least cost and the parabola, views = 0 giving plane -1 and depth 0, and with paths of 4 or 8 the path costs of
+ * ekf_dense_sweep_sgm and the winner of S.  Integers throughout; tests/best_oracle.py restates it.  No default, result,
+ * launch, profile count or prototype of the calls above changes; ekf_abi_version() stays 6 (additions only).
+ *  - ekf_dense_sweep_best: census is 0 or 1.  paths = 0 takes the pixel-wise winner, and p1 and p2 must then be 0; paths = 4 or
+ *    8 aggregates as ekf_dense_sweep_sgm does, with its checks on p1, p2 and the volume size, and ekf_dense_get_volume works
+ *    afterwards.  EKF_ERR_ARG, before the device is touched, for everything the corresponding existing sweep refuses, n_best
+ *    outside 1 .. n_src, and census or paths outside their sets.  State rules, allocation failures (EKF_ERR_DEVICE, the
+ *    earlier maps still readable) and invalidation are those of the existing sweeps.  The call always launches the kernels
+ *    below, also for n_best = n_src;
+ *  - ekf_dense_get_best_profile: HIP-event milliseconds and launch counts of 4 kinds since the last ekf_dense_profile:
+ *    k_plane_sweep_best ([0]), k_plane_sweep_best_census ([1]), k_sweep_volume_best ([2]), k_sweep_volume_best_census ([3]).
+ *    k_census keeps counting under ekf_dense_get_census_profile [0], the directions and the winner under
+ *    ekf_dense_get_sgm_profile [1] .. [9]; ekf_dense_get_profile gains nothing. */
+int ekf_dense_sweep_best(ekf_dense* h, int ref, const int* src, int n_src, int n_best, double w_min, double w_max,
+                         int planes, int radius, int trunc, int census, int paths, int p1, int p2);
+int ekf_dense_get_best_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -544,6 +544,20 @@ class DenseStereoHip {
   }
   // HIP-event milliseconds and launch counts of k_census ([0]), k_plane_sweep_census ([1]), k_sweep_volume_census ([2])
   void getCensusProfile(double kernel_ms[3], long long launches[3]) { check(ekf_dense_get_census_profile(d_, kernel_ms, launches)); }
+  // the sweeps with best-K source selection: per pixel and plane the n_best cheapest of the sources,
+  // for views that do not all see every reference pixel; census: the matching cost of sweepCensus; paths 0: the pixel-wise
+  // winner; 4 or 8: the aggregation of sweepSgm, with its 2 n and 16 n for p1, p2 <= 0 where n = (2 radius + 1)^2 n_best
+  void sweepBest(int ref, const std::vector<int>& src, int n_best, double w_min, double w_max, int planes = 64, int radius = 2,
+                 int trunc = 40, bool census = false, int paths = 0, int p1 = 0, int p2 = 0) {
+    const int n = (2 * radius + 1) * (2 * radius + 1) * n_best;
+    if (paths != 0) { p1 = p1 > 0 ? p1 : 2 * n; p2 = p2 > 0 ? p2 : 16 * n; }
+    check(ekf_dense_sweep_best(d_, ref, src.data(), (int)src.size(), n_best, w_min, w_max, planes, radius, trunc, census ? 1 : 0, paths,
+                               p1, p2));
+    if (paths != 0) sgm_planes_ = planes;
+  }
+  // HIP-event milliseconds and launch counts of k_plane_sweep_best ([0]), k_plane_sweep_best_census ([1]), k_sweep_volume_best
+  // ([2]), k_sweep_volume_best_census ([3])
+  void getBestProfile(double kernel_ms[4], long long launches[4]) { check(ekf_dense_get_best_profile(d_, kernel_ms, launches)); }
   void filter(int ref, const std::vector<int>& src, double rel_tol = 0.01, int min_agree = 1) {
     check(ekf_dense_filter(d_, ref, src.data(), (int)src.size(), rel_tol, min_agree));
   }

@@ -29,6 +29,9 @@ static pthread_barrier_t g_barrier;
 #define __syncthreads() pthread_barrier_wait(&g_barrier)
 using std::max;
 using std::min;
+#ifndef __clang__
+#define __builtin_assume(x) ((void)0)                       // a hint to the device compiler (csrc/ekf_dense_stereo.hpp)
+#endif
 #define EKF_KERNELS_ONLY
 
 // A kernel that reads another lane's register (csrc/ekf_dense_sgm.hpp: wave_read, the device's __shfl) gets exactly that
