@@ -88,7 +88,7 @@ static const char* kLaunchNames[EKF_LAUNCH_KINDS] = {
     "row_rider", "row_gemv", "row_tile_gemm", "w_update_gemm", "w_recompute",
     "chain_step_launches", "chain_persistent", "solve", "solve_two_groups", "update_oneblock", "update_allinone",
     "chain_trail_diag", "split_image", "state_update_tail", "update_onelaunch", "chain_dist_gather", "chain_step_fused",
-    "downdate_mirror_bounds"};
+    "downdate_mirror_bounds", "solve_poll_chain"};
 
 static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
@@ -332,6 +332,10 @@ struct Filter : FilterBase {
   // EKF_SYRK_MIRROR_SKIP=0: every k_syrk_bf16x6 launch stores every mirror (rounds 5-6; A/B and bit-identity check).  1: launches
   // 0 .. G-2 of an update mirror only the tiles whose rows the re-evaluation of the next chunk reads as columns (Syrk6Args::mirror_rows)
   int opt_syrk_mirror_skip = 1;
+  // EKF_SOLVE_POLL_CHAIN=0: every overlapped solve sits behind a stream wait for the chain's event (rounds 1-7; A/B and
+  // bit-identity check).  1: the solves of chunks 1 .. G-2 are launched without it and wait for the chain in their prologue
+  // (GemmArgs::chain_word; Filter::update), in plans of at most 16 block steps; 2: in every plan (solve_polls_chain)
+  int opt_solve_poll_chain = 1;
   int opt_fuse_split = 1;                               // EKF_FUSE_SPLIT=0: the plane image of V_g by its own launch behind the solve (rounds 5)
   int opt_chain_defer = 1;                              // EKF_CHAIN_DEFER=0: a chunk's event behind the trailing update of its last step (rounds 1-5)
   int td_min_blocks = 24;                               // EKF_TD_MIN_BLOCKS: steps with fewer blocks in their update keep the three launches
@@ -474,8 +478,8 @@ struct Filter : FilterBase {
     HIPCHK(hipMemsetAsync(d_status, 0, 16 * sizeof(int), stream));
     HIPCHK(d_tmp.reserve(64));
     // (behind the queue heads: the row bounds of the mirror rule, written by the first launch of every update)
-    HIPCHK(d_counters.reserve(kQueueCounters + kMirrorRowsInts));
-    HIPCHK(hipMemset(d_counters, 0, (kQueueCounters + kMirrorRowsInts) * sizeof(int)));
+    HIPCHK(d_counters.reserve(kResetInts + kMirrorRowsInts));
+    HIPCHK(hipMemset(d_counters, 0, (kResetInts + kMirrorRowsInts) * sizeof(int)));
     {
       hipDeviceProp_t prop;
       HIPCHK(hipGetDeviceProperties(&prop, device));
@@ -519,6 +523,7 @@ struct Filter : FilterBase {
       if (const char* e = getenv("EKF_FUSE_SPLIT")) opt_fuse_split = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SU_TAIL")) opt_su_tail = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SYRK_MIRROR_SKIP")) opt_syrk_mirror_skip = atoi(e) ? 1 : 0;
+      if (const char* e = getenv("EKF_SOLVE_POLL_CHAIN")) opt_solve_poll_chain = std::max(0, std::min(2, atoi(e)));
       if (const char* e = getenv("EKF_SMALL_ONELAUNCH")) opt_small_onelaunch = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_STEP_FUSED")) opt_step_fused = atoi(e) ? 1 : 0;
       if (const char* e = getenv("EKF_SHARD_DIST_CHAIN")) opt_shard_dist_chain = atoi(e) ? 1 : 0;
@@ -1411,6 +1416,7 @@ struct Filter : FilterBase {
     void* img = nullptr; int img_nkc = 0, img_c0 = 0;
     bool two_groups = false;                            // ROLE_SOLVE: two wave groups per workgroup (want_solve_s2)
     bool one_per_cu = false;                            // ROLE_SOLVE, queued: one workgroup per CU (solve_shape)
+    const unsigned* chain_word = nullptr; unsigned chain_epoch = 0;   // ROLE_SOLVE: wait for the chain in the kernel (solve_polls_chain)
     hipStream_t st = nullptr;                           // null: the main stream
   };
   // Everything an update decides before its first launch: filled once by plan_update(), a local of update() / shard_update()
@@ -1460,6 +1466,7 @@ struct Filter : FilterBase {
     g.zrow = c.zrow; g.zcol_end = c.zcol_end;
     g.stagger = (ROLE == ROLE_DOWNDATE) ? 1 : 0;
     g.img = c.img; g.img_nkc = c.img_nkc; g.img_c0 = c.img_c0;
+    g.chain_word = c.chain_word; g.chain_epoch = c.chain_epoch; g.status = d_status;
     hipStream_t st = c.st ? c.st : stream;
     const bool mf = kIsF32 && opt_mfma;
     dim3 grid(c.cols / (mf ? TN : 64), c.rows / (mf ? TM : 64));
@@ -1673,7 +1680,7 @@ struct Filter : FilterBase {
       T* nuq = with_nu ? nu_row : nullptr;
       // the slab also writes the row bounds of the chunks' features (the mirror rule of the bf16x6 downdate)
       const ChunkTab st = tab ? *tab : ChunkTab{0, {}};
-      int* mrows = (with_nu && tab) ? d_counters + kQueueCounters : nullptr;
+      int* mrows = (with_nu && tab) ? d_counters + kResetInts : nullptr;
       if (small) {
         constexpr int RB = 4;
         dim3 grid((m_pad / 2 + 255) / 256, (n + RB - 1) / RB + extra);
@@ -2100,6 +2107,23 @@ struct Filter : FilterBase {
   bool chunk_su_tail(const UpdatePlan& p, int g, const UpdateCtx& ux) const {
     return kIsF32 && opt_su_tail && !chunk_overlaps(p, g) && p.nchunks > 1 && chunk_splits(p, ux);
   }
+  // The overlapped solve waits for the chain inside the kernel, not behind a stream wait (EKF_SOLVE_POLL_CHAIN): a cross-stream
+  // wait costs the second stream 6-12 us even when its event fired long ago (profiles/r6_step_timeline.txt), a poll of a word
+  // that is already there a fraction of one.  Only where a spinning solve cannot hold what the chain needs: the second stream
+  // is masked off the reserved CUs and the chain always finds those.  Not chunk 0 -- its chain has the whole chip, workgroups
+  // that sit on the second stream's CUs for its 150 us would confine it to the reserved ones, and its stream wait is also what
+  // orders the second stream behind the reset of the queue heads and of the epoch word.  Not the last chunk -- its solve runs
+  // on every CU, where spinning workgroups could keep the producer's from being placed: it keeps its event wait.
+  // Only plans of at most 16 block steps (N <= 1000), by measurement (profiles/r7_solve_poll_chain_ab.txt): 16 steps 0.865 ->
+  // 0.853 ms per step with the poll, 10 steps 0.482 = 0.482, 32 steps (N = 2000) 4.66 -> 4.82.  The likely cause of that loss:
+  // a solve that really has to wait sits on the second stream's CUs meanwhile, and k_trail_diag (one workgroup per CU, 141 KB
+  // of LDS) fits on none of them, so a chain that is BEHIND stays confined to the reserved CUs where it would have had the
+  // idle chip.  EKF_SOLVE_POLL_CHAIN=2
+  // polls at any size (A/B runs).
+  bool solve_polls_chain(const UpdatePlan& p, int g) const {
+    return kIsF32 && opt_mfma && opt_solve_poll_chain && (p.nsteps <= 16 || opt_solve_poll_chain > 1) && g > 0 &&
+           chunk_overlaps(p, g) && stream_b_masked && reserved_cus > 0 && !p.oneblock;
+  }
   enum SolveShape { SOLVE_64X64, SOLVE_128_ONE_PER_CU, SOLVE_64X128, SOLVE_128 };
   SolveShape solve_shape(const UpdatePlan& p, int g) const {
     const bool mf = kIsF32 && opt_mfma;
@@ -2166,6 +2190,10 @@ struct Filter : FilterBase {
     c.rows = p.npad_live + p.nb; c.cols = width; c.K = width; c.ktri = KTRI_UPPER;
     c.two_groups = want_solve_s2(width, p.npad_live);
     c.st = ss;
+    if (ss == stream_b && solve_polls_chain(p, gi)) {
+      c.chain_word = reinterpret_cast<const unsigned*>(d_counters + kChainEpochWord); c.chain_epoch = (unsigned)gi + 1;
+      ++launch_cnt[EKF_LAUNCH_SOLVE_POLL_CHAIN];
+    }
     switch (solve_shape(p, gi)) {
       case SOLVE_64X64:
         c.tile_list = tilemap.d + solve6464_off + 2 * (2 * ntc - 2 * wt) * 2 * ntr; c.ntiles = 2 * wt * 2 * ntr;
@@ -2235,7 +2263,7 @@ struct Filter : FilterBase {
       // nothing when W is updated right-looking (nobody reads Sigma between the launches: the empty entry)
       const int* mirror_rows = nullptr;
       if (opt_syrk_mirror_skip && gi + 1 < p.nchunks)
-        mirror_rows = d_counters + kQueueCounters + 2 * (p.recompute ? gi + 1 : kMirrorEmpty);
+        mirror_rows = d_counters + kResetInts + 2 * (p.recompute ? gi + 1 : kMirrorEmpty);
       return launch_downdate_bf16x6(ux, c0, c1, m_pad, ss, !vimg_done, tilemap.d + tri6_off, tri_count, 0, 0, INT_MAX,
                                     double(n) * n * (std::min(c1, m) - std::min(c0, m)), row_rider, su_tail, mirror_rows);
     }
@@ -2356,8 +2384,13 @@ struct Filter : FilterBase {
       }
       if (overlap) {
         b_inflight = true;
-        HIPCHK(hipEventRecord(ev_chain[gi], stream));
-        HIPCHK(hipStreamWaitEvent(stream_b, ev_chain[gi], 0));
+        if (solve_polls_chain(p, gi)) {              // the solve's workgroups wait for this word themselves
+          if constexpr (kIsF32)
+            k_publish_epoch<<<1, 64, 0, stream>>>(reinterpret_cast<unsigned*>(d_counters + kChainEpochWord), (unsigned)gi + 1);
+        } else {
+          HIPCHK(hipEventRecord(ev_chain[gi], stream));
+          HIPCHK(hipStreamWaitEvent(stream_b, ev_chain[gi], 0));
+        }
       }
       bool vimg_done = false;                       // this chunk's solve writes the plane image of V_g
       rc = solve_chunk(p, gi, ux, ss, &vimg_done);

@@ -20,6 +20,8 @@ namespace ekf {
 // ---------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kQueueCounters = 256;              // work-queue heads of the queued launches of one update (8 ints apart)
+constexpr int kChainEpochWord = kQueueCounters;  // behind them, on a line of its own: the chain's epoch (k_publish_epoch)
+constexpr int kResetInts = kQueueCounters + 32;  // what the first launch of an update clears: the heads and the epoch word
 
 // A measured list read from DEVICE memory (ekf_update_device) cannot be checked on the host: an entry outside
 // [0, nfeat) or a list that is not strictly ascending raises status[1] (the next synchronising call returns
@@ -79,7 +81,7 @@ __global__ void k_innovation(const T* __restrict__ z, const T* __restrict__ h, c
                              int* __restrict__ counters, int nfeat, int* __restrict__ status) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (counters)                                          // work-queue heads / dependency counters of this update's queued GEMMs
-    for (int c = t; c < kQueueCounters; c += gridDim.x * blockDim.x) counters[c] = 0;
+    for (int c = t; c < kResetInts; c += gridDim.x * blockDim.x) counters[c] = 0;
   if (t >= m_pad) return;
   T v = T(0);
   if (t < 2 * M) {
@@ -120,7 +122,7 @@ __global__ void k_sigma_ht(const T* __restrict__ S, int ld, int n,
     // one more slab of workgroups than the rows need: the innovation nu = z - h (k_innovation folded into this
     // launch: one launch less in front of the chain) and the reset of the work-queue heads of this update
     if (counters)
-      for (int c = k; c < kQueueCounters; c += gridDim.x * blockDim.x) counters[c] = 0;
+      for (int c = k; c < kResetInts; c += gridDim.x * blockDim.x) counters[c] = 0;
     if (mirror_rows && blockIdx.x == 0) mirror_rows_slab(tab, midx, M, nfeat, pos, coding, mirror_rows);
     if (k >= nslots) return;
     if (k < M) check_measured_entry(midx, k, nfeat, status);
@@ -240,7 +242,7 @@ k_sigma_ht_fast(const float* __restrict__ S, int ld, int n,
     const int nslots = m_pad / 2;
     if (q_old && k < 4) q_old[k] = mu[3 + k];
     if (counters)
-      for (int c = k; c < kQueueCounters; c += gridDim.x * blockDim.x) counters[c] = 0;
+      for (int c = k; c < kResetInts; c += gridDim.x * blockDim.x) counters[c] = 0;
     if (mirror_rows && blockIdx.x == 0) mirror_rows_slab(tab, midx, M, nfeat, pos, coding, mirror_rows);
     if (k >= nslots) return;
     if (k < M) check_measured_entry(midx, k, nfeat, status);
@@ -510,7 +512,17 @@ struct GemmArgs {
   // (ekf_syrk6.hpp: three bf16 planes, 12 KB records), through LDS, with k_split_image's arithmetic -- the separate image
   // launch behind every solve is gone (round 6; round 5 had measured it when the chain, not the second stream, bounded the step)
   void* img = nullptr; int img_nkc = 0, img_c0 = 0;
+  // Optional (k_gemm_mfma<ROLE_SOLVE, ..>): the launch was issued WITHOUT a stream wait for the chain; every workgroup waits in
+  // its prologue until *chain_word has reached chain_epoch (k_publish_epoch on the chain's stream), bounded (status[3])
+  const unsigned* chain_word = nullptr; unsigned chain_epoch = 0; int* status = nullptr;
 };
+
+// The chain's stream tells the second stream that column chunk g is factored: ONE lane stores g + 1 into the word the
+// overlapped solve polls (GemmArgs::chain_word).  Stream order puts the store behind the chunk's last chain kernel, whose
+// end has released everything it wrote; the store itself is an agent-scope atomic, the form a poll on another XCD sees.
+__global__ void k_publish_epoch(unsigned* word, unsigned epoch) {
+  if (threadIdx.x == 0) __hip_atomic_store(word, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 constexpr int kSecondProduct = 0x10000;         // flag on bj for a tile of the second product
 constexpr int kHalfTile = 0x20000;              // flag on bi: 64-row half tile, bi & 0xffff in 64-row units (k_gemm_mfma, downdate)
 constexpr int kMirrorTile = 0x40000;            // flag on bi, tri == 3 (tiles taken as listed): also store the transposed tile
@@ -662,6 +674,26 @@ __global__ void __launch_bounds__(S2 ? 512 : 256, S2 ? 1 : ((ROLE == ROLE_TRAILI
   if (ROLE == ROLE_PANEL || ROLE == ROLE_TRAILING) __builtin_amdgcn_s_setprio(2);   // part of the serial chain
   if (g.stagger && g.tile_map && blockIdx.x >= gridDim.x / 2)
     for (int i = 0; i < g.stagger; ++i) __builtin_amdgcn_s_sleep(127);
+  if constexpr (ROLE == ROLE_SOLVE) {
+    // The overlapped solve of a chunk waits for the chain HERE instead of behind a stream wait (Filter::update,
+    // EKF_SOLVE_POLL_CHAIN): one lane polls the chain's epoch word, relaxed and with a sleep (k_chain_step_fused's
+    // convention: bounded, status[3] on time-out and the update fails), then ONE agent-scope acquire drops this CU's stale
+    // lines; its wait holds the barrier until the invalidate is done, and every wave reads Z and W with plain loads behind it.
+    // Nothing of the chain's is read in front of this point (the queue head is the second stream's own).
+    if (g.chain_word != nullptr) {
+      if (threadIdx.x == 0) {
+        bool ok = false;
+        for (int spin = 0; spin < (1 << 20) && !ok; ++spin) {
+          ok = (int)(__hip_atomic_load(g.chain_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - g.chain_epoch) >= 0;
+          if (!ok) __builtin_amdgcn_s_sleep(8);
+        }
+        if (!ok) g.status[3] = 1;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      __syncthreads();
+    }
+  }
   int bi, bj, iter = 0;
   while (gemm_next_tile(g, s_tile_p, iter, bi, bj)) {
   bool listed_mirror = false;

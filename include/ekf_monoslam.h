@@ -454,6 +454,7 @@ enum ekf_launch_kind {
   EKF_LAUNCH_CHAIN_DIST_GATHER,       /* sharded step, distributed chain: all-gathers of a block step's panel (round 6) */
   EKF_LAUNCH_CHAIN_STEP_FUSED,        /* k_chain_step_fused: factor, panel and trailing update of a block step as ONE launch (one-chunk maps, round 6) */
   EKF_LAUNCH_DOWNDATE_MIRROR_BOUNDS,  /* k_syrk_bf16x6 launches that ran with row bounds for their mirror stores (EKF_SYRK_MIRROR_SKIP = 1, round 7): the launches of an update before its last */
+  EKF_LAUNCH_SOLVE_POLL_CHAIN,        /* triangular-solve launches that waited for the chain in their prologue instead of behind a stream wait (EKF_SOLVE_POLL_CHAIN = 1, round 7): the overlapped chunks 1 .. G-2 of an update whose plan has at most 16 block steps */
   EKF_LAUNCH_KINDS
 };
 int ekf_launch_kinds(void);

@@ -1,5 +1,5 @@
 """Step time at N = 1000 for a list of environment settings: python tools/knob_ab.py "EKF_SIDE2=1" "EKF_SIDE2=1 EKF_CHUNKS=3,9,16" ...
-("" = defaults).  Each setting: build, 10 warm-up steps, 150 timed steps with resident inputs; also checks mu against the default."""
+("" = defaults; a launch-structure knob alone against the defaults: python tools/knob_ab.py "" "EKF_SOLVE_POLL_CHAIN=0").  Each setting: build, 10 warm-up steps, 150 timed steps with resident inputs; also checks mu against the default."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
