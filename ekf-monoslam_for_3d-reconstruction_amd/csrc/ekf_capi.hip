@@ -5279,6 +5279,7 @@ int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense
   if (e == hipSuccess) e = d->timer.create();
   if (e == hipSuccess) e = d->census_timer.create();
   if (e == hipSuccess) e = d->best_timer.create();
+  if (e == hipSuccess) e = d->unique_timer.create();
   auto* h = new ekf_dense{d, {}};
   if (e == hipSuccess) e = h->sgm.timer.create();
   if (e != hipSuccess) {
@@ -5319,7 +5320,7 @@ static void dense_commit(ekf::DenseView& v, const double* K, const double t[3], 
   std::copy(q, q + 4, v.q);
   std::copy(t, t + 3, v.t);
   std::copy(R, R + 9, v.R);
-  v.swept = v.filtered = v.sgm = false;
+  v.swept = v.filtered = v.sgm = v.has_runner = false;
 }
 
 // ---- setting a view, grey (C = 1) or colour (C = 3; DESIGN.md §18.1: the slot keeps the B, G, R image, its grey image is
@@ -5532,23 +5533,37 @@ int ekf_dense_sweep(ekf_dense* h, int ref, const int* src, int n_src, double w_m
   return dense_sweep(h, "ekf_dense_sweep", false, ref, src, n_src, w_min, w_max, planes, radius, trunc);
 }
 
-int ekf_dense_filter(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree) {
+// ekf_dense_filter, and with the uniqueness test ekf_dense_filter_unique: one set of checks and state rules
+static int dense_filter(ekf_dense* h, const char* who, int ref, const int* src, int n_src, double rel_tol, int min_agree,
+                        int uniqueness) {
   if (!h) return EKF_ERR_ARG;
   auto* d = h->impl;
   if (!dense_slots_ok(d, ref, src, n_src) || !std::isfinite(rel_tol) || rel_tol < 0.0 || min_agree < 1 || min_agree > n_src) {
-    d->err = "ekf_dense_filter: ref and 1..8 other, distinct source slots, all set; rel_tol finite and >= 0, min_agree 1..n_src";
+    d->err = std::string(who) + ": ref and 1..8 other, distinct source slots, all set; rel_tol finite and >= 0, min_agree 1..n_src";
+    return EKF_ERR_ARG;
+  }
+  if (uniqueness < 0 || uniqueness > 100) {
+    d->err = std::string(who) + ": uniqueness is 0..100 (per cent)";
     return EKF_ERR_ARG;
   }
   bool swept = d->v[ref].swept;
   for (int i = 0; i < n_src; ++i) swept = swept && d->v[src[i]].swept;
   if (!swept) {
-    d->err = "ekf_dense_filter: a named slot has not been swept since its image or pose last changed";
+    d->err = std::string(who) + ": a named slot has not been swept since its image or pose last changed";
+    return EKF_ERR_STATE;
+  }
+  if (uniqueness > 0 && !d->v[ref].has_runner) {
+    d->err = std::string(who) + ": uniqueness > 0 needs the runner-up map of ref (a sweep of it after ekf_dense_keep_runner_up(h, 1))";
     return EKF_ERR_STATE;
   }
   std::string& err = d->err;
   HIPCHK(hipSetDevice(d->device));
-  HIPCHK(d->filter_points(ref, src, n_src, rel_tol, min_agree, false, false));
+  HIPCHK(d->filter_points(ref, src, n_src, rel_tol, min_agree, false, false, uniqueness));
   return EKF_OK;
+}
+
+int ekf_dense_filter(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree) {
+  return dense_filter(h, "ekf_dense_filter", ref, src, n_src, rel_tol, min_agree, 0);
 }
 
 // slot in range with the asked-for map: EKF_OK, or the code with the message set
@@ -5604,6 +5619,7 @@ int ekf_dense_profile(ekf_dense* h, int enable) {
   h->impl->timer.enable(enable != 0);
   h->impl->census_timer.enable(enable != 0);
   h->impl->best_timer.enable(enable != 0);
+  h->impl->unique_timer.enable(enable != 0);
   h->sgm.timer.enable(enable != 0);
   return EKF_OK;
 }
@@ -5725,6 +5741,42 @@ int ekf_dense_sweep_best(ekf_dense* h, int ref, const int* src, int n_src, int n
 int ekf_dense_get_best_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->impl->best_timer.read(kernel_ms, launches, 0, 4);
+  return EKF_OK;
+}
+
+// ---- runner-up cost and uniqueness test -------------------------------------------------------------------------
+int ekf_dense_keep_runner_up(ekf_dense* h, int enable) {
+  if (!h) return EKF_ERR_ARG;
+  h->impl->keep_runner = enable != 0;
+  return EKF_OK;
+}
+
+int ekf_dense_get_runner_up(ekf_dense* h, int slot, unsigned int* out) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (slot < 0 || slot >= d->max_views || !out) {
+    d->err = "ekf_dense_get_runner_up: slot in 0..max_views-1, out must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set || !v.swept || !v.has_runner) {
+    d->err = "ekf_dense_get_runner_up: the slot has no runner-up map (a sweep after ekf_dense_keep_runner_up(h, 1), with no "
+             "setter or sweep of the slot since)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(hipMemcpy(out, v.runner, d->npix() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_dense_filter_unique(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree, int uniqueness) {
+  return dense_filter(h, "ekf_dense_filter_unique", ref, src, n_src, rel_tol, min_agree, uniqueness);
+}
+
+int ekf_dense_get_unique_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->impl->unique_timer.read(kernel_ms, launches, 0, ekf::kUniqueKinds);
   return EKF_OK;
 }
 

@@ -171,10 +171,20 @@ struct SgmWinnerArgs {
 // One lane per pixel over the aggregate: the winner update of k_plane_sweep (selects), V of the winning plane from the
 // stored counts, and the same write.  The lanes of a wave read D words apart, but a lane's next 31 planes lie in the cache
 // line it has just touched.
-__global__ void __launch_bounds__(256) k_sgm_winner(SgmWinnerArgs a) {
+// RUNNER: the twin that also writes the runner-up of §22, C2 = min { S_k : |k - k*| > 1 } (kRunnerAbsent where D <= 3 leaves
+// no such plane), in the same pass by the four smallest keys of the pixel-wise sweeps; S < 2^24 and k < 1024 make a 34-bit
+// key, a long long.  (A second pass with a masked min, k* being known by then, read the volume twice, and the compiler made
+// of the mask a branch round every load: 0.458 ms beside k_sgm_winner's 0.062 ms at 640 x 480 with 128 planes, §22.5.)
+template <bool RUNNER>
+__device__ __forceinline__ void sgm_winner_body(const SgmWinnerArgs& a, unsigned* runner) {
   const size_t n = (size_t)a.out.W * a.out.H;
   const size_t o = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (o >= n) return;
+  long long top[kRunnerKeys];                                               // RUNNER only
+  if constexpr (RUNNER) {
+#pragma unroll
+    for (int i = 0; i < kRunnerKeys; ++i) top[i] = runner_none<long long>();
+  }
   int prev = 0, bestC = INT_MAX, bestK = -2, bestM = 0, bestP = 0;
 #pragma unroll 8
   for (int k = 0; k < a.out.D; ++k) {
@@ -185,9 +195,14 @@ __global__ void __launch_bounds__(256) k_sgm_winner(SgmWinnerArgs a) {
     bestK = better ? k : bestK;
     bestC = better ? C : bestC;
     prev = C;
+    if constexpr (RUNNER) runner_insert(top, ((long long)C << 10) | k);
   }
   sweep_write_winner(a.out, o, bestK, bestM, bestC, bestP, (int)a.V[(size_t)bestK * n + o]);
+  if constexpr (RUNNER) runner[o] = runner_take(top);
 }
+
+__global__ void __launch_bounds__(256) k_sgm_winner(SgmWinnerArgs a) { sgm_winner_body<false>(a, nullptr); }
+__global__ void __launch_bounds__(256) k_sgm_winner_unique(SgmWinnerArgs a, unsigned* runner) { sgm_winner_body<true>(a, runner); }
 
 // A cost volume as the host getter delivers it: plane-major, D x H x W.
 inline void sgm_volume_to_planes(const unsigned* vol, unsigned* out, size_t npix, int D) {
@@ -222,7 +237,8 @@ struct DenseSgm {
     for (DenseView& v : d.v) v.sgm = false;                                 // the volumes are about to change hands
     if ((e = r.depth.reserve(n)) != hipSuccess || (e = r.plane.reserve(n)) != hipSuccess ||
         (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess ||
-        (e = C.reserve(elems)) != hipSuccess || (e = S.reserve(elems)) != hipSuccess || (e = V.reserve(elems)) != hipSuccess) {
+        (e = C.reserve(elems)) != hipSuccess || (e = S.reserve(elems)) != hipSuccess || (e = V.reserve(elems)) != hipSuccess ||
+        (d.keep_runner && (e = r.runner.reserve(n)) != hipSuccess)) {
       (void)hipGetLastError();                                              // the slot's maps are as they were
       return e;
     }
@@ -234,7 +250,7 @@ struct DenseSgm {
     a.w_min = w_min;
     a.step = (w_max - w_min) / (double)(D_ - 1);
     for (int i = 0; i < n_src; ++i) d.relative(r, d.v[src[i]], a.s[i]);
-    r.swept = r.filtered = false;
+    r.swept = r.filtered = r.has_runner = false;
     const SweepVolume vol{C, V};
     const dim3 grid((unsigned)((d.W + kDenseTW - 1) / kDenseTW), (unsigned)((d.H + kDenseTH - 1) / kDenseTH));
     // the census volume (§20) counts under the census profile, its directions and winner below like any other
@@ -264,9 +280,14 @@ struct DenseSgm {
       if (e != hipSuccess) return e;
     }
     const SgmWinnerArgs w{S, V, a};
-    if ((e = timer.run(9, [&] { k_sgm_winner<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(w); })) != hipSuccess) return e;
+    unsigned* const ru = r.runner;
+    const unsigned wg_w = (unsigned)((n + 255) / 256);
+    e = d.keep_runner ? d.unique_timer.run(4, [&] { k_sgm_winner_unique<<<wg_w, 256, 0, nullptr>>>(w, ru); })   // §22
+                      : timer.run(9, [&] { k_sgm_winner<<<wg_w, 256, 0, nullptr>>>(w); });
+    if (e != hipSuccess) return e;
     D = D_;
     r.swept = r.sgm = true;
+    r.has_runner = d.keep_runner;
     return hipSuccess;
   }
 };

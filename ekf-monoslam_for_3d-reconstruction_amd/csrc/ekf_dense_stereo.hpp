@@ -11,6 +11,7 @@
 #include <climits>
 #include <cmath>
 #include <cstddef>
+#include <limits>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -139,6 +140,41 @@ __global__ void __launch_bounds__(256) k_census(CensusArgs a) {
   }
 }
 
+// ---- runner-up cost -----------------------------------------------------------------------------------------
+// C2 = min { C_k : |k - k*| > 1 }, found in the one pass over the planes, before k* is known: a plane that beats the runner-up
+// (cheaper, or as cheap with a smaller index) is k* or one of its two neighbours, so the runner-up is among the four smallest
+// pairs (C, k).  C <= 81 * 8 * 255 < 2^18 and k < 1024: key = C << 10 | k < 2^28 orders them as the pairs (an int; the
+// aggregate of §19, S < 2^24, takes a long long: k_sgm_winner_unique).  Four keys per pixel, sorted, the largest value of the
+// type where there is no plane yet; runner_insert is best_insert's min / max chain (§21.2), every index a compile-time
+// constant; runner_take reads the winner's plane from the smallest key and takes the first key two planes away.
+constexpr int kRunnerKeys = 4;
+constexpr unsigned kRunnerAbsent = 0xffffffffu;   // no plane with |k - k*| > 1 (D <= 3 only)
+static_assert(kDenseMaxPlanes <= 1024 && 81 * kDenseMaxSrc * 255 < (1 << 18), "a (cost, plane) pair is a 28-bit key");
+template <typename Key>
+constexpr Key runner_none() { return std::numeric_limits<Key>::max(); }     // no plane: more than any key
+
+template <typename Key>
+__device__ __forceinline__ void runner_insert(Key (&t)[kRunnerKeys], Key key) {
+#pragma unroll
+  for (int i = 0; i < kRunnerKeys; ++i) {
+    const bool less = key < t[i];
+    const Key lo = less ? key : t[i];
+    key = less ? t[i] : key;
+    t[i] = lo;
+  }
+}
+template <typename Key>
+__device__ __forceinline__ unsigned runner_take(const Key (&t)[kRunnerKeys]) {
+  const int ks = (int)(t[0] & 1023);                                        // the winner of §15.1: least cost, then least k
+  unsigned c2 = kRunnerAbsent;
+#pragma unroll
+  for (int i = kRunnerKeys - 1; i >= 1; --i) {                               // the smallest such key is assigned last
+    const int d = (int)(t[i] & 1023) - ks;
+    c2 = (t[i] != runner_none<Key>() && (d > 1 || d < -1)) ? (unsigned)(t[i] >> 10) : c2;
+  }
+  return c2;
+}
+
 // The cost c_v of one halo pixel (ray (hx, hy), reference value or descriptor `ref`) on the plane of depth z in the source
 // view s: §15.1's warp and validity test, then the truncated absolute difference of the 5-bit bilinear sample or (CENSUS, §20)
 // the truncated Hamming distance at the nearest pixel.  An invalid warp costs trunc; a valid one adds 1 to nv.  Written once
@@ -183,9 +219,11 @@ __device__ __forceinline__ int sweep_view_cost(const SweepArgs& a, const DenseSr
 // census descriptors, not the absolute grey difference.  A halo pixel's register value is then its 64-bit descriptor, and
 // per source the four byte gathers and the blend become one 8-byte load at the nearest pixel and a popcount.  The warp, the
 // window, the winner and the volume stores are the same lines.
-template <bool VOLUME, bool CENSUS = false>
-__device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const SweepVolume& vol) {
+// RUNNER (§22; a third one): the four smallest keys of each owned pixel ride along and its runner-up goes to `runner`, W H words.
+template <bool VOLUME, bool CENSUS = false, bool RUNNER = false>
+__device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const SweepVolume& vol, unsigned* runner = nullptr) {
 #pragma clang fp contract(off)
+  static_assert(!(VOLUME && RUNNER), "the runner-up of an aggregated sweep is k_sgm_winner_unique's");
   __shared__ int s_c[kDenseHH][kDenseHW + 1];
   __shared__ int s_h[kDenseHH][kDenseTW + 1];
   const int tid = threadIdx.x;
@@ -224,6 +262,13 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
   }
   const size_t plane_elems = (size_t)W * H;
   int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
+  int top[2][kRunnerKeys];                                                  // RUNNER only
+  if constexpr (RUNNER) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < kRunnerKeys; ++i) top[j][i] = runner_none<int>();
+  }
   for (int k = 0; k < a.D; ++k) {
     const double z = 1.0 / (a.w_min + (double)k * a.step);
 #pragma unroll
@@ -270,6 +315,7 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
       bestK[j] = better ? k : bestK[j];
       bestC[j] = better ? C : bestC[j];
       prevC[j] = C;
+      if constexpr (RUNNER) runner_insert(top[j], (C << 10) | k);
     }
   }
   if constexpr (VOLUME) return;
@@ -278,12 +324,20 @@ __device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const Sweep
     const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
     if (X >= W || Y >= H) continue;
     sweep_write_winner(a, (size_t)Y * W + X, bestK[j], bestM[j], bestC[j], bestP[j], bestV[j]);
+    if constexpr (RUNNER) runner[(size_t)Y * W + X] = runner_take(top[j]);
   }
 }
 
 __global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) { plane_sweep_body<false>(a, SweepVolume{nullptr, nullptr}); }
 __global__ void __launch_bounds__(256) k_plane_sweep_census(SweepArgs a) {
   plane_sweep_body<false, true>(a, SweepVolume{nullptr, nullptr});
+}
+// ... and their twins that also write the runner-up (§22)
+__global__ void __launch_bounds__(256) k_plane_sweep_unique(SweepArgs a, unsigned* runner) {
+  plane_sweep_body<false, false, true>(a, SweepVolume{nullptr, nullptr}, runner);
+}
+__global__ void __launch_bounds__(256) k_plane_sweep_census_unique(SweepArgs a, unsigned* runner) {
+  plane_sweep_body<false, true, true>(a, SweepVolume{nullptr, nullptr}, runner);
 }
 
 // ---- best-K source selection ------------------------------------------------------------------------------
@@ -317,9 +371,10 @@ __device__ __forceinline__ int best_take(const int (&s)[kDenseMaxSrc], int n_bes
   return sum;
 }
 
-template <bool VOLUME, bool CENSUS>
-__device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const SweepVolume& vol, int n_best) {
+template <bool VOLUME, bool CENSUS, bool RUNNER = false>
+__device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const SweepVolume& vol, int n_best, unsigned* runner = nullptr) {
 #pragma clang fp contract(off)
+  static_assert(!(VOLUME && RUNNER), "the runner-up of an aggregated sweep is k_sgm_winner_unique's");
   __shared__ int s_c[kBestPairs][kDenseHH][kDenseHW + 1];
   __shared__ int s_h[kBestPairs][kDenseHH][kDenseTW + 1];
   const int tid = threadIdx.x;
@@ -370,6 +425,13 @@ __device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const 
   }
   const size_t plane_elems = (size_t)W * H;
   int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
+  int top[2][kRunnerKeys];                                                  // RUNNER only
+  if constexpr (RUNNER) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < kRunnerKeys; ++i) top[j][i] = runner_none<int>();
+  }
   for (int k = 0; k < a.D; ++k) {
     const double z = 1.0 / (a.w_min + (double)k * a.step);
 #pragma unroll
@@ -438,6 +500,7 @@ __device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const 
       bestK[j] = better ? k : bestK[j];
       bestC[j] = better ? C : bestC[j];
       prevC[j] = C;
+      if constexpr (RUNNER) runner_insert(top[j], (C << 10) | k);
     }
   }
   if constexpr (VOLUME) return;
@@ -446,6 +509,7 @@ __device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const 
     const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
     if (X >= W || Y >= H) continue;
     sweep_write_winner(a, (size_t)Y * W + X, bestK[j], bestM[j], bestC[j], bestP[j], bestV[j]);
+    if constexpr (RUNNER) runner[(size_t)Y * W + X] = runner_take(top[j]);
   }
 }
 
@@ -454,6 +518,12 @@ __global__ void __launch_bounds__(256) k_plane_sweep_best(SweepArgs a, int n_bes
 }
 __global__ void __launch_bounds__(256) k_plane_sweep_best_census(SweepArgs a, int n_best) {
   plane_sweep_best_body<false, true>(a, SweepVolume{nullptr, nullptr}, n_best);
+}
+__global__ void __launch_bounds__(256) k_plane_sweep_best_unique(SweepArgs a, int n_best, unsigned* runner) {
+  plane_sweep_best_body<false, false, true>(a, SweepVolume{nullptr, nullptr}, n_best, runner);
+}
+__global__ void __launch_bounds__(256) k_plane_sweep_best_census_unique(SweepArgs a, int n_best, unsigned* runner) {
+  plane_sweep_best_body<false, true, true>(a, SweepVolume{nullptr, nullptr}, n_best, runner);
 }
 __global__ void __launch_bounds__(256) k_sweep_volume_best(SweepArgs a, SweepVolume vol, int n_best) {
   plane_sweep_best_body<true, false>(a, vol, n_best);
@@ -475,8 +545,18 @@ struct FilterArgs {
   DenseSrc s[kDenseMaxSrc];
 };
 
+// The uniqueness test of §22.1 on the reference view's own pixel, in 64-bit integers: passed iff there is no runner-up or
+// (C2 - C1) 100 >= u C2.  u = 0 passes everything, a flat curve (C2 = C1) fails every u > 0: also the curve that is 0 on
+// every plane, the untextured patch itself, which the inequality alone would pass as 0 >= 0.
+__device__ __forceinline__ bool unique_pass(unsigned c1, unsigned c2, int u) {
+  const bool margin = ((long long)c2 - (long long)c1) * 100ll >= (long long)u * (long long)c2;
+  return c2 == kRunnerAbsent || (margin && (u == 0 || c2 != c1));
+}
+
 // One lane per pixel: the geometric filter against the swept depths of the sources, and / or the back-projection.
-__global__ void __launch_bounds__(256) k_depth_filter_points(FilterArgs a) {
+// UNIQUE (§22): a pixel is kept iff it was kept before and unique_pass(cost, runner, uniqueness) of the reference's maps.
+template <bool UNIQUE>
+__device__ __forceinline__ void depth_filter_points_body(FilterArgs a, const unsigned* cost, const unsigned* runner, int uniqueness) {
 #pragma clang fp contract(off)
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned npix = (unsigned)a.W * (unsigned)a.H;
@@ -507,6 +587,7 @@ __global__ void __launch_bounds__(256) k_depth_filter_points(FilterArgs a) {
     }
     keep = agree >= a.min_agree;
   }
+  if constexpr (UNIQUE) keep = keep && unique_pass(cost[i], runner[i], uniqueness);
   if (a.out_depth) {
     a.out_depth[i] = keep ? zf : 0.f;
     a.out_plane[i] = keep ? a.plane[i] : -1;
@@ -518,6 +599,11 @@ __global__ void __launch_bounds__(256) k_depth_filter_points(FilterArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = keep ? a.R[3 * c] * p0 + a.R[3 * c + 1] * p1 + a.R[3 * c + 2] * p2 + a.t[c] : nan;
   }
+}
+
+__global__ void __launch_bounds__(256) k_depth_filter_points(FilterArgs a) { depth_filter_points_body<false>(a, nullptr, nullptr, 0); }
+__global__ void __launch_bounds__(256) k_depth_filter_unique(FilterArgs a, const unsigned* cost, const unsigned* runner, int uniqueness) {
+  depth_filter_points_body<true>(a, cost, runner, uniqueness);
 }
 
 // ---- colour views --------------------------------------------------------------------------------------------
@@ -564,6 +650,10 @@ inline bool dense_pose(const double* p, double t[3], double R[9], double q[4]) {
 }
 
 #ifndef EKF_KERNELS_ONLY
+// timed kinds of §22: k_plane_sweep_unique, k_plane_sweep_census_unique, k_plane_sweep_best_unique,
+// k_plane_sweep_best_census_unique, k_sgm_winner_unique, k_depth_filter_unique
+constexpr int kUniqueKinds = 6;
+
 struct DenseView {
   DevBuf<unsigned char> img;
   DevBuf<unsigned char> bgr;          // W x H x 3, tight: the colour image `img` was derived from (colour = true only)
@@ -572,6 +662,7 @@ struct DenseView {
   DevBuf<unsigned> cost;
   DevBuf<unsigned char> nviews;
   DevBuf<unsigned long long> census;  // W x H descriptors of `img` (§20), allocated by the slot's first census sweep or getter
+  DevBuf<unsigned> runner;            // W x H runner-up costs (§22), allocated by the slot's first sweep that keeps them
   double K[4] = {}, t[3] = {}, R[9] = {}, q[4] = {};
   bool set = false;                   // an image, K and a pose
   bool colour = false;                // `bgr` holds the slot's image in colour (§18): every grey setter drops it
@@ -579,6 +670,7 @@ struct DenseView {
   bool filtered = false;              // filtered since it was last swept
   bool sgm = false;                   // the handle's cost volumes are those of this slot's maps (§19: DenseSgm)
   bool census_valid = false;          // `census` is that of `img`: every setter of the image clears it, a new pose does not
+  bool has_runner = false;            // `runner` belongs to the slot's swept maps (§22): cleared wherever `swept` is
 };
 
 // Host side of one handle (`ekf_dense`).  Everything runs on the default stream of the handle's device, as the rectified
@@ -591,6 +683,8 @@ struct DenseStereo {
   KernelTimer<2> timer;               // k_plane_sweep, k_depth_filter_points
   KernelTimer<3> census_timer;        // k_census, k_plane_sweep_census, k_sweep_volume_census (§20)
   KernelTimer<4> best_timer;          // k_plane_sweep_best, .._best_census, k_sweep_volume_best, .._best_census (§21)
+  KernelTimer<kUniqueKinds> unique_timer;   // the twins of §22, in the order of kUniqueKinds' comment
+  bool keep_runner = false;           // ekf_dense_keep_runner_up: every sweep launches its twin and records the runner-up
 
   size_t npix() const { return (size_t)W * H; }
   const unsigned char* colour_of(int slot) const { return v[slot].colour ? (const unsigned char*)v[slot].bgr : nullptr; }
@@ -655,7 +749,8 @@ struct DenseStereo {
     hipError_t e;
     const size_t n = npix();
     if ((e = r.depth.reserve(n)) != hipSuccess || (e = r.plane.reserve(n)) != hipSuccess ||
-        (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess)
+        (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess ||
+        (keep_runner && (e = r.runner.reserve(n)) != hipSuccess))
       return e;
     if (census && ((e = census_reserve(ref, src, n_src)) != hipSuccess || (e = census_update(ref, src, n_src)) != hipSuccess)) return e;
     SweepArgs a{};
@@ -665,9 +760,16 @@ struct DenseStereo {
     a.w_min = w_min;
     a.step = (w_max - w_min) / (double)(D - 1);
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
-    r.swept = r.filtered = r.sgm = false;
+    r.swept = r.filtered = r.sgm = r.has_runner = false;
     const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
-    if (n_best > 0)
+    unsigned* const ru = r.runner;
+    if (keep_runner && n_best > 0)                                          // the twins of §22: the same four maps, and `runner`
+      e = census ? unique_timer.run(3, [&] { k_plane_sweep_best_census_unique<<<grid, 256, 0, nullptr>>>(a, n_best, ru); })
+                 : unique_timer.run(2, [&] { k_plane_sweep_best_unique<<<grid, 256, 0, nullptr>>>(a, n_best, ru); });
+    else if (keep_runner)
+      e = census ? unique_timer.run(1, [&] { k_plane_sweep_census_unique<<<grid, 256, 0, nullptr>>>(a, ru); })
+                 : unique_timer.run(0, [&] { k_plane_sweep_unique<<<grid, 256, 0, nullptr>>>(a, ru); });
+    else if (n_best > 0)
       e = census ? best_timer.run(1, [&] { k_plane_sweep_best_census<<<grid, 256, 0, nullptr>>>(a, n_best); })
                  : best_timer.run(0, [&] { k_plane_sweep_best<<<grid, 256, 0, nullptr>>>(a, n_best); });
     else
@@ -675,12 +777,15 @@ struct DenseStereo {
                  : timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); });
     if (e != hipSuccess) return e;
     r.swept = true;
+    r.has_runner = keep_runner;
     return hipSuccess;
   }
 
   // The one launch of k_depth_filter_points.  n_src > 0: the filter of view `ref` (swept -> filtered); xyz: the points of
-  // its swept or filtered map, into d_xyz.
-  hipError_t filter_points(int ref, const int* src, int n_src, double rel_tol, int min_agree, bool from_filtered, bool xyz) {
+  // its swept or filtered map, into d_xyz.  uniqueness > 0 (§22; with n_src > 0, on a slot with a runner-up map): the one
+  // launch is k_depth_filter_unique's.
+  hipError_t filter_points(int ref, const int* src, int n_src, double rel_tol, int min_agree, bool from_filtered, bool xyz,
+                           int uniqueness = 0) {
     DenseView& r = v[ref];
     hipError_t e;
     const size_t n = npix();
@@ -702,7 +807,11 @@ struct DenseStereo {
     for (int i = 0; i < 9; ++i) a.R[i] = r.R[i];
     for (int i = 0; i < 3; ++i) a.t[i] = r.t[i];
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
-    if ((e = timer.run(1, [&] { k_depth_filter_points<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(a); })) != hipSuccess) return e;
+    const unsigned wg = (unsigned)((n + 255) / 256);
+    const unsigned *c1 = r.cost, *c2 = r.runner;
+    e = uniqueness > 0 ? unique_timer.run(5, [&] { k_depth_filter_unique<<<wg, 256, 0, nullptr>>>(a, c1, c2, uniqueness); })
+                       : timer.run(1, [&] { k_depth_filter_points<<<wg, 256, 0, nullptr>>>(a); });
+    if (e != hipSuccess) return e;
     if (n_src > 0) r.filtered = true;
     return hipSuccess;
   }

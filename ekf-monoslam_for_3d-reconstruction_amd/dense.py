@@ -16,6 +16,8 @@ from . import capi, formats
 from .capi import ptr as _ptr
 
 MAX_VIEWS, MAX_SOURCES = 16, 8
+UNIQUE_KERNELS = ("k_plane_sweep_unique", "k_plane_sweep_census_unique", "k_plane_sweep_best_unique",
+                  "k_plane_sweep_best_census_unique", "k_sgm_winner_unique", "k_depth_filter_unique")
 
 
 @dataclass
@@ -30,6 +32,7 @@ class DepthMap:
     cost: np.ndarray               # (H, W) uint32
     views: np.ndarray              # (H, W) uint8
     points: np.ndarray             # (H, W, 3) float64 of the filtered map, NaN where there is no depth
+    runner_up: Optional[np.ndarray] = None    # (H, W) uint32, 0xFFFFFFFF = absent (§22); None when not recorded
 
 
 class DenseStereo(capi.Handle):
@@ -152,9 +155,26 @@ class DenseStereo(capi.Handle):
         self._check(self._lib.ekf_dense_get_census(self._h, int(slot), _ptr(out)))
         return out
 
-    def filter(self, ref: int, sources: Sequence[int], rel_tol: float = 0.01, min_agree: int = 1):
+    def filter(self, ref: int, sources: Sequence[int], rel_tol: float = 0.01, min_agree: int = 1, uniqueness: int = 0):
+        """``uniqueness``: 0 .. 100 per cent.  0 is the geometric filter alone; u > 0 also drops the pixels of ``ref`` whose
+        runner-up cost C2 has (C2 - cost) 100 < u C2 and needs ``ref`` swept under ``keep_runner_up()``."""
         src = np.ascontiguousarray(sources, np.int32).reshape(-1)
-        self._check(self._lib.ekf_dense_filter(self._h, int(ref), _ptr(src), len(src), float(rel_tol), int(min_agree)))
+        if uniqueness == 0:
+            self._check(self._lib.ekf_dense_filter(self._h, int(ref), _ptr(src), len(src), float(rel_tol), int(min_agree)))
+            return
+        self._check(self._lib.ekf_dense_filter_unique(self._h, int(ref), _ptr(src), len(src), float(rel_tol), int(min_agree),
+                                                      int(uniqueness)))
+
+    # ---- the runner-up cost (DESIGN.md §22) ----
+    def keep_runner_up(self, on: bool = True):
+        """While on, every sweep also records its slot's runner-up cost, the least cost at least two planes from the winner."""
+        self._check(self._lib.ekf_dense_keep_runner_up(self._h, 1 if on else 0))
+
+    def runner_up(self, slot: int) -> np.ndarray:
+        """(height, width) uint32 of a slot swept under ``keep_runner_up()``; 0xFFFFFFFF where no plane is two away."""
+        out = np.zeros(self.shape, np.uint32)
+        self._check(self._lib.ekf_dense_get_runner_up(self._h, int(slot), _ptr(out)))
+        return out
 
     # ---- results ----
     def depth(self, slot: int, filtered: bool = False) -> dict:
@@ -215,6 +235,13 @@ class DenseStereo(capi.Handle):
         self._check(self._lib.ekf_dense_get_best_profile(self._h, _ptr(ms), _ptr(cnt)))
         names = ("k_plane_sweep_best", "k_plane_sweep_best_census", "k_sweep_volume_best", "k_sweep_volume_best_census")
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(names)}
+
+    def get_unique_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the six kernels of the runner-up cost and the uniqueness test (§22)
+        since the last ``profile()``."""
+        ms, cnt = np.zeros(len(UNIQUE_KERNELS), np.float64), np.zeros(len(UNIQUE_KERNELS), np.int64)
+        self._check(self._lib.ekf_dense_get_unique_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(UNIQUE_KERNELS)}
 
 
 def _cost_entry(lib, cost, name):
@@ -290,7 +317,7 @@ def neighbours_of(i: int, n: int, neighbours: int):
 def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, neighbours: int = 2, w_min: float = 0.05,
                               w_max: float = 2.0, planes: int = 64, radius: int = 2, trunc: int = 40, rel_tol: float = 0.01,
                               min_agree: int = 1, device: int = 0, sgm=None, cost: str = "ad",
-                              best: Optional[int] = None):
+                              best: Optional[int] = None, uniqueness: int = 0):
     """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
     order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
     The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
@@ -298,7 +325,11 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
     ``sgm``: ``None`` sweeps with ``sweep``; ``True`` or a dict of ``p1`` / ``p2`` / ``paths`` with ``sweep_sgm`` (§19).
     ``cost``: ``"ad"`` or ``"census"`` (§20), the matching cost of either sweep.
     ``best``: ``None``, or the number of cheapest sources either sweep keeps per pixel and plane (§21); a key frame with fewer
-    sources than that keeps them all, as with ``min_agree``."""
+    sources than that keeps them all, as with ``min_agree``.
+    ``uniqueness``: 0, or the per cent of the uniqueness test every map's filter also applies (§22); the sweeps then record
+    their runner-up costs, which each ``DepthMap`` carries."""
+    if not 0 <= int(uniqueness) <= 100:
+        raise ValueError("uniqueness is 0 .. 100")
     if best is not None and int(best) < 1:
         raise ValueError("best is None or an int >= 1")
     if cost not in ("ad", "census"):
@@ -317,6 +348,8 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
     loaded = swept = 0                                             # key frames [0, loaded) are in their slots, [0, swept) swept
     out = []
     try:
+        if uniqueness:
+            ds.keep_runner_up(True)
         for i in range(n):
             while loaded < min(n, i + 2 * neighbours + 1):
                 ds.set_view(loaded % ring, images[loaded], K, poses[loaded])
@@ -331,10 +364,11 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
                                  **({} if sgm is True else sgm))
                 swept += 1
             src = neighbours_of(i, n, neighbours)
-            ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)))
+            ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)), int(uniqueness))
             raw, flt = ds.depth(i % ring, False), ds.depth(i % ring, True)
             out.append(DepthMap(ids[i], poses[i].copy(), tuple(ids[j] for j in src), flt["depth"], flt["plane"], raw["depth"],
-                                raw["cost"], raw["views"], ds.points(i % ring, True)))
+                                raw["cost"], raw["views"], ds.points(i % ring, True),
+                                ds.runner_up(i % ring) if uniqueness else None))
     finally:
         ds.close()
     return out

@@ -308,7 +308,8 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     ``sgm=True`` (or a dict of ``p1`` / ``p2`` / ``paths``) among ``sweep_kwargs`` sweeps with semi-global aggregation
     (DESIGN.md §19), for recordings with textureless surfaces; ``cost="census"`` sweeps with the census matching cost
     (§20), for recordings whose key frames differ in exposure or gain; ``best=n`` keeps the n cheapest sources per pixel and
-    plane (§21), for neighbours that do not all see every pixel of a key frame."""
+    plane (§21), for neighbours that do not all see every pixel of a key frame; ``uniqueness=u`` (per cent) also drops the
+    pixels whose runner-up cost is within u % of the winner's (§22), for recordings with untextured surfaces."""
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
@@ -379,8 +380,8 @@ def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Opti
                     **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
-    frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…`` and ``best=…``
-    reach the sweep as they do through ``mesh_from_recording``."""
+    frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``
+    and ``uniqueness=…`` reach the sweep and the filter as they do through ``mesh_from_recording``."""
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)

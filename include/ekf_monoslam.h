@@ -1000,6 +1000,38 @@ int ekf_dense_sweep_best(ekf_dense* h, int ref, const int* src, int n_src, int n
                          int planes, int radius, int trunc, int census, int paths, int p1, int p2);
 int ekf_dense_get_best_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
+/* ---- runner-up cost and uniqueness test for the dense sweeps ------------------------------------------
+ * The sweeps above keep the plane of least cost and forget how close the other planes came; only the geometric filter
+ * rejects a depth, and where the reference image has no texture every view makes the same arbitrary choice and the views
+ * agree.  Opt-in, a sweep also records the runner-up: for a pixel with cost curve C_0 .. C_{D-1} and winner k* (the smallest
+ * k of least cost),
+ *   C2 = min { C_k : |k - k*| > 1 },   0xFFFFFFFF ("absent") where no such plane exists (planes <= 3 only),
+ * on the curve the sweep takes its winner from: the summed window cost, the census cost, the best-K cost, or the aggregate S
+ * of ekf_dense_sweep_sgm.  C2 is defined for every pixel, whatever views says.  The uniqueness test with u in 0 .. 100 (per
+ * cent) passes a pixel iff C2 is absent or (C2 - C1) 100 >= u C2 in 64-bit integers, C1 being the pixel's cost: u = 0 passes
+ * everything, a flat curve (C2 = C1) fails every u > 0, the curve that is 0 on every plane included (where the inequality
+ * alone reads 0 >= 0).  tests/unique_oracle.py restates it.  No default, result, launch,
+ * profile count or prototype of the calls above changes while the switch is off; ekf_abi_version() stays 6 (additions only).
+ *  - ekf_dense_keep_runner_up: a switch of the handle, off at creation.  While it is on, every sweep entry point above
+ *    (plain, census, best, sgm, sgm_census) launches the twin of its winner kernel, which writes the same four maps byte for
+ *    byte and the slot's runner-up map; while it is off, a sweep launches exactly what it did and drops the slot's runner-up
+ *    map.  A setter or a sweep of a slot takes its runner-up map together with its swept maps;
+ *  - ekf_dense_get_runner_up: the width x height runner-up costs of a slot.  EKF_ERR_STATE if the slot's last sweep did not
+ *    record them or the slot was invalidated since;
+ *  - ekf_dense_filter_unique: ekf_dense_filter, with all of its argument and state rules, keeping a pixel iff it passed
+ *    before AND the reference view's own pixel passes the uniqueness test; the sources' swept depths are read as before.
+ *    uniqueness outside 0 .. 100: EKF_ERR_ARG before the device is touched.  uniqueness > 0 on a reference slot without a
+ *    runner-up map: EKF_ERR_STATE.  uniqueness = 0 needs no map, launches k_depth_filter_points and equals ekf_dense_filter
+ *    byte for byte;
+ *  - ekf_dense_get_unique_profile: HIP-event milliseconds and launch counts of 6 kinds since the last ekf_dense_profile:
+ *    k_plane_sweep_unique ([0]), k_plane_sweep_census_unique ([1]), k_plane_sweep_best_unique ([2]),
+ *    k_plane_sweep_best_census_unique ([3]), k_sgm_winner_unique ([4]), k_depth_filter_unique ([5]).  A twin counts here and
+ *    not where the kernel it stands in for does; every other kernel of a sweep keeps counting where it did. */
+int ekf_dense_keep_runner_up(ekf_dense* h, int enable);
+int ekf_dense_get_runner_up(ekf_dense* h, int slot, unsigned int* out);
+int ekf_dense_filter_unique(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree, int uniqueness);
+int ekf_dense_get_unique_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

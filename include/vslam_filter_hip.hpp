@@ -561,6 +561,22 @@ class DenseStereoHip {
   void filter(int ref, const std::vector<int>& src, double rel_tol = 0.01, int min_agree = 1) {
     check(ekf_dense_filter(d_, ref, src.data(), (int)src.size(), rel_tol, min_agree));
   }
+  // the runner-up cost and the uniqueness test.  keepRunnerUp: while on, every sweep above also records
+  // its slot's runner-up cost, the least cost at least two planes from the winner (0xFFFFFFFF: no such plane); runnerUp reads
+  // it.  filterUnique: filter, which also drops the pixels of ref with (C2 - cost) 100 < uniqueness C2; uniqueness is 0 .. 100
+  // per cent, 0 being filter itself, and more than 0 needs ref swept while keepRunnerUp was on
+  void keepRunnerUp(bool on = true) { check(ekf_dense_keep_runner_up(d_, on ? 1 : 0)); }
+  std::vector<unsigned int> runnerUp(int slot) {
+    std::vector<unsigned int> r(pixels());
+    check(ekf_dense_get_runner_up(d_, slot, r.data()));
+    return r;
+  }
+  void filterUnique(int ref, const std::vector<int>& src, int uniqueness, double rel_tol = 0.01, int min_agree = 1) {
+    check(ekf_dense_filter_unique(d_, ref, src.data(), (int)src.size(), rel_tol, min_agree, uniqueness));
+  }
+  // HIP-event milliseconds and launch counts of k_plane_sweep_unique ([0]), k_plane_sweep_census_unique ([1]),
+  // k_plane_sweep_best_unique ([2]), k_plane_sweep_best_census_unique ([3]), k_sgm_winner_unique ([4]), k_depth_filter_unique ([5])
+  void getUniqueProfile(double kernel_ms[6], long long launches[6]) { check(ekf_dense_get_unique_profile(d_, kernel_ms, launches)); }
   Depth depth(int slot, bool filtered = false) {
     Depth r;
     r.depth.resize(pixels()); r.plane.resize(pixels()); r.cost.resize(pixels()); r.views.resize(pixels());
