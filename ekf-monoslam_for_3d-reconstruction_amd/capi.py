@@ -221,6 +221,10 @@ _PROTOS = {
     "ekf_dense_get_runner_up": (C.c_int, [_P, C.c_int, _P]),
     "ekf_dense_filter_unique": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int]),
     "ekf_dense_get_unique_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_dense_filter_speckle": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "ekf_dense_get_segments": (C.c_int, [_P, C.c_int, _P, _P]),
+    "ekf_dense_speckle_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "ekf_dense_get_speckle_profile": (C.c_int, [_P, _P, _P]),
     "ekf_colour_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "ekf_colour_has": (C.c_int, [_P]),
     "ekf_colour_integrate_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -33,6 +33,7 @@
 #include "ekf_keyframe.hpp"
 #include "ekf_dense_stereo.hpp"
 #include "ekf_dense_sgm.hpp"
+#include "ekf_dense_speckle.hpp"
 #include "ekf_fusion.hpp"
 #include "ekf_raycast.hpp"
 
@@ -5259,6 +5260,7 @@ int ekf_keyframe_reset(ekf_keyframe* s) {
 struct ekf_dense {
   ekf::DenseStereo* impl;
   ekf::DenseSgm sgm;                  // the cost volumes of the semi-global sweep
+  ekf::DenseSpeckle speckle;          // the segment planes of the speckle filter
 };
 
 int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense** out) {
@@ -5280,8 +5282,9 @@ int ekf_dense_create(int width, int height, int max_views, int device, ekf_dense
   if (e == hipSuccess) e = d->census_timer.create();
   if (e == hipSuccess) e = d->best_timer.create();
   if (e == hipSuccess) e = d->unique_timer.create();
-  auto* h = new ekf_dense{d, {}};
+  auto* h = new ekf_dense{d, {}, {}};
   if (e == hipSuccess) e = h->sgm.timer.create();
+  if (e == hipSuccess) e = h->speckle.timer.create();
   if (e != hipSuccess) {
     ekf::g_create_error = std::string("ekf_dense_create: ") + hipGetErrorString(e);
     delete h;
@@ -5320,7 +5323,7 @@ static void dense_commit(ekf::DenseView& v, const double* K, const double t[3], 
   std::copy(q, q + 4, v.q);
   std::copy(t, t + 3, v.t);
   std::copy(R, R + 9, v.R);
-  v.swept = v.filtered = v.sgm = v.has_runner = false;
+  v.swept = v.filtered = v.sgm = v.has_runner = v.seg = false;
 }
 
 // ---- setting a view, grey (C = 1) or colour (C = 3; DESIGN.md §18.1: the slot keeps the B, G, R image, its grey image is
@@ -5621,6 +5624,7 @@ int ekf_dense_profile(ekf_dense* h, int enable) {
   h->impl->best_timer.enable(enable != 0);
   h->impl->unique_timer.enable(enable != 0);
   h->sgm.timer.enable(enable != 0);
+  h->speckle.timer.enable(enable != 0);
   return EKF_OK;
 }
 
@@ -5777,6 +5781,84 @@ int ekf_dense_filter_unique(ekf_dense* h, int ref, const int* src, int n_src, do
 int ekf_dense_get_unique_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->impl->unique_timer.read(kernel_ms, launches, 0, ekf::kUniqueKinds);
+  return EKF_OK;
+}
+
+// ---- speckle filter: connected segments of a depth map ----------------------------------------------------------
+// min_size and max_diff in their ranges: EKF_OK, or EKF_ERR_ARG with the message set
+static int speckle_args_ok(ekf::DenseStereo* d, const char* who, int min_size, int max_diff) {
+  if (min_size < 1 || min_size > ekf::kSpeckleMaxSize || max_diff < 0 || max_diff > ekf::kSpeckleMaxDiff) {
+    d->err = std::string(who) + ": min_size is 1..2^26, max_diff 0..1023";
+    return EKF_ERR_ARG;
+  }
+  return EKF_OK;
+}
+
+int ekf_dense_filter_speckle(ekf_dense* h, int slot, int min_size, int max_diff) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  int rc = speckle_args_ok(d, "ekf_dense_filter_speckle", min_size, max_diff);
+  if (rc == EKF_OK) rc = dense_map_ok(d, "ekf_dense_filter_speckle", slot, 1);
+  if (rc != EKF_OK) return rc;
+  std::string& err = d->err;
+  ekf::DenseView& v = d->v[slot];
+  for (ekf::DenseView& o : d->v) o.seg = false;                             // the planes are about to change hands
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(h->speckle.run(d->W, d->H, v.fdepth, v.fplane, min_size, max_diff));
+  v.seg = true;
+  return EKF_OK;
+}
+
+int ekf_dense_get_segments(ekf_dense* h, int slot, unsigned int* label, unsigned int* size) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (slot < 0 || slot >= d->max_views) {
+    d->err = "ekf_dense_get_segments: slot in 0..max_views-1";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set || !v.swept || !v.filtered || !v.seg) {
+    d->err = "ekf_dense_get_segments: the segments are not those of this slot (the handle's last ekf_dense_filter_speckle, with "
+             "no setter, sweep or filter of the slot and no ekf_dense_speckle_host since)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = d->err;
+  HIPCHK(hipSetDevice(d->device));
+  if (label) HIPCHK(hipMemcpy(label, h->speckle.R, d->npix() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (size) HIPCHK(hipMemcpy(size, h->speckle.L, d->npix() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_dense_speckle_host(ekf_dense* h, float* depth, int* plane, int min_size, int max_diff, unsigned int* label,
+                           unsigned int* size) {
+  if (!h) return EKF_ERR_ARG;
+  auto* d = h->impl;
+  if (!depth || !plane) {
+    d->err = "ekf_dense_speckle_host: depth and plane must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const int rc = speckle_args_ok(d, "ekf_dense_speckle_host", min_size, max_diff);
+  if (rc != EKF_OK) return rc;
+  std::string& err = d->err;
+  ekf::DenseSpeckle& s = h->speckle;
+  const size_t n = d->npix();
+  for (ekf::DenseView& o : d->v) o.seg = false;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(s.h_depth.reserve(n));
+  HIPCHK(s.h_plane.reserve(n));
+  HIPCHK(hipMemcpy(s.h_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(s.h_plane, plane, n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(s.run(d->W, d->H, s.h_depth, s.h_plane, min_size, max_diff));
+  HIPCHK(hipMemcpy(depth, s.h_depth, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(plane, s.h_plane, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (label) HIPCHK(hipMemcpy(label, s.R, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (size) HIPCHK(hipMemcpy(size, s.L, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_dense_get_speckle_profile(const ekf_dense* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->speckle.timer.read(kernel_ms, launches, 0, ekf::kSpeckleKinds);
   return EKF_OK;
 }
 

@@ -250,7 +250,7 @@ struct DenseSgm {
     a.w_min = w_min;
     a.step = (w_max - w_min) / (double)(D_ - 1);
     for (int i = 0; i < n_src; ++i) d.relative(r, d.v[src[i]], a.s[i]);
-    r.swept = r.filtered = r.has_runner = false;
+    r.swept = r.filtered = r.has_runner = r.seg = false;
     const SweepVolume vol{C, V};
     const dim3 grid((unsigned)((d.W + kDenseTW - 1) / kDenseTW), (unsigned)((d.H + kDenseTH - 1) / kDenseTH));
     // the census volume (§20) counts under the census profile, its directions and winner below like any other

@@ -671,6 +671,8 @@ struct DenseView {
   bool sgm = false;                   // the handle's cost volumes are those of this slot's maps (§19: DenseSgm)
   bool census_valid = false;          // `census` is that of `img`: every setter of the image clears it, a new pose does not
   bool has_runner = false;            // `runner` belongs to the slot's swept maps (§22): cleared wherever `swept` is
+  bool seg = false;                   // the handle's segment planes are those of this slot's filtered map (§23: DenseSpeckle):
+                                      // cleared wherever `filtered` is
 };
 
 // Host side of one handle (`ekf_dense`).  Everything runs on the default stream of the handle's device, as the rectified
@@ -760,7 +762,7 @@ struct DenseStereo {
     a.w_min = w_min;
     a.step = (w_max - w_min) / (double)(D - 1);
     for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
-    r.swept = r.filtered = r.sgm = r.has_runner = false;
+    r.swept = r.filtered = r.sgm = r.has_runner = r.seg = false;
     const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
     unsigned* const ru = r.runner;
     if (keep_runner && n_best > 0)                                          // the twins of §22: the same four maps, and `runner`
@@ -796,7 +798,7 @@ struct DenseStereo {
       if ((e = r.fdepth.reserve(n)) != hipSuccess || (e = r.fplane.reserve(n)) != hipSuccess) return e;
       a.out_depth = r.fdepth;
       a.out_plane = r.fplane;
-      r.filtered = false;
+      r.filtered = r.seg = false;
     }
     if (xyz) {
       if ((e = d_xyz.reserve(n * 3)) != hipSuccess) return e;

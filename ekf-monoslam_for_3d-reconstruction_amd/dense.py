@@ -18,6 +18,7 @@ from .capi import ptr as _ptr
 MAX_VIEWS, MAX_SOURCES = 16, 8
 UNIQUE_KERNELS = ("k_plane_sweep_unique", "k_plane_sweep_census_unique", "k_plane_sweep_best_unique",
                   "k_plane_sweep_best_census_unique", "k_sgm_winner_unique", "k_depth_filter_unique")
+SPECKLE_KERNELS = ("k_speckle_label", "k_speckle_merge", "k_speckle_count", "k_speckle_apply")
 
 
 @dataclass
@@ -33,6 +34,7 @@ class DepthMap:
     views: np.ndarray              # (H, W) uint8
     points: np.ndarray             # (H, W, 3) float64 of the filtered map, NaN where there is no depth
     runner_up: Optional[np.ndarray] = None    # (H, W) uint32, 0xFFFFFFFF = absent (§22); None when not recorded
+    segment_size: Optional[np.ndarray] = None  # (H, W) uint32, a pixel's segment before the speckle filter (§23); None without it
 
 
 class DenseStereo(capi.Handle):
@@ -176,6 +178,32 @@ class DenseStereo(capi.Handle):
         self._check(self._lib.ekf_dense_get_runner_up(self._h, int(slot), _ptr(out)))
         return out
 
+    # ---- the speckle filter ----
+    def filter_speckle(self, slot: int, min_size: int, max_diff: int = 1):
+        """Drops, from the slot's filtered map in place, the connected segments of fewer than ``min_size`` pixels; two
+        4-neighbours are in one segment if both have a plane and the planes differ by at most ``max_diff``.  The swept map
+        stays; a later ``filter`` of the slot starts again from it."""
+        self._check(self._lib.ekf_dense_filter_speckle(self._h, int(slot), int(min_size), int(max_diff)))
+
+    def segments(self, slot: int):
+        """(label, size), both (height, width) uint32, before the removal of the last ``filter_speckle``, whose slot ``slot``
+        must be, with no setter, sweep or filter of it since: a pixel's label is the least index y width + x of its segment
+        (0xFFFFFFFF: no plane), its size the segment's pixel count."""
+        label, size = np.zeros(self.shape, np.uint32), np.zeros(self.shape, np.uint32)
+        self._check(self._lib.ekf_dense_get_segments(self._h, int(slot), _ptr(label), _ptr(size)))
+        return label, size
+
+    def speckle_maps(self, depth, plane, min_size: int, max_diff: int = 1) -> dict:
+        """The speckle filter of (height, width) maps from the host, whatever made them: dict(depth, plane, label, size), the
+        filtered copies and the segments before the removal.  The inputs are not modified; no slot is touched."""
+        if np.shape(depth) != self.shape or np.shape(plane) != self.shape:
+            raise ValueError("depth and plane must be (height, width) = %r" % (self.shape,))
+        out = dict(depth=np.array(depth, np.float32, order="C"), plane=np.array(plane, np.int32, order="C"),
+                   label=np.zeros(self.shape, np.uint32), size=np.zeros(self.shape, np.uint32))
+        self._check(self._lib.ekf_dense_speckle_host(self._h, _ptr(out["depth"]), _ptr(out["plane"]), int(min_size), int(max_diff),
+                                                     _ptr(out["label"]), _ptr(out["size"])))
+        return out
+
     # ---- results ----
     def depth(self, slot: int, filtered: bool = False) -> dict:
         """depth float32 (0 = none), plane int32 (-1 = none), and of the sweep cost uint32 and views uint8."""
@@ -242,6 +270,13 @@ class DenseStereo(capi.Handle):
         ms, cnt = np.zeros(len(UNIQUE_KERNELS), np.float64), np.zeros(len(UNIQUE_KERNELS), np.int64)
         self._check(self._lib.ekf_dense_get_unique_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(UNIQUE_KERNELS)}
+
+    def get_speckle_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the four kernels of the speckle filter (§23) since the last
+        ``profile()``."""
+        ms, cnt = np.zeros(len(SPECKLE_KERNELS), np.float64), np.zeros(len(SPECKLE_KERNELS), np.int64)
+        self._check(self._lib.ekf_dense_get_speckle_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(SPECKLE_KERNELS)}
 
 
 def _cost_entry(lib, cost, name):
@@ -317,7 +352,7 @@ def neighbours_of(i: int, n: int, neighbours: int):
 def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, neighbours: int = 2, w_min: float = 0.05,
                               w_max: float = 2.0, planes: int = 64, radius: int = 2, trunc: int = 40, rel_tol: float = 0.01,
                               min_agree: int = 1, device: int = 0, sgm=None, cost: str = "ad",
-                              best: Optional[int] = None, uniqueness: int = 0):
+                              best: Optional[int] = None, uniqueness: int = 0, speckle=None):
     """Sweeps every key frame of a rectified recording against its ``neighbours`` nearest key frames on each side in file
     order, filters each map against the swept maps of the same neighbours and returns one ``DepthMap`` per key frame.
     The views pass through a ring of 16 device slots, so ``neighbours`` is 1 .. 3 (a map needs the views two
@@ -327,7 +362,13 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
     ``best``: ``None``, or the number of cheapest sources either sweep keeps per pixel and plane (§21); a key frame with fewer
     sources than that keeps them all, as with ``min_agree``.
     ``uniqueness``: 0, or the per cent of the uniqueness test every map's filter also applies (§22); the sweeps then record
-    their runner-up costs, which each ``DepthMap`` carries."""
+    their runner-up costs, which each ``DepthMap`` carries.
+    ``speckle``: ``None``, an int ``min_size`` or ``(min_size, max_diff)``: the speckle filter (§23) of every map right after
+    its filter (``max_diff`` 1 for an int); each ``DepthMap`` then carries its pixels' segment sizes."""
+    if speckle is not None:
+        speckle = (speckle, 1) if isinstance(speckle, (int, np.integer)) and not isinstance(speckle, bool) else speckle
+        if not (isinstance(speckle, tuple) and len(speckle) == 2 and 1 <= int(speckle[0]) <= 1 << 26 and 0 <= int(speckle[1]) <= 1023):
+            raise ValueError("speckle is None, an int min_size in 1 .. 2^26, or (min_size, max_diff) with max_diff in 0 .. 1023")
     if not 0 <= int(uniqueness) <= 100:
         raise ValueError("uniqueness is 0 .. 100")
     if best is not None and int(best) < 1:
@@ -365,10 +406,13 @@ def depth_maps_from_recording(directory: str, nodes_out: Optional[str] = None, n
                 swept += 1
             src = neighbours_of(i, n, neighbours)
             ds.filter(i % ring, [j % ring for j in src], rel_tol, min(min_agree, len(src)), int(uniqueness))
+            if speckle is not None:
+                ds.filter_speckle(i % ring, int(speckle[0]), int(speckle[1]))
             raw, flt = ds.depth(i % ring, False), ds.depth(i % ring, True)
             out.append(DepthMap(ids[i], poses[i].copy(), tuple(ids[j] for j in src), flt["depth"], flt["plane"], raw["depth"],
                                 raw["cost"], raw["views"], ds.points(i % ring, True),
-                                ds.runner_up(i % ring) if uniqueness else None))
+                                ds.runner_up(i % ring) if uniqueness else None,
+                                ds.segments(i % ring)[1] if speckle is not None else None))
     finally:
         ds.close()
     return out

@@ -309,7 +309,9 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     (DESIGN.md §19), for recordings with textureless surfaces; ``cost="census"`` sweeps with the census matching cost
     (§20), for recordings whose key frames differ in exposure or gain; ``best=n`` keeps the n cheapest sources per pixel and
     plane (§21), for neighbours that do not all see every pixel of a key frame; ``uniqueness=u`` (per cent) also drops the
-    pixels whose runner-up cost is within u % of the winner's (§22), for recordings with untextured surfaces."""
+    pixels whose runner-up cost is within u % of the winner's (§22), for recordings with untextured surfaces;
+    ``speckle=min_size`` or ``speckle=(min_size, max_diff)`` then drops from every filtered map the connected segments of fewer
+    than ``min_size`` pixels (§23), the islands that would become floating fragments of the mesh."""
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
@@ -380,8 +382,8 @@ def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Opti
                     **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
-    frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``
-    and ``uniqueness=…`` reach the sweep and the filter as they do through ``mesh_from_recording``."""
+    frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
+    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters as they do through ``mesh_from_recording``."""
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)

@@ -1032,6 +1032,40 @@ int ekf_dense_get_runner_up(ekf_dense* h, int slot, unsigned int* out);
 int ekf_dense_filter_unique(ekf_dense* h, int ref, const int* src, int n_src, double rel_tol, int min_agree, int uniqueness);
 int ekf_dense_get_unique_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
+/* ---- speckle filter: connected segments of a depth map -------------------------------------------------
+ * What the geometric filter and the uniqueness test leave of a wrong surface are islands of a few pixels whose neighbours
+ * were all dropped; the fusion gives them full weight.  The speckle filter segments a map into connected regions of
+ * similar plane and drops the small ones.  For a plane map of height x width int with its depth map, min_size >= 1 and
+ * max_diff >= 0: a pixel is valid iff plane >= 0; two 4-neighbours are linked iff both are valid and
+ * |plane_a - plane_b| <= max_diff (the difference in 64 bits); a segment is a connected component of the links (a ramp
+ * 0, 1, 2, ... is one segment at max_diff = 1); a valid pixel's label is the least linear index y width + x of its
+ * segment and its size the segment's pixel count; an invalid pixel has label 0xFFFFFFFF and size 0.  The filter sets
+ * depth = 0 and plane = -1 where size < min_size and leaves every other element bit for bit.  min_size = 1 changes nothing,
+ * the filter is idempotent, and labels, sizes and the output do not depend on any order of execution.
+ * tests/speckle_oracle.py restates it.  Four launches a call whatever the map holds: k_speckle_label, k_speckle_merge,
+ * k_speckle_count, k_speckle_apply.  Opt-in: nothing above calls it, and no default, result, launch, profile count or
+ * prototype of the calls above changes; ekf_abi_version() stays 6 (additions only).
+ *  - ekf_dense_filter_speckle: filters the slot's FILTERED map in place; ekf_dense_get_depth(.., filtered = 1),
+ *    ekf_dense_get_points, ekf_fusion_integrate(.., filtered = 1) and ekf_raycast_render_view then read it as they read any
+ *    filtered map.  The swept map, which the filters of other views read, is never touched.  EKF_ERR_ARG before the device
+ *    is touched: slot out of range, min_size outside 1 .. 2^26, max_diff outside 0 .. 1023.  EKF_ERR_STATE: the slot has no
+ *    filtered map.  A later ekf_dense_filter / ekf_dense_filter_unique of the slot starts again from the swept map;
+ *  - ekf_dense_get_segments: the height x width labels and sizes BEFORE the removal of the handle's last
+ *    ekf_dense_filter_speckle; either pointer may be NULL.  EKF_ERR_STATE unless `slot` is the slot of that call and has had
+ *    no setter, sweep or filter since and ekf_dense_speckle_host has not run since (the rule of ekf_dense_get_volume);
+ *  - ekf_dense_speckle_host: the same launches over tight height x width maps of the handle's size on the host, in and
+ *    out, for depth maps that come from elsewhere; label / size (before the removal) may be NULL.  It touches no slot, and
+ *    it takes over the planes ekf_dense_get_segments reads.  EKF_ERR_ARG: depth or plane NULL, min_size or max_diff out of
+ *    range;
+ *  - ekf_dense_get_speckle_profile: HIP-event milliseconds and launch counts of 4 kinds since the last ekf_dense_profile:
+ *    k_speckle_label ([0]), k_speckle_merge ([1]), k_speckle_count ([2]), k_speckle_apply ([3]).  The other profile getters
+ *    gain nothing. */
+int ekf_dense_filter_speckle(ekf_dense* h, int slot, int min_size, int max_diff);
+int ekf_dense_get_segments(ekf_dense* h, int slot, unsigned int* label, unsigned int* size);
+int ekf_dense_speckle_host(ekf_dense* h, float* depth, int* plane, int min_size, int max_diff, unsigned int* label,
+                           unsigned int* size);
+int ekf_dense_get_speckle_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -577,6 +577,31 @@ class DenseStereoHip {
   // HIP-event milliseconds and launch counts of k_plane_sweep_unique ([0]), k_plane_sweep_census_unique ([1]),
   // k_plane_sweep_best_unique ([2]), k_plane_sweep_best_census_unique ([3]), k_sgm_winner_unique ([4]), k_depth_filter_unique ([5])
   void getUniqueProfile(double kernel_ms[6], long long launches[6]) { check(ekf_dense_get_unique_profile(d_, kernel_ms, launches)); }
+  // the speckle filter.  filterSpeckle: drops, from the slot's filtered map in place, the connected
+  // segments of fewer than min_size pixels; two 4-neighbours share a segment if both have a plane and the planes differ by at
+  // most max_diff.  segments: the labels (the least index y width + x of a pixel's segment, 0xFFFFFFFF: no plane) and sizes
+  // before the removal of the last filterSpeckle, whose slot `slot` must be.  speckleMaps: the same for height x width maps
+  // of the caller's, filtered in place; it touches no slot
+  struct Segments {
+    std::vector<unsigned int> label, size;
+  };
+  void filterSpeckle(int slot, int min_size, int max_diff = 1) { check(ekf_dense_filter_speckle(d_, slot, min_size, max_diff)); }
+  Segments segments(int slot) {
+    Segments s;
+    s.label.resize(pixels()); s.size.resize(pixels());
+    check(ekf_dense_get_segments(d_, slot, s.label.data(), s.size.data()));
+    return s;
+  }
+  Segments speckleMaps(std::vector<float>& depth, std::vector<int>& plane, int min_size, int max_diff = 1) {
+    if (depth.size() != pixels() || plane.size() != pixels()) throw std::runtime_error("speckleMaps: depth and plane are height x width");
+    Segments s;
+    s.label.resize(pixels()); s.size.resize(pixels());
+    check(ekf_dense_speckle_host(d_, depth.data(), plane.data(), min_size, max_diff, s.label.data(), s.size.data()));
+    return s;
+  }
+  // HIP-event milliseconds and launch counts of k_speckle_label ([0]), k_speckle_merge ([1]), k_speckle_count ([2]),
+  // k_speckle_apply ([3])
+  void getSpeckleProfile(double kernel_ms[4], long long launches[4]) { check(ekf_dense_get_speckle_profile(d_, kernel_ms, launches)); }
   Depth depth(int slot, bool filtered = false) {
     Depth r;
     r.depth.resize(pixels()); r.plane.resize(pixels()); r.cost.resize(pixels()); r.views.resize(pixels());
