@@ -5527,7 +5527,7 @@ static int dense_sweep(ekf_dense* h, const char* who, bool census, int ref, cons
   }
   std::string& err = d->err;
   HIPCHK(hipSetDevice(d->device));
-  HIPCHK(d->sweep(ref, src, n_src, w_min, w_max, planes, radius, trunc, census));
+  HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, 0, 0, 0, census));
   return EKF_OK;
 }
 
@@ -5735,10 +5735,7 @@ int ekf_dense_sweep_best(ekf_dense* h, int ref, const int* src, int n_src, int n
   }
   std::string& err = d->err;
   HIPCHK(hipSetDevice(d->device));
-  if (sgm)
-    HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths, census != 0, n_best));
-  else
-    HIPCHK(d->sweep(ref, src, n_src, w_min, w_max, planes, radius, trunc, census != 0, n_best));
+  HIPCHK(h->sgm.sweep(*d, ref, src, n_src, w_min, w_max, planes, radius, trunc, p1, p2, paths, census != 0, n_best));
   return EKF_OK;
 }
 

@@ -21,9 +21,6 @@ constexpr int kSgmKinds = 10;                    // timed kinds: the volume swee
 // The (dx, dy) of §19.1, in their order; paths = 4 takes the first four.
 constexpr int kSgmDir[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, -1}, {1, -1}, {-1, 1}};
 
-__global__ void __launch_bounds__(256) k_sweep_volume(SweepArgs a, SweepVolume vol) { plane_sweep_body<true>(a, vol); }
-__global__ void __launch_bounds__(256) k_sweep_volume_census(SweepArgs a, SweepVolume vol) { plane_sweep_body<true, true>(a, vol); }
-
 // What a lane of k_sgm_path takes from other lanes of its wave (every lane of the wave makes each call):
 //   wave_read(v, src)  v of lane src (ds_bpermute; once a launch, for the longest line of the wave);
 //   lane_below(v)      v of lane - 1, lane_above(v): v of lane + 1 (lane 0 / 63: its own v) -- one DPP move each;
@@ -180,25 +177,10 @@ __device__ __forceinline__ void sgm_winner_body(const SgmWinnerArgs& a, unsigned
   const size_t n = (size_t)a.out.W * a.out.H;
   const size_t o = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (o >= n) return;
-  long long top[kRunnerKeys];                                               // RUNNER only
-  if constexpr (RUNNER) {
-#pragma unroll
-    for (int i = 0; i < kRunnerKeys; ++i) top[i] = runner_none<long long>();
-  }
-  int prev = 0, bestC = INT_MAX, bestK = -2, bestM = 0, bestP = 0;
+  SweepWinner<RUNNER, long long> win;
 #pragma unroll 8
-  for (int k = 0; k < a.out.D; ++k) {
-    const int C = (int)a.S[o * (size_t)a.out.D + (size_t)k];               // < 2^24
-    const bool pending = bestK == k - 1, better = C < bestC;
-    bestP = (pending || better) ? C : bestP;
-    bestM = better ? prev : bestM;
-    bestK = better ? k : bestK;
-    bestC = better ? C : bestC;
-    prev = C;
-    if constexpr (RUNNER) runner_insert(top, ((long long)C << 10) | k);
-  }
-  sweep_write_winner(a.out, o, bestK, bestM, bestC, bestP, (int)a.V[(size_t)bestK * n + o]);
-  if constexpr (RUNNER) runner[o] = runner_take(top);
+  for (int k = 0; k < a.out.D; ++k) win.step(k, (int)a.S[o * (size_t)a.out.D + (size_t)k]);      // < 2^24
+  win.write(a.out, o, (int)a.V[(size_t)win.K * n + o], runner);
 }
 
 __global__ void __launch_bounds__(256) k_sgm_winner(SgmWinnerArgs a) { sgm_winner_body<false>(a, nullptr); }
@@ -210,31 +192,115 @@ inline void sgm_volume_to_planes(const unsigned* vol, unsigned* out, size_t npix
     for (size_t p = 0; p < npix; ++p) out[(size_t)d * npix + p] = vol[p * (size_t)D + (size_t)d];
 }
 
-#ifndef EKF_KERNELS_ONLY
-// The planes a lane carries for D planes on G lanes, and the launch of one direction.
-template <int G, int NP>
-inline void sgm_launch_path(const SgmPathArgs& a, bool first, unsigned grid) {
-  if (first)
-    k_sgm_path<G, NP, true><<<grid, 256, 0, nullptr>>>(a);
-  else
-    k_sgm_path<G, NP, false><<<grid, 256, 0, nullptr>>>(a);
+// ---- the launches of a sweep ---------------------------------------------------------------------------------
+// The timed kinds: a pixel-wise sweep is kSweep + 4 (it keeps the runner-up) + 2 (n_best > 0) + 1 (census), a volume sweep
+// kVolume + 2 (n_best > 0) + 1 (census), direction i of kSgmDir is kSgmPath + i.
+enum SweepKind {
+  kSweep, kSweepCensus, kSweepBest, kSweepBestCensus, kSweepUnique, kSweepCensusUnique, kSweepBestUnique, kSweepBestCensusUnique,
+  kVolume, kVolumeCensus, kVolumeBest, kVolumeBestCensus,
+  kSgmPath, kSgmWinner = kSgmPath + 8, kSgmWinnerUnique
+};
+struct SweepGrid {
+  unsigned x, y;                      // workgroups of 256 lanes
+};
+struct SweepMode {
+  bool census;                        // the census cost (§20), not absolute differences
+  int n_best;                         // 0: the sum over all sources; 1 .. n_src: over the cheapest per pixel and plane (§21)
+  unsigned* runner;                   // where the runner-up goes (§22); NULL: nowhere
+  int paths, p1, p2;                  // paths = 0: the pixel-wise sweep; 4 or 8: the semi-global one (§19)
+};
+
+// One direction: G lanes a line and NP planes a lane for D planes, a workgroup for 256 / G lines.
+template <bool FIRST, typename Go>
+auto sgm_path_launch(Go& go, int kind, const SgmPathArgs& p) {
+  const bool diag = p.dx != 0 && p.dy != 0;
+  const int nlines = diag ? p.W + p.H - 1 : (p.dy == 0 ? p.H : p.W);
+  const int G = p.D <= 16 ? 16 : 64;
+  const SweepGrid grid{(unsigned)((nlines + 256 / G - 1) / (256 / G)), 1};
+  const int np = (p.D + 63) / 64;                                           // planes per lane at G = 64: 1 .. 16
+  if (G == 16) return go(kind, grid, k_sgm_path<16, 1, FIRST>, p);
+  if (np <= 1) return go(kind, grid, k_sgm_path<64, 1, FIRST>, p);
+  if (np <= 2) return go(kind, grid, k_sgm_path<64, 2, FIRST>, p);
+  if (np <= 4) return go(kind, grid, k_sgm_path<64, 4, FIRST>, p);
+  if (np <= 8) return go(kind, grid, k_sgm_path<64, 8, FIRST>, p);
+  return go(kind, grid, k_sgm_path<64, 16, FIRST>, p);
 }
 
-// Host side of the semi-global sweep of one handle: one raw and one aggregated volume (and the valid-view counts), grow-only,
-// and a timer of its own.  DenseView::sgm says which slot, if any, the volumes belong to.
+// Every launch of one sweep, in order, each made by go(kind, grid, kernel, args...): which of the twelve sweep kernels, and
+// for the semi-global sweep every direction's instantiation of k_sgm_path and the winner or its twin, with their grids.  This
+// is the one place that decides them: the library's go times and launches, the host checks' go (tools/host_kernels.hpp) runs
+// the kernel on the host.  It returns what go returns, whose value-initialised value (hipSuccess) means that the launch was
+// made, and stops at the first that was not.  `vol` and `S` are read with paths > 0 alone.
+template <typename Go>
+auto sweep_launches(const SweepArgs& a, const SweepVolume& vol, unsigned* S, const SweepMode& m, Go go) {
+  const SweepGrid tiles{(unsigned)((a.W + kDenseTW - 1) / kDenseTW), (unsigned)((a.H + kDenseTH - 1) / kDenseTH)};
+  const int sub = (m.n_best > 0 ? 2 : 0) + (m.census ? 1 : 0), nb = m.n_best;
+  unsigned* const ru = m.runner;
+  if (m.paths == 0) {
+    switch (kSweep + (ru ? 4 : 0) + sub) {
+      case kSweep: return go(kSweep, tiles, k_plane_sweep, a);
+      case kSweepCensus: return go(kSweepCensus, tiles, k_plane_sweep_census, a);
+      case kSweepBest: return go(kSweepBest, tiles, k_plane_sweep_best, a, nb);
+      case kSweepBestCensus: return go(kSweepBestCensus, tiles, k_plane_sweep_best_census, a, nb);
+      case kSweepUnique: return go(kSweepUnique, tiles, k_plane_sweep_unique, a, ru);
+      case kSweepCensusUnique: return go(kSweepCensusUnique, tiles, k_plane_sweep_census_unique, a, ru);
+      case kSweepBestUnique: return go(kSweepBestUnique, tiles, k_plane_sweep_best_unique, a, nb, ru);
+      default: return go(kSweepBestCensusUnique, tiles, k_plane_sweep_best_census_unique, a, nb, ru);
+    }
+  }
+  auto e = sub == 0   ? go(kVolume, tiles, k_sweep_volume, a, vol)
+           : sub == 1 ? go(kVolumeCensus, tiles, k_sweep_volume_census, a, vol)
+           : sub == 2 ? go(kVolumeBest, tiles, k_sweep_volume_best, a, vol, nb)
+                      : go(kVolumeBestCensus, tiles, k_sweep_volume_best_census, a, vol, nb);
+  const decltype(e) made{};
+  for (int i = 0; i < m.paths && e == made; ++i) {
+    const SgmPathArgs p{vol.C, S, a.W, a.H, a.D, m.p1, m.p2, kSgmDir[i][0], kSgmDir[i][1]};
+    e = i == 0 ? sgm_path_launch<true>(go, kSgmPath, p) : sgm_path_launch<false>(go, kSgmPath + i, p);
+  }
+  if (!(e == made)) return e;
+  const SgmWinnerArgs w{S, vol.V, a};
+  const SweepGrid lanes{(unsigned)(((size_t)a.W * a.H + 255) / 256), 1};
+  return ru ? go(kSgmWinnerUnique, lanes, k_sgm_winner_unique, w, ru) : go(kSgmWinner, lanes, k_sgm_winner, w);
+}
+
+#ifndef EKF_KERNELS_ONLY
+// Host side of a sweep of one handle, pixel-wise or semi-global: for the latter one raw and one aggregated volume (and the
+// valid-view counts), grow-only, and a timer of its own.  DenseView::sgm says which slot, if any, the volumes belong to.
 struct DenseSgm {
   DevBuf<unsigned> C, S;
   DevBuf<unsigned char> V;
   int D = 0;                          // planes of the volumes' sweep
   KernelTimer<kSgmKinds> timer;
 
+  // The launch of one kind under the profile that counts it (the getters' orders of kinds, ekf_capi.hip): a census volume
+  // (§20) under the census profile, the volume of the n_best cheapest sources (§21) under the best profile, their directions
+  // and winner here like any other, every twin of §22 under the unique profile.
+  template <typename F>
+  hipError_t timed(DenseStereo& d, int kind, F launch) {
+    switch (kind) {
+      case kSweep: return d.timer.run(0, launch);
+      case kSweepCensus: return d.census_timer.run(1, launch);
+      case kSweepBest: case kSweepBestCensus: return d.best_timer.run(kind - kSweepBest, launch);
+      case kSweepUnique: case kSweepCensusUnique: case kSweepBestUnique: case kSweepBestCensusUnique:
+        return d.unique_timer.run(kind - kSweepUnique, launch);
+      case kVolume: return timer.run(0, launch);
+      case kVolumeCensus: return d.census_timer.run(2, launch);
+      case kVolumeBest: case kVolumeBestCensus: return d.best_timer.run(2 + kind - kVolumeBest, launch);
+      case kSgmWinner: return timer.run(9, launch);
+      case kSgmWinnerUnique: return d.unique_timer.run(4, launch);
+      default: return timer.run(1 + kind - kSgmPath, launch);
+    }
+  }
+
+  // paths = 0: the pixel-wise sweep of §15 (p1 = p2 = 0; the volumes stay whose they are); 4 or 8: the semi-global one.
+  // n_best = 0: the sum over all sources; 1 .. n_src: the n_best cheapest sources per pixel and plane (§21, also for n_src).
   hipError_t sweep(DenseStereo& d, int ref, const int* src, int n_src, double w_min, double w_max, int D_, int radius, int trunc,
                    int p1, int p2, int paths, bool census = false, int n_best = 0) {
-#pragma clang fp contract(off)
     DenseView& r = d.v[ref];
     hipError_t e;
-    const size_t n = d.npix(), elems = n * (size_t)D_;
-    for (DenseView& v : d.v) v.sgm = false;                                 // the volumes are about to change hands
+    const size_t n = d.npix(), elems = paths ? n * (size_t)D_ : 0;
+    if (paths)
+      for (DenseView& v : d.v) v.sgm = false;                               // the volumes are about to change hands
     if ((e = r.depth.reserve(n)) != hipSuccess || (e = r.plane.reserve(n)) != hipSuccess ||
         (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess ||
         (e = C.reserve(elems)) != hipSuccess || (e = S.reserve(elems)) != hipSuccess || (e = V.reserve(elems)) != hipSuccess ||
@@ -243,50 +309,20 @@ struct DenseSgm {
       return e;
     }
     if (census && ((e = d.census_reserve(ref, src, n_src)) != hipSuccess || (e = d.census_update(ref, src, n_src)) != hipSuccess)) return e;
-    SweepArgs a{};
+    DenseCam cam[1 + kDenseMaxSrc] = {r.cam()};
+    for (int i = 0; i < n_src; ++i) cam[1 + i] = d.v[src[i]].cam();
+    SweepArgs a = sweep_args(cam, n_src, d.W, d.H, D_, radius, trunc, w_min, w_max);
     a.ref = r.img; a.ref_census = r.census; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
-    a.W = d.W; a.H = d.H; a.D = D_; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
-    a.fx = r.K[0]; a.fy = r.K[1]; a.cx = r.K[2]; a.cy = r.K[3];
-    a.w_min = w_min;
-    a.step = (w_max - w_min) / (double)(D_ - 1);
-    for (int i = 0; i < n_src; ++i) d.relative(r, d.v[src[i]], a.s[i]);
-    r.swept = r.filtered = r.has_runner = r.seg = false;
-    const SweepVolume vol{C, V};
-    const dim3 grid((unsigned)((d.W + kDenseTW - 1) / kDenseTW), (unsigned)((d.H + kDenseTH - 1) / kDenseTH));
-    // the census volume (§20) counts under the census profile, its directions and winner below like any other
-    // and the volume of the n_best cheapest sources (§21; n_best = 0: of all of them) under the best profile
-    if (n_best > 0)
-      e = census ? d.best_timer.run(3, [&] { k_sweep_volume_best_census<<<grid, 256, 0, nullptr>>>(a, vol, n_best); })
-                 : d.best_timer.run(2, [&] { k_sweep_volume_best<<<grid, 256, 0, nullptr>>>(a, vol, n_best); });
-    else
-      e = census ? d.census_timer.run(2, [&] { k_sweep_volume_census<<<grid, 256, 0, nullptr>>>(a, vol); })
-                 : timer.run(0, [&] { k_sweep_volume<<<grid, 256, 0, nullptr>>>(a, vol); });
+    for (int i = 0; i < n_src; ++i) DenseStereo::source_pointers(d.v[src[i]], a.s[i]);
+    r.swept = r.filtered = r.sgm = r.has_runner = r.seg = false;
+    const SweepMode m{census, n_best, d.keep_runner ? (unsigned*)r.runner : nullptr, paths, p1, p2};
+    e = sweep_launches(a, SweepVolume{C, V}, S, m, [&](int kind, SweepGrid g, auto kernel, const auto&... args) {
+      return timed(d, kind, [&] { kernel<<<dim3(g.x, g.y), 256, 0, nullptr>>>(args...); });
+    });
     if (e != hipSuccess) return e;
-    for (int i = 0; i < paths; ++i) {
-      const SgmPathArgs p{C, S, d.W, d.H, D_, p1, p2, kSgmDir[i][0], kSgmDir[i][1]};
-      const bool diag = p.dx != 0 && p.dy != 0;
-      const int nlines = diag ? d.W + d.H - 1 : (p.dy == 0 ? d.H : d.W);
-      const int G = D_ <= 16 ? 16 : 64;
-      const unsigned wg = (unsigned)((nlines + 256 / G - 1) / (256 / G));
-      const int np = (D_ + 63) / 64;                                        // planes per lane at G = 64: 1 .. 16
-      e = timer.run(1 + i, [&] {
-        if (G == 16) sgm_launch_path<16, 1>(p, i == 0, wg);
-        else if (np <= 1) sgm_launch_path<64, 1>(p, i == 0, wg);
-        else if (np <= 2) sgm_launch_path<64, 2>(p, i == 0, wg);
-        else if (np <= 4) sgm_launch_path<64, 4>(p, i == 0, wg);
-        else if (np <= 8) sgm_launch_path<64, 8>(p, i == 0, wg);
-        else sgm_launch_path<64, 16>(p, i == 0, wg);
-      });
-      if (e != hipSuccess) return e;
-    }
-    const SgmWinnerArgs w{S, V, a};
-    unsigned* const ru = r.runner;
-    const unsigned wg_w = (unsigned)((n + 255) / 256);
-    e = d.keep_runner ? d.unique_timer.run(4, [&] { k_sgm_winner_unique<<<wg_w, 256, 0, nullptr>>>(w, ru); })   // §22
-                      : timer.run(9, [&] { k_sgm_winner<<<wg_w, 256, 0, nullptr>>>(w); });
-    if (e != hipSuccess) return e;
-    D = D_;
-    r.swept = r.sgm = true;
+    if (paths) D = D_;
+    r.swept = true;
+    r.sgm = paths != 0;
     r.has_runner = d.keep_runner;
     return hipSuccess;
   }

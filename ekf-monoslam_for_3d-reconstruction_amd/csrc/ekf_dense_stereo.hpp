@@ -16,8 +16,9 @@
 #include <type_traits>
 #include <vector>
 
-// EKF_KERNELS_ONLY: the structs, the two kernel bodies and dense_pose alone, for tools/dense_host_check.cpp, which runs
-// the kernels lane by lane on the host; tools/host_kernels.hpp supplies threadIdx, __syncthreads and the like.
+// EKF_KERNELS_ONLY: the structs, the kernels and what fills their arguments (dense_pose, dense_relative, sweep_args) alone,
+// for the host checks (tools/*_host_check.cpp), which run the kernels lane by lane on the host; tools/host_kernels.hpp supplies
+// threadIdx, __syncthreads and the like.
 #ifndef EKF_KERNELS_ONLY
 #include <hip/hip_runtime.h>
 
@@ -175,10 +176,41 @@ __device__ __forceinline__ unsigned runner_take(const Key (&t)[kRunnerKeys]) {
   return c2;
 }
 
+// The winner of one pixel over the planes k = 0, 1, .. in turn (§15.1), in registers: the cost of the previous plane, the least
+// cost C with its plane K (the first of equals), its neighbours' costs M and P and its count of valid views V; with RUNNER the
+// four smallest keys as well.  Written once for the sweeps (Key = int) and the aggregate's winner (long long, whose V is read
+// from the stored counts after the loop: write takes the count).
+template <bool RUNNER, typename Key>
+struct SweepWinner {
+  int prev = 0, C = INT_MAX, K = -2, M = 0, P = 0, V = 0;
+  Key top[kRunnerKeys];                                                     // RUNNER only
+  __device__ __forceinline__ SweepWinner() {
+    if constexpr (RUNNER) {
+#pragma unroll
+      for (int i = 0; i < kRunnerKeys; ++i) top[i] = runner_none<Key>();
+    }
+  }
+  // selects, not branches: the plane after the best one delivers its C+ (K = -2 before plane 0: never pending), a strictly
+  // smaller cost takes over (C starts at INT_MAX, so plane 0 always does)
+  __device__ __forceinline__ void step(int k, int c, int nv = 0) {
+    const bool pending = K == k - 1, better = c < C;
+    P = (pending || better) ? c : P;
+    M = better ? prev : M;
+    V = better ? nv : V;
+    K = better ? k : K;
+    C = better ? c : C;
+    prev = c;
+    if constexpr (RUNNER) runner_insert(top, ((Key)c << 10) | k);
+  }
+  __device__ __forceinline__ void write(const SweepArgs& a, size_t o, int nv, unsigned* runner) const {
+    sweep_write_winner(a, o, K, M, C, P, nv);
+    if constexpr (RUNNER) runner[o] = runner_take(top);
+  }
+};
+
 // The cost c_v of one halo pixel (ray (hx, hy), reference value or descriptor `ref`) on the plane of depth z in the source
 // view s: §15.1's warp and validity test, then the truncated absolute difference of the 5-bit bilinear sample or (CENSUS, §20)
-// the truncated Hamming distance at the nearest pixel.  An invalid warp costs trunc; a valid one adds 1 to nv.  Written once
-// for plane_sweep_body and plane_sweep_best_body (§21).
+// the truncated Hamming distance at the nearest pixel.  An invalid warp costs trunc; a valid one adds 1 to nv.
 template <bool CENSUS, typename Ref>
 __device__ __forceinline__ int sweep_view_cost(const SweepArgs& a, const DenseSrc& s, double hx, double hy, double z, Ref ref,
                                                double qx_max, double qy_max, int& nv) {
@@ -215,140 +247,15 @@ __device__ __forceinline__ int sweep_view_cost(const SweepArgs& a, const DenseSr
   return c;
 }
 
-// CENSUS (§20; a second template parameter, so the fp64 warp is written once): the matching cost is the Hamming distance of
-// census descriptors, not the absolute grey difference.  A halo pixel's register value is then its 64-bit descriptor, and
-// per source the four byte gathers and the blend become one 8-byte load at the nearest pixel and a popcount.  The warp, the
-// window, the winner and the volume stores are the same lines.
-// RUNNER (§22; a third one): the four smallest keys of each owned pixel ride along and its runner-up goes to `runner`, W H words.
-template <bool VOLUME, bool CENSUS = false, bool RUNNER = false>
-__device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const SweepVolume& vol, unsigned* runner = nullptr) {
-#pragma clang fp contract(off)
-  static_assert(!(VOLUME && RUNNER), "the runner-up of an aggregated sweep is k_sgm_winner_unique's");
-  __shared__ int s_c[kDenseHH][kDenseHW + 1];
-  __shared__ int s_h[kDenseHH][kDenseTW + 1];
-  const int tid = threadIdx.x;
-  const int r = a.radius, hw = kDenseTW + 2 * r, hh = kDenseTH + 2 * r, nh = hw * hh;
-  const int x0 = (int)blockIdx.x * kDenseTW - r, y0 = (int)blockIdx.y * kDenseTH - r;
-  const int W = a.W, H = a.H;
-  const double qx_max = (double)(32 * (W - 1)), qy_max = (double)(32 * (H - 1));
-
-  // the lane's halo pixels: position in the halo, ray and reference grey value, fixed for the launch
-  int h_off[kDenseHaloPerLane];                                           // h_off < 0: none, or outside the image
-  typename std::conditional<CENSUS, unsigned long long, int>::type h_ref[kDenseHaloPerLane];
-  double h_x[kDenseHaloPerLane], h_y[kDenseHaloPerLane];
-#pragma unroll
-  for (int i = 0; i < kDenseHaloPerLane; ++i) {
-    const int h = tid + 256 * i;
-    const int hy = h / hw, hx = h - hy * hw;
-    const int X = x0 + hx, Y = y0 + hy;
-    const bool in = h < nh && X >= 0 && X < W && Y >= 0 && Y < H;
-    h_off[i] = h < nh ? (in ? hy * (kDenseHW + 1) + hx : -1 - (hy * (kDenseHW + 1) + hx)) : INT_MIN;
-    if constexpr (CENSUS)
-      h_ref[i] = in ? a.ref_census[(size_t)Y * W + X] : 0ull;
-    else
-      h_ref[i] = in ? (int)a.ref[(size_t)Y * W + X] : 0;
-    h_x[i] = ((double)X - a.cx) / a.fx;
-    h_y[i] = ((double)Y - a.cy) / a.fy;
-  }
-  const int tx = tid & 31, ty = tid >> 5;
-  int* const sc = &s_c[0][0];
-
-  // VOLUME: where the two owned pixels go in a plane of the volume (-1: outside the image)
-  long own[2] = {-1, -1};
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
-    if (VOLUME && X < W && Y < H) own[j] = (long)Y * W + X;
-  }
-  const size_t plane_elems = (size_t)W * H;
-  int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
-  int top[2][kRunnerKeys];                                                  // RUNNER only
-  if constexpr (RUNNER) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < kRunnerKeys; ++i) top[j][i] = runner_none<int>();
-  }
-  for (int k = 0; k < a.D; ++k) {
-    const double z = 1.0 / (a.w_min + (double)k * a.step);
-#pragma unroll
-    for (int i = 0; i < kDenseHaloPerLane; ++i) {
-      if (h_off[i] == INT_MIN) continue;
-      if (h_off[i] < 0) {                                                   // a window position outside the image: nothing
-        sc[-1 - h_off[i]] = 0;
-        continue;
-      }
-      int csum = 0, nv = 0;
-      for (int v = 0; v < a.n_src; ++v) csum += sweep_view_cost<CENSUS>(a, a.s[v], h_x[i], h_y[i], z, h_ref[i], qx_max, qy_max, nv);
-      sc[h_off[i]] = csum | (nv << 16);                                     // csum <= 8 * 255
-    }
-    __syncthreads();
-    // horizontal pass over the hh halo rows, 32 columns each; the valid count of the owned pixels is read here, before the
-    // barrier after which other lanes may overwrite s_c for the next plane
-    for (int e = tid; e < hh * kDenseTW; e += 256) {
-      const int row = e >> 5, col = e & 31;
-      int sum = 0;
-      for (int d = 0; d <= 2 * r; ++d) sum += s_c[row][col + d] & 0xffff;
-      s_h[row][col] = sum;
-    }
-    const int nv0 = s_c[ty + r][tx + r] >> 16, nv1 = s_c[ty + 8 + r][tx + r] >> 16;
-    __syncthreads();
-    // vertical pass: the two owned pixels (the next write of s_h comes after the next plane's first barrier)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int oy = ty + 8 * j;
-      int C = 0;
-      for (int d = 0; d <= 2 * r; ++d) C += s_h[oy + d][tx];
-      if constexpr (VOLUME) {
-        if (own[j] >= 0) {
-          vol.C[(size_t)own[j] * (size_t)a.D + (size_t)k] = (unsigned)C;
-          vol.V[(size_t)k * plane_elems + (size_t)own[j]] = (unsigned char)(j == 0 ? nv0 : nv1);
-        }
-        continue;
-      }
-      // selects, not branches: the plane after the best one delivers its C+ (bestK = -2 before plane 0: never pending),
-      // a strictly smaller C takes over (bestC starts at INT_MAX, so plane 0 always does)
-      const bool pending = bestK[j] == k - 1, better = C < bestC[j];
-      bestP[j] = (pending || better) ? C : bestP[j];
-      bestM[j] = better ? prevC[j] : bestM[j];
-      bestV[j] = better ? (j == 0 ? nv0 : nv1) : bestV[j];
-      bestK[j] = better ? k : bestK[j];
-      bestC[j] = better ? C : bestC[j];
-      prevC[j] = C;
-      if constexpr (RUNNER) runner_insert(top[j], (C << 10) | k);
-    }
-  }
-  if constexpr (VOLUME) return;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
-    if (X >= W || Y >= H) continue;
-    sweep_write_winner(a, (size_t)Y * W + X, bestK[j], bestM[j], bestC[j], bestP[j], bestV[j]);
-    if constexpr (RUNNER) runner[(size_t)Y * W + X] = runner_take(top[j]);
-  }
-}
-
-__global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) { plane_sweep_body<false>(a, SweepVolume{nullptr, nullptr}); }
-__global__ void __launch_bounds__(256) k_plane_sweep_census(SweepArgs a) {
-  plane_sweep_body<false, true>(a, SweepVolume{nullptr, nullptr});
-}
-// ... and their twins that also write the runner-up (§22)
-__global__ void __launch_bounds__(256) k_plane_sweep_unique(SweepArgs a, unsigned* runner) {
-  plane_sweep_body<false, false, true>(a, SweepVolume{nullptr, nullptr}, runner);
-}
-__global__ void __launch_bounds__(256) k_plane_sweep_census_unique(SweepArgs a, unsigned* runner) {
-  plane_sweep_body<false, true, true>(a, SweepVolume{nullptr, nullptr}, runner);
-}
-
 // ---- best-K source selection ------------------------------------------------------------------------------
 // Per pixel and plane the cost is the sum of the n_best smallest per-view window sums C_k^v, not the sum of all of them: a
 // selection does not commute with the window sum, so the windowed cost must exist per view and the one pair of LDS passes of
-// plane_sweep_body becomes one per PAIR of views.  Two views share an LDS word as 16-bit halves: a pixel cost is <= 255, a
-// horizontal sum <= 9 * 255 = 2295 and a window sum <= 81 * 255 = 20 655 < 2^16, so no carry crosses the halves and one
+// a plane serves one PAIR of views a word, not all views.  Two views share an LDS word as 16-bit halves: a pixel cost is <= 255,
+// a horizontal sum <= 9 * 255 = 2295 and a window sum <= 81 * 255 = 20 655 < 2^16, so no carry crosses the halves and one
 // integer add serves both.  All kBestPairs planes of words stay in LDS at once (4 * 7104 = 28 416 B), so a plane of the sweep
 // still costs two barriers whatever n_src is (§21.2 has the reasons).  The count of valid warps, whose place in the upper
 // half is now taken, rides in the top byte of the first pair's word of s_c (bits 8 .. 15 and 24 .. 31 of a pair of pixel costs
-// are free); the horizontal pass masks it off.  The tile, the halo in registers, the grid and the winner are plane_sweep_body's.
+// are free); the horizontal pass masks it off.
 constexpr int kBestPairs = kDenseMaxSrc / 2;
 constexpr int kBestNone = 0xffff;                 // no view: more than any window sum
 
@@ -371,24 +278,38 @@ __device__ __forceinline__ int best_take(const int (&s)[kDenseMaxSrc], int n_bes
   return sum;
 }
 
-template <bool VOLUME, bool CENSUS, bool RUNNER = false>
-__device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const SweepVolume& vol, int n_best, unsigned* runner = nullptr) {
+// The one body of the twelve sweep kernels: the tile, the halo in registers, the two LDS passes of a plane, the volume stores
+// or the winner, and four template parameters for what differs.
+// CENSUS (§20; the fp64 warp is sweep_view_cost's either way): the matching cost is the Hamming distance of census
+// descriptors, not the absolute grey difference.  A halo pixel's register value is then its 64-bit descriptor, and per source
+// the four byte gathers and the blend become one 8-byte load at the nearest pixel and a popcount.
+// BEST (§21): the cost of a plane is that of the n_best cheapest views.  It picks three stages: the words a halo pixel
+// writes to LDS (one a pair of views, not one), what the horizontal pass masks and how often it runs (once a pair), and the
+// vertical pass, which ends in the selection.
+// RUNNER (§22): the four smallest keys of each owned pixel ride along and its runner-up goes to `runner`, W H words.
+template <bool VOLUME, bool CENSUS, bool BEST, bool RUNNER>
+__device__ __forceinline__ void plane_sweep_body(const SweepArgs& a, const SweepVolume& vol, int n_best, unsigned* runner) {
 #pragma clang fp contract(off)
   static_assert(!(VOLUME && RUNNER), "the runner-up of an aggregated sweep is k_sgm_winner_unique's");
-  __shared__ int s_c[kBestPairs][kDenseHH][kDenseHW + 1];
-  __shared__ int s_h[kBestPairs][kDenseHH][kDenseTW + 1];
+  constexpr int kWords = BEST ? kBestPairs : 1;                             // LDS words of a halo pixel
+  constexpr int kCostMask = BEST ? 0x00ff00ff : 0xffff, kCountShift = BEST ? 24 : 16;     // of a word of s_c
+  __shared__ int s_c[kWords][kDenseHH][kDenseHW + 1];
+  __shared__ int s_h[kWords][kDenseHH][kDenseTW + 1];
   const int tid = threadIdx.x;
   const int r = a.radius, hw = kDenseTW + 2 * r, hh = kDenseTH + 2 * r, nh = hw * hh;
   const int x0 = (int)blockIdx.x * kDenseTW - r, y0 = (int)blockIdx.y * kDenseTH - r;
   const int W = a.W, H = a.H;
-  const int n_pairs = (a.n_src + 1) >> 1;                                   // a kernel argument: uniform
-  // what ekf_dense_sweep_best has checked: without it every loop below gets a guard, kept as a lane mask in two SGPRs
-  __builtin_assume(r >= 0 && r <= kDenseMaxRadius);
-  __builtin_assume(a.n_src >= 1 && a.n_src <= kDenseMaxSrc);
-  __builtin_assume(a.D >= 1);
+  const int n_pairs = BEST ? (a.n_src + 1) >> 1 : 1;                        // a kernel argument: uniform
+  // what ekf_dense_sweep_best has checked: without it every loop below gets a guard, kept as a lane mask in two SGPRs.
+  // (BEST only: the other six kernels keep the code, and the registers tests/test_isa_census.py holds, that they have without.)
+  if constexpr (BEST) {
+    __builtin_assume(r >= 0 && r <= kDenseMaxRadius);
+    __builtin_assume(a.n_src >= 1 && a.n_src <= kDenseMaxSrc);
+    __builtin_assume(a.D >= 1);
+  }
   const double qx_max = (double)(32 * (W - 1)), qy_max = (double)(32 * (H - 1));
 
-  // the lane's halo pixels, as in plane_sweep_body
+  // the lane's halo pixels: position in the halo, ray and reference grey value or descriptor, fixed for the launch
   int h_off[kDenseHaloPerLane];                                           // h_off < 0: none, or outside the image
   typename std::conditional<CENSUS, unsigned long long, int>::type h_ref[kDenseHaloPerLane];
   double h_x[kDenseHaloPerLane], h_y[kDenseHaloPerLane];
@@ -411,125 +332,148 @@ __device__ __forceinline__ void plane_sweep_best_body(const SweepArgs& a, const 
   static_assert(kDenseTW * kDenseTH >= 512, "halo positions 0 .. 511 exist at every radius");
   int* const sc = &s_c[0][0][0];
 
-  // VOLUME: where plane 0 of the two owned pixels goes in the volumes (NULL: outside the image); kept per lane, so the
-  // plane loop holds no base pointer in SGPRs
+  // the two owned pixels: whether pixel j lies inside the image, and its index `o` in a W x H map
+  auto owned = [&](int j, size_t& o) {
+    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
+    o = (size_t)Y * W + X;
+    return X < W && Y < H;
+  };
+  // VOLUME: where they go in the volumes, in the form each pair of kernels was measured with (§15.6).  BEST: the addresses
+  // of plane 0 (NULL: outside the image), per lane, so that the plane loop holds no base pointer in SGPRs, of which these
+  // kernels have none to spare.  Otherwise the map index (-1: outside the image) beside the base pointers: the pointers cost
+  // k_sweep_volume about 1 % at 320 x 240.
+  long own[2] = {-1, -1};
   unsigned* own_C[2] = {nullptr, nullptr};
   unsigned char* own_V[2] = {nullptr, nullptr};
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
-    if (VOLUME && X < W && Y < H) {
-      own_C[j] = vol.C + ((size_t)Y * W + X) * (size_t)a.D;
-      own_V[j] = vol.V + ((size_t)Y * W + X);
+    size_t o;
+    if (VOLUME && owned(j, o)) {
+      own[j] = (long)o;
+      own_C[j] = vol.C + o * (size_t)a.D;
+      own_V[j] = vol.V + o;
     }
   }
   const size_t plane_elems = (size_t)W * H;
-  int prevC[2] = {0, 0}, bestC[2] = {INT_MAX, INT_MAX}, bestK[2] = {-2, -2}, bestM[2] = {0, 0}, bestP[2] = {0, 0}, bestV[2] = {0, 0};
-  int top[2][kRunnerKeys];                                                  // RUNNER only
-  if constexpr (RUNNER) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < kRunnerKeys; ++i) top[j][i] = runner_none<int>();
-  }
+  SweepWinner<RUNNER, int> win[2];
   for (int k = 0; k < a.D; ++k) {
     const double z = 1.0 / (a.w_min + (double)k * a.step);
 #pragma unroll
     for (int i = 0; i < kDenseHaloPerLane; ++i) {
-      if (i >= 2 && h_off[i] == INT_MIN) continue;                          // (the first 512 halo positions always exist)
+      if ((!BEST || i >= 2) && h_off[i] == INT_MIN) continue;               // (BEST knows r >= 0: the first 512 always exist)
       if (h_off[i] < 0) {                                                   // a window position outside the image: nothing
         for (int p = 0; p < n_pairs; ++p) sc[p * pair_words - 1 - h_off[i]] = 0;
         continue;
       }
-      // one view a turn, as in plane_sweep_body (the view's 38 words of kernel arguments sit in SGPRs; unrolled by two, the
-      // compiler keeps two views' and spills): an even view opens a word, an odd one or the last one closes it.  The upper
-      // half of an odd n_src's last word keeps trunc, the cost of a view whose every warp is invalid: no real view's window
-      // sum is larger, so it sorts last and is never among the n_best <= n_src smallest.  The branches are uniform.
-      int nv = 0, word = 0, word0 = 0;
+      int nv = 0;
+      if constexpr (BEST) {
+        // one view a turn (the view's 38 words of kernel arguments sit in SGPRs; unrolled by two, the compiler keeps two
+        // views' and spills): an even view opens a word, an odd one or the last one closes it.  The upper half of an odd
+        // n_src's last word keeps trunc, the cost of a view whose every warp is invalid: no real view's window sum is
+        // larger, so it sorts last and is never among the n_best <= n_src smallest.  The branches are uniform.
+        int word = 0, word0 = 0;
 #pragma unroll 1
-      for (int v = 0; v < a.n_src; ++v) {
-        const int c = sweep_view_cost<CENSUS>(a, a.s[v], h_x[i], h_y[i], z, h_ref[i], qx_max, qy_max, nv);
-        word = (v & 1) ? (word & 0xffff) | (c << 16) : c | (a.trunc << 16);  // each half <= 255
-        if ((v & 1) || v == a.n_src - 1) {
-          if (v < 2) word0 = word;                                          // waits for the count of all views
-          else sc[(v >> 1) * pair_words + h_off[i]] = word;
+        for (int v = 0; v < a.n_src; ++v) {
+          const int c = sweep_view_cost<CENSUS>(a, a.s[v], h_x[i], h_y[i], z, h_ref[i], qx_max, qy_max, nv);
+          word = (v & 1) ? (word & 0xffff) | (c << 16) : c | (a.trunc << 16);  // each half <= 255
+          if ((v & 1) || v == a.n_src - 1) {
+            if (v < 2) word0 = word;                                        // waits for the count of all views
+            else sc[(v >> 1) * pair_words + h_off[i]] = word;
+          }
         }
+        sc[h_off[i]] = word0 | (nv << kCountShift);                         // nv <= 8
+      } else {
+        int csum = 0;
+        for (int v = 0; v < a.n_src; ++v) csum += sweep_view_cost<CENSUS>(a, a.s[v], h_x[i], h_y[i], z, h_ref[i], qx_max, qy_max, nv);
+        sc[h_off[i]] = csum | (nv << kCountShift);                          // csum <= 8 * 255
       }
-      sc[h_off[i]] = word0 | (nv << 24);                                    // nv <= 8
     }
     __syncthreads();
-    // horizontal pass over the hh halo rows, 32 columns each, of every pair; the valid count of the owned pixels is read
+    // horizontal pass over the hh halo rows, 32 columns each, of every word; the valid count of the owned pixels is read
     // here, before the barrier after which other lanes may overwrite s_c for the next plane
     for (int e = tid; e < hh * kDenseTW; e += 256) {
       const int row = e >> 5, col = e & 31;
       for (int p = 0; p < n_pairs; ++p) {
         int sum = 0;
-        for (int d = 0; d <= 2 * r; ++d) sum += s_c[p][row][col + d] & 0x00ff00ff;
-        s_h[p][row][col] = sum;                                             // each half <= 2295
+        for (int d = 0; d <= 2 * r; ++d) sum += s_c[p][row][col + d] & kCostMask;
+        s_h[p][row][col] = sum;                                             // BEST: each half <= 2295
       }
     }
-    const int nv0 = s_c[0][ty + r][tx + r] >> 24, nv1 = s_c[0][ty + 8 + r][tx + r] >> 24;
+    const int nv_own[2] = {s_c[0][ty + r][tx + r] >> kCountShift, s_c[0][ty + 8 + r][tx + r] >> kCountShift};
     __syncthreads();
-    // vertical pass and selection: the two owned pixels (the next write of s_h comes after the next plane's first barrier)
+    // vertical pass, BEST: and selection: the two owned pixels (the next write of s_h comes after the next plane's first barrier)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int oy = ty + 8 * j;
-      int best[kDenseMaxSrc];
+      int C = 0;
+      if constexpr (BEST) {
+        int best[kDenseMaxSrc];
 #pragma unroll
-      for (int i = 0; i < kDenseMaxSrc; ++i) best[i] = kBestNone;
+        for (int i = 0; i < kDenseMaxSrc; ++i) best[i] = kBestNone;
 #pragma unroll 1
-      for (int p = 0; p < n_pairs; ++p) {
-        unsigned word = 0;
-        for (int d = 0; d <= 2 * r; ++d) word += (unsigned)s_h[p][oy + d][tx];     // each half <= 20 655
-        best_insert(best, (int)(word & 0xffffu));
-        best_insert(best, (int)(word >> 16));                               // (an odd n_src's last: the all-trunc view)
+        for (int p = 0; p < n_pairs; ++p) {
+          unsigned word = 0;
+          for (int d = 0; d <= 2 * r; ++d) word += (unsigned)s_h[p][oy + d][tx];   // each half <= 20 655
+          best_insert(best, (int)(word & 0xffffu));
+          best_insert(best, (int)(word >> 16));                             // (an odd n_src's last: the all-trunc view)
+        }
+        C = best_take(best, n_best);
+      } else {
+        for (int d = 0; d <= 2 * r; ++d) C += s_h[0][oy + d][tx];
       }
-      const int C = best_take(best, n_best);
-      if constexpr (VOLUME) {
+      if constexpr (VOLUME && BEST) {
         if (own_C[j]) {
           own_C[j][k] = (unsigned)C;
-          own_V[j][(size_t)k * plane_elems] = (unsigned char)(j == 0 ? nv0 : nv1);
+          own_V[j][(size_t)k * plane_elems] = (unsigned char)nv_own[j];
         }
-        continue;
+      } else if constexpr (VOLUME) {
+        if (own[j] >= 0) {
+          vol.C[(size_t)own[j] * (size_t)a.D + (size_t)k] = (unsigned)C;
+          vol.V[(size_t)k * plane_elems + (size_t)own[j]] = (unsigned char)nv_own[j];
+        }
+      } else {
+        win[j].step(k, C, nv_own[j]);
       }
-      // the winner selects of plane_sweep_body
-      const bool pending = bestK[j] == k - 1, better = C < bestC[j];
-      bestP[j] = (pending || better) ? C : bestP[j];
-      bestM[j] = better ? prevC[j] : bestM[j];
-      bestV[j] = better ? (j == 0 ? nv0 : nv1) : bestV[j];
-      bestK[j] = better ? k : bestK[j];
-      bestC[j] = better ? C : bestC[j];
-      prevC[j] = C;
-      if constexpr (RUNNER) runner_insert(top[j], (C << 10) | k);
     }
   }
-  if constexpr (VOLUME) return;
+  if constexpr (!VOLUME) {
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int X = (int)blockIdx.x * kDenseTW + tx, Y = (int)blockIdx.y * kDenseTH + ty + 8 * j;
-    if (X >= W || Y >= H) continue;
-    sweep_write_winner(a, (size_t)Y * W + X, bestK[j], bestM[j], bestC[j], bestP[j], bestV[j]);
-    if constexpr (RUNNER) runner[(size_t)Y * W + X] = runner_take(top[j]);
+    for (int j = 0; j < 2; ++j) {
+      size_t o;
+      if (owned(j, o)) win[j].write(a, o, win[j].V, runner);
+    }
   }
 }
 
+__global__ void __launch_bounds__(256) k_plane_sweep(SweepArgs a) { plane_sweep_body<false, false, false, false>(a, {}, 0, nullptr); }
+__global__ void __launch_bounds__(256) k_plane_sweep_census(SweepArgs a) { plane_sweep_body<false, true, false, false>(a, {}, 0, nullptr); }
 __global__ void __launch_bounds__(256) k_plane_sweep_best(SweepArgs a, int n_best) {
-  plane_sweep_best_body<false, false>(a, SweepVolume{nullptr, nullptr}, n_best);
+  plane_sweep_body<false, false, true, false>(a, {}, n_best, nullptr);
 }
 __global__ void __launch_bounds__(256) k_plane_sweep_best_census(SweepArgs a, int n_best) {
-  plane_sweep_best_body<false, true>(a, SweepVolume{nullptr, nullptr}, n_best);
+  plane_sweep_body<false, true, true, false>(a, {}, n_best, nullptr);
+}
+// ... their twins that also write the runner-up (§22)
+__global__ void __launch_bounds__(256) k_plane_sweep_unique(SweepArgs a, unsigned* runner) {
+  plane_sweep_body<false, false, false, true>(a, {}, 0, runner);
+}
+__global__ void __launch_bounds__(256) k_plane_sweep_census_unique(SweepArgs a, unsigned* runner) {
+  plane_sweep_body<false, true, false, true>(a, {}, 0, runner);
 }
 __global__ void __launch_bounds__(256) k_plane_sweep_best_unique(SweepArgs a, int n_best, unsigned* runner) {
-  plane_sweep_best_body<false, false, true>(a, SweepVolume{nullptr, nullptr}, n_best, runner);
+  plane_sweep_body<false, false, true, true>(a, {}, n_best, runner);
 }
 __global__ void __launch_bounds__(256) k_plane_sweep_best_census_unique(SweepArgs a, int n_best, unsigned* runner) {
-  plane_sweep_best_body<false, true, true>(a, SweepVolume{nullptr, nullptr}, n_best, runner);
+  plane_sweep_body<false, true, true, true>(a, {}, n_best, runner);
 }
+// ... and the first stage of the semi-global sweep (§19; ekf_dense_sgm.hpp has what follows it)
+__global__ void __launch_bounds__(256) k_sweep_volume(SweepArgs a, SweepVolume vol) { plane_sweep_body<true, false, false, false>(a, vol, 0, nullptr); }
+__global__ void __launch_bounds__(256) k_sweep_volume_census(SweepArgs a, SweepVolume vol) { plane_sweep_body<true, true, false, false>(a, vol, 0, nullptr); }
 __global__ void __launch_bounds__(256) k_sweep_volume_best(SweepArgs a, SweepVolume vol, int n_best) {
-  plane_sweep_best_body<true, false>(a, vol, n_best);
+  plane_sweep_body<true, false, true, false>(a, vol, n_best, nullptr);
 }
 __global__ void __launch_bounds__(256) k_sweep_volume_best_census(SweepArgs a, SweepVolume vol, int n_best) {
-  plane_sweep_best_body<true, true>(a, vol, n_best);
+  plane_sweep_body<true, true, true, false>(a, vol, n_best, nullptr);
 }
 
 struct FilterArgs {
@@ -649,6 +593,34 @@ inline bool dense_pose(const double* p, double t[3], double R[9], double q[4]) {
   return true;
 }
 
+// A view as the host holds it: K = (fx fy cx cy) and the t and R of dense_pose.
+struct DenseCam {
+  const double *K, *t, *R;
+};
+
+// A (row-major), b and K of source view s seen from reference view r
+inline void dense_relative(const DenseCam& r, const DenseCam& s, DenseSrc& o) {
+#pragma clang fp contract(off)
+  const double d[3] = {r.t[0] - s.t[0], r.t[1] - s.t[1], r.t[2] - s.t[2]};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) o.A[3 * i + j] = s.R[i] * r.R[j] + s.R[3 + i] * r.R[3 + j] + s.R[6 + i] * r.R[6 + j];
+    o.b[i] = s.R[i] * d[0] + s.R[3 + i] * d[1] + s.R[6 + i] * d[2];
+  }
+  o.fx = s.K[0]; o.fy = s.K[1]; o.cx = s.K[2]; o.cy = s.K[3];
+}
+
+// The arguments of a sweep of view cam[0] against cam[1 .. n_src], but for the pointers, which the caller adds.
+inline SweepArgs sweep_args(const DenseCam* cam, int n_src, int W, int H, int D, int radius, int trunc, double w_min, double w_max) {
+#pragma clang fp contract(off)
+  SweepArgs a{};
+  a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
+  a.fx = cam[0].K[0]; a.fy = cam[0].K[1]; a.cx = cam[0].K[2]; a.cy = cam[0].K[3];
+  a.w_min = w_min;
+  a.step = (w_max - w_min) / (double)(D - 1);
+  for (int i = 0; i < n_src; ++i) dense_relative(cam[0], cam[1 + i], a.s[i]);
+  return a;
+}
+
 #ifndef EKF_KERNELS_ONLY
 // timed kinds of §22: k_plane_sweep_unique, k_plane_sweep_census_unique, k_plane_sweep_best_unique,
 // k_plane_sweep_best_census_unique, k_sgm_winner_unique, k_depth_filter_unique
@@ -673,6 +645,7 @@ struct DenseView {
   bool has_runner = false;            // `runner` belongs to the slot's swept maps (§22): cleared wherever `swept` is
   bool seg = false;                   // the handle's segment planes are those of this slot's filtered map (§23: DenseSpeckle):
                                       // cleared wherever `filtered` is
+  DenseCam cam() const { return {K, t, R}; }
 };
 
 // Host side of one handle (`ekf_dense`).  Everything runs on the default stream of the handle's device, as the rectified
@@ -704,13 +677,11 @@ struct DenseStereo {
 
   // A (row-major) and b of source view s seen from reference view r
   void relative(const DenseView& r, const DenseView& s, DenseSrc& o) const {
-#pragma clang fp contract(off)
-    const double d[3] = {r.t[0] - s.t[0], r.t[1] - s.t[1], r.t[2] - s.t[2]};
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) o.A[3 * i + j] = s.R[i] * r.R[j] + s.R[3 + i] * r.R[3 + j] + s.R[6 + i] * r.R[6 + j];
-      o.b[i] = s.R[i] * d[0] + s.R[3 + i] * d[1] + s.R[6 + i] * d[2];
-    }
-    o.fx = s.K[0]; o.fy = s.K[1]; o.cx = s.K[2]; o.cy = s.K[3];
+    dense_relative(r.cam(), s.cam(), o);
+    source_pointers(s, o);
+  }
+  // ... and what a kernel reads of source view s
+  static void source_pointers(const DenseView& s, DenseSrc& o) {
     o.img = s.img;
     o.census = s.census;
     o.depth = s.depth;
@@ -740,47 +711,6 @@ struct DenseStereo {
     hipError_t e = census_update(ref);
     for (int i = 0; i < n_src && e == hipSuccess; ++i) e = census_update(src[i]);
     return e;
-  }
-
-  // n_best = 0: the sum over all sources (k_plane_sweep, k_plane_sweep_census); 1 .. n_src: the n_best cheapest sources per
-  // pixel and plane (§21: k_plane_sweep_best, k_plane_sweep_best_census, also for n_best = n_src).
-  hipError_t sweep(int ref, const int* src, int n_src, double w_min, double w_max, int D, int radius, int trunc, bool census = false,
-                   int n_best = 0) {
-#pragma clang fp contract(off)
-    DenseView& r = v[ref];
-    hipError_t e;
-    const size_t n = npix();
-    if ((e = r.depth.reserve(n)) != hipSuccess || (e = r.plane.reserve(n)) != hipSuccess ||
-        (e = r.cost.reserve(n)) != hipSuccess || (e = r.nviews.reserve(n)) != hipSuccess ||
-        (keep_runner && (e = r.runner.reserve(n)) != hipSuccess))
-      return e;
-    if (census && ((e = census_reserve(ref, src, n_src)) != hipSuccess || (e = census_update(ref, src, n_src)) != hipSuccess)) return e;
-    SweepArgs a{};
-    a.ref = r.img; a.ref_census = r.census; a.depth = r.depth; a.plane = r.plane; a.cost = r.cost; a.views = r.nviews;
-    a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
-    a.fx = r.K[0]; a.fy = r.K[1]; a.cx = r.K[2]; a.cy = r.K[3];
-    a.w_min = w_min;
-    a.step = (w_max - w_min) / (double)(D - 1);
-    for (int i = 0; i < n_src; ++i) relative(r, v[src[i]], a.s[i]);
-    r.swept = r.filtered = r.sgm = r.has_runner = r.seg = false;
-    const dim3 grid((unsigned)((W + kDenseTW - 1) / kDenseTW), (unsigned)((H + kDenseTH - 1) / kDenseTH));
-    unsigned* const ru = r.runner;
-    if (keep_runner && n_best > 0)                                          // the twins of §22: the same four maps, and `runner`
-      e = census ? unique_timer.run(3, [&] { k_plane_sweep_best_census_unique<<<grid, 256, 0, nullptr>>>(a, n_best, ru); })
-                 : unique_timer.run(2, [&] { k_plane_sweep_best_unique<<<grid, 256, 0, nullptr>>>(a, n_best, ru); });
-    else if (keep_runner)
-      e = census ? unique_timer.run(1, [&] { k_plane_sweep_census_unique<<<grid, 256, 0, nullptr>>>(a, ru); })
-                 : unique_timer.run(0, [&] { k_plane_sweep_unique<<<grid, 256, 0, nullptr>>>(a, ru); });
-    else if (n_best > 0)
-      e = census ? best_timer.run(1, [&] { k_plane_sweep_best_census<<<grid, 256, 0, nullptr>>>(a, n_best); })
-                 : best_timer.run(0, [&] { k_plane_sweep_best<<<grid, 256, 0, nullptr>>>(a, n_best); });
-    else
-      e = census ? census_timer.run(1, [&] { k_plane_sweep_census<<<grid, 256, 0, nullptr>>>(a); })
-                 : timer.run(0, [&] { k_plane_sweep<<<grid, 256, 0, nullptr>>>(a); });
-    if (e != hipSuccess) return e;
-    r.swept = true;
-    r.has_runner = keep_runner;
-    return hipSuccess;
   }
 
   // The one launch of k_depth_filter_points.  n_src > 0: the filter of view `ref` (swept -> filtered); xyz: the points of

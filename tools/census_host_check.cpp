@@ -1,19 +1,12 @@
 // The kernels of the census matching cost (csrc/ekf_dense_stereo.hpp: k_census, k_plane_sweep_census; csrc/ekf_dense_sgm.hpp:
 // k_sweep_volume_census, followed by the unchanged k_sgm_path and k_sgm_winner) run lane by lane on the host (DESIGN.md section
 // 20.5) by host_kernels.hpp, which says how to build and run this.  It reads the case files tools/census_host_check.py writes
-// (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs), makes the launches of DenseStereo::sweep
-// and DenseSgm::sweep for the census cost -- k_census of the reference and of every source first -- and compares bit for bit.
+// (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs), makes the launches of DenseSgm::sweep
+// for the census cost, pixel-wise and semi-global, by the launch plan it calls (ekf::sweep_launches) -- k_census of the
+// reference and of every source first -- and compares bit for bit.
 #include "host_kernels.hpp"
 
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_sgm.hpp"
-
-template <int G, int NP>
-static void path(const ekf::SgmPathArgs& p, bool first, unsigned wg) {
-  if (first)
-    launch({wg, 1, 1}, [&] { ekf::k_sgm_path<G, NP, true>(p); });
-  else
-    launch({wg, 1, 1}, [&] { ekf::k_sgm_path<G, NP, false>(p); });
-}
 
 // case file: ints kind (0 descriptor, 1 sweep, 2 semi-global sweep) W H D radius trunc n_src p1 p2 paths; doubles w_min w_max;
 // per view (0 = reference, then the sources) 4 + 7 doubles (K, pose) and W H bytes; then the oracle: kind 0 the W H
@@ -56,62 +49,28 @@ static int run(const char* path_) {
     return bad ? 1 : 0;
   }
 
-  // the host side of DenseStereo::relative, from the same dense_pose
+  // K, t and R of every view, as the library holds them
   std::vector<double> t(3 * (n_src + 1)), R(9 * (n_src + 1));
+  std::vector<ekf::DenseCam> cam;
   for (int v = 0; v <= n_src; ++v) {
     double q[4];
     if (!ekf::dense_pose(pose[v].data(), &t[3 * v], &R[9 * v], q)) return 2;
+    cam.push_back({K[v].data(), &t[3 * v], &R[9 * v]});
   }
   std::vector<float> depth(n);
   std::vector<int> plane(n);
   std::vector<unsigned> cost(n), C(elems), S(elems);
   std::vector<unsigned char> views(n), V(elems);
-  ekf::SweepArgs a{};
-  a.ref = img[0].data(); a.ref_census = T[0].data();
+  ekf::SweepArgs a = ekf::sweep_args(cam.data(), n_src, W, H, D, radius, trunc, par[0], par[1]);
+  a.ref_census = T[0].data();                             // and no image: the census sweeps read none
   a.depth = depth.data(); a.plane = plane.data(); a.cost = cost.data(); a.views = views.data();
-  a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
-  a.fx = K[0][0]; a.fy = K[0][1]; a.cx = K[0][2]; a.cy = K[0][3];
-  a.w_min = par[0];
-  a.step = (par[1] - par[0]) / (double)(D - 1);
-  for (int v = 1; v <= n_src; ++v) {
-    ekf::DenseSrc& o = a.s[v - 1];
-    const double *Rr = &R[0], *Rs = &R[9 * v];
-    const double d[3] = {t[0] - t[3 * v], t[1] - t[3 * v + 1], t[2] - t[3 * v + 2]};
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) o.A[3 * i + j] = Rs[i] * Rr[j] + Rs[3 + i] * Rr[3 + j] + Rs[6 + i] * Rr[6 + j];
-      o.b[i] = Rs[i] * d[0] + Rs[3 + i] * d[1] + Rs[6 + i] * d[2];
-    }
-    o.fx = K[v][0]; o.fy = K[v][1]; o.cx = K[v][2]; o.cy = K[v][3];
-    o.img = nullptr;                                      // the census sweeps read no image
-    o.census = T[v].data();
-    o.depth = nullptr;
-  }
-  a.ref = nullptr;
+  for (int v = 1; v <= n_src; ++v) a.s[v - 1].census = T[v].data();
+  ekf::sweep_launches(a, {C.data(), V.data()}, S.data(), {true, 0, nullptr, kind == 2 ? paths : 0, p1, p2}, HostGo{});
   int bad = 0;
-  if (kind == 1) {
-    launch(tiles, [&] { ekf::k_plane_sweep_census(a); });
-  } else {
-    const ekf::SweepVolume vol{C.data(), V.data()};
-    launch(tiles, [&] { ekf::k_sweep_volume_census(a, vol); });
+  if (kind == 2) {
     std::vector<unsigned> planes(elems);                  // as ekf_dense_get_volume delivers a volume
     ekf::sgm_volume_to_planes(C.data(), planes.data(), n, D);
     bad += differs("raw volume", planes, w_C);
-    for (int i = 0; i < paths; ++i) {                     // DenseSgm::sweep's choice of grid and instantiation
-      const ekf::SgmPathArgs p{C.data(), S.data(), W, H, D, p1, p2, ekf::kSgmDir[i][0], ekf::kSgmDir[i][1]};
-      const bool diag = p.dx != 0 && p.dy != 0;
-      const int nlines = diag ? W + H - 1 : (p.dy == 0 ? H : W);
-      const int G = D <= 16 ? 16 : 64;
-      const unsigned wg = (unsigned)((nlines + 256 / G - 1) / (256 / G));
-      const int np = (D + 63) / 64;
-      if (G == 16) path<16, 1>(p, i == 0, wg);
-      else if (np <= 1) path<64, 1>(p, i == 0, wg);
-      else if (np <= 2) path<64, 2>(p, i == 0, wg);
-      else if (np <= 4) path<64, 4>(p, i == 0, wg);
-      else if (np <= 8) path<64, 8>(p, i == 0, wg);
-      else path<64, 16>(p, i == 0, wg);
-    }
-    const ekf::SgmWinnerArgs w{S.data(), V.data(), a};
-    launch({(unsigned)((n + 255) / 256), 1, 1}, [&] { ekf::k_sgm_winner(w); });
     ekf::sgm_volume_to_planes(S.data(), planes.data(), n, D);
     bad += differs("aggregated volume", planes, w_S);
   }

@@ -1,9 +1,10 @@
 // The two kernels of csrc/ekf_dense_stereo.hpp run lane by lane on the host by host_kernels.hpp,
 // which says how to build and run this.  It reads the case files tools/dense_host_check.py writes (inputs in buffers of
-// exactly the device's sizes, and the numpy oracle's outputs) and compares bit for bit.
+// exactly the device's sizes, and the numpy oracle's outputs), makes the library's launches of a pixel-wise sweep
+// (ekf::sweep_launches, csrc/ekf_dense_sgm.hpp) and of the filter, and compares bit for bit.
 #include "host_kernels.hpp"
 
-#include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_stereo.hpp"
+#include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_sgm.hpp"
 
 // case file: ints W H D radius trunc n_src min_agree; doubles w_min w_max rel_tol; per view (0 = reference, then the
 // sources) 4 + 7 doubles (K, pose) and W H bytes; the sources' swept depths; then the oracle: depth plane cost views of the
@@ -34,37 +35,24 @@ static int run(const char* path) {
   const auto w_fpts = take<double>(f, 3 * n);
   std::fclose(f);
 
-  // the host side of DenseStereo::relative, from the same dense_pose
+  // K, t and R of every view, as the library holds them
   std::vector<double> t(3 * (n_src + 1)), R(9 * (n_src + 1));
+  std::vector<ekf::DenseCam> cam;
   for (int v = 0; v <= n_src; ++v) {
     double q[4];
     if (!ekf::dense_pose(pose[v].data(), &t[3 * v], &R[9 * v], q)) return 2;
+    cam.push_back({K[v].data(), &t[3 * v], &R[9 * v]});
   }
-  auto relative = [&](int v, ekf::DenseSrc& o) {
-    const double *Rr = &R[0], *Rs = &R[9 * v];
-    const double d[3] = {t[0] - t[3 * v], t[1] - t[3 * v + 1], t[2] - t[3 * v + 2]};
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) o.A[3 * i + j] = Rs[i] * Rr[j] + Rs[3 + i] * Rr[3 + j] + Rs[6 + i] * Rr[6 + j];
-      o.b[i] = Rs[i] * d[0] + Rs[3 + i] * d[1] + Rs[6 + i] * d[2];
-    }
-    o.fx = K[v][0]; o.fy = K[v][1]; o.cx = K[v][2]; o.cy = K[v][3];
-    o.img = img[v].data();
-    o.depth = src_depth[v - 1].data();
-  };
 
   std::vector<float> depth(n), fdepth(n);
   std::vector<int> plane(n), fplane(n);
   std::vector<unsigned> cost(n);
   std::vector<unsigned char> views(n);
   std::vector<double> pts(3 * n), fpts(3 * n);
-  ekf::SweepArgs a{};
+  ekf::SweepArgs a = ekf::sweep_args(cam.data(), n_src, W, H, D, radius, trunc, par[0], par[1]);
   a.ref = img[0].data(); a.depth = depth.data(); a.plane = plane.data(); a.cost = cost.data(); a.views = views.data();
-  a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
-  a.fx = K[0][0]; a.fy = K[0][1]; a.cx = K[0][2]; a.cy = K[0][3];
-  a.w_min = par[0];
-  a.step = (par[1] - par[0]) / (double)(D - 1);
-  for (int v = 1; v <= n_src; ++v) relative(v, a.s[v - 1]);
-  launch({(unsigned)((W + ekf::kDenseTW - 1) / ekf::kDenseTW), (unsigned)((H + ekf::kDenseTH - 1) / ekf::kDenseTH), 1}, [&] { ekf::k_plane_sweep(a); });
+  for (int v = 1; v <= n_src; ++v) a.s[v - 1].img = img[v].data();
+  ekf::sweep_launches(a, {}, nullptr, {false, 0, nullptr, 0, 0, 0}, HostGo{});
 
   ekf::FilterArgs fa{};
   fa.depth = depth.data(); fa.plane = plane.data(); fa.out_depth = fdepth.data(); fa.out_plane = fplane.data(); fa.xyz = nullptr;
@@ -72,7 +60,10 @@ static int run(const char* path) {
   fa.fx = K[0][0]; fa.fy = K[0][1]; fa.cx = K[0][2]; fa.cy = K[0][3];
   std::copy(&R[0], &R[9], fa.R);
   std::copy(&t[0], &t[3], fa.t);
-  for (int v = 1; v <= n_src; ++v) relative(v, fa.s[v - 1]);
+  for (int v = 1; v <= n_src; ++v) {
+    ekf::dense_relative(cam[0], cam[v], fa.s[v - 1]);
+    fa.s[v - 1].depth = src_depth[v - 1].data();
+  }
   const Idx3 grid1 = {(unsigned)((n + 255) / 256), 1, 1};
   launch(grid1, [&] { ekf::k_depth_filter_points(fa); });
   fa.n_src = 0; fa.out_depth = nullptr; fa.out_plane = nullptr;

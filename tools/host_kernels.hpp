@@ -64,6 +64,16 @@ static void launch(Idx3 grid, F body) {
   for (auto& l : lanes) l.join();
 }
 
+// The launcher that a launch plan of csrc takes (ekf::sweep_launches): the library's times and launches, this one runs the
+// kernel the plan chose on the grid it chose.  0: made, as every launch here is.
+struct HostGo {
+  template <typename Grid, typename Kernel, typename... Args>
+  int operator()(int, Grid grid, Kernel kernel, const Args&... args) const {
+    launch({grid.x, grid.y, 1}, [&] { kernel(args...); });
+    return 0;
+  }
+};
+
 template <typename T>
 static std::vector<T> take(FILE* f, size_t n) {
   std::vector<T> v(n);

@@ -3,30 +3,21 @@
 // csrc/ekf_dense_sgm.hpp: k_sgm_winner_unique behind the unchanged volume and path kernels) run lane by lane on the host
 //  by host_kernels.hpp, which says how to build and run this.  It reads the case files
 // tools/unique_host_check.py writes (inputs in buffers of exactly the device's sizes, and the numpy oracle's outputs), makes
-// the launches of DenseStereo::sweep, DenseSgm::sweep and DenseStereo::filter_points with the switch on, and compares bit for
-// bit: the four existing maps and the runner-up of a sweep, the filtered depth and plane of a filter.
+// the launches of DenseSgm::sweep (by the launch plan it calls, ekf::sweep_launches) and DenseStereo::filter_points with the
+// switch on, and compares bit for bit: the four existing maps and the runner-up of a sweep, the filtered depth and plane of a filter.
 #include "host_kernels.hpp"
 
 #include "../ekf-monoslam_for_3d-reconstruction_amd/csrc/ekf_dense_sgm.hpp"
 
-template <int G, int NP>
-static void path(const ekf::SgmPathArgs& p, bool first, unsigned wg) {
-  if (first)
-    launch({wg, 1, 1}, [&] { ekf::k_sgm_path<G, NP, true>(p); });
-  else
-    launch({wg, 1, 1}, [&] { ekf::k_sgm_path<G, NP, false>(p); });
-}
-
-// the host side of DenseStereo::relative, from the same dense_pose: view v seen from view 0
-static bool relative(const std::vector<std::vector<double>>& K, const std::vector<std::vector<double>>& pose, int v, ekf::DenseSrc& o) {
-  double tr[3], Rr[9], ts[3], Rs[9], q[4];
-  if (!ekf::dense_pose(pose[0].data(), tr, Rr, q) || !ekf::dense_pose(pose[v].data(), ts, Rs, q)) return false;
-  const double d[3] = {tr[0] - ts[0], tr[1] - ts[1], tr[2] - ts[2]};
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) o.A[3 * i + j] = Rs[i] * Rr[j] + Rs[3 + i] * Rr[3 + j] + Rs[6 + i] * Rr[6 + j];
-    o.b[i] = Rs[i] * d[0] + Rs[3 + i] * d[1] + Rs[6 + i] * d[2];
+// K, t and R of every view, as the library holds them (t and R live in tR: 12 doubles a view); false: not a pose
+static bool cams(const std::vector<std::vector<double>>& K, const std::vector<std::vector<double>>& pose, std::vector<double>& tR,
+                 std::vector<ekf::DenseCam>& cam) {
+  tR.resize(12 * pose.size());
+  for (size_t v = 0; v < pose.size(); ++v) {
+    double q[4];
+    if (!ekf::dense_pose(pose[v].data(), &tR[12 * v], &tR[12 * v + 3], q)) return false;
+    cam.push_back({K[v].data(), &tR[12 * v], &tR[12 * v + 3]});
   }
-  o.fx = K[v][0]; o.fy = K[v][1]; o.cx = K[v][2]; o.cy = K[v][3];
   return true;
 }
 
@@ -58,54 +49,23 @@ static int run_sweep(FILE* f, const char* path_) {
     const ekf::CensusArgs c{img[v].data(), T[v].data(), W, H};
     launch(tiles, [&] { ekf::k_census(c); });
   }
+  std::vector<double> tR;
+  std::vector<ekf::DenseCam> cam;
+  if (!cams(K, pose, tR, cam)) return 2;
   std::vector<float> depth(n);
   std::vector<int> plane(n);
   std::vector<unsigned> cost(n), runner(n), C(elems), S(elems);
   std::vector<unsigned char> views(n), V(elems);
-  ekf::SweepArgs a{};
-  a.ref = census ? nullptr : img[0].data();               // each cost reads its own inputs alone
-  a.ref_census = census ? T[0].data() : nullptr;
+  ekf::SweepArgs a = ekf::sweep_args(cam.data(), n_src, W, H, D, radius, trunc, par[0], par[1]);
   a.depth = depth.data(); a.plane = plane.data(); a.cost = cost.data(); a.views = views.data();
-  a.W = W; a.H = H; a.D = D; a.radius = radius; a.trunc = trunc; a.n_src = n_src;
-  a.fx = K[0][0]; a.fy = K[0][1]; a.cx = K[0][2]; a.cy = K[0][3];
-  a.w_min = par[0];
-  a.step = (par[1] - par[0]) / (double)(D - 1);
-  for (int v = 1; v <= n_src; ++v) {
-    ekf::DenseSrc& o = a.s[v - 1];
-    if (!relative(K, pose, v, o)) return 2;
-    o.img = census ? nullptr : img[v].data();
-    o.census = census ? T[v].data() : nullptr;
-    o.depth = nullptr;
-  }
-  unsigned* const ru = runner.data();
-  if (paths == 0) {
-    if (n_best > 0 && census) launch(tiles, [&] { ekf::k_plane_sweep_best_census_unique(a, n_best, ru); });
-    else if (n_best > 0) launch(tiles, [&] { ekf::k_plane_sweep_best_unique(a, n_best, ru); });
-    else if (census) launch(tiles, [&] { ekf::k_plane_sweep_census_unique(a, ru); });
-    else launch(tiles, [&] { ekf::k_plane_sweep_unique(a, ru); });
+  if (census) {                                           // each cost gets its own inputs alone
+    a.ref_census = T[0].data();
+    for (int v = 1; v <= n_src; ++v) a.s[v - 1].census = T[v].data();
   } else {
-    const ekf::SweepVolume vol{C.data(), V.data()};
-    if (n_best > 0 && census) launch(tiles, [&] { ekf::k_sweep_volume_best_census(a, vol, n_best); });
-    else if (n_best > 0) launch(tiles, [&] { ekf::k_sweep_volume_best(a, vol, n_best); });
-    else if (census) launch(tiles, [&] { ekf::k_sweep_volume_census(a, vol); });
-    else launch(tiles, [&] { ekf::k_sweep_volume(a, vol); });
-    for (int i = 0; i < paths; ++i) {                     // DenseSgm::sweep's choice of grid and instantiation
-      const ekf::SgmPathArgs p{C.data(), S.data(), W, H, D, p1, p2, ekf::kSgmDir[i][0], ekf::kSgmDir[i][1]};
-      const bool diag = p.dx != 0 && p.dy != 0;
-      const int nlines = diag ? W + H - 1 : (p.dy == 0 ? H : W);
-      const int G = D <= 16 ? 16 : 64;
-      const unsigned wg = (unsigned)((nlines + 256 / G - 1) / (256 / G));
-      const int np = (D + 63) / 64;
-      if (G == 16) path<16, 1>(p, i == 0, wg);
-      else if (np <= 1) path<64, 1>(p, i == 0, wg);
-      else if (np <= 2) path<64, 2>(p, i == 0, wg);
-      else if (np <= 4) path<64, 4>(p, i == 0, wg);
-      else if (np <= 8) path<64, 8>(p, i == 0, wg);
-      else path<64, 16>(p, i == 0, wg);
-    }
-    const ekf::SgmWinnerArgs w{S.data(), V.data(), a};
-    launch({(unsigned)((n + 255) / 256), 1, 1}, [&] { ekf::k_sgm_winner_unique(w, ru); });
+    a.ref = img[0].data();
+    for (int v = 1; v <= n_src; ++v) a.s[v - 1].img = img[v].data();
   }
+  ekf::sweep_launches(a, {C.data(), V.data()}, S.data(), {census != 0, n_best, runner.data(), paths, p1, p2}, HostGo{});
   const int bad = differs("depth", depth, w_depth) + differs("plane", plane, w_plane) + differs("cost", cost, w_cost) +
                   differs("views", views, w_views) + differs("runner-up", runner, w_runner);
   size_t absent = 0;
@@ -142,8 +102,11 @@ static int run_filter(FILE* f, const char* path_) {
   a.depth = depth.data(); a.plane = plane.data(); a.out_depth = fdepth.data(); a.out_plane = fplane.data(); a.xyz = nullptr;
   a.W = W; a.H = H; a.n_src = n_src; a.min_agree = min_agree; a.rel_tol = rel_tol;
   a.fx = K[0][0]; a.fy = K[0][1]; a.cx = K[0][2]; a.cy = K[0][3];
+  std::vector<double> tR;
+  std::vector<ekf::DenseCam> cam;
+  if (!cams(K, pose, tR, cam)) return 2;
   for (int v = 1; v <= n_src; ++v) {
-    if (!relative(K, pose, v, a.s[v - 1])) return 2;
+    ekf::dense_relative(cam[0], cam[v], a.s[v - 1]);
     a.s[v - 1].depth = sdepth[v - 1].data();
   }
   const unsigned *c1 = cost.data(), *c2 = runner.data();
