@@ -16,3 +16,4 @@ from .keyframes import KeyframeSelector, KeyframeRecorder, KeyframeRecord, Keyfr
 from .dense import DenseStereo, DepthMap, depth_maps_from_recording  # noqa: F401
 from .fusion import Mesh, TsdfVolume, mesh_from_recording, read_mesh_ply, weld, write_mesh_ply  # noqa: F401
 from .fusion import Render, audit_recording, shade  # noqa: F401
+from .fusion import IndexedMesh  # noqa: F401

@@ -233,6 +233,9 @@ _PROTOS = {
     "ekf_colour_get_mesh": (C.c_int, [_P, _P, C.c_ulonglong]),
     "ekf_colour_get_profile": (C.c_int, [_P, _P, _P]),
     "ekf_colour_get_render": (C.c_int, [_P, _P]),
+    "ekf_mesh_weld": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "ekf_mesh_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
+    "ekf_mesh_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

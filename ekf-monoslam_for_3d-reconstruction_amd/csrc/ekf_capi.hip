@@ -36,6 +36,7 @@
 #include "ekf_dense_speckle.hpp"
 #include "ekf_fusion.hpp"
 #include "ekf_raycast.hpp"
+#include "ekf_mesh.hpp"
 
 namespace ekf {
 
@@ -5863,6 +5864,7 @@ int ekf_dense_get_speckle_profile(const ekf_dense* h, double* kernel_ms, long lo
 struct ekf_fusion {
   ekf::TsdfFusion* impl;
   ekf::TsdfRaycast rc;                // the last render of the volume (ekf_raycast_*)
+  ekf::TsdfMesh mesh;                 // the last weld of the volume's mesh (ekf_mesh_*)
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6131,6 +6133,7 @@ int ekf_colour_get_mesh(ekf_fusion* h, unsigned char* bgr, unsigned long long ma
 int ekf_fusion_profile(ekf_fusion* h, int enable) {
   if (!h) return EKF_ERR_ARG;
   h->impl->timer.enable(enable != 0);   // the four kinds of the fusion, the two of the ray caster and the three of colour
+  h->mesh.timer.enable(enable != 0);    // the five of the weld
   return EKF_OK;
 }
 
@@ -6246,6 +6249,59 @@ int ekf_colour_get_render(ekf_fusion* h, unsigned char* bgr) {
 int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->impl->timer.read(kernel_ms, launches, 4, 2);
+  return EKF_OK;
+}
+
+// ---- the welded mesh of the volume and its vertex normals -------------------------------------------------
+int ekf_mesh_weld(ekf_fusion* h, int min_count, int normals, unsigned long long* n_vert, unsigned long long* n_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (min_count < 1 || min_count > ekf::kFusionMaxMaps || (normals != 0 && normals != 1) || !n_vert || !n_tri) {
+    f->err = "ekf_mesh_weld: min_count 1..65535, normals 0 or 1, n_vert and n_tri not NULL";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->mesh.weld(*f, min_count, normals != 0));
+  *n_vert = h->mesh.n_vert;
+  *n_tri = h->mesh.n_tri;
+  return EKF_OK;
+}
+
+int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                 unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfMesh& m = h->mesh;
+  if (bgr && !f->colour) {
+    f->err = "ekf_mesh_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_ARG;
+  }
+  if (!m.current(*f)) {
+    f->err = "ekf_mesh_get: no ekf_mesh_weld since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  if (normal && !m.has_normals) {
+    f->err = "ekf_mesh_get: normal must be NULL after an ekf_mesh_weld without normals";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(m.n_vert, max_vert), nc = (size_t)std::min(m.n_tri, max_tri) * 3;
+  HIPCHK(hipSetDevice(f->device));
+  if (nv > 0) {
+    if (xyz) HIPCHK(hipMemcpy(xyz, m.xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (grey) HIPCHK(hipMemcpy(grey, m.grey, nv, hipMemcpyDeviceToHost));
+    if (bgr) HIPCHK(hipMemcpy(bgr, m.bgr, nv * 3, hipMemcpyDeviceToHost));
+    if (normal) HIPCHK(hipMemcpy(normal, m.normal, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (key) HIPCHK(hipMemcpy(key, m.key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  }
+  if (nc > 0 && faces) HIPCHK(hipMemcpy(faces, m.faces, nc * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_mesh_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->mesh.timer.read(kernel_ms, launches, 0, ekf::kMeshKinds);
   return EKF_OK;
 }
 

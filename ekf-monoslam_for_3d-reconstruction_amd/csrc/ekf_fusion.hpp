@@ -359,6 +359,7 @@ struct TsdfFusion {
   DevBuf<unsigned char> m_grey, m_bgr;          // m_bgr: three bytes a vertex, colour volumes only
   unsigned long long n_tri = 0;
   bool mesh_valid = false;            // an extract since the volume last changed
+  int mesh_count = 0;                 // the min_count of that extract (ekf_mesh.hpp welds the soup it finds, if it is the one asked for)
   unsigned long long changes = 0;     // counts the changes of the volume (integrate, reset, ekf_fusion_set_volume): ekf_raycast.hpp
   int maps = 0;                       // maps integrated since the last reset (or what ekf_fusion_set_volume said)
   // k_tsdf_integrate, k_tsdf_count, k_tsdf_scan, k_tsdf_emit; 4, 5: ekf_raycast.hpp; 6, 7, 8: k_tsdf_integrate_colour,
@@ -448,6 +449,7 @@ struct TsdfFusion {
       }
     }
     n_tri = total;
+    mesh_count = min_count;
     mesh_valid = true;
     return hipSuccess;
   }

@@ -4,7 +4,8 @@
 over a rectified recording.  ``TsdfVolume.raycast`` / ``raycast_view`` mirror ``ekf_raycast_*`` (§17): the volume seen from a
 pose as a depth, a normal and a grey image; ``shade`` turns one into a picture and ``audit_recording`` compares the
 reconstruction of a recording with its own key frames.  ``TsdfVolume(..., colour=True)`` is a colour volume (§18): meshes,
-renders and audits then carry B, G, R beside the grey.
+renders and audits then carry B, G, R beside the grey.  ``TsdfVolume.weld`` mirrors ``ekf_mesh_*`` (§24): the same indexed mesh
+welded on the device, with per-vertex normals on request.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ MAX_DIM, MAX_VOXELS, MAX_MAPS = 1024, 1 << 28, 65535
 KERNELS = ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")
 RAYCAST_KERNELS = ("k_tsdf_mean", "k_tsdf_raycast")
 COLOUR_KERNELS = ("k_tsdf_integrate_colour", "k_tsdf_colour_vertices", "k_tsdf_raycast_colour")
+MESH_KERNELS = ("k_mesh_cells", "k_mesh_edges", "k_tsdf_scan", "k_mesh_vertices", "k_mesh_faces")
 
 
 @dataclass
@@ -30,6 +32,18 @@ class Mesh:
     key: np.ndarray                # (n, 3) uint64: equal keys are bit-equal vertices
     grey: np.ndarray               # (n, 3) uint8
     colour: Optional[np.ndarray] = None       # (n, 3, 3) uint8, B G R of each vertex: colour volumes only
+
+
+@dataclass
+class IndexedMesh:
+    """The welded mesh of ``TsdfVolume.weld``: one vertex per distinct key of the soup, by ascending key; what ``weld`` makes
+    of ``TsdfVolume.extract`` on the host, bit for bit."""
+    vertices: np.ndarray           # (m, 3) float64
+    faces: np.ndarray              # (n, 3) uint32 into vertices, in the soup's triangle order
+    grey: np.ndarray               # (m,) uint8
+    colour: Optional[np.ndarray] = None       # (m, 3) uint8, B G R: colour volumes only
+    normals: Optional[np.ndarray] = None      # (m, 3) float32, unit, towards free space (0 0 0: no gradient): ``normals=True`` only
+    key: Optional[np.ndarray] = None          # (m,) uint64, ascending
 
 
 @dataclass
@@ -74,6 +88,9 @@ class RecordingMesh:
     trunc: float
     maps: list                     # the DepthMaps that were fused
     colour: Optional[np.ndarray] = None       # (m, 3) uint8, B G R: colour recordings only
+    # (m, 3) float32 vertex normals, set by ``normals=True`` only.  An attribute beside the fields, not a field: ``colour`` stays
+    # the last positional argument of the constructor
+    normals = None
 
 
 class TsdfVolume(capi.Handle):
@@ -153,6 +170,21 @@ class TsdfVolume(capi.Handle):
             self._check(self._lib.ekf_colour_get_mesh(self._h, _ptr(m.colour), n))
         return m
 
+    def weld(self, min_count: int = 1, normals: bool = False) -> IndexedMesh:
+        """The indexed mesh, welded on the device: ``weld(self.extract(min_count))`` bit for bit, without the
+        soup's way over the host and without a sort.  It extracts first unless the handle holds the soup of this
+        ``min_count``; ``extract``'s mesh stays valid.  ``normals``: unit vertex normals from the gradient of the mean field.
+        The first weld allocates 4 bytes a voxel and 1 byte a cell of scratch on the device."""
+        nv, nt = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self._lib.ekf_mesh_weld(self._h, int(min_count), 1 if normals else 0, C.byref(nv), C.byref(nt)))
+        nv, nt = int(nv.value), int(nt.value)
+        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
+                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
+                        np.zeros(nv, np.uint64))
+        self._check(self._lib.ekf_mesh_get(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour), _ptr(m.normals),
+                                           _ptr(m.key), nv, nt))
+        return m
+
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
         self._check(self._lib.ekf_raycast_get(self._h, None, None, None, C.byref(w), C.byref(h)))
@@ -198,6 +230,12 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_colour_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(COLOUR_KERNELS)}
 
+    def get_mesh_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the five launches of a weld since the last ``profile()``."""
+        ms, cnt = np.zeros(5, np.float64), np.zeros(5, np.int64)
+        self._check(self._lib.ekf_mesh_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(MESH_KERNELS)}
+
     def get_profile(self) -> dict:
         """HIP-event milliseconds and launch counts of the four kernels since the last ``profile()``."""
         ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
@@ -218,27 +256,31 @@ def weld(mesh: Mesh, colour: bool = False):
     return out + (mesh.colour.reshape(-1, 3)[first],)
 
 
-def write_mesh_ply(path: str, vertices, faces, grey, colour=None) -> None:
+def write_mesh_ply(path: str, vertices, faces, grey, colour=None, normals=None) -> None:
     """ASCII PLY: vertices ``x y z`` as doubles with ``intensity``, faces as ``list uchar int vertex_indices``.  ``colour``
-    ((m, 3), B, G, R) adds ``red green blue`` after the intensity."""
+    ((m, 3), B, G, R) adds ``red green blue`` after the intensity; ``normals`` ((m, 3) float32) adds ``nx ny nz`` as the last
+    vertex properties, written with ``%.9g`` (which a float32 survives)."""
     rgb = "" if colour is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    if normals is not None:
+        rgb += "property float nx\nproperty float ny\nproperty float nz\n"
     with open(path, "w") as fh:
         fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
                  "property uchar intensity\n%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
                  % (len(vertices), rgb, len(faces)))
+        tail = [""] * len(vertices) if normals is None else [" %.9g %.9g %.9g" % (float(a), float(b), float(c)) for a, b, c in normals]
         if colour is None:
-            for (x, y, z), g in zip(vertices, grey):
-                fh.write("%.17g %.17g %.17g %d\n" % (x, y, z, int(g)))
+            for (x, y, z), g, t in zip(vertices, grey, tail):
+                fh.write("%.17g %.17g %.17g %d%s\n" % (x, y, z, int(g), t))
         else:
-            for (x, y, z), g, (b, gr, r) in zip(vertices, grey, colour):
-                fh.write("%.17g %.17g %.17g %d %d %d %d\n" % (x, y, z, int(g), int(r), int(gr), int(b)))
+            for (x, y, z), g, (b, gr, r), t in zip(vertices, grey, colour, tail):
+                fh.write("%.17g %.17g %.17g %d %d %d %d%s\n" % (x, y, z, int(g), int(r), int(gr), int(b), t))
         for a, b, c in faces:
             fh.write("3 %d %d %d\n" % (a, b, c))
 
 
-def read_mesh_ply(path: str, colour: bool = False):
-    """What ``write_mesh_ply`` wrote: (vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8), and with ``colour`` the
-    (m, 3) uint8 colours swapped back to B, G, R order."""
+def read_mesh_ply(path: str, colour: bool = False, normals: bool = False):
+    """What ``write_mesh_ply`` wrote: (vertices (m, 3) float64, faces (n, 3) int64, grey (m,) uint8), with ``colour`` the
+    (m, 3) uint8 colours swapped back to B, G, R order, and with ``normals`` the (m, 3) float32 normals last."""
     with open(path) as fh:
         lines = fh.read().splitlines()
     end = lines.index("end_header")
@@ -249,11 +291,17 @@ def read_mesh_ply(path: str, colour: bool = False):
     out = (np.array([[float(t) for t in r[:3]] for r in rows], np.float64).reshape(-1, 3),
            np.array([[int(t) for t in r[1:4]] for r in faces], np.int64).reshape(-1, 3),
            np.array([int(r[3]) for r in rows], np.uint8))
-    if not colour:
-        return out
-    if "property uchar red" not in lines[:end]:
-        raise ValueError("%s has no colour" % path)
-    return out + (np.array([[int(r[6]), int(r[5]), int(r[4])] for r in rows], np.uint8).reshape(-1, 3),)
+    has_colour = "property uchar red" in lines[:end]
+    if colour:
+        if not has_colour:
+            raise ValueError("%s has no colour" % path)
+        out += (np.array([[int(r[6]), int(r[5]), int(r[4])] for r in rows], np.uint8).reshape(-1, 3),)
+    if normals:
+        if "property float nx" not in lines[:end]:
+            raise ValueError("%s has no normals" % path)
+        at = 7 if has_colour else 4
+        out += (np.array([[float(t) for t in r[at:at + 3]] for r in rows], np.float64).astype(np.float32).reshape(-1, 3),)
+    return out
 
 
 def auto_grid(points, voxel: Optional[float] = None, bounds=None, trunc: Optional[float] = None):
@@ -301,7 +349,7 @@ def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
 
 def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                         trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                        **sweep_kwargs) -> RecordingMesh:
+                        weld: str = "host", normals: bool = False, **sweep_kwargs) -> RecordingMesh:
     """``dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)``, then every filtered map with its key
     frame's image into one volume (``auto_grid`` where voxel / bounds / trunc are None), extract, weld.  ``trunc`` is the
     truncation distance of the volume; the sweep's cost truncation, also called ``trunc`` there, is ``sweep_trunc`` here.
@@ -311,21 +359,34 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     plane (§21), for neighbours that do not all see every pixel of a key frame; ``uniqueness=u`` (per cent) also drops the
     pixels whose runner-up cost is within u % of the winner's (§22), for recordings with untextured surfaces;
     ``speckle=min_size`` or ``speckle=(min_size, max_diff)`` then drops from every filtered map the connected segments of fewer
-    than ``min_size`` pixels (§23), the islands that would become floating fragments of the mesh."""
+    than ``min_size`` pixels (§23), the islands that would become floating fragments of the mesh.  ``weld="device"`` welds on
+    the device (§24): the same arrays without the soup's way over the host; ``normals=True`` does so too and fills
+    ``RecordingMesh.normals``."""
+    _weld_mode(weld)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        welded = _welded(vol, min_count)
+        welded = _welded(vol, min_count, weld, normals)
     finally:
         vol.close()
-    return RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
+    out = RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
+    out.normals = welded[4]
+    return out
 
 
-def _welded(vol: TsdfVolume, min_count: int):
-    """(vertices, faces, grey, colour or None) of the volume's mesh."""
+def _weld_mode(mode):
+    if mode not in ("host", "device"):
+        raise ValueError('weld is "host" or "device"')
+
+
+def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False):
+    """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh."""
+    if mode == "device" or normals:
+        m = vol.weld(min_count, normals)
+        return m.vertices, m.faces.astype(np.int64), m.grey, m.colour, m.normals
     mesh = vol.extract(min_count)
-    return weld(mesh, True) if vol.colour else weld(mesh) + (None,)
+    return (weld(mesh, True) if vol.colour else weld(mesh) + (None,)) + (None,)
 
 
 def shade(render: Render, light=(0.0, 0.0, -1.0), albedo: bool = False) -> np.ndarray:
@@ -379,20 +440,24 @@ def grey_image(bgr) -> np.ndarray:
 
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                     trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                    **sweep_kwargs) -> RecordingAudit:
+                    weld: str = "host", normals: bool = False, **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
     frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
-    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters as they do through ``mesh_from_recording``."""
+    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…`` and ``normals=…`` the mesh, as they do
+    through ``mesh_from_recording``."""
+    _weld_mode(weld)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey, colour = _welded(vol, min_count)
+        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals)
         z_near, z_far = audit_range(maps, tr)
         h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)
                   for m, img in zip(maps, images)]
     finally:
         vol.close()
-    return RecordingAudit(RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps, colour), frames, z_near, z_far, vx / 2.0)
+    mesh = RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps, colour)
+    mesh.normals = vertex_normals
+    return RecordingAudit(mesh, frames, z_near, z_far, vx / 2.0)

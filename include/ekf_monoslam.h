@@ -1066,6 +1066,39 @@ int ekf_dense_speckle_host(ekf_dense* h, float* depth, int* plane, int min_size,
                            unsigned int* size);
 int ekf_dense_get_speckle_profile(const ekf_dense* h, double* kernel_ms, long long* launches);
 
+/* ---- the welded mesh of the TSDF volume and its vertex normals -----------------------------------------
+ * ekf_fusion_get_mesh delivers a triangle soup, 99 to 108 bytes a triangle, which the caller welds by sorting the vertex
+ * keys.  These additions weld on the device: a key is 8 la + d (la the linear index of the smaller end of a cell edge, d in
+ * 1..7 the bits of the steps to its other end), so the welded vertices are the edges that carry a vertex in (la, d) order,
+ * an exclusive scan over a 7-bit mask per voxel.  Edge (la, d) carries a vertex iff sum[la] < 0 differs from sum[lb] < 0 and
+ * one of the cells that contain the edge has all eight cnt >= min_count.  The result equals the host weld of the soup bit
+ * for bit: vertices by ascending key with the coordinates, grey and colour of ekf_fusion_get_mesh / ekf_colour_get_mesh,
+ * faces[3 t + v] = the rank of key (t, v) of the soup, in the soup's triangle order.  Normals (opt-in): the mean field
+ * v = (double) sum / (double) cnt, its gradient at a voxel by central differences ((v+ - v-) * 0.5; one-sided v+ - v or
+ * v - v- where only one neighbour is in the grid with cnt >= min_count; 0.0 where none is), blended along the edge by the
+ * vertex's u, n = g(la) + u (g(lb) - g(la)), divided by sqrt((n0 n0 + n1 n1) + n2 n2) and rounded once to float; 0 0 0
+ * where that length is 0 or not finite.  They point towards free space, as the normals of ekf_raycast_get and the triangles'
+ * (B - A) x (C - A) do.  tests/mesh_oracle.py restates all of it.  Opt-in: nothing above calls it, and no result, launch,
+ * profile count or prototype above changes; ekf_abi_version() stays 6 (additions only).  The functions take an ekf_fusion
+ * handle.
+ *  - ekf_mesh_weld: if the handle holds no extract at this min_count since the volume last changed, exactly the launches of
+ *    ekf_fusion_extract first; then k_mesh_cells, k_mesh_edges, k_tsdf_scan, one 8-byte read-back, k_mesh_vertices (not for
+ *    an empty mesh) and k_mesh_faces (likewise); reports the numbers of vertices and triangles.  ekf_fusion_get_mesh and
+ *    ekf_colour_get_mesh stay valid.  The first weld allocates 4 bytes a voxel and 1 byte a cell of scratch (grow-only,
+ *    1.25 GB at 2^28 voxels).  EKF_ERR_ARG before the device is touched: min_count outside 1..65535, normals not 0 or 1, a
+ *    NULL count.  A failed allocation is EKF_ERR_DEVICE and leaves the soup and the volume as they were;
+ *  - ekf_mesh_get: the first min(n_vert, max_vert) vertices (xyz 3 doubles, grey 1 byte, bgr 3 bytes, normal 3 floats, key)
+ *    and the first min(n_tri, max_tri) triangles (faces: 3 unsigned int); every pointer may be NULL.  EKF_ERR_ARG: bgr on a
+ *    plain volume, or normal after a weld without normals.  EKF_ERR_STATE before a weld or after the volume changed since
+ *    the last one (integrate, reset, set_volume);
+ *  - ekf_mesh_get_profile: HIP-event milliseconds and launch counts of 5 kinds since the last ekf_fusion_profile:
+ *    k_mesh_cells ([0]), k_mesh_edges ([1]), the weld's k_tsdf_scan ([2]), k_mesh_vertices ([3]), k_mesh_faces ([4]).  The
+ *    other profile getters gain nothing from a weld but the launches of an extract it had to make. */
+int ekf_mesh_weld(ekf_fusion* h, int min_count, int normals, unsigned long long* n_vert, unsigned long long* n_tri);
+int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned int* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                 unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri);
+int ekf_mesh_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

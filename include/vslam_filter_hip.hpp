@@ -634,6 +634,7 @@ class DenseStereoHip {
 // on the device, extract() = marching tetrahedra into a triangle soup in a fixed order.  raycast() / raycastView() mirror
 // ekf_raycast_* (section 17): the volume seen from a pose as a depth, a normal and a grey image.  Values are plain arrays.
 // A colour volume (the constructor's `colour`, section 18, ekf_colour_*) also fills the `colour` arrays: B, G, R.
+// weld() / mesh() mirror ekf_mesh_* (section 24): the indexed mesh welded on the device, with vertex normals on request.
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -642,6 +643,16 @@ class TsdfVolumeHip {
     std::vector<unsigned char> grey;           // 3 per triangle
     std::vector<unsigned char> colour;         // 9 per triangle, B G R of each vertex: colour volumes only
     size_t triangles() const { return key.size() / 3; }
+  };
+  struct IndexedMesh {                         // one vertex per distinct key of the soup, by ascending key
+    std::vector<double> xyz;                   // 3 per vertex
+    std::vector<unsigned int> faces;           // 3 per triangle, into the vertices, in the soup's triangle order
+    std::vector<unsigned char> grey;           // 1 per vertex
+    std::vector<unsigned char> colour;         // 3 per vertex, B G R: colour volumes only
+    std::vector<float> normal;                 // 3 per vertex: unit, towards free space (0 0 0: no gradient); weld(.., true) only
+    std::vector<unsigned long long> key;       // 1 per vertex, ascending
+    size_t vertices() const { return key.size(); }
+    size_t triangles() const { return faces.size() / 3; }
   };
   struct Volume {
     std::vector<float> sum;
@@ -705,6 +716,27 @@ class TsdfVolumeHip {
     }
     return m;
   }
+  // The indexed mesh, welded on the device: what sorting the keys of extract(min_count) gives, bit for bit.  It extracts first
+  // unless the handle holds the soup of this min_count; the mesh of extract() stays valid.  The first weld allocates 4 bytes a
+  // voxel and 1 byte a cell of scratch on the device.
+  IndexedMesh weld(int min_count = 1, bool normals = false) {
+    check(ekf_mesh_weld(f_, min_count, normals ? 1 : 0, &weld_vertices_, &weld_triangles_));
+    weld_normals_ = normals;
+    return mesh();
+  }
+  // the arrays of the last weld() again
+  IndexedMesh mesh() {
+    IndexedMesh m;
+    const size_t nv = (size_t)weld_vertices_, nt = (size_t)weld_triangles_;
+    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
+    if (colour_) m.colour.resize(nv * 3);
+    if (weld_normals_) m.normal.resize(nv * 3);
+    check(ekf_mesh_get(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
+                       weld_normals_ ? m.normal.data() : nullptr, m.key.data(), weld_vertices_, weld_triangles_));
+    return m;
+  }
+  // HIP-event milliseconds and launch counts of k_mesh_cells, k_mesh_edges, the weld's k_tsdf_scan, k_mesh_vertices, k_mesh_faces
+  void getMeshProfile(double kernel_ms[5], long long launches[5]) { check(ekf_mesh_get_profile(f_, kernel_ms, launches)); }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
@@ -742,5 +774,7 @@ class TsdfVolumeHip {
   }
   size_t n_;
   bool colour_;
+  unsigned long long weld_vertices_ = 0, weld_triangles_ = 0;
+  bool weld_normals_ = false;
   ekf_fusion* f_ = nullptr;
 };
