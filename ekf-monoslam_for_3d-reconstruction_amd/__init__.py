@@ -17,3 +17,4 @@ from .dense import DenseStereo, DepthMap, depth_maps_from_recording  # noqa: F40
 from .fusion import Mesh, TsdfVolume, mesh_from_recording, read_mesh_ply, weld, write_mesh_ply  # noqa: F401
 from .fusion import Render, audit_recording, shade  # noqa: F401
 from .fusion import IndexedMesh  # noqa: F401
+from .fusion import MeshComponents  # noqa: F401

@@ -236,6 +236,11 @@ _PROTOS = {
     "ekf_mesh_weld": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "ekf_mesh_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
     "ekf_mesh_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_components_find": (C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
+    "ekf_components_get": (C.c_int, [_P, _P, _P, C.c_ulonglong]),
+    "ekf_components_prune": (C.c_int, [_P, C.c_uint, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "ekf_components_get_pruned": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
+    "ekf_components_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

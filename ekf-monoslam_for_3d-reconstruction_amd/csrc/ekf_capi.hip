@@ -37,6 +37,7 @@
 #include "ekf_fusion.hpp"
 #include "ekf_raycast.hpp"
 #include "ekf_mesh.hpp"
+#include "ekf_mesh_components.hpp"
 
 namespace ekf {
 
@@ -5865,6 +5866,7 @@ struct ekf_fusion {
   ekf::TsdfFusion* impl;
   ekf::TsdfRaycast rc;                // the last render of the volume (ekf_raycast_*)
   ekf::TsdfMesh mesh;                 // the last weld of the volume's mesh (ekf_mesh_*)
+  ekf::TsdfComponents comp;           // that weld's components and its pruned copy
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6134,6 +6136,7 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   if (!h) return EKF_ERR_ARG;
   h->impl->timer.enable(enable != 0);   // the four kinds of the fusion, the two of the ray caster and the three of colour
   h->mesh.timer.enable(enable != 0);    // the five of the weld
+  h->comp.timer.enable(enable != 0);    // the eight of the components
   return EKF_OK;
 }
 
@@ -6302,6 +6305,100 @@ int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* gre
 int ekf_mesh_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->mesh.timer.read(kernel_ms, launches, 0, ekf::kMeshKinds);
+  return EKF_OK;
+}
+
+// ---- the connected components of the welded mesh and its pruned copy ---------------------------------------
+int ekf_components_find(ekf_fusion* h, unsigned long long* n_comp) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!n_comp) {
+    f->err = "ekf_components_find: n_comp not NULL";
+    return EKF_ERR_ARG;
+  }
+  if (!h->mesh.current(*f)) {
+    f->err = "ekf_components_find: no ekf_mesh_weld since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->comp.components(h->mesh, f->colour));
+  *n_comp = h->comp.n_comp;
+  return EKF_OK;
+}
+
+int ekf_components_get(ekf_fusion* h, unsigned* label, unsigned* size, unsigned long long max_vert) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!h->mesh.current(*f) || !h->comp.have_components(h->mesh)) {
+    f->err = "ekf_components_get: no ekf_components_find or ekf_components_prune since the last ekf_mesh_weld";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(h->mesh.n_vert, max_vert);
+  HIPCHK(hipSetDevice(f->device));
+  if (nv > 0) {
+    if (label) HIPCHK(hipMemcpy(label, h->comp.R, nv * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (size) HIPCHK(hipMemcpy(size, h->comp.L, nv * sizeof(unsigned), hipMemcpyDeviceToHost));
+  }
+  return EKF_OK;
+}
+
+int ekf_components_prune(ekf_fusion* h, unsigned min_triangles, int largest, unsigned long long* n_vert, unsigned long long* n_tri,
+                   unsigned long long* n_kept) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (min_triangles == 0 || (largest != 0 && largest != 1) || !n_vert || !n_tri || !n_kept) {
+    f->err = "ekf_components_prune: min_triangles >= 1, largest 0 or 1, n_vert, n_tri and n_kept not NULL";
+    return EKF_ERR_ARG;
+  }
+  if (!h->mesh.current(*f)) {
+    f->err = "ekf_components_prune: no ekf_mesh_weld since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->comp.prune(h->mesh, f->colour, min_triangles, largest != 0));
+  *n_vert = h->comp.n_vert;
+  *n_tri = h->comp.n_tri;
+  *n_kept = h->comp.n_kept;
+  return EKF_OK;
+}
+
+int ekf_components_get_pruned(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                        unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfComponents& m = h->comp;
+  if (bgr && !f->colour) {
+    f->err = "ekf_components_get_pruned: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_ARG;
+  }
+  if (!h->mesh.current(*f) || !m.have_pruned(h->mesh)) {
+    f->err = "ekf_components_get_pruned: no ekf_components_prune since the last ekf_mesh_weld";
+    return EKF_ERR_STATE;
+  }
+  if (normal && !m.has_normals) {
+    f->err = "ekf_components_get_pruned: normal must be NULL after an ekf_mesh_weld without normals";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(m.n_vert, max_vert), nc = (size_t)std::min(m.n_tri, max_tri) * 3;
+  HIPCHK(hipSetDevice(f->device));
+  if (nv > 0) {
+    if (xyz) HIPCHK(hipMemcpy(xyz, m.xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (grey) HIPCHK(hipMemcpy(grey, m.grey, nv, hipMemcpyDeviceToHost));
+    if (bgr) HIPCHK(hipMemcpy(bgr, m.bgr, nv * 3, hipMemcpyDeviceToHost));
+    if (normal) HIPCHK(hipMemcpy(normal, m.normal, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (key) HIPCHK(hipMemcpy(key, m.key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  }
+  if (nc > 0 && faces) HIPCHK(hipMemcpy(faces, m.faces, nc * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->comp.timer.read(kernel_ms, launches, 0, ekf::kCompKinds);
   return EKF_OK;
 }
 

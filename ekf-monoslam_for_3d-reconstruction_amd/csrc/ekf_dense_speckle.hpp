@@ -26,6 +26,7 @@
 // time; no lane ever waits for another: no flag, no spin, no ordered hand-over.
 #pragma once
 #include "ekf_dense_stereo.hpp"
+#include "ekf_union_find.hpp"
 
 namespace ekf {
 
@@ -36,69 +37,11 @@ constexpr int kSpeckleKinds = 4;                 // timed kinds: k_speckle_label
 constexpr int kSegTile = kDenseTW * kDenseTH;    // 512 pixels, two a lane as in the sweeps
 static_assert((long long)kDenseMaxDim * kDenseMaxDim <= (long long)kSpeckleMaxSize, "a linear index and a size fit 27 bits");
 
-// The accessors of the forest.  Global (the words of L that k_speckle_merge shares between workgroups): relaxed atomics of
-// agent scope, which go to the memory all CUs share and never to a CU's own L1.  Lds (the tile's forest in k_speckle_label
-// and the counters of k_speckle_count): relaxed atomics of workgroup scope, so that a lane re-reads a word another lane
-// may have lowered.  The host check (tools/speckle_host_check.cpp) defines EKF_SPECKLE_HOST_ATOMICS and the same six
-// functions with the __atomic builtins before it includes this header.
-#ifndef EKF_SPECKLE_HOST_ATOMICS
-__device__ __forceinline__ unsigned seg_global_load(const unsigned* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned seg_global_min(unsigned* p, unsigned v) {
-  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned seg_global_add(unsigned* p, unsigned v) {
-  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned seg_lds_load(const unsigned* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ unsigned seg_lds_min(unsigned* p, unsigned v) {
-  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ unsigned seg_lds_add(unsigned* p, unsigned v) {
-  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-#endif
-
-struct SegGlobal {
-  static __device__ __forceinline__ unsigned load(const unsigned* p) { return seg_global_load(p); }
-  static __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) { return seg_global_min(p, v); }
-};
-struct SegLds {
-  static __device__ __forceinline__ unsigned load(const unsigned* p) { return seg_lds_load(p); }
-  static __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) { return seg_lds_min(p, v); }
-};
-
-// The root of x.  On the way every visited word is lowered to its grandparent (path halving, by fetch_min: the word keeps
-// whatever smaller value another lane has given it meanwhile), which keeps the chains of the later calls short.
-template <typename A>
-__device__ __forceinline__ unsigned seg_find(unsigned* L, unsigned x) {
-  unsigned p = A::load(L + x);                                               // p <= x
-  while (p != x) {
-    const unsigned g = A::load(L + p);                                       // g <= p < x
-    if (g != p) A::fetch_min(L + x, g);
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-// a and b in one segment from now on.  (a, b) -> (old, lo) with old < hi = max(a, b): a + b falls with every turn.
-template <typename A>
-__device__ __forceinline__ void seg_union(unsigned* L, unsigned a, unsigned b) {
-  for (;;) {
-    a = seg_find<A>(L, a);
-    b = seg_find<A>(L, b);
-    if (a == b) return;
-    const unsigned hi = max(a, b), lo = min(a, b);
-    const unsigned old = A::fetch_min(L + hi, lo);
-    if (old == hi) return;                                                   // hi was a root and now hangs below lo
-    a = old;                                                                 // hi had been hooked to old < hi by another lane
-    b = lo;
-  }
-}
+// The accessors of the forest (SegGlobal for the words of L that k_speckle_merge shares between workgroups, SegLds for the
+// tile's forest in k_speckle_label and the counters of k_speckle_count), seg_find and seg_union: ekf_union_find.hpp, which
+// the components of the welded mesh share (ekf_mesh_components.hpp).  The host check
+// (tools/speckle_host_check.cpp) defines EKF_SPECKLE_HOST_ATOMICS and the six accessor functions with the __atomic builtins
+// before it includes this header.
 
 // Linked iff both valid and at most max_diff apart; the difference in 64 bits.
 __device__ __forceinline__ bool seg_linked(int p, int q, int max_diff) {

@@ -226,6 +226,7 @@ struct TsdfMesh {
   DevBuf<unsigned> faces;
   unsigned long long n_vert = 0, n_tri = 0;
   unsigned long long weld_changes = 0;           // TsdfFusion::changes when the weld was made
+  unsigned long long serial = 0;                 // counts the welds: what ekf_mesh_components.hpp derives from one names it
   bool valid = false, has_normals = false;
   KernelTimer<kMeshKinds> timer;
 
@@ -243,6 +244,7 @@ struct TsdfMesh {
     const unsigned nvox = (unsigned)f.nvox(), nc = f.ncell();
     const unsigned vblk = (nvox + kFusionBlock - 1) / kFusionBlock, cblk = (nc + kFusionBlock - 1) / kFusionBlock;
     valid = false;
+    ++serial;
     if ((e = cell_ok.reserve(nc)) != hipSuccess || (e = code.reserve(nvox)) != hipSuccess || (e = blk_tot.reserve(vblk)) != hipSuccess ||
         (e = blk_off.reserve((size_t)vblk + 1)) != hipSuccess) {
       (void)hipGetLastError();

@@ -5,7 +5,8 @@ over a rectified recording.  ``TsdfVolume.raycast`` / ``raycast_view`` mirror ``
 pose as a depth, a normal and a grey image; ``shade`` turns one into a picture and ``audit_recording`` compares the
 reconstruction of a recording with its own key frames.  ``TsdfVolume(..., colour=True)`` is a colour volume (§18): meshes,
 renders and audits then carry B, G, R beside the grey.  ``TsdfVolume.weld`` mirrors ``ekf_mesh_*`` (§24): the same indexed mesh
-welded on the device, with per-vertex normals on request.
+welded on the device, with per-vertex normals on request; ``TsdfVolume.components`` and ``.prune`` find its connected
+components there and drop the small ones (§25).
 """
 from __future__ import annotations
 
@@ -23,6 +24,8 @@ KERNELS = ("k_tsdf_integrate", "k_tsdf_count", "k_tsdf_scan", "k_tsdf_emit")
 RAYCAST_KERNELS = ("k_tsdf_mean", "k_tsdf_raycast")
 COLOUR_KERNELS = ("k_tsdf_integrate_colour", "k_tsdf_colour_vertices", "k_tsdf_raycast_colour")
 MESH_KERNELS = ("k_mesh_cells", "k_mesh_edges", "k_tsdf_scan", "k_mesh_vertices", "k_mesh_faces")
+COMPONENT_KERNELS = ("k_comp_init", "k_comp_union", "k_comp_count", "k_comp_largest", "k_comp_flags", "k_tsdf_scan", "k_comp_vertices",
+                     "k_comp_faces")
 
 
 @dataclass
@@ -44,6 +47,15 @@ class IndexedMesh:
     colour: Optional[np.ndarray] = None       # (m, 3) uint8, B G R: colour volumes only
     normals: Optional[np.ndarray] = None      # (m, 3) float32, unit, towards free space (0 0 0: no gradient): ``normals=True`` only
     key: Optional[np.ndarray] = None          # (m,) uint64, ascending
+
+
+@dataclass
+class MeshComponents:
+    """The connected components of the last ``TsdfVolume.weld``: two vertices are linked iff a triangle has
+    both, by index, not by coordinate."""
+    label: np.ndarray              # (m,) uint32: the least vertex index of the vertex's component
+    size: np.ndarray               # (m,) uint32: the number of triangles of that component
+    count: int                     # the number of components
 
 
 @dataclass
@@ -106,6 +118,8 @@ class TsdfVolume(capi.Handle):
         self.colour = bool(colour)
         self.dims, self.origin, self.voxel, self.trunc, self.device = (nx, ny, nz), o, float(voxel), float(trunc), int(device)
         self.shape = (nz, ny, nx)
+        self._weld_counts = (0, 0, False)       # vertices, triangles and normals of the last weld
+        self.pruned_components = 0              # the number of components the last prune kept
 
     def integrate(self, dense_stereo, slot: int, filtered: bool = True):
         """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""
@@ -178,12 +192,47 @@ class TsdfVolume(capi.Handle):
         nv, nt = C.c_ulonglong(0), C.c_ulonglong(0)
         self._check(self._lib.ekf_mesh_weld(self._h, int(min_count), 1 if normals else 0, C.byref(nv), C.byref(nt)))
         nv, nt = int(nv.value), int(nt.value)
+        self._weld_counts = (nv, nt, bool(normals))
         m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
                         np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
                         np.zeros(nv, np.uint64))
         self._check(self._lib.ekf_mesh_get(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour), _ptr(m.normals),
                                            _ptr(m.key), nv, nt))
         return m
+
+    def components(self) -> MeshComponents:
+        """The connected components of the last ``weld``, found on the device.  The first call allocates 16 bytes
+        a vertex and 4 bytes a triangle of scratch."""
+        n = C.c_ulonglong(0)
+        self._check(self._lib.ekf_components_find(self._h, C.byref(n)))
+        nv = self._weld_counts[0]
+        out = MeshComponents(np.zeros(nv, np.uint32), np.zeros(nv, np.uint32), int(n.value))
+        self._check(self._lib.ekf_components_get(self._h, _ptr(out.label), _ptr(out.size), nv))
+        return out
+
+    def prune(self, min_triangles: int = 1, largest: bool = False) -> IndexedMesh:
+        """The last ``weld`` without its small components: a component is kept iff it has at least
+        ``min_triangles`` triangles and, with ``largest``, is the one of greatest size (the least label among equals).  Vertices
+        and triangles keep their order, the kept rows are the weld's bit for bit (normals iff the weld had them), and the faces
+        are re-indexed; ``prune(1)`` is the identity.  The components are found first unless the handle holds them for this
+        weld; the weld itself stays as it was."""
+        nv, nt, nk = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self._lib.ekf_components_prune(self._h, int(min_triangles), 1 if largest else 0, C.byref(nv), C.byref(nt), C.byref(nk)))
+        nv, nt, normals = int(nv.value), int(nt.value), self._weld_counts[2]
+        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
+                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
+                        np.zeros(nv, np.uint64))
+        self._check(self._lib.ekf_components_get_pruned(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour),
+                                                  _ptr(m.normals), _ptr(m.key), nv, nt))
+        self.pruned_components = int(nk.value)
+        return m
+
+    def get_component_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the eight kinds of launch of ``components`` and ``prune`` since the last
+        ``profile()``."""
+        ms, cnt = np.zeros(8, np.float64), np.zeros(8, np.int64)
+        self._check(self._lib.ekf_components_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(COMPONENT_KERNELS)}
 
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
@@ -349,7 +398,7 @@ def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
 
 def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                         trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                        weld: str = "host", normals: bool = False, **sweep_kwargs) -> RecordingMesh:
+                        weld: str = "host", normals: bool = False, components=None, **sweep_kwargs) -> RecordingMesh:
     """``dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)``, then every filtered map with its key
     frame's image into one volume (``auto_grid`` where voxel / bounds / trunc are None), extract, weld.  ``trunc`` is the
     truncation distance of the volume; the sweep's cost truncation, also called ``trunc`` there, is ``sweep_trunc`` here.
@@ -361,13 +410,15 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     ``speckle=min_size`` or ``speckle=(min_size, max_diff)`` then drops from every filtered map the connected segments of fewer
     than ``min_size`` pixels (§23), the islands that would become floating fragments of the mesh.  ``weld="device"`` welds on
     the device (§24): the same arrays without the soup's way over the host; ``normals=True`` does so too and fills
-    ``RecordingMesh.normals``."""
-    _weld_mode(weld)
+    ``RecordingMesh.normals``.  ``components=n`` drops the connected components of the mesh of fewer than ``n`` triangles and
+    ``components="largest"`` keeps the largest one alone (§25); either welds on the device, and ``None`` makes today's
+    launches."""
+    _weld_mode(weld, components)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        welded = _welded(vol, min_count, weld, normals)
+        welded = _welded(vol, min_count, weld, normals, components)
     finally:
         vol.close()
     out = RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
@@ -375,15 +426,20 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     return out
 
 
-def _weld_mode(mode):
+def _weld_mode(mode, components=None):
     if mode not in ("host", "device"):
         raise ValueError('weld is "host" or "device"')
+    if not (components is None or components == "largest" or (isinstance(components, (int, np.integer)) and
+                                                              not isinstance(components, bool) and components >= 1)):
+        raise ValueError('components is None, an int >= 1 or "largest"')
 
 
-def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False):
+def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False, components=None):
     """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh."""
-    if mode == "device" or normals:
+    if mode == "device" or normals or components is not None:
         m = vol.weld(min_count, normals)
+        if components is not None:
+            m = vol.prune(largest=True) if components == "largest" else vol.prune(int(components))
         return m.vertices, m.faces.astype(np.int64), m.grey, m.colour, m.normals
     mesh = vol.extract(min_count)
     return (weld(mesh, True) if vol.colour else weld(mesh) + (None,)) + (None,)
@@ -440,18 +496,18 @@ def grey_image(bgr) -> np.ndarray:
 
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                     trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                    weld: str = "host", normals: bool = False, **sweep_kwargs) -> RecordingAudit:
+                    weld: str = "host", normals: bool = False, components=None, **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
     frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
-    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…`` and ``normals=…`` the mesh, as they do
-    through ``mesh_from_recording``."""
-    _weld_mode(weld)
+    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…`` and ``components=…`` the
+    mesh, as they do through ``mesh_from_recording``."""
+    _weld_mode(weld, components)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals)
+        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components)
         z_near, z_far = audit_range(maps, tr)
         h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)

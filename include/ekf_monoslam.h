@@ -1099,6 +1099,52 @@ int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned int* faces, unsigned char*
                  unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri);
 int ekf_mesh_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- the connected components of the welded mesh and its pruned copy ----------------------------------
+ * The weld still holds floating fragments: what the speckle filter (§23) leaves where maps disagree, where cnt falls below
+ * min_count round a voxel, or where noise makes an isolated sign change.  These additions find the connected components of
+ * the last ekf_mesh_weld on the device and make a pruned copy of it beside it.  The contract, restated by
+ * tests/component_oracle.py:
+ *  - two vertices are linked iff some triangle of `faces` has both; a component is a connected component of the links.
+ *    Linking is by index, not by coordinate: two vertices with different keys but equal coordinates (u exactly 0) are
+ *    distinct.  Every welded vertex lies in at least one triangle;
+ *  - label[v] is the least vertex index of v's component, size[v] the number of triangles of that component, n_comp the
+ *    number of distinct labels: functions of `faces` alone, whatever the order in which the device's atomics arrive;
+ *  - a component is kept iff size >= min_triangles and, with `largest`, it is the component of greatest size, the least
+ *    label among equals.  The pruned mesh is the weld without the vertices and triangles of the other components, order
+ *    preserved: xyz, key, grey, bgr and normal are the kept rows bit for bit (normal iff the weld had normals), faces the
+ *    kept triangles in the soup's order, re-indexed by the rank of each vertex among the kept ones.  So min_triangles = 1,
+ *    largest = 0 is the identity, keys stay ascending, pruning is idempotent, and a min_triangles above every size gives
+ *    the empty mesh.
+ * Opt-in: nothing above calls them, and no result, launch, profile count or prototype above changes; ekf_abi_version()
+ * stays 6 (additions only).  ekf_mesh_get, ekf_fusion_get_mesh and ekf_colour_get_mesh stay valid: the weld is only read.
+ * All take an ekf_fusion handle and work on its last weld: EKF_ERR_STATE before a weld or after the volume changed since
+ * (integrate, reset, set_volume); a new weld invalidates the labels and the pruned mesh.  No kernel is launched for a weld
+ * without triangles.  The first call allocates 16 bytes a vertex and 4 bytes a triangle of scratch (grow-only) and the pruned
+ * mesh its own buffers; a failed allocation is EKF_ERR_DEVICE and leaves the weld as it was.
+ *  - ekf_components_find: k_comp_init, k_comp_union, k_comp_count, k_comp_flags (for the sizes) and one 4-byte read-back;
+ *    reports n_comp.  EKF_ERR_ARG: a NULL n_comp;
+ *  - ekf_components_get: label and size of the first min(n_vert, max_vert) vertices of the weld; either may be NULL.
+ *    EKF_ERR_STATE also where neither ekf_components_find nor ekf_components_prune has run since the last weld;
+ *  - ekf_components_prune: the components first (k_comp_init, k_comp_union, k_comp_count) unless the handle holds them for this
+ *    weld; then k_comp_largest (only with `largest`), k_comp_flags, k_tsdf_scan three times (kept vertices, kept triangles,
+ *    kept components), one read-back of the three totals, k_comp_vertices and k_comp_faces (neither for an empty result);
+ *    reports the pruned mesh's vertices and triangles and the number of components kept.  EKF_ERR_ARG before the device is
+ *    touched: min_triangles == 0, largest not 0 or 1, a NULL count;
+ *  - ekf_components_get_pruned: ekf_mesh_get's rules on the pruned mesh: the first min(n_vert, max_vert) vertices and
+ *    min(n_tri, max_tri) triangles, every pointer may be NULL; EKF_ERR_ARG: bgr on a plain volume, or normal after a weld
+ *    without normals; EKF_ERR_STATE also where no ekf_components_prune has run since the last weld;
+ *  - ekf_components_get_profile: HIP-event milliseconds and launch counts of 8 kinds since the last
+ *    ekf_fusion_profile: k_comp_init ([0]), k_comp_union ([1]), k_comp_count ([2]), k_comp_largest ([3]), k_comp_flags
+ *    ([4]), the prune's k_tsdf_scan ([5]), k_comp_vertices ([6]), k_comp_faces ([7]).  The other profile getters gain
+ *    nothing. */
+int ekf_components_find(ekf_fusion* h, unsigned long long* n_comp);
+int ekf_components_get(ekf_fusion* h, unsigned int* label, unsigned int* size, unsigned long long max_vert);
+int ekf_components_prune(ekf_fusion* h, unsigned int min_triangles, int largest, unsigned long long* n_vert,
+                   unsigned long long* n_tri, unsigned long long* n_kept);
+int ekf_components_get_pruned(ekf_fusion* h, double* xyz, unsigned int* faces, unsigned char* grey, unsigned char* bgr,
+                        float* normal, unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri);
+int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -634,7 +634,8 @@ class DenseStereoHip {
 // on the device, extract() = marching tetrahedra into a triangle soup in a fixed order.  raycast() / raycastView() mirror
 // ekf_raycast_* (section 17): the volume seen from a pose as a depth, a normal and a grey image.  Values are plain arrays.
 // A colour volume (the constructor's `colour`, section 18, ekf_colour_*) also fills the `colour` arrays: B, G, R.
-// weld() / mesh() mirror ekf_mesh_* (section 24): the indexed mesh welded on the device, with vertex normals on request.
+// weld() / mesh() mirror ekf_mesh_* (section 24): the indexed mesh welded on the device, with vertex normals on request;
+// components() / prune() / pruned() its connected components and the weld without the small ones (section 25).
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -653,6 +654,11 @@ class TsdfVolumeHip {
     std::vector<unsigned long long> key;       // 1 per vertex, ascending
     size_t vertices() const { return key.size(); }
     size_t triangles() const { return faces.size() / 3; }
+  };
+  struct Components {                          // of the last weld(): section 25
+    std::vector<unsigned int> label;           // 1 per vertex: the least vertex index of its component
+    std::vector<unsigned int> size;            // 1 per vertex: the triangles of its component
+    unsigned long long count = 0;              // the number of components
   };
   struct Volume {
     std::vector<float> sum;
@@ -737,6 +743,41 @@ class TsdfVolumeHip {
   }
   // HIP-event milliseconds and launch counts of k_mesh_cells, k_mesh_edges, the weld's k_tsdf_scan, k_mesh_vertices, k_mesh_faces
   void getMeshProfile(double kernel_ms[5], long long launches[5]) { check(ekf_mesh_get_profile(f_, kernel_ms, launches)); }
+  // The connected components of the last weld() (section 25), found on the device: two vertices are linked iff a triangle has
+  // both, by index.  label: the least vertex index of a vertex's component; size: the triangles of that component.
+  Components components() {
+    Components c;
+    check(ekf_components_find(f_, &c.count));
+    c.label.resize((size_t)weld_vertices_);
+    c.size.resize((size_t)weld_vertices_);
+    check(ekf_components_get(f_, c.label.data(), c.size.data(), weld_vertices_));
+    return c;
+  }
+  // The last weld() without the components of fewer than min_triangles triangles and, with `largest`, without all but the one
+  // of greatest size (the least label among equals); order kept, rows bit for bit, faces re-indexed.  prune(1) is the identity;
+  // the weld stays as it was.  kept (optional): the number of components kept.
+  IndexedMesh prune(unsigned int min_triangles = 1, bool largest = false, unsigned long long* kept = nullptr) {
+    unsigned long long nk = 0;
+    check(ekf_components_prune(f_, min_triangles, largest ? 1 : 0, &pruned_vertices_, &pruned_triangles_, &nk));
+    if (kept) *kept = nk;
+    return pruned();
+  }
+  // the arrays of the last prune() again
+  IndexedMesh pruned() {
+    IndexedMesh m;
+    const size_t nv = (size_t)pruned_vertices_, nt = (size_t)pruned_triangles_;
+    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
+    if (colour_) m.colour.resize(nv * 3);
+    if (weld_normals_) m.normal.resize(nv * 3);
+    check(ekf_components_get_pruned(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
+                              weld_normals_ ? m.normal.data() : nullptr, m.key.data(), pruned_vertices_, pruned_triangles_));
+    return m;
+  }
+  // HIP-event milliseconds and launch counts of k_comp_init, k_comp_union, k_comp_count, k_comp_largest, k_comp_flags, the
+  // prune's k_tsdf_scan, k_comp_vertices, k_comp_faces
+  void getComponentProfile(double kernel_ms[8], long long launches[8]) {
+    check(ekf_components_get_profile(f_, kernel_ms, launches));
+  }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
@@ -775,6 +816,7 @@ class TsdfVolumeHip {
   size_t n_;
   bool colour_;
   unsigned long long weld_vertices_ = 0, weld_triangles_ = 0;
+  unsigned long long pruned_vertices_ = 0, pruned_triangles_ = 0;
   bool weld_normals_ = false;
   ekf_fusion* f_ = nullptr;
 };
