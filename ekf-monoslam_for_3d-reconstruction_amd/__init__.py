@@ -18,3 +18,4 @@ from .fusion import Mesh, TsdfVolume, mesh_from_recording, read_mesh_ply, weld, 
 from .fusion import Render, audit_recording, shade  # noqa: F401
 from .fusion import IndexedMesh  # noqa: F401
 from .fusion import MeshComponents  # noqa: F401
+from .fusion import MeshAdjacency  # noqa: F401

@@ -241,6 +241,11 @@ _PROTOS = {
     "ekf_components_prune": (C.c_int, [_P, C.c_uint, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "ekf_components_get_pruned": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
     "ekf_components_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_smooth_run": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_ulonglong),
+                                 C.POINTER(C.c_ulonglong)]),
+    "ekf_smooth_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
+    "ekf_smooth_get_adjacency": (C.c_int, [_P, _P, _P, _P, C.c_ulonglong]),
+    "ekf_smooth_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

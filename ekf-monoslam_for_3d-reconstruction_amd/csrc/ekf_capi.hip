@@ -38,6 +38,7 @@
 #include "ekf_raycast.hpp"
 #include "ekf_mesh.hpp"
 #include "ekf_mesh_components.hpp"
+#include "ekf_mesh_smooth.hpp"
 
 namespace ekf {
 
@@ -5867,6 +5868,7 @@ struct ekf_fusion {
   ekf::TsdfRaycast rc;                // the last render of the volume (ekf_raycast_*)
   ekf::TsdfMesh mesh;                 // the last weld of the volume's mesh (ekf_mesh_*)
   ekf::TsdfComponents comp;           // that weld's components and its pruned copy
+  ekf::TsdfSmooth smooth;             // the smoothed copy of either of them
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6137,6 +6139,7 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   h->impl->timer.enable(enable != 0);   // the four kinds of the fusion, the two of the ray caster and the three of colour
   h->mesh.timer.enable(enable != 0);    // the five of the weld
   h->comp.timer.enable(enable != 0);    // the eight of the components
+  h->smooth.timer.enable(enable != 0);  // the seven of the smoothing
   return EKF_OK;
 }
 
@@ -6399,6 +6402,111 @@ int ekf_components_get_pruned(ekf_fusion* h, double* xyz, unsigned* faces, unsig
 int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->comp.timer.read(kernel_ms, launches, 0, ekf::kCompKinds);
+  return EKF_OK;
+}
+
+// ---- Taubin smoothing of the welded or the pruned mesh -----------------------------------------------------
+// The mesh a smoothing call is about, if the handle holds it: EKF_OK, or EKF_ERR_STATE with the message set.
+static int smooth_source(ekf_fusion* h, const char* who, int source, ekf::SmoothSource* s) {
+  auto* f = h->impl;
+  if (!h->mesh.current(*f)) {
+    f->err = std::string(who) + ": no ekf_mesh_weld since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  if (source == 1 && !h->comp.have_pruned(h->mesh)) {
+    f->err = std::string(who) + ": source 1 needs an ekf_components_prune since the last ekf_mesh_weld";
+    return EKF_ERR_STATE;
+  }
+  *s = ekf::SmoothSource::of(source, h->mesh, h->comp);
+  return EKF_OK;
+}
+
+// The mesh the last run smoothed, if it is still the handle's: the run's source says which.
+static int smooth_result(ekf_fusion* h, const char* who, ekf::SmoothSource* s) {
+  auto* f = h->impl;
+  const ekf::TsdfSmooth& m = h->smooth;
+  const bool held = m.res_valid && h->mesh.current(*f) && (m.res.source == 0 || h->comp.have_pruned(h->mesh));
+  if (held) *s = ekf::SmoothSource::of(m.res.source, h->mesh, h->comp);
+  if (!held || !m.have_result(*s)) {
+    f->err = std::string(who) + ": no ekf_smooth_run on the current mesh";
+    return EKF_ERR_STATE;
+  }
+  return EKF_OK;
+}
+
+int ekf_smooth_run(ekf_fusion* h, int source, int iterations, double lambda, double mu, int pin_boundary, int normals,
+                   unsigned long long* n_vert, unsigned long long* n_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if ((source != 0 && source != 1) || iterations < 1 || iterations > ekf::kSmoothMaxIterations || !std::isfinite(lambda) ||
+      !(lambda > 0.0) || lambda > 1.0 || !std::isfinite(mu) || mu < -1.0 || mu > 0.0 || (pin_boundary != 0 && pin_boundary != 1) ||
+      (normals != 0 && normals != 1) || !n_vert || !n_tri) {
+    f->err = "ekf_smooth_run: source 0 or 1, iterations 1..1024, 0 < lambda <= 1, -1 <= mu <= 0, pin_boundary and normals 0 or 1, "
+             "n_vert and n_tri not NULL";
+    return EKF_ERR_ARG;
+  }
+  ekf::SmoothSource s;
+  const int rc = smooth_source(h, "ekf_smooth_run", source, &s);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->smooth.run(s, iterations, lambda, mu, pin_boundary != 0, normals != 0));
+  *n_vert = s.n_vert;
+  *n_tri = s.n_tri;
+  return EKF_OK;
+}
+
+int ekf_smooth_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                   unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfSmooth& m = h->smooth;
+  if (bgr && !f->colour) {
+    f->err = "ekf_smooth_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_ARG;
+  }
+  ekf::SmoothSource s;
+  const int rc = smooth_result(h, "ekf_smooth_get", &s);
+  if (rc != EKF_OK) return rc;
+  if (normal && !m.has_normals) {
+    f->err = "ekf_smooth_get: normal must be NULL after an ekf_smooth_run without normals";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(s.n_vert, max_vert), nc = (size_t)std::min(s.n_tri, max_tri) * 3;
+  const bool weld = s.source == 0;                         // faces, key, grey and bgr are the source's own buffers
+  HIPCHK(hipSetDevice(f->device));
+  if (nv > 0) {
+    if (xyz) HIPCHK(hipMemcpy(xyz, m.pos[m.last], nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (grey) HIPCHK(hipMemcpy(grey, weld ? h->mesh.grey : h->comp.grey, nv, hipMemcpyDeviceToHost));
+    if (bgr) HIPCHK(hipMemcpy(bgr, weld ? h->mesh.bgr : h->comp.bgr, nv * 3, hipMemcpyDeviceToHost));
+    if (normal) HIPCHK(hipMemcpy(normal, m.normal, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (key) HIPCHK(hipMemcpy(key, weld ? h->mesh.key : h->comp.key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  }
+  if (nc > 0 && faces) HIPCHK(hipMemcpy(faces, s.faces, nc * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned* inc, unsigned* deg, unsigned char* boundary, unsigned long long max_vert) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  ekf::SmoothSource s;
+  const int rc = smooth_result(h, "ekf_smooth_get_adjacency", &s);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(s.n_vert, max_vert);
+  HIPCHK(hipSetDevice(f->device));
+  if (nv > 0) {
+    if (inc) HIPCHK(hipMemcpy(inc, h->smooth.inc, nv * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (deg) HIPCHK(hipMemcpy(deg, h->smooth.deg, nv * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (boundary) HIPCHK(hipMemcpy(boundary, h->smooth.boundary, nv, hipMemcpyDeviceToHost));
+  }
+  return EKF_OK;
+}
+
+int ekf_smooth_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->smooth.timer.read(kernel_ms, launches, 0, ekf::kSmoothKinds);
   return EKF_OK;
 }
 

@@ -292,6 +292,7 @@ struct TsdfComponents {
   unsigned long long n_comp = 0;                               // of the components
   unsigned long long n_vert = 0, n_tri = 0, n_kept = 0;        // of the pruned mesh
   unsigned long long comp_serial = 0, prune_serial = 0;
+  unsigned long long prunes = 0;                               // counts the prunes: what ekf_mesh_smooth.hpp derives from one names it
   bool comp_valid = false, prune_valid = false, has_normals = false;
   KernelTimer<kCompKinds> timer;
 
@@ -357,6 +358,7 @@ struct TsdfComponents {
     hipError_t e;
     if (!have_components(m) && (e = components(m, colour, false)) != hipSuccess) return e;
     prune_valid = false;
+    ++prunes;
     unsigned long long totals[3] = {0, 0, 0};
     if (m.n_tri > 0) {
       const unsigned vblk = blocks(m.n_vert), tblk = blocks(m.n_tri);

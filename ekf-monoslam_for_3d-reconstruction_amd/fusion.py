@@ -6,7 +6,8 @@ pose as a depth, a normal and a grey image; ``shade`` turns one into a picture a
 reconstruction of a recording with its own key frames.  ``TsdfVolume(..., colour=True)`` is a colour volume (§18): meshes,
 renders and audits then carry B, G, R beside the grey.  ``TsdfVolume.weld`` mirrors ``ekf_mesh_*`` (§24): the same indexed mesh
 welded on the device, with per-vertex normals on request; ``TsdfVolume.components`` and ``.prune`` find its connected
-components there and drop the small ones (§25).
+components there and drop the small ones (§25); ``TsdfVolume.smooth`` smooths either mesh there with Taubin's scheme and gives
+it normals from its own triangles (§26).
 """
 from __future__ import annotations
 
@@ -26,6 +27,8 @@ COLOUR_KERNELS = ("k_tsdf_integrate_colour", "k_tsdf_colour_vertices", "k_tsdf_r
 MESH_KERNELS = ("k_mesh_cells", "k_mesh_edges", "k_tsdf_scan", "k_mesh_vertices", "k_mesh_faces")
 COMPONENT_KERNELS = ("k_comp_init", "k_comp_union", "k_comp_count", "k_comp_largest", "k_comp_flags", "k_tsdf_scan", "k_comp_vertices",
                      "k_comp_faces")
+SMOOTH_KERNELS = ("k_smooth_count", "k_smooth_offsets", "k_tsdf_scan", "k_smooth_fill", "k_smooth_lists", "k_smooth_step",
+                  "k_smooth_normals")
 
 
 @dataclass
@@ -56,6 +59,14 @@ class MeshComponents:
     label: np.ndarray              # (m,) uint32: the least vertex index of the vertex's component
     size: np.ndarray               # (m,) uint32: the number of triangles of that component
     count: int                     # the number of components
+
+
+@dataclass
+class MeshAdjacency:
+    """The adjacency of the mesh the last ``TsdfVolume.smooth`` ran on: a function of its faces alone."""
+    inc: np.ndarray                # (m,) uint32: the number of triangles that contain the vertex
+    deg: np.ndarray                # (m,) uint32: the number of distinct vertices that share a triangle with it
+    boundary: np.ndarray           # (m,) uint8: 1 iff it has an edge that lies in exactly one triangle
 
 
 @dataclass
@@ -120,6 +131,7 @@ class TsdfVolume(capi.Handle):
         self.shape = (nz, ny, nx)
         self._weld_counts = (0, 0, False)       # vertices, triangles and normals of the last weld
         self.pruned_components = 0              # the number of components the last prune kept
+        self._smooth_vertices = 0               # the vertices of the last smooth
 
     def integrate(self, dense_stereo, slot: int, filtered: bool = True):
         """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""
@@ -233,6 +245,42 @@ class TsdfVolume(capi.Handle):
         ms, cnt = np.zeros(8, np.float64), np.zeros(8, np.int64)
         self._check(self._lib.ekf_components_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(COMPONENT_KERNELS)}
+
+    def smooth(self, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, pin_boundary: bool = False,
+               normals: bool = False, source: str = "weld") -> IndexedMesh:
+        """The last ``weld`` (``source="weld"``) or the last ``prune`` (``"pruned"``) smoothed on the device with Taubin's scheme
+        (DESIGN.md §26): ``iterations`` times a step towards the mean of a vertex's neighbours with factor ``lam`` and then,
+        unless ``mu`` is 0, one with ``mu`` (Taubin wants ``mu < -lam``, which does not shrink; ``mu=0`` is plain Laplacian
+        smoothing).  ``pin_boundary`` keeps the bits of the vertices on an open edge.  ``normals``: unit vertex normals from
+        the smoothed triangles, weighted by area; without it the result has none (the weld's describe another surface).
+        Faces, grey, colour and key are the source's; the source itself stays as it was.  The adjacency is built by the first
+        run on a mesh (13 bytes a vertex and 36 bytes a triangle of scratch) and kept for the next."""
+        if source not in ("weld", "pruned"):
+            raise ValueError('source is "weld" or "pruned"')
+        nv, nt = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self._lib.ekf_smooth_run(self._h, 1 if source == "pruned" else 0, int(iterations), float(lam), float(mu),
+                                             1 if pin_boundary else 0, 1 if normals else 0, C.byref(nv), C.byref(nt)))
+        nv, nt = int(nv.value), int(nt.value)
+        self._smooth_vertices = nv
+        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
+                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
+                        np.zeros(nv, np.uint64))
+        self._check(self._lib.ekf_smooth_get(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour), _ptr(m.normals),
+                                             _ptr(m.key), nv, nt))
+        return m
+
+    def adjacency(self) -> MeshAdjacency:
+        """The adjacency of the mesh the last ``smooth`` ran on."""
+        nv = self._smooth_vertices
+        out = MeshAdjacency(np.zeros(nv, np.uint32), np.zeros(nv, np.uint32), np.zeros(nv, np.uint8))
+        self._check(self._lib.ekf_smooth_get_adjacency(self._h, _ptr(out.inc), _ptr(out.deg), _ptr(out.boundary), nv))
+        return out
+
+    def get_smooth_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the seven kinds of launch of ``smooth`` since the last ``profile()``."""
+        ms, cnt = np.zeros(7, np.float64), np.zeros(7, np.int64)
+        self._check(self._lib.ekf_smooth_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(SMOOTH_KERNELS)}
 
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
@@ -398,7 +446,8 @@ def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
 
 def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                         trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                        weld: str = "host", normals: bool = False, components=None, **sweep_kwargs) -> RecordingMesh:
+                        weld: str = "host", normals: bool = False, components=None, smooth=None,
+                        **sweep_kwargs) -> RecordingMesh:
     """``dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)``, then every filtered map with its key
     frame's image into one volume (``auto_grid`` where voxel / bounds / trunc are None), extract, weld.  ``trunc`` is the
     truncation distance of the volume; the sweep's cost truncation, also called ``trunc`` there, is ``sweep_trunc`` here.
@@ -412,13 +461,16 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     the device (§24): the same arrays without the soup's way over the host; ``normals=True`` does so too and fills
     ``RecordingMesh.normals``.  ``components=n`` drops the connected components of the mesh of fewer than ``n`` triangles and
     ``components="largest"`` keeps the largest one alone (§25); either welds on the device, and ``None`` makes today's
-    launches."""
+    launches.  ``smooth=n`` then smooths the mesh (the pruned one, if ``components`` is given) with ``n`` rounds of
+    ``TsdfVolume.smooth`` at its defaults, and ``smooth=dict(...)`` with those keyword arguments (§26); it welds on the device
+    too, with ``normals=True`` the normals are the smoothed mesh's own, and ``None`` makes today's launches."""
     _weld_mode(weld, components)
+    smooth = _smooth_kwargs(smooth)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        welded = _welded(vol, min_count, weld, normals, components)
+        welded = _welded(vol, min_count, weld, normals, components, smooth)
     finally:
         vol.close()
     out = RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
@@ -434,12 +486,27 @@ def _weld_mode(mode, components=None):
         raise ValueError('components is None, an int >= 1 or "largest"')
 
 
-def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False, components=None):
-    """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh."""
-    if mode == "device" or normals or components is not None:
-        m = vol.weld(min_count, normals)
+def _smooth_kwargs(smooth):
+    """The keyword arguments of ``TsdfVolume.smooth`` that ``smooth=`` of ``mesh_from_recording`` stands for, or None."""
+    if smooth is None:
+        return None
+    if isinstance(smooth, dict):
+        if not set(smooth) <= {"iterations", "lam", "mu", "pin_boundary"}:
+            raise ValueError("smooth takes iterations, lam, mu and pin_boundary")
+        return dict(smooth)
+    if isinstance(smooth, (int, np.integer)) and not isinstance(smooth, bool) and smooth >= 1:
+        return dict(iterations=int(smooth))
+    raise ValueError("smooth is None, an int >= 1 or a dict of keyword arguments of TsdfVolume.smooth")
+
+
+def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False, components=None, smooth=None):
+    """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh.  ``smooth``: what ``_smooth_kwargs`` gave."""
+    if mode == "device" or normals or components is not None or smooth is not None:
+        m = vol.weld(min_count, normals and smooth is None)
         if components is not None:
             m = vol.prune(largest=True) if components == "largest" else vol.prune(int(components))
+        if smooth is not None:
+            m = vol.smooth(normals=normals, source="weld" if components is None else "pruned", **smooth)
         return m.vertices, m.faces.astype(np.int64), m.grey, m.colour, m.normals
     mesh = vol.extract(min_count)
     return (weld(mesh, True) if vol.colour else weld(mesh) + (None,)) + (None,)
@@ -496,18 +563,20 @@ def grey_image(bgr) -> np.ndarray:
 
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                     trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                    weld: str = "host", normals: bool = False, components=None, **sweep_kwargs) -> RecordingAudit:
+                    weld: str = "host", normals: bool = False, components=None, smooth=None,
+                    **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
     frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
-    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…`` and ``components=…`` the
-    mesh, as they do through ``mesh_from_recording``."""
+    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…``, ``components=…`` and ``smooth=…``
+    the mesh, as they do through ``mesh_from_recording``."""
     _weld_mode(weld, components)
+    smooth = _smooth_kwargs(smooth)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components)
+        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components, smooth)
         z_near, z_far = audit_range(maps, tr)
         h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)

@@ -1145,6 +1145,55 @@ int ekf_components_get_pruned(ekf_fusion* h, double* xyz, unsigned int* faces, u
                         float* normal, unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri);
 int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- Taubin smoothing of the welded or the pruned mesh, and normals from its own triangles -------------
+ * The weld is the raw marching-tetrahedra surface: the noise of the mean field and the lattice's staircase stand in its
+ * vertices.  These additions smooth the last ekf_mesh_weld (source 0) or the last ekf_components_prune (source 1) on the
+ * device with Taubin's lambda | mu scheme, which does not shrink the surface as plain Laplacian smoothing does, and give the
+ * result normals from its own triangles (the weld's normals are gradients of the unsmoothed field and are not copied).
+ * The contract, restated by tests/smooth_oracle.py, on a mesh (X, F) whose triangles have three distinct indices:
+ *  - the adjacency is a function of F alone.  T(v): the ascending list of the triangles that contain v, inc(v) = |T(v)|;
+ *    N(v): the ascending list of the distinct w != v that share a triangle with v, deg(v) = |N(v)|; m(v, w): the number of
+ *    triangles that hold both; boundary(v) = 1 iff some w has m(v, w) = 1.  Every vertex lies in a triangle, so deg >= 2;
+ *  - one step with factor f, every operation rounded once: s = X[w0][c], then s = s + X[wi][c] in the order of N(v);
+ *    mean = s / (double) deg(v); X'[v][c] = X[v][c] + f * (mean - X[v][c]).  With pin_boundary, a vertex with
+ *    boundary(v) = 1 keeps its bits;
+ *  - a run is `iterations` times a step with lambda and then, unless mu == 0, a step with mu.  Taubin's scheme wants
+ *    mu < -lambda (0.5 and -0.53 are common); mu == 0 launches single steps: plain Laplacian smoothing;
+ *  - faces, key, grey and bgr of the result are the source's rows bit for bit;
+ *  - normals, on request, from the final positions: the cross products (B - A) x (C - A) of the triangles of T(v) in
+ *    ascending order, summed from left to right from the first one's, len = sqrt((a0 a0 + a1 a1) + a2 a2), each a_c / len
+ *    rounded once to float, 0 0 0 where len is 0 or not finite: ekf_mesh_weld's normalisation and orientation (towards
+ *    free space), weighted by area.
+ * The sums are fp64 over lists the device gathers with integer atomics; every list is put in ascending order before it is
+ * read, so the order of arrival costs no bit.
+ * Opt-in: nothing above calls them, and no result, launch, profile count or prototype above changes; ekf_abi_version()
+ * stays 6 (additions only).  The weld and the pruned mesh are only read and stay valid.  EKF_ERR_STATE before a weld, after
+ * the volume changed since (integrate, reset, set_volume), and for source 1 without an ekf_components_prune since the last
+ * weld; a new weld invalidates the adjacency and the result, a new prune those made from the pruned mesh.  No kernel is
+ * launched for a mesh without triangles.  The adjacency (13 bytes a vertex, 36 bytes a triangle, grow-only) is kept for
+ * the source mesh: a second run on the same mesh rebuilds nothing.  A failed allocation is EKF_ERR_DEVICE and leaves the
+ * source as it was.
+ *  - ekf_smooth_run: the adjacency unless the handle holds it for this mesh (k_smooth_count, k_smooth_offsets, k_tsdf_scan,
+ *    k_smooth_fill, k_smooth_lists), then k_smooth_step `iterations` times, or twice that with mu != 0, with nothing between
+ *    them, then k_smooth_normals with `normals`; reports the vertices and triangles of the result (the source's).
+ *    EKF_ERR_ARG before the device is touched: source not 0 or 1, iterations outside 1..1024, lambda not finite or outside
+ *    (0, 1], mu not finite or outside [-1, 0], pin_boundary or normals not 0 or 1, a NULL count;
+ *  - ekf_smooth_get: ekf_mesh_get's rules on the result: the first min(n_vert, max_vert) vertices and min(n_tri, max_tri)
+ *    triangles, every pointer may be NULL; EKF_ERR_ARG: bgr on a plain volume, or normal after a run without normals;
+ *    EKF_ERR_STATE also without an ekf_smooth_run on the current mesh;
+ *  - ekf_smooth_get_adjacency: inc, deg (uint32) and boundary (uint8) of the first min(n_vert, max_vert) vertices of the
+ *    last run's mesh; any may be NULL.  EKF_ERR_STATE as ekf_smooth_get;
+ *  - ekf_smooth_get_profile: HIP-event milliseconds and launch counts of 7 kinds since the last ekf_fusion_profile:
+ *    k_smooth_count ([0]), k_smooth_offsets ([1]), k_tsdf_scan ([2]), k_smooth_fill ([3]), k_smooth_lists ([4]),
+ *    k_smooth_step ([5]), k_smooth_normals ([6]).  The other profile getters gain nothing. */
+int ekf_smooth_run(ekf_fusion* h, int source, int iterations, double lambda, double mu, int pin_boundary, int normals,
+                   unsigned long long* n_vert, unsigned long long* n_tri);
+int ekf_smooth_get(ekf_fusion* h, double* xyz, unsigned int* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                   unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri);
+int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned int* inc, unsigned int* deg, unsigned char* boundary,
+                             unsigned long long max_vert);
+int ekf_smooth_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -635,7 +635,8 @@ class DenseStereoHip {
 // ekf_raycast_* (section 17): the volume seen from a pose as a depth, a normal and a grey image.  Values are plain arrays.
 // A colour volume (the constructor's `colour`, section 18, ekf_colour_*) also fills the `colour` arrays: B, G, R.
 // weld() / mesh() mirror ekf_mesh_* (section 24): the indexed mesh welded on the device, with vertex normals on request;
-// components() / prune() / pruned() its connected components and the weld without the small ones (section 25).
+// components() / prune() / pruned() its connected components and the weld without the small ones (section 25);
+// smooth() / smoothed() / adjacency() either of them smoothed with Taubin's scheme, with normals of its own (section 26).
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -659,6 +660,11 @@ class TsdfVolumeHip {
     std::vector<unsigned int> label;           // 1 per vertex: the least vertex index of its component
     std::vector<unsigned int> size;            // 1 per vertex: the triangles of its component
     unsigned long long count = 0;              // the number of components
+  };
+  struct Adjacency {                           // of the mesh the last smooth() ran on: section 26
+    std::vector<unsigned int> inc;             // 1 per vertex: the triangles that contain it
+    std::vector<unsigned int> deg;             // 1 per vertex: the distinct vertices that share a triangle with it
+    std::vector<unsigned char> boundary;       // 1 per vertex: 1 iff it has an edge that lies in exactly one triangle
   };
   struct Volume {
     std::vector<float> sum;
@@ -778,6 +784,40 @@ class TsdfVolumeHip {
   void getComponentProfile(double kernel_ms[8], long long launches[8]) {
     check(ekf_components_get_profile(f_, kernel_ms, launches));
   }
+  // The last weld() (pruned = false) or the last prune() smoothed on the device with Taubin's scheme (section 26): `iterations`
+  // times a step towards the mean of a vertex's neighbours with factor lambda and then, unless mu is 0, one with mu (Taubin
+  // wants mu < -lambda; mu = 0 is plain Laplacian smoothing).  pin_boundary keeps the bits of the vertices on an open edge.
+  // normals: unit vertex normals from the smoothed triangles, weighted by area; without it the result has none.  faces, grey,
+  // colour and key are the source's; the source stays as it was.
+  IndexedMesh smooth(int iterations = 10, double lambda = 0.5, double mu = -0.53, bool pin_boundary = false, bool normals = false,
+                     bool pruned = false) {
+    check(ekf_smooth_run(f_, pruned ? 1 : 0, iterations, lambda, mu, pin_boundary ? 1 : 0, normals ? 1 : 0, &smooth_vertices_,
+                         &smooth_triangles_));
+    smooth_normals_ = normals;
+    return smoothed();
+  }
+  // the arrays of the last smooth() again
+  IndexedMesh smoothed() {
+    IndexedMesh m;
+    const size_t nv = (size_t)smooth_vertices_, nt = (size_t)smooth_triangles_;
+    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
+    if (colour_) m.colour.resize(nv * 3);
+    if (smooth_normals_) m.normal.resize(nv * 3);
+    check(ekf_smooth_get(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
+                         smooth_normals_ ? m.normal.data() : nullptr, m.key.data(), smooth_vertices_, smooth_triangles_));
+    return m;
+  }
+  // the adjacency of the mesh the last smooth() ran on
+  Adjacency adjacency() {
+    Adjacency a;
+    const size_t nv = (size_t)smooth_vertices_;
+    a.inc.resize(nv); a.deg.resize(nv); a.boundary.resize(nv);
+    check(ekf_smooth_get_adjacency(f_, a.inc.data(), a.deg.data(), a.boundary.data(), smooth_vertices_));
+    return a;
+  }
+  // HIP-event milliseconds and launch counts of k_smooth_count, k_smooth_offsets, the adjacency's k_tsdf_scan, k_smooth_fill,
+  // k_smooth_lists, k_smooth_step, k_smooth_normals
+  void getSmoothProfile(double kernel_ms[7], long long launches[7]) { check(ekf_smooth_get_profile(f_, kernel_ms, launches)); }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
@@ -817,6 +857,7 @@ class TsdfVolumeHip {
   bool colour_;
   unsigned long long weld_vertices_ = 0, weld_triangles_ = 0;
   unsigned long long pruned_vertices_ = 0, pruned_triangles_ = 0;
-  bool weld_normals_ = false;
+  unsigned long long smooth_vertices_ = 0, smooth_triangles_ = 0;
+  bool weld_normals_ = false, smooth_normals_ = false;
   ekf_fusion* f_ = nullptr;
 };
