@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 namespace ekf {
@@ -70,6 +71,42 @@ class Buf {
 
 template <typename T> using DevBuf = Buf<T, DeviceAlloc>;
 template <typename T> using PinnedBuf = Buf<T, PinnedAlloc>;
+
+// Move-only owner of the six arrays of an indexed mesh and of its counts: the weld of ekf_mesh.hpp, its pruned copy and
+// whatever is derived from them next.  The holder sets the counts once its kernels have filled the arrays.
+template <typename Alloc>
+struct IndexedMeshBufs {
+  Buf<double, Alloc> xyz;                        // three a vertex, by ascending key
+  Buf<unsigned long long, Alloc> key;
+  Buf<unsigned char, Alloc> grey, bgr;           // bgr: three a vertex, colour volumes only
+  Buf<float, Alloc> normal;                      // three a vertex, meshes with normals only
+  Buf<unsigned, Alloc> faces;                    // three a triangle
+  unsigned long long n_vert = 0, n_tri = 0;
+  bool has_normals = false;
+
+  // Room for nv vertices and ncorner face indices, bgr only with `colour`, normal only with `normals`.  Buffers that have it
+  // are left alone.  Otherwise all six are replaced together, by new ones made beside them: a failed allocation returns its
+  // error and leaves every buffer, and so the previous mesh, as it was.
+  hipError_t grow(size_t nv, size_t ncorner, bool colour, bool normals) {
+    if (nv * 3 <= xyz.capacity() && nv <= key.capacity() && nv <= grey.capacity() && (!colour || nv * 3 <= bgr.capacity()) &&
+        (!normals || nv * 3 <= normal.capacity()) && ncorner <= faces.capacity())
+      return hipSuccess;
+    IndexedMeshBufs t;
+    hipError_t e;
+    if ((e = t.xyz.reserve(nv * 3)) != hipSuccess || (e = t.key.reserve(nv)) != hipSuccess || (e = t.grey.reserve(nv)) != hipSuccess ||
+        (colour && (e = t.bgr.reserve(nv * 3)) != hipSuccess) || (normals && (e = t.normal.reserve(nv * 3)) != hipSuccess) ||
+        (e = t.faces.reserve(ncorner)) != hipSuccess)
+      return e;
+    xyz = std::move(t.xyz);
+    key = std::move(t.key);
+    grey = std::move(t.grey);
+    bgr = std::move(t.bgr);
+    normal = std::move(t.normal);
+    faces = std::move(t.faces);
+    return hipSuccess;
+  }
+};
+using DevMeshBufs = IndexedMeshBufs<DeviceAlloc>;
 
 // Per-kernel times of N kinds of launch on the null stream of the owner's device, behind a switch.  Off: run() makes no
 // event call at all.  On: it records round the launch, waits for the second event and adds the time to the kind's pair.

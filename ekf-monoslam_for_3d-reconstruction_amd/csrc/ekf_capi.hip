@@ -6269,31 +6269,18 @@ int ekf_mesh_weld(ekf_fusion* h, int min_count, int normals, unsigned long long*
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
   HIPCHK(h->mesh.weld(*f, min_count, normals != 0));
-  *n_vert = h->mesh.n_vert;
-  *n_tri = h->mesh.n_tri;
+  *n_vert = h->mesh.out.n_vert;
+  *n_tri = h->mesh.out.n_tri;
   return EKF_OK;
 }
 
-int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
-                 unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  const ekf::TsdfMesh& m = h->mesh;
-  if (bgr && !f->colour) {
-    f->err = "ekf_mesh_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
-    return EKF_ERR_ARG;
-  }
-  if (!m.current(*f)) {
-    f->err = "ekf_mesh_get: no ekf_mesh_weld since the volume last changed";
-    return EKF_ERR_STATE;
-  }
-  if (normal && !m.has_normals) {
-    f->err = "ekf_mesh_get: normal must be NULL after an ekf_mesh_weld without normals";
-    return EKF_ERR_ARG;
-  }
-  std::string& err = f->err;
+// The arrays of `m` to the caller's, for the three getters of an indexed mesh, behind their own checks: at most max_vert
+// vertices and max_tri triangles; a NULL array is skipped, and so is every array of a count of 0.
+static int mesh_copy_out(ekf_fusion* h, const ekf::MeshView& m, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr,
+                         float* normal, unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
+  std::string& err = h->impl->err;
   const size_t nv = (size_t)std::min(m.n_vert, max_vert), nc = (size_t)std::min(m.n_tri, max_tri) * 3;
-  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(hipSetDevice(h->impl->device));
   if (nv > 0) {
     if (xyz) HIPCHK(hipMemcpy(xyz, m.xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (grey) HIPCHK(hipMemcpy(grey, m.grey, nv, hipMemcpyDeviceToHost));
@@ -6303,6 +6290,25 @@ int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* gre
   }
   if (nc > 0 && faces) HIPCHK(hipMemcpy(faces, m.faces, nc * sizeof(unsigned), hipMemcpyDeviceToHost));
   return EKF_OK;
+}
+
+int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                 unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (bgr && !f->colour) {
+    f->err = "ekf_mesh_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_ARG;
+  }
+  if (!h->mesh.current(*f)) {
+    f->err = "ekf_mesh_get: no ekf_mesh_weld since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  if (normal && !h->mesh.out.has_normals) {
+    f->err = "ekf_mesh_get: normal must be NULL after an ekf_mesh_weld without normals";
+    return EKF_ERR_ARG;
+  }
+  return mesh_copy_out(h, h->mesh.view(), xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_mesh_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
@@ -6338,7 +6344,7 @@ int ekf_components_get(ekf_fusion* h, unsigned* label, unsigned* size, unsigned 
     return EKF_ERR_STATE;
   }
   std::string& err = f->err;
-  const size_t nv = (size_t)std::min(h->mesh.n_vert, max_vert);
+  const size_t nv = (size_t)std::min(h->mesh.out.n_vert, max_vert);
   HIPCHK(hipSetDevice(f->device));
   if (nv > 0) {
     if (label) HIPCHK(hipMemcpy(label, h->comp.R, nv * sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -6362,8 +6368,8 @@ int ekf_components_prune(ekf_fusion* h, unsigned min_triangles, int largest, uns
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
   HIPCHK(h->comp.prune(h->mesh, f->colour, min_triangles, largest != 0));
-  *n_vert = h->comp.n_vert;
-  *n_tri = h->comp.n_tri;
+  *n_vert = h->comp.out.n_vert;
+  *n_tri = h->comp.out.n_tri;
   *n_kept = h->comp.n_kept;
   return EKF_OK;
 }
@@ -6372,31 +6378,19 @@ int ekf_components_get_pruned(ekf_fusion* h, double* xyz, unsigned* faces, unsig
                         unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
-  const ekf::TsdfComponents& m = h->comp;
   if (bgr && !f->colour) {
     f->err = "ekf_components_get_pruned: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
     return EKF_ERR_ARG;
   }
-  if (!h->mesh.current(*f) || !m.have_pruned(h->mesh)) {
+  if (!h->mesh.current(*f) || !h->comp.have_pruned(h->mesh)) {
     f->err = "ekf_components_get_pruned: no ekf_components_prune since the last ekf_mesh_weld";
     return EKF_ERR_STATE;
   }
-  if (normal && !m.has_normals) {
+  if (normal && !h->comp.out.has_normals) {
     f->err = "ekf_components_get_pruned: normal must be NULL after an ekf_mesh_weld without normals";
     return EKF_ERR_ARG;
   }
-  std::string& err = f->err;
-  const size_t nv = (size_t)std::min(m.n_vert, max_vert), nc = (size_t)std::min(m.n_tri, max_tri) * 3;
-  HIPCHK(hipSetDevice(f->device));
-  if (nv > 0) {
-    if (xyz) HIPCHK(hipMemcpy(xyz, m.xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (grey) HIPCHK(hipMemcpy(grey, m.grey, nv, hipMemcpyDeviceToHost));
-    if (bgr) HIPCHK(hipMemcpy(bgr, m.bgr, nv * 3, hipMemcpyDeviceToHost));
-    if (normal) HIPCHK(hipMemcpy(normal, m.normal, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (key) HIPCHK(hipMemcpy(key, m.key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  }
-  if (nc > 0 && faces) HIPCHK(hipMemcpy(faces, m.faces, nc * sizeof(unsigned), hipMemcpyDeviceToHost));
-  return EKF_OK;
+  return mesh_copy_out(h, h->comp.pruned_view(h->mesh), xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
@@ -6407,7 +6401,7 @@ int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long
 
 // ---- Taubin smoothing of the welded or the pruned mesh -----------------------------------------------------
 // The mesh a smoothing call is about, if the handle holds it: EKF_OK, or EKF_ERR_STATE with the message set.
-static int smooth_source(ekf_fusion* h, const char* who, int source, ekf::SmoothSource* s) {
+static int smooth_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s) {
   auto* f = h->impl;
   if (!h->mesh.current(*f)) {
     f->err = std::string(who) + ": no ekf_mesh_weld since the volume last changed";
@@ -6417,20 +6411,20 @@ static int smooth_source(ekf_fusion* h, const char* who, int source, ekf::Smooth
     f->err = std::string(who) + ": source 1 needs an ekf_components_prune since the last ekf_mesh_weld";
     return EKF_ERR_STATE;
   }
-  *s = ekf::SmoothSource::of(source, h->mesh, h->comp);
+  *s = source == 0 ? h->mesh.view() : h->comp.pruned_view(h->mesh);
   return EKF_OK;
 }
 
-// The mesh the last run smoothed, if it is still the handle's: the run's source says which.
-static int smooth_result(ekf_fusion* h, const char* who, ekf::SmoothSource* s) {
+// The last run's mesh, if the mesh it smoothed is still the handle's: the run's source says which.
+static int smooth_result(ekf_fusion* h, const char* who, ekf::MeshView* r) {
   auto* f = h->impl;
   const ekf::TsdfSmooth& m = h->smooth;
-  const bool held = m.res_valid && h->mesh.current(*f) && (m.res.source == 0 || h->comp.have_pruned(h->mesh));
-  if (held) *s = ekf::SmoothSource::of(m.res.source, h->mesh, h->comp);
-  if (!held || !m.have_result(*s)) {
+  ekf::MeshView s;
+  if (!m.res_valid || smooth_source(h, who, m.res.source, &s) != EKF_OK || !m.have_result(s)) {
     f->err = std::string(who) + ": no ekf_smooth_run on the current mesh";
     return EKF_ERR_STATE;
   }
+  *r = m.result(s);
   return EKF_OK;
 }
 
@@ -6445,7 +6439,7 @@ int ekf_smooth_run(ekf_fusion* h, int source, int iterations, double lambda, dou
              "n_vert and n_tri not NULL";
     return EKF_ERR_ARG;
   }
-  ekf::SmoothSource s;
+  ekf::MeshView s;
   const int rc = smooth_source(h, "ekf_smooth_run", source, &s);
   if (rc != EKF_OK) return rc;
   std::string& err = f->err;
@@ -6460,37 +6454,24 @@ int ekf_smooth_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* g
                    unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
-  const ekf::TsdfSmooth& m = h->smooth;
   if (bgr && !f->colour) {
     f->err = "ekf_smooth_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
     return EKF_ERR_ARG;
   }
-  ekf::SmoothSource s;
-  const int rc = smooth_result(h, "ekf_smooth_get", &s);
+  ekf::MeshView m;                                         // faces, key, grey and bgr are the source's own buffers
+  const int rc = smooth_result(h, "ekf_smooth_get", &m);
   if (rc != EKF_OK) return rc;
   if (normal && !m.has_normals) {
     f->err = "ekf_smooth_get: normal must be NULL after an ekf_smooth_run without normals";
     return EKF_ERR_ARG;
   }
-  std::string& err = f->err;
-  const size_t nv = (size_t)std::min(s.n_vert, max_vert), nc = (size_t)std::min(s.n_tri, max_tri) * 3;
-  const bool weld = s.source == 0;                         // faces, key, grey and bgr are the source's own buffers
-  HIPCHK(hipSetDevice(f->device));
-  if (nv > 0) {
-    if (xyz) HIPCHK(hipMemcpy(xyz, m.pos[m.last], nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (grey) HIPCHK(hipMemcpy(grey, weld ? h->mesh.grey : h->comp.grey, nv, hipMemcpyDeviceToHost));
-    if (bgr) HIPCHK(hipMemcpy(bgr, weld ? h->mesh.bgr : h->comp.bgr, nv * 3, hipMemcpyDeviceToHost));
-    if (normal) HIPCHK(hipMemcpy(normal, m.normal, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (key) HIPCHK(hipMemcpy(key, weld ? h->mesh.key : h->comp.key, nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  }
-  if (nc > 0 && faces) HIPCHK(hipMemcpy(faces, s.faces, nc * sizeof(unsigned), hipMemcpyDeviceToHost));
-  return EKF_OK;
+  return mesh_copy_out(h, m, xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned* inc, unsigned* deg, unsigned char* boundary, unsigned long long max_vert) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
-  ekf::SmoothSource s;
+  ekf::MeshView s;
   const int rc = smooth_result(h, "ekf_smooth_get_adjacency", &s);
   if (rc != EKF_OK) return rc;
   std::string& err = f->err;

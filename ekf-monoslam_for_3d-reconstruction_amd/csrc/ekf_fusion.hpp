@@ -30,6 +30,8 @@ namespace ekf {
 constexpr int kFusionMaxDim = 1024, kFusionMaxMaps = 65535, kFusionMaxMapDim = 8192;
 constexpr long long kFusionMaxVoxels = 1ll << 28;
 constexpr int kFusionBlock = 256;                // cells per workgroup of the extraction, voxels per workgroup of the integration
+// the workgroups of a launch with one lane for each of n items
+inline unsigned fusion_blocks(unsigned long long n) { return (unsigned)((n + kFusionBlock - 1) / kFusionBlock); }
 
 struct TsdfGrid {
   int nx, ny, nz;

@@ -212,6 +212,30 @@ __global__ void __launch_bounds__(256) k_mesh_faces(MeshArgs a) {
 }
 
 #ifndef EKF_KERNELS_ONLY
+// An indexed mesh on the device as whoever reads it sees it: the six arrays, the counts, and which mesh it is.  `source` 0 is
+// the last weld and 1 the last pruned mesh (ekf_mesh_components.hpp); `serial` counts the welds and `prune` the prunes, so the
+// three name one mesh.  A view owns nothing and holds as long as its mesh does.
+struct MeshView {
+  const double* xyz = nullptr;
+  const unsigned long long* key = nullptr;
+  const unsigned char* grey = nullptr;
+  const unsigned char* bgr = nullptr;            // of a colour volume only
+  const float* normal = nullptr;                 // to be read with has_normals only
+  const unsigned* faces = nullptr;
+  unsigned long long n_vert = 0, n_tri = 0;
+  bool has_normals = false;
+  int source = 0;
+  unsigned long long serial = 0, prune = 0;
+
+  static MeshView of(const DevMeshBufs& b, int source, unsigned long long serial, unsigned long long prune) {
+    MeshView v;
+    v.xyz = b.xyz; v.key = b.key; v.grey = b.grey; v.bgr = b.bgr; v.normal = b.normal; v.faces = b.faces;
+    v.n_vert = b.n_vert; v.n_tri = b.n_tri; v.has_normals = b.has_normals;
+    v.source = source; v.serial = serial; v.prune = prune;
+    return v;
+  }
+};
+
 // Host side: the scratch and the indexed mesh of the last weld, owned by the fusion handle they belong to; allocated at the
 // first weld, grow-only.  The scratch is 4 bytes a voxel and 1 byte a cell (1.25 GB at 2^28 voxels).  The five launches are
 // kinds of a timer of their own, so that the fusion handle's counts stay what they are without a weld.
@@ -219,18 +243,14 @@ struct TsdfMesh {
   DevBuf<unsigned char> cell_ok;
   DevBuf<unsigned> code, blk_tot;
   DevBuf<unsigned long long> blk_off;
-  DevBuf<double> xyz;
-  DevBuf<unsigned long long> key;
-  DevBuf<unsigned char> grey, bgr;    // bgr: colour volumes only
-  DevBuf<float> normal;               // welds with normals only
-  DevBuf<unsigned> faces;
-  unsigned long long n_vert = 0, n_tri = 0;
+  DevMeshBufs out;                               // the welded mesh; bgr: colour volumes only, normal: welds with normals only
   unsigned long long weld_changes = 0;           // TsdfFusion::changes when the weld was made
   unsigned long long serial = 0;                 // counts the welds: what ekf_mesh_components.hpp derives from one names it
-  bool valid = false, has_normals = false;
+  bool valid = false;
   KernelTimer<kMeshKinds> timer;
 
   bool current(const TsdfFusion& f) const { return valid && weld_changes == f.changes; }
+  MeshView view() const { return MeshView::of(out, 0, serial, 0); }
 
   // (extract, unless the handle holds the soup of this min_count) -> cells -> edges -> scan -> one 8-byte read-back -> (grow
   // the mesh buffers) -> vertices -> faces.  A failed allocation leaves the soup and the volume as they were; the previous
@@ -242,7 +262,7 @@ struct TsdfMesh {
       if ((e = f.extract(min_count)) != hipSuccess) return e;
     }
     const unsigned nvox = (unsigned)f.nvox(), nc = f.ncell();
-    const unsigned vblk = (nvox + kFusionBlock - 1) / kFusionBlock, cblk = (nc + kFusionBlock - 1) / kFusionBlock;
+    const unsigned vblk = fusion_blocks(nvox), cblk = fusion_blocks(nc);
     valid = false;
     ++serial;
     if ((e = cell_ok.reserve(nc)) != hipSuccess || (e = code.reserve(nvox)) != hipSuccess || (e = blk_tot.reserve(vblk)) != hipSuccess ||
@@ -260,28 +280,12 @@ struct TsdfMesh {
     unsigned long long total = 0;
     if ((e = hipMemcpy(&total, blk_off + vblk, sizeof(total), hipMemcpyDeviceToHost)) != hipSuccess) return e;
     const size_t nv = (size_t)total, ncorner = (size_t)f.n_tri * 3;
-    if (nv * 3 > xyz.capacity() || nv > key.capacity() || nv > grey.capacity() || (f.colour && nv * 3 > bgr.capacity()) ||
-        (normals && nv * 3 > normal.capacity()) || ncorner > faces.capacity()) {
-      DevBuf<double> x;
-      DevBuf<unsigned long long> k;
-      DevBuf<unsigned char> gr, co;
-      DevBuf<float> nr;
-      DevBuf<unsigned> fa;
-      if ((e = x.reserve(nv * 3)) != hipSuccess || (e = k.reserve(nv)) != hipSuccess || (e = gr.reserve(nv)) != hipSuccess ||
-          (f.colour && (e = co.reserve(nv * 3)) != hipSuccess) || (normals && (e = nr.reserve(nv * 3)) != hipSuccess) ||
-          (e = fa.reserve(ncorner)) != hipSuccess) {
-        (void)hipGetLastError();
-        return e;
-      }
-      xyz = std::move(x);
-      key = std::move(k);
-      grey = std::move(gr);
-      bgr = std::move(co);
-      normal = std::move(nr);
-      faces = std::move(fa);
+    if ((e = out.grow(nv, ncorner, f.colour, normals)) != hipSuccess) {
+      (void)hipGetLastError();
+      return e;
     }
-    a.xyz = xyz; a.key = key; a.grey = grey; a.bgr = bgr; a.normal = normal;
-    a.soup_key = f.m_key; a.faces = faces; a.ncorner = (unsigned long long)ncorner;
+    a.xyz = out.xyz; a.key = out.key; a.grey = out.grey; a.bgr = out.bgr; a.normal = out.normal;
+    a.soup_key = f.m_key; a.faces = out.faces; a.ncorner = (unsigned long long)ncorner;
     if (nv > 0) {
       if (normals)
         e = timer.run(3, [&] { k_mesh_vertices<true><<<vblk, kFusionBlock, 0, nullptr>>>(a); });
@@ -289,13 +293,11 @@ struct TsdfMesh {
         e = timer.run(3, [&] { k_mesh_vertices<false><<<vblk, kFusionBlock, 0, nullptr>>>(a); });
       if (e != hipSuccess) return e;
     }
-    if (ncorner > 0) {
-      const unsigned fblk = (unsigned)((ncorner + kFusionBlock - 1) / kFusionBlock);
-      if ((e = timer.run(4, [&] { k_mesh_faces<<<fblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
-    }
-    n_vert = total;
-    n_tri = f.n_tri;
-    has_normals = normals;
+    if (ncorner > 0 && (e = timer.run(4, [&] { k_mesh_faces<<<fusion_blocks(ncorner), kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess)
+      return e;
+    out.n_vert = total;
+    out.n_tri = f.n_tri;
+    out.has_normals = normals;
     weld_changes = f.changes;
     valid = true;
     return hipSuccess;

@@ -284,51 +284,48 @@ __global__ void __launch_bounds__(256) k_comp_faces(CompArgs a) {
 struct TsdfComponents {
   DevBuf<unsigned> L, R, S, V, T, blk_tot, n_roots;
   DevBuf<unsigned long long> off, best;
-  DevBuf<double> xyz;                 // the pruned mesh
-  DevBuf<unsigned long long> key;
-  DevBuf<unsigned char> grey, bgr;
-  DevBuf<float> normal;
-  DevBuf<unsigned> faces;
+  DevMeshBufs out;                                             // the pruned mesh
   unsigned long long n_comp = 0;                               // of the components
-  unsigned long long n_vert = 0, n_tri = 0, n_kept = 0;        // of the pruned mesh
+  unsigned long long n_kept = 0;                               // of the pruned mesh
   unsigned long long comp_serial = 0, prune_serial = 0;
   unsigned long long prunes = 0;                               // counts the prunes: what ekf_mesh_smooth.hpp derives from one names it
-  bool comp_valid = false, prune_valid = false, has_normals = false;
+  bool comp_valid = false, prune_valid = false;
   KernelTimer<kCompKinds> timer;
 
-  bool have_components(const TsdfMesh& m) const { return comp_valid && comp_serial == m.serial; }
-  bool have_pruned(const TsdfMesh& m) const { return prune_valid && prune_serial == m.serial; }
+  bool have_components(const TsdfMesh& w) const { return comp_valid && comp_serial == w.serial; }
+  bool have_pruned(const TsdfMesh& w) const { return prune_valid && prune_serial == w.serial; }
+  MeshView pruned_view(const TsdfMesh& w) const { return MeshView::of(out, 1, w.serial, prunes); }
 
-  static unsigned blocks(unsigned long long n) { return (unsigned)((n + kFusionBlock - 1) / kFusionBlock); }
   // three rows of offsets, each ending at the last word of its row of `pitch` words, so that the totals stand one pitch apart
   static size_t pitch(unsigned vblk, unsigned tblk) { return (size_t)std::max(vblk, tblk) + 1; }
 
-  CompArgs args(const TsdfMesh& m, bool colour) const {
+  CompArgs args(const MeshView& m, bool colour) const {
     CompArgs a{};
     a.faces = m.faces;
     a.L = L; a.R = R; a.S = S; a.V = V; a.T = T; a.blk_tot = blk_tot;
     a.best = best; a.n_roots = n_roots;
-    a.n_vert = (unsigned)m.n_vert; a.vblk = blocks(m.n_vert); a.n_tri = m.n_tri;
-    const unsigned tblk = blocks(m.n_tri);
+    a.n_vert = (unsigned)m.n_vert; a.vblk = fusion_blocks(m.n_vert); a.n_tri = m.n_tri;
+    const unsigned tblk = fusion_blocks(m.n_tri);
     const size_t P = pitch(a.vblk, tblk);
     a.off_v = off + (P - 1 - a.vblk);
     a.off_t = off + P + (P - 1 - tblk);
     a.min_triangles = 1; a.largest = 0;
     a.xyz = m.xyz; a.key = m.key; a.grey = m.grey;
-    a.bgr = colour ? (const unsigned char*)m.bgr : nullptr;
-    a.normal = m.has_normals ? (const float*)m.normal : nullptr;
+    a.bgr = colour ? m.bgr : nullptr;
+    a.normal = m.has_normals ? m.normal : nullptr;
     return a;
   }
 
   // init -> union -> count -> (flags, for the sizes in L, unless a prune follows, whose own flags leave them there) -> one
   // 4-byte read-back.  No launch for a weld without triangles.
-  hipError_t components(const TsdfMesh& m, bool colour, bool with_sizes = true) {
+  hipError_t components(const TsdfMesh& w, bool colour, bool with_sizes = true) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
     comp_valid = prune_valid = false;
+    const MeshView m = w.view();
     if (m.n_tri > 0) {
       const size_t nv = (size_t)m.n_vert, nt = (size_t)m.n_tri;
-      const unsigned vblk = blocks(m.n_vert), tblk = blocks(m.n_tri);
+      const unsigned vblk = fusion_blocks(m.n_vert), tblk = fusion_blocks(m.n_tri);
       if ((e = L.reserve(nv)) != hipSuccess || (e = R.reserve(nv)) != hipSuccess || (e = S.reserve(nv)) != hipSuccess ||
           (e = V.reserve(nv)) != hipSuccess || (e = T.reserve(nt)) != hipSuccess ||
           (e = blk_tot.reserve((size_t)vblk * 2 + tblk)) != hipSuccess || (e = off.reserve(3 * pitch(vblk, tblk))) != hipSuccess ||
@@ -354,14 +351,15 @@ struct TsdfComponents {
 
   // (components, unless the handle holds them for this weld) -> (largest) -> flags -> three scans -> one read-back of the three
   // totals -> (grow the pruned mesh's buffers) -> vertices -> faces.  The weld is only read.
-  hipError_t prune(const TsdfMesh& m, bool colour, unsigned min_triangles, bool largest) {
+  hipError_t prune(const TsdfMesh& w, bool colour, unsigned min_triangles, bool largest) {
     hipError_t e;
-    if (!have_components(m) && (e = components(m, colour, false)) != hipSuccess) return e;
+    if (!have_components(w) && (e = components(w, colour, false)) != hipSuccess) return e;
     prune_valid = false;
     ++prunes;
+    const MeshView m = w.view();
     unsigned long long totals[3] = {0, 0, 0};
     if (m.n_tri > 0) {
-      const unsigned vblk = blocks(m.n_vert), tblk = blocks(m.n_tri);
+      const unsigned vblk = fusion_blocks(m.n_vert), tblk = fusion_blocks(m.n_tri);
       const size_t P = pitch(vblk, tblk);
       CompArgs a = args(m, colour);
       a.min_triangles = min_triangles;
@@ -379,35 +377,18 @@ struct TsdfComponents {
       if ((e = hipMemcpy2D(totals, sizeof(totals[0]), off + (P - 1), P * sizeof(totals[0]), sizeof(totals[0]), 3, hipMemcpyDeviceToHost)) != hipSuccess)
         return e;
       const size_t nv = (size_t)totals[0], ncorner = (size_t)totals[1] * 3;
-      const bool normals = m.has_normals;
-      if (nv * 3 > xyz.capacity() || nv > key.capacity() || nv > grey.capacity() || (colour && nv * 3 > bgr.capacity()) ||
-          (normals && nv * 3 > normal.capacity()) || ncorner > faces.capacity()) {
-        DevBuf<double> x;
-        DevBuf<unsigned long long> k;
-        DevBuf<unsigned char> gr, co;
-        DevBuf<float> nr;
-        DevBuf<unsigned> fa;
-        if ((e = x.reserve(nv * 3)) != hipSuccess || (e = k.reserve(nv)) != hipSuccess || (e = gr.reserve(nv)) != hipSuccess ||
-            (colour && (e = co.reserve(nv * 3)) != hipSuccess) || (normals && (e = nr.reserve(nv * 3)) != hipSuccess) ||
-            (e = fa.reserve(ncorner)) != hipSuccess) {
-          (void)hipGetLastError();
-          return e;
-        }
-        xyz = std::move(x);
-        key = std::move(k);
-        grey = std::move(gr);
-        bgr = std::move(co);
-        normal = std::move(nr);
-        faces = std::move(fa);
+      if ((e = out.grow(nv, ncorner, colour, m.has_normals)) != hipSuccess) {
+        (void)hipGetLastError();
+        return e;
       }
-      a.p_xyz = xyz; a.p_key = key; a.p_grey = grey; a.p_bgr = bgr; a.p_normal = normal; a.p_faces = faces;
+      a.p_xyz = out.xyz; a.p_key = out.key; a.p_grey = out.grey; a.p_bgr = out.bgr; a.p_normal = out.normal; a.p_faces = out.faces;
       if (nv > 0 && (e = timer.run(6, [&] { k_comp_vertices<<<vblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
       if (ncorner > 0 && (e = timer.run(7, [&] { k_comp_faces<<<tblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
     }
-    n_vert = totals[0];
-    n_tri = totals[1];
+    out.n_vert = totals[0];
+    out.n_tri = totals[1];
     n_kept = totals[2];
-    has_normals = m.has_normals;
+    out.has_normals = m.has_normals;
     prune_serial = m.serial;
     prune_valid = true;
     return hipSuccess;

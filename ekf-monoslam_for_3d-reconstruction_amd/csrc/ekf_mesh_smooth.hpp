@@ -218,51 +218,35 @@ __global__ void __launch_bounds__(256) k_smooth_normals(SmoothArgs a) {
 }
 
 #ifndef EKF_KERNELS_ONLY
-// What a run reads: the last weld (source 0) or the last pruned mesh (source 1).  `serial` counts the welds and `prune` the
-// prunes, so the pair names one mesh.
-struct SmoothSource {
-  int source = 0;
-  unsigned long long serial = 0, prune = 0;
-  const double* xyz = nullptr;
-  const unsigned* faces = nullptr;
-  unsigned long long n_vert = 0, n_tri = 0;
-
-  static SmoothSource of(int source, const TsdfMesh& m, const TsdfComponents& c) {
-    SmoothSource s;
-    s.source = source;
-    s.serial = m.serial;
-    if (source == 0) {
-      s.xyz = m.xyz; s.faces = m.faces; s.n_vert = m.n_vert; s.n_tri = m.n_tri;
-    } else {
-      s.prune = c.prunes;
-      s.xyz = c.xyz; s.faces = c.faces; s.n_vert = c.n_vert; s.n_tri = c.n_tri;
-    }
-    return s;
-  }
-};
-
 // Host side: the adjacency of one source mesh and the last run's positions and normals, owned by the fusion handle beside
-// its TsdfMesh and TsdfComponents; allocated by the first run, grow-only.  The source is only read.  A timer of its own, so that
-// the other getters count what they counted.
+// its TsdfMesh and TsdfComponents; allocated by the first run, grow-only.  A run reads the view of the last weld or of the last
+// pruned mesh and only reads it.  A timer of its own, so that the other getters count what they counted.
 struct TsdfSmooth {
   DevBuf<unsigned> inc, pre, deg, blk_tot, tri, nbr;
   DevBuf<unsigned char> boundary;
   DevBuf<unsigned long long> off;
   DevBuf<double> pos[2];
   DevBuf<float> normal;
-  SmoothSource adj, res;              // the mesh the adjacency and the result were made from
+  MeshView adj, res;                  // the mesh the adjacency and the result were made from: only what `same` compares is used
   bool adj_valid = false, res_valid = false, has_normals = false;
   int last = 0;                       // the buffer that holds the result
   KernelTimer<kSmoothKinds> timer;
 
-  static bool same(const SmoothSource& a, const SmoothSource& b) {
+  static bool same(const MeshView& a, const MeshView& b) {
     return a.source == b.source && a.serial == b.serial && a.prune == b.prune;
   }
-  bool have_adjacency(const SmoothSource& s) const { return adj_valid && same(adj, s); }
-  bool have_result(const SmoothSource& s) const { return res_valid && same(res, s); }
-  static unsigned blocks(unsigned long long n) { return (unsigned)((n + kFusionBlock - 1) / kFusionBlock); }
+  bool have_adjacency(const MeshView& s) const { return adj_valid && same(adj, s); }
+  bool have_result(const MeshView& s) const { return res_valid && same(res, s); }
+  // the last run's mesh: its source `s` with the positions and the normals of the run
+  MeshView result(const MeshView& s) const {
+    MeshView r = s;
+    r.xyz = pos[last];
+    r.normal = normal;
+    r.has_normals = has_normals;
+    return r;
+  }
 
-  SmoothArgs args(const SmoothSource& s) const {
+  SmoothArgs args(const MeshView& s) const {
     SmoothArgs a{};
     a.faces = s.faces;
     a.inc = inc; a.pre = pre; a.deg = deg; a.boundary = boundary; a.blk_tot = blk_tot; a.off = off; a.tri = tri; a.nbr = nbr;
@@ -271,11 +255,11 @@ struct TsdfSmooth {
   }
 
   // memset -> count -> offsets -> scan -> fill -> lists.  No read-back: the lists' total is 3 n_tri.
-  hipError_t adjacency(const SmoothSource& s) {
+  hipError_t adjacency(const MeshView& s) {
     hipError_t e;
     adj_valid = false;
     const size_t nv = (size_t)s.n_vert, nt = (size_t)s.n_tri;
-    const unsigned vblk = blocks(s.n_vert), tblk = blocks(s.n_tri);
+    const unsigned vblk = fusion_blocks(s.n_vert), tblk = fusion_blocks(s.n_tri);
     if (s.n_tri > 0xffffffffull) return hipErrorInvalidValue;                // a triangle's number is a word of `tri`
     if ((e = inc.reserve(nv)) != hipSuccess || (e = pre.reserve(nv)) != hipSuccess || (e = deg.reserve(nv)) != hipSuccess ||
         (e = boundary.reserve(nv)) != hipSuccess || (e = blk_tot.reserve(vblk)) != hipSuccess ||
@@ -300,13 +284,13 @@ struct TsdfSmooth {
 
   // (the adjacency, unless the handle holds it for this mesh) -> the steps, from the source into pos[0], then between pos[0]
   // and pos[1] -> (normals).  Every buffer is there before the first step; nothing is read back.
-  hipError_t run(const SmoothSource& s, int iterations, double lambda, double mu, bool pin, bool normals) {
+  hipError_t run(const MeshView& s, int iterations, double lambda, double mu, bool pin, bool normals) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
     res_valid = false;
     if (s.n_tri > 0) {
       const size_t nv = (size_t)s.n_vert;
-      const unsigned vblk = blocks(s.n_vert);
+      const unsigned vblk = fusion_blocks(s.n_vert);
       const int steps = mu != 0.0 ? 2 * iterations : iterations;
       if ((e = pos[0].reserve(nv * 3)) != hipSuccess || (steps > 1 && (e = pos[1].reserve(nv * 3)) != hipSuccess) ||
           (normals && (e = normal.reserve(nv * 3)) != hipSuccess)) {

@@ -196,6 +196,14 @@ class TsdfVolume(capi.Handle):
             self._check(self._lib.ekf_colour_get_mesh(self._h, _ptr(m.colour), n))
         return m
 
+    def _indexed_mesh(self, getter, nv: int, nt: int, normals: bool) -> IndexedMesh:
+        """The arrays of a mesh of ``nv`` vertices and ``nt`` triangles on the device, fetched by one of the three getters."""
+        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
+                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
+                        np.zeros(nv, np.uint64))
+        self._check(getter(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour), _ptr(m.normals), _ptr(m.key), nv, nt))
+        return m
+
     def weld(self, min_count: int = 1, normals: bool = False) -> IndexedMesh:
         """The indexed mesh, welded on the device: ``weld(self.extract(min_count))`` bit for bit, without the
         soup's way over the host and without a sort.  It extracts first unless the handle holds the soup of this
@@ -205,12 +213,7 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_mesh_weld(self._h, int(min_count), 1 if normals else 0, C.byref(nv), C.byref(nt)))
         nv, nt = int(nv.value), int(nt.value)
         self._weld_counts = (nv, nt, bool(normals))
-        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
-                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
-                        np.zeros(nv, np.uint64))
-        self._check(self._lib.ekf_mesh_get(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour), _ptr(m.normals),
-                                           _ptr(m.key), nv, nt))
-        return m
+        return self._indexed_mesh(self._lib.ekf_mesh_get, nv, nt, normals)
 
     def components(self) -> MeshComponents:
         """The connected components of the last ``weld``, found on the device.  The first call allocates 16 bytes
@@ -231,11 +234,7 @@ class TsdfVolume(capi.Handle):
         nv, nt, nk = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
         self._check(self._lib.ekf_components_prune(self._h, int(min_triangles), 1 if largest else 0, C.byref(nv), C.byref(nt), C.byref(nk)))
         nv, nt, normals = int(nv.value), int(nt.value), self._weld_counts[2]
-        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
-                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
-                        np.zeros(nv, np.uint64))
-        self._check(self._lib.ekf_components_get_pruned(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour),
-                                                  _ptr(m.normals), _ptr(m.key), nv, nt))
+        m = self._indexed_mesh(self._lib.ekf_components_get_pruned, nv, nt, normals)
         self.pruned_components = int(nk.value)
         return m
 
@@ -262,12 +261,7 @@ class TsdfVolume(capi.Handle):
                                              1 if pin_boundary else 0, 1 if normals else 0, C.byref(nv), C.byref(nt)))
         nv, nt = int(nv.value), int(nt.value)
         self._smooth_vertices = nv
-        m = IndexedMesh(np.zeros((nv, 3), np.float64), np.zeros((nt, 3), np.uint32), np.zeros(nv, np.uint8),
-                        np.zeros((nv, 3), np.uint8) if self.colour else None, np.zeros((nv, 3), np.float32) if normals else None,
-                        np.zeros(nv, np.uint64))
-        self._check(self._lib.ekf_smooth_get(self._h, _ptr(m.vertices), _ptr(m.faces), _ptr(m.grey), _ptr(m.colour), _ptr(m.normals),
-                                             _ptr(m.key), nv, nt))
-        return m
+        return self._indexed_mesh(self._lib.ekf_smooth_get, nv, nt, normals)
 
     def adjacency(self) -> MeshAdjacency:
         """The adjacency of the mesh the last ``smooth`` ran on."""

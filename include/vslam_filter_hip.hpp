@@ -737,16 +737,7 @@ class TsdfVolumeHip {
     return mesh();
   }
   // the arrays of the last weld() again
-  IndexedMesh mesh() {
-    IndexedMesh m;
-    const size_t nv = (size_t)weld_vertices_, nt = (size_t)weld_triangles_;
-    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
-    if (colour_) m.colour.resize(nv * 3);
-    if (weld_normals_) m.normal.resize(nv * 3);
-    check(ekf_mesh_get(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
-                       weld_normals_ ? m.normal.data() : nullptr, m.key.data(), weld_vertices_, weld_triangles_));
-    return m;
-  }
+  IndexedMesh mesh() { return fetch(ekf_mesh_get, weld_vertices_, weld_triangles_, weld_normals_); }
   // HIP-event milliseconds and launch counts of k_mesh_cells, k_mesh_edges, the weld's k_tsdf_scan, k_mesh_vertices, k_mesh_faces
   void getMeshProfile(double kernel_ms[5], long long launches[5]) { check(ekf_mesh_get_profile(f_, kernel_ms, launches)); }
   // The connected components of the last weld() (section 25), found on the device: two vertices are linked iff a triangle has
@@ -769,16 +760,7 @@ class TsdfVolumeHip {
     return pruned();
   }
   // the arrays of the last prune() again
-  IndexedMesh pruned() {
-    IndexedMesh m;
-    const size_t nv = (size_t)pruned_vertices_, nt = (size_t)pruned_triangles_;
-    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
-    if (colour_) m.colour.resize(nv * 3);
-    if (weld_normals_) m.normal.resize(nv * 3);
-    check(ekf_components_get_pruned(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
-                              weld_normals_ ? m.normal.data() : nullptr, m.key.data(), pruned_vertices_, pruned_triangles_));
-    return m;
-  }
+  IndexedMesh pruned() { return fetch(ekf_components_get_pruned, pruned_vertices_, pruned_triangles_, weld_normals_); }
   // HIP-event milliseconds and launch counts of k_comp_init, k_comp_union, k_comp_count, k_comp_largest, k_comp_flags, the
   // prune's k_tsdf_scan, k_comp_vertices, k_comp_faces
   void getComponentProfile(double kernel_ms[8], long long launches[8]) {
@@ -797,16 +779,7 @@ class TsdfVolumeHip {
     return smoothed();
   }
   // the arrays of the last smooth() again
-  IndexedMesh smoothed() {
-    IndexedMesh m;
-    const size_t nv = (size_t)smooth_vertices_, nt = (size_t)smooth_triangles_;
-    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
-    if (colour_) m.colour.resize(nv * 3);
-    if (smooth_normals_) m.normal.resize(nv * 3);
-    check(ekf_smooth_get(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
-                         smooth_normals_ ? m.normal.data() : nullptr, m.key.data(), smooth_vertices_, smooth_triangles_));
-    return m;
-  }
+  IndexedMesh smoothed() { return fetch(ekf_smooth_get, smooth_vertices_, smooth_triangles_, smooth_normals_); }
   // the adjacency of the mesh the last smooth() ran on
   Adjacency adjacency() {
     Adjacency a;
@@ -852,6 +825,19 @@ class TsdfVolumeHip {
       check(ekf_colour_get_render(f_, r.colour.data()));
     }
     return r;
+  }
+  // the arrays of a mesh of n_vert vertices and n_tri triangles on the device, by ekf_mesh_get or one of its two siblings
+  using MeshGetter = int (*)(ekf_fusion*, double*, unsigned int*, unsigned char*, unsigned char*, float*, unsigned long long*,
+                             unsigned long long, unsigned long long);
+  IndexedMesh fetch(MeshGetter getter, unsigned long long n_vert, unsigned long long n_tri, bool normals) {
+    IndexedMesh m;
+    const size_t nv = (size_t)n_vert, nt = (size_t)n_tri;
+    m.xyz.resize(nv * 3); m.faces.resize(nt * 3); m.grey.resize(nv); m.key.resize(nv);
+    if (colour_) m.colour.resize(nv * 3);
+    if (normals) m.normal.resize(nv * 3);
+    check(getter(f_, m.xyz.data(), m.faces.data(), m.grey.data(), colour_ ? m.colour.data() : nullptr,
+                 normals ? m.normal.data() : nullptr, m.key.data(), n_vert, n_tri));
+    return m;
   }
   size_t n_;
   bool colour_;

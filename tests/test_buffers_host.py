@@ -1,5 +1,5 @@
-"""csrc/ekf_buffers.hpp on the CPU: tests/buffers_host.cpp instantiates Buf with a counting malloc / free allocator and is
-built with the host compiler under AddressSanitizer and UBSan (a stand-alone program: nothing is loaded into Python).
+"""csrc/ekf_buffers.hpp on the CPU: tests/buffers_host.cpp instantiates Buf, and IndexedMeshBufs with its all-or-nothing grow,
+with a counting malloc / free allocator and is built with the host compiler under AddressSanitizer and UBSan (a stand-alone program: nothing is loaded into Python).
 The header includes the HIP runtime's API header for hipError_t, so the build needs ROCm's include path, not its library."""
 import os
 import shutil
@@ -32,4 +32,4 @@ def test_buf_ownership_under_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr
     run = subprocess.run([exe], capture_output=True, text=True, timeout=60)     # (LeakSanitizer on, as by default)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert run.stdout.strip() == "allocs=6 frees=6 ok"
+    assert run.stdout.strip() == "allocs=48 frees=48 ok"

@@ -177,6 +177,36 @@ def test_a_colour_volume_with_weld_normals_keeps_its_rows_and_gets_normals_of_it
         v.close()
 
 
+def test_one_handle_regrows_and_reuses_its_mesh_buffers(pkg):
+    """Three rounds of weld, prune and smooth on one handle: a mesh, a larger one, so that the buffers of all three grow, and the
+    first again, in the buffers the larger one left.  The sizes are the oracle's, asserted so that the test cannot stop growing."""
+    name = "41x41x41"
+    planes, dims, origin, voxel, trunc, _ = cs.cases()[name]
+    sizes = {2: (5099, 7154), 1: (7685, 13536)}
+    v = _volume(pkg, planes, dims, origin, voxel, trunc)
+    try:
+        for mc in (2, 1, 2):
+            src = cs.oracle_mesh(name, mc, True)
+            assert (len(src["key"]), len(src["faces"])) == sizes[mc]
+            cut = co.prune(src, 3)
+            weld = v.weld(mc, normals=True)
+            assert _same_mesh(weld, src), mc
+            assert _same_mesh(v.prune(3), cut), mc
+            assert _same_mesh(v.smooth(2, normals=True, source="pruned"), so.smooth(cut, 2, normals=True)), mc
+            assert _same_mesh(_weld_back(pkg, v, weld), src), mc
+        # the weld again, with room for the larger mesh of round two: the rows past the counts are not written
+        (nv, nt), (big_v, big_t) = sizes[2], sizes[1]
+        xyz, faces, grey = np.full((big_v, 3), -1.0), np.full((big_t, 3), 0xFFFFFFFF, np.uint32), np.full(big_v, 0xA5, np.uint8)
+        bgr, nrm, key = np.full((big_v, 3), 0xA5, np.uint8), np.full((big_v, 3), -2.0, np.float32), np.full(big_v, 2**64 - 1, np.uint64)
+        assert pkg.load_library().ekf_mesh_get(v._h, P(xyz), P(faces), P(grey), P(bgr), P(nrm), P(key), big_v, big_t) == 0
+        got = pkg.IndexedMesh(xyz[:nv], faces[:nt], grey[:nv], bgr[:nv], nrm[:nv], key[:nv])
+        assert _same_mesh(got, cs.oracle_mesh(name, 2, True))
+        assert (xyz[nv:] == -1.0).all() and (faces[nt:] == 0xFFFFFFFF).all() and (grey[nv:] == 0xA5).all()
+        assert (bgr[nv:] == 0xA5).all() and (nrm[nv:] == -2.0).all() and (key[nv:] == 2**64 - 1).all()
+    finally:
+        v.close()
+
+
 def test_the_empty_volume_launches_nothing(pkg):
     v = pkg.TsdfVolume(fs.DIMS, fs.ORIGIN, fs.VOXEL, fs.TRUNC)
     try:
