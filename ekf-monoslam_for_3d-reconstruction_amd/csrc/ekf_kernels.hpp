@@ -692,12 +692,15 @@ __global__ void k_compact_transform(const T* __restrict__ src, T* __restrict__ d
           acc = T(0);
           for (int a = 0; a < 6; ++a) acc = t_fma(Jy[ci0 * 6 + a], src[(size_t)(si0 + a) * ld + sj], acc);
         } else if (jp <= ip) {
-          // 3 x 3 block of two converted entries, lower triangle: sum_a Jy_i[a] (sum_b S[i+a][j+b] Jy_j[b])
+          // 3 x 3 block of two converted entries, lower triangle: sum_a Jy_i[a] (sum_b S[i+a][j+b] Jy_j[b]).  Every step is
+          // a spelled-out fma, here and in the mirror order below: left to the compiler's contraction the fp32 build packed
+          // the products of one order (v_pk_mul_f32, then unfused adds) and fused those of the other, and the two
+          // triangles differed in the last bits
           acc = T(0);
           for (int a = 0; a < 6; ++a) {
             T inner = T(0);
-            for (int b = 0; b < 6; ++b) inner += src[(size_t)(si0 + a) * ld + sj + b] * Jy[cj * 6 + b];
-            acc += Jy[ci0 * 6 + a] * inner;
+            for (int b = 0; b < 6; ++b) inner = t_fma(src[(size_t)(si0 + a) * ld + sj + b], Jy[cj * 6 + b], inner);
+            acc = t_fma(Jy[ci0 * 6 + a], inner, acc);
           }
         } else {
           // ... upper triangle: Jy (S Jy^T) is symmetric only up to rounding, so the element is evaluated in the ORDER of its
@@ -708,8 +711,8 @@ __global__ void k_compact_transform(const T* __restrict__ src, T* __restrict__ d
           acc = T(0);
           for (int b = 0; b < 6; ++b) {
             T inner = T(0);
-            for (int a = 0; a < 6; ++a) inner += src[(size_t)(si0 + a) * ld + sj + b] * Jy[ci0 * 6 + a];
-            acc += Jy[cj * 6 + b] * inner;
+            for (int a = 0; a < 6; ++a) inner = t_fma(src[(size_t)(si0 + a) * ld + sj + b], Jy[ci0 * 6 + a], inner);
+            acc = t_fma(Jy[cj * 6 + b], inner, acc);
           }
         }
         dst[(size_t)ip * ld + jp] = acc;
@@ -996,30 +999,35 @@ __global__ void k_chi2_gate(const T* __restrict__ h, const T* __restrict__ Sd, c
 // Invariants of the device covariance (test / debug entry ekf_check_invariants): out[0] = max |S[i][j]| outside the
 // live n x n within the n_pad x ld buffer (must be 0: the tile kernels carry no edge guards), out[1] = max
 // |S[i][j] - S[j][i]| over the live block, out[2] = max |S[i][j]| over it.  Non-negative floats order like their
-// bit patterns, so the three maxima are integer atomicMax on the float bits of the (double -> float) values.
+// bit patterns, so the three maxima are integer maxima (atomicMax) over the float bits of the (double -> float) values.
+// A NaN is recorded as the canonical quiet NaN, whose bits order above +inf: a NaN anywhere in a region makes that
+// region's output NaN (fmaxf would drop it, and a covariance full of NaN would read as (0, 0, 0)).
+__device__ __forceinline__ unsigned int invariant_key(float x) {
+  return (x != x) ? 0x7fc00000u : __float_as_uint(fabsf(x));
+}
 template <typename T>
 __global__ void k_check_invariants(const T* __restrict__ S, int ld, int n, int n_pad, unsigned int* __restrict__ out) {
   const int i = blockIdx.y;
-  float pad = 0.f, asym = 0.f, big = 0.f;
+  unsigned int pad = 0u, asym = 0u, big = 0u;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < ld; j += gridDim.x * blockDim.x) {
     const T v = S[(size_t)i * ld + j];
     if (i >= n || j >= n) {
-      pad = fmaxf(pad, fabsf(float(v)));
+      pad = max(pad, invariant_key(float(v)));
     } else {
-      big = fmaxf(big, fabsf(float(v)));
-      if (j < i) asym = fmaxf(asym, fabsf(float(v - S[(size_t)j * ld + i])));
+      big = max(big, invariant_key(float(v)));
+      if (j < i) asym = max(asym, invariant_key(float(v - S[(size_t)j * ld + i])));
     }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    pad = fmaxf(pad, __shfl_down(pad, off, 64));
-    asym = fmaxf(asym, __shfl_down(asym, off, 64));
-    big = fmaxf(big, __shfl_down(big, off, 64));
+    pad = max(pad, __shfl_down(pad, off, 64));
+    asym = max(asym, __shfl_down(asym, off, 64));
+    big = max(big, __shfl_down(big, off, 64));
   }
   if ((threadIdx.x & 63) == 0) {
-    if (pad > 0.f) atomicMax(out + 0, __float_as_uint(pad));
-    if (asym > 0.f) atomicMax(out + 1, __float_as_uint(asym));
-    if (big > 0.f) atomicMax(out + 2, __float_as_uint(big));
+    if (pad > 0u) atomicMax(out + 0, pad);
+    if (asym > 0u) atomicMax(out + 1, asym);
+    if (big > 0u) atomicMax(out + 2, big);
   }
 }
 

@@ -466,7 +466,10 @@ class VSlamFilter(capi.Handle):
         return out.value
 
     def checkInvariants(self):
-        """(max |Sigma| outside the live block of the padded device buffer, max |Sigma - Sigma^T|, max |Sigma|)."""
+        """(max |Sigma| outside the live block of the padded device buffer, max |Sigma - Sigma^T|, max |Sigma|).
+
+        A NaN is reported, not dropped: one in the padding makes the first value NaN, one in the live block the third,
+        and one in an off-diagonal live entry the second as well -- `pad == 0.0 and asym <= c * big` is False then."""
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         self._check(self._lib.ekf_check_invariants(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value

@@ -329,7 +329,11 @@ int ekf_covariance_parameter(ekf_filter* f, double* out);
 /* Invariants of the device-resident covariance, evaluated on the device (no n^2 copy): max |Sigma| outside the live
  * n x n inside the padded buffer (the tile kernels rely on exact zeros there), max |Sigma[i][j] - Sigma[j][i]| and
  * max |Sigma[i][j]| over the live block (the reference never symmetrises, vR.cpp:1279; this implementation keeps
- * Sigma exactly symmetric).  Any pointer may be NULL.  Test / debug entry: no counterpart in the reference. */
+ * Sigma exactly symmetric).  A NaN is never dropped: one anywhere outside the live block makes max_abs_outside_live
+ * NaN, one in the live block makes max_abs_live NaN, and one in an off-diagonal live entry (or an entry pair whose
+ * difference is NaN, such as inf - inf) makes max_asymmetry NaN as well, so that `pad == 0 && asym <= c * big` is
+ * false on a covariance that holds a NaN.  Finite input is reported as its maxima, rounded to float.
+ * Any pointer may be NULL.  Test / debug entry: no counterpart in the reference. */
 int ekf_check_invariants(ekf_filter* f, double* max_abs_outside_live, double* max_asymmetry, double* max_abs_live);
 /* inverseDepth2XyzWorld mode 1 + Jf Sigma_ff Jf^T (vR.cpp:690-738,
  * RosVSLAMRansac.cpp:177-183): world point (3) and 3x3 covariance (column-major). */
