@@ -19,3 +19,4 @@ from .fusion import Render, audit_recording, shade  # noqa: F401
 from .fusion import IndexedMesh  # noqa: F401
 from .fusion import MeshComponents  # noqa: F401
 from .fusion import MeshAdjacency  # noqa: F401
+from .fusion import SimplifyStats  # noqa: F401

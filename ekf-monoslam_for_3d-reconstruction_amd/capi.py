@@ -246,6 +246,11 @@ _PROTOS = {
     "ekf_smooth_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
     "ekf_smooth_get_adjacency": (C.c_int, [_P, _P, _P, _P, C.c_ulonglong]),
     "ekf_smooth_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_simplify_run": (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                   C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "ekf_simplify_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
+    "ekf_simplify_get_map": (C.c_int, [_P, _P, C.c_ulonglong]),
+    "ekf_simplify_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -39,6 +39,7 @@
 #include "ekf_mesh.hpp"
 #include "ekf_mesh_components.hpp"
 #include "ekf_mesh_smooth.hpp"
+#include "ekf_mesh_simplify.hpp"
 
 namespace ekf {
 
@@ -5869,6 +5870,7 @@ struct ekf_fusion {
   ekf::TsdfMesh mesh;                 // the last weld of the volume's mesh (ekf_mesh_*)
   ekf::TsdfComponents comp;           // that weld's components and its pruned copy
   ekf::TsdfSmooth smooth;             // the smoothed copy of either of them
+  ekf::TsdfSimplify simp;             // the simplified copy of any of the three
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6140,6 +6142,7 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   h->mesh.timer.enable(enable != 0);    // the five of the weld
   h->comp.timer.enable(enable != 0);    // the eight of the components
   h->smooth.timer.enable(enable != 0);  // the seven of the smoothing
+  h->simp.timer.enable(enable != 0);    // the ten of the simplification
   return EKF_OK;
 }
 
@@ -6488,6 +6491,96 @@ int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned* inc, unsigned* deg, unsign
 int ekf_smooth_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->smooth.timer.read(kernel_ms, launches, 0, ekf::kSmoothKinds);
+  return EKF_OK;
+}
+
+// ---- vertex-clustering simplification of the welded, the pruned or the smoothed mesh -----------------------
+// The mesh a simplification is about, if the handle holds it, and for source 2 the number of the smooth run that made it:
+// EKF_OK, or EKF_ERR_STATE with the message set.
+static int simplify_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s, unsigned long long* run) {
+  *run = 0;
+  if (source != 2) return smooth_source(h, who, source, s);
+  auto* f = h->impl;
+  if (!h->mesh.current(*f)) {
+    f->err = std::string(who) + ": no ekf_mesh_weld since the volume last changed";
+    return EKF_ERR_STATE;
+  }
+  if (smooth_result(h, who, s) != EKF_OK) {
+    f->err = std::string(who) + ": source 2 needs an ekf_smooth_run on the current mesh";
+    return EKF_ERR_STATE;
+  }
+  *run = h->smooth.runs;
+  return EKF_OK;
+}
+
+// Whether the last run's result is still that of the handle's meshes: its source says which.
+static int simplify_result(ekf_fusion* h, const char* who) {
+  auto* f = h->impl;
+  const ekf::TsdfSimplify& m = h->simp;
+  ekf::MeshView s;
+  unsigned long long run = 0;
+  if (!m.valid || simplify_source(h, who, m.from, &s, &run) != EKF_OK || !m.have_result(m.from, s, run)) {
+    f->err = std::string(who) + ": no ekf_simplify_run on the current mesh";
+    return EKF_ERR_STATE;
+  }
+  return EKF_OK;
+}
+
+int ekf_simplify_run(ekf_fusion* h, int source, double cell, unsigned long long* n_vert, unsigned long long* n_tri,
+                     unsigned long long* n_degenerate, unsigned long long* n_duplicate) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (source < 0 || source > 2 || !std::isfinite(cell) || !(cell >= f->g.voxel) || !n_vert || !n_tri || !n_degenerate || !n_duplicate) {
+    f->err = "ekf_simplify_run: source 0, 1 or 2, cell finite and >= the voxel, n_vert, n_tri, n_degenerate and n_duplicate not NULL";
+    return EKF_ERR_ARG;
+  }
+  ekf::MeshView s;
+  unsigned long long run = 0;
+  const int rc = simplify_source(h, "ekf_simplify_run", source, &s, &run);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->simp.run(s, source, run, f->g, cell, f->colour));
+  *n_vert = h->simp.out.n_vert;
+  *n_tri = h->simp.out.n_tri;
+  *n_degenerate = h->simp.n_degenerate;
+  *n_duplicate = h->simp.n_duplicate;
+  return EKF_OK;
+}
+
+int ekf_simplify_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                     unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (bgr && !f->colour) {
+    f->err = "ekf_simplify_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_ARG;
+  }
+  const int rc = simplify_result(h, "ekf_simplify_get");
+  if (rc != EKF_OK) return rc;
+  if (normal && !h->simp.out.has_normals) {
+    f->err = "ekf_simplify_get: normal must be NULL after an ekf_simplify_run on a source without normals";
+    return EKF_ERR_ARG;
+  }
+  return mesh_copy_out(h, ekf::MeshView::of(h->simp.out, h->simp.from, h->simp.src.serial, h->simp.src.prune), xyz, faces, grey, bgr, normal,
+                       key, max_vert, max_tri);
+}
+
+int ekf_simplify_get_map(ekf_fusion* h, unsigned* map, unsigned long long max_vert) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const int rc = simplify_result(h, "ekf_simplify_get_map");
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  const size_t nv = (size_t)std::min(h->simp.n_src_vert, max_vert);
+  HIPCHK(hipSetDevice(f->device));
+  if (nv > 0 && map) HIPCHK(hipMemcpy(map, h->simp.map, nv * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_simplify_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->simp.timer.read(kernel_ms, launches, 0, ekf::kSimpKinds);
   return EKF_OK;
 }
 

@@ -230,6 +230,7 @@ struct TsdfSmooth {
   MeshView adj, res;                  // the mesh the adjacency and the result were made from: only what `same` compares is used
   bool adj_valid = false, res_valid = false, has_normals = false;
   int last = 0;                       // the buffer that holds the result
+  unsigned long long runs = 0;        // counts the runs: what ekf_mesh_simplify.hpp derives from a result names it
   KernelTimer<kSmoothKinds> timer;
 
   static bool same(const MeshView& a, const MeshView& b) {
@@ -288,6 +289,7 @@ struct TsdfSmooth {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
     res_valid = false;
+    ++runs;
     if (s.n_tri > 0) {
       const size_t nv = (size_t)s.n_vert;
       const unsigned vblk = fusion_blocks(s.n_vert);

@@ -7,7 +7,8 @@ reconstruction of a recording with its own key frames.  ``TsdfVolume(..., colour
 renders and audits then carry B, G, R beside the grey.  ``TsdfVolume.weld`` mirrors ``ekf_mesh_*`` (§24): the same indexed mesh
 welded on the device, with per-vertex normals on request; ``TsdfVolume.components`` and ``.prune`` find its connected
 components there and drop the small ones (§25); ``TsdfVolume.smooth`` smooths either mesh there with Taubin's scheme and gives
-it normals from its own triangles (§26).
+it normals from its own triangles (§26); ``TsdfVolume.simplify`` clusters the vertices of any of the three on a grid of cells
+(§28).
 """
 from __future__ import annotations
 
@@ -29,6 +30,9 @@ COMPONENT_KERNELS = ("k_comp_init", "k_comp_union", "k_comp_count", "k_comp_larg
                      "k_comp_faces")
 SMOOTH_KERNELS = ("k_smooth_count", "k_smooth_offsets", "k_tsdf_scan", "k_smooth_fill", "k_smooth_lists", "k_smooth_step",
                   "k_smooth_normals")
+SIMPLIFY_KERNELS = ("k_simp_cells", "k_simp_count", "k_simp_offsets", "k_tsdf_scan", "k_simp_fill", "k_simp_lists", "k_simp_flags",
+                    "k_simp_vertices", "k_simp_faces", "k_simp_map")
+SIMPLIFY_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2}
 
 
 @dataclass
@@ -67,6 +71,13 @@ class MeshAdjacency:
     inc: np.ndarray                # (m,) uint32: the number of triangles that contain the vertex
     deg: np.ndarray                # (m,) uint32: the number of distinct vertices that share a triangle with it
     boundary: np.ndarray           # (m,) uint8: 1 iff it has an edge that lies in exactly one triangle
+
+
+@dataclass
+class SimplifyStats:
+    """The triangles the last ``TsdfVolume.simplify`` dropped: kept + degenerate + duplicate = the source's."""
+    degenerate: int                # two of the three vertices fell into one cell
+    duplicate: int                 # a triangle with a smaller index has the same unordered triple of cells
 
 
 @dataclass
@@ -131,7 +142,11 @@ class TsdfVolume(capi.Handle):
         self.shape = (nz, ny, nx)
         self._weld_counts = (0, 0, False)       # vertices, triangles and normals of the last weld
         self.pruned_components = 0              # the number of components the last prune kept
+        self._pruned_vertices = 0               # the vertices of the last prune
         self._smooth_vertices = 0               # the vertices of the last smooth
+        self._smooth_normals = False            # whether it made normals
+        self._simplify_vertices = 0             # the vertices of the source of the last simplify
+        self.simplify_stats = SimplifyStats(0, 0)
 
     def integrate(self, dense_stereo, slot: int, filtered: bool = True):
         """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""
@@ -236,6 +251,7 @@ class TsdfVolume(capi.Handle):
         nv, nt, normals = int(nv.value), int(nt.value), self._weld_counts[2]
         m = self._indexed_mesh(self._lib.ekf_components_get_pruned, nv, nt, normals)
         self.pruned_components = int(nk.value)
+        self._pruned_vertices = nv
         return m
 
     def get_component_profile(self) -> dict:
@@ -261,6 +277,7 @@ class TsdfVolume(capi.Handle):
                                              1 if pin_boundary else 0, 1 if normals else 0, C.byref(nv), C.byref(nt)))
         nv, nt = int(nv.value), int(nt.value)
         self._smooth_vertices = nv
+        self._smooth_normals = bool(normals)
         return self._indexed_mesh(self._lib.ekf_smooth_get, nv, nt, normals)
 
     def adjacency(self) -> MeshAdjacency:
@@ -275,6 +292,40 @@ class TsdfVolume(capi.Handle):
         ms, cnt = np.zeros(7, np.float64), np.zeros(7, np.int64)
         self._check(self._lib.ekf_smooth_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(SMOOTH_KERNELS)}
+
+    def simplify(self, cell: float, source: str = "weld") -> IndexedMesh:
+        """The last ``weld`` (``source="weld"``), the last ``prune`` (``"pruned"``) or the last ``smooth`` (``"smoothed"``)
+        simplified on the device by vertex clustering: the vertices that fall into one cell of side ``cell``
+        (>= the voxel) of a grid from the volume's origin become one vertex, their mean, with the cell's id as its key; a
+        triangle whose vertices share a cell goes, and so does one whose three cells an earlier triangle has; a cell that no
+        kept triangle has gives no vertex.  Normals iff the source has them.  ``simplify_stats`` holds the numbers of
+        degenerate and duplicate triangles.  The source stays as it was.  Scratch: 20 bytes a cell, 12 a source vertex and 20 a
+        source triangle."""
+        if source not in SIMPLIFY_SOURCES:
+            raise ValueError('source is "weld", "pruned" or "smoothed"')
+        nv, nt, nd, nu = (C.c_ulonglong(0) for _ in range(4))
+        self._check(self._lib.ekf_simplify_run(self._h, SIMPLIFY_SOURCES[source], float(cell), C.byref(nv), C.byref(nt), C.byref(nd),
+                                               C.byref(nu)))
+        self.simplify_stats = SimplifyStats(int(nd.value), int(nu.value))
+        normals = self._smooth_normals if source == "smoothed" else self._weld_counts[2]
+        m = self._indexed_mesh(self._lib.ekf_simplify_get, int(nv.value), int(nt.value), normals)
+        # the source's vertices, for simplify_map: a copy of none of them, only their number
+        self._simplify_vertices = {"weld": self._weld_counts[0], "pruned": self._pruned_vertices,
+                                   "smoothed": self._smooth_vertices}[source]
+        return m
+
+    def simplify_map(self) -> np.ndarray:
+        """For every vertex of the source of the last ``simplify``, the number of its vertex in the result, or 0xffffffff where
+        its cell gave none: (m,) uint32."""
+        out = np.zeros(self._simplify_vertices, np.uint32)
+        self._check(self._lib.ekf_simplify_get_map(self._h, _ptr(out), len(out)))
+        return out
+
+    def get_simplify_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the ten kinds of launch of ``simplify`` since the last ``profile()``."""
+        ms, cnt = np.zeros(10, np.float64), np.zeros(10, np.int64)
+        self._check(self._lib.ekf_simplify_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(SIMPLIFY_KERNELS)}
 
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
@@ -440,7 +491,7 @@ def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
 
 def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                         trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                        weld: str = "host", normals: bool = False, components=None, smooth=None,
+                        weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None,
                         **sweep_kwargs) -> RecordingMesh:
     """``dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)``, then every filtered map with its key
     frame's image into one volume (``auto_grid`` where voxel / bounds / trunc are None), extract, weld.  ``trunc`` is the
@@ -457,14 +508,17 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     ``components="largest"`` keeps the largest one alone (§25); either welds on the device, and ``None`` makes today's
     launches.  ``smooth=n`` then smooths the mesh (the pruned one, if ``components`` is given) with ``n`` rounds of
     ``TsdfVolume.smooth`` at its defaults, and ``smooth=dict(...)`` with those keyword arguments (§26); it welds on the device
-    too, with ``normals=True`` the normals are the smoothed mesh's own, and ``None`` makes today's launches."""
+    too, with ``normals=True`` the normals are the smoothed mesh's own, and ``None`` makes today's launches.  ``simplify=f`` (a
+    float >= 1) is applied last, after ``components`` and ``smooth``: ``TsdfVolume.simplify`` of that mesh with cells of
+    ``f`` voxels (§28); it welds on the device too, and ``None`` makes today's launches."""
     _weld_mode(weld, components)
     smooth = _smooth_kwargs(smooth)
+    simplify = _simplify_factor(simplify)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        welded = _welded(vol, min_count, weld, normals, components, smooth)
+        welded = _welded(vol, min_count, weld, normals, components, smooth, simplify)
     finally:
         vol.close()
     out = RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
@@ -493,14 +547,31 @@ def _smooth_kwargs(smooth):
     raise ValueError("smooth is None, an int >= 1 or a dict of keyword arguments of TsdfVolume.smooth")
 
 
-def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False, components=None, smooth=None):
-    """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh.  ``smooth``: what ``_smooth_kwargs`` gave."""
-    if mode == "device" or normals or components is not None or smooth is not None:
+def _simplify_factor(simplify):
+    """The cell size in voxels that ``simplify=`` of ``mesh_from_recording`` stands for, or None."""
+    if simplify is None:
+        return None
+    if isinstance(simplify, (int, float, np.integer, np.floating)) and not isinstance(simplify, bool) and np.isfinite(simplify) \
+            and simplify >= 1:
+        return float(simplify)
+    raise ValueError("simplify is None or a finite number >= 1: the side of a cell in voxels")
+
+
+def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False, components=None, smooth=None,
+            simplify=None):
+    """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh.  ``smooth``: what ``_smooth_kwargs`` gave;
+    ``simplify``: what ``_simplify_factor`` gave."""
+    if mode == "device" or normals or components is not None or smooth is not None or simplify is not None:
         m = vol.weld(min_count, normals and smooth is None)
+        source = "weld"
         if components is not None:
             m = vol.prune(largest=True) if components == "largest" else vol.prune(int(components))
+            source = "pruned"
         if smooth is not None:
-            m = vol.smooth(normals=normals, source="weld" if components is None else "pruned", **smooth)
+            m = vol.smooth(normals=normals, source=source, **smooth)
+            source = "smoothed"
+        if simplify is not None:
+            m = vol.simplify(simplify * vol.voxel, source)
         return m.vertices, m.faces.astype(np.int64), m.grey, m.colour, m.normals
     mesh = vol.extract(min_count)
     return (weld(mesh, True) if vol.colour else weld(mesh) + (None,)) + (None,)
@@ -557,20 +628,21 @@ def grey_image(bgr) -> np.ndarray:
 
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                     trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                    weld: str = "host", normals: bool = False, components=None, smooth=None,
+                    weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None,
                     **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
     frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
-    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…``, ``components=…`` and ``smooth=…``
-    the mesh, as they do through ``mesh_from_recording``."""
+    ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…``, ``components=…``, ``smooth=…``
+    and ``simplify=…`` the mesh, as they do through ``mesh_from_recording``."""
     _weld_mode(weld, components)
     smooth = _smooth_kwargs(smooth)
+    simplify = _simplify_factor(simplify)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components, smooth)
+        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components, smooth, simplify)
         z_near, z_far = audit_range(maps, tr)
         h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)

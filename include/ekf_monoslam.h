@@ -1198,6 +1198,63 @@ int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned int* inc, unsigned int* deg
                              unsigned long long max_vert);
 int ekf_smooth_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- Vertex-clustering simplification of the welded, the pruned or the smoothed mesh -------------------
+ * The surface is marching tetrahedra: up to seven vertices belong to one voxel, far more triangles than its geometry needs.
+ * These additions cluster the vertices of the last ekf_mesh_weld (source 0), the last ekf_components_prune (source 1) or the
+ * last ekf_smooth_run's result (source 2) on a grid of cells of side `cell` (Rossignac and Borrel) on the device, into a mesh
+ * of its own.  The contract, restated by tests/simplify_oracle.py.  Input: a source mesh (X, F, grey, optional bgr, optional
+ * normals) with n_vert vertices and n_tri triangles, the volume's origin, dims and voxel, and `cell` (fp64, finite,
+ * cell >= voxel).  Every fp64 operation is rounded once, with contraction off:
+ *  1. the grid.  G_a = (int) floor(((double)(dims_a - 1) * voxel) / cell) + 1 for a = x, y, z, so G_a <= dims_a: the grid
+ *     never has more cells than the volume has voxels.  For a vertex, q_a = floor((X[v][a] - origin[a]) / cell): a division,
+ *     not a multiplication by a reciprocal; a result that is not finite counts as 0; the result is clamped to [0, G_a - 1]
+ *     (a smoothed vertex may leave the box, so the clamp is part of the contract).  cell(v) = (q_z G_y + q_y) G_x + q_x, x
+ *     fastest, as in the volume;
+ *  2. the triangles.  Triangle t has the cells (cell(F[t][0]), cell(F[t][1]), cell(F[t][2])).  It is degenerate iff two of
+ *     them are equal.  A non-degenerate triangle is a duplicate iff a non-degenerate triangle with a smaller index has the
+ *     same unordered triple of cells.  The kept triangles are the rest, in the source's order and with the source's winding;
+ *  3. the vertices.  A cell is used iff a kept triangle has it.  The output has one vertex per used cell, numbered by
+ *     ascending cell id; that cell id is the output's key, so keys ascend strictly.  A cell that holds vertices but no kept
+ *     triangle gives no vertex.  With M(c) the ascending list of the source vertices of cell c and n = |M(c)|:
+ *       position: per coordinate, s = X[m0], then s = s + X[mi] in the order of M(c), then s / (double) n;
+ *       grey, and each of B, G, R of a colour volume: (2 S + n) / (2 n) in unsigned 64-bit integer arithmetic, S the sum:
+ *         the mean, with halves rounded up;
+ *       normal (iff the source has normals): the members' float normals summed as doubles in the order of M(c), starting
+ *         from the first one's; len = sqrt((a0 a0 + a1 a1) + a2 a2); each a_c / len rounded once to float; 0 0 0 where len
+ *         is 0 or not finite: ekf_mesh_weld's normalisation.  A source without normals gives a result without normals;
+ *  4. the faces: the kept triangles, each index replaced by the output number of its cell;
+ *  5. the vertex map: for every source vertex, the output number of its cell, or 0xffffffff if the cell is unused;
+ *  6. the counts: n_vert_out, n_tri_out, n_degenerate, n_duplicate, with n_tri_out + n_degenerate + n_duplicate = n_tri.
+ * Arrival order costs no bit: the only atomics are integer adds and cursors, and every list (the members of a cell, the
+ * non-degenerate triangles filed under their least cell for the duplicate test) is put in ascending order by the one lane
+ * that owns it before anything reads it, whatever its length; no workgroup waits for another inside a launch.
+ * Opt-in and terminal: nothing above calls them, and no result, launch, profile count or prototype above changes;
+ * ekf_abi_version() stays 6 (additions only).  The sources are only read and stay valid; ekf_smooth_run keeps refusing
+ * source 2.  EKF_ERR_STATE before a weld, after the volume changed since (integrate, reset, set_volume), for source 1
+ * without an ekf_components_prune since the last weld and for source 2 without an ekf_smooth_run on the current mesh.  A new
+ * weld invalidates the result, a new prune one made from the pruned or a smoothed pruned mesh, a new smooth run one made
+ * from source 2.  No kernel is launched for a source without triangles.  Scratch (grow-only): 20 bytes a cell, 12 bytes a
+ * source vertex, 20 bytes a source triangle.  A failed allocation is EKF_ERR_DEVICE and leaves every source as it was.
+ *  - ekf_simplify_run: k_simp_cells, k_simp_count, k_simp_offsets, k_tsdf_scan twice, k_simp_fill, k_simp_lists,
+ *    k_simp_flags, k_tsdf_scan three times, one read-back of the totals, k_simp_map, and for a result that is not empty
+ *    k_simp_vertices and k_simp_faces; reports the four counts.  EKF_ERR_ARG before the device is touched: source not 0, 1
+ *    or 2, cell not finite or below the voxel, a NULL count;
+ *  - ekf_simplify_get: ekf_mesh_get's rules on the result: the first min(n_vert, max_vert) vertices and min(n_tri, max_tri)
+ *    triangles, every pointer may be NULL; EKF_ERR_ARG: bgr on a plain volume, or normal after a run on a source without
+ *    normals; EKF_ERR_STATE also without an ekf_simplify_run on the current mesh;
+ *  - ekf_simplify_get_map: the vertex map of the first min(n_vert of the source, max_vert) source vertices (uint32); map may
+ *    be NULL.  EKF_ERR_STATE as ekf_simplify_get;
+ *  - ekf_simplify_get_profile: HIP-event milliseconds and launch counts of 10 kinds since the last ekf_fusion_profile:
+ *    k_simp_cells ([0]), k_simp_count ([1]), k_simp_offsets ([2]), k_tsdf_scan ([3]), k_simp_fill ([4]), k_simp_lists ([5]),
+ *    k_simp_flags ([6]), k_simp_vertices ([7]), k_simp_faces ([8]), k_simp_map ([9]).  The other profile getters gain
+ *    nothing. */
+int ekf_simplify_run(ekf_fusion* h, int source, double cell, unsigned long long* n_vert, unsigned long long* n_tri,
+                     unsigned long long* n_degenerate, unsigned long long* n_duplicate);
+int ekf_simplify_get(ekf_fusion* h, double* xyz, unsigned int* faces, unsigned char* grey, unsigned char* bgr, float* normal,
+                     unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri);
+int ekf_simplify_get_map(ekf_fusion* h, unsigned int* map, unsigned long long max_vert);
+int ekf_simplify_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -636,7 +636,8 @@ class DenseStereoHip {
 // A colour volume (the constructor's `colour`, section 18, ekf_colour_*) also fills the `colour` arrays: B, G, R.
 // weld() / mesh() mirror ekf_mesh_* (section 24): the indexed mesh welded on the device, with vertex normals on request;
 // components() / prune() / pruned() its connected components and the weld without the small ones (section 25);
-// smooth() / smoothed() / adjacency() either of them smoothed with Taubin's scheme, with normals of its own (section 26).
+// smooth() / smoothed() / adjacency() either of them smoothed with Taubin's scheme, with normals of its own (section 26);
+// simplify() / simplified() / simplifyMap() any of the three with its vertices clustered on a grid of cells (section 28).
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -665,6 +666,10 @@ class TsdfVolumeHip {
     std::vector<unsigned int> inc;             // 1 per vertex: the triangles that contain it
     std::vector<unsigned int> deg;             // 1 per vertex: the distinct vertices that share a triangle with it
     std::vector<unsigned char> boundary;       // 1 per vertex: 1 iff it has an edge that lies in exactly one triangle
+  };
+  struct SimplifyStats {                       // of the last simplify(): section 28
+    unsigned long long degenerate = 0;         // the triangles of which two vertices fell into one cell
+    unsigned long long duplicate = 0;          // those whose unordered triple of cells a triangle with a smaller index has
   };
   struct Volume {
     std::vector<float> sum;
@@ -791,6 +796,30 @@ class TsdfVolumeHip {
   // HIP-event milliseconds and launch counts of k_smooth_count, k_smooth_offsets, the adjacency's k_tsdf_scan, k_smooth_fill,
   // k_smooth_lists, k_smooth_step, k_smooth_normals
   void getSmoothProfile(double kernel_ms[7], long long launches[7]) { check(ekf_smooth_get_profile(f_, kernel_ms, launches)); }
+  // The last weld() (source 0), the last prune() (1) or the last smooth() (2) simplified on the device by vertex clustering
+  // (section 28): the vertices that fall into one cell of side `cell` (>= the voxel) of a grid from the volume's origin become
+  // one vertex, their mean, with the cell's id as its key; a triangle whose vertices share a cell goes, and so does one whose
+  // three cells an earlier triangle has; a cell that no kept triangle has gives no vertex.  Normals iff the source has them.
+  // The source stays as it was.  stats (optional): the numbers of degenerate and duplicate triangles.
+  IndexedMesh simplify(double cell, int source = 0, SimplifyStats* stats = nullptr) {
+    SimplifyStats st;
+    check(ekf_simplify_run(f_, source, cell, &simplify_vertices_, &simplify_triangles_, &st.degenerate, &st.duplicate));
+    simplify_normals_ = source == 2 ? smooth_normals_ : weld_normals_;
+    simplify_source_vertices_ = source == 2 ? smooth_vertices_ : (source == 1 ? pruned_vertices_ : weld_vertices_);
+    if (stats) *stats = st;
+    return simplified();
+  }
+  // the arrays of the last simplify() again
+  IndexedMesh simplified() { return fetch(ekf_simplify_get, simplify_vertices_, simplify_triangles_, simplify_normals_); }
+  // for every vertex of the source of the last simplify(), the number of its vertex in the result, or 0xffffffff
+  std::vector<unsigned int> simplifyMap() {
+    std::vector<unsigned int> map((size_t)simplify_source_vertices_);
+    check(ekf_simplify_get_map(f_, map.data(), simplify_source_vertices_));
+    return map;
+  }
+  // HIP-event milliseconds and launch counts of k_simp_cells, k_simp_count, k_simp_offsets, the simplification's k_tsdf_scan,
+  // k_simp_fill, k_simp_lists, k_simp_flags, k_simp_vertices, k_simp_faces, k_simp_map
+  void getSimplifyProfile(double kernel_ms[10], long long launches[10]) { check(ekf_simplify_get_profile(f_, kernel_ms, launches)); }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
@@ -826,7 +855,7 @@ class TsdfVolumeHip {
     }
     return r;
   }
-  // the arrays of a mesh of n_vert vertices and n_tri triangles on the device, by ekf_mesh_get or one of its two siblings
+  // the arrays of a mesh of n_vert vertices and n_tri triangles on the device, by ekf_mesh_get or one of its three siblings
   using MeshGetter = int (*)(ekf_fusion*, double*, unsigned int*, unsigned char*, unsigned char*, float*, unsigned long long*,
                              unsigned long long, unsigned long long);
   IndexedMesh fetch(MeshGetter getter, unsigned long long n_vert, unsigned long long n_tri, bool normals) {
@@ -844,6 +873,7 @@ class TsdfVolumeHip {
   unsigned long long weld_vertices_ = 0, weld_triangles_ = 0;
   unsigned long long pruned_vertices_ = 0, pruned_triangles_ = 0;
   unsigned long long smooth_vertices_ = 0, smooth_triangles_ = 0;
-  bool weld_normals_ = false, smooth_normals_ = false;
+  unsigned long long simplify_vertices_ = 0, simplify_triangles_ = 0, simplify_source_vertices_ = 0;
+  bool weld_normals_ = false, smooth_normals_ = false, simplify_normals_ = false;
   ekf_fusion* f_ = nullptr;
 };
