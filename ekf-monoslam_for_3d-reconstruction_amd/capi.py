@@ -251,6 +251,13 @@ _PROTOS = {
     "ekf_simplify_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
     "ekf_simplify_get_map": (C.c_int, [_P, _P, C.c_ulonglong]),
     "ekf_simplify_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_texture_begin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "ekf_texture_add_view": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_ulonglong)]),
+    "ekf_texture_add_view_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_double, C.c_double,
+                                            C.POINTER(C.c_ulonglong)]),
+    "ekf_texture_finish": (C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
+    "ekf_texture_get": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_ulonglong]),
+    "ekf_texture_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -40,6 +40,7 @@
 #include "ekf_mesh_components.hpp"
 #include "ekf_mesh_smooth.hpp"
 #include "ekf_mesh_simplify.hpp"
+#include "ekf_mesh_texture.hpp"
 
 namespace ekf {
 
@@ -5871,6 +5872,7 @@ struct ekf_fusion {
   ekf::TsdfComponents comp;           // that weld's components and its pruned copy
   ekf::TsdfSmooth smooth;             // the smoothed copy of either of them
   ekf::TsdfSimplify simp;             // the simplified copy of any of the three
+  ekf::TsdfTexture tex;               // the texture atlas of any of the four
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6143,6 +6145,7 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   h->comp.timer.enable(enable != 0);    // the eight of the components
   h->smooth.timer.enable(enable != 0);  // the seven of the smoothing
   h->simp.timer.enable(enable != 0);    // the ten of the simplification
+  h->tex.timer.enable(enable != 0);     // the four of the texture
   return EKF_OK;
 }
 
@@ -6581,6 +6584,205 @@ int ekf_simplify_get_map(ekf_fusion* h, unsigned* map, unsigned long long max_ve
 int ekf_simplify_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->simp.timer.read(kernel_ms, launches, 0, ekf::kSimpKinds);
+  return EKF_OK;
+}
+
+// ---- a per-triangle texture atlas of the welded, the pruned, the smoothed or the simplified mesh ------------
+// The mesh a texture is about, if the handle holds it, and the number of the smooth run (2) or the simplify run (3) that made
+// it: EKF_OK, or EKF_ERR_STATE with the message set.
+static int texture_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s, unsigned long long* run) {
+  if (source != 3) return simplify_source(h, who, source, s, run);
+  const int rc = simplify_result(h, who);
+  if (rc != EKF_OK) {
+    h->impl->err = std::string(who) + ": source 3 needs an ekf_simplify_run on the current mesh";
+    return rc;
+  }
+  *s = ekf::MeshView::of(h->simp.out, 3, h->simp.src.serial, h->simp.src.prune);
+  *run = h->simp.runs;
+  return EKF_OK;
+}
+
+// Whether the texture begun last is still that of the handle's meshes: its source says which.
+static int texture_current(ekf_fusion* h, const char* who) {
+  auto* f = h->impl;
+  const ekf::TsdfTexture& m = h->tex;
+  ekf::MeshView s;
+  unsigned long long run = 0;
+  if (!m.begun || texture_source(h, who, m.from, &s, &run) != EKF_OK || !ekf::TsdfSmooth::same(m.src, s) ||
+      (m.from >= 2 && m.run_id != run)) {
+    f->err = std::string(who) + ": no ekf_texture_begin on the current mesh";
+    return EKF_ERR_STATE;
+  }
+  return EKF_OK;
+}
+
+int ekf_texture_begin(ekf_fusion* h, int source, int patch, int channels, int* atlas_side) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (source < 0 || source > 3 || patch < ekf::kTexMinPatch || patch > ekf::kTexMaxPatch || (channels != 1 && channels != 3) ||
+      !atlas_side) {
+    f->err = "ekf_texture_begin: source 0, 1, 2 or 3, patch 2..32, channels 1 or 3, atlas_side not NULL";
+    return EKF_ERR_ARG;
+  }
+  ekf::MeshView s;
+  unsigned long long run = 0;
+  const int rc = texture_source(h, "ekf_texture_begin", source, &s, &run);
+  if (rc != EKF_OK) return rc;
+  if (s.n_tri == 0) {
+    f->err = "ekf_texture_begin: the source mesh has no triangle";
+    return EKF_ERR_STATE;
+  }
+  int B;
+  long long Q, A;
+  ekf::tex_layout(s.n_tri, patch, B, Q, A);
+  if (A > ekf::kTexMaxSide) {
+    f->err = "ekf_texture_begin: the atlas would be " + std::to_string(A) + " texels a side, more than 16384 (a smaller patch, or ekf_simplify_run first)";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->tex.begin(s, source, run, patch, channels, f->colour && channels == 3));
+  *atlas_side = (int)A;
+  return EKF_OK;
+}
+
+// What both ways of adding a view check after their own arguments: EKF_OK with *zbuf the z-buffer (NULL: occlusion off).
+static int texture_view_ok(ekf_fusion* h, const char* who, int width, int height, int occlusion, const float** zbuf) {
+  auto* f = h->impl;
+  const int rc = texture_current(h, who);
+  if (rc != EKF_OK) return rc;
+  if (h->tex.finished) {
+    f->err = std::string(who) + ": the texture is finished (ekf_texture_begin starts the next)";
+    return EKF_ERR_STATE;
+  }
+  *zbuf = nullptr;
+  if (occlusion) {
+    if (!h->rc.current(*f) || h->rc.W != width || h->rc.H != height) {
+      f->err = std::string(who) + ": occlusion needs an ekf_raycast_render of the view's size since the volume last changed";
+      return EKF_ERR_STATE;
+    }
+    *zbuf = h->rc.depth;
+  }
+  return EKF_OK;
+}
+
+int ekf_texture_add_view(ekf_fusion* h, ekf_dense* dense, int slot, int occlusion, double tol, double min_area2,
+                         unsigned long long* n_won) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!dense || dense->impl->device != f->device) {
+    f->err = "ekf_texture_add_view: a dense handle on the volume's device";
+    return EKF_ERR_ARG;
+  }
+  auto* d = dense->impl;
+  if (slot < 0 || slot >= d->max_views || (occlusion != 0 && occlusion != 1) || !std::isfinite(tol) || tol < 0.0 ||
+      !std::isfinite(min_area2) || min_area2 < 0.0 || !n_won) {
+    f->err = "ekf_texture_add_view: slot in 0..max_views-1, occlusion 0 or 1, tol and min_area2 finite and >= 0, n_won not NULL";
+    return EKF_ERR_ARG;
+  }
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set) {
+    f->err = "ekf_texture_add_view: the slot is not set";
+    return EKF_ERR_STATE;
+  }
+  const float* zbuf = nullptr;
+  const int rc = texture_view_ok(h, "ekf_texture_add_view", d->W, d->H, occlusion, &zbuf);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  const unsigned char* bgr = h->tex.C == 3 ? d->colour_of(slot) : nullptr;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->tex.add_view(bgr ? bgr : (const unsigned char*)v.img, bgr ? 3 : 1, d->W, d->H, v.K, v.R, v.t, zbuf, tol, min_area2, n_won));
+  return EKF_OK;
+}
+
+int ekf_texture_add_view_host(ekf_fusion* h, const unsigned char* img, int pitch, int channels, int width, int height, const double* K,
+                              const double* pose7, int occlusion, double tol, double min_area2, unsigned long long* n_won) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  double t[3], R[9], q[4];
+  if (!img || (channels != 1 && channels != 3) || width < 1 || height < 1 || width > ekf::kFusionMaxMapDim ||
+      height > ekf::kFusionMaxMapDim || pitch < channels * width || !K || !pinhole_ok(K) || !pose7 || !ekf::dense_pose(pose7, t, R, q) ||
+      (occlusion != 0 && occlusion != 1) || !std::isfinite(tol) || tol < 0.0 || !std::isfinite(min_area2) || min_area2 < 0.0 || !n_won) {
+    f->err = "ekf_texture_add_view_host: img, K, pose7 and n_won not NULL; channels 1 or 3; 1 <= width, height <= 8192; pitch >= "
+             "channels width; K finite with fx, fy > 0; pose7 finite with q != 0; occlusion 0 or 1; tol and min_area2 finite and >= 0";
+    return EKF_ERR_ARG;
+  }
+  const float* zbuf = nullptr;
+  const int rc = texture_view_ok(h, "ekf_texture_add_view_host", width, height, occlusion, &zbuf);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  ekf::TsdfTexture& m = h->tex;
+  const size_t n = (size_t)width * height;
+  const int vch = (channels == 3 && m.C == 3) ? 3 : 1;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(m.d_img.reserve(n * vch));
+  if (channels == 3 && vch == 1) {                           // a colour view for a 1-channel atlas: its bgr2gray image
+    std::vector<unsigned char> grey(n);
+    for (int y = 0; y < height; ++y) {
+      const unsigned char* row = img + (size_t)y * (size_t)pitch;
+      for (int x = 0; x < width; ++x)
+        grey[(size_t)y * width + x] = (unsigned char)((row[3 * x] * 1868u + row[3 * x + 1] * 9617u + row[3 * x + 2] * 4899u + 8192u) >> 14);
+    }
+    HIPCHK(hipMemcpy(m.d_img, grey.data(), n, hipMemcpyHostToDevice));
+  } else {
+    const size_t row = (size_t)vch * width;
+    HIPCHK(hipMemcpy2D(m.d_img, row, img, (size_t)pitch, row, (size_t)height, hipMemcpyHostToDevice));
+  }
+  HIPCHK(m.add_view(m.d_img, vch, width, height, K, R, t, zbuf, tol, min_area2, n_won));
+  return EKF_OK;
+}
+
+int ekf_texture_finish(ekf_fusion* h, unsigned long long* n_textured) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!n_textured) {
+    f->err = "ekf_texture_finish: n_textured must not be NULL";
+    return EKF_ERR_ARG;
+  }
+  const int rc = texture_current(h, "ekf_texture_finish");
+  if (rc != EKF_OK) return rc;
+  if (h->tex.finished) {
+    f->err = "ekf_texture_finish: the texture is finished (ekf_texture_begin starts the next)";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->tex.finish());
+  *n_textured = h->tex.n_textured;
+  return EKF_OK;
+}
+
+int ekf_texture_get(ekf_fusion* h, unsigned char* atlas, int pitch, double* uv, int* view, double* score, unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfTexture& m = h->tex;
+  const int rc = texture_current(h, "ekf_texture_get");
+  if (rc != EKF_OK) return rc;
+  const size_t row = (size_t)m.A * (size_t)m.C;
+  if (atlas && (pitch < 0 || (size_t)pitch < row)) {
+    f->err = "ekf_texture_get: pitch >= atlas_side channels";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t nt = (size_t)std::min(m.src.n_tri, max_tri);
+  HIPCHK(hipSetDevice(f->device));
+  if (atlas && (size_t)pitch == row) {                       // tight rows: one copy
+    HIPCHK(hipMemcpy(atlas, m.atlas, row * (size_t)m.A, hipMemcpyDeviceToHost));
+  } else if (atlas) {
+    HIPCHK(hipMemcpy2D(atlas, (size_t)pitch, m.atlas, row, row, (size_t)m.A, hipMemcpyDeviceToHost));
+  }
+  if (uv)
+    for (size_t t = 0; t < nt; ++t) ekf::tex_uv(t, m.P, m.B, m.Q, m.A, uv + 6 * t);
+  if (nt > 0) {
+    if (view) HIPCHK(hipMemcpy(view, m.best_view, nt * sizeof(int), hipMemcpyDeviceToHost));
+    if (score) HIPCHK(hipMemcpy(score, m.best_score, nt * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return EKF_OK;
+}
+
+int ekf_texture_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->tex.timer.read(kernel_ms, launches, 0, ekf::kTexKinds);
   return EKF_OK;
 }
 

@@ -397,6 +397,7 @@ struct TsdfSimplify {
   int from = 0;                                  // the run's source: 0 the weld, 1 the pruned, 2 the smoothed mesh
   unsigned long long smooth_run = 0;             // TsdfSmooth::runs at a run from source 2
   unsigned long long n_src_vert = 0, n_degenerate = 0, n_duplicate = 0;
+  unsigned long long runs = 0;                   // counts the runs: what ekf_mesh_texture.hpp derives from a result names it
   bool valid = false;
   KernelTimer<kSimpKinds> timer;
 
@@ -412,6 +413,7 @@ struct TsdfSimplify {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
     valid = false;
+    ++runs;
     unsigned long long totals[3] = {0, 0, 0};
     if (s.n_tri > 0) {
       if (s.n_tri > 0xffffffffull) return hipErrorInvalidValue;              // a triangle's number is a word of `tl`

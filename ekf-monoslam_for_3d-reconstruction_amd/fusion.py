@@ -8,11 +8,15 @@ renders and audits then carry B, G, R beside the grey.  ``TsdfVolume.weld`` mirr
 welded on the device, with per-vertex normals on request; ``TsdfVolume.components`` and ``.prune`` find its connected
 components there and drop the small ones (§25); ``TsdfVolume.smooth`` smooths either mesh there with Taubin's scheme and gives
 it normals from its own triangles (§26); ``TsdfVolume.simplify`` clusters the vertices of any of the three on a grid of cells
-(§28).
+(§28); ``TsdfVolume.texture_begin`` / ``texture_add_view`` / ``texture_finish`` fill a per-triangle texture atlas of any of the
+four from views (§29), and ``write_mesh_obj`` stores a mesh with its atlas.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
+import struct
+import zlib
 from dataclasses import dataclass
 from typing import Optional
 
@@ -33,6 +37,8 @@ SMOOTH_KERNELS = ("k_smooth_count", "k_smooth_offsets", "k_tsdf_scan", "k_smooth
 SIMPLIFY_KERNELS = ("k_simp_cells", "k_simp_count", "k_simp_offsets", "k_tsdf_scan", "k_simp_fill", "k_simp_lists", "k_simp_flags",
                     "k_simp_vertices", "k_simp_faces", "k_simp_map")
 SIMPLIFY_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2}
+TEXTURE_KERNELS = ("k_tex_project", "k_tex_select", "k_tex_fill", "k_tex_fallback")
+TEXTURE_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2, "simplified": 3}
 
 
 @dataclass
@@ -81,6 +87,16 @@ class SimplifyStats:
 
 
 @dataclass
+class TextureAtlas:
+    """What ``TsdfVolume.texture_finish`` returns: triangle t of the source owns one half of block t >> 1."""
+    atlas: np.ndarray              # (A, A) uint8, or (A, A, 3) in B, G, R order; row 0 first
+    uv: np.ndarray                 # (n, 3, 2) float64: u, v of the three corners, v measured from row 0
+    view: np.ndarray               # (n,) int32: the number of the view that textured the triangle, -1: none (vertex colours)
+    score: np.ndarray              # (n,) float64: twice the triangle's area in that view's pixels, 0: none
+    n_textured: int                # the number of triangles with a view
+
+
+@dataclass
 class Render:
     """What ``TsdfVolume.raycast`` returns; a pixel without a hit has depth 0, normal 0 and grey 0."""
     depth: np.ndarray              # (H, W) float32: camera-z depth of the surface
@@ -125,6 +141,8 @@ class RecordingMesh:
     # (m, 3) float32 vertex normals, set by ``normals=True`` only.  An attribute beside the fields, not a field: ``colour`` stays
     # the last positional argument of the constructor
     normals = None
+    # the TextureAtlas of ``texture=``, an attribute like ``normals``
+    texture = None
 
 
 class TsdfVolume(capi.Handle):
@@ -146,7 +164,10 @@ class TsdfVolume(capi.Handle):
         self._smooth_vertices = 0               # the vertices of the last smooth
         self._smooth_normals = False            # whether it made normals
         self._simplify_vertices = 0             # the vertices of the source of the last simplify
+        self._pruned_triangles = self._smooth_triangles = self._simplify_triangles = 0      # the triangles of the last of each
+        self._simplify_cell = 0.0               # the cell of the last simplify
         self.simplify_stats = SimplifyStats(0, 0)
+        self._texture = None                    # (triangles, atlas side, channels, source) of the last texture_begin
 
     def integrate(self, dense_stereo, slot: int, filtered: bool = True):
         """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""
@@ -252,6 +273,7 @@ class TsdfVolume(capi.Handle):
         m = self._indexed_mesh(self._lib.ekf_components_get_pruned, nv, nt, normals)
         self.pruned_components = int(nk.value)
         self._pruned_vertices = nv
+        self._pruned_triangles = nt
         return m
 
     def get_component_profile(self) -> dict:
@@ -277,6 +299,7 @@ class TsdfVolume(capi.Handle):
                                              1 if pin_boundary else 0, 1 if normals else 0, C.byref(nv), C.byref(nt)))
         nv, nt = int(nv.value), int(nt.value)
         self._smooth_vertices = nv
+        self._smooth_triangles = nt
         self._smooth_normals = bool(normals)
         return self._indexed_mesh(self._lib.ekf_smooth_get, nv, nt, normals)
 
@@ -307,6 +330,7 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_simplify_run(self._h, SIMPLIFY_SOURCES[source], float(cell), C.byref(nv), C.byref(nt), C.byref(nd),
                                                C.byref(nu)))
         self.simplify_stats = SimplifyStats(int(nd.value), int(nu.value))
+        self._simplify_triangles, self._simplify_cell = int(nt.value), float(cell)
         normals = self._smooth_normals if source == "smoothed" else self._weld_counts[2]
         m = self._indexed_mesh(self._lib.ekf_simplify_get, int(nv.value), int(nt.value), normals)
         # the source's vertices, for simplify_map: a copy of none of them, only their number
@@ -326,6 +350,84 @@ class TsdfVolume(capi.Handle):
         ms, cnt = np.zeros(10, np.float64), np.zeros(10, np.int64)
         self._check(self._lib.ekf_simplify_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(SIMPLIFY_KERNELS)}
+
+    def texture_begin(self, source: str = "weld", patch: int = 8, channels: Optional[int] = None) -> int:
+        """Starts a texture atlas of the last ``weld``, ``prune`` (``"pruned"``), ``smooth`` (``"smoothed"``) or
+        ``simplify`` (``"simplified"``): every pair of triangles gets a block of ``patch`` + 2 texels a side.  ``channels``: 1 or
+        3, by default 3 for a colour volume.  Returns the atlas's side.  Views are then added one at a time; the source is only
+        read.  Device memory: the atlas, 13 bytes a triangle and 17 bytes a source vertex."""
+        if source not in TEXTURE_SOURCES:
+            raise ValueError('source is "weld", "pruned", "smoothed" or "simplified"')
+        channels = (3 if self.colour else 1) if channels is None else int(channels)
+        side = C.c_int(0)
+        self._check(self._lib.ekf_texture_begin(self._h, TEXTURE_SOURCES[source], int(patch), channels, C.byref(side)))
+        self._texture = (int(side.value), channels, source)
+        return int(side.value)
+
+    def _texture_tol(self, tol):
+        """The default of ``tol``: the voxel, and for a simplified source the cell of that run."""
+        if tol is not None:
+            return float(tol)
+        return self._simplify_cell if self._texture and self._texture[2] == "simplified" else self.voxel
+
+    def texture_add_view(self, dense_stereo, slot: int, occlusion=None, tol: Optional[float] = None, min_area2: float = 0.0) -> int:
+        """Adds the image, K and pose of a set slot of a ``DenseStereo`` as the next view, straight from its device buffers, and
+        returns the number of triangles it won: those it sees whole, from the free-space side and larger (in pixels) than every
+        earlier view did.  ``occlusion``: None, or ``(z_near, z_far[, step, min_count])``: the volume is ray-cast at the slot's
+        pose first, and a vertex counts as seen only if it lies no more than ``tol`` (default: the voxel; for a simplified
+        source its cell) behind that render.  ``min_area2``: twice the least area in pixels a triangle must have."""
+        if occlusion is not None:
+            self.raycast_view(dense_stereo, slot, *occlusion)
+        n = C.c_ulonglong(0)
+        self._check(self._lib.ekf_texture_add_view(self._h, dense_stereo._h, int(slot), 0 if occlusion is None else 1,
+                                                   self._texture_tol(tol), float(min_area2), C.byref(n)))
+        return int(n.value)
+
+    def texture_add_view_host(self, image, K, pose7, occlusion=None, tol: Optional[float] = None, min_area2: float = 0.0) -> int:
+        """``texture_add_view`` for an image from the host: (H, W) uint8, or (H, W, 3) in B, G, R order."""
+        img = np.ascontiguousarray(image, np.uint8)
+        if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3):
+            raise ValueError("the image is (H, W) or (H, W, 3)")
+        K = np.ascontiguousarray(K, np.float64).reshape(4)
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        h, w = img.shape[:2]
+        if occlusion is not None:
+            self.raycast((w, h), K, pose, *occlusion)
+        n = C.c_ulonglong(0)
+        self._check(self._lib.ekf_texture_add_view_host(self._h, _ptr(img), img.strides[0], 3 if img.ndim == 3 else 1, w, h, _ptr(K),
+                                                        _ptr(pose), 0 if occlusion is None else 1, self._texture_tol(tol),
+                                                        float(min_area2), C.byref(n)))
+        return int(n.value)
+
+    def _texture_get(self, n_textured: int) -> "TextureAtlas":
+        side, channels, source = self._texture
+        nt = {"weld": self._weld_counts[1], "pruned": self._pruned_triangles, "smoothed": self._smooth_triangles,
+              "simplified": self._simplify_triangles}[source]
+        out = TextureAtlas(np.zeros((side, side) if channels == 1 else (side, side, 3), np.uint8), np.zeros((nt, 3, 2), np.float64),
+                           np.zeros(nt, np.int32), np.zeros(nt, np.float64), n_textured)
+        self._check(self._lib.ekf_texture_get(self._h, _ptr(out.atlas), side * channels, _ptr(out.uv), _ptr(out.view), _ptr(out.score), nt))
+        return out
+
+    def texture_finish(self) -> "TextureAtlas":
+        """Fills the triangles that no view won with the blend of their vertices' grey (or B, G, R) and returns the atlas."""
+        n = C.c_ulonglong(0)
+        self._check(self._lib.ekf_texture_finish(self._h, C.byref(n)))
+        return self._texture_get(int(n.value))
+
+    def texture_peek(self) -> "TextureAtlas":
+        """The atlas as it is now, any time after ``texture_begin`` (``n_textured`` counts the triangles with a view)."""
+        if self._texture is None:                            # the library says so: EKF_ERR_STATE with its message
+            self._check(self._lib.ekf_texture_get(self._h, None, 0, None, None, None, 0))
+            raise ValueError("texture_peek: no texture_begin through this object")
+        out = self._texture_get(0)
+        out.n_textured = int((out.view >= 0).sum())
+        return out
+
+    def get_texture_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the four kinds of launch of the texture since the last ``profile()``."""
+        ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
+        self._check(self._lib.ekf_texture_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(TEXTURE_KERNELS)}
 
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
@@ -446,6 +548,93 @@ def read_mesh_ply(path: str, colour: bool = False, normals: bool = False):
     return out
 
 
+def _png_chunk(kind: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def write_png(path: str, image) -> None:
+    """An 8-bit PNG of an (H, W) grey or an (H, W, 3) B, G, R image, with the standard library's ``zlib``: filter 0 on every row."""
+    img = np.ascontiguousarray(image, np.uint8)
+    if img.ndim == 3:
+        img = np.ascontiguousarray(img[:, :, ::-1])
+    h, w = img.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, -1)], axis=1)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0 if img.ndim == 2 else 2, 0, 0, 0)) +
+                 _png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+
+
+def read_png(path: str) -> np.ndarray:
+    """An 8-bit grey or RGB PNG without interlace as (H, W) or (H, W, 3) uint8 in B, G, R order: what ``write_png`` wrote, and
+    any of the five row filters."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("%s is no PNG" % path)
+    at, idat, head = 8, b"", None
+    while at < len(data):
+        n, kind = struct.unpack(">I", data[at:at + 4])[0], data[at + 4:at + 8]
+        body = data[at + 8:at + 8 + n]
+        if struct.unpack(">I", data[at + 8 + n:at + 12 + n])[0] != (zlib.crc32(kind + body) & 0xFFFFFFFF):
+            raise ValueError("%s: a chunk's CRC is wrong" % path)
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat += body
+        at += 12 + n
+    if head is None or head[2] != 8 or head[3] not in (0, 2) or head[6] != 0:
+        raise ValueError("%s: only 8-bit grey or RGB without interlace" % path)
+    w, h, c = head[0], head[1], 1 if head[3] == 0 else 3
+    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + w * c)
+    out = np.zeros((h, w * c), np.uint8)
+    for y in range(h):
+        f, line = int(raw[y, 0]), raw[y, 1:].astype(np.int64)
+        up = out[y - 1].astype(np.int64) if y else np.zeros(w * c, np.int64)
+        if f == 0:
+            out[y] = line
+        elif f == 2:
+            out[y] = (line + up) & 255
+        else:                                                # 1, 3, 4 need the pixel to the left: byte by byte
+            cur = np.zeros(w * c, np.int64)
+            for i in range(w * c):
+                a = cur[i - c] if i >= c else 0
+                b, cc = up[i], (up[i - c] if i >= c else 0)
+                if f == 1:
+                    pred = a
+                elif f == 3:
+                    pred = (a + b) >> 1
+                elif f == 4:
+                    pa, pb, pc = abs(b - cc), abs(a - cc), abs(a + b - 2 * cc)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else cc)
+                else:
+                    raise ValueError("%s: row filter %d" % (path, f))
+                cur[i] = (line[i] + pred) & 255
+            out[y] = cur
+    return out.reshape(h, w) if c == 1 else np.ascontiguousarray(out.reshape(h, w, 3)[:, :, ::-1])
+
+
+def write_mesh_obj(path: str, vertices, faces, atlas: TextureAtlas) -> None:
+    """Wavefront OBJ of a mesh with its ``TextureAtlas``: ``path`` itself (``v`` with ``%.17g``, three ``vt`` a triangle that
+    carry u and 1 - v, since OBJ measures v from the bottom row, ``f`` lines of ``v/vt``), beside it a ``.mtl`` that names the
+    atlas as ``map_Kd`` and the atlas as an 8-bit ``.png``."""
+    base = os.path.splitext(path)[0]
+    name = os.path.basename(base)
+    faces = np.asarray(faces).reshape(-1, 3)
+    if len(atlas.uv) != len(faces):
+        raise ValueError("the atlas is of %d triangles, the mesh has %d" % (len(atlas.uv), len(faces)))
+    write_png(base + ".png", atlas.atlas)
+    with open(base + ".mtl", "w") as fh:
+        fh.write("newmtl %s\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd %s.png\n" % (name, name))
+    with open(path, "w") as fh:
+        fh.write("mtllib %s.mtl\nusemtl %s\n" % (name, name))
+        for x, y, z in np.asarray(vertices, np.float64).reshape(-1, 3):
+            fh.write("v %.17g %.17g %.17g\n" % (x, y, z))
+        for u, v in np.asarray(atlas.uv, np.float64).reshape(-1, 2):
+            fh.write("vt %.17g %.17g\n" % (u, 1.0 - v))
+        for t, (a, b, c) in enumerate(faces):
+            fh.write("f %d/%d %d/%d %d/%d\n" % (a + 1, 3 * t + 1, b + 1, 3 * t + 2, c + 1, 3 * t + 3))
+
+
 def auto_grid(points, voxel: Optional[float] = None, bounds=None, trunc: Optional[float] = None):
     """(origin, dims, voxel, trunc) of ``mesh_from_recording``.  The box is ``bounds`` = (lo, hi), or the
     box of all finite ``points`` padded by trunc; voxel = its longest side before the padding / 128, doubled until the
@@ -491,7 +680,7 @@ def _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs):
 
 def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                         trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                        weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None,
+                        weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None, texture=None,
                         **sweep_kwargs) -> RecordingMesh:
     """``dense.depth_maps_from_recording(directory, nodes_out, **sweep_kwargs)``, then every filtered map with its key
     frame's image into one volume (``auto_grid`` where voxel / bounds / trunc are None), extract, weld.  ``trunc`` is the
@@ -510,19 +699,26 @@ def mesh_from_recording(directory: str, nodes_out: Optional[str] = None, voxel: 
     ``TsdfVolume.smooth`` at its defaults, and ``smooth=dict(...)`` with those keyword arguments (§26); it welds on the device
     too, with ``normals=True`` the normals are the smoothed mesh's own, and ``None`` makes today's launches.  ``simplify=f`` (a
     float >= 1) is applied last, after ``components`` and ``smooth``: ``TsdfVolume.simplify`` of that mesh with cells of
-    ``f`` voxels (§28); it welds on the device too, and ``None`` makes today's launches."""
+    ``f`` voxels (§28); it welds on the device too, and ``None`` makes today's launches.  ``texture=P`` (an int, the patch size)
+    or ``texture=dict(patch=, channels=, tol=, min_area2=, occlusion=)`` then textures that mesh (§29): every key frame's image
+    is added in recording order with ``K`` and the pose of its map, behind a ray cast of the volume over ``audit_range`` unless
+    ``occlusion=False``, and the ``TextureAtlas`` lands in ``RecordingMesh.texture``; it welds on the device too, and ``None``
+    makes today's launches."""
     _weld_mode(weld, components)
     smooth = _smooth_kwargs(smooth)
     simplify = _simplify_factor(simplify)
+    texture = _texture_kwargs(texture)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        welded = _welded(vol, min_count, weld, normals, components, smooth, simplify)
+        welded = _welded(vol, min_count, weld, normals, components, smooth, simplify, texture is not None)
+        atlas = _textured(vol, texture, _last_source(components, smooth, simplify), maps, images, K, tr, min_count)
     finally:
         vol.close()
     out = RecordingMesh(*welded[:3], origin, dims, vx, tr, maps, welded[3])
     out.normals = welded[4]
+    out.texture = atlas
     return out
 
 
@@ -557,11 +753,43 @@ def _simplify_factor(simplify):
     raise ValueError("simplify is None or a finite number >= 1: the side of a cell in voxels")
 
 
+def _texture_kwargs(texture):
+    """What ``texture=`` of ``mesh_from_recording`` stands for: a dict of patch, channels, tol, min_area2 and occlusion, or None."""
+    if texture is None:
+        return None
+    out = dict(patch=8, channels=None, tol=None, min_area2=0.0, occlusion=True)
+    if isinstance(texture, dict):
+        if not set(texture) <= set(out):
+            raise ValueError("texture takes patch, channels, tol, min_area2 and occlusion")
+        out.update(texture)
+        return out
+    if isinstance(texture, (int, np.integer)) and not isinstance(texture, bool) and 2 <= texture <= 32:
+        out["patch"] = int(texture)
+        return out
+    raise ValueError("texture is None, a patch size 2..32 or a dict of patch, channels, tol, min_area2 and occlusion")
+
+
+def _last_source(components, smooth, simplify) -> str:
+    """The name of the mesh ``_welded`` returned on the device path."""
+    return "simplified" if simplify is not None else "smoothed" if smooth is not None else "pruned" if components is not None else "weld"
+
+
+def _textured(vol: TsdfVolume, texture, source: str, maps, images, K, trunc: float, min_count: int):
+    """The ``TextureAtlas`` of the mesh ``_welded`` has just made from every key frame in recording order, or None."""
+    if texture is None:
+        return None
+    vol.texture_begin(source, texture["patch"], texture["channels"])
+    occlusion = audit_range(maps, trunc) + (None, min_count) if texture["occlusion"] else None
+    for m, img in zip(maps, images):
+        vol.texture_add_view_host(img, K, m.pose, occlusion, texture["tol"], texture["min_area2"])
+    return vol.texture_finish()
+
+
 def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool = False, components=None, smooth=None,
-            simplify=None):
+            simplify=None, device: bool = False):
     """(vertices, faces, grey, colour or None, normals or None) of the volume's mesh.  ``smooth``: what ``_smooth_kwargs`` gave;
-    ``simplify``: what ``_simplify_factor`` gave."""
-    if mode == "device" or normals or components is not None or smooth is not None or simplify is not None:
+    ``simplify``: what ``_simplify_factor`` gave; ``device``: weld on the device whatever ``mode`` says."""
+    if mode == "device" or device or normals or components is not None or smooth is not None or simplify is not None:
         m = vol.weld(min_count, normals and smooth is None)
         source = "weld"
         if components is not None:
@@ -628,21 +856,24 @@ def grey_image(bgr) -> np.ndarray:
 
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                     trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
-                    weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None,
+                    weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None, texture=None,
                     **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
     frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
     ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…``, ``components=…``, ``smooth=…``
-    and ``simplify=…`` the mesh, as they do through ``mesh_from_recording``."""
+    ``simplify=…`` and ``texture=…`` the mesh, as they do through ``mesh_from_recording``."""
     _weld_mode(weld, components)
     smooth = _smooth_kwargs(smooth)
     simplify = _simplify_factor(simplify)
+    texture = _texture_kwargs(texture)
     if sweep_trunc is not None:
         sweep_kwargs["trunc"] = sweep_trunc
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
-        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components, smooth, simplify)
+        vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components, smooth, simplify,
+                                                                texture is not None)
+        atlas = _textured(vol, texture, _last_source(components, smooth, simplify), maps, images, K, tr, min_count)
         z_near, z_far = audit_range(maps, tr)
         h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)
@@ -651,4 +882,5 @@ def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Opti
         vol.close()
     mesh = RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps, colour)
     mesh.normals = vertex_normals
+    mesh.texture = atlas
     return RecordingAudit(mesh, frames, z_near, z_far, vx / 2.0)

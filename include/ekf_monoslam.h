@@ -1255,6 +1255,81 @@ int ekf_simplify_get(ekf_fusion* h, double* xyz, unsigned int* faces, unsigned c
 int ekf_simplify_get_map(ekf_fusion* h, unsigned int* map, unsigned long long max_vert);
 int ekf_simplify_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- A per-triangle texture atlas of the welded, the pruned, the smoothed or the simplified mesh ----------
+ * A simplified mesh carries one grey or B, G, R value per vertex, the mean of up to hundreds of source vertices; the key
+ * frames that made it hold far more.  These additions texture the last ekf_mesh_weld (source 0), the last
+ * ekf_components_prune (1), the last ekf_smooth_run's result (2) or the last ekf_simplify_run's result (3) on the device from
+ * views that are fed one at a time, so that there is no limit on their number and only the current view's image is resident.
+ * The contract, restated by tests/texture_oracle.py.  Input: a source mesh (X fp64, F uint32, vertex grey and optional B, G,
+ * R) with n_tri > 0 triangles, a patch size P in 2..32 and `channels`, 1 or 3.  Every fp64 operation is rounded once, in the
+ * written order, with contraction off:
+ *  1. the layout.  Triangles are paired into square blocks of side B = P + 2 texels: block q = t >> 1 holds triangle 2 q
+ *     (the lower one) and 2 q + 1 (the upper one).  n_sq = (n_tri + 1) >> 1, Q is the least integer with Q Q >= n_sq, the
+ *     atlas is A x A texels with A = Q B, row 0 first, and block q sits at (bx, by) = (q % Q, q / Q).  A texel with
+ *     block-local coordinates (a, b) belongs to the lower triangle iff a + b <= P, otherwise to the upper one.  Corner texel
+ *     centres: lower c0 = (0, 0), c1 = (P - 1, 0), c2 = (0, P - 1); upper c0 = (P + 1, P + 1), c1 = (2, P + 1),
+ *     c2 = (P + 1, 2), so a bilinear look-up inside a triangle's UV triangle touches texels of that triangle only; the
+ *     diagonals a + b = P and P + 1 are gutters, filled by extrapolation.  Barycentrics of a texel: lower
+ *     l1 = (double) a / (double)(P - 1), l2 = (double) b / (double)(P - 1); upper l1 = (double)(P + 1 - a) / (double)(P - 1),
+ *     l2 = (double)(P + 1 - b) / (double)(P - 1); l0 = (1.0 - l1) - l2.  UV of corner i of triangle t:
+ *     ((double)(bx B + c_i.x) + 0.5) / (double) A, likewise for y, measured from row 0: made on the host, without a launch;
+ *  2. a vertex in a view (an image of W x H, K = fx fy cx cy, a pose, an optional z-buffer): p = R^T (X - t),
+ *     sx = fx (p0 / p2) + cx, sy = fy (p1 / p2) + cy in ekf_fusion_integrate's operation order.  It is visible iff p2 > 0,
+ *     0 <= sx <= W - 1, 0 <= sy <= H - 1 (a NaN fails) and, with occlusion on, D = (double) zbuf[floor(sy + 0.5) W +
+ *     floor(sx + 0.5)] has D > 0 and p2 <= D + tol.  D == 0 (the ray cast found no surface) fails on purpose;
+ *  3. a triangle in a view is a candidate iff its three vertices are visible; its score is sigma ((sx1 - sx0)(sy2 - sy0) -
+ *     (sy1 - sy0)(sx2 - sx0)), twice its signed area in pixels, with sigma = -1: a triangle of a weld seen from the
+ *     free-space side scores positive.  The view wins triangle t iff score > min_area2 and score > best_score[t];
+ *     best_score starts at 0 and best_view at -1, and the strict > lets the earlier view keep a tie.  A view's number is the
+ *     count of views added since ekf_texture_begin;
+ *  4. the fill, for every texel of a triangle the current view has just won: Xp = (l0 X0 + l1 X1) + l2 X2 per coordinate,
+ *     projected as in 2; if !(p2 > 0) or a coordinate is NaN the texel is left as it is; sx is clamped to [0, W - 1] and sy to
+ *     [0, H - 1]; the sample is ekf_get_frame_rectified's blend: q = (int) floor(s 32 + 0.5), i = q >> 5, alpha = q & 31, the
+ *     second tap min(i + 1, dim - 1), weights (32 - ax)(32 - ay) and so on, the value (sum w tap + 512) >> 10.  A 3-channel
+ *     atlas takes B, G, R and a grey view replicates its value; a 1-channel atlas takes the view's grey image (of a colour
+ *     view: the grey image ekf_dense_set_view_colour derived, the library's B, G, R -> grey conversion);
+ *  5. the finish: the texels of a triangle with best_view = -1 get, per channel, floor(((l0 g0 + l1 g1) + l2 g2) + 0.5)
+ *     clamped to 0..255, g the source's vertex grey, or its B, G, R on a colour volume with a 3-channel atlas.  Padding
+ *     (t >= n_tri) stays 0.  n_textured is the number of triangles with a view.
+ * A triangle and a texel belong to one lane; the only atomics are two integer adds a workgroup of k_tex_select (the triangles
+ * a view won, and won for the first time), exact in any order.  Opt-in and terminal: nothing above calls them, and no
+ * result, launch, profile count or prototype above changes; ekf_abi_version() stays 6 (additions only).  The sources and the
+ * last render are only read and stay valid.  EKF_ERR_STATE as ekf_simplify_run's for sources 0, 1 and 2, and for source 3
+ * without an ekf_simplify_run on the current mesh; whatever invalidates the source mesh invalidates the texture: a new weld,
+ * a prune, smooth or simplify run on which the source depends, a change of the volume.  Device memory (grow-only):
+ * A A channels bytes, 13 bytes a triangle, 17 bytes a source vertex.  A failed allocation in ekf_texture_begin is
+ * EKF_ERR_DEVICE and leaves everything as it was, the texture begun before included; a clear that fails after it leaves the
+ * handle without a texture (the buffers may be the earlier texture's own).  The image of ekf_texture_add_view_host is staged
+ * in a buffer that grows by itself: a failed growth is EKF_ERR_DEVICE, loses only that staging buffer and adds no view.
+ * Argument errors are reported before the device is touched.
+ *  - ekf_texture_begin: allocates and clears; reports A.  EKF_ERR_ARG: source not 0..3, patch not 2..32, channels not 1 or
+ *    3, a NULL atlas_side, A > 16384; EKF_ERR_STATE also for a source without triangles;
+ *  - ekf_texture_add_view: the image, K and pose of a set slot of a dense handle, read where they lie on the device
+ *    (EKF_ERR_ARG: a dense handle on another device): k_tex_project, k_tex_select, one read-back of the two counters and,
+ *    if the view won a triangle, k_tex_fill; reports the triangles it won.  occlusion is 0 or 1; 1 takes the depth image of
+ *    the handle's current ekf_raycast_render / _render_view as the z-buffer (EKF_ERR_STATE without one since the volume last
+ *    changed, or if its size is not the view's; that its pose is the view's is the caller's duty; the render stays
+ *    readable).  tol and min_area2 are finite and >= 0.  EKF_ERR_STATE before ekf_texture_begin and after ekf_texture_finish;
+ *  - ekf_texture_add_view_host: the same for an image from the host: rows of channels width bytes (1: grey; 3: B, G, R),
+ *    1 <= width, height <= 8192, K finite with fx, fy > 0;
+ *  - ekf_texture_finish: k_tex_fallback; reports n_textured.  EKF_ERR_STATE when called twice;
+ *  - ekf_texture_get: readable any time after ekf_texture_begin; every pointer may be NULL.  atlas: A rows of A channels
+ *    bytes, `pitch` bytes apart (EKF_ERR_ARG: pitch < A channels); uv: 6 doubles a triangle (u, v of corners 0, 1, 2); view:
+ *    int32; score: double; each for the first min(n_tri, max_tri) triangles;
+ *  - ekf_texture_get_profile: HIP-event milliseconds and launch counts of 4 kinds since the last ekf_fusion_profile:
+ *    k_tex_project ([0]), k_tex_select ([1]), k_tex_fill ([2]), k_tex_fallback ([3]).  The other profile getters gain
+ *    nothing. */
+int ekf_texture_begin(ekf_fusion* h, int source, int patch, int channels, int* atlas_side);
+int ekf_texture_add_view(ekf_fusion* h, ekf_dense* dense, int slot, int occlusion, double tol, double min_area2,
+                         unsigned long long* n_won);
+int ekf_texture_add_view_host(ekf_fusion* h, const unsigned char* img, int pitch, int channels, int width, int height,
+                              const double* K, const double* pose7, int occlusion, double tol, double min_area2,
+                              unsigned long long* n_won);
+int ekf_texture_finish(ekf_fusion* h, unsigned long long* n_textured);
+int ekf_texture_get(ekf_fusion* h, unsigned char* atlas, int pitch, double* uv, int* view, double* score,
+                    unsigned long long max_tri);
+int ekf_texture_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -637,7 +637,9 @@ class DenseStereoHip {
 // weld() / mesh() mirror ekf_mesh_* (section 24): the indexed mesh welded on the device, with vertex normals on request;
 // components() / prune() / pruned() its connected components and the weld without the small ones (section 25);
 // smooth() / smoothed() / adjacency() either of them smoothed with Taubin's scheme, with normals of its own (section 26);
-// simplify() / simplified() / simplifyMap() any of the three with its vertices clustered on a grid of cells (section 28).
+// simplify() / simplified() / simplifyMap() any of the three with its vertices clustered on a grid of cells (section 28);
+// textureBegin() / textureAddView() / textureAddViewHost() / textureFinish() a per-triangle texture atlas of any of the four,
+// filled from views that are fed one at a time (section 29).
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -671,6 +673,22 @@ class TsdfVolumeHip {
     unsigned long long degenerate = 0;         // the triangles of which two vertices fell into one cell
     unsigned long long duplicate = 0;          // those whose unordered triple of cells a triangle with a smaller index has
   };
+  struct Occlusion {                           // the ray cast that gives a view of the texture its z-buffer: section 29
+    double z_near, z_far;
+    double step = 0.0;                         // 0: half a voxel
+    int min_count = 1;
+    Occlusion(double near_, double far_, double step_ = 0.0, int min_count_ = 1)
+        : z_near(near_), z_far(far_), step(step_), min_count(min_count_) {}
+  };
+  struct TextureAtlas {                        // of textureFinish(): section 29; triangle t owns one half of block t >> 1
+    int side = 0, channels = 0;
+    std::vector<unsigned char> atlas;          // side rows of side x channels bytes, row 0 first; 3 channels: B G R
+    std::vector<double> uv;                    // 6 per triangle: u, v of its corners 0, 1 and 2, v measured from row 0
+    std::vector<int> view;                     // 1 per triangle: the number of the view that textured it, -1: none
+    std::vector<double> score;                 // 1 per triangle: twice its area in that view's pixels, 0: none
+    unsigned long long n_textured = 0;         // the triangles with a view
+    size_t triangles() const { return view.size(); }
+  };
   struct Volume {
     std::vector<float> sum;
     std::vector<unsigned short> cnt;
@@ -687,7 +705,7 @@ class TsdfVolumeHip {
   };
 
   TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0, bool colour = false)
-      : n_((size_t)nx * (size_t)ny * (size_t)nz), colour_(colour) {
+      : n_((size_t)nx * (size_t)ny * (size_t)nz), colour_(colour), voxel_(voxel) {
     if ((colour ? ekf_colour_create : ekf_fusion_create)(nx, ny, nz, origin, voxel, trunc, device, &f_) != EKF_OK)
       throw std::runtime_error(std::string("ekf_fusion_create: ") + ekf_fusion_last_error(nullptr));
   }
@@ -804,6 +822,7 @@ class TsdfVolumeHip {
   IndexedMesh simplify(double cell, int source = 0, SimplifyStats* stats = nullptr) {
     SimplifyStats st;
     check(ekf_simplify_run(f_, source, cell, &simplify_vertices_, &simplify_triangles_, &st.degenerate, &st.duplicate));
+    simplify_cell_ = cell;
     simplify_normals_ = source == 2 ? smooth_normals_ : weld_normals_;
     simplify_source_vertices_ = source == 2 ? smooth_vertices_ : (source == 1 ? pruned_vertices_ : weld_vertices_);
     if (stats) *stats = st;
@@ -820,6 +839,67 @@ class TsdfVolumeHip {
   // HIP-event milliseconds and launch counts of k_simp_cells, k_simp_count, k_simp_offsets, the simplification's k_tsdf_scan,
   // k_simp_fill, k_simp_lists, k_simp_flags, k_simp_vertices, k_simp_faces, k_simp_map
   void getSimplifyProfile(double kernel_ms[10], long long launches[10]) { check(ekf_simplify_get_profile(f_, kernel_ms, launches)); }
+  // Starts a texture atlas (section 29) of the last weld() (source 0), prune() (1), smooth() (2) or simplify() (3): every pair of
+  // triangles gets a block of patch + 2 texels a side (patch 2..32); channels 1 or 3 (0: 3 for a colour volume, else 1).  Returns
+  // the atlas's side.  The source is only read.
+  int textureBegin(int source = 0, int patch = 8, int channels = 0) {
+    const int c = channels ? channels : (colour_ ? 3 : 1);
+    int side = 0;
+    check(ekf_texture_begin(f_, source, patch, c, &side));
+    texture_side_ = side;
+    texture_channels_ = c;
+    texture_source_ = source;
+    texture_triangles_ = source == 3 ? simplify_triangles_ : (source == 2 ? smooth_triangles_ : (source == 1 ? pruned_triangles_ : weld_triangles_));
+    return side;
+  }
+  // The image, K and pose of a set slot of a dense handle as the next view, straight from its device buffers; returns the
+  // triangles it won.  occlusion (optional): the volume is ray-cast at the slot's pose first (raycastView with that range), and a
+  // vertex counts as seen only if it lies no more than tol behind that render; tol < 0: the voxel, and for a simplified source
+  // its cell.  min_area2: twice the least area in pixels a triangle must have.
+  unsigned long long textureAddView(DenseStereoHip& dense, int slot, const Occlusion* occlusion = nullptr, double tol = -1.0,
+                                    double min_area2 = 0.0) {
+    if (occlusion)
+      check(ekf_raycast_render_view(f_, dense.handle(), slot, occlusion->z_near, occlusion->z_far,
+                                    occlusion->step > 0.0 ? occlusion->step : voxel_ / 2.0, occlusion->min_count));
+    unsigned long long n = 0;
+    check(ekf_texture_add_view(f_, dense.handle(), slot, occlusion ? 1 : 0, textureTol(tol), min_area2, &n));
+    return n;
+  }
+  // the same for an image from the host: height rows of channels x width bytes (1: grey, 3: B G R), `pitch` bytes apart (0: tight);
+  // occlusion: the volume is ray-cast with that size, K and pose first (raycast with that range)
+  unsigned long long textureAddViewHost(const unsigned char* img, int channels, int width, int height, const double K[4],
+                                        const double pose7[7], const Occlusion* occlusion = nullptr, double tol = -1.0,
+                                        double min_area2 = 0.0, int pitch = 0) {
+    if (occlusion)
+      check(ekf_raycast_render(f_, width, height, K, pose7, occlusion->z_near, occlusion->z_far,
+                               occlusion->step > 0.0 ? occlusion->step : voxel_ / 2.0, occlusion->min_count));
+    unsigned long long n = 0;
+    check(ekf_texture_add_view_host(f_, img, pitch ? pitch : channels * width, channels, width, height, K, pose7, occlusion ? 1 : 0,
+                                    textureTol(tol), min_area2, &n));
+    return n;
+  }
+  // fills the triangles no view won with the blend of their vertices' grey (or B, G, R) and returns the atlas
+  TextureAtlas textureFinish() {
+    unsigned long long n = 0;
+    check(ekf_texture_finish(f_, &n));
+    TextureAtlas t = texture();
+    t.n_textured = n;
+    return t;
+  }
+  // the atlas as it is now, any time after textureBegin() (n_textured: the triangles with a view)
+  TextureAtlas texture() {
+    TextureAtlas t;
+    t.side = texture_side_;
+    t.channels = texture_channels_;
+    const size_t nt = (size_t)texture_triangles_;
+    t.atlas.resize((size_t)t.side * (size_t)t.side * (size_t)t.channels);
+    t.uv.resize(nt * 6); t.view.resize(nt); t.score.resize(nt);
+    check(ekf_texture_get(f_, t.atlas.data(), t.side * t.channels, t.uv.data(), t.view.data(), t.score.data(), texture_triangles_));
+    for (size_t i = 0; i < nt; ++i) t.n_textured += t.view[i] >= 0 ? 1 : 0;
+    return t;
+  }
+  // HIP-event milliseconds and launch counts of k_tex_project, k_tex_select, k_tex_fill, k_tex_fallback
+  void getTextureProfile(double kernel_ms[4], long long launches[4]) { check(ekf_texture_get_profile(f_, kernel_ms, launches)); }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
@@ -868,12 +948,17 @@ class TsdfVolumeHip {
                  normals ? m.normal.data() : nullptr, m.key.data(), n_vert, n_tri));
     return m;
   }
+  // the default of tol: the voxel, and for a simplified source the cell of that run
+  double textureTol(double tol) const { return tol >= 0.0 ? tol : (texture_source_ == 3 ? simplify_cell_ : voxel_); }
   size_t n_;
   bool colour_;
+  double voxel_, simplify_cell_ = 0.0;
   unsigned long long weld_vertices_ = 0, weld_triangles_ = 0;
   unsigned long long pruned_vertices_ = 0, pruned_triangles_ = 0;
   unsigned long long smooth_vertices_ = 0, smooth_triangles_ = 0;
   unsigned long long simplify_vertices_ = 0, simplify_triangles_ = 0, simplify_source_vertices_ = 0;
+  unsigned long long texture_triangles_ = 0;
+  int texture_side_ = 0, texture_channels_ = 0, texture_source_ = 0;
   bool weld_normals_ = false, smooth_normals_ = false, simplify_normals_ = false;
   ekf_fusion* f_ = nullptr;
 };
