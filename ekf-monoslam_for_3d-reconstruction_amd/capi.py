@@ -258,6 +258,12 @@ _PROTOS = {
     "ekf_texture_finish": (C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
     "ekf_texture_get": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_ulonglong]),
     "ekf_texture_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_raster_set_mesh": (C.c_int, [_P, _P, _P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
+    "ekf_raster_render": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "ekf_raster_render_view": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "ekf_raster_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ekf_raster_set_small_limit": (C.c_int, [_P, C.c_int]),
+    "ekf_raster_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -41,6 +41,7 @@
 #include "ekf_mesh_smooth.hpp"
 #include "ekf_mesh_simplify.hpp"
 #include "ekf_mesh_texture.hpp"
+#include "ekf_mesh_raster.hpp"
 
 namespace ekf {
 
@@ -5873,6 +5874,7 @@ struct ekf_fusion {
   ekf::TsdfSmooth smooth;             // the smoothed copy of either of them
   ekf::TsdfSimplify simp;             // the simplified copy of any of the three
   ekf::TsdfTexture tex;               // the texture atlas of any of the four
+  ekf::TsdfRaster rast;               // the last rasterisation of any of them, or of a mesh the caller gave
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6146,6 +6148,7 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   h->smooth.timer.enable(enable != 0);  // the seven of the smoothing
   h->simp.timer.enable(enable != 0);    // the ten of the simplification
   h->tex.timer.enable(enable != 0);     // the four of the texture
+  h->rast.timer.enable(enable != 0);    // the four of the rasteriser
   return EKF_OK;
 }
 
@@ -6783,6 +6786,158 @@ int ekf_texture_get(ekf_fusion* h, unsigned char* atlas, int pitch, double* uv, 
 int ekf_texture_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->tex.timer.read(kernel_ms, launches, 0, ekf::kTexKinds);
+  return EKF_OK;
+}
+
+// ---- a rasteriser for the indexed meshes: depth, triangle, barycentric, normal and shaded images ------------
+int ekf_raster_set_mesh(ekf_fusion* h, const double* xyz, const unsigned* faces, const unsigned char* grey, const unsigned char* bgr,
+                        unsigned long long n_vert, unsigned long long n_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  bool ok = xyz && faces && grey && n_vert > 0 && n_vert <= 0xffffffffull && n_tri > 0 && n_tri <= 0xffffffffull;
+  for (unsigned long long i = 0; ok && i < n_vert * 3; ++i) ok = std::isfinite(xyz[i]);
+  for (unsigned long long i = 0; ok && i < n_tri * 3; ++i) ok = faces[i] < n_vert;
+  if (!ok) {
+    f->err = "ekf_raster_set_mesh: xyz, faces and grey not NULL; 0 < n_vert, n_tri < 2^32; xyz finite; every index < n_vert";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->rast.set_mesh(xyz, faces, grey, bgr, (size_t)n_vert, (size_t)n_tri));
+  return EKF_OK;
+}
+
+// Everything of a render but the view: EKF_OK with the source's arrays and, for shading 1, the atlas; otherwise the status with
+// the message set.  Arguments first, then the state.
+static int raster_source(ekf_fusion* h, const char* who, int source, double z_near, int cull, int shading, int cover, ekf::RastMesh* s,
+                         ekf::RastAtlas* atlas) {
+  auto* f = h->impl;
+  if (source < 0 || source > 4 || !std::isfinite(z_near) || z_near < 0.0 || (cull != 0 && cull != 1) || (shading != 0 && shading != 1) ||
+      (cover != 0 && cover != 1)) {
+    f->err = std::string(who) + ": source 0..4; z_near finite and >= 0; cull, shading and cover 0 or 1";
+    return EKF_ERR_ARG;
+  }
+  if (source == 4 && shading == 1) {
+    f->err = std::string(who) + ": shading 1 needs a source with a texture: 0, 1, 2 or 3";
+    return EKF_ERR_ARG;
+  }
+  if (source == 4) {
+    if (!h->rast.m_set) {
+      f->err = std::string(who) + ": source 4 needs an ekf_raster_set_mesh";
+      return EKF_ERR_STATE;
+    }
+    *s = h->rast.own_mesh();
+    return EKF_OK;
+  }
+  ekf::MeshView m;
+  unsigned long long run = 0;
+  const int rc = texture_source(h, who, source, &m, &run);
+  if (rc != EKF_OK) return rc;
+  if (m.n_tri == 0) {
+    f->err = std::string(who) + ": the source mesh has no triangle";
+    return EKF_ERR_STATE;
+  }
+  s->xyz = m.xyz; s->faces = m.faces; s->grey = m.grey; s->bgr = f->colour ? m.bgr : nullptr;
+  s->n_vert = m.n_vert; s->n_tri = m.n_tri;
+  if (shading == 1) {
+    const ekf::TsdfTexture& t = h->tex;
+    if (texture_current(h, who) != EKF_OK || !t.finished || t.from != source) {
+      f->err = std::string(who) + ": shading 1 needs a finished texture (ekf_texture_finish) of the source that is rendered";
+      return EKF_ERR_STATE;
+    }
+    atlas->atlas = t.atlas; atlas->P = t.P; atlas->B = t.B; atlas->Q = (int)t.Q; atlas->A = (int)t.A; atlas->C = t.C;
+  }
+  return EKF_OK;
+}
+
+int ekf_raster_render(ekf_fusion* h, int source, int width, int height, const double* K, const double* pose7, double z_near, int cull,
+                      int shading, int cover) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  double t[3], R[9], q[4];
+  if (width < 1 || height < 1 || width > ekf::kRaycastMaxDim || height > ekf::kRaycastMaxDim || !K || !sba_finite(K, 4) || K[0] == 0.0 ||
+      K[1] == 0.0 || !pose7 || !ekf::dense_pose(pose7, t, R, q)) {
+    f->err = "ekf_raster_render: 1 <= width, height <= 8192; K finite with fx, fy != 0; pose7 finite with q != 0";
+    return EKF_ERR_ARG;
+  }
+  ekf::RastMesh s;
+  ekf::RastAtlas atlas;
+  const int rc = raster_source(h, "ekf_raster_render", source, z_near, cull, shading, cover, &s, &atlas);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->rast.render(s, shading ? &atlas : nullptr, width, height, K, R, t, z_near, cull, cover));
+  return EKF_OK;
+}
+
+int ekf_raster_render_view(ekf_fusion* h, int source, ekf_dense* dense, int slot, double z_near, int cull, int shading, int cover) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!dense || dense->impl->device != f->device) {
+    f->err = "ekf_raster_render_view: a dense handle on the volume's device";
+    return EKF_ERR_ARG;
+  }
+  auto* d = dense->impl;
+  if (slot < 0 || slot >= d->max_views) {
+    f->err = "ekf_raster_render_view: slot in 0..max_views-1";
+    return EKF_ERR_ARG;
+  }
+  ekf::RastMesh s;
+  ekf::RastAtlas atlas;
+  const int rc = raster_source(h, "ekf_raster_render_view", source, z_near, cull, shading, cover, &s, &atlas);
+  if (rc != EKF_OK) return rc;
+  const ekf::DenseView& v = d->v[slot];
+  if (!v.set) {
+    f->err = "ekf_raster_render_view: the slot is not set";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->rast.render(s, shading ? &atlas : nullptr, d->W, d->H, v.K, v.R, v.t, z_near, cull, cover));
+  return EKF_OK;
+}
+
+int ekf_raster_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, unsigned char* bgr, int* tri, float* bary,
+                   unsigned* cover, int* width, int* height) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfRaster& m = h->rast;
+  if (!m.valid) {
+    f->err = "ekf_raster_get: no ekf_raster_render";
+    return EKF_ERR_STATE;
+  }
+  if ((bgr && !m.has_bgr) || (cover && !m.has_cover)) {
+    f->err = "ekf_raster_get: bgr must be NULL when the render has no colour image, and cover when it was rendered with cover = 0";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t n = (size_t)m.W * (size_t)m.H;
+  HIPCHK(hipSetDevice(f->device));
+  if (depth) HIPCHK(hipMemcpy(depth, m.depth, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (normal) HIPCHK(hipMemcpy(normal, m.normal, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (grey) HIPCHK(hipMemcpy(grey, m.grey, n, hipMemcpyDeviceToHost));
+  if (bgr) HIPCHK(hipMemcpy(bgr, m.bgr, n * 3, hipMemcpyDeviceToHost));
+  if (tri) HIPCHK(hipMemcpy(tri, m.tri, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (bary) HIPCHK(hipMemcpy(bary, m.bary, n * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (cover) HIPCHK(hipMemcpy(cover, m.cover, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (width) *width = m.W;
+  if (height) *height = m.H;
+  return EKF_OK;
+}
+
+int ekf_raster_set_small_limit(ekf_fusion* h, int limit) {
+  if (!h) return EKF_ERR_ARG;
+  if (limit < 0 || limit > (int)ekf::kRastMaxSmallLimit) {
+    h->impl->err = "ekf_raster_set_small_limit: limit in 0..65536";
+    return EKF_ERR_ARG;
+  }
+  h->rast.small_limit = (unsigned)limit;
+  return EKF_OK;
+}
+
+int ekf_raster_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->rast.timer.read(kernel_ms, launches, 0, ekf::kRastKinds);
   return EKF_OK;
 }
 

@@ -81,8 +81,10 @@ struct TexArgs {
   double R[9], t[3];                  // x_cam = R^T (X - t)
 };
 
-// Step 2's projection: p2 (the caller tests it), sx and sy.
-__device__ __forceinline__ double tex_project(const TexArgs& a, double X0, double X1, double X2, double& sx, double& sy) {
+// Step 2's projection: p2 (the caller tests it), sx and sy.  `a` is whatever holds the view's K, R and t: the rasteriser of
+// ekf_mesh_raster.hpp projects through this function too.
+template <typename Args>
+__device__ __forceinline__ double tex_project(const Args& a, double X0, double X1, double X2, double& sx, double& sy) {
 #pragma clang fp contract(off)
   const double d0 = X0 - a.t[0], d1 = X1 - a.t[1], d2 = X2 - a.t[2];
   const double p0 = a.R[0] * d0 + a.R[3] * d1 + a.R[6] * d2;

@@ -9,7 +9,8 @@ welded on the device, with per-vertex normals on request; ``TsdfVolume.component
 components there and drop the small ones (§25); ``TsdfVolume.smooth`` smooths either mesh there with Taubin's scheme and gives
 it normals from its own triangles (§26); ``TsdfVolume.simplify`` clusters the vertices of any of the three on a grid of cells
 (§28); ``TsdfVolume.texture_begin`` / ``texture_add_view`` / ``texture_finish`` fill a per-triangle texture atlas of any of the
-four from views (§29), and ``write_mesh_obj`` stores a mesh with its atlas.
+four from views (§29), and ``write_mesh_obj`` stores a mesh with its atlas; ``TsdfVolume.rasterise`` / ``rasterise_view``
+render any of the four, or a mesh given with ``set_raster_mesh``, from a pose with its vertex colours or that atlas (§30).
 """
 from __future__ import annotations
 
@@ -39,6 +40,9 @@ SIMPLIFY_KERNELS = ("k_simp_cells", "k_simp_count", "k_simp_offsets", "k_tsdf_sc
 SIMPLIFY_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2}
 TEXTURE_KERNELS = ("k_tex_project", "k_tex_select", "k_tex_fill", "k_tex_fallback")
 TEXTURE_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2, "simplified": 3}
+RASTER_KERNELS = ("k_rast_project", "k_rast_small", "k_rast_large", "k_rast_resolve")
+RASTER_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2, "simplified": 3, "mesh": 4}
+RASTER_SHADINGS = {"vertex": 0, "texture": 1}
 
 
 @dataclass
@@ -106,6 +110,15 @@ class Render:
 
 
 @dataclass
+class MeshRender(Render):
+    """What ``TsdfVolume.rasterise`` returns: a mesh seen from a pose.  ``normal`` is the winning triangle's own,
+    not flipped for a back face; a pixel without a hit has depth 0, tri -1, bary 0, normal 0 and colour 0."""
+    tri: Optional[np.ndarray] = None          # (H, W) int32: the triangle of the source that the pixel shows, -1: none
+    bary: Optional[np.ndarray] = None         # (H, W, 2) float32: its perspective-correct barycentrics l1, l2 (l0 = 1 - l1 - l2)
+    cover: Optional[np.ndarray] = None        # (H, W) uint32: the triangles that cover the pixel; ``cover=True`` only
+
+
+@dataclass
 class FrameAudit:
     """One key frame of ``audit_recording``: the volume rendered at its pose against its filtered depth map and image."""
     id: int
@@ -115,6 +128,9 @@ class FrameAudit:
     p90: float                     # its 90th percentile
     grey_error: float              # mean |grey - image| over the pixels the render hit (NaN if there are none)
     colour_error: float = float("nan")        # the mean over those pixels of the mean |channel - image channel|; NaN for grey
+    # with ``audit_recording(render="mesh")`` a second FrameAudit: the last mesh of the chain rasterised at the same pose (§30)
+    # against the same depth map and image.  An attribute beside the fields, as ``RecordingMesh.normals`` is
+    mesh = None
 
 
 @dataclass
@@ -168,6 +184,7 @@ class TsdfVolume(capi.Handle):
         self._simplify_cell = 0.0               # the cell of the last simplify
         self.simplify_stats = SimplifyStats(0, 0)
         self._texture = None                    # (triangles, atlas side, channels, source) of the last texture_begin
+        self._raster_mesh_colour = False        # whether the last set_raster_mesh gave B, G, R
 
     def integrate(self, dense_stereo, slot: int, filtered: bool = True):
         """The swept or filtered map of a slot of a ``DenseStereo``, straight from its device buffers."""
@@ -428,6 +445,78 @@ class TsdfVolume(capi.Handle):
         ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
         self._check(self._lib.ekf_texture_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(TEXTURE_KERNELS)}
+
+    def set_raster_mesh(self, vertices, faces, grey, colour=None):
+        """Gives the rasteriser a mesh of the caller's (source ``"mesh"``), for instance one read back with
+        ``read_mesh_ply``: ``vertices`` (m, 3) finite, ``faces`` (n, 3) with every index < m, ``grey`` (m,) uint8 and optionally
+        ``colour`` (m, 3) uint8 in B, G, R order.  It is copied to buffers of the rasteriser's own."""
+        X = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
+        F = np.asarray(faces).reshape(-1, 3)
+        if F.size and (F.min() < 0 or F.max() > 0xFFFFFFFF):
+            raise ValueError("a face index is negative or does not fit 32 bits")
+        F = np.ascontiguousarray(F, np.uint32)
+        g = np.ascontiguousarray(grey, np.uint8).reshape(-1)
+        c = None if colour is None else np.ascontiguousarray(colour, np.uint8).reshape(-1, 3)
+        if len(g) != len(X) or (c is not None and len(c) != len(X)):
+            raise ValueError("grey and colour have one row a vertex")
+        self._check(self._lib.ekf_raster_set_mesh(self._h, _ptr(X), _ptr(F), _ptr(g), _ptr(c), len(X), len(F)))
+        self._raster_mesh_colour = c is not None
+
+    def _raster_args(self, source, shading):
+        if source not in RASTER_SOURCES:
+            raise ValueError('source is "weld", "pruned", "smoothed", "simplified" or "mesh"')
+        if shading not in RASTER_SHADINGS:
+            raise ValueError('shading is "vertex" or "texture"')
+        return RASTER_SOURCES[source], RASTER_SHADINGS[shading]
+
+    def _mesh_render(self, source: str, shading: str, cover: bool) -> MeshRender:
+        w, h = C.c_int(0), C.c_int(0)
+        self._check(self._lib.ekf_raster_get(self._h, None, None, None, None, None, None, None, C.byref(w), C.byref(h)))
+        n = (h.value, w.value)
+        if shading == "texture":
+            colour = self._texture is not None and self._texture[1] == 3
+        else:
+            colour = self._raster_mesh_colour if source == "mesh" else self.colour
+        r = MeshRender(np.zeros(n, np.float32), np.zeros(n + (3,), np.float32), np.zeros(n, np.uint8),
+                       np.zeros(n + (3,), np.uint8) if colour else None, np.zeros(n, np.int32), np.zeros(n + (2,), np.float32),
+                       np.zeros(n, np.uint32) if cover else None)
+        self._check(self._lib.ekf_raster_get(self._h, _ptr(r.depth), _ptr(r.normal), _ptr(r.grey), _ptr(r.colour), _ptr(r.tri),
+                                             _ptr(r.bary), _ptr(r.cover), None, None))
+        return r
+
+    def rasterise(self, shape, K, pose7, source: str = "weld", z_near: float = 0.0, cull: bool = True, shading: str = "vertex",
+                  cover: bool = False) -> MeshRender:
+        """The last ``weld``, ``prune`` (``"pruned"``), ``smooth`` (``"smoothed"``) or ``simplify`` (``"simplified"``), or the mesh
+        of ``set_raster_mesh`` (``"mesh"``), seen by a pinhole camera of ``shape`` = (width, height) pixels, ``K`` = (fx, fy, cx,
+        cy), at ``pose7``: the nearest triangle of every pixel, its depth, its barycentrics, its normal and its
+        colour.  A triangle with a vertex at or in front of ``z_near`` is dropped whole; ``cull`` drops the triangles seen from
+        behind.  ``shading``: ``"vertex"`` blends the vertex grey (and B, G, R), ``"texture"`` samples the finished texture of
+        that source.  ``cover`` also counts the triangles that cover every pixel.  The source is only read."""
+        src, shade_ = self._raster_args(source, shading)
+        K = np.ascontiguousarray(K, np.float64).reshape(4)
+        pose = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        self._check(self._lib.ekf_raster_render(self._h, src, int(shape[0]), int(shape[1]), _ptr(K), _ptr(pose), float(z_near),
+                                                1 if cull else 0, shade_, 1 if cover else 0))
+        return self._mesh_render(source, shading, cover)
+
+    def rasterise_view(self, dense_stereo, slot: int, source: str = "weld", z_near: float = 0.0, cull: bool = True,
+                       shading: str = "vertex", cover: bool = False) -> MeshRender:
+        """``rasterise`` with the size, K and pose of a set slot of a ``DenseStereo``."""
+        src, shade_ = self._raster_args(source, shading)
+        self._check(self._lib.ekf_raster_render_view(self._h, src, dense_stereo._h, int(slot), float(z_near), 1 if cull else 0,
+                                                     shade_, 1 if cover else 0))
+        return self._mesh_render(source, shading, cover)
+
+    def set_raster_small_limit(self, limit: int = 16):
+        """A triangle whose box on the image has at most ``limit`` pixels (0..65536) is walked by one lane, a larger one by a
+        workgroup; the images do not depend on it."""
+        self._check(self._lib.ekf_raster_set_small_limit(self._h, int(limit)))
+
+    def get_raster_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the four kinds of launch of the rasteriser since the last ``profile()``."""
+        ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
+        self._check(self._lib.ekf_raster_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(RASTER_KERNELS)}
 
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
@@ -857,12 +946,17 @@ def grey_image(bgr) -> np.ndarray:
 def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Optional[float] = None, bounds=None,
                     trunc: Optional[float] = None, min_count: int = 2, sweep_trunc: Optional[int] = None,
                     weld: str = "host", normals: bool = False, components=None, smooth=None, simplify=None, texture=None,
-                    **sweep_kwargs) -> RecordingAudit:
+                    render: Optional[str] = None, **sweep_kwargs) -> RecordingAudit:
     """``mesh_from_recording`` with the same arguments, then the volume rendered at every key frame's pose with the
     recording's camera (samples voxel / 2 apart over ``audit_range``, the mesh's ``min_count``) and compared with that key
     frame's filtered depth map and image: the only end-to-end check that needs no ground truth.  ``sgm=…``, ``cost=…``, ``best=…``,
     ``uniqueness=…`` and ``speckle=…`` reach the sweep and the filters, and ``weld=…``, ``normals=…``, ``components=…``, ``smooth=…``
-    ``simplify=…`` and ``texture=…`` the mesh, as they do through ``mesh_from_recording``."""
+    ``simplify=…`` and ``texture=…`` the mesh, as they do through ``mesh_from_recording``.  ``render="mesh"`` also rasterises the
+    last mesh of the chain at every key frame's pose (§30; z_near 0, culling on, ``shading="texture"`` when ``texture=`` was given
+    and ``"vertex"`` otherwise) and puts the ``FrameAudit`` of that image against the same depth map and image into the frame's
+    ``mesh`` attribute: the check that sees the mesh itself.  It welds on the device too; ``None`` makes today's launches."""
+    if render not in (None, "mesh"):
+        raise ValueError('render is None or "mesh"')
     _weld_mode(weld, components)
     smooth = _smooth_kwargs(smooth)
     simplify = _simplify_factor(simplify)
@@ -872,12 +966,17 @@ def audit_recording(directory: str, nodes_out: Optional[str] = None, voxel: Opti
     vol, maps, K, images, origin, dims, vx, tr = _fuse_recording(directory, nodes_out, voxel, bounds, trunc, sweep_kwargs)
     try:
         vertices, faces, grey, colour, vertex_normals = _welded(vol, min_count, weld, normals, components, smooth, simplify,
-                                                                texture is not None)
-        atlas = _textured(vol, texture, _last_source(components, smooth, simplify), maps, images, K, tr, min_count)
+                                                                texture is not None or render is not None)
+        source = _last_source(components, smooth, simplify)
+        atlas = _textured(vol, texture, source, maps, images, K, tr, min_count)
         z_near, z_far = audit_range(maps, tr)
         h, w = images[0].shape[:2]
         frames = [audit_frame(m.id, vol.raycast((w, h), K, m.pose, z_near, z_far, None, min_count), m.depth, img)
                   for m, img in zip(maps, images)]
+        if render is not None:
+            for fr, m, img in zip(frames, maps, images):
+                fr.mesh = audit_frame(m.id, vol.rasterise((w, h), K, m.pose, source, 0.0, True, "vertex" if texture is None else "texture"),
+                                      m.depth, img)
     finally:
         vol.close()
     mesh = RecordingMesh(vertices, faces, grey, origin, dims, vx, tr, maps, colour)

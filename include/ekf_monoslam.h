@@ -1330,6 +1330,83 @@ int ekf_texture_get(ekf_fusion* h, unsigned char* atlas, int pitch, double* uv, 
                     unsigned long long max_tri);
 int ekf_texture_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- A rasteriser for the indexed meshes: depth, triangle, barycentric, normal and shaded images ----------
+ * ekf_raycast_* renders the volume; these additions render the mesh itself: the last ekf_mesh_weld (source 0), the last
+ * ekf_components_prune (1), the last ekf_smooth_run's result (2), the last ekf_simplify_run's result (3) or a mesh the caller
+ * gave with ekf_raster_set_mesh (4), from any pinhole pose, with its vertex colours (shading 0) or the atlas of §29
+ * (shading 1).  The contract, restated by tests/raster_oracle.py.  Input: a source mesh (X fp64, F uint32, vertex grey and
+ * optional B, G, R), an image of W x H, both in 1..8192, K = fx fy cx cy, a pose (normalised as ekf_raycast_render normalises
+ * it), z_near >= 0, cull, shading and cover, each 0 or 1.  Every fp64 operation is rounded once, in the written order, with
+ * contraction off:
+ *  1. a vertex: p2, sx, sy as in §29's step 2 (the same function).  It is usable iff p2 > z_near and sx and sy are finite;
+ *  2. a triangle t with the vertex indices (i0, i1, i2) is dropped if a vertex is unusable: there is no clipping, and a
+ *     triangle that straddles z_near disappears whole.  area2 = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0); area2 == 0 or NaN
+ *     drops the triangle; front = area2 < 0 (§29's sigma = -1); with cull a triangle that is not front is dropped;
+ *     s = front ? -1 : +1.  Its box: x from max(0, ceil(min sx)) to min(W - 1, floor(max sx)), y likewise; an empty box drops
+ *     the triangle.  Pixel (px, py) is sampled at ((double) px, (double) py): a pixel's centre is its integer coordinate;
+ *  3. coverage, watertight by construction.  Edge k runs from corner k to corner k + 1 mod 3 and weighs corner k + 2 mod 3.
+ *     It is evaluated from the endpoint with the lower vertex index: if i_a < i_b, E = (xb - xa)(py - ya) - (yb - ya)(px - xa)
+ *     and canon = true; otherwise E = -((xa - xb)(py - yb) - (ya - yb)(px - xb)) and canon = false: two triangles that share
+ *     an edge get exactly negated values, whatever their corner order.  e_k = s E.  The pixel is inside edge k iff e_k > 0, or
+ *     e_k == 0 and canon != front: the triangle that runs the edge in ascending index order after its flip owns the tie.  A
+ *     pixel is covered iff it is inside all three edges and ssum = (b0 + b1) + b2 > 0, b_k the e of the edge opposite
+ *     corner k;
+ *  4. depth: w_k = (b_k / ssum) / p2_k, ws = (w0 + w1) + w2, z = 1.0 / ws, z32 = (float) z; the pixel is skipped unless
+ *     ws > 0 and z32 is finite.  Perspective-correct barycentrics l_k = w_k / ws.  The pixel's key is
+ *     ((uint64) bits(z32) << 32) | t; the image of keys starts at all ones and takes the minimum: the nearest depth wins and,
+ *     among equal depths, the least triangle index.  With cover a uint32 image counts, for every pixel, the triangles that
+ *     gave it a key;
+ *  5. resolve, for every pixel whose key is not all ones, applies 2 to 4 again for the winning triangle, so that the depth is
+ *     the key's own: depth (float32) = z32, tri (int32) = t, bary = ((float) l1, (float) l2), normal = (X1 - X0) x (X2 - X0),
+ *     each component a b - c d in fp64, divided by sqrt((n0 n0 + n1 n1) + n2 n2) and converted to float; it is 0 where that
+ *     length is 0 or not finite, and it is not flipped for a back face.  Shading 0: per channel
+ *     floor(((l0 g0 + l1 g1) + l2 g2) + 0.5) clamped to 0..255: the grey image and, where the source has B, G, R (sources 0..3
+ *     of a colour volume, source 4 given with bgr), the colour image.  Shading 1: tx = ((l0 c0x + l1 c1x) + l2 c2x) +
+ *     (double)(bx B), ty likewise, with §29's c_i, bx, by of t; both clamped to [0, A - 1]; §29's 5-bit blend:
+ *     q = (int) floor(s 32 + 0.5), i = q >> 5, alpha = q & 31, the second tap min(i + 1, A - 1), (sum w tap + 512) >> 10.  A
+ *     3-channel atlas gives the colour image, and the grey image is the library's B, G, R -> grey conversion of it; a
+ *     1-channel atlas gives the grey image and no colour image.  A pixel without a hit has depth 0, tri -1, bary 0, normal 0
+ *     and colour 0.
+ * The only atomics are the 64-bit minimum of the keys, the integer add of the cover image and the cursor of a list of
+ * deferred triangles, all exact in any order: the images do not depend on how the work is divided.  Opt-in and terminal:
+ * nothing above calls them, and no result, launch, profile count or prototype above changes; ekf_abi_version() stays 6
+ * (additions only).  The sources, the atlas and the last ray cast are only read and stay valid.  Sources 0..3 are valid under
+ * ekf_texture_begin's rules and give its EKF_ERR_STATE otherwise (also for a source without triangles); source 4 is
+ * EKF_ERR_STATE before an ekf_raster_set_mesh.  Shading 1 needs a finished texture (ekf_texture_finish) whose source is the one
+ * rendered, otherwise EKF_ERR_STATE; it is EKF_ERR_ARG for source 4.  The images are a snapshot: readable from a successful
+ * render until the next render begins, whatever becomes of the source.  Device memory (grow-only): 8 bytes a pixel of keys, 29
+ * of images (32 with a colour image), 4 of cover when it is asked for, 25 bytes a vertex and 4 a triangle of scratch, and the
+ * rows of source 4.  A failed allocation is EKF_ERR_DEVICE and leaves the previous images and everything else as they were.
+ * Argument errors are reported before the device is touched, each with a message through ekf_fusion_last_error.
+ *  - ekf_raster_set_mesh: copies a mesh to buffers of the rasteriser's own: xyz 3 doubles a vertex, faces 3 uint32 a
+ *    triangle, grey a byte a vertex, bgr 3 bytes a vertex or NULL.  EKF_ERR_ARG: a NULL xyz, faces or grey, n_vert or n_tri
+ *    0 or >= 2^32, an xyz that is not finite, an index >= n_vert;
+ *  - ekf_raster_render: memsets, k_rast_project, k_rast_small, k_rast_large (unless small_limit >= width height: no box is
+ *    larger than the image) and k_rast_resolve on the default stream, without a read-back.  EKF_ERR_ARG: width or height not
+ *    in 1..8192, K not finite or fx or fy 0, a pose that is not finite or has q = 0, source not 0..4, z_near not finite or
+ *    < 0, cull, shading or cover not 0 or 1;
+ *  - ekf_raster_render_view: the same with the K, pose and size of a set slot of a dense handle (EKF_ERR_ARG: a dense handle
+ *    on another device, a slot out of range; EKF_ERR_STATE: a slot that is not set);
+ *  - ekf_raster_get: every pointer may be NULL.  depth, normal (3 floats a pixel), grey, bgr (3 bytes a pixel), tri (int32),
+ *    bary (2 floats a pixel), cover (uint32), tight rows, row 0 first.  EKF_ERR_ARG: bgr when the render has no colour image,
+ *    cover when it was rendered with cover = 0; EKF_ERR_STATE without a render;
+ *  - ekf_raster_set_small_limit: a triangle whose clamped box has at most `limit` pixels (0..65536, default 16) is walked by
+ *    one lane of k_rast_small, a larger one by a workgroup of k_rast_large; 0 defers every triangle.  The images do not
+ *    depend on it;
+ *  - ekf_raster_get_profile: HIP-event milliseconds and launch counts of 4 kinds since the last ekf_fusion_profile:
+ *    k_rast_project ([0]), k_rast_small ([1]), k_rast_large ([2]), k_rast_resolve ([3]).  The other profile getters gain
+ *    nothing. */
+int ekf_raster_set_mesh(ekf_fusion* h, const double* xyz, const unsigned int* faces, const unsigned char* grey,
+                        const unsigned char* bgr, unsigned long long n_vert, unsigned long long n_tri);
+int ekf_raster_render(ekf_fusion* h, int source, int width, int height, const double* K, const double* pose7, double z_near,
+                      int cull, int shading, int cover);
+int ekf_raster_render_view(ekf_fusion* h, int source, ekf_dense* dense, int slot, double z_near, int cull, int shading,
+                           int cover);
+int ekf_raster_get(ekf_fusion* h, float* depth, float* normal, unsigned char* grey, unsigned char* bgr, int* tri, float* bary,
+                   unsigned int* cover, int* width, int* height);
+int ekf_raster_set_small_limit(ekf_fusion* h, int limit);
+int ekf_raster_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

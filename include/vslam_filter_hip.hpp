@@ -639,7 +639,8 @@ class DenseStereoHip {
 // smooth() / smoothed() / adjacency() either of them smoothed with Taubin's scheme, with normals of its own (section 26);
 // simplify() / simplified() / simplifyMap() any of the three with its vertices clustered on a grid of cells (section 28);
 // textureBegin() / textureAddView() / textureAddViewHost() / textureFinish() a per-triangle texture atlas of any of the four,
-// filled from views that are fed one at a time (section 29).
+// filled from views that are fed one at a time (section 29); setRasterMesh() / rasterise() / rasteriseView() / rastered() any of
+// the four, or a mesh of the caller's, seen from a pose with its vertex colours or that atlas (section 30).
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -702,6 +703,11 @@ class TsdfVolumeHip {
     std::vector<float> normal;                 // 3 per pixel: unit, world frame, towards free space
     std::vector<unsigned char> grey;
     std::vector<unsigned char> colour;         // 3 per pixel, B G R: colour volumes only
+  };
+  struct MeshRender : Render {                 // of rasterise(): section 30; the normal is the triangle's own, not flipped
+    std::vector<int> tri;                      // the triangle of the source that the pixel shows, -1: none
+    std::vector<float> bary;                   // 2 per pixel: its perspective-correct barycentrics l1, l2
+    std::vector<unsigned int> cover;           // the triangles that cover the pixel: rasterise(.., cover = true) only
   };
 
   TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0, bool colour = false)
@@ -900,6 +906,47 @@ class TsdfVolumeHip {
   }
   // HIP-event milliseconds and launch counts of k_tex_project, k_tex_select, k_tex_fill, k_tex_fallback
   void getTextureProfile(double kernel_ms[4], long long launches[4]) { check(ekf_texture_get_profile(f_, kernel_ms, launches)); }
+  // Gives the rasteriser a mesh of the caller's (source 4, section 30): xyz 3 per vertex, faces 3 per triangle, grey 1 per vertex,
+  // colour 3 per vertex (B G R) or empty.  It is copied to buffers of the rasteriser's own.
+  void setRasterMesh(const std::vector<double>& xyz, const std::vector<unsigned int>& faces, const std::vector<unsigned char>& grey,
+                     const std::vector<unsigned char>& colour = std::vector<unsigned char>()) {
+    check(ekf_raster_set_mesh(f_, xyz.data(), faces.data(), grey.data(), colour.empty() ? nullptr : colour.data(), xyz.size() / 3,
+                              faces.size() / 3));
+    raster_mesh_colour_ = !colour.empty();
+  }
+  // The last weld() (source 0), prune() (1), smooth() (2), simplify() (3) or the mesh of setRasterMesh() (4) seen by a width x
+  // height pinhole camera K = (fx, fy, cx, cy) at pose7 (section 30): the nearest triangle of every pixel, its depth, barycentrics,
+  // normal and colour.  A triangle with a vertex at or in front of z_near is dropped whole; cull drops the triangles seen from
+  // behind; shading 0 blends the vertex colours, 1 samples the finished texture of that source; cover also counts the triangles
+  // that cover every pixel.  The source is only read.
+  MeshRender rasterise(int width, int height, const double K[4], const double pose7[7], int source = 0, double z_near = 0.0,
+                       bool cull = true, int shading = 0, bool cover = false) {
+    check(ekf_raster_render(f_, source, width, height, K, pose7, z_near, cull ? 1 : 0, shading, cover ? 1 : 0));
+    return rastered(source, shading, cover);
+  }
+  // the same with the size, K and pose of a set slot of a dense handle
+  MeshRender rasteriseView(DenseStereoHip& dense, int slot, int source = 0, double z_near = 0.0, bool cull = true, int shading = 0,
+                           bool cover = false) {
+    check(ekf_raster_render_view(f_, source, dense.handle(), slot, z_near, cull ? 1 : 0, shading, cover ? 1 : 0));
+    return rastered(source, shading, cover);
+  }
+  // the images of the last rasterise(), given what it was asked for
+  MeshRender rastered(int source = 0, int shading = 0, bool cover = false) {
+    MeshRender r;
+    check(ekf_raster_get(f_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &r.width, &r.height));
+    const size_t n = (size_t)r.width * (size_t)r.height;
+    const bool colour = shading ? texture_channels_ == 3 : (source == 4 ? raster_mesh_colour_ : colour_);
+    r.depth.resize(n); r.normal.resize(n * 3); r.grey.resize(n); r.tri.resize(n); r.bary.resize(n * 2);
+    if (colour) r.colour.resize(n * 3);
+    if (cover) r.cover.resize(n);
+    check(ekf_raster_get(f_, r.depth.data(), r.normal.data(), r.grey.data(), colour ? r.colour.data() : nullptr, r.tri.data(),
+                         r.bary.data(), cover ? r.cover.data() : nullptr, nullptr, nullptr));
+    return r;
+  }
+  // a triangle whose box on the image has at most `limit` pixels (0..65536) is walked by one lane, a larger one by a workgroup
+  void setRasterSmallLimit(int limit) { check(ekf_raster_set_small_limit(f_, limit)); }
+  // HIP-event milliseconds and launch counts of k_rast_project, k_rast_small, k_rast_large, k_rast_resolve
+  void getRasterProfile(double kernel_ms[4], long long launches[4]) { check(ekf_raster_get_profile(f_, kernel_ms, launches)); }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
@@ -960,5 +1007,6 @@ class TsdfVolumeHip {
   unsigned long long texture_triangles_ = 0;
   int texture_side_ = 0, texture_channels_ = 0, texture_source_ = 0;
   bool weld_normals_ = false, smooth_normals_ = false, simplify_normals_ = false;
+  bool raster_mesh_colour_ = false;
   ekf_fusion* f_ = nullptr;
 };
