@@ -22,3 +22,4 @@ from .fusion import MeshAdjacency  # noqa: F401
 from .fusion import SimplifyStats  # noqa: F401
 from .fusion import TextureAtlas, read_png, write_mesh_obj, write_png  # noqa: F401
 from .fusion import MeshRender  # noqa: F401
+from .fusion import DistanceStats, MeshDistance, compare_meshes  # noqa: F401

@@ -264,6 +264,15 @@ _PROTOS = {
     "ekf_raster_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ekf_raster_set_small_limit": (C.c_int, [_P, C.c_int]),
     "ekf_raster_get_profile": (C.c_int, [_P, _P, _P]),
+    "ekf_distance_set_mesh": (C.c_int, [_P, _P, _P, C.c_ulonglong, C.c_ulonglong]),
+    "ekf_distance_run": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "ekf_distance_run_points": (C.c_int, [_P, C.c_int, _P, C.c_ulonglong]),
+    "ekf_distance_get": (C.c_int, [_P, _P, _P, _P, _P, C.c_ulonglong]),
+    "ekf_distance_get_stats": (C.c_int, [_P, C.c_double, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_ulonglong), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]),
+    "ekf_distance_set_grid": (C.c_int, [_P, C.c_int]),
+    "ekf_distance_get_grid": (C.c_int, [_P, _P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]),
+    "ekf_distance_get_profile": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -42,6 +42,7 @@
 #include "ekf_mesh_simplify.hpp"
 #include "ekf_mesh_texture.hpp"
 #include "ekf_mesh_raster.hpp"
+#include "ekf_mesh_distance.hpp"
 
 namespace ekf {
 
@@ -5875,6 +5876,7 @@ struct ekf_fusion {
   ekf::TsdfSimplify simp;             // the simplified copy of any of the three
   ekf::TsdfTexture tex;               // the texture atlas of any of the four
   ekf::TsdfRaster rast;               // the last rasterisation of any of them, or of a mesh the caller gave
+  ekf::TsdfDistance dist;             // the last distance from the vertices of one of them, or from points, to another
 };
 
 static int fusion_create(int nx, int ny, int nz, const double* origin, double voxel, double trunc, int device, bool colour,
@@ -6149,6 +6151,7 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   h->simp.timer.enable(enable != 0);    // the ten of the simplification
   h->tex.timer.enable(enable != 0);     // the four of the texture
   h->rast.timer.enable(enable != 0);    // the four of the rasteriser
+  h->dist.timer.enable(enable != 0);    // the nine of the distance
   return EKF_OK;
 }
 
@@ -6938,6 +6941,194 @@ int ekf_raster_set_small_limit(ekf_fusion* h, int limit) {
 int ekf_raster_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
   h->rast.timer.read(kernel_ms, launches, 0, ekf::kRastKinds);
+  return EKF_OK;
+}
+
+// ---- a mesh-to-mesh distance: the nearest triangle of a target mesh for every query point ---------------------
+int ekf_distance_set_mesh(ekf_fusion* h, const double* xyz, const unsigned* faces, unsigned long long n_vert, unsigned long long n_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  bool ok = xyz && faces && n_vert > 0 && n_vert <= 0xffffffffull && n_tri > 0 && n_tri <= 0xffffffffull;
+  for (unsigned long long i = 0; ok && i < n_vert * 3; ++i) ok = std::isfinite(xyz[i]);
+  for (unsigned long long i = 0; ok && i < n_tri * 3; ++i) ok = faces[i] < n_vert;
+  if (!ok) {
+    f->err = "ekf_distance_set_mesh: xyz and faces not NULL; 0 < n_vert, n_tri < 2^32; xyz finite; every index < n_vert";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->dist.set_mesh(xyz, faces, (size_t)n_vert, (size_t)n_tri));
+  return EKF_OK;
+}
+
+// The rows of a source as the distance reads them: EKF_OK, or EKF_ERR_STATE with the message set.
+static int distance_source(ekf_fusion* h, const char* who, int source, ekf::RastMesh* s) {
+  auto* f = h->impl;
+  if (source == 4) {
+    if (!h->dist.m_set) {
+      f->err = std::string(who) + ": source 4 needs an ekf_distance_set_mesh";
+      return EKF_ERR_STATE;
+    }
+    s->xyz = h->dist.m_xyz; s->faces = h->dist.m_faces; s->n_vert = h->dist.m_vert; s->n_tri = h->dist.m_tri;
+    return EKF_OK;
+  }
+  ekf::MeshView m;
+  unsigned long long run = 0;
+  const int rc = texture_source(h, who, source, &m, &run);
+  if (rc != EKF_OK) return rc;
+  s->xyz = m.xyz; s->faces = m.faces; s->n_vert = m.n_vert; s->n_tri = m.n_tri;
+  return EKF_OK;
+}
+
+// The target of a run, then the run: what the two entry points share.  pts: the query's rows on the device.
+static int distance_run(ekf_fusion* h, const char* who, const ekf::RastMesh& t, const double* pts, unsigned long long n) {
+  auto* f = h->impl;
+  std::string& err = f->err;
+  ekf::TsdfDistance::Status st;
+  HIPCHK(h->dist.run(t.xyz, t.faces, t.n_tri, pts, n, &st));
+  if (st == ekf::TsdfDistance::kNoValid) {
+    f->err = std::string(who) + ": the target mesh has no valid triangle";
+    return EKF_ERR_STATE;
+  }
+  if (st == ekf::TsdfDistance::kTooMany) {
+    f->err = std::string(who) + ": 2^32 entries or more in the cell lists: use fewer cells (ekf_distance_set_grid)";
+    return EKF_ERR_DEVICE;
+  }
+  return EKF_OK;
+}
+
+static int distance_target(ekf_fusion* h, const char* who, int target, ekf::RastMesh* t) {
+  const int rc = distance_source(h, who, target, t);
+  if (rc != EKF_OK) return rc;
+  if (t->n_tri == 0) {
+    h->impl->err = std::string(who) + ": the target mesh has no valid triangle";
+    return EKF_ERR_STATE;
+  }
+  return EKF_OK;
+}
+
+int ekf_distance_run(ekf_fusion* h, int target, int query, unsigned long long* n_points) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (target < 0 || target > 4 || query < 0 || query > 4) {
+    f->err = "ekf_distance_run: target and query 0..4";
+    return EKF_ERR_ARG;
+  }
+  ekf::RastMesh t, q;
+  int rc = distance_target(h, "ekf_distance_run", target, &t);
+  if (rc != EKF_OK) return rc;
+  if ((rc = distance_source(h, "ekf_distance_run", query, &q)) != EKF_OK) return rc;
+  if (q.n_vert == 0) {
+    f->err = "ekf_distance_run: the query mesh has no vertex";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  rc = distance_run(h, "ekf_distance_run", t, q.xyz, q.n_vert);
+  if (rc == EKF_OK && n_points) *n_points = q.n_vert;
+  return rc;
+}
+
+int ekf_distance_run_points(ekf_fusion* h, int target, const double* xyz, unsigned long long n_points) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (target < 0 || target > 4 || !xyz || n_points < 1 || n_points > 0xffffffffull) {
+    f->err = "ekf_distance_run_points: target 0..4; xyz not NULL; 0 < n_points < 2^32";
+    return EKF_ERR_ARG;
+  }
+  ekf::RastMesh t;
+  const int rc = distance_target(h, "ekf_distance_run_points", target, &t);
+  if (rc != EKF_OK) return rc;
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  HIPCHK(h->dist.set_points(xyz, (size_t)n_points));
+  return distance_run(h, "ekf_distance_run_points", t, h->dist.q_xyz, n_points);
+}
+
+int ekf_distance_get(ekf_fusion* h, double* dist, unsigned* tri, double* closest, signed char* side, unsigned long long max_points) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfDistance& m = h->dist;
+  if (!m.valid) {
+    f->err = "ekf_distance_get: no ekf_distance_run";
+    return EKF_ERR_STATE;
+  }
+  if ((dist || tri || closest || side) && max_points < m.n_points) {
+    f->err = "ekf_distance_get: max_points is less than the points of the run";
+    return EKF_ERR_ARG;
+  }
+  std::string& err = f->err;
+  const size_t n = (size_t)m.n_points;
+  HIPCHK(hipSetDevice(f->device));
+  if (dist) HIPCHK(hipMemcpy(dist, m.dist, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (tri) HIPCHK(hipMemcpy(tri, m.tri, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (closest) HIPCHK(hipMemcpy(closest, m.closest, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (side) HIPCHK(hipMemcpy(side, m.side, n, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_distance_get_stats(ekf_fusion* h, double thr, unsigned long long* n, unsigned long long* n_bad, double* max, unsigned long long* argmax,
+                           double* mean, double* rms, unsigned long long* within) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  if (!(thr >= 0.0)) {
+    f->err = "ekf_distance_get_stats: thr >= 0";
+    return EKF_ERR_ARG;
+  }
+  if (!h->dist.valid) {
+    f->err = "ekf_distance_get_stats: no ekf_distance_run";
+    return EKF_ERR_STATE;
+  }
+  std::string& err = f->err;
+  HIPCHK(hipSetDevice(f->device));
+  ekf::DistSums s;
+  HIPCHK(h->dist.stats(thr, &s));
+  const unsigned long long good = h->dist.n_points - s.bad;
+  const double nan = __builtin_nan("");
+  if (n) *n = good;
+  if (n_bad) *n_bad = s.bad;
+  if (max) *max = good ? s.max : nan;
+  if (argmax) *argmax = good ? s.argmax : 0xffffffffull;
+  if (mean) *mean = good ? s.sum / (double)good : nan;
+  if (rms) *rms = good ? std::sqrt(s.sum2 / (double)good) : nan;
+  if (within) *within = s.within;
+  return EKF_OK;
+}
+
+int ekf_distance_set_grid(ekf_fusion* h, int g) {
+  if (!h) return EKF_ERR_ARG;
+  if (g < 0 || g > (int)ekf::kDistMaxG) {
+    h->impl->err = "ekf_distance_set_grid: g in 0..128";
+    return EKF_ERR_ARG;
+  }
+  h->dist.grid_g = (unsigned)g;
+  return EKF_OK;
+}
+
+int ekf_distance_get_grid(ekf_fusion* h, int* cells, unsigned long long* entries, unsigned* longest) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  const ekf::TsdfDistance& m = h->dist;
+  if (!m.valid) {
+    f->err = "ekf_distance_get_grid: no ekf_distance_run";
+    return EKF_ERR_STATE;
+  }
+  if (cells)
+    for (int k = 0; k < 3; ++k) cells[k] = m.grid.G[k];
+  if (entries) *entries = m.entries;
+  if (longest) {
+    std::string& err = f->err;
+    std::vector<unsigned> cnt(m.ncell);
+    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipMemcpy(cnt.data(), m.cnt, (size_t)m.ncell * sizeof(unsigned), hipMemcpyDeviceToHost));
+    *longest = *std::max_element(cnt.begin(), cnt.end());
+  }
+  return EKF_OK;
+}
+
+int ekf_distance_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
+  h->dist.timer.read(kernel_ms, launches, 0, ekf::kDistKinds);
   return EKF_OK;
 }
 

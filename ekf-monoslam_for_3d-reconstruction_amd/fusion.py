@@ -10,7 +10,9 @@ components there and drop the small ones (§25); ``TsdfVolume.smooth`` smooths e
 it normals from its own triangles (§26); ``TsdfVolume.simplify`` clusters the vertices of any of the three on a grid of cells
 (§28); ``TsdfVolume.texture_begin`` / ``texture_add_view`` / ``texture_finish`` fill a per-triangle texture atlas of any of the
 four from views (§29), and ``write_mesh_obj`` stores a mesh with its atlas; ``TsdfVolume.rasterise`` / ``rasterise_view``
-render any of the four, or a mesh given with ``set_raster_mesh``, from a pose with its vertex colours or that atlas (§30).
+render any of the four, or a mesh given with ``set_raster_mesh``, from a pose with its vertex colours or that atlas (§30);
+``TsdfVolume.distance`` / ``distance_points`` / ``distance_stats`` and ``compare_meshes`` measure how far the vertices of one of
+them, or points of the caller's, lie from another, or from a mesh given with ``set_distance_mesh`` (§31).
 """
 from __future__ import annotations
 
@@ -43,6 +45,9 @@ TEXTURE_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2, "simplified": 3}
 RASTER_KERNELS = ("k_rast_project", "k_rast_small", "k_rast_large", "k_rast_resolve")
 RASTER_SOURCES = {"weld": 0, "pruned": 1, "smoothed": 2, "simplified": 3, "mesh": 4}
 RASTER_SHADINGS = {"vertex": 0, "texture": 1}
+DISTANCE_KERNELS = ("k_dist_box", "k_dist_grid", "k_dist_count", "k_dist_offsets", "k_tsdf_scan", "k_dist_fill", "k_dist_query",
+                    "k_dist_stats", "k_dist_reduce")
+DISTANCE_SOURCES = RASTER_SOURCES
 
 
 @dataclass
@@ -116,6 +121,28 @@ class MeshRender(Render):
     tri: Optional[np.ndarray] = None          # (H, W) int32: the triangle of the source that the pixel shows, -1: none
     bary: Optional[np.ndarray] = None         # (H, W, 2) float32: its perspective-correct barycentrics l1, l2 (l0 = 1 - l1 - l2)
     cover: Optional[np.ndarray] = None        # (H, W) uint32: the triangles that cover the pixel; ``cover=True`` only
+
+
+@dataclass
+class MeshDistance:
+    """What ``TsdfVolume.distance`` and ``distance_points`` return: for every query point the nearest point on the
+    target mesh.  A point that is not finite has dist NaN, tri 0xffffffff, closest NaN and side 0."""
+    dist: np.ndarray               # (n,) float64
+    tri: np.ndarray                # (n,) uint32: the nearest triangle of the target, the least index among equally near ones
+    closest: np.ndarray            # (n, 3) float64: the nearest point on it
+    side: np.ndarray               # (n,) int8: the sign of (p - closest) . n of that triangle: +1 is the free-space side of a weld
+
+
+@dataclass
+class DistanceStats:
+    """``TsdfVolume.distance_stats``: the last distance run summed up in a fixed order, over its finite points."""
+    n: int                         # the points with a distance
+    n_bad: int                     # the others
+    max: float                     # the one-sided Hausdorff distance, and the least index that has it
+    argmax: int
+    mean: float
+    rms: float
+    within: int                    # the points with dist <= threshold
 
 
 @dataclass
@@ -518,6 +545,67 @@ class TsdfVolume(capi.Handle):
         self._check(self._lib.ekf_raster_get_profile(self._h, _ptr(ms), _ptr(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(RASTER_KERNELS)}
 
+    def set_distance_mesh(self, vertices, faces):
+        """Gives the distance a mesh of the caller's (source ``"mesh"``), for instance a ground truth:
+        ``vertices`` (m, 3) finite, ``faces`` (n, 3) with every index < m.  It is copied to buffers of the distance's own and is
+        independent of ``set_raster_mesh``."""
+        X = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
+        F = np.asarray(faces).reshape(-1, 3)
+        if F.size and (F.min() < 0 or F.max() > 0xFFFFFFFF):
+            raise ValueError("a face index is negative or does not fit 32 bits")
+        F = np.ascontiguousarray(F, np.uint32)
+        self._check(self._lib.ekf_distance_set_mesh(self._h, _ptr(X), _ptr(F), len(X), len(F)))
+
+    def _distance_source(self, source):
+        if source not in DISTANCE_SOURCES:
+            raise ValueError('a source is "weld", "pruned", "smoothed", "simplified" or "mesh"')
+        return DISTANCE_SOURCES[source]
+
+    def _distance(self, n: int) -> MeshDistance:
+        r = MeshDistance(np.zeros(n, np.float64), np.zeros(n, np.uint32), np.zeros((n, 3), np.float64), np.zeros(n, np.int8))
+        self._check(self._lib.ekf_distance_get(self._h, _ptr(r.dist), _ptr(r.tri), _ptr(r.closest), _ptr(r.side), n))
+        return r
+
+    def distance(self, target: str = "weld", query: str = "simplified") -> MeshDistance:
+        """For every vertex of ``query`` the nearest point on the mesh ``target``: each is the last ``weld``,
+        ``prune`` (``"pruned"``), ``smooth`` (``"smoothed"``), ``simplify`` (``"simplified"``) or the mesh of
+        ``set_distance_mesh`` (``"mesh"``); they may be the same.  Both are only read."""
+        n = C.c_ulonglong(0)
+        self._check(self._lib.ekf_distance_run(self._h, self._distance_source(target), self._distance_source(query), C.byref(n)))
+        return self._distance(int(n.value))
+
+    def distance_points(self, target: str, points) -> MeshDistance:
+        """The same for ``points`` (n, 3) of the caller's, n >= 1."""
+        P = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        self._check(self._lib.ekf_distance_run_points(self._h, self._distance_source(target), _ptr(P), len(P)))
+        return self._distance(len(P))
+
+    def distance_stats(self, threshold: float = 0.0) -> DistanceStats:
+        """The last ``distance`` or ``distance_points`` summed up: the maximum (the one-sided Hausdorff distance) and where, the
+        mean, the RMS and the number of points within ``threshold`` >= 0, in a fixed order of summation."""
+        n, bad, arg, within = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        mx, mean, rms = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        self._check(self._lib.ekf_distance_get_stats(self._h, float(threshold), C.byref(n), C.byref(bad), C.byref(mx), C.byref(arg),
+                                                     C.byref(mean), C.byref(rms), C.byref(within)))
+        return DistanceStats(int(n.value), int(bad.value), mx.value, int(arg.value), mean.value, rms.value, int(within.value))
+
+    def set_distance_grid(self, g: int = 0):
+        """The cells of the search grid along the longest axis of the target's box: 1..128, or 0 for the automatic choice; 1 is
+        brute force on the device.  The result does not depend on it."""
+        self._check(self._lib.ekf_distance_set_grid(self._h, int(g)))
+
+    def distance_grid(self) -> dict:
+        """Of the last run, for measurements: the cells along x, y, z, the entries of all cell lists and the longest list."""
+        cells, entries, longest = np.zeros(3, np.int32), C.c_ulonglong(0), C.c_uint(0)
+        self._check(self._lib.ekf_distance_get_grid(self._h, _ptr(cells), C.byref(entries), C.byref(longest)))
+        return dict(cells=tuple(int(c) for c in cells), entries=int(entries.value), longest=int(longest.value))
+
+    def get_distance_profile(self) -> dict:
+        """HIP-event milliseconds and launch counts of the nine kinds of launch of the distance since the last ``profile()``."""
+        ms, cnt = np.zeros(9, np.float64), np.zeros(9, np.int64)
+        self._check(self._lib.ekf_distance_get_profile(self._h, _ptr(ms), _ptr(cnt)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(DISTANCE_KERNELS)}
+
     def _render(self) -> Render:
         w, h = C.c_int(0), C.c_int(0)
         self._check(self._lib.ekf_raycast_get(self._h, None, None, None, C.byref(w), C.byref(h)))
@@ -892,6 +980,17 @@ def _welded(vol: TsdfVolume, min_count: int, mode: str = "host", normals: bool =
         return m.vertices, m.faces.astype(np.int64), m.grey, m.colour, m.normals
     mesh = vol.extract(min_count)
     return (weld(mesh, True) if vol.colour else weld(mesh) + (None,)) + (None,)
+
+
+def compare_meshes(vol: TsdfVolume, a: str, b: str, threshold: float = 0.0):
+    """Both one-sided distances between two meshes of a volume: the ``DistanceStats`` of the vertices of ``a``
+    against ``b`` and of the vertices of ``b`` against ``a``, and the symmetric maximum over vertices (the larger of the two
+    one-sided Hausdorff distances)."""
+    vol.distance(b, a)
+    ab = vol.distance_stats(threshold)
+    vol.distance(a, b)
+    ba = vol.distance_stats(threshold)
+    return ab, ba, max(ab.max, ba.max)
 
 
 def shade(render: Render, light=(0.0, 0.0, -1.0), albedo: bool = False) -> np.ndarray:

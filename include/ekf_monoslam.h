@@ -1407,6 +1407,78 @@ int ekf_raster_get(ekf_fusion* h, float* depth, float* normal, unsigned char* gr
 int ekf_raster_set_small_limit(ekf_fusion* h, int limit);
 int ekf_raster_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
 
+/* ---- A mesh-to-mesh distance: the nearest triangle of a target mesh for every query point -----------------
+ * How far one of the handle's meshes lies from another, in 3-D: for every query point the nearest point on a target mesh,
+ * and from it the one-sided Hausdorff distance, the mean, the RMS and the share within a threshold.  The contract, restated by
+ * tests/distance_oracle.py.  All arithmetic is fp64, every operation rounded once, in the written order, contraction off:
+ *  1. the target is a mesh (X, F): the last ekf_mesh_weld (source 0), the last ekf_components_prune (1), the last
+ *     ekf_smooth_run's result (2), the last ekf_simplify_run's result (3), valid under ekf_texture_begin's rules, or a mesh given
+ *     with ekf_distance_set_mesh (4), which is independent of the rasteriser's source 4.  A triangle t = (i0, i1, i2) with the
+ *     corners A, B, C is valid iff its indices are distinct, its nine coordinates are finite and, with u = B - A, v = C - A,
+ *     n = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0), nn = (n0 n0 + n1 n1) + n2 n2 is finite and > 0.  Invalid triangles take
+ *     no part; a target without a valid triangle is EKF_ERR_STATE;
+ *  2. point to triangle: Ericson, Real-Time Collision Detection, section 5.1.5, the six region tests in the book's order, with
+ *     dot(a, b) = (a0 b0 + a1 b1) + a2 b2, ab = B - A, ac = C - A, ap = p - A, bp = p - B, cp = p - C:
+ *       d1 = dot(ab, ap), d2 = dot(ac, ap);  d1 <= 0 and d2 <= 0:                                  c = A
+ *       d3 = dot(ab, bp), d4 = dot(ac, bp);  d3 >= 0 and d4 <= d3:                                 c = B
+ *       vc = d1 d4 - d3 d2;  vc <= 0 and d1 >= 0 and d3 <= 0:      v = d1 / (d1 - d3),             c = A + v ab
+ *       d5 = dot(ab, cp), d6 = dot(ac, cp);  d6 >= 0 and d5 <= d6:                                 c = C
+ *       vb = d5 d2 - d1 d6;  vb <= 0 and d2 >= 0 and d6 <= 0:      w = d2 / (d2 - d6),             c = A + w ac
+ *       va = d3 d6 - d5 d4, e = d4 - d3, f = d5 - d6;  va <= 0 and e >= 0 and f >= 0:  w = e / (e + f),  c = B + w (C - B)
+ *       otherwise s = (va + vb) + vc, v = vb / s, w = vc / s,                                      c = (A + v ab) + w ac
+ *     then every component of c is clamped to the triangle's own box by comparisons, lo_k = min(A_k, B_k, C_k),
+ *     hi_k = max(A_k, B_k, C_k), c_k = c_k < lo_k ? lo_k : (c_k > hi_k ? hi_k : c_k) (a NaN stays), and with q = p - c,
+ *     d2 = (q0 q0 + q1 q1) + q2 q2;
+ *  3. the result for a finite p: over all valid triangles the least (d2, t): t replaces the best iff d2 < best, or d2 == best
+ *     and t < best_t, from (+inf, 0xffffffff), so a d2 that is NaN never wins and among equal d2 the least index does.
+ *     dist = sqrt(d2) (double), tri = t (uint32), closest = the winner's c (3 doubles), side (int8) = the sign of
+ *     (q0 n0 + q1 n1) + q2 n2 with the winner's n: +1 is the free-space side of a weld, 0 means zero (or NaN).  A p with a
+ *     coordinate that is not finite gets dist = NaN, tri = 0xffffffff, closest = NaN, side = 0;
+ *  4. the queries are the vertices of a source 0..4 (target and query may be the same source) or n points from the host;
+ *  5. statistics of the last run for a threshold thr >= 0: a point is bad iff its dist is NaN; n_bad counts the bad points and
+ *     n the others; max and argmax, its least index; within = #{dist <= thr}; sum of dist and sum2 of dist dist, a bad point
+ *     giving 0, summed in a fixed order: per block of 256 consecutive points the tree for s = 128 .. 1: v[l] += v[l + s]; the
+ *     block partials go to one workgroup whose lane l adds the partials l, l + 256, .. in ascending order from 0.0, then the
+ *     same tree.  mean = sum / n, rms = sqrt(sum2 / n); with n = 0 they and max are NaN and argmax is 0xffffffff.
+ * A uniform grid over the box of the valid triangles only prunes the search (csrc/ekf_mesh_distance.hpp has the termination
+ * rule and its proof): the result is the same at every setting of ekf_distance_set_grid.  Opt-in and terminal: nothing above
+ * calls these, and no result, launch, profile count or prototype above changes; ekf_abi_version() stays 6 (additions only).
+ * The sources are only read.  The arrays are a snapshot: readable from a successful run until the next run begins, whatever
+ * becomes of the sources.  A failed allocation is EKF_ERR_DEVICE and leaves the previous result and every source intact: new
+ * buffers replace old ones only when all exist.  Argument errors are reported before the device is touched, each with a
+ * message through ekf_fusion_last_error.
+ *  - ekf_distance_set_mesh: copies a mesh to buffers of the feature's own: xyz 3 doubles a vertex, faces 3 uint32 a triangle.
+ *    EKF_ERR_ARG: a NULL xyz or faces, n_vert or n_tri 0 or >= 2^32, an xyz that is not finite, an index >= n_vert;
+ *  - ekf_distance_run: the vertices of source `query` against source `target`; *n_points (may be NULL) is their number.
+ *    EKF_ERR_ARG: target or query not 0..4.  EKF_ERR_STATE: a source that is not valid (ekf_texture_begin's messages; source 4
+ *    before an ekf_distance_set_mesh), a target without a valid triangle, a query without a vertex.  EKF_ERR_DEVICE: 2^32
+ *    entries or more in the cell lists;
+ *  - ekf_distance_run_points: n_points points from the host (3 doubles each), 0 < n_points < 2^32, otherwise EKF_ERR_ARG;
+ *  - ekf_distance_get: every pointer may be NULL.  dist (double), tri (uint32), closest (3 doubles a point), side (int8).
+ *    EKF_ERR_ARG: a pointer given and max_points less than the points of the run; EKF_ERR_STATE without a run;
+ *  - ekf_distance_get_stats: step 5; every output pointer may be NULL.  EKF_ERR_ARG: thr < 0 or NaN; EKF_ERR_STATE without a
+ *    run.  It launches k_dist_stats and k_dist_reduce;
+ *  - ekf_distance_set_grid: g = 0 (the default) chooses the cells along the longest axis of the box automatically,
+ *    clamp(ceil(sqrt(n_valid / 2)), 1, 128), settled from the timing table of DESIGN.md §31.4; g in 1..128 sets them; the
+ *    other axes are in proportion, at least 1.  g = 1 is brute force on the device.  EKF_ERR_ARG otherwise.  The result does
+ *    not depend on it;
+ *  - ekf_distance_get_grid: of the last run, for measurements: the cells along x, y, z, the entries of all cell lists and the
+ *    longest list (which costs a copy of the counts); every pointer may be NULL;
+ *  - ekf_distance_get_profile: HIP-event milliseconds and launch counts of 9 kinds since the last ekf_fusion_profile:
+ *    k_dist_box ([0]), k_dist_grid ([1]), k_dist_count ([2]), k_dist_offsets ([3]), k_tsdf_scan ([4]), k_dist_fill ([5]),
+ *    k_dist_query ([6]), k_dist_stats ([7]), k_dist_reduce ([8]).  The other profile getters gain nothing. */
+int ekf_distance_set_mesh(ekf_fusion* h, const double* xyz, const unsigned int* faces, unsigned long long n_vert,
+                          unsigned long long n_tri);
+int ekf_distance_run(ekf_fusion* h, int target, int query, unsigned long long* n_points);
+int ekf_distance_run_points(ekf_fusion* h, int target, const double* xyz, unsigned long long n_points);
+int ekf_distance_get(ekf_fusion* h, double* dist, unsigned int* tri, double* closest, signed char* side,
+                     unsigned long long max_points);
+int ekf_distance_get_stats(ekf_fusion* h, double thr, unsigned long long* n, unsigned long long* n_bad, double* max,
+                           unsigned long long* argmax, double* mean, double* rms, unsigned long long* within);
+int ekf_distance_set_grid(ekf_fusion* h, int g);
+int ekf_distance_get_grid(ekf_fusion* h, int* cells, unsigned long long* entries, unsigned int* longest);
+int ekf_distance_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches);
+
 #ifdef __cplusplus
 }
 #endif

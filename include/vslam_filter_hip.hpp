@@ -640,7 +640,9 @@ class DenseStereoHip {
 // simplify() / simplified() / simplifyMap() any of the three with its vertices clustered on a grid of cells (section 28);
 // textureBegin() / textureAddView() / textureAddViewHost() / textureFinish() a per-triangle texture atlas of any of the four,
 // filled from views that are fed one at a time (section 29); setRasterMesh() / rasterise() / rasteriseView() / rastered() any of
-// the four, or a mesh of the caller's, seen from a pose with its vertex colours or that atlas (section 30).
+// the four, or a mesh of the caller's, seen from a pose with its vertex colours or that atlas (section 30); setDistanceMesh() /
+// distance() / distancePoints() / distanceStats() how far the vertices of one of them, or points of the caller's, lie from another
+// (section 31).
 class TsdfVolumeHip {
  public:
   struct Mesh {
@@ -708,6 +710,18 @@ class TsdfVolumeHip {
     std::vector<int> tri;                      // the triangle of the source that the pixel shows, -1: none
     std::vector<float> bary;                   // 2 per pixel: its perspective-correct barycentrics l1, l2
     std::vector<unsigned int> cover;           // the triangles that cover the pixel: rasterise(.., cover = true) only
+  };
+
+  struct MeshDistance {                        // of distance() and distancePoints(): section 31
+    std::vector<double> dist;                  // NaN for a point that is not finite
+    std::vector<unsigned int> tri;             // the nearest triangle of the target, the least index among equally near ones
+    std::vector<double> closest;               // 3 per point: the nearest point on it
+    std::vector<signed char> side;             // the sign of (p - closest) . n of that triangle: +1 is the free-space side of a weld
+    size_t points() const { return dist.size(); }
+  };
+  struct DistanceStats {                       // of distanceStats(): the last run over its finite points, summed in a fixed order
+    unsigned long long n = 0, n_bad = 0, argmax = 0, within = 0;
+    double max = 0.0, mean = 0.0, rms = 0.0;   // max: the one-sided Hausdorff distance
   };
 
   TsdfVolumeHip(int nx, int ny, int nz, const double origin[3], double voxel, double trunc, int device = 0, bool colour = false)
@@ -947,6 +961,41 @@ class TsdfVolumeHip {
   void setRasterSmallLimit(int limit) { check(ekf_raster_set_small_limit(f_, limit)); }
   // HIP-event milliseconds and launch counts of k_rast_project, k_rast_small, k_rast_large, k_rast_resolve
   void getRasterProfile(double kernel_ms[4], long long launches[4]) { check(ekf_raster_get_profile(f_, kernel_ms, launches)); }
+  // Gives the distance a mesh of the caller's (source 4, section 31), for instance a ground truth: xyz 3 per vertex, faces 3 per
+  // triangle.  It is copied to buffers of the distance's own and is independent of setRasterMesh().
+  void setDistanceMesh(const std::vector<double>& xyz, const std::vector<unsigned int>& faces) {
+    check(ekf_distance_set_mesh(f_, xyz.data(), faces.data(), xyz.size() / 3, faces.size() / 3));
+  }
+  // For every vertex of source `query` the nearest point on source `target` (section 31): the last weld() (0), prune() (1),
+  // smooth() (2), simplify() (3) or the mesh of setDistanceMesh() (4); they may be the same.  Both are only read.
+  MeshDistance distance(int target = 0, int query = 3) {
+    unsigned long long n = 0;
+    check(ekf_distance_run(f_, target, query, &n));
+    return distanced((size_t)n);
+  }
+  // the same for points of the caller's, 3 doubles each, at least one
+  MeshDistance distancePoints(int target, const std::vector<double>& xyz) {
+    check(ekf_distance_run_points(f_, target, xyz.data(), xyz.size() / 3));
+    return distanced(xyz.size() / 3);
+  }
+  // the arrays of the last distance() or distancePoints(), which had n points
+  MeshDistance distanced(size_t n) {
+    MeshDistance r;
+    r.dist.resize(n); r.tri.resize(n); r.closest.resize(n * 3); r.side.resize(n);
+    check(ekf_distance_get(f_, r.dist.data(), r.tri.data(), r.closest.data(), r.side.data(), n));
+    return r;
+  }
+  // the last run summed up: the maximum and where, the mean, the RMS and the points with dist <= threshold (>= 0)
+  DistanceStats distanceStats(double threshold = 0.0) {
+    DistanceStats s;
+    check(ekf_distance_get_stats(f_, threshold, &s.n, &s.n_bad, &s.max, &s.argmax, &s.mean, &s.rms, &s.within));
+    return s;
+  }
+  // the cells of the search grid along the longest axis of the target's box: 1..128, 0 = automatic; the result does not depend on it
+  void setDistanceGrid(int g) { check(ekf_distance_set_grid(f_, g)); }
+  // HIP-event milliseconds and launch counts of k_dist_box, k_dist_grid, k_dist_count, k_dist_offsets, k_tsdf_scan, k_dist_fill,
+  // k_dist_query, k_dist_stats, k_dist_reduce
+  void getDistanceProfile(double kernel_ms[9], long long launches[9]) { check(ekf_distance_get_profile(f_, kernel_ms, launches)); }
   // The volume seen by a width x height pinhole camera K = (fx, fy, cx, cy) at pose7: samples of the camera-z depth at
   // z_near + n step up to z_far over the voxels with at least min_count maps.  The mesh of the last extract stays valid.
   Render raycast(int width, int height, const double K[4], const double pose7[7], double z_near, double z_far, double step,
