@@ -5870,6 +5870,7 @@ int ekf_dense_get_speckle_profile(const ekf_dense* h, double* kernel_ms, long lo
 struct ekf_fusion {
   ekf::TsdfFusion* impl;
   ekf::TsdfRaycast rc;                // the last render of the volume (ekf_raycast_*)
+  ekf::MeshStamps stamps;             // which mesh is which, and what is still made from it
   ekf::TsdfMesh mesh;                 // the last weld of the volume's mesh (ekf_mesh_*)
   ekf::TsdfComponents comp;           // that weld's components and its pruned copy
   ekf::TsdfSmooth smooth;             // the smoothed copy of either of them
@@ -6155,16 +6156,22 @@ int ekf_fusion_profile(ekf_fusion* h, int enable) {
   return EKF_OK;
 }
 
-int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+// What the getters of a profile of the fusion handle share: `read` is the timer's read of its kinds.
+extern "C++" {
+template <class Read>
+static int fusion_profile(const ekf_fusion* h, const double* kernel_ms, const long long* launches, Read read) {
   if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->impl->timer.read(kernel_ms, launches, 0, 4);
+  read();
   return EKF_OK;
+}
+}
+
+int ekf_fusion_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
+  return fusion_profile(h, kernel_ms, launches, [&] { h->impl->timer.read(kernel_ms, launches, 0, 4); });
 }
 
 int ekf_colour_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->impl->timer.read(kernel_ms, launches, 6, 3);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->impl->timer.read(kernel_ms, launches, 6, 3); });
 }
 
 // ---- ray casting of the volume ---------------------------------------------------------------------------
@@ -6265,9 +6272,7 @@ int ekf_colour_get_render(ekf_fusion* h, unsigned char* bgr) {
 }
 
 int ekf_raycast_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->impl->timer.read(kernel_ms, launches, 4, 2);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->impl->timer.read(kernel_ms, launches, 4, 2); });
 }
 
 // ---- the welded mesh of the volume and its vertex normals -------------------------------------------------
@@ -6280,19 +6285,69 @@ int ekf_mesh_weld(ekf_fusion* h, int min_count, int normals, unsigned long long*
   }
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->mesh.weld(*f, min_count, normals != 0));
+  HIPCHK(h->mesh.weld(h->stamps, *f, min_count, normals != 0));
   *n_vert = h->mesh.out.n_vert;
   *n_tri = h->mesh.out.n_tri;
   return EKF_OK;
 }
 
-// The arrays of `m` to the caller's, for the three getters of an indexed mesh, behind their own checks: at most max_vert
-// vertices and max_tri triangles; a NULL array is skipped, and so is every array of a count of 0.
-static int mesh_copy_out(ekf_fusion* h, const ekf::MeshView& m, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr,
-                         float* normal, unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
-  std::string& err = h->impl->err;
+// Which mesh `source` (0 the weld, 1 the pruned, 2 the smoothed, 3 the simplified mesh) means now, for every entry point that
+// takes a source: EKF_OK with its view, or EKF_ERR_STATE with the message set.  The message, `who` and ": " before it:
+//
+//   source | no weld since the volume last changed              | a current weld, but not the source's own mesh
+//   -------+----------------------------------------------------+------------------------------------------------------------------
+//     0    | no ekf_mesh_weld since the volume last changed     | -
+//     1    | no ekf_mesh_weld since the volume last changed     | source 1 needs an ekf_components_prune since the last ekf_mesh_weld
+//     2    | no ekf_mesh_weld since the volume last changed     | source 2 needs an ekf_smooth_run on the current mesh
+//     3    | source 3 needs an ekf_simplify_run on the current mesh, in both columns: source 3 never speaks of the weld
+//
+// A source's own mesh is current by the one rule of ekf_mesh_stamp.hpp, so "not the source's own mesh" covers a mesh never
+// made, a failed attempt, and a mesh whose own source has been made again since.
+static int mesh_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* out) {
+  static const char* const kNeeds[4] = {nullptr, ": source 1 needs an ekf_components_prune since the last ekf_mesh_weld",
+                                        ": source 2 needs an ekf_smooth_run on the current mesh",
+                                        ": source 3 needs an ekf_simplify_run on the current mesh"};
+  auto* f = h->impl;
+  const ekf::MeshStamps& st = h->stamps;
+  const unsigned long long id = st.current(source, f->changes);
+  if (id == 0) {
+    const bool welded = st.current(0, f->changes) != 0;
+    f->err = std::string(who) + (source != 3 && !welded ? ": no ekf_mesh_weld since the volume last changed" : kNeeds[source]);
+    return EKF_ERR_STATE;
+  }
+  switch (source) {
+    case 0: *out = ekf::MeshView::of(h->mesh.out, id); break;
+    case 1: *out = ekf::MeshView::of(h->comp.out, id); break;
+    case 2: *out = h->smooth.result(st.smooth.from == 0 ? h->mesh.out : h->comp.out, id); break;   // the run's source says which
+    default: *out = ekf::MeshView::of(h->simp.out, id); break;
+  }
+  return EKF_OK;
+}
+
+// The four getters of an indexed mesh: the rows of `source` to the caller's arrays, at most max_vert vertices and max_tri
+// triangles; a NULL array is skipped, and so is every array of a count of 0.  `none` and `no_normals` end the two messages
+// that differ from getter to getter.
+static int mesh_get(ekf_fusion* h, const char* who, int source, const char* none, const char* no_normals, double* xyz, unsigned* faces,
+                    unsigned char* grey, unsigned char* bgr, float* normal, unsigned long long* key, unsigned long long max_vert,
+                    unsigned long long max_tri) {
+  if (!h) return EKF_ERR_ARG;
+  auto* f = h->impl;
+  std::string& err = f->err;
+  if (bgr && !f->colour) {
+    err = std::string(who) + ": bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
+    return EKF_ERR_ARG;
+  }
+  ekf::MeshView m;                                         // of a smoothed mesh faces, key, grey and bgr are the source's own buffers
+  if (mesh_source(h, who, source, &m) != EKF_OK) {
+    err = std::string(who) + none;
+    return EKF_ERR_STATE;
+  }
+  if (normal && !m.has_normals) {
+    err = std::string(who) + ": normal must be NULL after " + no_normals;
+    return EKF_ERR_ARG;
+  }
   const size_t nv = (size_t)std::min(m.n_vert, max_vert), nc = (size_t)std::min(m.n_tri, max_tri) * 3;
-  HIPCHK(hipSetDevice(h->impl->device));
+  HIPCHK(hipSetDevice(f->device));
   if (nv > 0) {
     if (xyz) HIPCHK(hipMemcpy(xyz, m.xyz, nv * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (grey) HIPCHK(hipMemcpy(grey, m.grey, nv, hipMemcpyDeviceToHost));
@@ -6306,27 +6361,12 @@ static int mesh_copy_out(ekf_fusion* h, const ekf::MeshView& m, double* xyz, uns
 
 int ekf_mesh_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
                  unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  if (bgr && !f->colour) {
-    f->err = "ekf_mesh_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
-    return EKF_ERR_ARG;
-  }
-  if (!h->mesh.current(*f)) {
-    f->err = "ekf_mesh_get: no ekf_mesh_weld since the volume last changed";
-    return EKF_ERR_STATE;
-  }
-  if (normal && !h->mesh.out.has_normals) {
-    f->err = "ekf_mesh_get: normal must be NULL after an ekf_mesh_weld without normals";
-    return EKF_ERR_ARG;
-  }
-  return mesh_copy_out(h, h->mesh.view(), xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
+  return mesh_get(h, "ekf_mesh_get", 0, ": no ekf_mesh_weld since the volume last changed", "an ekf_mesh_weld without normals", xyz, faces,
+                  grey, bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_mesh_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->mesh.timer.read(kernel_ms, launches, 0, ekf::kMeshKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->mesh.timer.read(kernel_ms, launches, 0, ekf::kMeshKinds); });
 }
 
 // ---- the connected components of the welded mesh and its pruned copy ---------------------------------------
@@ -6337,13 +6377,12 @@ int ekf_components_find(ekf_fusion* h, unsigned long long* n_comp) {
     f->err = "ekf_components_find: n_comp not NULL";
     return EKF_ERR_ARG;
   }
-  if (!h->mesh.current(*f)) {
-    f->err = "ekf_components_find: no ekf_mesh_weld since the volume last changed";
-    return EKF_ERR_STATE;
-  }
+  ekf::MeshView w;
+  const int rc = mesh_source(h, "ekf_components_find", 0, &w);
+  if (rc != EKF_OK) return rc;
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->comp.components(h->mesh, f->colour));
+  HIPCHK(h->comp.components(h->stamps, w, f->colour));
   *n_comp = h->comp.n_comp;
   return EKF_OK;
 }
@@ -6351,7 +6390,7 @@ int ekf_components_find(ekf_fusion* h, unsigned long long* n_comp) {
 int ekf_components_get(ekf_fusion* h, unsigned* label, unsigned* size, unsigned long long max_vert) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
-  if (!h->mesh.current(*f) || !h->comp.have_components(h->mesh)) {
+  if (!h->stamps.has(h->stamps.comp, f->changes)) {
     f->err = "ekf_components_get: no ekf_components_find or ekf_components_prune since the last ekf_mesh_weld";
     return EKF_ERR_STATE;
   }
@@ -6373,13 +6412,12 @@ int ekf_components_prune(ekf_fusion* h, unsigned min_triangles, int largest, uns
     f->err = "ekf_components_prune: min_triangles >= 1, largest 0 or 1, n_vert, n_tri and n_kept not NULL";
     return EKF_ERR_ARG;
   }
-  if (!h->mesh.current(*f)) {
-    f->err = "ekf_components_prune: no ekf_mesh_weld since the volume last changed";
-    return EKF_ERR_STATE;
-  }
+  ekf::MeshView w;
+  const int rc = mesh_source(h, "ekf_components_prune", 0, &w);
+  if (rc != EKF_OK) return rc;
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->comp.prune(h->mesh, f->colour, min_triangles, largest != 0));
+  HIPCHK(h->comp.prune(h->stamps, w, f->colour, min_triangles, largest != 0));
   *n_vert = h->comp.out.n_vert;
   *n_tri = h->comp.out.n_tri;
   *n_kept = h->comp.n_kept;
@@ -6388,56 +6426,20 @@ int ekf_components_prune(ekf_fusion* h, unsigned min_triangles, int largest, uns
 
 int ekf_components_get_pruned(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
                         unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  if (bgr && !f->colour) {
-    f->err = "ekf_components_get_pruned: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
-    return EKF_ERR_ARG;
-  }
-  if (!h->mesh.current(*f) || !h->comp.have_pruned(h->mesh)) {
-    f->err = "ekf_components_get_pruned: no ekf_components_prune since the last ekf_mesh_weld";
-    return EKF_ERR_STATE;
-  }
-  if (normal && !h->comp.out.has_normals) {
-    f->err = "ekf_components_get_pruned: normal must be NULL after an ekf_mesh_weld without normals";
-    return EKF_ERR_ARG;
-  }
-  return mesh_copy_out(h, h->comp.pruned_view(h->mesh), xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
+  return mesh_get(h, "ekf_components_get_pruned", 1, ": no ekf_components_prune since the last ekf_mesh_weld",
+                  "an ekf_mesh_weld without normals", xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_components_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->comp.timer.read(kernel_ms, launches, 0, ekf::kCompKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->comp.timer.read(kernel_ms, launches, 0, ekf::kCompKinds); });
 }
 
 // ---- Taubin smoothing of the welded or the pruned mesh -----------------------------------------------------
-// The mesh a smoothing call is about, if the handle holds it: EKF_OK, or EKF_ERR_STATE with the message set.
-static int smooth_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s) {
-  auto* f = h->impl;
-  if (!h->mesh.current(*f)) {
-    f->err = std::string(who) + ": no ekf_mesh_weld since the volume last changed";
-    return EKF_ERR_STATE;
-  }
-  if (source == 1 && !h->comp.have_pruned(h->mesh)) {
-    f->err = std::string(who) + ": source 1 needs an ekf_components_prune since the last ekf_mesh_weld";
-    return EKF_ERR_STATE;
-  }
-  *s = source == 0 ? h->mesh.view() : h->comp.pruned_view(h->mesh);
-  return EKF_OK;
-}
-
-// The last run's mesh, if the mesh it smoothed is still the handle's: the run's source says which.
+// The last run's mesh, if the mesh it smoothed is still the handle's.
 static int smooth_result(ekf_fusion* h, const char* who, ekf::MeshView* r) {
-  auto* f = h->impl;
-  const ekf::TsdfSmooth& m = h->smooth;
-  ekf::MeshView s;
-  if (!m.res_valid || smooth_source(h, who, m.res.source, &s) != EKF_OK || !m.have_result(s)) {
-    f->err = std::string(who) + ": no ekf_smooth_run on the current mesh";
-    return EKF_ERR_STATE;
-  }
-  *r = m.result(s);
-  return EKF_OK;
+  if (mesh_source(h, who, 2, r) == EKF_OK) return EKF_OK;
+  h->impl->err = std::string(who) + ": no ekf_smooth_run on the current mesh";
+  return EKF_ERR_STATE;
 }
 
 int ekf_smooth_run(ekf_fusion* h, int source, int iterations, double lambda, double mu, int pin_boundary, int normals,
@@ -6452,11 +6454,11 @@ int ekf_smooth_run(ekf_fusion* h, int source, int iterations, double lambda, dou
     return EKF_ERR_ARG;
   }
   ekf::MeshView s;
-  const int rc = smooth_source(h, "ekf_smooth_run", source, &s);
+  const int rc = mesh_source(h, "ekf_smooth_run", source, &s);
   if (rc != EKF_OK) return rc;
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->smooth.run(s, iterations, lambda, mu, pin_boundary != 0, normals != 0));
+  HIPCHK(h->smooth.run(h->stamps, s, source, iterations, lambda, mu, pin_boundary != 0, normals != 0));
   *n_vert = s.n_vert;
   *n_tri = s.n_tri;
   return EKF_OK;
@@ -6464,20 +6466,8 @@ int ekf_smooth_run(ekf_fusion* h, int source, int iterations, double lambda, dou
 
 int ekf_smooth_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
                    unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  if (bgr && !f->colour) {
-    f->err = "ekf_smooth_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
-    return EKF_ERR_ARG;
-  }
-  ekf::MeshView m;                                         // faces, key, grey and bgr are the source's own buffers
-  const int rc = smooth_result(h, "ekf_smooth_get", &m);
-  if (rc != EKF_OK) return rc;
-  if (normal && !m.has_normals) {
-    f->err = "ekf_smooth_get: normal must be NULL after an ekf_smooth_run without normals";
-    return EKF_ERR_ARG;
-  }
-  return mesh_copy_out(h, m, xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
+  return mesh_get(h, "ekf_smooth_get", 2, ": no ekf_smooth_run on the current mesh", "an ekf_smooth_run without normals", xyz, faces, grey,
+                  bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned* inc, unsigned* deg, unsigned char* boundary, unsigned long long max_vert) {
@@ -6498,41 +6488,15 @@ int ekf_smooth_get_adjacency(ekf_fusion* h, unsigned* inc, unsigned* deg, unsign
 }
 
 int ekf_smooth_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->smooth.timer.read(kernel_ms, launches, 0, ekf::kSmoothKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->smooth.timer.read(kernel_ms, launches, 0, ekf::kSmoothKinds); });
 }
 
 // ---- vertex-clustering simplification of the welded, the pruned or the smoothed mesh -----------------------
-// The mesh a simplification is about, if the handle holds it, and for source 2 the number of the smooth run that made it:
-// EKF_OK, or EKF_ERR_STATE with the message set.
-static int simplify_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s, unsigned long long* run) {
-  *run = 0;
-  if (source != 2) return smooth_source(h, who, source, s);
-  auto* f = h->impl;
-  if (!h->mesh.current(*f)) {
-    f->err = std::string(who) + ": no ekf_mesh_weld since the volume last changed";
-    return EKF_ERR_STATE;
-  }
-  if (smooth_result(h, who, s) != EKF_OK) {
-    f->err = std::string(who) + ": source 2 needs an ekf_smooth_run on the current mesh";
-    return EKF_ERR_STATE;
-  }
-  *run = h->smooth.runs;
-  return EKF_OK;
-}
-
-// Whether the last run's result is still that of the handle's meshes: its source says which.
+// Whether the last run's result is still that of the handle's meshes.
 static int simplify_result(ekf_fusion* h, const char* who) {
-  auto* f = h->impl;
-  const ekf::TsdfSimplify& m = h->simp;
-  ekf::MeshView s;
-  unsigned long long run = 0;
-  if (!m.valid || simplify_source(h, who, m.from, &s, &run) != EKF_OK || !m.have_result(m.from, s, run)) {
-    f->err = std::string(who) + ": no ekf_simplify_run on the current mesh";
-    return EKF_ERR_STATE;
-  }
-  return EKF_OK;
+  if (h->stamps.current(3, h->impl->changes) != 0) return EKF_OK;
+  h->impl->err = std::string(who) + ": no ekf_simplify_run on the current mesh";
+  return EKF_ERR_STATE;
 }
 
 int ekf_simplify_run(ekf_fusion* h, int source, double cell, unsigned long long* n_vert, unsigned long long* n_tri,
@@ -6544,12 +6508,11 @@ int ekf_simplify_run(ekf_fusion* h, int source, double cell, unsigned long long*
     return EKF_ERR_ARG;
   }
   ekf::MeshView s;
-  unsigned long long run = 0;
-  const int rc = simplify_source(h, "ekf_simplify_run", source, &s, &run);
+  const int rc = mesh_source(h, "ekf_simplify_run", source, &s);
   if (rc != EKF_OK) return rc;
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->simp.run(s, source, run, f->g, cell, f->colour));
+  HIPCHK(h->simp.run(h->stamps, s, source, f->g, cell, f->colour));
   *n_vert = h->simp.out.n_vert;
   *n_tri = h->simp.out.n_tri;
   *n_degenerate = h->simp.n_degenerate;
@@ -6559,20 +6522,8 @@ int ekf_simplify_run(ekf_fusion* h, int source, double cell, unsigned long long*
 
 int ekf_simplify_get(ekf_fusion* h, double* xyz, unsigned* faces, unsigned char* grey, unsigned char* bgr, float* normal,
                      unsigned long long* key, unsigned long long max_vert, unsigned long long max_tri) {
-  if (!h) return EKF_ERR_ARG;
-  auto* f = h->impl;
-  if (bgr && !f->colour) {
-    f->err = "ekf_simplify_get: bgr must be NULL on a plain volume (ekf_colour_create makes a colour volume)";
-    return EKF_ERR_ARG;
-  }
-  const int rc = simplify_result(h, "ekf_simplify_get");
-  if (rc != EKF_OK) return rc;
-  if (normal && !h->simp.out.has_normals) {
-    f->err = "ekf_simplify_get: normal must be NULL after an ekf_simplify_run on a source without normals";
-    return EKF_ERR_ARG;
-  }
-  return mesh_copy_out(h, ekf::MeshView::of(h->simp.out, h->simp.from, h->simp.src.serial, h->simp.src.prune), xyz, faces, grey, bgr, normal,
-                       key, max_vert, max_tri);
+  return mesh_get(h, "ekf_simplify_get", 3, ": no ekf_simplify_run on the current mesh", "an ekf_simplify_run on a source without normals",
+                  xyz, faces, grey, bgr, normal, key, max_vert, max_tri);
 }
 
 int ekf_simplify_get_map(ekf_fusion* h, unsigned* map, unsigned long long max_vert) {
@@ -6588,38 +6539,15 @@ int ekf_simplify_get_map(ekf_fusion* h, unsigned* map, unsigned long long max_ve
 }
 
 int ekf_simplify_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->simp.timer.read(kernel_ms, launches, 0, ekf::kSimpKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->simp.timer.read(kernel_ms, launches, 0, ekf::kSimpKinds); });
 }
 
 // ---- a per-triangle texture atlas of the welded, the pruned, the smoothed or the simplified mesh ------------
-// The mesh a texture is about, if the handle holds it, and the number of the smooth run (2) or the simplify run (3) that made
-// it: EKF_OK, or EKF_ERR_STATE with the message set.
-static int texture_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s, unsigned long long* run) {
-  if (source != 3) return simplify_source(h, who, source, s, run);
-  const int rc = simplify_result(h, who);
-  if (rc != EKF_OK) {
-    h->impl->err = std::string(who) + ": source 3 needs an ekf_simplify_run on the current mesh";
-    return rc;
-  }
-  *s = ekf::MeshView::of(h->simp.out, 3, h->simp.src.serial, h->simp.src.prune);
-  *run = h->simp.runs;
-  return EKF_OK;
-}
-
-// Whether the texture begun last is still that of the handle's meshes: its source says which.
+// Whether the texture begun last is still that of the handle's meshes.
 static int texture_current(ekf_fusion* h, const char* who) {
-  auto* f = h->impl;
-  const ekf::TsdfTexture& m = h->tex;
-  ekf::MeshView s;
-  unsigned long long run = 0;
-  if (!m.begun || texture_source(h, who, m.from, &s, &run) != EKF_OK || !ekf::TsdfSmooth::same(m.src, s) ||
-      (m.from >= 2 && m.run_id != run)) {
-    f->err = std::string(who) + ": no ekf_texture_begin on the current mesh";
-    return EKF_ERR_STATE;
-  }
-  return EKF_OK;
+  if (h->stamps.has(h->stamps.tex, h->impl->changes)) return EKF_OK;
+  h->impl->err = std::string(who) + ": no ekf_texture_begin on the current mesh";
+  return EKF_ERR_STATE;
 }
 
 int ekf_texture_begin(ekf_fusion* h, int source, int patch, int channels, int* atlas_side) {
@@ -6631,8 +6559,7 @@ int ekf_texture_begin(ekf_fusion* h, int source, int patch, int channels, int* a
     return EKF_ERR_ARG;
   }
   ekf::MeshView s;
-  unsigned long long run = 0;
-  const int rc = texture_source(h, "ekf_texture_begin", source, &s, &run);
+  const int rc = mesh_source(h, "ekf_texture_begin", source, &s);
   if (rc != EKF_OK) return rc;
   if (s.n_tri == 0) {
     f->err = "ekf_texture_begin: the source mesh has no triangle";
@@ -6647,7 +6574,7 @@ int ekf_texture_begin(ekf_fusion* h, int source, int patch, int channels, int* a
   }
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->tex.begin(s, source, run, patch, channels, f->colour && channels == 3));
+  HIPCHK(h->tex.begin(h->stamps, s, source, patch, channels, f->colour && channels == 3));
   *atlas_side = (int)A;
   return EKF_OK;
 }
@@ -6787,32 +6714,35 @@ int ekf_texture_get(ekf_fusion* h, unsigned char* atlas, int pitch, double* uv, 
 }
 
 int ekf_texture_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->tex.timer.read(kernel_ms, launches, 0, ekf::kTexKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->tex.timer.read(kernel_ms, launches, 0, ekf::kTexKinds); });
 }
 
 // ---- a rasteriser for the indexed meshes: depth, triangle, barycentric, normal and shaded images ------------
+// What both ekf_*_set_mesh ask of the caller's rows (each says so in its own words).
+static bool caller_mesh_ok(const double* xyz, const unsigned* faces, unsigned long long n_vert, unsigned long long n_tri) {
+  bool ok = xyz && faces && n_vert > 0 && n_vert <= 0xffffffffull && n_tri > 0 && n_tri <= 0xffffffffull;
+  for (unsigned long long i = 0; ok && i < n_vert * 3; ++i) ok = std::isfinite(xyz[i]);
+  for (unsigned long long i = 0; ok && i < n_tri * 3; ++i) ok = faces[i] < n_vert;
+  return ok;
+}
+
 int ekf_raster_set_mesh(ekf_fusion* h, const double* xyz, const unsigned* faces, const unsigned char* grey, const unsigned char* bgr,
                         unsigned long long n_vert, unsigned long long n_tri) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
-  bool ok = xyz && faces && grey && n_vert > 0 && n_vert <= 0xffffffffull && n_tri > 0 && n_tri <= 0xffffffffull;
-  for (unsigned long long i = 0; ok && i < n_vert * 3; ++i) ok = std::isfinite(xyz[i]);
-  for (unsigned long long i = 0; ok && i < n_tri * 3; ++i) ok = faces[i] < n_vert;
-  if (!ok) {
+  if (!grey || !caller_mesh_ok(xyz, faces, n_vert, n_tri)) {
     f->err = "ekf_raster_set_mesh: xyz, faces and grey not NULL; 0 < n_vert, n_tri < 2^32; xyz finite; every index < n_vert";
     return EKF_ERR_ARG;
   }
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->rast.set_mesh(xyz, faces, grey, bgr, (size_t)n_vert, (size_t)n_tri));
+  HIPCHK(h->rast.own.upload(xyz, faces, grey, bgr, (size_t)n_vert, (size_t)n_tri));
   return EKF_OK;
 }
 
 // Everything of a render but the view: EKF_OK with the source's arrays and, for shading 1, the atlas; otherwise the status with
 // the message set.  Arguments first, then the state.
-static int raster_source(ekf_fusion* h, const char* who, int source, double z_near, int cull, int shading, int cover, ekf::RastMesh* s,
+static int raster_source(ekf_fusion* h, const char* who, int source, double z_near, int cull, int shading, int cover, ekf::MeshView* s,
                          ekf::RastAtlas* atlas) {
   auto* f = h->impl;
   if (source < 0 || source > 4 || !std::isfinite(z_near) || z_near < 0.0 || (cull != 0 && cull != 1) || (shading != 0 && shading != 1) ||
@@ -6825,26 +6755,23 @@ static int raster_source(ekf_fusion* h, const char* who, int source, double z_ne
     return EKF_ERR_ARG;
   }
   if (source == 4) {
-    if (!h->rast.m_set) {
+    if (!h->rast.own.set) {
       f->err = std::string(who) + ": source 4 needs an ekf_raster_set_mesh";
       return EKF_ERR_STATE;
     }
-    *s = h->rast.own_mesh();
+    *s = h->rast.own.view();
     return EKF_OK;
   }
-  ekf::MeshView m;
-  unsigned long long run = 0;
-  const int rc = texture_source(h, who, source, &m, &run);
+  const int rc = mesh_source(h, who, source, s);
   if (rc != EKF_OK) return rc;
-  if (m.n_tri == 0) {
+  if (s->n_tri == 0) {
     f->err = std::string(who) + ": the source mesh has no triangle";
     return EKF_ERR_STATE;
   }
-  s->xyz = m.xyz; s->faces = m.faces; s->grey = m.grey; s->bgr = f->colour ? m.bgr : nullptr;
-  s->n_vert = m.n_vert; s->n_tri = m.n_tri;
+  if (!f->colour) s->bgr = nullptr;
   if (shading == 1) {
     const ekf::TsdfTexture& t = h->tex;
-    if (texture_current(h, who) != EKF_OK || !t.finished || t.from != source) {
+    if (texture_current(h, who) != EKF_OK || !t.finished || h->stamps.tex.from != source) {
       f->err = std::string(who) + ": shading 1 needs a finished texture (ekf_texture_finish) of the source that is rendered";
       return EKF_ERR_STATE;
     }
@@ -6863,7 +6790,7 @@ int ekf_raster_render(ekf_fusion* h, int source, int width, int height, const do
     f->err = "ekf_raster_render: 1 <= width, height <= 8192; K finite with fx, fy != 0; pose7 finite with q != 0";
     return EKF_ERR_ARG;
   }
-  ekf::RastMesh s;
+  ekf::MeshView s;
   ekf::RastAtlas atlas;
   const int rc = raster_source(h, "ekf_raster_render", source, z_near, cull, shading, cover, &s, &atlas);
   if (rc != EKF_OK) return rc;
@@ -6885,7 +6812,7 @@ int ekf_raster_render_view(ekf_fusion* h, int source, ekf_dense* dense, int slot
     f->err = "ekf_raster_render_view: slot in 0..max_views-1";
     return EKF_ERR_ARG;
   }
-  ekf::RastMesh s;
+  ekf::MeshView s;
   ekf::RastAtlas atlas;
   const int rc = raster_source(h, "ekf_raster_render_view", source, z_near, cull, shading, cover, &s, &atlas);
   if (rc != EKF_OK) return rc;
@@ -6939,53 +6866,40 @@ int ekf_raster_set_small_limit(ekf_fusion* h, int limit) {
 }
 
 int ekf_raster_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->rast.timer.read(kernel_ms, launches, 0, ekf::kRastKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->rast.timer.read(kernel_ms, launches, 0, ekf::kRastKinds); });
 }
 
 // ---- a mesh-to-mesh distance: the nearest triangle of a target mesh for every query point ---------------------
 int ekf_distance_set_mesh(ekf_fusion* h, const double* xyz, const unsigned* faces, unsigned long long n_vert, unsigned long long n_tri) {
   if (!h) return EKF_ERR_ARG;
   auto* f = h->impl;
-  bool ok = xyz && faces && n_vert > 0 && n_vert <= 0xffffffffull && n_tri > 0 && n_tri <= 0xffffffffull;
-  for (unsigned long long i = 0; ok && i < n_vert * 3; ++i) ok = std::isfinite(xyz[i]);
-  for (unsigned long long i = 0; ok && i < n_tri * 3; ++i) ok = faces[i] < n_vert;
-  if (!ok) {
+  if (!caller_mesh_ok(xyz, faces, n_vert, n_tri)) {
     f->err = "ekf_distance_set_mesh: xyz and faces not NULL; 0 < n_vert, n_tri < 2^32; xyz finite; every index < n_vert";
     return EKF_ERR_ARG;
   }
   std::string& err = f->err;
   HIPCHK(hipSetDevice(f->device));
-  HIPCHK(h->dist.set_mesh(xyz, faces, (size_t)n_vert, (size_t)n_tri));
+  HIPCHK(h->dist.own.upload(xyz, faces, nullptr, nullptr, (size_t)n_vert, (size_t)n_tri));
   return EKF_OK;
 }
 
 // The rows of a source as the distance reads them: EKF_OK, or EKF_ERR_STATE with the message set.
-static int distance_source(ekf_fusion* h, const char* who, int source, ekf::RastMesh* s) {
-  auto* f = h->impl;
-  if (source == 4) {
-    if (!h->dist.m_set) {
-      f->err = std::string(who) + ": source 4 needs an ekf_distance_set_mesh";
-      return EKF_ERR_STATE;
-    }
-    s->xyz = h->dist.m_xyz; s->faces = h->dist.m_faces; s->n_vert = h->dist.m_vert; s->n_tri = h->dist.m_tri;
-    return EKF_OK;
+static int distance_source(ekf_fusion* h, const char* who, int source, ekf::MeshView* s) {
+  if (source != 4) return mesh_source(h, who, source, s);
+  if (!h->dist.own.set) {
+    h->impl->err = std::string(who) + ": source 4 needs an ekf_distance_set_mesh";
+    return EKF_ERR_STATE;
   }
-  ekf::MeshView m;
-  unsigned long long run = 0;
-  const int rc = texture_source(h, who, source, &m, &run);
-  if (rc != EKF_OK) return rc;
-  s->xyz = m.xyz; s->faces = m.faces; s->n_vert = m.n_vert; s->n_tri = m.n_tri;
+  *s = h->dist.own.view();
   return EKF_OK;
 }
 
 // The target of a run, then the run: what the two entry points share.  pts: the query's rows on the device.
-static int distance_run(ekf_fusion* h, const char* who, const ekf::RastMesh& t, const double* pts, unsigned long long n) {
+static int distance_run(ekf_fusion* h, const char* who, const ekf::MeshView& t, const double* pts, unsigned long long n) {
   auto* f = h->impl;
   std::string& err = f->err;
   ekf::TsdfDistance::Status st;
-  HIPCHK(h->dist.run(t.xyz, t.faces, t.n_tri, pts, n, &st));
+  HIPCHK(h->dist.run(t, pts, n, &st));
   if (st == ekf::TsdfDistance::kNoValid) {
     f->err = std::string(who) + ": the target mesh has no valid triangle";
     return EKF_ERR_STATE;
@@ -6997,7 +6911,7 @@ static int distance_run(ekf_fusion* h, const char* who, const ekf::RastMesh& t, 
   return EKF_OK;
 }
 
-static int distance_target(ekf_fusion* h, const char* who, int target, ekf::RastMesh* t) {
+static int distance_target(ekf_fusion* h, const char* who, int target, ekf::MeshView* t) {
   const int rc = distance_source(h, who, target, t);
   if (rc != EKF_OK) return rc;
   if (t->n_tri == 0) {
@@ -7014,7 +6928,7 @@ int ekf_distance_run(ekf_fusion* h, int target, int query, unsigned long long* n
     f->err = "ekf_distance_run: target and query 0..4";
     return EKF_ERR_ARG;
   }
-  ekf::RastMesh t, q;
+  ekf::MeshView t, q;
   int rc = distance_target(h, "ekf_distance_run", target, &t);
   if (rc != EKF_OK) return rc;
   if ((rc = distance_source(h, "ekf_distance_run", query, &q)) != EKF_OK) return rc;
@@ -7036,7 +6950,7 @@ int ekf_distance_run_points(ekf_fusion* h, int target, const double* xyz, unsign
     f->err = "ekf_distance_run_points: target 0..4; xyz not NULL; 0 < n_points < 2^32";
     return EKF_ERR_ARG;
   }
-  ekf::RastMesh t;
+  ekf::MeshView t;
   const int rc = distance_target(h, "ekf_distance_run_points", target, &t);
   if (rc != EKF_OK) return rc;
   std::string& err = f->err;
@@ -7127,9 +7041,7 @@ int ekf_distance_get_grid(ekf_fusion* h, int* cells, unsigned long long* entries
 }
 
 int ekf_distance_get_profile(const ekf_fusion* h, double* kernel_ms, long long* launches) {
-  if (!h || !kernel_ms || !launches) return EKF_ERR_ARG;
-  h->dist.timer.read(kernel_ms, launches, 0, ekf::kDistKinds);
-  return EKF_OK;
+  return fusion_profile(h, kernel_ms, launches, [&] { h->dist.timer.read(kernel_ms, launches, 0, ekf::kDistKinds); });
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 // EKF_KERNELS_ONLY: the structs and the kernel bodies alone, for tools/mesh_host_check.cpp, which runs the kernels lane by
 // lane on the host; tools/host_kernels.hpp supplies threadIdx, __syncthreads and the like.
 #include "ekf_fusion.hpp"
+#include "ekf_mesh_stamp.hpp"
 
 namespace ekf {
 
@@ -212,26 +213,62 @@ __global__ void __launch_bounds__(256) k_mesh_faces(MeshArgs a) {
 }
 
 #ifndef EKF_KERNELS_ONLY
-// An indexed mesh on the device as whoever reads it sees it: the six arrays, the counts, and which mesh it is.  `source` 0 is
-// the last weld and 1 the last pruned mesh (ekf_mesh_components.hpp); `serial` counts the welds and `prune` the prunes, so the
-// three name one mesh.  A view owns nothing and holds as long as its mesh does.
+// An indexed mesh on the device as whoever reads it sees it: the six arrays, the counts, and `id`, the stamp that names the mesh
+// (ekf_mesh_stamp.hpp; 0 for a mesh the caller gave).  A view owns nothing and holds as long as its mesh does.
 struct MeshView {
   const double* xyz = nullptr;
   const unsigned long long* key = nullptr;
   const unsigned char* grey = nullptr;
-  const unsigned char* bgr = nullptr;            // of a colour volume only
+  const unsigned char* bgr = nullptr;            // of a colour volume only; NULL: the mesh has no B, G, R
   const float* normal = nullptr;                 // to be read with has_normals only
   const unsigned* faces = nullptr;
   unsigned long long n_vert = 0, n_tri = 0;
   bool has_normals = false;
-  int source = 0;
-  unsigned long long serial = 0, prune = 0;
+  unsigned long long id = 0;
 
-  static MeshView of(const DevMeshBufs& b, int source, unsigned long long serial, unsigned long long prune) {
+  static MeshView of(const DevMeshBufs& b, unsigned long long id) {
     MeshView v;
     v.xyz = b.xyz; v.key = b.key; v.grey = b.grey; v.bgr = b.bgr; v.normal = b.normal; v.faces = b.faces;
     v.n_vert = b.n_vert; v.n_tri = b.n_tri; v.has_normals = b.has_normals;
-    v.source = source; v.serial = serial; v.prune = prune;
+    v.id = id;
+    return v;
+  }
+};
+
+// A mesh the caller gave: source 4 of the rasteriser and of the distance, each with one of its own.  grey and bgr are optional.
+struct CallerMesh {
+  DevBuf<double> xyz;
+  DevBuf<unsigned> faces;
+  DevBuf<unsigned char> grey, bgr;
+  unsigned long long n_vert = 0, n_tri = 0;
+  bool set = false, colour = false;
+
+  // New rows beside the old ones, which they replace only when all of them exist.
+  hipError_t upload(const double* x, const unsigned* f, const unsigned char* g, const unsigned char* c, size_t nv, size_t nt) {
+    hipError_t e;
+    DevBuf<double> nx;
+    DevBuf<unsigned> nf;
+    DevBuf<unsigned char> ng, nc;
+    if ((e = nx.reserve(std::max(nv * 3, xyz.capacity()))) != hipSuccess || (e = nf.reserve(std::max(nt * 3, faces.capacity()))) != hipSuccess ||
+        (g && (e = ng.reserve(std::max(nv, grey.capacity()))) != hipSuccess) || (c && (e = nc.reserve(std::max(nv * 3, bgr.capacity()))) != hipSuccess)) {
+      (void)hipGetLastError();
+      return e;
+    }
+    if ((e = hipMemcpy(nx, x, nv * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return e;
+    if ((e = hipMemcpy(nf, f, nt * 3 * sizeof(unsigned), hipMemcpyHostToDevice)) != hipSuccess) return e;
+    if (g && (e = hipMemcpy(ng, g, nv, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    if (c && (e = hipMemcpy(nc, c, nv * 3, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    xyz = std::move(nx); faces = std::move(nf);
+    if (g) grey = std::move(ng);
+    if (c) bgr = std::move(nc);
+    n_vert = nv; n_tri = nt; colour = c != nullptr; set = true;
+    return hipSuccess;
+  }
+
+  MeshView view() const {
+    MeshView v;
+    v.xyz = xyz; v.faces = faces; v.grey = grey; v.bgr = colour ? (const unsigned char*)bgr : nullptr;
+    v.n_vert = n_vert; v.n_tri = n_tri;
     return v;
   }
 };
@@ -244,18 +281,12 @@ struct TsdfMesh {
   DevBuf<unsigned> code, blk_tot;
   DevBuf<unsigned long long> blk_off;
   DevMeshBufs out;                               // the welded mesh; bgr: colour volumes only, normal: welds with normals only
-  unsigned long long weld_changes = 0;           // TsdfFusion::changes when the weld was made
-  unsigned long long serial = 0;                 // counts the welds: what ekf_mesh_components.hpp derives from one names it
-  bool valid = false;
   KernelTimer<kMeshKinds> timer;
-
-  bool current(const TsdfFusion& f) const { return valid && weld_changes == f.changes; }
-  MeshView view() const { return MeshView::of(out, 0, serial, 0); }
 
   // (extract, unless the handle holds the soup of this min_count) -> cells -> edges -> scan -> one 8-byte read-back -> (grow
   // the mesh buffers) -> vertices -> faces.  A failed allocation leaves the soup and the volume as they were; the previous
   // weld is lost only when its scratch had to grow.
-  hipError_t weld(TsdfFusion& f, int min_count, bool normals) {
+  hipError_t weld(MeshStamps& st, TsdfFusion& f, int min_count, bool normals) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
     if (!f.mesh_valid || f.mesh_count != min_count) {
@@ -263,8 +294,7 @@ struct TsdfMesh {
     }
     const unsigned nvox = (unsigned)f.nvox(), nc = f.ncell();
     const unsigned vblk = fusion_blocks(nvox), cblk = fusion_blocks(nc);
-    valid = false;
-    ++serial;
+    st.begin(st.weld);
     if ((e = cell_ok.reserve(nc)) != hipSuccess || (e = code.reserve(nvox)) != hipSuccess || (e = blk_tot.reserve(vblk)) != hipSuccess ||
         (e = blk_off.reserve((size_t)vblk + 1)) != hipSuccess) {
       (void)hipGetLastError();
@@ -298,8 +328,8 @@ struct TsdfMesh {
     out.n_vert = total;
     out.n_tri = f.n_tri;
     out.has_normals = normals;
-    weld_changes = f.changes;
-    valid = true;
+    st.weld_changes = f.changes;
+    st.weld.valid = true;
     return hipSuccess;
   }
 };

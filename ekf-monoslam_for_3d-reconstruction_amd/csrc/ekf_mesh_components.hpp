@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(256) k_comp_faces(CompArgs a) {
 
 #ifndef EKF_KERNELS_ONLY
 // Host side: the scratch, the labels and sizes of the last weld's components and the pruned copy of that weld, owned by the
-// fusion handle beside its TsdfMesh; allocated by the first call that needs them, grow-only.  `serial` of the TsdfMesh says
+// fusion handle beside its TsdfMesh; allocated by the first call that needs them, grow-only.  The handle's MeshStamps say
 // which weld they belong to.  A timer of its own, so that the four other getters count what they counted.
 struct TsdfComponents {
   DevBuf<unsigned> L, R, S, V, T, blk_tot, n_roots;
@@ -287,14 +287,7 @@ struct TsdfComponents {
   DevMeshBufs out;                                             // the pruned mesh
   unsigned long long n_comp = 0;                               // of the components
   unsigned long long n_kept = 0;                               // of the pruned mesh
-  unsigned long long comp_serial = 0, prune_serial = 0;
-  unsigned long long prunes = 0;                               // counts the prunes: what ekf_mesh_smooth.hpp derives from one names it
-  bool comp_valid = false, prune_valid = false;
   KernelTimer<kCompKinds> timer;
-
-  bool have_components(const TsdfMesh& w) const { return comp_valid && comp_serial == w.serial; }
-  bool have_pruned(const TsdfMesh& w) const { return prune_valid && prune_serial == w.serial; }
-  MeshView pruned_view(const TsdfMesh& w) const { return MeshView::of(out, 1, w.serial, prunes); }
 
   // three rows of offsets, each ending at the last word of its row of `pitch` words, so that the totals stand one pitch apart
   static size_t pitch(unsigned vblk, unsigned tblk) { return (size_t)std::max(vblk, tblk) + 1; }
@@ -318,11 +311,10 @@ struct TsdfComponents {
 
   // init -> union -> count -> (flags, for the sizes in L, unless a prune follows, whose own flags leave them there) -> one
   // 4-byte read-back.  No launch for a weld without triangles.
-  hipError_t components(const TsdfMesh& w, bool colour, bool with_sizes = true) {
+  hipError_t components(MeshStamps& st, const MeshView& m, bool colour, bool with_sizes = true) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
-    comp_valid = prune_valid = false;
-    const MeshView m = w.view();
+    st.comp.valid = st.pruned.valid = false;
     if (m.n_tri > 0) {
       const size_t nv = (size_t)m.n_vert, nt = (size_t)m.n_tri;
       const unsigned vblk = fusion_blocks(m.n_vert), tblk = fusion_blocks(m.n_tri);
@@ -344,19 +336,16 @@ struct TsdfComponents {
     } else {
       n_comp = 0;
     }
-    comp_serial = m.serial;
-    comp_valid = true;
+    st.made(st.comp, m.id, 0);
     return hipSuccess;
   }
 
   // (components, unless the handle holds them for this weld) -> (largest) -> flags -> three scans -> one read-back of the three
   // totals -> (grow the pruned mesh's buffers) -> vertices -> faces.  The weld is only read.
-  hipError_t prune(const TsdfMesh& w, bool colour, unsigned min_triangles, bool largest) {
+  hipError_t prune(MeshStamps& st, const MeshView& m, bool colour, unsigned min_triangles, bool largest) {
     hipError_t e;
-    if (!have_components(w) && (e = components(w, colour, false)) != hipSuccess) return e;
-    prune_valid = false;
-    ++prunes;
-    const MeshView m = w.view();
+    if (!st.comp.made_from(m.id) && (e = components(st, m, colour, false)) != hipSuccess) return e;
+    st.begin(st.pruned);
     unsigned long long totals[3] = {0, 0, 0};
     if (m.n_tri > 0) {
       const unsigned vblk = fusion_blocks(m.n_vert), tblk = fusion_blocks(m.n_tri);
@@ -366,7 +355,7 @@ struct TsdfComponents {
       a.largest = largest ? 1 : 0;
       if (largest && (e = timer.run(3, [&] { k_comp_largest<<<vblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
       if ((e = timer.run(4, [&] { k_comp_flags<<<vblk + tblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) {
-        comp_valid = false;             // L may not hold the sizes
+        st.comp.valid = false;          // L may not hold the sizes
         return e;
       }
       unsigned long long* off_r = off + 2 * P + (P - 1 - vblk);
@@ -389,8 +378,7 @@ struct TsdfComponents {
     out.n_tri = totals[1];
     n_kept = totals[2];
     out.has_normals = m.has_normals;
-    prune_serial = m.serial;
-    prune_valid = true;
+    st.made(st.pruned, m.id, 0);
     return hipSuccess;
   }
 };

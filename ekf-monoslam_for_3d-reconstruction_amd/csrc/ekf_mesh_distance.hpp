@@ -555,10 +555,7 @@ inline unsigned dist_auto_g(double n_valid) {
 // Host side: the grid, the outputs and the statistics of the distance, owned by the fusion handle beside its TsdfRaster;
 // grow-only.  The sources are only read.  A timer of its own, so that the other getters count what they counted.
 struct TsdfDistance {
-  DevBuf<double> m_xyz;                          // source 4: the mesh ekf_distance_set_mesh was given
-  DevBuf<unsigned> m_faces;
-  unsigned long long m_vert = 0, m_tri = 0;
-  bool m_set = false;
+  CallerMesh own;                                // source 4: the mesh ekf_distance_set_mesh was given
   DevBuf<double> q_xyz;                          // the host's points of the last ekf_distance_run_points
   DevBuf<double> part, head;                     // the scratch of the grid
   DevBuf<unsigned> part_n, cnt, cur, pre, tot, list;
@@ -575,22 +572,6 @@ struct TsdfDistance {
   KernelTimer<kDistKinds> timer;
 
   enum Status { kOk = 0, kNoValid = 1, kTooMany = 2 };
-
-  // New rows beside the old ones, which they replace only when both exist.
-  hipError_t set_mesh(const double* xyz, const unsigned* faces, size_t nv, size_t nt) {
-    hipError_t e;
-    DevBuf<double> x;
-    DevBuf<unsigned> f;
-    if ((e = x.reserve(std::max(nv * 3, m_xyz.capacity()))) != hipSuccess || (e = f.reserve(std::max(nt * 3, m_faces.capacity()))) != hipSuccess) {
-      (void)hipGetLastError();
-      return e;
-    }
-    if ((e = hipMemcpy(x, xyz, nv * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = hipMemcpy(f, faces, nt * 3 * sizeof(unsigned), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    m_xyz = std::move(x); m_faces = std::move(f);
-    m_vert = nv; m_tri = nt; m_set = true;
-    return hipSuccess;
-  }
 
   // The host's points into q_xyz: scratch, not part of the result.
   hipError_t set_points(const double* xyz, size_t n) {
@@ -611,12 +592,12 @@ struct TsdfDistance {
 
   // box -> grid -> (read back) -> count -> offsets -> scan -> (read back) -> fill -> query.  The previous result stays
   // readable until the new outputs exist and the fill begins: the scratch is no part of it.
-  hipError_t run(const double* xyz, const unsigned* faces, unsigned long long nt, const double* pts, unsigned long long np, Status* status) {
+  hipError_t run(const MeshView& t, const double* pts, unsigned long long np, Status* status) {
     hipError_t e;
     *status = kOk;
     if ((e = timer.create()) != hipSuccess) return e;
     DistArgs a{};
-    a.xyz = xyz; a.faces = faces; a.n_tri = (unsigned)nt; a.tblk = fusion_blocks(nt);
+    a.xyz = t.xyz; a.faces = t.faces; a.n_tri = (unsigned)t.n_tri; a.tblk = fusion_blocks(t.n_tri);
     a.pts = pts; a.n_pts = (unsigned)np; a.pblk = fusion_blocks(np);
     if ((e = scratch(part, (size_t)a.tblk * 6)) != hipSuccess || (e = scratch(part_n, a.tblk)) != hipSuccess || (e = scratch(head, 7)) != hipSuccess)
       return e;

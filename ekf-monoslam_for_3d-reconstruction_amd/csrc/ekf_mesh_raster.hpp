@@ -304,15 +304,6 @@ __global__ void __launch_bounds__(256) k_rast_resolve(RastArgs a) {
 }
 
 #ifndef EKF_KERNELS_ONLY
-// The arrays a render reads of its source: a MeshView's, or those of the mesh the caller gave.
-struct RastMesh {
-  const double* xyz = nullptr;
-  const unsigned* faces = nullptr;
-  const unsigned char* grey = nullptr;
-  const unsigned char* bgr = nullptr;            // NULL: the source has no B, G, R
-  unsigned long long n_vert = 0, n_tri = 0;
-};
-
 // The atlas a render with shading 1 samples: TsdfTexture's, only read.
 struct RastAtlas {
   const unsigned char* atlas = nullptr;
@@ -328,47 +319,15 @@ struct TsdfRaster {
   DevBuf<unsigned char> grey, bgr, usable;
   DevBuf<unsigned> cover, list, cursor;
   DevBuf<double> proj;
-  DevBuf<double> m_xyz;                          // source 4: the mesh ekf_raster_set_mesh was given
-  DevBuf<unsigned> m_faces;
-  DevBuf<unsigned char> m_grey, m_bgr;
-  unsigned long long m_vert = 0, m_tri = 0;
-  bool m_set = false, m_colour = false;
+  CallerMesh own;                                // source 4: the mesh ekf_raster_set_mesh was given
   int W = 0, H = 0;
   bool valid = false, has_bgr = false, has_cover = false;      // of the last render
   unsigned small_limit = kRastSmallLimit;
   KernelTimer<kRastKinds> timer;
 
-  // New rows beside the old ones, which they replace only when all of them exist.
-  hipError_t set_mesh(const double* xyz, const unsigned* faces, const unsigned char* g, const unsigned char* c, size_t nv, size_t nt) {
-    hipError_t e;
-    DevBuf<double> x;
-    DevBuf<unsigned> f;
-    DevBuf<unsigned char> gr, co;
-    if ((e = x.reserve(std::max(nv * 3, m_xyz.capacity()))) != hipSuccess || (e = f.reserve(std::max(nt * 3, m_faces.capacity()))) != hipSuccess ||
-        (e = gr.reserve(std::max(nv, m_grey.capacity()))) != hipSuccess || (c && (e = co.reserve(std::max(nv * 3, m_bgr.capacity()))) != hipSuccess)) {
-      (void)hipGetLastError();
-      return e;
-    }
-    if ((e = hipMemcpy(x, xyz, nv * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = hipMemcpy(f, faces, nt * 3 * sizeof(unsigned), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = hipMemcpy(gr, g, nv, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if (c && (e = hipMemcpy(co, c, nv * 3, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    m_xyz = std::move(x); m_faces = std::move(f); m_grey = std::move(gr);
-    if (c) m_bgr = std::move(co);
-    m_vert = nv; m_tri = nt; m_colour = c != nullptr; m_set = true;
-    return hipSuccess;
-  }
-
-  RastMesh own_mesh() const {
-    RastMesh m;
-    m.xyz = m_xyz; m.faces = m_faces; m.grey = m_grey; m.bgr = m_colour ? (const unsigned char*)m_bgr : nullptr;
-    m.n_vert = m_vert; m.n_tri = m_tri;
-    return m;
-  }
-
   // grow -> memsets -> project -> small -> (large) -> resolve.  A failed allocation leaves the previous images as they were:
   // new buffers replace the old ones only when all of them exist.
-  hipError_t render(const RastMesh& s, const RastAtlas* tex, int width, int height, const double K[4], const double R[9], const double t[3],
+  hipError_t render(const MeshView& s, const RastAtlas* tex, int width, int height, const double K[4], const double R[9], const double t[3],
                     double z_near, int cull, int want_cover) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;

@@ -393,27 +393,16 @@ struct TsdfSimplify {
   DevBuf<unsigned> vcell, mem, cells, tl, T, blk_tot, map;
   DevBuf<unsigned long long> pair, off;
   DevMeshBufs out;                               // the simplified mesh
-  MeshView src;                                  // the mesh the result was made from: only what TsdfSmooth::same compares is used
-  int from = 0;                                  // the run's source: 0 the weld, 1 the pruned, 2 the smoothed mesh
-  unsigned long long smooth_run = 0;             // TsdfSmooth::runs at a run from source 2
   unsigned long long n_src_vert = 0, n_degenerate = 0, n_duplicate = 0;
-  unsigned long long runs = 0;                   // counts the runs: what ekf_mesh_texture.hpp derives from a result names it
-  bool valid = false;
   KernelTimer<kSimpKinds> timer;
-
-  // whether the result was made from source `f`, whose view is `s` now (and, for 2, from the smooth run numbered `run`)
-  bool have_result(int f, const MeshView& s, unsigned long long run) const {
-    return valid && from == f && TsdfSmooth::same(src, s) && (f != 2 || smooth_run == run);
-  }
 
   // memset -> cells -> count -> offsets -> two scans -> fill -> lists -> flags -> three scans -> one read-back of the three
   // totals -> (grow the result's buffers) -> map -> vertices -> faces.  A failed allocation leaves every source as it was (they
   // are only read) and the handle without a result.
-  hipError_t run(const MeshView& s, int f, unsigned long long run_id, const TsdfGrid& g, double cell, bool colour) {
+  hipError_t run(MeshStamps& st, const MeshView& s, int source, const TsdfGrid& g, double cell, bool colour) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
-    valid = false;
-    ++runs;
+    st.begin(st.simp);
     unsigned long long totals[3] = {0, 0, 0};
     if (s.n_tri > 0) {
       if (s.n_tri > 0xffffffffull) return hipErrorInvalidValue;              // a triangle's number is a word of `tl`
@@ -477,10 +466,7 @@ struct TsdfSimplify {
     n_degenerate = totals[2];
     n_duplicate = s.n_tri - totals[1] - totals[2];
     n_src_vert = s.n_tri > 0 ? s.n_vert : 0;
-    src = s;
-    from = f;
-    smooth_run = run_id;
-    valid = true;
+    st.made(st.simp, s.id, source);
     return hipSuccess;
   }
 };

@@ -227,20 +227,13 @@ struct TsdfSmooth {
   DevBuf<unsigned long long> off;
   DevBuf<double> pos[2];
   DevBuf<float> normal;
-  MeshView adj, res;                  // the mesh the adjacency and the result were made from: only what `same` compares is used
-  bool adj_valid = false, res_valid = false, has_normals = false;
+  bool has_normals = false;
   int last = 0;                       // the buffer that holds the result
-  unsigned long long runs = 0;        // counts the runs: what ekf_mesh_simplify.hpp derives from a result names it
   KernelTimer<kSmoothKinds> timer;
 
-  static bool same(const MeshView& a, const MeshView& b) {
-    return a.source == b.source && a.serial == b.serial && a.prune == b.prune;
-  }
-  bool have_adjacency(const MeshView& s) const { return adj_valid && same(adj, s); }
-  bool have_result(const MeshView& s) const { return res_valid && same(res, s); }
-  // the last run's mesh: its source `s` with the positions and the normals of the run
-  MeshView result(const MeshView& s) const {
-    MeshView r = s;
+  // the last run's mesh, named `id`: the rows of its source with the positions and the normals of the run
+  MeshView result(const DevMeshBufs& src, unsigned long long id) const {
+    MeshView r = MeshView::of(src, id);
     r.xyz = pos[last];
     r.normal = normal;
     r.has_normals = has_normals;
@@ -256,9 +249,9 @@ struct TsdfSmooth {
   }
 
   // memset -> count -> offsets -> scan -> fill -> lists.  No read-back: the lists' total is 3 n_tri.
-  hipError_t adjacency(const MeshView& s) {
+  hipError_t adjacency(MeshStamps& st, const MeshView& s, int source) {
     hipError_t e;
-    adj_valid = false;
+    st.adj.valid = false;
     const size_t nv = (size_t)s.n_vert, nt = (size_t)s.n_tri;
     const unsigned vblk = fusion_blocks(s.n_vert), tblk = fusion_blocks(s.n_tri);
     if (s.n_tri > 0xffffffffull) return hipErrorInvalidValue;                // a triangle's number is a word of `tri`
@@ -278,18 +271,16 @@ struct TsdfSmooth {
     if ((e = timer.run(2, [&] { k_tsdf_scan<<<1, kFusionBlock, 0, nullptr>>>(tot, o, vblk); })) != hipSuccess) return e;
     if ((e = timer.run(3, [&] { k_smooth_fill<<<tblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
     if ((e = timer.run(4, [&] { k_smooth_lists<<<vblk, kFusionBlock, 0, nullptr>>>(a); })) != hipSuccess) return e;
-    adj = s;
-    adj_valid = true;
+    st.made(st.adj, s.id, source);
     return hipSuccess;
   }
 
   // (the adjacency, unless the handle holds it for this mesh) -> the steps, from the source into pos[0], then between pos[0]
   // and pos[1] -> (normals).  Every buffer is there before the first step; nothing is read back.
-  hipError_t run(const MeshView& s, int iterations, double lambda, double mu, bool pin, bool normals) {
+  hipError_t run(MeshStamps& st, const MeshView& s, int source, int iterations, double lambda, double mu, bool pin, bool normals) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
-    res_valid = false;
-    ++runs;
+    st.begin(st.smooth);
     if (s.n_tri > 0) {
       const size_t nv = (size_t)s.n_vert;
       const unsigned vblk = fusion_blocks(s.n_vert);
@@ -299,7 +290,7 @@ struct TsdfSmooth {
         (void)hipGetLastError();
         return e;
       }
-      if (!have_adjacency(s) && (e = adjacency(s)) != hipSuccess) return e;
+      if (!st.adj.made_from(s.id) && (e = adjacency(st, s, source)) != hipSuccess) return e;
       SmoothArgs a = args(s);
       a.pin = pin ? 1 : 0;
       for (int k = 0; k < steps; ++k) {
@@ -316,8 +307,7 @@ struct TsdfSmooth {
       }
     }
     has_normals = normals;
-    res = s;
-    res_valid = true;
+    st.made(st.smooth, s.id, source);
     return hipSuccess;
   }
 };

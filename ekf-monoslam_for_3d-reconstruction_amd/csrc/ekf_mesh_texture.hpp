@@ -265,13 +265,11 @@ struct TsdfTexture {
   DevBuf<double> best_score, sxy;
   DevBuf<int> best_view;
   DevBuf<unsigned> counts;
-  MeshView src;                                  // the mesh begin was given: only what TsdfSmooth::same compares, and the arrays
-  int from = 0;                                  // 0 the weld, 1 the pruned, 2 the smoothed, 3 the simplified mesh
-  unsigned long long run_id = 0;                 // TsdfSmooth::runs (2) or TsdfSimplify::runs (3) at begin
+  MeshView src;                                  // the mesh begin was given: its arrays, read while the texture is current
   int P = 0, B = 0, C = 0;
   long long Q = 0, A = 0;
   bool colour = false;                           // the fallback reads the source's B, G, R
-  bool begun = false, finished = false;
+  bool finished = false;
   int views = 0;
   unsigned long long n_textured = 0;
   KernelTimer<kTexKinds> timer;
@@ -280,7 +278,7 @@ struct TsdfTexture {
   // before as it was.  Then everything is cleared; the buffers may be that texture's own, so from the first clear on the handle
   // has no texture until all four clears are queued.  (d_img, the staging image of a view from the host, grows by itself: a
   // failed reserve loses only that image and adds no view.)
-  hipError_t begin(const MeshView& s, int f, unsigned long long run, int patch, int channels, bool use_bgr) {
+  hipError_t begin(MeshStamps& st, const MeshView& s, int source, int patch, int channels, bool use_bgr) {
     hipError_t e;
     if ((e = timer.create()) != hipSuccess) return e;
     int b;
@@ -302,16 +300,16 @@ struct TsdfTexture {
       atlas = std::move(n_atlas); won = std::move(n_won); vis = std::move(n_vis); best_score = std::move(n_score);
       sxy = std::move(n_sxy); best_view = std::move(n_view); counts = std::move(n_counts);
     }
-    begun = false;
+    st.tex.valid = false;
     if ((e = hipMemsetAsync(atlas, 0, na, nullptr)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(best_score, 0, nt * sizeof(double), nullptr)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(best_view, 0xff, nt * sizeof(int), nullptr)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(won, 0, nt, nullptr)) != hipSuccess) return e;
-    src = s; from = f; run_id = run;
+    src = s;
     P = patch; B = b; Q = q; A = side; C = channels; colour = use_bgr;
     views = 0; n_textured = 0;
     finished = false;
-    begun = true;
+    st.made(st.tex, s.id, source);
     return hipSuccess;
   }
 
